@@ -24,6 +24,12 @@ comm thread calls back into torch.distributed (RCCL point-to-point), one transfe
 `--local-devices N`: ONE process drives N logical devices instead (device DPB with event-ordered hipMemcpyPeerAsync), the
 reference's --framethr model.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times exactly N steps and prints the line (`value`,
+`ms_per_step` = milliseconds per timed step).  `--full` adds everything beside the headline: the launch-group survey and the
+roofline, the isolated survey, the variants, the other dealing, the check against the oracle, the reference's own stream, the live
+decoder and the CPU baseline.  `--dump-outputs DIR` writes what the timed path computed in its last step (same arguments, same
+inputs: two builds compare output for output).
+
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 import argparse
@@ -42,6 +48,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 HBM_PEAK_GBPS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MV_ROWS = 1 << 20       # --dump-outputs: refined-vector rows kept (5 float32 each: 20 MB at most)
 
 KNAME = {"mc": "k_mc2", "mcxa": "k_mcxa", "itx_luma": "k_itx_all (luma commands)", "lmcs_scale": "k_lmcs_scale",
          "itx_chroma": "k_itx_all (chroma commands + inverse-LMCS rider)", "dbf": "k_dbf_list<0> + k_dbf_list<1>",
@@ -155,6 +162,17 @@ def main():
     ap.add_argument("--ipic-workers", type=int, default=0, help="persistent workers of an I picture's ordered pass (0: the library's default, 4 x compute units)")
     ap.add_argument("--bpic-workers", type=int, default=0, help="persistent workers of a B picture's ordered pass (0: the library's default)")
     ap.add_argument("--ahead-own-queue", type=int, default=1, help="1: the look-ahead thread's stream gets a hardware queue no in-order thread's stream shares (probed at start)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the launch-group survey and roofline, the isolated survey, "
+                         "the variants, the other dealing, --check against the oracle, the reference's stream and the live decoder, the CPU baseline "
+                         "(the --no-* options and --check above act only with --full).  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps: what the timed path computed in its LAST step, as DIR/<name>.npy (float32): digests.npy = the "
+                         "per-picture fingerprints in decoding order [pictures, 16]; refined_mvs.npy = the DMVR-refined vectors the pictures' jobs "
+                         "returned, rows (picture's position in the step, mv0 x, y, mv1 x, y), a fixed sample when there are more than "
+                         f"{DUMP_MV_ROWS} rows.  With --output none / frame the fingerprints are taken inside the timed region (the frame threads "
+                         "compute them); with the default --output digest they are what the output thread receives anyway.  One process only")
     args = ap.parse_args()
 
     import torch
@@ -172,6 +190,8 @@ def main():
         args.local_devices = args.gpus
     if world > 1 and args.gpus not in (1, world):
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    if world > 1 and args.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of one process: run it without torch.distributed.run")
     if world == 1 and args.local_devices > 1 and not args.same_gpu and torch.cuda.device_count() < args.local_devices:
         raise SystemExit(f"bench.py: {args.local_devices} devices asked for, {torch.cuda.device_count()} visible (--same-gpu puts the logical devices on GPU 0)")
     # OVVC_BENCH_DEBUG_GLOO=1 (development only): all ranks on GPU 0, pictures exchanged through host memory over gloo -- runs
@@ -196,7 +216,7 @@ def main():
     hip_devices = [local_rank if (args.same_gpu or world > 1) else k for k in range(L)] if L > 1 else [local_rank]
 
     tools = synth.INTRA_TOOLS if args.intra_frac > 0 else synth.ALL_TOOLS
-    want_log = not args.no_isolated_survey
+    want_log = args.full and not args.no_isolated_survey          # (the call logs feed the recorded_in_run variant only)
     wls = [synth.make_workload(W, H, args.seed + 1000 * c + rank, tools=tools, intra_frac=args.intra_frac, calllog=want_log)
            for c in range(max(1, args.contents))]
     n_b = len(wls)
@@ -402,37 +422,39 @@ def main():
         present.remove("lmcs_scale")
     if not any(w.itasks is not None and len(w.itasks) for w in wls):
         present.remove("intra")
-    survey = {}
-    for name in present:
-        set_timer(name)
-        count(run_local(st_main, 2 * PPS)[0])
-        survey[name] = read_timer()
-    kern = {k: v for k, v in survey.items() if k != "h2d"}
-    # the roofline's subject = the launch group with the largest stream time, whatever it is (r2 left the ordered pass out)
-    dom = max(kern, key=kern.get)
-    stream_dom = max((k for k in kern if k != "intra"), key=kern.get)
-    isolated = {}
-    ipic_isolated_s = None
-    variants = {}
-    if not args.no_isolated_survey:
-        # the same groups with ONE picture in flight: what a launch takes when it has the device to itself
-        st_one = new_stream(1)
+    survey, kern, dom, stream_dom, isolated, ipic_isolated_s, variants = {}, {}, None, None, {}, None, {}
+    if args.full:
         for name in present:
-            if name == "h2d":
-                continue
             set_timer(name)
-            r1, _ = st_one.run(larr, NL, 0, 1 + 2 * G, flags=0)
-            isolated[name] = read_timer()
-            if name == "intra":
-                ipic_isolated_s = last_ipic_time[0]
-        set_timer(None)
-        st_one.close()
-    if world > 1:
-        pick = torch.tensor([present.index(dom)], dtype=torch.int64, device=None if debug_gloo else dev)
-        dist.broadcast(pick, 0)
-        dom = present[int(pick.item())]
+            count(run_local(st_main, 2 * PPS)[0])
+            survey[name] = read_timer()
+        kern = {k: v for k, v in survey.items() if k != "h2d"}
+        # the roofline's subject = the launch group with the largest stream time, whatever it is (r2 left the ordered pass out)
+        dom = max(kern, key=kern.get)
+        stream_dom = max((k for k in kern if k != "intra"), key=kern.get)
+        if not args.no_isolated_survey:
+            # the same groups with ONE picture in flight: what a launch takes when it has the device to itself
+            st_one = new_stream(1)
+            for name in present:
+                if name == "h2d":
+                    continue
+                set_timer(name)
+                r1, _ = st_one.run(larr, NL, 0, 1 + 2 * G, flags=0)
+                isolated[name] = read_timer()
+                if name == "intra":
+                    ipic_isolated_s = last_ipic_time[0]
+            set_timer(None)
+            st_one.close()
+        if world > 1:
+            pick = torch.tensor([present.index(dom)], dtype=torch.int64, device=None if debug_gloo else dev)
+            dist.broadcast(pick, 0)
+            dom = present[int(pick.item())]
 
-    # ---- timed region: EXACTLY --steps steps, one library call, only the dominant launch group bracketed ----
+    # ---- timed region: EXACTLY --steps steps, one library call, only the dominant launch group bracketed.  Without --full (no survey)
+    # the group the survey picks on this stream is bracketed: the ordered pass.  The bracket is part of the timed configuration: a job
+    # with a bracketed group uploads on its picture's own stream, not on the shared upload streams (ovvc_picture.hip: upload_stream_for)
+    if dom is None:
+        dom = "intra" if "intra" in present else present[0]
     set_timer(dom)
     strong = world > 1 and args.scaling == "strong"
     if world > 1:
@@ -487,7 +509,8 @@ def main():
         barrier()
         t0 = time.perf_counter()
         trace = np.zeros((args.steps * PPS * L, 8))
-        res, _ = st_t.run(tarr, NT, n_warm, args.steps * PPS * L, flags=capi.STREAM_KEEP | (capi.STREAM_RESIDENT if args.debug_resident else 0), trace=trace, digests=args.debug_digests_only)
+        res, dg = st_t.run(tarr, NT, n_warm, args.steps * PPS * L, flags=capi.STREAM_KEEP | (capi.STREAM_RESIDENT if args.debug_resident else 0), trace=trace,
+                           digests=args.debug_digests_only or bool(args.dump_outputs))
         barrier()
         dt = time.perf_counter() - t0
         if args.trace:
@@ -503,9 +526,11 @@ def main():
             cur[0] += args.steps * PPS * L
         n_timed_rank = n_timed_all = args.steps * PPS * L
         assert int(res.n_decoded) == n_timed_rank
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dg[-PPS * L:], tspics[n_warm + (args.steps - 1) * PPS * L:n_warm + args.steps * PPS * L], jobs)
         xfers = [0, 0]
         count(res)
-    dom_avg = read_timer()
+    dom_avg = read_timer() if args.full else None
     set_timer(None)
     q_moved, q_sharing = st_t.queue_info()
     ms_per_step = dt * 1e3 / args.steps
@@ -524,7 +549,7 @@ def main():
     # (one process per GPU: only on request or with --scaling strong -- the driver's weak-scaling runs are the first execution of the
     #  RCCL exchange on real devices, and the picture-interleaved dealing sends a picture per picture: the headline run is not put at
     #  the mercy of a second, much heavier exchange)
-    if L > 1 or (world > 1 and (args.both_dealings or args.scaling == "strong")):
+    if args.full and (L > 1 or (world > 1 and (args.both_dealings or args.scaling == "strong"))):
         od = "picture" if args.dealing == "gop" else "gop"
         ndev = world if world > 1 else L
         og_warm, og = (IP // G) * ndev, 2 * (IP // G) * ndev
@@ -546,7 +571,7 @@ def main():
                          "pictures_sent_by_this_rank": int(ores.n_sent), "peer_copies": int(dpb.stats().n_copies) - int(dpb_stats.n_copies)}
         count(ores)
         st_o.close()
-    if world > 1:
+    if world > 1 and args.full:
         st_main = new_stream(S)
         cur[0] = 0
         lpics, lspics = build(n_loc_gops, 1, args.dealing, 1)
@@ -569,7 +594,7 @@ def main():
         return n_pics / (time.perf_counter() - t0), r
 
     fps_res = None
-    if rank == 0 and not args.no_isolated_survey:
+    if rank == 0 and args.full and not args.no_isolated_survey:
         nv = 4 * PPS
         for mode in ("none", "digest", "frame"):
             if mode == args.output and world == 1:
@@ -607,7 +632,7 @@ def main():
 
     # ---- check: the device against the oracle on the first pictures of the stream; in flight vs one at a time on two GOPs ----
     check = None
-    if args.check > 0 and rank == 0:
+    if args.full and args.check > 0 and rank == 0:
         sys.path.insert(0, str(ROOT / "oracle"))
         import oracle_pipeline
         import ovvc_oracle_output as oo
@@ -648,84 +673,86 @@ def main():
     # the other ranks would sit idle behind rank 0 for minutes, and the figures would be the N = 1 run's again
     one_gpu = world == 1 and L == 1
     ref_stream = None
-    if rank == 0 and one_gpu and not args.no_reference_stream and (W, H) == (3840, 2160):
+    if rank == 0 and args.full and one_gpu and not args.no_reference_stream and (W, H) == (3840, 2160):
         ref_stream = reference_stream_on_device(engine, capi, ctx0, W, H, 17, 8)
         if ref_stream and (ref_stream["samples_differing_from_the_reference"] or ref_stream["refined_vectors_differing"]):
             raise SystemExit(f"bench: the reference's stream decodes differently on the device: {ref_stream}")
 
     live = None
-    if rank == 0 and one_gpu and not args.no_reference_stream and not args.no_live_decoder and (W, H) == (3840, 2160):
+    if rank == 0 and args.full and one_gpu and not args.no_reference_stream and not args.no_live_decoder and (W, H) == (3840, 2160):
         live = live_decoder_rates(W, H)
         if live and not live["bit_exact"]:
             raise SystemExit(f"bench: the live decode differs from the reference pass: {live}")
 
     if rank == 0:
-        algs = [algorithmic_bytes(wl, FB) for wl in wls]
-        use = np.zeros(len(wls))
-        for p in lspics[1:1 + 4 * PPS]:
-            use[p["content"]] += 1
-        use /= use.sum()
-        alg = {k: float(sum(u * a[k] for u, a in zip(use, algs))) for k in algs[0]}
-        alg = {k: v for k, v in alg.items() if k in kern}
-        tj = None
-        try:
-            tj = json.loads((ROOT / "profiles" / "traffic.json").read_text())
-            if tj["workload"] != {"width": W, "height": H, "seed": args.seed}:
-                tj = None
-        except (OSError, KeyError, ValueError):
+        roofline, alg = None, None
+        if args.full:
+            algs = [algorithmic_bytes(wl, FB) for wl in wls]
+            use = np.zeros(len(wls))
+            for p in lspics[1:1 + 4 * PPS]:
+                use[p["content"]] += 1
+            use /= use.sum()
+            alg = {k: float(sum(u * a[k] for u, a in zip(use, algs))) for k in algs[0]}
+            alg = {k: v for k, v in alg.items() if k in kern}
             tj = None
-
-        def traffic_of(name):
-            """(HBM bytes per launch group from the committed PMC passes, rocprofv3 kernel-trace average us) or (None, None)"""
-            if tj is None:
-                return None, None
             try:
-                names = [n.strip() for n in KNAME[name].split("(")[0].split("+")]
-                ks = [tj["kernels"][n] for n in names]
-                per_pic = 1.0
-                if name == "intra":
-                    # the ordered pass: the counters are per dispatch, a picture has several (flow chunks); averaged over the stream
-                    per_pic = ks[0]["dispatches"] / max(1, tj["kernels"]["k_alf"]["dispatches"])
-                t = int(sum(2 * k["fetch_kib"] + k["write_kib"] for k in ks) * 1024 * per_pic)
-                avg = round(sum(k["trace_avg_us"] for k in ks) * per_pic, 2) if all("trace_avg_us" in k for k in ks) else None
-                return t, avg
-            except (KeyError, ZeroDivisionError):
-                return None, None
+                tj = json.loads((ROOT / "profiles" / "traffic.json").read_text())
+                if tj["workload"] != {"width": W, "height": H, "seed": args.seed}:
+                    tj = None
+            except (OSError, KeyError, ValueError):
+                tj = None
 
-        def roof(name, avg_s):
-            tr, ravg = traffic_of(name)
-            a = alg[name] / avg_s / 1e9
-            d = {"kernel": KNAME[name], "achieved": round(a, 2), "frac": round(a / HBM_PEAK_GBPS, 5), "avg_launch_us": round(avg_s * 1e6, 2),
-                 "traffic": tr, "rocprof_avg_launch_us": ravg,
-                 "frac_at_rocprof_duration": round(alg[name] / ravg / 1e3 / HBM_PEAK_GBPS, 5) if ravg else None,
-                 "frac_isolated": round(alg[name] / isolated[name] / 1e9 / HBM_PEAK_GBPS, 5) if name in isolated and isolated[name] > 0 else None}
-            return d
+            def traffic_of(name):
+                """(HBM bytes per launch group from the committed PMC passes, rocprofv3 kernel-trace average us) or (None, None)"""
+                if tj is None:
+                    return None, None
+                try:
+                    names = [n.strip() for n in KNAME[name].split("(")[0].split("+")]
+                    ks = [tj["kernels"][n] for n in names]
+                    per_pic = 1.0
+                    if name == "intra":
+                        # the ordered pass: the counters are per dispatch, a picture has several (flow chunks); averaged over the stream
+                        per_pic = ks[0]["dispatches"] / max(1, tj["kernels"]["k_alf"]["dispatches"])
+                    t = int(sum(2 * k["fetch_kib"] + k["write_kib"] for k in ks) * 1024 * per_pic)
+                    avg = round(sum(k["trace_avg_us"] for k in ks) * per_pic, 2) if all("trace_avg_us" in k for k in ks) else None
+                    return t, avg
+                except (KeyError, ZeroDivisionError):
+                    return None, None
 
-        rd = roof(dom, dom_avg)
-        roofline = {"bound": "hbm", "kernel": rd["kernel"], "achieved": rd["achieved"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": rd["frac"],
-                    "traffic": rd["traffic"], "avg_launch_us": rd["avg_launch_us"], "rocprof_avg_launch_us": rd["rocprof_avg_launch_us"],
-                    "frac_at_rocprof_duration": rd["frac_at_rocprof_duration"], "frac_isolated": rd["frac_isolated"],
-                    "picked_from": "survey in the timed configuration (same jobs and pictures in flight): the launch group with the largest stream time "
-                                   "per picture, the ordered pass included"
-                                   + ("; it is a dependency chain (levels x latency per level, DESIGN 4.1): per launch = per picture" if dom == "intra" else ""),
-                    "largest_streaming_kernel": roof(stream_dom, kern[stream_dom]) if stream_dom != dom else None,
-                    "survey_launch_us": {k: round(v * 1e6, 2) for k, v in survey.items()},
-                    "frac_per_kernel": {k: round(alg[k] / kern[k] / 1e9 / HBM_PEAK_GBPS, 5) for k in alg if kern[k] > 0},
-                    "isolated_launch_us": {k: round(v * 1e6, 2) for k, v in isolated.items()},
-                    "frac_isolated_per_kernel": {k: round(alg[k] / isolated[k] / 1e9 / HBM_PEAK_GBPS, 5) for k in alg if k in isolated and isolated[k] > 0},
-                    "ordered_pass": ({"levels_per_i_picture": int(wls[-1].stats["n_ilevels"]), "levels_per_b_picture": int(wls[0].stats["n_ilevels"]),
-                                      "us_per_level_i_picture_isolated": round(ipic_isolated_s * 1e6 / max(1, int(wls[-1].stats["n_ilevels"])), 3) if ipic_isolated_s else None,
-                                      "i_picture_pass_isolated_us": round(ipic_isolated_s * 1e6, 1) if ipic_isolated_s else None} if "intra" in kern else None),
-                    "algorithmic_bytes": {k: int(v) for k, v in alg.items()},
-                    "frame_frac": round(sum(alg.values()) * fps / max(world, L) / 1e9 / HBM_PEAK_GBPS, 5),
-                    # SURVEY 8(d) as written: B_frame = (r_bar + 7) S + C, C = coefficients + commands consumed (the sum above also counts
-                    # the read-modify-write of the transform's residual add and the inverse luma mapping's pass)
-                    "frame_bytes_8d": int((float(np.dot(use, [w.stats["r_bar"] for w in wls])) + 7) * FB + float(np.dot(use, [w.stats["coef_bytes"] + 32 * (w.stats["n_tb_cmds"] + w.stats["n_mc_units"] + w.stats["n_mcx_units"] + w.stats["n_aff_units"]) for w in wls]))),
-                    "frame_frac_8d": None}
-        roofline["frame_frac_8d"] = round(roofline["frame_bytes_8d"] * fps / max(world, L) / 1e9 / HBM_PEAK_GBPS, 5)
+            def roof(name, avg_s):
+                tr, ravg = traffic_of(name)
+                a = alg[name] / avg_s / 1e9
+                d = {"kernel": KNAME[name], "achieved": round(a, 2), "frac": round(a / HBM_PEAK_GBPS, 5), "avg_launch_us": round(avg_s * 1e6, 2),
+                     "traffic": tr, "rocprof_avg_launch_us": ravg,
+                     "frac_at_rocprof_duration": round(alg[name] / ravg / 1e3 / HBM_PEAK_GBPS, 5) if ravg else None,
+                     "frac_isolated": round(alg[name] / isolated[name] / 1e9 / HBM_PEAK_GBPS, 5) if name in isolated and isolated[name] > 0 else None}
+                return d
+
+            rd = roof(dom, dom_avg)
+            roofline = {"bound": "hbm", "kernel": rd["kernel"], "achieved": rd["achieved"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": rd["frac"],
+                        "traffic": rd["traffic"], "avg_launch_us": rd["avg_launch_us"], "rocprof_avg_launch_us": rd["rocprof_avg_launch_us"],
+                        "frac_at_rocprof_duration": rd["frac_at_rocprof_duration"], "frac_isolated": rd["frac_isolated"],
+                        "picked_from": "survey in the timed configuration (same jobs and pictures in flight): the launch group with the largest stream time "
+                                       "per picture, the ordered pass included"
+                                       + ("; it is a dependency chain (levels x latency per level, DESIGN 4.1): per launch = per picture" if dom == "intra" else ""),
+                        "largest_streaming_kernel": roof(stream_dom, kern[stream_dom]) if stream_dom != dom else None,
+                        "survey_launch_us": {k: round(v * 1e6, 2) for k, v in survey.items()},
+                        "frac_per_kernel": {k: round(alg[k] / kern[k] / 1e9 / HBM_PEAK_GBPS, 5) for k in alg if kern[k] > 0},
+                        "isolated_launch_us": {k: round(v * 1e6, 2) for k, v in isolated.items()},
+                        "frac_isolated_per_kernel": {k: round(alg[k] / isolated[k] / 1e9 / HBM_PEAK_GBPS, 5) for k in alg if k in isolated and isolated[k] > 0},
+                        "ordered_pass": ({"levels_per_i_picture": int(wls[-1].stats["n_ilevels"]), "levels_per_b_picture": int(wls[0].stats["n_ilevels"]),
+                                          "us_per_level_i_picture_isolated": round(ipic_isolated_s * 1e6 / max(1, int(wls[-1].stats["n_ilevels"])), 3) if ipic_isolated_s else None,
+                                          "i_picture_pass_isolated_us": round(ipic_isolated_s * 1e6, 1) if ipic_isolated_s else None} if "intra" in kern else None),
+                        "algorithmic_bytes": {k: int(v) for k, v in alg.items()},
+                        "frame_frac": round(sum(alg.values()) * fps / max(world, L) / 1e9 / HBM_PEAK_GBPS, 5),
+                        # SURVEY 8(d) as written: B_frame = (r_bar + 7) S + C, C = coefficients + commands consumed (the sum above also counts
+                        # the read-modify-write of the transform's residual add and the inverse luma mapping's pass)
+                        "frame_bytes_8d": int((float(np.dot(use, [w.stats["r_bar"] for w in wls])) + 7) * FB + float(np.dot(use, [w.stats["coef_bytes"] + 32 * (w.stats["n_tb_cmds"] + w.stats["n_mc_units"] + w.stats["n_mcx_units"] + w.stats["n_aff_units"]) for w in wls]))),
+                        "frame_frac_8d": None}
+            roofline["frame_frac_8d"] = round(roofline["frame_bytes_8d"] * fps / max(world, L) / 1e9 / HBM_PEAK_GBPS, 5)
 
         cpu = None
-        if not args.no_cpu_baseline and one_gpu:
+        if args.full and not args.no_cpu_baseline and one_gpu:
             os.sched_setaffinity(0, all_cpus)            # the CPU legs use every core of the host
             import oracle_pipeline
             wl0 = wls[0]
@@ -826,7 +853,7 @@ def main():
                        "n_cu": st["n_cu"], "cu_modes": st["cu_modes"], "n_mc_units": st["n_mc_units"],
                        "n_mcx_units": st["n_mcx_units"], "n_aff_units": st["n_aff_units"], "n_tb_cmds": st["n_tb_cmds"],
                        "r_bar": round(st["r_bar"], 3), "coef_bytes": st["coef_bytes"],
-                       "frame_algorithmic_bytes": int(sum(alg.values())),
+                       "frame_algorithmic_bytes": int(sum(alg.values())) if alg is not None else None,
                        "resident_replay_fps": round(fps_res, 2) if fps_res else None,
                        "ranks": rank_accounts,
                        "exchange_consistent": (None if rank_accounts is None else bool(
@@ -855,6 +882,24 @@ def main():
     if world > 1:
         dist.destroy_process_group()
 
+
+def dump_outputs(d, digests, step_pics, jobs):
+    """--dump-outputs: what the timed path computed in its last step -> d/digests.npy [pictures, 16] and d/refined_mvs.npy [rows, 5]
+    (float32; the values are bytes and 1/16-sample vectors, exact in float32).  A pre-recorded job is in flight once at a time and its
+    pictures take it in decoding order (ovvc_stream.c: frame_thread), so after the run a job holds the refined vectors of the LAST
+    picture that used it: those of every picture of the step whose job no later picture of the step uses."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "digests.npy"), np.asarray(digests, np.float32))
+    last = {p["job"]: k for k, p in enumerate(step_pics)}
+    rows = [np.zeros((0, 5), np.float32)]
+    for k, p in enumerate(step_pics):
+        if last[p["job"]] == k:
+            mv = jobs[p["job"]].refined_mvs().astype(np.float32)
+            rows.append(np.concatenate([np.full((len(mv), 1), k, np.float32), mv], axis=1))
+    mvs = np.concatenate(rows)
+    if len(mvs) > DUMP_MV_ROWS:
+        mvs = mvs[np.sort(np.random.RandomState(0x266).choice(len(mvs), DUMP_MV_ROWS, replace=False))]
+    np.save(os.path.join(d, "refined_mvs.npy"), mvs)
 
 
 GEN_PIPE = ROOT / "oracle" / "_ref" / "gen_pipe"

@@ -46,5 +46,5 @@ def test_bench_and_entry_scripts_parse():
         py_compile.compile(str(root / f), doraise=True)
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--in-flight"):
+    for flag in ("--gpus", "--steps", "--warmup", "--in-flight", "--full", "--dump-outputs"):
         assert flag in out.stdout

@@ -1,7 +1,7 @@
 """GPU: the one-process-per-GPU path of the stream driver (ovhip_stream_xfer callbacks on the C communication thread) executed by two
 ranks -- on ONE GPU, pictures exchanged through host memory over gloo (OVVC_BENCH_DEBUG_GLOO=1: gpurun boxes have one GPU; the RCCL
 leg of the same callbacks first runs on the driver's multi-GPU node).  Both dealings; every rank's pictures are checked against the
-oracle / the one-at-a-time decode by bench.py --check inside the run."""
+oracle / the one-at-a-time decode by bench.py --full --check inside the run."""
 import json
 import os
 import socket
@@ -25,7 +25,7 @@ def _run(dealing):
     env = dict(os.environ, OVVC_BENCH_DEBUG_GLOO="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--width", "832", "--height", "480", "--no-cpu-baseline",
-           "--no-isolated-survey", "--check", "3", "--dealing", dealing, "--both-dealings"]
+           "--no-isolated-survey", "--check", "3", "--dealing", dealing, "--both-dealings", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -59,7 +59,7 @@ def test_gpus_flag_without_torchrun_drives_that_many_devices(built_lib):
     copies through the device DPB) -- here both on GPU 0 (--same-gpu) -- and says n_gpus: 2; with more devices than visible it refuses."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--same-gpu", "--steps", "1", "--warmup", "1", "--width", "832", "--height", "480",
-           "--no-cpu-baseline", "--no-isolated-survey", "--check", "3"]
+           "--no-cpu-baseline", "--no-isolated-survey", "--check", "3", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

@@ -31,7 +31,7 @@ done
 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_ref -o ${tag} -- python $R/tools/ref_stream_trace.py > $O/${tag}_ref.log 2>&1
 db=$(find $O/prof_${tag}_ref -name "*_results.db" | head -1)
 [ -n "$db" ] && python $R/tools/rocprof_summary.py $db > $O/${tag}_reference_stream_kernel_trace.txt 2>&1
-python $R/bench.py --steps 20 --warmup 5 > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+python $R/bench.py --steps 20 --warmup 5 --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 # the names the summaries are committed under (profiles/)
 mv $O/${tag}_trace.txt $O/${tag}_full_pipeline_kernel_trace.txt
 mv $O/${tag}_f.txt $O/${tag}_pmc_fetch.txt
