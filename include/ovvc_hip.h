@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define OVHIP_ABI_VERSION 8
+#define OVHIP_ABI_VERSION 9
 
 /* ---- error codes (negative, in the spirit of libovvc/overror.h:40-45) ---- */
 #define OVHIP_OK        0
@@ -187,6 +187,58 @@ typedef struct ovhip_aff_unit {
     uint32_t prof_off;        /* int32 index of the CU's PROFInfo in the side arena              */
     uint32_t pad[2];
 } ovhip_aff_unit;
+
+/* ------------------------------------------------------------------------------------
+ * Reference picture resampling (RPR): prediction from a reference of another size.  The reference
+ * keeps one scale factor per (picture, reference) pair and axis, ((ref_w << 14) + cur_w / 2) / cur_w
+ * over the scaling windows (ctudec_compute_refs_scaling, ctudec.c:43-86); 1 << 14 on both axes is
+ * "unscaled".  A unit that reads at least one scaled list is an ovhip_rpr_unit instead of an
+ * ovhip_mc_unit: a tile of at most 16x16 luma samples of one PU (+ its 4:2:0 chroma) that carries,
+ * per list, the PU's anchor AFTER clip_rpr_position and the tile's offset inside the PU, because
+ * per-column positions (anchor + ((col * step) << 4) + 8192) >> 14 use the ROUNDED step
+ * ((scale + 8) >> 4) << 4 and cannot be re-derived from the tile's own position
+ * (rcn_mcp_rpr_l / _bi_l / _c / _bi_c, rcn_inter.c:2009-2512; combined as rcn_mc_rpr_b_l / _c, :2522-2736).
+ * 64 bytes.
+ * ---------------------------------------------------------------------------------- */
+#define OVHIP_RPR_UNSCALED (1 << 14)
+typedef struct ovhip_ref_scale {
+    int32_t scale_hor, scale_ver;   /* scale_fact_rpl*[ref_idx][0 / 1]: 2048 (1/8) .. 32768 (2)                      */
+    int32_t ref_w, ref_h;           /* the reference's luma size (frame->width / height)                              */
+    uint8_t chroma_hor_col_flag;    /* sps_chroma_horizontal_collocated_flag (scale_info.chroma_hor_col_flag)         */
+    uint8_t chroma_ver_col_flag;    /* sps_chroma_vertical_collocated_flag                                            */
+    uint8_t pad[2];
+} ovhip_ref_scale;
+
+enum {                        /* ovhip_rpr_unit.flags */
+    OVHIP_RPR_S0        = 1,  /* list 0 is scaled (else: regular 14-bit interpolation, rcn_mcp_bidir0_l / _c)     */
+    OVHIP_RPR_S1        = 2,  /* list 1 is scaled                                                                  */
+    OVHIP_RPR_NO_LUMA   = 4,  /* = OVHIP_MC_NO_LUMA                                                                */
+    OVHIP_RPR_NO_CHROMA = 8,  /* = OVHIP_MC_NO_CHROMA                                                              */
+    OVHIP_RPR_LMCS      = 16, /* = OVHIP_MC_LMCS                                                                   */
+    OVHIP_RPR_HPEL_FILT = 32, /* unscaled side: = OVHIP_MC_HPEL_FILT                                               */
+    OVHIP_RPR_GPM       = 128 /* = OVHIP_MC_GPM, aux as there                                                      */
+};
+
+typedef struct ovhip_rpr_side {
+    int32_t pos_x, pos_y;     /* scaled: clipped luma anchor ref_pos (1/2^18 sample); unscaled: clip_mv()'d MV (1/16) */
+    int32_t cpos_x, cpos_y;   /* scaled: clipped chroma anchor (1/2^19 chroma sample); unscaled: 0                    */
+    uint16_t step_x, step_y;  /* scaled: ((scale + 8) >> 4) << 4; unscaled: 0                                        */
+    uint8_t  filt;            /* scaled: luma filter set, horizontal | vertical << 4 (compute_rpr_filter_idx, 0..5)  */
+    uint8_t  filt_c;          /* scaled: chroma filter set, horizontal | vertical << 4 (0..2)                        */
+    uint8_t  ref;             /* slot in the launch's reference table                                              */
+    uint8_t  pad;
+} ovhip_rpr_side;
+
+typedef struct ovhip_rpr_unit {
+    uint16_t x, y;            /* luma position of the tile in the picture                                          */
+    uint8_t  w, h;            /* luma size, 4..16                                                                  */
+    uint8_t  ox, oy;          /* the tile's offset inside its PU (luma; chroma ox / 2, oy / 2)                     */
+    uint8_t  dir;             /* 1, 2, 3 as in ovhip_mc_unit                                                       */
+    uint8_t  flags;           /* OVHIP_RPR_*                                                                       */
+    int8_t   w0, w1;          /* bi weights as in ovhip_mc_unit                                                    */
+    uint32_t aux;             /* as ovhip_mc_unit.aux (GPM weight plane or CIIP blend)                             */
+    ovhip_rpr_side s[2];
+} ovhip_rpr_unit;
 
 /* ------------------------------------------------------------------------------------
  * CIIP blend unit: dst = (intra * wt + inter * (4 - wt) + 2) >> 2 over one CU, luma and chroma
@@ -608,6 +660,14 @@ int   ovhip_rec_affine_cu(ovhip_recorder *rec, const ovhip_affine_desc *cu);
  * exactly one of pu (rcn_mcp_b; with refine flags the whole BDOF / DMVR coding unit, cut here as vcl_coding_unit.c:2450-2472 / :2598-2668
  * cut it; GPM) and aff (an affine coding unit) is non-NULL.  Returns what ovhip_rec_pu / ovhip_rec_affine_cu return. */
 int   ovhip_rec_cu_inter(ovhip_recorder *rec, const ovhip_pu_desc *pu, const ovhip_affine_desc *aff);
+/* Reference picture resampling: the scale of reference-table slot `slot` (0..255) for the picture being recorded; NULL
+ * restores the default (unscaled, what every slot is after ovhip_rec_create / ovhip_rec_reset).  ovhip_rec_pu and
+ * ovhip_rec_cu_inter then emit ovhip_rpr_unit for PUs that read a scaled slot.  Still refused with OVHIP_EUNSUP (the
+ * reason in ovhip_rec_refusal): DMVR / BDOF with a scaled reference, affine CUs with a scaled reference, 4x4 PUs with a
+ * scaled reference, a slot whose scale is 1 but whose size differs from the picture's.  Returns 0 or <0. */
+int   ovhip_rec_set_ref_scale(ovhip_recorder *rec, int32_t slot, const ovhip_ref_scale *scale);
+/* Why the last OVHIP_EUNSUP of this recorder was returned ("" when none since create / reset). */
+const char *ovhip_rec_refusal(const ovhip_recorder *rec);
 /* rcn_ciip_weighted_sum: mode_abv / mode_lft = part_map.cu_mode_x[x_right >> log2_min_cb] /
  * cu_mode_y[y_bottom >> log2_min_cb] as enum CUMode (cu_utils.h:132-139). */
 int   ovhip_rec_ciip(ovhip_recorder *rec, int32_t x0, int32_t y0, int32_t log2_w, int32_t log2_h,
@@ -659,7 +719,7 @@ int   ovhip_rec_dbf_mv_prepass_view(const ovhip_dbf_view *ctu, uint64_t *bs1_ver
 int   ovhip_rec_dbf_planes(const ovhip_recorder *rec, ovhip_dbf_planes *out);
 /* Bulk append of already-recorded commands to an EMPTY recorder (replay of a stored command stream). */
 enum { OVHIP_REC_TB = 0, OVHIP_REC_COEF, OVHIP_REC_MC, OVHIP_REC_MCX, OVHIP_REC_AFF, OVHIP_REC_SIDE, OVHIP_REC_REGION,
-       OVHIP_REC_CIIP, OVHIP_REC_EDGE_V, OVHIP_REC_EDGE_H, OVHIP_REC_ITASK };
+       OVHIP_REC_CIIP, OVHIP_REC_EDGE_V, OVHIP_REC_EDGE_H, OVHIP_REC_ITASK, OVHIP_REC_RPR };
 int   ovhip_rec_append_raw(ovhip_recorder *rec, int which, const void *data, size_t n);
 int   ovhip_rec_set_dbf_offsets(ovhip_recorder *rec, const ovhip_dbf_offsets *offsets, int n);
 /* Access to the recorded (host) buffers. */
@@ -675,6 +735,7 @@ const ovhip_mc_unit *ovhip_rec_mc_units(const ovhip_recorder *rec, size_t *n);
 /* The refined (OVHIP_MC_BDOF / OVHIP_MC_DMVR) units, kept apart so that each list is one launch. */
 const ovhip_mc_unit *ovhip_rec_mcx_units(const ovhip_recorder *rec, size_t *n);
 const ovhip_aff_unit *ovhip_rec_aff_units(const ovhip_recorder *rec, size_t *n);
+const ovhip_rpr_unit *ovhip_rec_rpr_units(const ovhip_recorder *rec, size_t *n);
 const ovhip_ciip_unit *ovhip_rec_ciip_units(const ovhip_recorder *rec, size_t *n);
 const int32_t        *ovhip_rec_aff_side(const ovhip_recorder *rec, size_t *n_int32);
 
@@ -753,6 +814,11 @@ int  ovhip_mcx_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *ref
  * unit of the list, other units' entries untouched), no sample written.  geom: any picture of the references' size. */
 int  ovhip_dmvr_search_launch(ovhip_ctx *ctx, const ovhip_pic *geom, const ovhip_pic *refs, uint32_t n_refs,
                               const ovhip_mc_unit *d_units, uint32_t n_units, int32_t *d_mv_out);
+/* Units that read a reference of another size (ovhip_rpr_unit).  Every reference is read with its OWN w / h / strides
+ * (coordinates clamped against it: the device form of emulate_block_border); dst and intra have the picture's size. */
+int  ovhip_mc_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs,
+                         const ovhip_rpr_unit *d_units, uint32_t n_units, const uint16_t *d_lmcs_fwd_lut,
+                         const ovhip_pic *intra);
 /* CIIP: blends the intra prediction held in `intra` into `dst` (which holds the inter prediction). */
 int  ovhip_ciip_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *intra,
                        const ovhip_ciip_unit *d_units, uint32_t n_units);

@@ -17,7 +17,7 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / os.environ.get("OVVC_HIP_LIB_NAME", "libovvc_hip.so")      # (the variable: A / B runs of kernel variants, tools/ only)
 
 # ---- constants (include/ovvc_hip.h) ----
-OVHIP_ABI_VERSION = 8
+OVHIP_ABI_VERSION = 9
 OVHIP_OK, OVHIP_ENODEV, OVHIP_ENOMEM, OVHIP_EINVAL, OVHIP_ELAUNCH, OVHIP_EUNSUP, OVHIP_EREF = 0, -1, -2, -3, -4, -5, -6
 DST_VII, DCT_VIII, DCT_II = 0, 1, 2
 TB_TR, TB_DC, TB_TS, TB_TS_RAW = 0, 1, 2, 3
@@ -86,6 +86,30 @@ class PuDesc(C.Structure):
                 ("lmcs", C.c_uint8), ("refine", C.c_uint8), ("mv0x", C.c_int32), ("mv0y", C.c_int32),
                 ("mv1x", C.c_int32), ("mv1y", C.c_int32), ("poc0", C.c_int32), ("poc1", C.c_int32),
                 ("ref0", C.c_uint8), ("ref1", C.c_uint8), ("gpm_split_dir", C.c_uint8), ("ciip_wt", C.c_uint8)]
+
+
+class RefScale(C.Structure):
+    """ovhip_ref_scale: reference picture resampling scale of one reference-table slot"""
+    _fields_ = [("scale_hor", C.c_int32), ("scale_ver", C.c_int32), ("ref_w", C.c_int32), ("ref_h", C.c_int32),
+                ("chroma_hor_col_flag", C.c_uint8), ("chroma_ver_col_flag", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class RprSide(C.Structure):
+    _fields_ = [("pos_x", C.c_int32), ("pos_y", C.c_int32), ("cpos_x", C.c_int32), ("cpos_y", C.c_int32),
+                ("step_x", C.c_uint16), ("step_y", C.c_uint16), ("filt", C.c_uint8), ("filt_c", C.c_uint8),
+                ("ref", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class RprUnit(C.Structure):
+    """ovhip_rpr_unit: a <= 16x16 tile of a PU that reads a scaled reference (64 bytes)"""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint8), ("h", C.c_uint8), ("ox", C.c_uint8), ("oy", C.c_uint8),
+                ("dir", C.c_uint8), ("flags", C.c_uint8), ("w0", C.c_int8), ("w1", C.c_int8), ("aux", C.c_uint32),
+                ("s", RprSide * 2)]
+
+
+RPR_UNSCALED = 1 << 14
+RPR_S0, RPR_S1, RPR_NO_LUMA, RPR_NO_CHROMA, RPR_LMCS, RPR_HPEL_FILT, RPR_GPM = 1, 2, 4, 8, 16, 32, 128
+OVHIP_REC_RPR = 11
 
 
 class AffineDesc(C.Structure):
@@ -401,6 +425,10 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_rec_reset": (None, [vp]),
         "ovhip_rec_tu": (C.c_int, [vp, P(TuState), P(TuDesc)]),
         "ovhip_rec_pu": (C.c_int, [vp, P(PuDesc)]),
+        "ovhip_rec_set_ref_scale": (C.c_int, [vp, i32, P(RefScale)]),
+        "ovhip_rec_refusal": (C.c_char_p, [vp]),
+        "ovhip_rec_rpr_units": (vp, [vp, P(C.c_size_t)]),
+        "ovhip_mc_rpr_launch": (C.c_int, [vp, P(Pic), P(Pic), u32, vp, u32, vp, P(Pic)]),
         "ovhip_rec_dbf_ctu": (C.c_int, [vp, vp]),
         "ovhip_rec_dbf_row": (C.c_int, [vp, vp, C.c_size_t]),
         "ovhip_rec_dbf_mv_prepass_view": (C.c_int, [vp, vp, vp, vp]),
@@ -603,6 +631,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_ctx_destroy", "ovhip_ctx_sync", "ovhip_ctx_shares_queue", "ovhip_ctx_new_stream", "ovhip_ctx_fork", "ovhip_ctx_join", "ovhip_last_error", "ovhip_ctx_stream", "ovhip_malloc",
     "ovhip_free", "ovhip_h2d", "ovhip_d2h", "ovhip_pic_alloc", "ovhip_pic_free", "ovhip_pic_upload",
     "ovhip_pic_download", "ovhip_itx_launch", "ovhip_mc_launch",
+    "ovhip_rec_set_ref_scale", "ovhip_rec_refusal", "ovhip_rec_rpr_units", "ovhip_mc_rpr_launch",
     "ovhip_rec_create_ex", "ovhip_rec_set_dense_dbf_planes", "ovhip_rec_dbf_edges", "ovhip_dbf_launch_edges_ex",
     "ovhip_dmvr_search_launch", "ovhip_rec_append_raw", "ovhip_rec_set_dbf_offsets", "ovhip_rec_tu_intra", "ovhip_rec_itasks", "ovhip_rec_itasks_sorted", "ovhip_itx_launch_classes_res", "ovhip_intra_level_launch", "ovhip_intra_level_geom", "ovhip_intra_sync_words", "ovhip_intra_ctu_launch", "ovhip_intra_flow_words", "ovhip_intra_flow_items", "ovhip_intra_flow_launch",
     "ovhip_rec_itask_levels", "ovhip_rec_isp_cu", "ovhip_isp_geometry", "ovhip_rec_itasks_by_ctu", "ovhip_rec_set_ctu_size", "ovhip_job_bind", "ovhip_job_create", "ovhip_job_destroy", "ovhip_job_recorder", "ovhip_job_begin",
@@ -621,6 +650,25 @@ EXPORTED_SYMBOLS = [
     "ovhip_calllog_create", "ovhip_calllog_destroy", "ovhip_calllog_reset", "ovhip_calllog_data", "ovhip_rec_set_calllog", "ovhip_calllog_replay",
     "ovhip_stream_create", "ovhip_stream_destroy", "ovhip_stream_run", "ovhip_stream_frame", "ovhip_stream_key", "ovhip_stream_queue_info",
 ]
+
+
+def rpr_units(lib, rec) -> list:
+    """Copies of the ovhip_rpr_unit array a recorder holds (reference picture resampling)."""
+    n = C.c_size_t(0)
+    ptr = lib.ovhip_rec_rpr_units(rec, C.byref(n))
+    if not ptr or not n.value:
+        return []
+    raw = C.string_at(ptr, n.value * C.sizeof(RprUnit))
+    return [RprUnit.from_buffer_copy(raw, i * C.sizeof(RprUnit)) for i in range(n.value)]
+
+
+def set_ref_scale(lib, rec, slot: int, scale_hor: int | None = None, scale_ver: int | None = None, ref_w: int = 0, ref_h: int = 0,
+                  col_hor: int = 0, col_ver: int = 0) -> int:
+    """ovhip_rec_set_ref_scale; scale_hor None restores the default (unscaled)."""
+    if scale_hor is None:
+        return lib.ovhip_rec_set_ref_scale(rec, slot, None)
+    sc = RefScale(scale_hor, scale_ver if scale_ver is not None else scale_hor, ref_w, ref_h, col_hor, col_ver)
+    return lib.ovhip_rec_set_ref_scale(rec, slot, C.byref(sc))
 
 
 class Recorder:

@@ -1,0 +1,217 @@
+// kernels_rpr.hip -- motion compensation from references of another size (reference picture resampling) on gfx950.
+//
+// One wavefront (= one 64-thread workgroup) per ovhip_rpr_unit (<= 16x16 luma + its 4:2:0 chroma), as k_mc2.  Per list
+// and plane: the horizontal pass runs over the reference rows the tile's vertical positions need (up to 2 * 16 + 8 luma
+// rows at 2:1) into an int16 LDS tile, the vertical pass runs from LDS into registers, then uni / average / BCW / GPM,
+// clip, LMCS forward mapping and the CIIP blend, and the store.  Unlike k_mc2 the integer position, the phase and (per
+// axis) the filter set vary per output column / row, so every lane fetches its own taps from a constant table.  Coordinates
+// are clamped against EACH reference's own size: the device form of emulate_block_border (rcn_inter.c:148-225).
+//
+// Scaled side (rcn_mcp_rpr_l / _bi_l / _c / _bi_c, rcn_inter.c:2009-2512; leaves put_vvc_{qpel,epel}_rpr_*,
+// put_vvc_pel_rpr*, rcn_mc.c:549-790): column c of the PU at (anchor + ((c * step) << shift_mv) + 8192) >> 14, integer part
+// >> shift_mv, phase & (2^shift_mv - 1).  Unscaled side of a mixed bi unit (rcn_mcp_bidir0_l / _c): the regular 14-bit
+// prediction with the regular filters of vvc_mc_taps.h (integer phase = identity row).  Combined as rpr_sum /
+// rpr_w / gpm_weighted (rcn_mc.c:649-700, :1630-1655), then lmcs_reshape_forward.  int16 x int8 on the VALU, no MFMA.
+#include "mc_common.hip.h"
+#include "vvc_rpr_taps.h"
+
+namespace {
+
+#define RPR_LROWS 48    /* luma H tile rows: (15 * 2) + 1 + 7 at 2:1, rounded up */
+#define RPR_CROWS 24    /* chroma: (7 * 2) + 1 + 3 */
+
+struct RprTaps {
+    int8_t rl[6][16][8];    // scaled luma sets
+    int8_t rc[3][32][4];    // scaled chroma sets
+    int8_t l[17][8];        // regular luma (row 16: half-pel smoothing)
+    int8_t c[32][4];        // regular chroma
+};
+constexpr RprTaps build_rpr_taps()
+{
+    RprTaps t{};
+    for (int s = 0; s < 6; ++s) for (int p = 0; p < 16; ++p) for (int k = 0; k < 8; ++k) t.rl[s][p][k] = ovt_rpr_luma[s][p][k];
+    for (int s = 0; s < 3; ++s) for (int p = 0; p < 32; ++p) for (int k = 0; k < 4; ++k) t.rc[s][p][k] = ovt_rpr_chroma[s][p][k];
+    for (int p = 0; p < 17; ++p) for (int k = 0; k < 8; ++k) t.l[p][k] = ovt_mc_luma[p][k];
+    for (int p = 0; p < 32; ++p) for (int k = 0; k < 4; ++k) t.c[p][k] = ovt_mc_chroma[p][k];
+    return t;
+}
+__device__ const RprTaps __attribute__((aligned(16))) g_rpr = build_rpr_taps();
+
+// Integer position and phase of output index i (column or row) of list side s along one axis.
+//   scaled: anchor a (int32 as the reference computes it, wrap included: unsigned arithmetic, arithmetic shifts)
+//   unscaled: base = tile position in the picture (plane units) + (mv >> shift_mv), phase = mv & mask
+struct Axis { int32_t a; uint32_t step; int sh; int base; int mvph; bool scaled; };
+__device__ __forceinline__ void axis_pos(const Axis &ax, int i_pu, int i_tile, int &ip, int &ph)
+{
+    if (ax.scaled) {
+        const int32_t pm = (int32_t)((uint32_t)ax.a + (((uint32_t)i_pu * ax.step) << ax.sh) + 8192u) >> 14;
+        ip = pm >> ax.sh; ph = pm & ((1 << ax.sh) - 1);
+    } else {
+        ip = ax.base + i_tile; ph = ax.mvph;
+    }
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// One list, one plane: H pass into tile, V pass; returns in out[] (per lane-owned sample, up to 4) either the 14-bit
+// intermediate (bi) or the clipped sample (uni).  NT: 8 (luma) or 4 (chroma).
+template <int NT, int ROWS>
+__device__ __forceinline__ void rpr_plane(const uint16_t *__restrict__ ref, int rstride, int rw, int rh, const Axis &axx, const Axis &axy,
+                                          int fh, int fv, bool hpel, bool uni, int w, int h, int ox, int oy, int16_t *tile, int lane,
+                                          int out[4])
+{
+    constexpr int B = NT / 2 - 1;                   // taps before the position: 3 / 1
+    int iy0, ph0, iyl, phl;
+    axis_pos(axy, oy, 0, iy0, ph0);
+    axis_pos(axy, oy + h - 1, h - 1, iyl, phl);
+    const int rb = iy0 - B;
+    const int nrows = min(iyl - iy0 + NT, ROWS);
+    // horizontal: rows rb .. rb + nrows - 1, column c -> tile[r * 16 + c]
+    for (int t = lane; t < nrows * w; t += 64) {
+        const int r = t / w, c = t - r * w;
+        int ix, ph;
+        axis_pos(axx, ox + c, c, ix, ph);
+        const int8_t *tp;
+        if (NT == 8) tp = axx.scaled ? g_rpr.rl[fh][ph] : g_rpr.l[(hpel && ph == 8) ? 16 : ph];
+        else         tp = axx.scaled ? g_rpr.rc[fh][ph] : g_rpr.c[ph];
+        const uint16_t *row = ref + (size_t)clampi(rb + r, 0, rh - 1) * rstride;
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) acc += (int)tp[k] * (int)row[clampi(ix - B + k, 0, rw - 1)];
+        tile[r * 16 + c] = (int16_t)(acc >> (OV_BD - 8));
+    }
+    __syncthreads();
+    int j = 0;
+    for (int t = lane; t < w * h; t += 64, ++j) {
+        const int r = t / w, c = t - r * w;
+        int iy, ph;
+        axis_pos(axy, oy + r, r, iy, ph);
+        const int8_t *tp;
+        if (NT == 8) tp = axy.scaled ? g_rpr.rl[fv][ph] : g_rpr.l[(hpel && ph == 8) ? 16 : ph];
+        else         tp = axy.scaled ? g_rpr.rc[fv][ph] : g_rpr.c[ph];
+        const int base = iy - iy0;
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) acc += (int)tp[k] * (int)tile[min(base + k, ROWS - 1) * 16 + c];
+        int v;
+        if (!uni) {
+            v = acc >> 6;                                                     // put_vvc_*_rpr_bi_v / put_vvc_pel_rpr_bi
+        } else if (fv == 0 && ph == 0) {
+            // put_vvc_pel_rpr_clip reads the horizontal intermediate as uint16: a negative one clips to the maximum
+            v = ov_clip_bd(((int)(uint16_t)tile[min(base + B, ROWS - 1) * 16 + c] + 8) >> 4);
+        } else {
+            v = ov_clip_bd(((acc >> 6) + 8) >> 4);                            // put_vvc_*_rpr_clip_v
+        }
+        if (j < 4) out[j] = v;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ int rpr_gpm(uint32_t aux, int x, int y, int p0, int p1)
+{
+    const int k = (int16_t)(aux & 0xffff), a = (int8_t)((aux >> 16) & 0xff), b = (int8_t)(aux >> 24);
+    const int wgt = ov_clip3((k + a * x + b * y) >> 3, 0, 8);
+    return ov_clip_bd((p1 * (8 - wgt) + p0 * wgt + 64) >> 7);
+}
+
+__global__ __launch_bounds__(64) void k_mc_rpr(ovhip_pic dst, RefTable refs, const ovhip_rpr_unit *__restrict__ units, uint32_t n_units,
+                                               const uint16_t *__restrict__ lmcs_fwd, ovhip_pic intra)
+{
+    __shared__ int16_t s_tile[RPR_LROWS * 16];
+    if (blockIdx.x >= n_units) return;
+    const ovhip_rpr_unit u = units[blockIdx.x];
+    const int lane = threadIdx.x;
+    const int dir = u.dir & 3;
+    const bool uni = dir != 3, gpm = (u.flags & OVHIP_RPR_GPM) != 0, hpel = (u.flags & OVHIP_RPR_HPEL_FILT) != 0;
+    const int w = u.w, h = u.h;
+    if (!dir || w < 4 || h < 4 || w > 16 || h > 16) return;
+
+    if (!(u.flags & OVHIP_RPR_NO_LUMA)) {
+        int P[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
+        for (int l = 0; l < 2; ++l) {
+            if (!(dir & (1 << l))) continue;
+            const ovhip_rpr_side s = u.s[l];
+            const ovhip_pic &rp = refs.p[min((int)s.ref, MC_MAX_REFS - 1)];
+            const bool sc = (u.flags & (l ? OVHIP_RPR_S1 : OVHIP_RPR_S0)) != 0;
+            const Axis ax = { s.pos_x, s.step_x, 4, u.x + (s.pos_x >> 4), s.pos_x & 15, sc };
+            const Axis ay = { s.pos_y, s.step_y, 4, u.y + (s.pos_y >> 4), s.pos_y & 15, sc };
+            rpr_plane<8, RPR_LROWS>(rp.y, rp.stride_y, rp.w, rp.h, ax, ay, min(s.filt & 15, 5), min(s.filt >> 4, 5), hpel && !sc, uni, w, h,
+                                    u.ox, u.oy, s_tile, lane, P[l]);
+        }
+        int j = 0;
+        for (int t = lane; t < w * h; t += 64, ++j) {
+            const int r = t / w, c = t - r * w;
+            const int p0 = P[0][j & 3], p1 = P[1][j & 3];
+            int v;
+            if (uni)                          v = dir == 1 ? p0 : p1;
+            else if (gpm)                     v = rpr_gpm(u.aux, c, r, p0, p1);
+            else if (u.w0 == 4 && u.w1 == 4)  v = ov_clip_bd((p0 + p1 + 16) >> 5);
+            else                              v = ov_clip_bd((p0 * u.w0 + p1 * u.w1 + 64) >> 7);
+            if ((u.flags & OVHIP_RPR_LMCS) && lmcs_fwd) v = lmcs_fwd[v];
+            const int px = u.x + c, py = u.y + r;
+            if (px >= dst.w || py >= dst.h) continue;
+            if (!gpm && u.aux) v = ov_clip_bd((intra.y[(size_t)py * intra.stride_y + px] * (int)(u.aux & 7) + v * (4 - (int)(u.aux & 7)) + 2) >> 2);
+            dst.y[(size_t)py * dst.stride_y + px] = (uint16_t)v;
+        }
+    }
+    if (!(u.flags & OVHIP_RPR_NO_CHROMA)) {
+        const int wc = w >> 1, hc = h >> 1;
+        for (int plane = 1; plane <= 2; ++plane) {
+            int P[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
+            for (int l = 0; l < 2; ++l) {
+                if (!(dir & (1 << l))) continue;
+                const ovhip_rpr_side s = u.s[l];
+                const ovhip_pic &rp = refs.p[min((int)s.ref, MC_MAX_REFS - 1)];
+                const bool sc = (u.flags & (l ? OVHIP_RPR_S1 : OVHIP_RPR_S0)) != 0;
+                const Axis ax = { s.cpos_x, s.step_x, 5, (u.x >> 1) + (s.pos_x >> 5), s.pos_x & 31, sc };
+                const Axis ay = { s.cpos_y, s.step_y, 5, (u.y >> 1) + (s.pos_y >> 5), s.pos_y & 31, sc };
+                rpr_plane<4, RPR_CROWS>(plane == 1 ? rp.cb : rp.cr, rp.stride_c, rp.w >> 1, rp.h >> 1, ax, ay, min(s.filt_c & 15, 2),
+                                        min(s.filt_c >> 4, 2), false, uni, wc, hc, u.ox >> 1, u.oy >> 1, s_tile, lane, P[l]);
+            }
+            uint16_t *d = plane == 1 ? dst.cb : dst.cr;
+            const uint16_t *ip = plane == 1 ? intra.cb : intra.cr;
+            const bool ciip = !gpm && u.aux && !(u.aux & 0x100);
+            int j = 0;
+            for (int t = lane; t < wc * hc; t += 64, ++j) {
+                const int r = t / wc, c = t - r * wc;
+                const int p0 = P[0][j & 3], p1 = P[1][j & 3];
+                int v;
+                if (uni)                          v = dir == 1 ? p0 : p1;
+                else if (gpm)                     v = rpr_gpm(u.aux, 2 * c, 2 * r, p0, p1);
+                else if (u.w0 == 4 && u.w1 == 4)  v = ov_clip_bd((p0 + p1 + 16) >> 5);
+                else                              v = ov_clip_bd((p0 * u.w0 + p1 * u.w1 + 64) >> 7);
+                const int px = (u.x >> 1) + c, py = (u.y >> 1) + r;
+                if (px >= (dst.w >> 1) || py >= (dst.h >> 1)) continue;
+                if (ciip) v = ov_clip_bd((ip[(size_t)py * intra.stride_c + px] * (int)(u.aux & 7) + v * (4 - (int)(u.aux & 7)) + 2) >> 2);
+                d[(size_t)py * dst.stride_c + px] = (uint16_t)v;
+            }
+        }
+    }
+}
+
+} // namespace
+
+extern "C" int ovhip_mc_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs,
+                                   const ovhip_rpr_unit *d_units, uint32_t n_units, const uint16_t *d_lmcs_fwd_lut,
+                                   const ovhip_pic *intra)
+{
+    if (!ctx || !dst) return OVHIP_EINVAL;
+    OV_DEVICE(ctx);
+    if (!n_units) return OVHIP_OK;
+    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
+        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_rpr_launch: bad reference table / units", hipSuccess);
+    RefTable t;
+    memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < n_refs; ++i) {
+        // every reference is read with its own geometry; only a plane that is not there is refused
+        if (!refs[i].y || !refs[i].cb || !refs[i].cr || refs[i].w < 8 || refs[i].h < 8 || refs[i].stride_y < refs[i].w ||
+            refs[i].stride_c < (refs[i].w >> 1))
+            return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_rpr_launch: bad reference picture", hipSuccess);
+        t.p[i] = refs[i];
+    }
+    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    hipLaunchKernelGGL(k_mc_rpr, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut,
+                       intra ? *intra : *dst);
+    OV_LAUNCH_CHECK(ctx, "k_mc_rpr");
+    return OVHIP_OK;
+}

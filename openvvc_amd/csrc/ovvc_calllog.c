@@ -11,7 +11,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_record_priv.h"
 
-enum { CL_CTU_SIZE = 1, CL_TU, CL_ISP, CL_PU, CL_AFF, CL_REGION, CL_DBF, CL_CIIP };
+enum { CL_CTU_SIZE = 1, CL_TU, CL_ISP, CL_PU, CL_AFF, CL_REGION, CL_DBF, CL_CIIP, CL_REF_SCALE };
 
 struct ovhip_calllog { unsigned char *data; size_t n, cap; int oom; };   /* oom: the log is unusable (allocation failed or a call could not be written down): _data returns NULL */
 
@@ -24,6 +24,7 @@ struct cl_tu {
 struct cl_isp { ovhip_tu_state st; ovhip_isp_desc cu; };
 struct cl_region { int32_t x0, y0; uint32_t abv, lft; };
 struct cl_ciip { int32_t x0, y0, log2_w, log2_h, mode_abv, mode_lft; };
+struct cl_ref_scale { int32_t slot; uint32_t has; ovhip_ref_scale sc; };   /* has = 0: the default (NULL) */
 
 ovhip_calllog *ovhip_calllog_create(void) { return (ovhip_calllog *)calloc(1, sizeof(ovhip_calllog)); }
 void ovhip_calllog_destroy(ovhip_calllog *l) { if (l) { free(l->data); free(l); } }
@@ -163,6 +164,17 @@ ovhip_calllog_ctu_size_(ovhip_calllog *l, int32_t log2_ctu_s)
     if (p) memcpy(p, &log2_ctu_s, sizeof(log2_ctu_s));
 }
 
+void
+ovhip_calllog_ref_scale_(ovhip_calllog *l, int32_t slot, const ovhip_ref_scale *sc)
+{
+    struct cl_ref_scale g;
+    memset(&g, 0, sizeof(g));
+    g.slot = slot;
+    if (sc) { g.has = 1; g.sc = *sc; memset(g.sc.pad, 0, sizeof(g.sc.pad)); }
+    unsigned char *p = cl_open(l, CL_REF_SCALE, sizeof(g));
+    if (p) memcpy(p, &g, sizeof(g));
+}
+
 int64_t
 ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec)
 {
@@ -228,6 +240,13 @@ ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec)
         case CL_REGION: { CL_NEED(sizeof(struct cl_region)) const struct cl_region *g = (const struct cl_region *)q; r = ovhip_rec_lmcs_region(rec, g->x0, g->y0, g->abv, g->lft); break; }
         case CL_DBF: CL_NEED(sizeof(ovhip_dbf_ctu)) r = ovhip_rec_dbf_ctu(rec, (const ovhip_dbf_ctu *)q); break;
         case CL_CIIP: { CL_NEED(sizeof(struct cl_ciip)) const struct cl_ciip *g = (const struct cl_ciip *)q; r = ovhip_rec_ciip(rec, g->x0, g->y0, g->log2_w, g->log2_h, g->mode_abv, g->mode_lft); break; }
+        case CL_REF_SCALE: {
+            CL_NEED(sizeof(struct cl_ref_scale))
+            const struct cl_ref_scale *g = (const struct cl_ref_scale *)q;
+            if (g->has > 1) { r = OVHIP_EINVAL; break; }
+            r = ovhip_rec_set_ref_scale(rec, g->slot, g->has ? &g->sc : NULL);
+            break;
+        }
         default: r = OVHIP_EINVAL;
         }
 #undef CL_NEED

@@ -17,7 +17,23 @@ namespace {
 
 struct DevBuf { void *p; size_t cap; };
 
-enum { B_TB, B_COEF, B_MC, B_MCX, B_MV, B_AFF, B_SIDE, B_REG, B_SCALE, B_EV, B_EH, B_PARAM, B_CLASS, B_CIIP, B_ITASK, B_ICTU, B_IITEM, B_TMVP, B_COUNT };
+enum { B_TB, B_COEF, B_MC, B_MCX, B_MV, B_AFF, B_SIDE, B_REG, B_SCALE, B_EV, B_EH, B_PARAM, B_CLASS, B_CIIP, B_ITASK, B_ICTU, B_IITEM, B_TMVP, B_RPR, B_COUNT };
+
+// Reference picture resampling: k_mc2 / k_mcxa / the DMVR search take the window geometry from the picture and refuse a reference
+// of another size.  Their units never read such a slot (the recorder sends every unit that reads a scaled reference to the RPR
+// array), so they get a table in which those slots hold a same-size stand-in (`geom` itself); k_mc_rpr gets the real table.
+static const ovhip_pic *same_size_refs(const ovhip_pic *geom, const ovhip_pic *refs, uint32_t n_refs, ovhip_pic *out)
+{
+    if (!refs || n_refs > 16) return refs;
+    bool any = false;
+    for (uint32_t i = 0; i < n_refs; ++i) {
+        const bool same = refs[i].w == geom->w && refs[i].h == geom->h && refs[i].stride_y == geom->stride_y && refs[i].stride_c == geom->stride_c;
+        out[i] = same ? refs[i] : *geom;
+        any |= !same;
+    }
+    return any ? out : refs;
+}
+
 
 // layout of the parameter block (one pinned staging copy, one H2D)
 struct ParamLayout { size_t sao, alf_ctus, lcoef, lclip, ccoef, cclip, cc, fwd, bwd, total; };
@@ -502,8 +518,9 @@ int64_t ovhip_job_dmvr_rows_begin_upto(ovhip_job *j, const ovhip_pic *refs, uint
         char *d_units = (char *)j->dev[B_MCX].p + first * sizeof(ovhip_mc_unit);
         int32_t *d_mv = (int32_t *)j->dev[B_MV].p + 4 * first;
         OV_HIP(ctx, hipMemcpyAsync(d_units, u + first, (n - first) * sizeof(ovhip_mc_unit), hipMemcpyHostToDevice, ctx->stream));
-        ovhip_pic geom = j->tmp;
-        CHK(ovhip_dmvr_search_launch(ctx, &geom, refs, n_refs, (const ovhip_mc_unit *)d_units, (uint32_t)(n - first), d_mv));
+        ovhip_pic geom = j->tmp, same[16];
+        CHK(ovhip_dmvr_search_launch(ctx, &geom, same_size_refs(&geom, refs, n_refs, same), n_refs, (const ovhip_mc_unit *)d_units,
+                                     (uint32_t)(n - first), d_mv));
         CHK(store_host(ctx, j->mv_host + 4 * first, d_mv, (n - first) * 16));
         if (log2_ctu_s) {
             // the same vectors as entries of the picture's collocated motion plane: what the caller patches before it publishes
@@ -601,6 +618,8 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
     const ovhip_ciip_unit *ciip = ovhip_rec_ciip_units(rec, &n_ciip);
     if (n_ciip && !intra)
         return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_flush: CIIP blend units recorded but no picture with their intra prediction", hipSuccess);
+    size_t n_rpr = 0;
+    const ovhip_rpr_unit *rpr = ovhip_rec_rpr_units(rec, &n_rpr);     // units that read a reference of another size (k_mc_rpr)
     // ordered tasks: grouped by CTU for the one-launch pass, or sorted by level for one launch per level
     size_t n_it = 0, n_ictu = 0; uint32_t n_lv = 0; const uint32_t *lv_start = nullptr; const ovhip_ictu *ictu = nullptr;
     const int by_ctu = pr->stages && (stages & OVHIP_STAGE_INTRA_CTU);
@@ -668,6 +687,7 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
         { j->items_host, by_flow ? n_items * sizeof(uint32_t) : 0, B_IITEM, 0 },
         { mcx, n_mcx * sizeof(*mcx), B_MCX, 0 }, { ciip, n_ciip * sizeof(*ciip), B_CIIP, 0 }, { aff, n_aff * sizeof(*aff), B_AFF, 0 },
         { side, n_side * sizeof(*side), B_SIDE, 0 }, { reg, n_reg * sizeof(*reg), B_REG, 0 },
+        { rpr, n_rpr * sizeof(*rpr), B_RPR, 0 },
         { ev, (stages & OVHIP_STAGE_DBF) ? n_ev * sizeof(*ev) : 0, B_EV, 0 }, { eh, (stages & OVHIP_STAGE_DBF) ? n_eh * sizeof(*eh) : 0, B_EH, 0 },
     };
     static_assert(B_COUNT <= 24, "packed_prev");
@@ -756,9 +776,14 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
 
     // ---- prediction ----
     if (stages & OVHIP_STAGE_MC) {
+        ovhip_pic same[16];
+        const ovhip_pic *refs_all = refs;
+        refs = same_size_refs(dst, refs, n_refs, same);
         { StageTimer t_(j, OVHIP_TIME_MC);
-        CHK(ovhip_mc_launch(ctx, dst, refs, n_refs, (const ovhip_mc_unit *)DEV(B_MC), (uint32_t)n_mc, d_fwd, intra)); }
-        j->st.n_launches += n_mc != 0;
+        CHK(ovhip_mc_launch(ctx, dst, refs, n_refs, (const ovhip_mc_unit *)DEV(B_MC), (uint32_t)n_mc, d_fwd, intra));
+        // beside k_mc2 (disjoint blocks), only on pictures that have such units
+        if (n_rpr) CHK(ovhip_mc_rpr_launch(ctx, dst, refs_all, n_refs, (const ovhip_rpr_unit *)DEV(B_RPR), (uint32_t)n_rpr, d_fwd, intra)); }
+        j->st.n_launches += (n_mc != 0) + (n_rpr != 0);
         // Nothing on the device reads the refined vectors unless the TMVP entries are asked for: k_mcxa then stores them (one 16-byte
         // store per unit) straight into the page-locked array the host reads -- not even k_store_host's launch is left
         const bool mv_direct = n_mcx && !pr->tmvp_cells && !j->resident && X_MV_D2H == 3;
@@ -1322,6 +1347,7 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
     B.row0 = bs->row_prev; B.row1 = row_end; B.c0 = c0; B.c1 = c1;
     size_t dummy = 0;
     if (ovhip_rec_ciip_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: stand-alone CIIP blend units (a second picture with the caller's intra prediction)", hipSuccess);
+    if (ovhip_rec_rpr_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: reference picture resampling units", hipSuccess);
     const size_t n_tb = c1.n_tb - c0.n_tb, n_coef = c1.n_coef - c0.n_coef, n_mc = c1.n_mc - c0.n_mc, n_mcx = c1.n_mcx - c0.n_mcx,
                  n_aff = c1.n_aff - c0.n_aff, n_side = c1.n_side - c0.n_side, n_reg = c1.n_reg - c0.n_reg, n_it_all = c1.n_itask - c0.n_itask,
                  n_ev = (stages & OVHIP_STAGE_DBF) ? c1.n_edge_v - c0.n_edge_v : 0, n_eh = (stages & OVHIP_STAGE_DBF) ? c1.n_edge_h - c0.n_edge_h : 0;

@@ -38,6 +38,7 @@ ovhip_rec_create_ex(int32_t pic_w, int32_t pic_h, const ovhip_allocator *a)
     r->pic_h = pic_h;
     r->dense_planes = 1;
     r->log2_ctu = 7;
+    ovhip_rec_rpr_reset_(r);
     if (a) { r->al = *a; r->has_al = 1; }
     return r;
 }
@@ -56,7 +57,7 @@ ovhip_rec_destroy(ovhip_recorder *r)
 {
     if (!r) return;
     void *bufs[] = { r->tb, r->coef, r->mc, r->mcx, r->aff, r->aff_side, r->reg, r->tb_split, r->ciip, r->edge_v, r->edge_h,
-                     r->itask, r->itask_sorted, r->itask_ctu, r->ictu };
+                     r->itask, r->itask_sorted, r->itask_ctu, r->ictu, r->rpr };
     free(r->ilevel_start); free(r->ctu_count);
     ovhip_rec_intra_free_(r);
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); ++i) ovhip_rec_free_(r, bufs[i]);
@@ -71,6 +72,7 @@ ovhip_rec_reset(ovhip_recorder *r)
     r->n_tb = r->n_coef = r->n_mc = r->n_mcx = r->n_aff = r->n_side = r->n_reg = r->n_ciip = 0;
     r->n_edge_v = r->n_edge_h = 0;
     r->n_dbf_off = 0;
+    ovhip_rec_rpr_reset_(r);
     ovhip_rec_intra_reset_(r);
     ovhip_rec_dbf_reset_(r);
 }
@@ -111,6 +113,7 @@ ACCESSOR(ovhip_mc_unit, ovhip_rec_mc_units, mc, n_mc)
 ACCESSOR(ovhip_mc_unit, ovhip_rec_mcx_units, mcx, n_mcx)
 ACCESSOR(ovhip_aff_unit, ovhip_rec_aff_units, aff, n_aff)
 ACCESSOR(int32_t, ovhip_rec_aff_side, aff_side, n_side)
+ACCESSOR(ovhip_rpr_unit, ovhip_rec_rpr_units, rpr, n_rpr)
 
 /* lengths of the arrays a band of CTU rows is cut from (ovhip_job_band) */
 void
@@ -167,6 +170,7 @@ ovhip_rec_append_raw(ovhip_recorder *r, int which, const void *data, size_t n)
     case OVHIP_REC_EDGE_V: p = (void **)&r->edge_v;   cnt = &r->n_edge_v; cap = &r->cap_edge_v; elem = sizeof(ovhip_dbf_edge); break;
     case OVHIP_REC_EDGE_H: p = (void **)&r->edge_h;   cnt = &r->n_edge_h; cap = &r->cap_edge_h; elem = sizeof(ovhip_dbf_edge); break;
     case OVHIP_REC_ITASK:  p = (void **)&r->itask;    cnt = &r->n_itask;  cap = &r->cap_itask;  elem = sizeof(ovhip_itask); break;
+    case OVHIP_REC_RPR:    p = (void **)&r->rpr;      cnt = &r->n_rpr;    cap = &r->cap_rpr;    elem = sizeof(ovhip_rpr_unit); break;
     default: return OVHIP_EINVAL;
     }
     if (grow(p, cap, *cnt + n, elem)) return OVHIP_ENOMEM;
@@ -790,12 +794,10 @@ rec_pu_refined(ovhip_recorder *r, const ovhip_pu_desc *pu)
  *   weightIdx = ((x + offX) * 2 + 1) * dis[angle] + ((y + offY) * 2 + 1) * dis[angle + 8]
  *   w = clip3(0, 8, ((partFlip ? 32 + weightIdx : 32 - weightIdx) + 4) >> 3) */
 #include "vvc_gpm_tables.h"
-static int
-rec_pu_gpm(ovhip_recorder *r, const ovhip_pu_desc *pu)
+static void
+gpm_plane(const ovhip_pu_desc *pu, int *pK, int *pA, int *pB)
 {
     const int pw = 1 << pu->log2_w, ph = 1 << pu->log2_h;
-    if (pu->gpm_split_dir > 63 || pu->log2_w < 3 || pu->log2_h < 3 || pu->log2_w > 6 || pu->log2_h > 6) return OVHIP_EINVAL;
-
     const int angle = ovt_gpm_params[pu->gpm_split_dir][0], dist = ovt_gpm_params[pu->gpm_split_dir][1];
     const int dx = ovt_gpm_dis[angle], dy = ovt_gpm_dis[(angle + 8) & 31];
     const int flip = (angle >= 13 && angle <= 27) ? 0 : 1;
@@ -807,7 +809,16 @@ rec_pu_gpm(ovhip_recorder *r, const ovhip_pu_desc *pu)
     }
     const int sgn = flip ? 1 : -1;
     const int A = sgn * 2 * dx, B = sgn * 2 * dy;
-    const int K = 36 + sgn * ((2 * off_x + 1) * dx + (2 * off_y + 1) * dy);
+    *pK = 36 + sgn * ((2 * off_x + 1) * dx + (2 * off_y + 1) * dy);
+    *pA = A; *pB = B;
+}
+
+static int
+rec_pu_gpm(ovhip_recorder *r, const ovhip_pu_desc *pu)
+{
+    const int pw = 1 << pu->log2_w, ph = 1 << pu->log2_h;
+    int K, A, B;
+    gpm_plane(pu, &K, &A, &B);
 
     int32_t mv0x = pu->mv0x, mv0y = pu->mv0y, mv1x = pu->mv1x, mv1y = pu->mv1y;
     clip_mv(r, pu->x0, pu->y0, pw, ph, &mv0x, &mv0y);
@@ -837,6 +848,173 @@ rec_pu_gpm(ovhip_recorder *r, const ovhip_pu_desc *pu)
     return n;
 }
 
+/* ---------------------------------------------------------------- reference picture resampling */
+static const ovhip_ref_scale rpr_default = { OVHIP_RPR_UNSCALED, OVHIP_RPR_UNSCALED, 0, 0, 0, 0, { 0, 0 } };
+
+void
+ovhip_rec_rpr_reset_(ovhip_recorder *r)
+{
+    r->n_rpr = 0;
+    r->refusal = "";
+    if (r->n_scaled || !r->ref_scale[0].scale_hor) {
+        for (int i = 0; i < 256; ++i) r->ref_scale[i] = rpr_default;
+        r->n_scaled = 0;
+    }
+}
+
+int
+ovhip_rec_set_ref_scale(ovhip_recorder *r, int32_t slot, const ovhip_ref_scale *sc)
+{
+    if (!r || slot < 0 || slot > 255) return OVHIP_EINVAL;
+    if (sc && (sc->scale_hor < (OVHIP_RPR_UNSCALED >> 3) || sc->scale_hor > 2 * OVHIP_RPR_UNSCALED ||
+               sc->scale_ver < (OVHIP_RPR_UNSCALED >> 3) || sc->scale_ver > 2 * OVHIP_RPR_UNSCALED ||
+               sc->ref_w < 0 || sc->ref_h < 0 || sc->ref_w > 16384 || sc->ref_h > 16384 ||
+               sc->chroma_hor_col_flag > 1 || sc->chroma_ver_col_flag > 1))
+        return OVHIP_EINVAL;     /* H.266: a reference at most 2x larger and 8x smaller than the picture */
+    if (r->log) ovhip_calllog_ref_scale_(r->log, slot, sc);
+    ovhip_ref_scale *d = &r->ref_scale[slot];
+    const int was = memcmp(d, &rpr_default, sizeof(*d)) != 0;
+    *d = sc ? *sc : rpr_default;
+    memset(d->pad, 0, sizeof(d->pad));
+    const int is = memcmp(d, &rpr_default, sizeof(*d)) != 0;
+    r->n_scaled += (uint32_t)(is - was);
+    return OVHIP_OK;
+}
+
+const char *ovhip_rec_refusal(const ovhip_recorder *r) { return r ? r->refusal : ""; }
+
+static int
+refuse(ovhip_recorder *r, const char *why)
+{
+    r->refusal = why;
+    return OVHIP_EUNSUP;
+}
+
+/* 1: the slot is scaled, 0: regular prediction, <0: refused (a scale of 1 on a reference of another size) */
+static int
+slot_scaled(ovhip_recorder *r, int slot)
+{
+    const ovhip_ref_scale *s = &r->ref_scale[slot];
+    if (s->scale_hor != OVHIP_RPR_UNSCALED || s->scale_ver != OVHIP_RPR_UNSCALED) return 1;
+    if ((s->ref_w && s->ref_w != r->pic_w) || (s->ref_h && s->ref_h != r->pic_h))
+        return refuse(r, "reference picture resampling: scale 1 on a reference of another size");
+    return 0;
+}
+
+/* compute_rpr_filter_idx (rcn_inter.c:1991-2006) */
+static int
+rpr_filter_idx(int scale, int flag_4x4)
+{
+    int idx = flag_4x4 ? 3 : 0;
+    if (scale > OVHIP_RPR_UNSCALED * 7 / 4) idx += 2;
+    else if (scale > OVHIP_RPR_UNSCALED * 5 / 4) idx += 1;
+    return idx;
+}
+
+/* One axis of the anchor of rcn_mcp_rpr_l / _c: ref_pos = ((pos << shift_mv) + mv) * scale + add + (1 << (shift_mv + 3)),
+ * the extent ref_pu_* of the PU in the reference, then clip_rpr_position (rcn_inter.c:2009-2026).  The reference computes in
+ * int32 and wraps at 4K with large vectors; the same wrap here in explicit unsigned 32-bit arithmetic (arithmetic shifts of
+ * the wrapped value, as the compiled reference does). */
+static int32_t
+rpr_anchor(int32_t pos, int32_t mv, int32_t scale, int32_t add, int pu_len, int pic_len, int shift_mv, int min1)
+{
+    const int shift_pos = 14 + shift_mv;
+    const uint32_t offset = 1u << 13;
+    const uint32_t step = (uint32_t)(((scale + 8) >> 4) << 4);
+    const int32_t ref_pos = (int32_t)((((uint32_t)pos << shift_mv) + (uint32_t)mv) * (uint32_t)scale + (uint32_t)add + (1u << (shift_mv + 3)));
+    const int32_t ref_i = (int32_t)((uint32_t)ref_pos + offset) >> shift_pos;
+    int32_t ext = ((int32_t)((uint32_t)ref_pos + (((uint32_t)(pu_len - 1) * step) << shift_mv) + offset) >> shift_pos) - ref_i + 1;
+    if (min1 && ext < 1) ext = 1;
+    const int32_t prec = ref_pos & ((1 << shift_pos) - 1);
+    const int32_t hi = (int32_t)((uint32_t)(pic_len + 3) << shift_pos);
+    const int32_t lo = (int32_t)(0u - ((uint32_t)(ext + 4) << shift_pos));
+    int32_t v = ref_pos;
+    const int32_t a = (int32_t)((uint32_t)lo + (uint32_t)prec), b = (int32_t)((uint32_t)hi + (uint32_t)prec);
+    v = v > a ? v : a;                 /* ov_clip = min(max(v, a), b) */
+    v = v < b ? v : b;
+    return v;
+}
+
+static void
+rpr_side(const ovhip_recorder *r, const ovhip_pu_desc *pu, int l, int scaled, int32_t mvx, int32_t mvy, ovhip_rpr_side *s)
+{
+    const int pw = 1 << pu->log2_w, ph = 1 << pu->log2_h;
+    memset(s, 0, sizeof(*s));
+    s->ref = l ? pu->ref1 : pu->ref0;
+    if (!scaled) {
+        /* rcn_mcp_bidir0_l / _c: the regular 14-bit prediction, clip_mv against the PU */
+        clip_mv(r, pu->x0, pu->y0, pw, ph, &mvx, &mvy);
+        s->pos_x = mvx; s->pos_y = mvy;
+        return;
+    }
+    const ovhip_ref_scale *sc = &r->ref_scale[s->ref];
+    const int f4 = pu->log2_w == 2 && pu->log2_h == 2;
+    s->step_x = (uint16_t)(((sc->scale_hor + 8) >> 4) << 4);
+    s->step_y = (uint16_t)(((sc->scale_ver + 8) >> 4) << 4);
+    s->filt = (uint8_t)(rpr_filter_idx(sc->scale_hor, f4) | rpr_filter_idx(sc->scale_ver, f4) << 4);
+    s->filt_c = s->filt;
+    s->pos_x = rpr_anchor(pu->x0, mvx, sc->scale_hor, 0, pw, sc->ref_w ? sc->ref_w : r->pic_w, 4, 0);
+    s->pos_y = rpr_anchor(pu->y0, mvy, sc->scale_ver, 0, ph, sc->ref_h ? sc->ref_h : r->pic_h, 4, 1);
+    /* chroma: add_x / add_y from the collocation flags (rcn_inter.c:2322-2323) */
+    const int32_t add_x = (1 - sc->chroma_hor_col_flag) * 8 * (sc->scale_hor - OVHIP_RPR_UNSCALED);
+    const int32_t add_y = (1 - sc->chroma_ver_col_flag) * 8 * (sc->scale_ver - OVHIP_RPR_UNSCALED);
+    s->cpos_x = rpr_anchor(pu->x0 >> 1, mvx, sc->scale_hor, add_x, pw >> 1, (sc->ref_w ? sc->ref_w : r->pic_w) >> 1, 5, 0);
+    s->cpos_y = rpr_anchor(pu->y0 >> 1, mvy, sc->scale_ver, add_y, ph >> 1, (sc->ref_h ? sc->ref_h : r->pic_h) >> 1, 5, 1);
+}
+
+/* A PU with at least one scaled list used (rcn_mcp_b / _l / _c, rcn_gpm_b and CIIP's rcn_mcp_b into RPR paths,
+ * rcn_inter.c:2750-2960, :3118-3143): cut into <=16x16 tiles that share the PU's anchors. */
+static int
+rec_pu_rpr(ovhip_recorder *r, const ovhip_pu_desc *pu, int dir, int s0, int s1)
+{
+    const int pw = 1 << pu->log2_w, ph = 1 << pu->log2_h;
+    if (pw == 4 && ph == 4) return refuse(r, "reference picture resampling: 4x4 prediction unit with a scaled reference");
+    const int gpm = (pu->refine & OVHIP_PU_GPM) != 0;
+    int K = 0, A = 0, B = 0;
+    if (gpm) gpm_plane(pu, &K, &A, &B);
+    int8_t w0 = 4, w1 = 4;
+    if (!gpm && dir == 3 && pu->bcw_idx_plus1 != 0 && pu->bcw_idx_plus1 != 3) {
+        static const int8_t bcw[5] = { -2, 3, 4, 5, 10 };
+        if (pu->bcw_idx_plus1 > 5) return OVHIP_EINVAL;
+        w1 = bcw[pu->bcw_idx_plus1 - 1];
+        w0 = (int8_t)(8 - w1);
+    }
+    ovhip_rpr_side sd[2];
+    memset(sd, 0, sizeof(sd));
+    if (dir & 1) rpr_side(r, pu, 0, s0, pu->mv0x, pu->mv0y, &sd[0]);
+    if (dir & 2) rpr_side(r, pu, 1, s1, pu->mv1x, pu->mv1y, &sd[1]);
+
+    uint8_t flags = (uint8_t)(((dir & 1) && s0 ? OVHIP_RPR_S0 : 0) | ((dir & 2) && s1 ? OVHIP_RPR_S1 : 0));
+    if (gpm)                flags |= OVHIP_RPR_GPM;
+    if (pu->prec_amvr_half) flags |= OVHIP_RPR_HPEL_FILT;
+    if (!(pu->planes & 1))  flags |= OVHIP_RPR_NO_LUMA;
+    if (!(pu->planes & 2))  flags |= OVHIP_RPR_NO_CHROMA;
+    if (pu->lmcs)           flags |= OVHIP_RPR_LMCS;
+
+    const int uw = pw > 16 ? 16 : pw, uh = ph > 16 ? 16 : ph;
+    const int nu = (pw / uw) * (ph / uh);
+    if (grow((void **)&r->rpr, &r->cap_rpr, r->n_rpr + (size_t)nu, sizeof(ovhip_rpr_unit))) return OVHIP_ENOMEM;
+    for (int uy = 0; uy < ph; uy += uh) {
+        for (int ux = 0; ux < pw; ux += uw) {
+            ovhip_rpr_unit *u = &r->rpr[r->n_rpr++];
+            memset(u, 0, sizeof(*u));
+            u->x = (uint16_t)(pu->x0 + ux); u->y = (uint16_t)(pu->y0 + uy);
+            u->w = (uint8_t)uw; u->h = (uint8_t)uh;
+            u->ox = (uint8_t)ux; u->oy = (uint8_t)uy;
+            u->dir = (uint8_t)dir; u->flags = flags;
+            u->w0 = w0; u->w1 = w1;
+            u->s[0] = sd[0]; u->s[1] = sd[1];
+            if (gpm) {
+                const int k = K + A * ux + B * uy;
+                u->aux = ((uint32_t)k & 0xffff) | ((uint32_t)(A & 0xff) << 16) | ((uint32_t)(B & 0xff) << 24);
+            } else if (pu->ciip_wt) {
+                u->aux = (uint32_t)(pu->ciip_wt & 7) | (pu->log2_w <= 2 ? 0x100u : 0u);
+            }
+        }
+    }
+    return nu;
+}
+
 int
 ovhip_rec_cu_inter(ovhip_recorder *r, const ovhip_pu_desc *pu, const ovhip_affine_desc *aff)
 {
@@ -852,12 +1030,32 @@ ovhip_rec_pu(ovhip_recorder *r, const ovhip_pu_desc *pu)
     int dir = pu->inter_dir & 3;
     if (!dir) return OVHIP_EINVAL;
     if (pu->ciip_wt > 3 || (pu->ciip_wt && pu->refine)) return OVHIP_EINVAL;
-    if (pu->refine & OVHIP_PU_GPM) return rec_pu_gpm(r, pu);
+    if (r->n_scaled && (pu->refine & OVHIP_PU_GPM || (pu->refine && (dir & 3) == 3))) {
+        /* rcn_gpm_b always takes rcn_mc_rpr_b_l / _c; DMVR / BDOF read no scale (H.266 disables them under RPR) */
+        const int g0 = slot_scaled(r, pu->ref0), g1 = g0 < 0 ? g0 : slot_scaled(r, pu->ref1);
+        if (pu->refine & OVHIP_PU_GPM) {
+            if (pu->gpm_split_dir > 63 || pu->log2_w < 3 || pu->log2_h < 3 || pu->log2_w > 6 || pu->log2_h > 6) return OVHIP_EINVAL;
+            if (g0 < 0 || g1 < 0) return OVHIP_EUNSUP;
+            if (g0 || g1) return rec_pu_rpr(r, pu, 3, g0, g1);
+        } else if (pu->refine && (dir & 3) == 3) {
+            if (g0 < 0 || g1 < 0) return OVHIP_EUNSUP;
+            if (g0 || g1) return refuse(r, "reference picture resampling: DMVR / BDOF with a scaled reference");
+        }
+    }
+    if (pu->refine & OVHIP_PU_GPM) {
+        if (pu->gpm_split_dir > 63 || pu->log2_w < 3 || pu->log2_h < 3 || pu->log2_w > 6 || pu->log2_h > 6) return OVHIP_EINVAL;
+        return rec_pu_gpm(r, pu);
+    }
     if (pu->refine) return rec_pu_refined(r, pu);
 
     /* rcn_mcp_b: bi with identical motion degenerates to uni-pred from list 1 */
     if (dir == 3 && pu->poc0 == pu->poc1 && pu->mv0x == pu->mv1x && pu->mv0y == pu->mv1y) dir = 2;
     else if (dir != 3 && (dir & 2)) dir = 2;
+    if (r->n_scaled) {
+        const int s0 = (dir & 1) ? slot_scaled(r, pu->ref0) : 0, s1 = (dir & 2) && s0 >= 0 ? slot_scaled(r, pu->ref1) : 0;
+        if (s0 < 0 || s1 < 0) return OVHIP_EUNSUP;
+        if (s0 || s1) return rec_pu_rpr(r, pu, dir, s0, s1);
+    }
 
     /* clip_mv(): keeps the reference window within [-(pb+3), pic+2] of the PU position */
     int32_t x_max = (r->pic_w + 2 - pu->x0) << 4, y_max = (r->pic_h + 2 - pu->y0) << 4;
@@ -917,6 +1115,11 @@ ovhip_rec_affine_cu(ovhip_recorder *r, const ovhip_affine_desc *cu)
     if (!dir || cw < 8 || ch < 8 || !cu->mv0 || !cu->mv1 || cu->mv_stride < (cw >> 2)) return OVHIP_EINVAL;
     if (r->log) ovhip_calllog_affine_(r->log, cu);
     if (dir != 3 && (dir & 2)) dir = 2;
+    if (r->n_scaled) {
+        const int s0 = (dir & 1) ? slot_scaled(r, cu->ref0) : 0, s1 = (dir & 2) && s0 >= 0 ? slot_scaled(r, cu->ref1) : 0;
+        if (s0 < 0 || s1 < 0) return OVHIP_EUNSUP;
+        if (s0 || s1) return refuse(r, "reference picture resampling: affine coding unit with a scaled reference");
+    }
 
     int8_t w0 = 4, w1 = 4;
     if (dir == 3 && cu->bcw_idx_plus1 != 0 && cu->bcw_idx_plus1 != 3) {
@@ -1103,3 +1306,7 @@ ovhip_ciip_weight(int32_t mode_abv, int32_t mode_lft)
 }
 
 ACCESSOR(ovhip_ciip_unit, ovhip_rec_ciip_units, ciip, n_ciip)
+
+_Static_assert(sizeof(ovhip_rpr_side) == 24, "ovhip_rpr_side is 24 bytes");
+_Static_assert(sizeof(ovhip_rpr_unit) == 64, "ovhip_rpr_unit is 64 bytes");
+_Static_assert(sizeof(ovhip_ref_scale) == 20, "ovhip_ref_scale is 20 bytes");

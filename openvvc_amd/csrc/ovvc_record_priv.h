@@ -37,6 +37,10 @@ struct ovhip_recorder {
     int scan_cx, scan_cy; uint32_t scan_deps, region_deps;
     uint16_t *reg_level; size_t cap_reglvl;     /* level of each chroma-scale region (0: derived by the unordered launch) */
     ovhip_calllog *log;                 /* ovhip_rec_set_calllog: every entry-point call is also serialised there */
+    /* reference picture resampling (ovhip_rec_set_ref_scale): per reference-table slot; n_scaled = slots not at the default */
+    ovhip_ref_scale ref_scale[256]; uint32_t n_scaled;
+    ovhip_rpr_unit *rpr; size_t n_rpr, cap_rpr;
+    const char *refusal;                /* reason of the last OVHIP_EUNSUP (ovhip_rec_refusal) */
 };
 
 /* ovvc_calllog.c */
@@ -48,8 +52,10 @@ void ovhip_calllog_region_(ovhip_calllog *l, int32_t x0, int32_t y0, uint32_t ab
 void ovhip_calllog_dbf_(ovhip_calllog *l, const ovhip_dbf_ctu *c);
 void ovhip_calllog_ciip_(ovhip_calllog *l, int32_t x0, int32_t y0, int32_t log2_w, int32_t log2_h, int32_t mode_abv, int32_t mode_lft);
 void ovhip_calllog_ctu_size_(ovhip_calllog *l, int32_t log2_ctu_s);
+void ovhip_calllog_ref_scale_(ovhip_calllog *l, int32_t slot, const ovhip_ref_scale *sc);
 
 int  ovhip_rec_intra_reset_(ovhip_recorder *r);
+void ovhip_rec_rpr_reset_(ovhip_recorder *r);
 void ovhip_rec_intra_free_(ovhip_recorder *r);
 /* recorder-internal: the ordered tasks of one TU, called by ovhip_rec_tu_intra around its transform blocks */
 int  ovhip_rec_itask_add_(ovhip_recorder *r, const ovhip_itask *t, uint16_t extra_level);

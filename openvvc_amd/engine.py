@@ -153,6 +153,15 @@ class Context:
         self._chk(self.lib.ovhip_mc_launch(self.h, C.byref(dst.s), arr, len(refs), units.ptr, n,
                                            lmcs_fwd.ptr if lmcs_fwd else None, C.byref(intra.s) if intra else None), "mc_launch")
 
+    def mc_rpr(self, dst: "DevPic", refs: list, units: "DevBuf", lmcs_fwd: "DevBuf | None" = None, n: int | None = None,
+               intra: "DevPic | None" = None):
+        """Units that read references of another size (ovhip_rpr_unit); each reference keeps its own geometry."""
+        n = units.count if n is None else n
+        arr = (capi.Pic * len(refs))(*[r.s for r in refs])
+        self._chk(self.lib.ovhip_mc_rpr_launch(self.h, C.byref(dst.s), arr, len(refs), units.ptr, n,
+                                               lmcs_fwd.ptr if lmcs_fwd else None, C.byref(intra.s) if intra else None),
+                  "mc_rpr_launch")
+
     def ciip(self, dst: "DevPic", intra: "DevPic", units: "DevBuf", n: int | None = None):
         n = units.count if n is None else n
         self._chk(self.lib.ovhip_ciip_launch(self.h, C.byref(dst.s), C.byref(intra.s), units.ptr, n), "ciip_launch")

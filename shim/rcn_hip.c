@@ -102,6 +102,7 @@ struct hip_entry {
     int whole_pic_entry;                 /* the entry being decoded covers the picture (no tile borders inside)                          */
     int err;
     const OVPicture *refs[16]; int n_refs;
+    uint32_t scale_set;                 /* reference-table slots whose scale this picture already handed to the recorder */
     ovhip_lmcs_luts luts; int have_luts, lmcs_region_live;
     ovhip_sao_ctu *sao; ovhip_alf_ctu *alf; size_t n_ctu; int sao_on, alf_on;
     int16_t alf_cc[2][4][8];
@@ -184,6 +185,8 @@ latch(struct hip_entry *e, int code, const char *what)
 {
     if (code >= 0 || e->err) return;
     e->err = code;
+    /* the recorder says which case of a tool it refused (reference picture resampling with DMVR / BDOF, affine, ...) */
+    if (code == OVHIP_EUNSUP && e->rec && *ovhip_rec_refusal(e->rec)) what = ovhip_rec_refusal(e->rec);
     if (code == OVHIP_EUNSUP) {
         /* a coding tool outside the device set (IBC, reference picture resampling, entry threads > 1): the picture is FAILED -- published
          * as such, so that nobody waits for it -- not reconstructed by a fallback this back-end does not have.  Said once per process in
@@ -236,9 +239,34 @@ ref_slot(struct hip_entry *e, const OVPicture *p)
     return e->n_refs++;
 }
 
+/* ref_slot, plus the slot's scale for reference picture resampling: scale_fact_rpl{list}[ref_idx] (ctudec_compute_refs_scaling,
+ * ctudec.c:43-86), the reference's size and its chroma collocation flags -- read from rpl0[ref_idx] whatever the list, as
+ * rcn_mcp_rpr_c does (rcn_inter.c:2322-2323; the flags are SPS-level).  Unscaled slots of the picture's size keep the recorder's
+ * default; the recorder emits RPR units for the others or refuses what the device path does not take. */
+static int
+ref_slot_scaled(struct hip_entry *e, const OVCTUDec *c, const OVPicture *p, int list, int ref_idx)
+{
+    const int k = ref_slot(e, p);
+    const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
+    const uint16_t *sf = list ? ic->scale_fact_rpl1[ref_idx & 15] : ic->scale_fact_rpl0[ref_idx & 15];
+    const OVFrame *f = p->frame;
+    if (k < 0 || k >= 32 || ((e->scale_set >> k) & 1) || !f) return k;
+    if (sf[0] != (1 << RPR_SCALE_BITS) || sf[1] != (1 << RPR_SCALE_BITS) || (int)f->width != e->pic_w || (int)f->height != e->pic_h) {
+        const OVPicture *q = ic->rpl0[ref_idx & 15] ? ic->rpl0[ref_idx & 15] : p;
+        ovhip_ref_scale s;
+        memset(&s, 0, sizeof(s));
+        s.scale_hor = sf[0]; s.scale_ver = sf[1];
+        s.ref_w = (int32_t)f->width; s.ref_h = (int32_t)f->height;
+        s.chroma_hor_col_flag = q->scale_info.chroma_hor_col_flag; s.chroma_ver_col_flag = q->scale_info.chroma_ver_col_flag;
+        latch(e, ovhip_rec_set_ref_scale(e->rec, k, &s), "ovhip_rec_set_ref_scale");
+    }
+    e->scale_set |= 1u << k;
+    return k;
+}
+
 static void
-fill_pu(struct hip_entry *e, const OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0, int log2_w, int log2_h, int inter_dir,
-        OVMV mv0, OVMV mv1, const OVPicture *p0, const OVPicture *p1)
+fill_pu_lists(struct hip_entry *e, const OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0, int log2_w, int log2_h, int inter_dir,
+              OVMV mv0, OVMV mv1, const OVPicture *p0, const OVPicture *p1, int list0, int list1)
 {
     const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
     const int l2 = c->part_ctx->log2_ctu_s;
@@ -252,14 +280,18 @@ fill_pu(struct hip_entry *e, const OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0
     d->planes = 3;
     d->lmcs = c->lmcs_info.lmcs_enabled_flag;
     d->mv0x = mv0.x; d->mv0y = mv0.y; d->mv1x = mv1.x; d->mv1y = mv1.y;
-    /* reference picture resampling (rcn_mcp_rpr_*, rcn_inter.c:2769-2800): not on the device path */
-    if (((inter_dir & 1) && (ic->scale_fact_rpl0[mv0.ref_idx & 15][0] != (1 << RPR_SCALE_BITS) || ic->scale_fact_rpl0[mv0.ref_idx & 15][1] != (1 << RPR_SCALE_BITS)))
-        || ((inter_dir & 2) && (ic->scale_fact_rpl1[mv1.ref_idx & 15][0] != (1 << RPR_SCALE_BITS) || ic->scale_fact_rpl1[mv1.ref_idx & 15][1] != (1 << RPR_SCALE_BITS))))
-        latch(e, OVHIP_EUNSUP, "reference picture resampling (scaled reference picture)");
-    if (p0 && (inter_dir & 1)) { d->poc0 = p0->poc; d->ref0 = (uint8_t)ref_slot(e, p0); }
-    if (p1 && (inter_dir & 2)) { d->poc1 = p1->poc; d->ref1 = (uint8_t)ref_slot(e, p1); }
+    /* reference picture resampling (rcn_mcp_rpr_*, rcn_inter.c:2769-2800): the slot's scale goes to the recorder with the slot */
+    if (p0 && (inter_dir & 1)) { d->poc0 = p0->poc; d->ref0 = (uint8_t)ref_slot_scaled(e, c, p0, list0, mv0.ref_idx); }
+    if (p1 && (inter_dir & 2)) { d->poc1 = p1->poc; d->ref1 = (uint8_t)ref_slot_scaled(e, c, p1, list1, mv1.ref_idx); }
     if (inter_dir == 1) { d->ref1 = d->ref0; d->poc1 = d->poc0 + 1; }      /* keep the identical-motion test off */
     if (inter_dir == 2) { d->ref0 = d->ref1; d->poc0 = d->poc1 + 1; }
+}
+
+static void
+fill_pu(struct hip_entry *e, const OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0, int log2_w, int log2_h, int inter_dir,
+        OVMV mv0, OVMV mv1, const OVPicture *p0, const OVPicture *p1)
+{
+    fill_pu_lists(e, c, d, x0, y0, log2_w, log2_h, inter_dir, mv0, mv1, p0, p1, 0, 1);
 }
 
 static void pend_close(struct hip_entry *e, OVCTUDec *c);
@@ -699,8 +731,8 @@ pend_close(struct hip_entry *e, OVCTUDec *c)
         d.lmcs = c->lmcs_info.lmcs_enabled_flag;
         const OVPicture *p0 = (e->pend.inter_dir & 1) ? ic->rpl0[e->pend.ref_idx0] : NULL;
         const OVPicture *p1 = (e->pend.inter_dir & 2) ? ic->rpl1[e->pend.ref_idx1] : NULL;
-        if (p0) { d.ref0 = (uint8_t)ref_slot(e, p0); d.poc0 = p0->poc; }
-        if (p1) { d.ref1 = (uint8_t)ref_slot(e, p1); d.poc1 = p1->poc; }
+        if (p0) { d.ref0 = (uint8_t)ref_slot_scaled(e, c, p0, 0, e->pend.ref_idx0); d.poc0 = p0->poc; }
+        if (p1) { d.ref1 = (uint8_t)ref_slot_scaled(e, c, p1, 1, e->pend.ref_idx1); d.poc1 = p1->poc; }
         if (!p0) { d.ref0 = d.ref1; d.poc0 = d.poc1 + 1; }
         if (!p1) { d.ref1 = d.ref0; d.poc1 = d.poc0 + 1; }
         d.mv_stride = 32; d.mv0 = e->pend.mv0; d.mv1 = e->pend.mv1;
@@ -941,8 +973,8 @@ hip_rcn_affine_cu(OVCTUDec *const c, struct InterDRVCtx *const ic, uint8_t x0, u
     d.inter_dir = inter_dir; d.bcw_idx_plus1 = b0->bcw_idx_plus1; d.prof_dir = prof_dir;
     d.lmcs = c->lmcs_info.lmcs_enabled_flag;
     const OVPicture *p0 = (inter_dir & 1) ? ic->rpl0[ref_idx0] : NULL, *p1 = (inter_dir & 2) ? ic->rpl1[ref_idx1] : NULL;
-    if (p0) { d.ref0 = (uint8_t)ref_slot(e, p0); d.poc0 = p0->poc; }
-    if (p1) { d.ref1 = (uint8_t)ref_slot(e, p1); d.poc1 = p1->poc; }
+    if (p0) { d.ref0 = (uint8_t)ref_slot_scaled(e, c, p0, 0, ref_idx0); d.poc0 = p0->poc; }
+    if (p1) { d.ref1 = (uint8_t)ref_slot_scaled(e, c, p1, 1, ref_idx1); d.poc1 = p1->poc; }
     if (!p0) { d.ref0 = d.ref1; d.poc0 = d.poc1 + 1; }
     if (!p1) { d.ref1 = d.ref0; d.poc1 = d.poc0 + 1; }
     d.mv_stride = 32; d.mv0 = e->pend.mv0; d.mv1 = e->pend.mv1;
@@ -1013,7 +1045,7 @@ hip_rcn_gpm_b(OVCTUDec *const c, struct VVCGPM *g, int x0, int y0, int log2_pb_w
     const OVPicture *p0 = g->inter_dir0 == 1 ? ic->rpl0[g->mv0.ref_idx] : ic->rpl1[g->mv0.ref_idx];
     const OVPicture *p1 = g->inter_dir1 == 1 ? ic->rpl0[g->mv1.ref_idx] : ic->rpl1[g->mv1.ref_idx];
     ovhip_pu_desc d;
-    fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, 3, g->mv0, g->mv1, p0, p1);
+    fill_pu_lists(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, 3, g->mv0, g->mv1, p0, p1, g->inter_dir0 == 1 ? 0 : 1, g->inter_dir1 == 1 ? 0 : 1);
     d.bcw_idx_plus1 = 0;
     d.refine = OVHIP_PU_GPM; d.gpm_split_dir = (uint8_t)g->split_dir;
     latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(gpm)");
@@ -1674,6 +1706,7 @@ begin_picture(struct hip_entry *e, const OVFrame *f, const struct RectEntryInfo 
     e->ctus_left = nw * nh;
     e->err = 0;
     e->n_refs = 0;
+    e->scale_set = 0;
     e->sao_on = e->alf_on = 0;
     e->lmcs_region_live = 0;
     e->n_refined = 0; e->dmvr_done = 0; e->row_mark = 0;
