@@ -1425,7 +1425,9 @@ extern "C" int ovhip_intra_ctu_launch(ovhip_ctx *ctx, const ovhip_pic *pic, cons
 // (<= cap) or 0 when the picture cannot take this path (more tasks or strips than an item word holds).  (Until round 5 a prediction
 // block less than a unit high -- horizontal ISP partitions of 1 or 2 rows, which share a state word with the partitions around them --
 // sent the whole picture to the per-level launches; they now hand over inside the unit by tagged samples, see k_intra_flow.)
-extern "C" size_t ovhip_intra_flow_items(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap)
+// ovhip_intra_flow_items_ (internal, ovvc_picture.hip): the count even where it exceeds cap -- only the first cap items are written,
+// items may be null with cap 0 -- and 0 only where the path is refused.  The count does not depend on the order of the tasks.
+extern "C" size_t ovhip_intra_flow_items_(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap)
 {
     size_t k = 0;
     for (size_t i = 0; sorted && i < n; ++i) {
@@ -1437,6 +1439,12 @@ extern "C" size_t ovhip_intra_flow_items(const ovhip_itask *sorted, size_t n, ui
         for (int st = 0; st < strips; ++st)
             for (int c = 0; c < comps; ++c) { if (k < cap) items[k] = (uint32_t)i | ((uint32_t)st << 24) | ((uint32_t)c << 29); ++k; }
     }
+    return k;
+}
+
+extern "C" size_t ovhip_intra_flow_items(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap)
+{
+    const size_t k = ovhip_intra_flow_items_(sorted, n, items, cap);
     return k <= cap ? k : 0;
 }
 

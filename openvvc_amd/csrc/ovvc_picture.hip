@@ -34,10 +34,6 @@ static const ovhip_pic *same_size_refs(const ovhip_pic *geom, const ovhip_pic *r
     return any ? out : refs;
 }
 
-
-// layout of the parameter block (one pinned staging copy, one H2D)
-struct ParamLayout { size_t sao, alf_ctus, lcoef, lclip, ccoef, cclip, cc, fwd, bwd, total; };
-
 } // namespace
 
 struct ovhip_job {
@@ -50,7 +46,7 @@ struct ovhip_job {
     ovhip_pic res;                       // residuals of the ordered tasks (allocated with the first picture that has any)
     uint32_t *d_sync; uint32_t epoch;    // CTU flags of the one-launch ordered pass (zeroed once; a new epoch per picture)
     uint32_t *d_flow;                    // unit state words of the flow launch (zeroed once)
-    uint32_t *items_host; size_t items_cap;   // pinned: items of the flow launch
+    uint32_t *items_host; size_t items_cap;   // pinned: items of the flow launch (items_cap in bytes)
     uint32_t *abort_host;                // pinned word the ordered pass writes when a bounded wait expired
     char *param_host; size_t param_cap;  // pinned staging of the picture-level tables
     int32_t *mv_host; size_t mv_cap;     // pinned: refined vectors, 4 int32 per refined unit
@@ -64,7 +60,6 @@ struct ovhip_job {
     size_t rows_end; int rows_pending;   // an eager pass is in flight: it covers [.., rows_end), ev_rows follows its copies
     hipEvent_t ev_rows;
     hipEvent_t ev_h2d, ev_done;
-    hipStream_t up;                      // uploads on one of the device's shared upload streams (upload_stream_for): up != NULL during such a flush
     int flow_on_device;                  // the last full flush uploaded the flow launch's item list (a resident replay may use it)
     int flushed;                         // ev_* recorded at least once
     const void *packed_prev[24];         // where the last full flush placed the arrays that rode in the parameter block
@@ -177,13 +172,13 @@ static int upload_stream_count()
     return __atomic_load_n(&g_up_n, __ATOMIC_RELAXED);
 }
 
-int h2d(ovhip_job *j, int k, const void *host, size_t bytes)
+int h2d(ovhip_job *j, hipStream_t st, int k, const void *host, size_t bytes)
 {
     if (!bytes) return OVHIP_OK;
     if (j->resident) return j->dev[k].cap >= bytes ? OVHIP_OK : ov_fail(j->ctx, OVHIP_EINVAL, "resident flush before a full one", hipSuccess);
     int r = dev_reserve(j, k, bytes);
     if (r) return r;
-    OV_HIP(j->ctx, hipMemcpyAsync(j->dev[k].p, host, bytes, hipMemcpyHostToDevice, j->up ? j->up : j->ctx->stream));
+    OV_HIP(j->ctx, hipMemcpyAsync(j->dev[k].p, host, bytes, hipMemcpyHostToDevice, st));
     j->st.h2d_bytes += bytes; j->st.n_h2d++;
     return OVHIP_OK;
 }
@@ -203,6 +198,10 @@ int pinned_reserve(ovhip_job *j, void **p, size_t *cap, size_t bytes)
 extern "C" const ovhip_tb_cmd *ovhip_rec_tb_cmds_split_tiny_(ovhip_recorder *r, size_t counts[4], size_t tiny[4][4], size_t *n);
 extern "C" int ovhip_itx_launch_ex_(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *res, const ovhip_tb_cmd *d_cmds, uint32_t n_large,
                                     uint32_t n_small, const uint32_t tiny3[4], const int16_t *d_coefs, const int16_t *d_lmcs_scales, const uint16_t *d_bwd_lut);
+
+extern "C" int ovhip_sao_launch_rows(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *src, const ovhip_sao_ctu *d_params, int32_t log2_ctu_s, int32_t row0, int32_t row1);
+extern "C" int ovhip_alf_launch_rows(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *src, const ovhip_alf_pic *alf, int32_t row0, int32_t row1);
+extern "C" size_t ovhip_intra_flow_items_(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap);
 
 #define CHK(x) do { int r__ = (x); if (r__ != OVHIP_OK) return r__; } while (0)
 
@@ -236,7 +235,7 @@ struct StageTimer {
     ovhip_job *j; int k;
     StageTimer(ovhip_job *job, int stage) : j(job), k(-1)
     {
-        if (j->t_stage != stage) return;
+        if (!j || j->t_stage != stage) return;
         k = j->t_next; j->t_next = (j->t_next + 1) % 32;
         if (t_collect(j, k) != OVHIP_OK || hipEventRecord(j->t_ev[k][0], j->ctx->stream) != hipSuccess) k = -1;
     }
@@ -246,15 +245,240 @@ struct StageTimer {
     }
 };
 
-// plane-wise device copy (the two pictures may come from different allocators)
-int copy_pic(ovhip_ctx *ctx, const ovhip_pic *d, const ovhip_pic *s)
+// rows [r0, r1) of every plane (chroma: r0 / 2 .. r1 / 2), one 2-D copy per plane (the two pictures may come from different allocators)
+int copy_rows(ovhip_ctx *ctx, const ovhip_pic *d, const ovhip_pic *s, int32_t r0, int32_t r1)
 {
     uint16_t *dp[3] = { d->y, d->cb, d->cr };
     uint16_t *sp[3] = { s->y, s->cb, s->cr };
     for (int p = 0; p < 3; ++p) {
-        const int w = p ? d->w / 2 : d->w, h = p ? d->h / 2 : d->h;
-        OV_HIP(ctx, hipMemcpy2DAsync(dp[p], (size_t)(p ? d->stride_c : d->stride_y) * 2, sp[p], (size_t)(p ? s->stride_c : s->stride_y) * 2,
-                                     (size_t)w * 2, h, hipMemcpyDeviceToDevice, ctx->stream));
+        const size_t ds = p ? d->stride_c : d->stride_y, ss = p ? s->stride_c : s->stride_y;
+        const int32_t a = p ? r0 / 2 : r0, b = p ? r1 / 2 : r1;
+        OV_HIP(ctx, hipMemcpy2DAsync(dp[p] + a * ds, ds * 2, sp[p] + a * ss, ss * 2, (size_t)(p ? d->w / 2 : d->w) * 2, b - a,
+                                     hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return OVHIP_OK;
+}
+
+// device state words of the ordered pass (d_flow, d_sync), zeroed once
+int state_words(ovhip_job *j, uint32_t **words, size_t n)
+{
+    if (*words) return OVHIP_OK;
+    OV_HIP(j->ctx, hipMalloc((void **)words, n * sizeof(uint32_t)));
+    OV_HIP(j->ctx, hipMemsetAsync(*words, 0, n * sizeof(uint32_t), j->ctx->stream));
+    return OVHIP_OK;
+}
+
+// before an ordered pass whose workgroups wait for each other (the flow launch, the one-launch pass): its state words, the pinned word
+// it writes when a bounded wait expired, and this picture's epoch
+int ordered_arm(ovhip_job *j, uint32_t **words, size_t n)
+{
+    CHK(state_words(j, words, n));
+    if (!j->abort_host) {
+        j->abort_host = (uint32_t *)pinned_alloc(nullptr, 64);
+        if (!j->abort_host) return ov_fail(j->ctx, OVHIP_ENOMEM, "pinned abort word", hipSuccess);
+        *j->abort_host = 0;
+    }
+    if (++j->epoch >= 0x7ffffff0u) j->epoch = 1;
+    return OVHIP_OK;
+}
+
+// No more workers than a flow launch's widest level can use (round 4): a worker beyond that only ever holds an item that is levels ahead
+// of the front -- and its wave slot, registers and LDS are then missing to the kernels of the pictures beside it for as long as the pass
+// runs.  Twice the widest level, in multiples of 64.
+int flow_widest(const ovhip_itask *sorted, const uint32_t *items, size_t n_items)
+{
+    size_t widest = 0, run = 0;
+    for (size_t q = 0; q < n_items; ++q) {
+        run = (q && sorted[items[q] & 0xffffff].level == sorted[items[q - 1] & 0xffffff].level) ? run + 1 : 1;
+        if (run > widest) widest = run;
+    }
+    return (int)((2 * widest + 63) & ~(size_t)63);
+}
+
+// the refined vectors of the units [first, n) as entries of the picture's collocated motion plane (4 per unit, recorder order), stored
+// into the page-locked array the host reads; d_units / d_mv: the device copies of the units and their vectors, at index first
+int tmvp_cells(ovhip_job *j, const ovhip_mc_unit *d_units, const int32_t *d_mv, size_t first, size_t n, int log2_ctu)
+{
+    ovhip_tmvp_cell *d_cells = (ovhip_tmvp_cell *)j->dev[B_TMVP].p + 4 * first;
+    CHK(ovhip_tmvp_cells_launch(j->ctx, d_units, (uint32_t)(n - first), d_mv, log2_ctu, (j->w + (1 << log2_ctu) - 1) >> log2_ctu, d_cells));
+    CHK(store_host(j->ctx, j->tmvp_host + 4 * first, d_cells, 4 * (n - first) * sizeof(ovhip_tmvp_cell)));
+    j->n_tmvp = 4 * n;
+    return OVHIP_OK;
+}
+
+// a staging block in 256-byte slots (one pinned block, one H2D)
+struct Layout {
+    size_t o = 0;
+    size_t put(size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; }
+};
+
+// the picture-level tables: ALF luma coefficients / clipping values, chroma coefficients / clipping values, CC-ALF coefficients, the LMCS
+// forward / inverse LUTs -- their slots in a staging block, their fill, the ALF launch's view of them at the block's device address
+enum { T_LCOEF, T_LCLIP, T_CCOEF, T_CCLIP, T_CC, T_FWD, T_BWD, T_COUNT };
+struct Tables { size_t at[T_COUNT]; };
+static const size_t TABLE_BYTES[T_COUNT] = { 24 * OVHIP_ALF_LUMA_SET_SIZE * 2, 24 * OVHIP_ALF_LUMA_SET_SIZE * 2, 8 * 7 * 2, 8 * 7 * 2, 2 * 4 * 8 * 2, 2048, 2048 };
+
+Tables tables_put(Layout &L, bool alf, bool lmcs)
+{
+    Tables t;
+    for (int k = 0; k < T_COUNT; ++k) t.at[k] = L.put((k < T_FWD ? alf : lmcs) ? TABLE_BYTES[k] : 0);
+    return t;
+}
+
+void tables_fill(char *h, const Tables &t, const ovhip_job_params *pr, bool alf, bool lmcs)
+{
+    const void *src[T_COUNT] = { pr->alf_luma_coeff, pr->alf_luma_clip, pr->alf_chroma_coeff, pr->alf_chroma_clip, pr->alf_cc_coeff,
+                                 lmcs ? pr->lmcs->fwd_lut : nullptr, lmcs ? pr->lmcs->bwd_lut : nullptr };
+    for (int k = 0; k < T_COUNT; ++k) if (k < T_FWD ? alf : lmcs) memcpy(h + t.at[k], src[k], TABLE_BYTES[k]);
+}
+
+ovhip_alf_pic alf_pic_at(const char *d, const Tables &t, const ovhip_alf_ctu *ctus, uint8_t *class_scratch, int log2_ctu)
+{
+    auto tab = [&](int k) { return (const int16_t *)(d + t.at[k]); };
+    return ovhip_alf_pic{ ctus, tab(T_LCOEF), tab(T_LCLIP), tab(T_CCOEF), tab(T_CCLIP), tab(T_CC), class_scratch, log2_ctu };
+}
+
+// ---- the launch chain, one implementation for ovhip_job_flush (the whole picture) and ovhip_job_band (a band of CTU rows) ----
+// What one submission reads.  Device pointers are rebased to the recorder's indexing: the commands' own indices (coefficient / side-arena
+// offsets, region numbers) stay what the recorder wrote, and a band's slice is addressed through a pointer moved back by its first index.
+struct Chain {
+    ovhip_job *j;
+    ovhip_job *timer;                     // whose ovhip_job_time_stage brackets the launch groups (nullptr: none; band-wise submission)
+    const ovhip_pic *dst, *res;           // res: where the residuals of the ordered tasks wait for their prediction, or nullptr
+    int log2_ctu;
+    const ovhip_lmcs_luts *luts; const uint16_t *d_fwd; int16_t *d_scales;
+    const ovhip_mc_unit *d_mc, *d_mcx; uint32_t n_mc, n_mcx;
+    const ovhip_aff_unit *d_aff; uint32_t n_aff; const int32_t *d_side;
+    const ovhip_rpr_unit *d_rpr; uint32_t n_rpr;                      // units that read a reference of another size (k_mc_rpr)
+    const ovhip_tb_cmd *d_tb; size_t cls[4], tiny[4][4]; const int16_t *d_coef;
+    const ovhip_lmcs_region *d_reg; uint32_t reg0, n_reg;             // this submission's regions: [reg0, reg0 + n_reg)
+    const ovhip_itask *d_it, *h_it; uint32_t n_it;                    // the level-sorted tasks (h_it: host copy, level geometry)
+    const uint32_t *lv_start; uint32_t n_lv;
+    const uint32_t *d_items; uint32_t n_items;                        // n_items != 0: a flow launch runs the ordered pass
+    int prepared;                                                     // (chain_residual) the chroma-scale launch prepared the flow state
+};
+
+// prediction: MC with the units that read a scaled reference beside it (disjoint blocks), then refined / affine MC.  refs: the reference
+// table of k_mc_rpr; refs_same: the same with a same-size stand-in for every scaled reference (same_size_refs).  intra: the picture with
+// the CIIP units' intra prediction, or nullptr.  d_mv: where k_mcxa leaves the refined vectors.
+int chain_predict(const Chain &c, const ovhip_pic *refs_same, const ovhip_pic *refs, uint32_t n_refs, const ovhip_pic *intra, int32_t *d_mv)
+{
+    ovhip_job *j = c.j;
+    {
+        StageTimer t_(c.timer, OVHIP_TIME_MC);
+        CHK(ovhip_mc_launch(j->ctx, c.dst, refs_same, n_refs, c.d_mc, c.n_mc, c.d_fwd, intra));
+        if (c.n_rpr) CHK(ovhip_mc_rpr_launch(j->ctx, c.dst, refs, n_refs, c.d_rpr, c.n_rpr, c.d_fwd, intra));
+    }
+    j->st.n_launches += (c.n_mc != 0) + (c.n_rpr != 0);
+    if (c.n_mcx || c.n_aff) {
+        StageTimer t_(c.timer, OVHIP_TIME_MCXA);
+        CHK(ovhip_mcxa_launch(j->ctx, c.dst, refs_same, n_refs, c.d_mcx, c.n_mcx, d_mv, c.d_aff, c.n_aff, c.d_side, c.d_fwd));
+        j->st.n_launches++;
+    }
+    return OVHIP_OK;
+}
+
+// residual: luma blocks, the chroma-scale derivation on the reconstructed luma (before a flow launch: the launch that also prepares its
+// state words), chroma blocks.  d_bwd: the inverse luma mapping follows at once (no ordered pass keeps the luma mapped) -- inside the
+// chroma launch where that has blocks
+int chain_residual(Chain &c, const uint16_t *d_bwd)
+{
+    ovhip_job *j = c.j;
+    ovhip_ctx *ctx = j->ctx;
+    const uint32_t t_luma[4] = { (uint32_t)c.tiny[1][0], (uint32_t)c.tiny[1][1], (uint32_t)c.tiny[1][2], (uint32_t)c.tiny[1][3] };
+    const uint32_t t_chroma[4] = { (uint32_t)c.tiny[3][0], (uint32_t)c.tiny[3][1], (uint32_t)c.tiny[3][2], (uint32_t)c.tiny[3][3] };
+    if (c.cls[0] + c.cls[1]) {
+        StageTimer t_(c.timer, OVHIP_TIME_ITX_LUMA);
+        CHK(ovhip_itx_launch_ex_(ctx, c.dst, c.res, c.d_tb, (uint32_t)c.cls[0], (uint32_t)c.cls[1], t_luma, c.d_coef, nullptr, nullptr));
+        j->st.n_launches++;
+    }
+    if (c.n_reg) {
+        if (!c.luts) return ov_fail(ctx, OVHIP_EINVAL, "chroma-scale regions recorded without LMCS tables", hipSuccess);
+        StageTimer t_(c.timer, OVHIP_TIME_LMCS_SCALE);
+        if (c.n_items) {
+            CHK(ovhip_lmcs_scale_prepare_launch(ctx, c.dst, c.d_reg + c.reg0, c.n_reg, c.luts, c.d_scales + c.reg0, c.d_it, c.n_it, j->d_flow, j->epoch));
+            c.prepared = 1;
+        } else CHK(ovhip_lmcs_scale_launch(ctx, c.dst, c.d_reg + c.reg0, c.n_reg, c.luts, c.d_scales + c.reg0));
+        j->st.n_launches++;
+    }
+    const ovhip_tb_cmd *d_tbc = c.d_tb + c.cls[0] + c.cls[1];
+    StageTimer t_(c.timer, OVHIP_TIME_ITX_CHROMA);
+    if (d_bwd && c.cls[3]) {
+        CHK(ovhip_itx_launch_ex_(ctx, c.dst, nullptr, d_tbc, (uint32_t)c.cls[2], (uint32_t)c.cls[3], t_chroma, c.d_coef, c.d_scales, d_bwd));
+        j->st.n_launches++;
+        return OVHIP_OK;
+    }
+    if (c.cls[2] + c.cls[3]) {
+        CHK(ovhip_itx_launch_ex_(ctx, c.dst, c.res, d_tbc, (uint32_t)c.cls[2], (uint32_t)c.cls[3], t_chroma, c.d_coef, c.d_scales, nullptr));
+        j->st.n_launches++;
+    }
+    if (d_bwd) { CHK(ovhip_lmcs_inverse_launch(ctx, c.dst, d_bwd)); j->st.n_launches++; }
+    return OVHIP_OK;
+}
+
+// ordered pass: ONE flow launch of n_workers persistent workers, or one launch per level (the launch boundary is the inter-level
+// synchronisation)
+int chain_ordered(const Chain &c, int n_workers)
+{
+    ovhip_job *j = c.j;
+    if (c.n_items) {
+        CHK(ovhip_intra_flow_launch(j->ctx, c.dst, c.res, c.d_it, c.n_it, c.d_items, c.n_items, c.d_reg, c.luts, c.d_scales, c.log2_ctu,
+                                    j->d_flow, j->epoch, j->abort_host, !c.prepared, n_workers));
+        j->st.n_launches += 1 + !c.prepared;
+        return OVHIP_OK;
+    }
+    for (uint32_t l = 0; l < c.n_lv; ++l) {
+        const uint32_t a = c.lv_start[l], b = c.lv_start[l + 1];
+        if (b > a) {
+            CHK(ovhip_intra_level_launch(j->ctx, c.dst, c.res, c.d_it + a, b - a, c.d_reg, c.luts, c.d_scales, c.log2_ctu,
+                                         ovhip_intra_level_geom(c.h_it + a, b - a)));
+            j->st.n_launches++;
+        }
+    }
+    return OVHIP_OK;
+}
+
+// tail, first half: the inverse luma mapping of rows [row0, row1) (d_bwd), which also drops the flow launches' hand-over bit -- or,
+// without it, the un-tag alone.  d_it[n_tagged]: the tasks whose samples still carry the bit.
+int chain_unmap(ovhip_job *j, const ovhip_pic *dst, int32_t row0, int32_t row1, const uint16_t *d_bwd, const ovhip_itask *d_it, uint32_t n_tagged)
+{
+    if (d_bwd) {
+        ovhip_pic view = *dst;                                // the luma rows; the chroma un-tag takes picture coordinates
+        view.y = dst->y + (size_t)row0 * dst->stride_y; view.h = row1 - row0;
+        CHK(ovhip_lmcs_inverse_untag_launch(j->ctx, &view, d_bwd, d_it, n_tagged));
+    } else if (n_tagged) CHK(ovhip_intra_flow_untag_launch(j->ctx, dst, d_it, n_tagged, 1));
+    else return OVHIP_OK;
+    j->st.n_launches++;
+    return OVHIP_OK;
+}
+
+// tail, second half: the deblocking of the edge lists (vertical, then horizontal)
+int chain_deblock(const Chain &c, const ovhip_dbf_edge *d_ev, uint32_t n_ev, const ovhip_dbf_edge *d_eh, uint32_t n_eh, const ovhip_dbf_offsets *offs)
+{
+    StageTimer t_(c.timer, OVHIP_TIME_DBF);
+    CHK(ovhip_dbf_launch_edges_ex(c.j->ctx, c.dst, d_ev, n_ev, d_eh, n_eh, offs));
+    c.j->st.n_launches += (n_ev != 0) + (n_eh != 0);
+    return OVHIP_OK;
+}
+
+// filters: SAO rows [s0, s1) into tmp, ALF rows [a0, a1) back into dst (d_sao / alf: nullptr when off; their CTU tables indexed from
+// the picture's first CTU row).  With only one of the two on, a copy of the rows stands in for the other, so that dst holds the result.
+int chain_filters(const Chain &c, const ovhip_sao_ctu *d_sao, const ovhip_alf_pic *alf, int32_t s0, int32_t s1, int32_t a0, int32_t a1)
+{
+    ovhip_job *j = c.j;
+    if (s1 > s0) {
+        if (d_sao) {
+            StageTimer t_(c.timer, OVHIP_TIME_SAO);
+            CHK(ovhip_sao_launch_rows(j->ctx, &j->tmp, c.dst, d_sao, c.log2_ctu, s0, s1));
+            j->st.n_launches++;
+        } else if (alf) CHK(copy_rows(j->ctx, &j->tmp, c.dst, s0, s1));
+    }
+    if (a1 > a0) {
+        if (alf) {
+            StageTimer t_(c.timer, OVHIP_TIME_ALF);
+            CHK(ovhip_alf_launch_rows(j->ctx, c.dst, &j->tmp, alf, a0, a1));
+            j->st.n_launches++;
+        } else if (d_sao) CHK(copy_rows(j->ctx, c.dst, &j->tmp, a0, a1));
     }
     return OVHIP_OK;
 }
@@ -331,12 +555,7 @@ int ovhip_job_reserve_for_picture(ovhip_job *j)
     CHK(pinned_reserve(j, (void **)&j->param_host, &j->param_cap, P / 2 + ((size_t)2 << 20)));
     CHK(pinned_reserve(j, (void **)&j->mv_host, &j->mv_cap, (P / 256 + 1024) * 16));
     CHK(pinned_reserve(j, (void **)&j->tmvp_host, &j->tmvp_cap, 4 * (P / 256 + 1024) * sizeof(ovhip_tmvp_cell)));
-    if (j->items_cap < P / 32 + 1024) {
-        pinned_free(nullptr, j->items_host);
-        j->items_cap = P / 32 + 1024;
-        j->items_host = (uint32_t *)pinned_alloc(nullptr, j->items_cap * sizeof(uint32_t));
-        if (!j->items_host) { j->items_cap = 0; return ov_fail(j->ctx, OVHIP_ENOMEM, "ovhip_job_reserve_for_picture: item list", hipSuccess); }
-    }
+    CHK(pinned_reserve(j, (void **)&j->items_host, &j->items_cap, (P / 32 + 1024) * sizeof(uint32_t)));
     if (!j->res.y) CHK(ovhip_pic_alloc(j->ctx, j->w, j->h, &j->res));
     return OVHIP_OK;
 }
@@ -522,15 +741,8 @@ int64_t ovhip_job_dmvr_rows_begin_upto(ovhip_job *j, const ovhip_pic *refs, uint
         CHK(ovhip_dmvr_search_launch(ctx, &geom, same_size_refs(&geom, refs, n_refs, same), n_refs, (const ovhip_mc_unit *)d_units,
                                      (uint32_t)(n - first), d_mv));
         CHK(store_host(ctx, j->mv_host + 4 * first, d_mv, (n - first) * 16));
-        if (log2_ctu_s) {
-            // the same vectors as entries of the picture's collocated motion plane: what the caller patches before it publishes
-            // the row (4 entries per unit, recorder order)
-            ovhip_tmvp_cell *d_cells = (ovhip_tmvp_cell *)j->dev[B_TMVP].p + 4 * first;
-            CHK(ovhip_tmvp_cells_launch(ctx, (const ovhip_mc_unit *)d_units, (uint32_t)(n - first), d_mv, log2_ctu_s,
-                                        (j->w + (1 << log2_ctu_s) - 1) >> log2_ctu_s, d_cells));
-            CHK(store_host(ctx, j->tmvp_host + 4 * first, d_cells, 4 * (n - first) * sizeof(ovhip_tmvp_cell)));
-            j->n_tmvp = 4 * n;
-        }
+        // the same vectors as entries of the picture's collocated motion plane: what the caller patches before it publishes the row
+        if (log2_ctu_s) CHK(tmvp_cells(j, (const ovhip_mc_unit *)d_units, d_mv, first, n, log2_ctu_s));
         OV_HIP(ctx, hipEventRecord(j->ev_rows, ctx->stream));
         j->rows_pending = 1;
     }
@@ -550,9 +762,6 @@ int64_t ovhip_job_dmvr_rows(ovhip_job *j, const ovhip_pic *refs, uint32_t n_refs
     const int64_t n = ovhip_job_dmvr_rows_begin(j, refs, n_refs, 0);
     return n < 0 ? n : ovhip_job_dmvr_rows_collect(j);
 }
-
-static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs, const ovhip_pic *intra,
-                          const ovhip_job_params *pr);
 
 int ovhip_job_flush(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs, const ovhip_pic *intra,
                     const ovhip_job_params *pr)
@@ -633,19 +842,19 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
                        : ovhip_rec_itasks_by_ctu(rec, pr->log2_ctu_s ? pr->log2_ctu_s : 7, &n_it, &ictu, &n_ictu);
     size_t n_items = 0;
     if (by_flow && n_it) {
-        if (j->items_cap < 4 * n_it + 16) {
-            pinned_free(nullptr, j->items_host);
-            j->items_cap = 8 * n_it + 1024;
-            j->items_host = (uint32_t *)pinned_alloc(nullptr, j->items_cap * sizeof(uint32_t));
-            if (!j->items_host) { j->items_cap = 0; return ov_fail(ctx, OVHIP_ENOMEM, "ovhip_job_flush: item list", hipSuccess); }
+        // (the count comes back even where the list does not fit: it grows to that)
+        n_items = ovhip_intra_flow_items_(it, n_it, j->items_host, j->items_cap / sizeof(uint32_t));
+        if (n_items > j->items_cap / sizeof(uint32_t)) {
+            CHK(pinned_reserve(j, (void **)&j->items_host, &j->items_cap, n_items * sizeof(uint32_t)));
+            n_items = ovhip_intra_flow_items_(it, n_it, j->items_host, n_items);
         }
-        n_items = ovhip_intra_flow_items(it, n_it, j->items_host, j->items_cap);
         if (!n_items) by_flow = 0;           // more tasks / strips than an item word holds: per-level launches
     }
     if (!it && ovhip_rec_itask_levels(rec)) return ov_fail(ctx, OVHIP_ENOMEM, "ovhip_job_flush: sorting the ordered tasks", hipSuccess);
     if (!by_level) n_lv = ovhip_rec_itask_levels(rec);
     if (!(stages & OVHIP_STAGE_INTRA)) { n_it = 0; n_lv = 0; n_ictu = 0; }
     const int ordered = n_it != 0;       // a picture with an ordered pass keeps its luma in the mapped domain until the pass has run
+    const bool flow = (stages & OVHIP_STAGE_INTRA) && by_flow && n_items;       // the ordered pass as ONE flow launch
     if (ordered && !j->res.y) CHK(ovhip_pic_alloc(ctx, j->w, j->h, &j->res));
     if (ordered && (dst->stride_y != j->res.stride_y || dst->stride_c != j->res.stride_c))
         return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_flush: pictures with ordered tasks need tight planes (stride = width)", hipSuccess);
@@ -660,18 +869,9 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
     const int sao_on = pr->sao && (stages & OVHIP_STAGE_SAO), alf_on = pr->alf_ctus && (stages & OVHIP_STAGE_ALF);
     if (alf_on && (!pr->alf_luma_coeff || !pr->alf_luma_clip || !pr->alf_chroma_coeff || !pr->alf_chroma_clip || !pr->alf_cc_coeff))
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_flush: ALF tables missing", hipSuccess);
-    ParamLayout L;
-    size_t o = 0;
-    auto put = [&o](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    L.sao = put(sao_on ? n_ctu * sizeof(ovhip_sao_ctu) : 0);
-    L.alf_ctus = put(alf_on ? n_ctu * sizeof(ovhip_alf_ctu) : 0);
-    L.lcoef = put(alf_on ? 24 * OVHIP_ALF_LUMA_SET_SIZE * 2 : 0);
-    L.lclip = put(alf_on ? 24 * OVHIP_ALF_LUMA_SET_SIZE * 2 : 0);
-    L.ccoef = put(alf_on ? 8 * 7 * 2 : 0);
-    L.cclip = put(alf_on ? 8 * 7 * 2 : 0);
-    L.cc = put(alf_on ? 2 * 4 * 8 * 2 : 0);
-    L.fwd = put(pr->lmcs ? 2048 : 0);
-    L.bwd = put(pr->lmcs ? 2048 : 0);
+    Layout L;
+    const size_t o_sao = L.put(sao_on ? n_ctu * sizeof(ovhip_sao_ctu) : 0), o_alf = L.put(alf_on ? n_ctu * sizeof(ovhip_alf_ctu) : 0);
+    const Tables tabs = tables_put(L, alf_on, pr->lmcs != nullptr);
     // Uploads are what the stream is bound by once the kernels are fast (round 4, tools/micro/h2d_concurrent.py on the GPU box: a 4K
     // picture's 8.7 MB in 10 copies on 16 streams at once = 3600 pictures/s of DMA and nothing else; one copy ~20 us of fixed cost;
     // 16 streams copying at once reach 31-38 GB/s where 1-4 reach 52-56).  So: arrays up to PACK_LIMIT ride in the staging block (one
@@ -692,28 +892,20 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
     };
     static_assert(B_COUNT <= 24, "packed_prev");
     const void *packed[24] = { nullptr };           // device address of a packed array (inside the parameter block)
-    for (auto &sm : small) if (sm.bytes && sm.bytes <= PACK_LIMIT && !j->resident) sm.at = put(sm.bytes) + 1;
-    L.total = o;
-    if (L.total) {
-        CHK(pinned_reserve(j, (void **)&j->param_host, &j->param_cap, L.total));
+    for (auto &sm : small) if (sm.bytes && sm.bytes <= PACK_LIMIT && !j->resident) sm.at = L.put(sm.bytes) + 1;
+    if (L.o) {
+        CHK(pinned_reserve(j, (void **)&j->param_host, &j->param_cap, L.o));
         char *ph = j->param_host;
         for (auto &sm : small) if (sm.at) memcpy(ph + sm.at - 1, sm.host, sm.bytes);
-        if (sao_on) memcpy(ph + L.sao, pr->sao, n_ctu * sizeof(ovhip_sao_ctu));
-        if (alf_on) {
-            memcpy(ph + L.alf_ctus, pr->alf_ctus, n_ctu * sizeof(ovhip_alf_ctu));
-            memcpy(ph + L.lcoef, pr->alf_luma_coeff, 24 * OVHIP_ALF_LUMA_SET_SIZE * 2);
-            memcpy(ph + L.lclip, pr->alf_luma_clip, 24 * OVHIP_ALF_LUMA_SET_SIZE * 2);
-            memcpy(ph + L.ccoef, pr->alf_chroma_coeff, 8 * 7 * 2);
-            memcpy(ph + L.cclip, pr->alf_chroma_clip, 8 * 7 * 2);
-            memcpy(ph + L.cc, pr->alf_cc_coeff, 2 * 4 * 8 * 2);
-        }
-        if (pr->lmcs) { memcpy(ph + L.fwd, pr->lmcs->fwd_lut, 2048); memcpy(ph + L.bwd, pr->lmcs->bwd_lut, 2048); }
+        if (sao_on) memcpy(ph + o_sao, pr->sao, n_ctu * sizeof(ovhip_sao_ctu));
+        if (alf_on) memcpy(ph + o_alf, pr->alf_ctus, n_ctu * sizeof(ovhip_alf_ctu));
+        tables_fill(ph, tabs, pr, alf_on, pr->lmcs != nullptr);
     }
 
     const double t_flush1 = host_now_us();
     // ---- H2D (asynchronous DMA out of page-locked memory, in stage order so that prediction can start early) ----
-    j->up = (j->resident || no_upload) ? nullptr : upload_stream_for(j);
-    if (j->up) {
+    const hipStream_t up = no_upload ? nullptr : upload_stream_for(j), ust = up ? up : ctx->stream;
+    if (up) {
         // The copies overwrite buffers the previous picture's launches and this picture's eager refinement rows read: the upload stream
         // waits for THEIR events (ev_done: the end of the last flush; ev_rows: the end of an eager pass not collected yet) -- with a frame
         // thread that waits for its picture before it takes the next, both long complete.  NOT for a fresh marker on the picture's own
@@ -721,34 +913,37 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
         // 7 ms ordered pass, a 0.8 ms frame download), and the shared upload stream would hold up every picture behind it (measured:
         // the in-order variant 2309 -> 1476, frames leaving the device 1247 -> 1022 pictures/s with such a marker)
         hipError_t e0 = hipSuccess;
-        if (j->flushed) e0 = hipStreamWaitEvent(j->up, j->ev_done, 0);
-        if (e0 == hipSuccess && j->rows_pending) e0 = hipStreamWaitEvent(j->up, j->ev_rows, 0);
-        if (e0 != hipSuccess) { j->up = nullptr; return ov_fail(ctx, OVHIP_ENODEV, "ovhip_job_flush: upload stream", e0); }
+        if (j->flushed) e0 = hipStreamWaitEvent(up, j->ev_done, 0);
+        if (e0 == hipSuccess && j->rows_pending) e0 = hipStreamWaitEvent(up, j->ev_rows, 0);
+        if (e0 != hipSuccess) return ov_fail(ctx, OVHIP_ENODEV, "ovhip_job_flush: upload stream", e0);
     }
-    {
-    StageTimer t_(j, OVHIP_TIME_H2D);
-    CHK(h2d(j, B_PARAM, j->param_host, L.total));
-    if (n_mcx) {
-        CHK(dev_reserve(j, B_MV, n_mcx * 16));
-        CHK(pinned_reserve(j, (void **)&j->mv_host, &j->mv_cap, n_mcx * 16));
-    }
-    if (n_reg) CHK(dev_reserve(j, B_SCALE, n_reg * 2));
-    // (refined units that went through the eager per-row search are uploaded again with the rest: the list is small and
-    // the full kernel repeats the search with the identical result)
-    for (auto &sm : small) {
-        if (j->resident) continue;
-        if (sm.at) packed[sm.buf] = (const char *)j->dev[B_PARAM].p + sm.at - 1;
-        else CHK(h2d(j, sm.buf, sm.host, sm.bytes));
-    }
-    }
+    auto upload = [&]() -> int {
+        StageTimer t_(j, OVHIP_TIME_H2D);
+        CHK(h2d(j, ust, B_PARAM, j->param_host, L.o));
+        if (n_mcx) {
+            CHK(dev_reserve(j, B_MV, n_mcx * 16));
+            CHK(pinned_reserve(j, (void **)&j->mv_host, &j->mv_cap, n_mcx * 16));
+        }
+        if (n_reg) CHK(dev_reserve(j, B_SCALE, n_reg * 2));
+        // (refined units that went through the eager per-row search are uploaded again with the rest: the list is small and
+        // the full kernel repeats the search with the identical result)
+        for (auto &sm : small) {
+            if (j->resident) continue;
+            if (sm.at) packed[sm.buf] = (const char *)j->dev[B_PARAM].p + sm.at - 1;
+            else CHK(h2d(j, ust, sm.buf, sm.host, sm.bytes));
+        }
+        return OVHIP_OK;
+    };
+    const int r_up = upload();
+    // ev_h2d behind the copies on the stream that carries them -- also when one of them failed: ovhip_job_begin orders the reuse of the
+    // page-locked arrays behind it
+    OV_HIP(ctx, hipEventRecord(j->ev_h2d, ust));
+    j->flushed = 1;
+    if (r_up != OVHIP_OK) return r_up;
+    if (up) OV_HIP(ctx, hipStreamWaitEvent(ctx->stream, j->ev_h2d, 0));
     // a resident replay re-uses the placement of the flush before it
     if (no_upload) memcpy(packed, j->packed_prev, sizeof(packed)); else { memcpy(j->packed_prev, packed, sizeof(packed)); j->flow_on_device = by_flow && n_items; }
     auto DEV = [&](int k) -> const void * { return packed[k] ? packed[k] : j->dev[k].p; };
-    if (j->up) {
-        hipStream_t up = j->up; j->up = nullptr;
-        OV_HIP(ctx, hipEventRecord(j->ev_h2d, up));
-        OV_HIP(ctx, hipStreamWaitEvent(ctx->stream, j->ev_h2d, 0));
-    } else OV_HIP(ctx, hipEventRecord(j->ev_h2d, ctx->stream));
     const double t_flush2 = host_now_us();
     // everything below reads or writes pictures: behind the pictures this one depends on
     for (uint32_t i = 0; i < pr->n_wait_events; ++i)
@@ -770,30 +965,25 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
     j->st.host_us_wait = (uint32_t)(t_flush3 - t_flush2);
 
     const char *dp = (const char *)j->dev[B_PARAM].p;
-    const uint16_t *d_fwd = pr->lmcs ? (const uint16_t *)(dp + L.fwd) : nullptr;
-    const uint16_t *d_bwd = pr->lmcs ? (const uint16_t *)(dp + L.bwd) : nullptr;
-    const int16_t *d_scales = n_reg ? (const int16_t *)j->dev[B_SCALE].p : nullptr;
+    const uint16_t *d_bwd = pr->lmcs ? (const uint16_t *)(dp + tabs.at[T_BWD]) : nullptr;
+    Chain c = {};
+    c.j = j; c.timer = j; c.dst = dst; c.res = ordered ? &j->res : nullptr; c.log2_ctu = log2_ctu;
+    c.luts = pr->lmcs; c.d_fwd = pr->lmcs ? (const uint16_t *)(dp + tabs.at[T_FWD]) : nullptr; c.d_scales = (int16_t *)j->dev[B_SCALE].p;
+    c.d_mc = (const ovhip_mc_unit *)DEV(B_MC); c.n_mc = (uint32_t)n_mc; c.d_mcx = (const ovhip_mc_unit *)DEV(B_MCX); c.n_mcx = (uint32_t)n_mcx;
+    c.d_aff = (const ovhip_aff_unit *)DEV(B_AFF); c.n_aff = (uint32_t)n_aff; c.d_side = (const int32_t *)DEV(B_SIDE);
+    c.d_rpr = (const ovhip_rpr_unit *)DEV(B_RPR); c.n_rpr = (uint32_t)n_rpr;
+    c.d_tb = (const ovhip_tb_cmd *)DEV(B_TB); memcpy(c.cls, cls, sizeof(cls)); memcpy(c.tiny, tiny, sizeof(tiny)); c.d_coef = (const int16_t *)DEV(B_COEF);
+    c.d_reg = (const ovhip_lmcs_region *)DEV(B_REG); c.n_reg = (uint32_t)n_reg;
+    c.d_it = (const ovhip_itask *)DEV(B_ITASK); c.h_it = it; c.n_it = (uint32_t)n_it; c.lv_start = lv_start; c.n_lv = n_lv;
+    c.d_items = (const uint32_t *)DEV(B_IITEM); c.n_items = flow ? (uint32_t)n_items : 0;
 
-    // ---- prediction ----
+    // ---- prediction (+ the refined vectors back to the host, their TMVP plane cells, the CIIP blend) ----
     if (stages & OVHIP_STAGE_MC) {
-        ovhip_pic same[16];
-        const ovhip_pic *refs_all = refs;
-        refs = same_size_refs(dst, refs, n_refs, same);
-        { StageTimer t_(j, OVHIP_TIME_MC);
-        CHK(ovhip_mc_launch(ctx, dst, refs, n_refs, (const ovhip_mc_unit *)DEV(B_MC), (uint32_t)n_mc, d_fwd, intra));
-        // beside k_mc2 (disjoint blocks), only on pictures that have such units
-        if (n_rpr) CHK(ovhip_mc_rpr_launch(ctx, dst, refs_all, n_refs, (const ovhip_rpr_unit *)DEV(B_RPR), (uint32_t)n_rpr, d_fwd, intra)); }
-        j->st.n_launches += (n_mc != 0) + (n_rpr != 0);
         // Nothing on the device reads the refined vectors unless the TMVP entries are asked for: k_mcxa then stores them (one 16-byte
         // store per unit) straight into the page-locked array the host reads -- not even k_store_host's launch is left
         const bool mv_direct = n_mcx && !pr->tmvp_cells && !j->resident && X_MV_D2H == 3;
-        if (n_mcx || n_aff) {
-            StageTimer t_(j, OVHIP_TIME_MCXA);
-            CHK(ovhip_mcxa_launch(ctx, dst, refs, n_refs, (const ovhip_mc_unit *)DEV(B_MCX), (uint32_t)n_mcx,
-                                  mv_direct ? j->mv_host : (int32_t *)j->dev[B_MV].p, (const ovhip_aff_unit *)DEV(B_AFF), (uint32_t)n_aff,
-                                  (const int32_t *)DEV(B_SIDE), d_fwd));
-            j->st.n_launches++;
-        }
+        ovhip_pic same[16];
+        CHK(chain_predict(c, same_size_refs(dst, refs, n_refs, same), refs, n_refs, intra, mv_direct ? j->mv_host : (int32_t *)j->dev[B_MV].p));
         if (mv_direct) j->st.d2h_bytes += n_mcx * 16;
         else if (n_mcx && !j->resident && X_MV_D2H) {
             // refined vectors back to the host as early as the stream allows (the decoder's TMVP field needs them)
@@ -809,30 +999,14 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
             const size_t bytes = 4 * n_mcx * sizeof(ovhip_tmvp_cell);
             CHK(dev_reserve(j, B_TMVP, bytes));
             CHK(pinned_reserve(j, (void **)&j->tmvp_host, &j->tmvp_cap, bytes));
-            CHK(ovhip_tmvp_cells_launch(ctx, (const ovhip_mc_unit *)DEV(B_MCX), (uint32_t)n_mcx, (const int32_t *)j->dev[B_MV].p, log2_ctu,
-                                        (j->w + (1 << log2_ctu) - 1) >> log2_ctu, (ovhip_tmvp_cell *)j->dev[B_TMVP].p));
-            CHK(store_host(ctx, j->tmvp_host, j->dev[B_TMVP].p, bytes));
+            CHK(tmvp_cells(j, c.d_mcx, (const int32_t *)j->dev[B_MV].p, 0, n_mcx, log2_ctu));
             j->st.n_launches++; j->st.d2h_bytes += bytes;
-            j->n_tmvp = 4 * n_mcx;
         }
         if (n_ciip) { CHK(ovhip_ciip_launch(ctx, dst, intra, (const ovhip_ciip_unit *)DEV(B_CIIP), (uint32_t)n_ciip)); j->st.n_launches++; }
     }
-    // ---- the flow launch of the ordered pass: state block, abort word, this picture's epoch (before the residual stage: the
-    //      chroma-scale launch prepares the state words as a rider) ----
-    int flow_prepared = 0;
-    const ovhip_itask *d_it_early = (const ovhip_itask *)DEV(B_ITASK);
-    if ((stages & OVHIP_STAGE_INTRA) && by_flow && n_items) {
-        if (!j->d_flow) {
-            const size_t words = ovhip_intra_flow_words(j->w, j->h);
-            OV_HIP(ctx, hipMalloc((void **)&j->d_flow, words * sizeof(uint32_t)));
-            OV_HIP(ctx, hipMemsetAsync(j->d_flow, 0, words * sizeof(uint32_t), ctx->stream));
-        }
-        if (!j->abort_host) {
-            j->abort_host = (uint32_t *)pinned_alloc(nullptr, 64);
-            if (!j->abort_host) return ov_fail(ctx, OVHIP_ENOMEM, "ovhip_job_flush: pinned abort word", hipSuccess);
-            *j->abort_host = 0;
-        }
-        if (++j->epoch >= 0x7ffffff0u) j->epoch = 1;
+    // ---- the flow launch's state (before the residual stage: the chroma-scale launch prepares the state words as a rider) ----
+    if (flow) {
+        CHK(ordered_arm(j, &j->d_flow, ovhip_intra_flow_words(j->w, j->h)));
         // test hook (ovhip_job_test_abort_next_flow): the abort word is set on the device BEFORE the launch, so every item that has to
         // wait for another gives up at once -- a real abandoned first pass, picture incomplete and partly tagged
         if (j->test_abort && j->n_retries == 0) {
@@ -841,65 +1015,18 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
             *(volatile uint32_t *)j->abort_host = 1;
         }
     }
-    // ---- residual: luma blocks, chroma-scale derivation on the reconstructed luma, chroma blocks (+ inverse mapping) ----
-    if (stages & OVHIP_STAGE_ITX) {
-        const ovhip_tb_cmd *d_tb = (const ovhip_tb_cmd *)DEV(B_TB);
-        const int16_t *d_coef = (const int16_t *)DEV(B_COEF);
-        const uint32_t t_luma[4] = { (uint32_t)tiny[1][0], (uint32_t)tiny[1][1], (uint32_t)tiny[1][2], (uint32_t)tiny[1][3] };
-        const uint32_t t_chroma[4] = { (uint32_t)tiny[3][0], (uint32_t)tiny[3][1], (uint32_t)tiny[3][2], (uint32_t)tiny[3][3] };
-        if (cls[0] + cls[1]) {
-            StageTimer t_(j, OVHIP_TIME_ITX_LUMA);
-            CHK(ovhip_itx_launch_ex_(ctx, dst, ordered ? &j->res : nullptr, d_tb, (uint32_t)cls[0], (uint32_t)cls[1], t_luma, d_coef, nullptr, nullptr));
-            j->st.n_launches++;
-        }
-        if (n_reg) {
-            if (!pr->lmcs) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_flush: chroma-scale regions recorded without LMCS tables", hipSuccess);
-            StageTimer t_(j, OVHIP_TIME_LMCS_SCALE);
-            if ((stages & OVHIP_STAGE_INTRA) && by_flow && n_items) {
-                CHK(ovhip_lmcs_scale_prepare_launch(ctx, dst, (const ovhip_lmcs_region *)DEV(B_REG), (uint32_t)n_reg, pr->lmcs,
-                                                    (int16_t *)j->dev[B_SCALE].p, d_it_early, (uint32_t)n_it, j->d_flow, j->epoch));
-                flow_prepared = 1;
-            } else
-            CHK(ovhip_lmcs_scale_launch(ctx, dst, (const ovhip_lmcs_region *)DEV(B_REG), (uint32_t)n_reg, pr->lmcs,
-                                        (int16_t *)j->dev[B_SCALE].p));
-            j->st.n_launches++;
-        }
-        const ovhip_tb_cmd *d_tbc = d_tb + cls[0] + cls[1];
-        StageTimer t_(j, OVHIP_TIME_ITX_CHROMA);
-        if (pr->lmcs && cls[3] && !ordered) {
-            CHK(ovhip_itx_launch_ex_(ctx, dst, nullptr, d_tbc, (uint32_t)cls[2], (uint32_t)cls[3], t_chroma, d_coef, d_scales, d_bwd));
-            j->st.n_launches++;
-        } else {
-            if (cls[2] + cls[3]) {
-                CHK(ovhip_itx_launch_ex_(ctx, dst, ordered ? &j->res : nullptr, d_tbc, (uint32_t)cls[2], (uint32_t)cls[3], t_chroma, d_coef, d_scales, nullptr));
-                j->st.n_launches++;
-            }
-            if (pr->lmcs && !ordered) { CHK(ovhip_lmcs_inverse_launch(ctx, dst, d_bwd)); j->st.n_launches++; }
-        }
-    }
-    // ---- ordered pass: one launch per level (the launch boundary is the inter-level synchronisation) or, on request, ONE launch
-    // (a workgroup per CTU with tasks, CTU samples in LDS, neighbour CTUs chained by flags); then the inverse luma mapping ----
+    // ---- residual (+ the inverse luma mapping where no ordered pass follows) ----
+    if (stages & OVHIP_STAGE_ITX) CHK(chain_residual(c, ordered ? nullptr : d_bwd));
+    // ---- ordered pass: one launch per level, the flow launch or, on request, ONE launch (a workgroup per CTU with tasks, CTU samples in
+    // LDS, neighbour CTUs chained by flags); then the inverse luma mapping ----
     if (ordered) {
         StageTimer t_(j, OVHIP_TIME_INTRA);
-        const ovhip_itask *d_it = (const ovhip_itask *)DEV(B_ITASK);
         if (!by_level) {
-            if (!j->d_sync) {
-                const size_t words = ovhip_intra_sync_words(j->w, j->h, 5);          // the smallest CTU: enough for every size
-                OV_HIP(ctx, hipMalloc((void **)&j->d_sync, words * sizeof(uint32_t)));
-                OV_HIP(ctx, hipMemsetAsync(j->d_sync, 0, words * sizeof(uint32_t), ctx->stream));
-            }
-            if (!j->abort_host) {
-                j->abort_host = (uint32_t *)pinned_alloc(nullptr, 64);
-                if (!j->abort_host) return ov_fail(ctx, OVHIP_ENOMEM, "ovhip_job_flush: pinned abort word", hipSuccess);
-                *j->abort_host = 0;
-            }
-            if (++j->epoch >= 0x7ffffff0u) j->epoch = 1;
-            CHK(ovhip_intra_ctu_launch(ctx, dst, &j->res, d_it, (const ovhip_ictu *)DEV(B_ICTU), (uint32_t)n_ictu,
-                                       (const ovhip_lmcs_region *)DEV(B_REG), pr->lmcs, (int16_t *)j->dev[B_SCALE].p, log2_ctu, j->d_sync, j->epoch,
-                                       j->abort_host));
+            CHK(ordered_arm(j, &j->d_sync, ovhip_intra_sync_words(j->w, j->h, 5)));          // the smallest CTU: enough for every size
+            CHK(ovhip_intra_ctu_launch(ctx, dst, &j->res, c.d_it, (const ovhip_ictu *)DEV(B_ICTU), (uint32_t)n_ictu, c.d_reg, pr->lmcs, c.d_scales,
+                                       log2_ctu, j->d_sync, j->epoch, j->abort_host));
             j->st.n_launches++;
-        }
-        if (by_flow && n_items) {
+        } else {
             // ONE launch of W persistent workers (k_intra_flow): worker b takes the items b, b + W, ... in level order.  W bounds the
             // pollers of the launch, and the launches in flight together must fit the device for the forward-progress argument (an item
             // waits only for lower items; the lowest unfinished item's worker is resident or will be): the kernel holds 109 VGPRs = 16
@@ -922,72 +1049,30 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
             // pictures (tools/sweep_bpic_workers.sh, interleaved, six runs each: 1024 workers 3220 pictures/s, 1536 3308, 2048 2-10
             // second passes per run); an abandoned launch still halves the default (g_flow_shift).
             int n_workers = pr->flow_workers ? (int)pr->flow_workers : (WORKERS >= 0 ? (int)WORKERS : (6 * ctx->num_cus) >> flow_shift_of(ctx->device));
-            if (!pr->flow_workers && WORKERS < 0) {
-                // No more workers than the picture's widest level can use (round 4): a worker beyond that only ever holds an item that is
-                // levels ahead of the front -- and its wave slot, registers and LDS are then missing to the kernels of the pictures beside
-                // this one for as long as the pass runs.  An I picture has ~100 items per level and runs 5 ms: 4 x CUs = 1024 workers
-                // gave 2830-2930 pictures/s on bench.py's stream, 128-512 gave 3000-3150 (tools/sweep_ipic_workers.sh); a B picture's
-                // levels are 1000+ items wide and keep the full count.
-                size_t widest = 0, run = 0;
-                for (size_t q = 0; q < n_items; ++q) {
-                    run = (q && it[j->items_host[q] & 0xffffff].level == it[j->items_host[q - 1] & 0xffffff].level) ? run + 1 : 1;
-                    if (run > widest) widest = run;
-                }
-                const int want = (int)((2 * widest + 63) & ~(size_t)63);
+            if (flow && !pr->flow_workers && WORKERS < 0) {
+                // (flow_widest) An I picture has ~100 items per level and runs 5 ms: 4 x CUs = 1024 workers gave 2830-2930 pictures/s on
+                // bench.py's stream, 128-512 gave 3000-3150 (tools/sweep_ipic_workers.sh); a B picture's levels are 1000+ items wide and
+                // keep the full count.
+                const int want = flow_widest(it, j->items_host, n_items);
                 if (want < n_workers) n_workers = want < 64 ? 64 : want;
             }
             if (n_workers < 1) n_workers = 1;
-            CHK(ovhip_intra_flow_launch(ctx, dst, &j->res, d_it, (uint32_t)n_it, (const uint32_t *)DEV(B_IITEM), (uint32_t)n_items,
-                                        (const ovhip_lmcs_region *)DEV(B_REG), pr->lmcs, (int16_t *)j->dev[B_SCALE].p, log2_ctu, j->d_flow, j->epoch,
-                                        j->abort_host, !flow_prepared, n_workers));
-            j->st.n_launches += 1 + !flow_prepared;
-            j->flow_launched = 1;
-            j->st.flow_shift = (uint32_t)flow_shift_of(ctx->device);
+            CHK(chain_ordered(c, n_workers));
+            if (flow) { j->flow_launched = 1; j->st.flow_shift = (uint32_t)flow_shift_of(ctx->device); }
         }
-        for (uint32_t l = 0; by_level && !by_flow && l < n_lv; ++l) {
-            const uint32_t a = lv_start[l], b = lv_start[l + 1];
-            if (b > a) {
-                CHK(ovhip_intra_level_launch(ctx, dst, &j->res, d_it + a, b - a, (const ovhip_lmcs_region *)DEV(B_REG), pr->lmcs,
-                                             (int16_t *)j->dev[B_SCALE].p, log2_ctu, ovhip_intra_level_geom(it + a, b - a)));
-                j->st.n_launches++;
-            }
-        }
-        const bool inverse = pr->lmcs && (stages & OVHIP_STAGE_ITX);
         // the flow launches leave a hand-over bit in what they wrote: dropped by the inverse mapping's launch, or by one of its own
-        if (inverse) { CHK(ovhip_lmcs_inverse_untag_launch(ctx, dst, d_bwd, d_it, by_flow && n_items ? (uint32_t)n_it : 0u)); j->st.n_launches++; }
-        else if (by_flow && n_items) { CHK(ovhip_intra_flow_untag_launch(ctx, dst, d_it, (uint32_t)n_it, 1)); j->st.n_launches++; }
+        CHK(chain_unmap(j, dst, 0, j->h, (pr->lmcs && (stages & OVHIP_STAGE_ITX)) ? d_bwd : nullptr, c.d_it, c.n_items ? c.n_it : 0u));
     }
     // ---- in-loop filters ----
-    if (stages & OVHIP_STAGE_DBF) {
-        StageTimer t_(j, OVHIP_TIME_DBF);
-        CHK(ovhip_dbf_launch_edges_ex(ctx, dst, (const ovhip_dbf_edge *)DEV(B_EV), (uint32_t)n_ev,
-                                      (const ovhip_dbf_edge *)DEV(B_EH), (uint32_t)n_eh, &offs));
-        j->st.n_launches += (n_ev != 0) + (n_eh != 0);
-    }
-    // SAO writes tmp, ALF writes dst; with only one of the two the result is copied back so that dst always holds it
-    if (sao_on) {
-        StageTimer t_(j, OVHIP_TIME_SAO);
-        CHK(ovhip_sao_launch(ctx, &j->tmp, dst, (const ovhip_sao_ctu *)(dp + L.sao), log2_ctu));
-        j->st.n_launches++;
-    }
+    if (stages & OVHIP_STAGE_DBF)
+        CHK(chain_deblock(c, (const ovhip_dbf_edge *)DEV(B_EV), (uint32_t)n_ev, (const ovhip_dbf_edge *)DEV(B_EH), (uint32_t)n_eh, &offs));
+    ovhip_alf_pic ap;
     if (alf_on) {
         CHK(dev_reserve(j, B_CLASS, (size_t)((j->w + 3) / 4) * ((j->h + 3) / 4)));
-        ovhip_alf_pic ap;
-        ap.ctus = (const ovhip_alf_ctu *)(dp + L.alf_ctus);
-        ap.luma_coeff = (const int16_t *)(dp + L.lcoef); ap.luma_clip = (const int16_t *)(dp + L.lclip);
-        ap.chroma_coeff = (const int16_t *)(dp + L.ccoef); ap.chroma_clip = (const int16_t *)(dp + L.cclip);
-        ap.cc_coeff = (const int16_t *)(dp + L.cc);
-        ap.class_scratch = (uint8_t *)j->dev[B_CLASS].p;
-        ap.log2_ctu_s = log2_ctu;
-        if (!sao_on) CHK(copy_pic(ctx, &j->tmp, dst));
-        StageTimer t_(j, OVHIP_TIME_ALF);
-        CHK(ovhip_alf_launch(ctx, dst, &j->tmp, &ap));
-        j->st.n_launches++;
-    } else if (sao_on) {
-        CHK(copy_pic(ctx, dst, &j->tmp));
+        ap = alf_pic_at(dp, tabs, (const ovhip_alf_ctu *)(dp + o_alf), (uint8_t *)j->dev[B_CLASS].p, log2_ctu);
     }
+    CHK(chain_filters(c, sao_on ? (const ovhip_sao_ctu *)(dp + o_sao) : nullptr, alf_on ? &ap : nullptr, 0, j->h, 0, j->h));
     OV_HIP(ctx, hipEventRecord(j->ev_done, ctx->stream));
-    j->flushed = 1;
     j->st.host_us_launch = (uint32_t)(host_now_us() - t_flush3);
     return OVHIP_OK;
 }
@@ -1024,8 +1109,6 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
 // =====================================================================================================================================
 extern "C" void ovhip_rec_tb_split_range_(const ovhip_recorder *r, size_t first, size_t n, ovhip_tb_cmd *out, size_t counts[4], size_t tiny[4][4]);
 extern "C" int  ovhip_rec_itasks_sorted_range_(const ovhip_recorder *r, size_t first, size_t n, ovhip_itask *out, uint32_t *level_start, size_t cap, uint32_t *n_levels);
-extern "C" int  ovhip_sao_launch_rows(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *src, const ovhip_sao_ctu *d_params, int32_t log2_ctu_s, int32_t row0, int32_t row1);
-extern "C" int  ovhip_alf_launch_rows(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *src, const ovhip_alf_pic *alf, int32_t row0, int32_t row1);
 
 enum { MAX_BANDS = 96, ARENA_CHUNKS = 16, BAND_LEVELS = 4096 };
 struct ArenaChunk { char *host, *dev; size_t cap, used; };
@@ -1101,11 +1184,12 @@ static int band_flow_take(ovhip_ctx *ctx, int want)
 }
 static void band_flow_give(ovhip_ctx *ctx, int n) { if (n) __atomic_fetch_sub(&g_band_flow_inflight[ctx->device & (FLOW_DEVS - 1)], n, __ATOMIC_RELAXED); }
 
-// the charges of bands whose reconstruction has completed go back (in order: a later band's launches are behind the earlier ones')
+// the charges of bands whose reconstruction has completed go back (in order: a later band's launches are behind the earlier ones'); the
+// record of the band after the last one holds the charge of a call for it that failed (ovhip_job_band)
 static void band_flow_reclaim(ovhip_job *j, int wait)
 {
     BandState *bs = j->bs;
-    for (int b = 0; bs && b < bs->n; ++b) {
+    for (int b = 0; bs && b <= bs->n && b < MAX_BANDS; ++b) {
         BandRec &B = bs->band[b];
         if (!B.flow_charge) continue;
         if (wait) (void)hipEventSynchronize(bs->ev_recon[b]);
@@ -1247,12 +1331,7 @@ extern "C" int ovhip_job_band_reserve(ovhip_job *j)
     }
     if (!bs->keep) OV_HIP(j->ctx, hipMalloc((void **)&bs->keep, (size_t)4 * j->w * sizeof(uint16_t)));
     if (!j->res.y) CHK(ovhip_pic_alloc(j->ctx, j->w, j->h, &j->res));
-    if (!j->d_flow) {
-        const size_t words = ovhip_intra_flow_words(j->w, j->h);
-        OV_HIP(j->ctx, hipMalloc((void **)&j->d_flow, words * sizeof(uint32_t)));
-        OV_HIP(j->ctx, hipMemsetAsync(j->d_flow, 0, words * sizeof(uint32_t), j->ctx->stream));
-    }
-    return OVHIP_OK;
+    return state_words(j, &j->d_flow, ovhip_intra_flow_words(j->w, j->h));
 }
 
 // 1: the reconstruction of the last band submitted is still running on the device.  A caller that is ahead of the device leaves its
@@ -1288,10 +1367,7 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
     if (dst->w != j->w || dst->h != j->h) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_band: picture size differs from the job's", hipSuccess);
     if (dst->stride_y != j->tmp.stride_y || dst->stride_c != j->tmp.stride_c)
         return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: tight planes only (stride = width)", hipSuccess);
-    if (!j->bs) {
-        j->bs = (BandState *)calloc(1, sizeof(BandState));
-        if (!j->bs) return OVHIP_ENOMEM;
-    }
+    if (!j->bs || !j->bs->active) CHK(ovhip_job_band_reserve(j));       // (the first band of a picture)
     BandState *bs = j->bs;
     ovhip_recorder *rec = j->rec;
     const int log2_ctu = pr->log2_ctu_s ? pr->log2_ctu_s : 7;
@@ -1308,20 +1384,8 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
         bs->log2_ctu = log2_ctu; bs->filters_latched = 0; bs->lmcs_up = 0; bs->alf_up = 0; bs->have_luts = 0;
         bs->stages = pr->stages ? pr->stages : 0xffffffffu;
         bs->last_event = nullptr; bs->last_rows = 0; bs->keep_valid = 0;
-        if (!bs->keep) OV_HIP(ctx, hipMalloc((void **)&bs->keep, (size_t)4 * j->w * sizeof(uint16_t)));
         j->again.valid = 0; j->n_retries = 0;       // (n_mv / n_tmvp: the eager DMVR rows' -- a pass may have run before the first band)
-        if (!j->res.y) CHK(ovhip_pic_alloc(ctx, j->w, j->h, &j->res));
-        if (!j->d_flow) {
-            const size_t words = ovhip_intra_flow_words(j->w, j->h);
-            OV_HIP(ctx, hipMalloc((void **)&j->d_flow, words * sizeof(uint32_t)));
-            OV_HIP(ctx, hipMemsetAsync(j->d_flow, 0, words * sizeof(uint32_t), ctx->stream));
-        }
-        if (!j->abort_host) {
-            j->abort_host = (uint32_t *)pinned_alloc(nullptr, 64);
-            if (!j->abort_host) return ov_fail(ctx, OVHIP_ENOMEM, "ovhip_job_band: pinned abort word", hipSuccess);
-            *j->abort_host = 0;
-        }
-        if (++j->epoch >= 0x7ffffff0u) j->epoch = 1;
+        CHK(ordered_arm(j, &j->d_flow, ovhip_intra_flow_words(j->w, j->h)));
         CHK(dev_reserve(j, B_SCALE, 65536));                               // 32767 regions at most (ovhip_rec_lmcs_region)
         CHK(dev_reserve(j, B_CLASS, (size_t)((j->w + 3) / 4) * ((j->h + 3) / 4)));
     }
@@ -1343,7 +1407,9 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
     const ovhip_band_counts c0 = bs->cur;
     const int b = bs->n;
     BandRec &B = bs->band[b];
+    const int charged = B.flow_charge;           // left by a call for this band that failed after its charge (band_flow_reclaim)
     memset(&B, 0, sizeof(B));
+    B.flow_charge = charged;
     B.row0 = bs->row_prev; B.row1 = row_end; B.c0 = c0; B.c1 = c1;
     size_t dummy = 0;
     if (ovhip_rec_ciip_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: stand-alone CIIP blend units (a second picture with the caller's intra prediction)", hipSuccess);
@@ -1353,16 +1419,8 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
                  n_ev = (stages & OVHIP_STAGE_DBF) ? c1.n_edge_v - c0.n_edge_v : 0, n_eh = (stages & OVHIP_STAGE_DBF) ? c1.n_edge_h - c0.n_edge_h : 0;
     const size_t n_it = (stages & OVHIP_STAGE_INTRA) ? n_it_all : 0;
     const ovhip_itask *it_all = ovhip_rec_itasks(rec, &dummy);
-    // flow items of the band: counted first (the count does not depend on the order), built after the sort
-    size_t n_items = 0; int by_flow = n_it != 0 && !(pr->stages && (stages & OVHIP_STAGE_INTRA_LEVELS));
-    for (size_t i = 0; i < n_it && by_flow; ++i) {
-        const ovhip_itask &t = it_all[c0.n_itask + i];
-        if (t.kind == OVHIP_IT_REGION) { ++n_items; continue; }
-        const int npx = 1 << (t.log2_w + t.log2_h), strips = (npx + 255) / 256;          // (FSTRIP = 256, kernels_intra.hip)
-        if (strips > 32) by_flow = 0;
-        n_items += (size_t)strips * (t.kind == OVHIP_IT_LUMA ? 1 : 2);
-    }
-    if (!by_flow) n_items = 0;
+    // flow items of the band: counted first (the count does not depend on the order), built after the sort; 0: one launch per level
+    const size_t n_items = n_it && !(pr->stages && (stages & OVHIP_STAGE_INTRA_LEVELS)) ? ovhip_intra_flow_items_(it_all + c0.n_itask, n_it, nullptr, 0) : 0;
 
     // ---- which tails this call runs, and the filter rows they make final ----
     const int t_first = bs->tails, t_end = b + 1;                     // tails [t_first, t_end): this band's (see "bottom row" below)
@@ -1391,32 +1449,26 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
     const size_t n_sao = sao_on ? (size_t)(sao_r1 - sao_r0) * nb_ctu_w : 0, n_alf = alf_on ? (size_t)(alf_r1 - alf_r0) * nb_ctu_w : 0;
 
     // ---- one staging block: layout ----
-    size_t o = 0;
-    auto put = [&o](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+    Layout L;
     const bool lmcs_now = pr->lmcs && !bs->lmcs_up, alf_now = alf_on && !bs->alf_up;
-    const size_t o_fwd = put(lmcs_now ? 2048 : 0), o_bwd = put(lmcs_now ? 2048 : 0);
-    const size_t o_lco = put(alf_now ? 24 * OVHIP_ALF_LUMA_SET_SIZE * 2 : 0), o_lcl = put(alf_now ? 24 * OVHIP_ALF_LUMA_SET_SIZE * 2 : 0),
-                 o_cco = put(alf_now ? 8 * 7 * 2 : 0), o_ccl = put(alf_now ? 8 * 7 * 2 : 0), o_cc = put(alf_now ? 2 * 4 * 8 * 2 : 0);
-    const size_t o_tb = put(n_tb * sizeof(ovhip_tb_cmd)), o_coef = put(n_coef * 2), o_mc = put(n_mc * sizeof(ovhip_mc_unit)),
-                 o_mcx = put(n_mcx * sizeof(ovhip_mc_unit)), o_aff = put(n_aff * sizeof(ovhip_aff_unit)), o_side = put(n_side * 4),
-                 o_reg = put(n_reg * sizeof(ovhip_lmcs_region)), o_it = put(n_it * sizeof(ovhip_itask)), o_items = put(n_items * 4),
-                 o_ev = put(n_ev * sizeof(ovhip_dbf_edge)), o_eh = put(n_eh * sizeof(ovhip_dbf_edge)),
-                 o_sao = put(n_sao * sizeof(ovhip_sao_ctu)), o_alf = put(n_alf * sizeof(ovhip_alf_ctu));
-    const size_t upload_bytes = o;
-    const size_t o_mv = put(n_mcx * 16);                                // device only: the refined vectors k_mcxa leaves (nobody reads them here)
+    const Tables tabs = tables_put(L, alf_now, lmcs_now);
+    const size_t o_tb = L.put(n_tb * sizeof(ovhip_tb_cmd)), o_coef = L.put(n_coef * 2), o_mc = L.put(n_mc * sizeof(ovhip_mc_unit)),
+                 o_mcx = L.put(n_mcx * sizeof(ovhip_mc_unit)), o_aff = L.put(n_aff * sizeof(ovhip_aff_unit)), o_side = L.put(n_side * 4),
+                 o_reg = L.put(n_reg * sizeof(ovhip_lmcs_region)), o_it = L.put(n_it * sizeof(ovhip_itask)), o_items = L.put(n_items * 4),
+                 o_ev = L.put(n_ev * sizeof(ovhip_dbf_edge)), o_eh = L.put(n_eh * sizeof(ovhip_dbf_edge)),
+                 o_sao = L.put(n_sao * sizeof(ovhip_sao_ctu)), o_alf = L.put(n_alf * sizeof(ovhip_alf_ctu));
+    const size_t upload_bytes = L.o;
+    const size_t o_mv = L.put(n_mcx * 16);                              // device only: the refined vectors k_mcxa leaves (nobody reads them here)
     char *hb = nullptr, *db = nullptr;
-    if (o) CHK(arena_take(j, o, &hb, &db));
+    if (L.o) CHK(arena_take(j, L.o, &hb, &db));
 
     // ---- fill it ----
     size_t cls[4] = { 0, 0, 0, 0 }, tiny[4][4] = { { 0 } };
     if (n_tb) ovhip_rec_tb_split_range_(rec, c0.n_tb, n_tb, (ovhip_tb_cmd *)(hb + o_tb), cls, tiny);
     uint32_t n_lv = 0; int have_levels = 0;
     if (n_it) have_levels = ovhip_rec_itasks_sorted_range_(rec, c0.n_itask, n_it, (ovhip_itask *)(hb + o_it), bs->level_start, BAND_LEVELS + 2, &n_lv) == 0;
-    if (n_it && !have_levels && !by_flow) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: a band with more levels than the table holds and blocks the flow launch cannot take", hipSuccess);
-    if (n_items) {
-        const size_t k = ovhip_intra_flow_items((const ovhip_itask *)(hb + o_it), n_it, (uint32_t *)(hb + o_items), n_items);
-        if (k != n_items) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_band: flow item count", hipSuccess);
-    }
+    if (n_it && !have_levels && !n_items) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: a band with more levels than the table holds and blocks the flow launch cannot take", hipSuccess);
+    if (n_items) (void)ovhip_intra_flow_items_((const ovhip_itask *)(hb + o_it), n_it, (uint32_t *)(hb + o_items), n_items);
     {
         size_t n;
         if (n_coef) memcpy(hb + o_coef, ovhip_rec_coefs(rec, &n) + c0.n_coef, n_coef * 2);
@@ -1432,156 +1484,89 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
         if (n_eh) memcpy(hb + o_eh, eh + c0.n_edge_h, n_eh * sizeof(ovhip_dbf_edge));
         if (n_sao) memcpy(hb + o_sao, pr->sao + (size_t)sao_r0 * nb_ctu_w, n_sao * sizeof(ovhip_sao_ctu));
         if (n_alf) memcpy(hb + o_alf, pr->alf_ctus + (size_t)alf_r0 * nb_ctu_w, n_alf * sizeof(ovhip_alf_ctu));
-        if (lmcs_now) { memcpy(hb + o_fwd, pr->lmcs->fwd_lut, 2048); memcpy(hb + o_bwd, pr->lmcs->bwd_lut, 2048); }
-        if (alf_now) {
-            memcpy(hb + o_lco, pr->alf_luma_coeff, 24 * OVHIP_ALF_LUMA_SET_SIZE * 2); memcpy(hb + o_lcl, pr->alf_luma_clip, 24 * OVHIP_ALF_LUMA_SET_SIZE * 2);
-            memcpy(hb + o_cco, pr->alf_chroma_coeff, 8 * 7 * 2); memcpy(hb + o_ccl, pr->alf_chroma_clip, 8 * 7 * 2);
-            memcpy(hb + o_cc, pr->alf_cc_coeff, 2 * 4 * 8 * 2);
-        }
+        tables_fill(hb, tabs, pr, alf_now, lmcs_now);
     }
     if (upload_bytes) {
         OV_HIP(ctx, hipMemcpyAsync(db, hb, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
         j->st.h2d_bytes += upload_bytes; j->st.n_h2d++;
     }
     OV_HIP(ctx, hipEventRecord(j->ev_h2d, ctx->stream));
-    if (lmcs_now) { bs->d_fwd = (const uint16_t *)(db + o_fwd); bs->d_bwd = (const uint16_t *)(db + o_bwd); bs->lmcs_up = 1; bs->luts = *pr->lmcs; bs->have_luts = 1; }
-    if (alf_now) {
-        bs->d_alf.luma_coeff = (const int16_t *)(db + o_lco); bs->d_alf.luma_clip = (const int16_t *)(db + o_lcl);
-        bs->d_alf.chroma_coeff = (const int16_t *)(db + o_cco); bs->d_alf.chroma_clip = (const int16_t *)(db + o_ccl);
-        bs->d_alf.cc_coeff = (const int16_t *)(db + o_cc);
-        bs->d_alf.class_scratch = (uint8_t *)j->dev[B_CLASS].p; bs->d_alf.log2_ctu_s = log2_ctu;
-        bs->alf_up = 1;
-    }
+    if (lmcs_now) { bs->d_fwd = (const uint16_t *)(db + tabs.at[T_FWD]); bs->d_bwd = (const uint16_t *)(db + tabs.at[T_BWD]); bs->lmcs_up = 1; bs->luts = *pr->lmcs; bs->have_luts = 1; }
+    if (alf_now) { bs->d_alf = alf_pic_at(db, tabs, nullptr, (uint8_t *)j->dev[B_CLASS].p, log2_ctu); bs->alf_up = 1; }
     if (pr->lmcs && !bs->lmcs_up) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_band: LMCS tables", hipSuccess);
-    const ovhip_lmcs_luts *luts = pr->lmcs ? &bs->luts : nullptr;
-    const uint16_t *d_fwd = pr->lmcs ? bs->d_fwd : nullptr, *d_bwd = pr->lmcs ? bs->d_bwd : nullptr;
-    int16_t *d_scales = (int16_t *)j->dev[B_SCALE].p;
-    // the band's slices through pointers moved back by the slice's first index: the commands' own indices stay what the recorder wrote
-    const ovhip_lmcs_region *d_reg = (const ovhip_lmcs_region *)(db + o_reg);
-    const ovhip_lmcs_region *d_reg_g = d_reg - c0.n_reg;
-    const int16_t *d_coef_g = (const int16_t *)(db + o_coef) - c0.n_coef;
-    const int32_t *d_side_g = (const int32_t *)(db + o_side) - c0.n_side;
-    const ovhip_itask *d_it = (const ovhip_itask *)(db + o_it);
-    B.d_it = d_it; B.n_it = (uint32_t)n_it;
+    const uint16_t *d_bwd = pr->lmcs ? bs->d_bwd : nullptr;
+    Chain c = {};
+    c.j = j; c.dst = dst; c.res = &j->res; c.log2_ctu = log2_ctu;
+    c.luts = pr->lmcs ? &bs->luts : nullptr; c.d_fwd = pr->lmcs ? bs->d_fwd : nullptr; c.d_scales = (int16_t *)j->dev[B_SCALE].p;
+    c.d_mc = (const ovhip_mc_unit *)(db + o_mc); c.n_mc = (uint32_t)n_mc; c.d_mcx = (const ovhip_mc_unit *)(db + o_mcx); c.n_mcx = (uint32_t)n_mcx;
+    c.d_aff = (const ovhip_aff_unit *)(db + o_aff); c.n_aff = (uint32_t)n_aff; c.d_side = (const int32_t *)(db + o_side) - c0.n_side;
+    c.d_tb = (const ovhip_tb_cmd *)(db + o_tb); memcpy(c.cls, cls, sizeof(cls)); memcpy(c.tiny, tiny, sizeof(tiny));
+    c.d_coef = (const int16_t *)(db + o_coef) - c0.n_coef;
+    c.d_reg = (const ovhip_lmcs_region *)(db + o_reg) - c0.n_reg; c.reg0 = c0.n_reg; c.n_reg = (uint32_t)n_reg;
+    c.d_it = (const ovhip_itask *)(db + o_it); c.h_it = (const ovhip_itask *)(hb + o_it); c.n_it = (uint32_t)n_it;
+    c.lv_start = bs->level_start; c.n_lv = n_lv;
+    c.d_items = (const uint32_t *)(db + o_items);
+    B.d_it = c.d_it; B.n_it = (uint32_t)n_it;
     B.d_ev = (const ovhip_dbf_edge *)(db + o_ev); B.n_ev = (uint32_t)n_ev; B.d_eh = (const ovhip_dbf_edge *)(db + o_eh); B.n_eh = (uint32_t)n_eh;
     j->st.n_tb += (uint32_t)n_tb; j->st.n_mc += (uint32_t)n_mc; j->st.n_mcx += (uint32_t)n_mcx; j->st.n_aff += (uint32_t)n_aff;
     j->st.n_edges_v += (uint32_t)n_ev; j->st.n_edges_h += (uint32_t)n_eh; j->st.n_regions += (uint32_t)n_reg; j->st.n_itasks += (uint32_t)n_it; j->st.n_ilevels += n_lv;
 
     // ---- recon(b) ----
-    if (stages & OVHIP_STAGE_MC) {
-        if (n_mc) { CHK(ovhip_mc_launch(ctx, dst, refs, n_refs, (const ovhip_mc_unit *)(db + o_mc), (uint32_t)n_mc, d_fwd, nullptr)); j->st.n_launches++; }
-        if (n_mcx || n_aff) {
-            CHK(ovhip_mcxa_launch(ctx, dst, refs, n_refs, (const ovhip_mc_unit *)(db + o_mcx), (uint32_t)n_mcx, (int32_t *)(db + o_mv),
-                                  (const ovhip_aff_unit *)(db + o_aff), (uint32_t)n_aff, d_side_g, d_fwd));
-            j->st.n_launches++;
-        }
-    }
+    if (stages & OVHIP_STAGE_MC) CHK(chain_predict(c, refs, refs, n_refs, nullptr, (int32_t *)(db + o_mv)));
+    if (!bs->ev_recon[b]) OV_HIP(ctx, hipEventCreateWithFlags(&bs->ev_recon[b], hipEventDisableTiming));
     int flow_workers = 0;
-    if (by_flow && n_items) {
+    if (n_items) {
         // workers: no more than the band's widest level can use, no more than the device's budget has left (else: one launch per level)
-        size_t widest = 0, run = 0;
-        const ovhip_itask *hs = (const ovhip_itask *)(hb + o_it); const uint32_t *items = (const uint32_t *)(hb + o_items);
-        for (size_t q = 0; q < n_items; ++q) {
-            run = (q && hs[items[q] & 0xffffff].level == hs[items[q - 1] & 0xffffff].level) ? run + 1 : 1;
-            if (run > widest) widest = run;
-        }
-        int want = pr->flow_workers ? (int)pr->flow_workers : (int)((2 * widest + 63) & ~(size_t)63);
+        int want = pr->flow_workers ? (int)pr->flow_workers : flow_widest(c.h_it, (const uint32_t *)(hb + o_items), n_items);
         const int most = (6 * ctx->num_cus) >> flow_shift_of(ctx->device);
         if (want > most) want = most;
         if (want < 64) want = 64;
         flow_workers = band_flow_take(ctx, (want + 63) & ~63);
-        if (!flow_workers) { by_flow = 0; if (!have_levels) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: flow budget exhausted and no level table", hipSuccess); }
-        B.flow_charge = flow_workers;
+        if (!flow_workers && !have_levels) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: flow budget exhausted and no level table", hipSuccess);
+        B.flow_charge += flow_workers;
+        c.n_items = flow_workers ? (uint32_t)n_items : 0;
     }
-    // the row above the band as the band's reconstruction must see it (k_band_row): unfiltered, mapped -- and without the hand-over bit
-    // when the readers are the per-level kernels, which take samples as they are
-    const bool swap_row = b > 0 && bs->keep_valid && (n_it || n_reg) && B.row0 > 0;
-    if (swap_row) CHK(band_row(j, dst, B.row0 - 1, 1, (by_flow && n_items) ? 0xffffu : 0x03ffu));
-    int flow_prepared = 0;
-    if (stages & OVHIP_STAGE_ITX) {
-        const ovhip_tb_cmd *d_tb = (const ovhip_tb_cmd *)(db + o_tb);
-        const uint32_t t_luma[4] = { (uint32_t)tiny[1][0], (uint32_t)tiny[1][1], (uint32_t)tiny[1][2], (uint32_t)tiny[1][3] };
-        const uint32_t t_chroma[4] = { (uint32_t)tiny[3][0], (uint32_t)tiny[3][1], (uint32_t)tiny[3][2], (uint32_t)tiny[3][3] };
-        if (cls[0] + cls[1]) { CHK(ovhip_itx_launch_ex_(ctx, dst, &j->res, d_tb, (uint32_t)cls[0], (uint32_t)cls[1], t_luma, d_coef_g, nullptr, nullptr)); j->st.n_launches++; }
-        if (n_reg) {
-            if (!luts) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_band: chroma-scale regions recorded without LMCS tables", hipSuccess);
-            if (by_flow && n_items) {
-                CHK(ovhip_lmcs_scale_prepare_launch(ctx, dst, d_reg, (uint32_t)n_reg, luts, d_scales + c0.n_reg, d_it, (uint32_t)n_it, j->d_flow, j->epoch));
-                flow_prepared = 1;
-            } else CHK(ovhip_lmcs_scale_launch(ctx, dst, d_reg, (uint32_t)n_reg, luts, d_scales + c0.n_reg));
-            j->st.n_launches++;
-        }
-        if (cls[2] + cls[3]) {
-            CHK(ovhip_itx_launch_ex_(ctx, dst, &j->res, d_tb + cls[0] + cls[1], (uint32_t)cls[2], (uint32_t)cls[3], t_chroma, d_coef_g, d_scales, nullptr));
-            j->st.n_launches++;
-        }
-    }
-    if (n_it) {
-        if (by_flow && n_items) {
-            CHK(ovhip_intra_flow_launch(ctx, dst, &j->res, d_it, (uint32_t)n_it, (const uint32_t *)(db + o_items), (uint32_t)n_items, d_reg_g, luts, d_scales,
-                                        log2_ctu, j->d_flow, j->epoch, j->abort_host, !flow_prepared, flow_workers));
-            j->st.n_launches += 1 + !flow_prepared;
-            B.tagged = 1;
-        } else {
+    // What follows enqueues the work the charge covers.  A failure leaves the charge with the band's record, ev_recon recorded behind
+    // what was enqueued: band_flow_reclaim gives it back once that has run (a retry of the band adds its own charge to it).
+    auto recon = [&]() -> int {
+        // the row above the band as the band's reconstruction must see it (k_band_row): unfiltered, mapped -- and without the hand-over
+        // bit when the readers are the per-level kernels, which take samples as they are
+        const bool swap_row = b > 0 && bs->keep_valid && (n_it || n_reg) && B.row0 > 0;
+        if (swap_row) CHK(band_row(j, dst, B.row0 - 1, 1, c.n_items ? 0xffffu : 0x03ffu));
+        if (stages & OVHIP_STAGE_ITX) CHK(chain_residual(c, nullptr));
+        if (n_it) {
             // one launch per level: its kernels read plain samples -- the band above must not carry the flow launches' hand-over bit any more
-            if (b > 0 && bs->band[b - 1].tagged && bs->tails < b) {
+            if (!c.n_items && b > 0 && bs->band[b - 1].tagged && bs->tails < b) {
                 CHK(ovhip_intra_flow_untag_launch(ctx, dst, bs->band[b - 1].d_it, bs->band[b - 1].n_it, 1));
-                bs->band[b - 1].tagged = 2;                          // (un-tagged early; the tail's own un-tag is then idempotent)
+                bs->band[b - 1].tagged = 2;                          // (un-tagged early: the tail leaves the bit alone)
                 j->st.n_launches++;
             }
-            const ovhip_itask *hs = (const ovhip_itask *)(hb + o_it);
-            for (uint32_t l = 0; l < n_lv; ++l) {
-                const uint32_t a = bs->level_start[l], e = bs->level_start[l + 1];
-                if (e > a) {
-                    CHK(ovhip_intra_level_launch(ctx, dst, &j->res, d_it + a, e - a, d_reg_g, luts, d_scales, log2_ctu, ovhip_intra_level_geom(hs + a, e - a)));
-                    j->st.n_launches++;
-                }
-            }
+            CHK(chain_ordered(c, flow_workers));
+            if (c.n_items) B.tagged = 1;
         }
+        if (swap_row) CHK(band_row(j, dst, B.row0 - 1, 2, 0));
+        if (!last && B.row1 > B.row0) { CHK(band_row(j, dst, B.row1 - 1, 0, 0)); bs->keep_valid = 1; }
+        OV_HIP(ctx, hipEventRecord(bs->ev_recon[b], ctx->stream));
+        return OVHIP_OK;
+    };
+    const int r = recon();
+    if (r != OVHIP_OK) {
+        if (B.flow_charge) (void)hipEventRecord(bs->ev_recon[b], ctx->stream);
+        return r;
     }
-    if (swap_row) CHK(band_row(j, dst, B.row0 - 1, 2, 0));
-    if (!last && B.row1 > B.row0) { CHK(band_row(j, dst, B.row1 - 1, 0, 0)); bs->keep_valid = 1; }
-    if (!bs->ev_recon[b]) OV_HIP(ctx, hipEventCreateWithFlags(&bs->ev_recon[b], hipEventDisableTiming));
-    OV_HIP(ctx, hipEventRecord(bs->ev_recon[b], ctx->stream));
     bs->n = b + 1; bs->cur = c1; bs->row_prev = row_end;
 
     // ---- tails: inverse luma mapping + un-tag, deblocking, per band; then the SAO / ALF rows they made final, once ----
     for (int t = t_first; t < t_end; ++t) {
-        BandRec &T = bs->band[t];
-        if (T.row1 > T.row0) {
-            const bool inverse = pr->lmcs && (stages & OVHIP_STAGE_ITX);
-            if (inverse) {
-                ovhip_pic view = *dst;                                // the band's luma rows; the chroma un-tag takes picture coordinates
-                view.y = dst->y + (size_t)T.row0 * dst->stride_y; view.h = T.row1 - T.row0;
-                CHK(ovhip_lmcs_inverse_untag_launch(ctx, &view, d_bwd, T.d_it, T.tagged ? T.n_it : 0u));
-                j->st.n_launches++;
-            } else if (T.tagged == 1 && T.n_it) { CHK(ovhip_intra_flow_untag_launch(ctx, dst, T.d_it, T.n_it, 1)); j->st.n_launches++; }
-        }
-        if ((stages & OVHIP_STAGE_DBF) && (T.n_ev || T.n_eh)) {
-            CHK(ovhip_dbf_launch_edges_ex(ctx, dst, T.d_ev, T.n_ev, T.d_eh, T.n_eh, &bs->offs));
-            j->st.n_launches += (T.n_ev != 0) + (T.n_eh != 0);
-        }
+        const BandRec &T = bs->band[t];
+        if (T.row1 > T.row0) CHK(chain_unmap(j, dst, T.row0, T.row1, (stages & OVHIP_STAGE_ITX) ? d_bwd : nullptr, T.d_it, T.tagged == 1 ? T.n_it : 0u));
+        if (stages & OVHIP_STAGE_DBF) CHK(chain_deblock(c, T.d_ev, T.n_ev, T.d_eh, T.n_eh, &bs->offs));
     }
     if (t_end > t_first) {
-        const ovhip_sao_ctu *d_sao = sao_on ? (const ovhip_sao_ctu *)(db + o_sao) - (size_t)sao_r0 * nb_ctu_w : nullptr;
         ovhip_alf_pic ap = bs->d_alf;
         ap.ctus = alf_on ? (const ovhip_alf_ctu *)(db + o_alf) - (size_t)alf_r0 * nb_ctu_w : nullptr;
-        auto copy_rows = [&](const ovhip_pic *d, const ovhip_pic *s_, int32_t r0, int32_t r1) -> int {
-            if (r1 <= r0) return OVHIP_OK;
-            OV_HIP(ctx, hipMemcpyAsync(d->y + (size_t)r0 * d->stride_y, s_->y + (size_t)r0 * s_->stride_y, (size_t)(r1 - r0) * d->stride_y * 2, hipMemcpyDeviceToDevice, ctx->stream));
-            const int32_t c0_ = r0 / 2, c1_ = r1 == j->h ? j->h / 2 : r1 / 2;
-            OV_HIP(ctx, hipMemcpyAsync(d->cb + (size_t)c0_ * d->stride_c, s_->cb + (size_t)c0_ * s_->stride_c, (size_t)(c1_ - c0_) * d->stride_c * 2, hipMemcpyDeviceToDevice, ctx->stream));
-            OV_HIP(ctx, hipMemcpyAsync(d->cr + (size_t)c0_ * d->stride_c, s_->cr + (size_t)c0_ * s_->stride_c, (size_t)(c1_ - c0_) * d->stride_c * 2, hipMemcpyDeviceToDevice, ctx->stream));
-            return OVHIP_OK;
-        };
-        if (sao_new > bs->sao_rows) {
-            if (sao_on) { CHK(ovhip_sao_launch_rows(ctx, &j->tmp, dst, d_sao, log2_ctu, bs->sao_rows, sao_new)); j->st.n_launches++; }
-            else if (alf_on) CHK(copy_rows(&j->tmp, dst, bs->sao_rows, sao_new));
-        }
-        if (alf_new > bs->alf_rows) {
-            if (alf_on) { CHK(ovhip_alf_launch_rows(ctx, dst, &j->tmp, &ap, bs->alf_rows, alf_new)); j->st.n_launches++; }
-            else if (sao_on) CHK(copy_rows(dst, &j->tmp, bs->alf_rows, alf_new));
-        }
+        CHK(chain_filters(c, sao_on ? (const ovhip_sao_ctu *)(db + o_sao) - (size_t)sao_r0 * nb_ctu_w : nullptr, alf_on ? &ap : nullptr,
+                          bs->sao_rows, sao_new, bs->alf_rows, alf_new));
         bs->dbf_rows = dbf_new; bs->sao_rows = sao_new; bs->alf_rows = alf_new;
         bs->rows_final = (sao_on || alf_on) ? alf_new : dbf_new;
         bs->tails = t_end;

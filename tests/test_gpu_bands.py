@@ -137,3 +137,34 @@ def test_band_rows_become_final_in_order(ctx):
     assert job.band_progress() == h and seen == sorted(seen) and seen[-1] > 0
     _same(dst.download(), whole, "finished picture")
     job.close()
+
+
+def test_failed_band_returns_its_flow_charge(ctx):
+    """A band that fails after it took workers from the device's flow budget (here: chroma-scale regions without LMCS tables, refused
+    after the charge) gives them back: three such failures leave the budget as it was, and the same band picture afterwards runs its
+    ordered pass as the flow launch it had before (the same launches, the same picture)."""
+    w, h = 832, 480
+    _, wl = _workload(w, h, 0x266, tools=synth.INTRA_TOOLS, intra_frac=0.2)
+    assert wl.lmcs_regions is not None and len(wl.lmcs_regions) and wl.itasks is not None and len(wl.itasks)
+    job = engine.Job(ctx, w, h)
+    refs = [ctx.upload_pic(*r) for r in wl.refs]
+    dst = ctx.new_pic(w, h)
+
+    def valid_band():
+        job.load_workload(wl)
+        job.band(dst, refs, h, True)
+        job.wait()
+        return job.stats().n_launches, dst.download()
+
+    launches, pic = valid_band()
+    for _ in range(3):
+        job.load_workload(wl)
+        p = job.make_params(wl)
+        p.lmcs = None
+        p.flow_workers = 1 << 20
+        with pytest.raises(engine.EngineError, match="chroma-scale regions recorded without LMCS tables"):
+            job.band(dst, refs, h, True, None, p)
+    again, pic2 = valid_band()
+    assert again == launches
+    _same(pic2, pic, "band picture after three failed bands")
+    job.close()
