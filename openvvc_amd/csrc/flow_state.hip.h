@@ -18,6 +18,31 @@ static inline FlowState flow_state_of(uint32_t *d_state, int w, int h)
     return fs;
 }
 
+// An item of the flow launch in one word: index of the task in the level-sorted list, strip of the block, colour plane of a chroma
+// task.  A picture with more tasks, or a block with more strips, than the fields hold does not take the flow path.
+#define FLOW_ITEM_TASK_BITS  24
+#define FLOW_ITEM_STRIP_BITS 5               // (a 64x64 block: 16 strips)
+#define FLOW_ITEM_MAX_TASKS  ((size_t)1 << FLOW_ITEM_TASK_BITS)
+#define FLOW_ITEM_MAX_STRIPS (1 << FLOW_ITEM_STRIP_BITS)
+struct FlowItem { uint32_t task; int strip, plane; };
+
+__host__ __device__ static inline uint32_t flow_item_pack(uint32_t task, int strip, int plane)
+{
+    return task | ((uint32_t)strip << FLOW_ITEM_TASK_BITS) | ((uint32_t)plane << (FLOW_ITEM_TASK_BITS + FLOW_ITEM_STRIP_BITS));
+}
+__host__ __device__ static inline FlowItem flow_item_unpack(uint32_t word)
+{
+    FlowItem it;
+    it.task = word & ((1u << FLOW_ITEM_TASK_BITS) - 1);
+    it.strip = (int)((word >> FLOW_ITEM_TASK_BITS) & (FLOW_ITEM_MAX_STRIPS - 1));
+    it.plane = (int)((word >> (FLOW_ITEM_TASK_BITS + FLOW_ITEM_STRIP_BITS)) & 1);
+    return it;
+}
+
+// ovhip_intra_flow_items() for the picture jobs (kernels_intra.hip): the count even where it exceeds cap -- only the first cap items
+// are written, items may be null with cap 0 -- and 0 only where the path is refused.  The count does not depend on the order of the tasks.
+extern "C" size_t ovhip_intra_flow_items_(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap);
+
 // 2 * epoch = "an ordered task of this picture will write this unit" into the words of the units task t covers; 16 lanes per task
 __device__ __forceinline__ void flow_prepare_task(const ovhip_itask &t, const FlowState &fs, unsigned epoch, int lane16)
 {

@@ -1,5 +1,5 @@
 // kernels_intra.hip -- the ordered pass on gfx950: intra prediction (+ CIIP's planar part, ordered chroma-scale regions and the
-// chroma residuals that hang on them), one LAUNCH PER LEVEL (ovhip_itask.level), one wavefront per task.
+// chroma residuals that hang on them), one wavefront per (task, strip of the block, colour plane) = ITEM.
 //
 // Replaces, for every block of an intra CU, the reference's per-block chain
 //   rcn_intra_tu / rcn_tu_st / rcn_tu_c (rcn_transform_tree.c:1384-1430, :1269-1287, :1349-1382)
@@ -7,19 +7,28 @@
 //        rcn_intra_cclm.c, rcn_fill_ref.c, rcn_intra_angular.c, rcn_intra_dc_planar.c)
 //     -> ict.add / ict.ict of the block's residual                                     (rcn_residuals.c:46-222)
 // The reference gets the order for free (decoding order on one core); here the recorder computed for every task the level
-// of its inputs, a level's tasks are mutually independent, and the launch boundary between levels is what makes one
-// level's stores visible to the next (per-XCD L2s are not coherent inside a launch).
+// of its inputs (ovhip_itask.level), a level's tasks are mutually independent, and three kernels differ in how one level's
+// stores reach the next (per-XCD L2s are not coherent inside a launch):
+//   k_intra_flow  (the default) ONE launch of persistent workers that take the items in level order; an item waits for its inputs
+//                 through tagged samples and per-unit state words, reads and writes past the caches;
+//   k_intra_level one launch PER LEVEL, the launch boundary orders the levels: the stand-alone entry point, and the second pass
+//                 that decodes a picture again whose flow launch gave up;
+//   k_intra_ctu   (on request) one launch, a workgroup per CTU with the CTU's samples in LDS, neighbour CTUs chained by flags.
+// What an item IS is written once for the three: its decode (Item / item_of), the prediction dispatch (predict_item) and, for
+// the two kernels that finish sample by sample, the epilogue (epilogue_load / epilogue_store).  The kernels supply the strip size,
+// where the samples and residuals live (accessors, dst / rp) and how the reference arms arrive (the fetch policy).
 //
-// Mapping: one 64-lane workgroup per (task, strip of 1024 samples, colour plane); lane = sample (<= 16 samples per lane).
-// A level is LATENCY bound (few, small, mutually independent tasks; the next level waits for all of them), so the kernel is
-// arranged around the number of dependent memory round trips: task -> {reference samples, residual, CIIP's inter samples:
-// all issued together} -> prediction out of LDS into an LDS tile -> epilogue (blend, residual, clip, store).
+// Mapping: lane = sample (<= 16 samples per lane).  The pass is LATENCY bound (few, small, mutually independent tasks per level;
+// the next level waits for all of them), so an item is arranged around the number of dependent memory round trips: task ->
+// {reference samples, residual, CIIP's inter samples: all issued together} -> prediction out of LDS into an LDS tile -> epilogue
+// (blend, residual, clip, store).
 // Reference samples of the block are fetched once into LDS with the substitution rules of 8.4.5.2.8 (availability = unit
 // counts from the recorder), smoothed copies next to them when the mode asks for them; every prediction mode then reads
 // LDS only.  int16 / int32 arithmetic, no MFMA: per-sample stencils.
 #include <stdlib.h>
 #include "ovvc_common.hip.h"
 #include "flow_state.hip.h"
+#include "lmcs_wnd.hip.h"
 #define OVT_ATTR __device__
 #include "vvc_mip_tables.h"
 
@@ -460,9 +469,7 @@ __device__ __forceinline__ void pred_cclm(IntraLds &s, const Acc ya, const Acc c
 #undef Y
 }
 
-struct LmcsWnd { uint16_t bnd[17]; int min_idx, max_idx, crs_offset; };
-
-// rcn_lmcs_compute_chroma_scale for one region (same arithmetic as k_lmcs_scale, kernels_lmcs.hip)
+// rcn_lmcs_compute_chroma_scale for one region (k_lmcs_scale, kernels_lmcs.hip, with the luma behind an accessor)
 template <class Acc>
 __device__ __forceinline__ int region_scale(const Acc ya, const ovhip_lmcs_region &g, const LmcsWnd &wnd, int lane)
 {
@@ -472,15 +479,109 @@ __device__ __forceinline__ int region_scale(const Acc ya, const ovhip_lmcs_regio
     int sum = (g.n_abv ? va : 0) + (g.n_lft ? vl : 0);
 #pragma unroll
     for (int m = 32; m; m >>= 1) sum += __shfl_xor(sum, m);
-    const int nb_units = (g.n_abv ? 16 : 0) + (g.n_lft ? 16 : 0);
-    int log2_nb = 0;
-    for (int v = nb_units; v; v >>= 1) ++log2_nb;
-    const int avg = log2_nb ? (sum + (1 << log2_nb)) >> (log2_nb + 1) : 512;
-    int idx = wnd.min_idx;
-    for (; idx < wnd.max_idx; ++idx) if (avg < wnd.bnd[idx + 1]) break;
-    idx = min(idx, 15);
-    const int wnd_sz = (int)wnd.bnd[idx + 1] - (int)wnd.bnd[idx];
-    return wnd_sz == 0 ? 1 << 11 : (1 << (OV_BD - 4 + 11)) / (wnd_sz + wnd.crs_offset);
+    return lmcs_scale_of_sum(wnd, sum, g.n_abv, g.n_lft);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// What one item is, for the three kernels.
+//
+// The decode of (task, strip, plane).  Nothing in it points anywhere: the kernels add their own dst / rp (picture planes, or the CTU
+// tile in LDS) and fetch the derived scale (scale_idx) in their own way.
+struct Item {
+    bool luma, region, res_only;         // the task's kind (none of them: a chroma prediction task)
+    bool lm;                             // cross-component linear model
+    bool has_res;                        // this plane of the block carries a residual
+    bool scaled, scale_idx;              // chroma residual scaling; the scale is scales[t.c_scale] (else t.c_scale itself)
+    int ciip_wt;                         // != 0: blend with the inter prediction already in the picture
+    int res_mask, res_l2pb;              // ISP blocks of several thin partitions: only those that carry a residual add one
+    int p0, p1;                          // the strip: raster sample range [p0, p1) of the block
+    __device__ __forceinline__ bool need_d() const { return ciip_wt || res_only; }          // the epilogue reads the old sample
+    __device__ __forceinline__ bool skip() const { return res_only && !has_res; }
+    __device__ __forceinline__ bool res_at(int x) const { return (res_mask >> (x >> res_l2pb)) & 1; }
+};
+
+template <int STRIP_>
+__device__ __forceinline__ Item item_of(const ovhip_itask &t, int strip, int plane)
+{
+    Item it;
+    it.luma = t.kind == OVHIP_IT_LUMA; it.region = t.kind == OVHIP_IT_REGION; it.res_only = t.kind == OVHIP_IT_RES_C;
+    // (a block-DPCM task is recorded with mode 0; the flag is part of the predicate so that no kernel depends on that)
+    it.lm = t.kind == OVHIP_IT_CHROMA && t.mode >= 67 && !(t.flags & OVHIP_IF_BDPCM);
+    it.has_res = t.flags & (it.luma ? OVHIP_IF_RES_Y : (plane ? OVHIP_IF_RES_CR : OVHIP_IF_RES_CB));
+    it.scaled = !it.luma && (t.flags & OVHIP_IF_RES_SCALE);
+    it.scale_idx = it.scaled && (t.flags & OVHIP_IF_SCALE_IDX);
+    it.ciip_wt = it.res_only ? 0 : t.ciip_wt;
+    const bool isp = t.flags & OVHIP_IF_ISP;
+    it.res_mask = isp ? t.isp_res_mask : 0xff; it.res_l2pb = isp ? t.isp_log2_pb : 6;
+    it.p0 = strip * STRIP_; it.p1 = min(1 << (t.log2_w + t.log2_h), it.p0 + STRIP_);
+    return it;
+}
+
+// How the level and the CTU kernel get the arms of a regular block: straight through the accessor
+struct DirectRefs {
+    template <class Acc>
+    __device__ __forceinline__ bool operator()(IntraLds &s, const Acc acc, int unit, const ovhip_itask &t, int mrl, int lane) const
+    {
+        fetch_refs(s, acc, t.x, t.y, 1 << t.log2_w, 1 << t.log2_h, unit, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, mrl, lane);
+        return true;
+    }
+    __device__ __forceinline__ void arms_ready() const { }
+};
+
+// The strip's prediction into s.pred: the only place that lists the modes.  ya / ca: the luma plane and the item's chroma plane.
+// fetch(s, acc, unit, t, mrl, lane) brings the arms of a regular block into LDS -- false: it gave up, and so does the item (the
+// flow kernel's bounded wait); fetch.arms_ready() is called when a luma block's arms can be read (where the flow kernel's probe
+// stamps).  NP: samples per lane of a strip.
+template <int NP, class Acc, class Fetch>
+__device__ __forceinline__ bool predict_item(IntraLds &s, const ovhip_itask &t, const Item &it, const Acc ya, const Acc ca, int log2_ctu,
+                                             const Fetch fetch, int lane)
+{
+    const Strip st = { it.p0, it.p1 };
+    if (it.luma) {
+        if (t.flags & OVHIP_IF_ISP) fetch_refs_isp(s, ya, t, lane);
+        else if (!fetch(s, ya, 4, t, (t.flags & OVHIP_IF_MIP) ? 0 : t.mrl_idx, lane)) return false;
+        wave_sync();
+        fetch.arms_ready();
+        if (t.flags & OVHIP_IF_MIP) pred_mip(s, t, st, lane);
+        else pred_regular(s, t, true, st, lane);
+    } else if (it.lm) pred_cclm<NP>(s, ya, ca, t, log2_ctu, st, lane);
+    else {
+        if (!fetch(s, ca, 2, t, 0, lane)) return false;
+        wave_sync();
+        pred_regular(s, t, false, st, lane);
+    }
+    wave_sync();
+    return true;
+}
+
+// The sample-by-sample epilogue of the level and the CTU kernel: prediction or old sample -> CIIP blend -> (scaled) residual ->
+// clip -> store.  What it needs from dst / rp is read by epilogue_load: in front of the prediction where that is a memory round
+// trip (the level kernel), right before the store where it is LDS (the CTU kernel).
+template <int NP>
+__device__ __forceinline__ void epilogue_load(int (&rv)[NP], int (&dv)[NP], const Item &it, const uint16_t *dst, int dstride, const int16_t *rp, int rstride,
+                                              int l2w, int lane)
+{
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int p = it.p0 + lane + 64 * i, x = p & ((1 << l2w) - 1), y = p >> l2w;
+        rv[i] = (it.has_res && p < it.p1 && it.res_at(x)) ? rp[y * rstride + x] : 0;
+        dv[i] = (it.need_d() && p < it.p1) ? dst[y * dstride + x] : 0;
+    }
+}
+
+template <int NP>
+__device__ __forceinline__ void epilogue_store(const IntraLds &s, const int (&rv)[NP], const int (&dv)[NP], const Item &it, int scale, uint16_t *dst, int dstride,
+                                               int l2w, int lane)
+{
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int p = it.p0 + lane + 64 * i, x = p & ((1 << l2w) - 1), y = p >> l2w;
+        if (p >= it.p1) break;
+        int v = it.res_only ? dv[i] : s.pred[p - it.p0];
+        if (it.ciip_wt) v = (v * it.ciip_wt + dv[i] * (4 - it.ciip_wt) + 2) >> 2;
+        if (it.has_res) v = ov_clip_bd(v + (it.scaled ? res_scale(rv[i], scale) : rv[i]));
+        dst[y * dstride + x] = (uint16_t)v;
+    }
 }
 
 __global__ __launch_bounds__(64) void k_intra_level(ovhip_pic pic, ovhip_pic res, const ovhip_itask *__restrict__ tasks, uint32_t n,
@@ -494,65 +595,24 @@ __global__ __launch_bounds__(64) void k_intra_level(ovhip_pic pic, ovhip_pic res
     const int lane = threadIdx.x;
     load_tables(s, lane);
     const ovhip_itask t = tasks[bid];
-    const int l2w = t.log2_w, w = 1 << l2w, h = 1 << t.log2_h, npx = w * h;
+    const Item it = item_of<STRIP>(t, strip, comp);
     const PlaneAcc ya = { pic.y, pic.stride_y };
-    if (t.kind == OVHIP_IT_REGION) {
+    if (it.region) {
         if (!strip && !comp) { const int v = region_scale(ya, regs[t.c_scale], wnd, lane); if (lane == 0) scales[t.c_scale] = (int16_t)v; }
         return;
     }
-    const bool luma = t.kind == OVHIP_IT_LUMA;
-    Strip st; st.p0 = strip * STRIP; st.p1 = min(npx, st.p0 + STRIP);
-    if (st.p0 >= npx || (luma && comp)) return;
-    const bool has_res = t.flags & (luma ? OVHIP_IF_RES_Y : (comp ? OVHIP_IF_RES_CR : OVHIP_IF_RES_CB));
-    const bool res_only = t.kind == OVHIP_IT_RES_C;
-    if (res_only && !has_res) return;
-    uint16_t *pl = luma ? pic.y : (comp ? pic.cr : pic.cb);
-    const int dstride = luma ? pic.stride_y : pic.stride_c, rstride = luma ? res.stride_y : res.stride_c;
+    if (it.p0 >= it.p1 || (it.luma && comp) || it.skip()) return;
+    uint16_t *pl = it.luma ? pic.y : (comp ? pic.cr : pic.cb);
+    const int dstride = it.luma ? pic.stride_y : pic.stride_c, rstride = it.luma ? res.stride_y : res.stride_c;
     uint16_t *dst = pl + t.y * dstride + t.x;
-    const int16_t *rp = reinterpret_cast<const int16_t *>(luma ? res.y : (comp ? res.cr : res.cb)) + t.y * rstride + t.x;
-    const int ciip_wt = res_only ? 0 : t.ciip_wt;
-    const bool need_d = ciip_wt || res_only;
-
-    // ISP blocks of several thin partitions: only those that carry a residual add one
-    const int res_mask = (t.flags & OVHIP_IF_ISP) ? t.isp_res_mask : 0xff, res_l2pb = (t.flags & OVHIP_IF_ISP) ? t.isp_log2_pb : 6;
+    const int16_t *rp = reinterpret_cast<const int16_t *>(it.luma ? res.y : (comp ? res.cr : res.cb)) + t.y * rstride + t.x;
     // everything the epilogue needs from memory is requested before the prediction starts
     int rv[NPL], dv[NPL];
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int p = st.p0 + lane + 64 * i, x = p & (w - 1), y = p >> l2w;
-        rv[i] = (has_res && p < st.p1 && ((res_mask >> (x >> res_l2pb)) & 1)) ? rp[y * rstride + x] : 0;
-        dv[i] = (need_d && p < st.p1) ? dst[y * dstride + x] : 0;
-    }
-    const bool scaled = !luma && (t.flags & OVHIP_IF_RES_SCALE);
-    const int scale = scaled ? ((t.flags & OVHIP_IF_SCALE_IDX) ? scales[t.c_scale] : t.c_scale) : 0;
-
-    if (!res_only) {
-        if (luma) {
-            if (t.flags & OVHIP_IF_ISP) fetch_refs_isp(s, ya, t, lane);
-            else fetch_refs(s, ya, t.x, t.y, w, h, 4, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, (t.flags & OVHIP_IF_MIP) ? 0 : t.mrl_idx, lane);
-            wave_sync();
-            if (t.flags & OVHIP_IF_MIP) pred_mip(s, t, st, lane);
-            else pred_regular(s, t, true, st, lane);
-        } else {
-            const PlaneAcc ca = { pl, pic.stride_c };
-            if (t.mode >= 67) pred_cclm<NPL>(s, ya, ca, t, log2_ctu, st, lane);
-            else {
-                fetch_refs(s, ca, t.x, t.y, w, h, 2, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, 0, lane);
-                wave_sync();
-                pred_regular(s, t, false, st, lane);
-            }
-        }
-        wave_sync();
-    }
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int p = st.p0 + lane + 64 * i, x = p & (w - 1), y = p >> l2w;
-        if (p >= st.p1) break;
-        int v = res_only ? dv[i] : s.pred[p - st.p0];
-        if (ciip_wt) v = (v * ciip_wt + dv[i] * (4 - ciip_wt) + 2) >> 2;
-        if (has_res) v = ov_clip_bd(v + (scaled ? res_scale(rv[i], scale) : rv[i]));
-        dst[y * dstride + x] = (uint16_t)v;
-    }
+    epilogue_load(rv, dv, it, dst, dstride, rp, rstride, t.log2_w, lane);
+    const int scale = it.scaled ? (it.scale_idx ? scales[t.c_scale] : t.c_scale) : 0;
+    const PlaneAcc ca = { pl, pic.stride_c };
+    if (!it.res_only) predict_item<NPL>(s, t, it, ya, ca, log2_ctu, DirectRefs(), lane);
+    epilogue_store(s, rv, dv, it, scale, dst, dstride, t.log2_w, lane);
 }
 
 
@@ -617,6 +677,15 @@ __device__ const uint32_t *g_probe_items;      // the picture's first item: laun
 #endif
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
+// A bounded wait expired (or somebody else's did): the picture's abort word, which ends every other waiter of the launch, and its
+// mirror in host memory, which ovhip_job_wait reads.  Lane 0 stores; the caller leaves the kernel.
+__device__ __forceinline__ void flow_give_up(unsigned *sync, unsigned *abort_mirror, int lane)
+{
+    if (lane != 0) return;
+    __hip_atomic_store(sync, 1u + blockIdx.x, RLX_AGENT);
+    if (abort_mirror) __hip_atomic_store(abort_mirror, 1u + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __device__ __forceinline__ ovhip_itask uniform_task(const ovhip_itask *p)
 {
     union { ovhip_itask t; unsigned u[8]; } v;
@@ -630,62 +699,30 @@ __device__ __forceinline__ ovhip_itask uniform_task(const ovhip_itask *p)
 __device__ void ctu_item(CtuLds &L, IntraLds &s, const ovhip_itask &t, int strip, int comp, int X0, int Y0,
                          const ovhip_lmcs_region *__restrict__ regs, const LmcsWnd &wnd, int16_t *__restrict__ scales, int log2_ctu, int lane)
 {
-    const int l2w = t.log2_w, w = 1 << l2w, h = 1 << t.log2_h, npx = w * h;
+    const Item it = item_of<STRIP>(t, strip, comp);
     const TileAcc ya = { &L.ty[0][0], L.top_y, CT_YS, X0, Y0 };
-    if (t.kind == OVHIP_IT_REGION) {
+    if (it.region) {
         const int v = region_scale(ya, regs[t.c_scale], wnd, lane);
         if (lane == 0) { const int k = atomicAdd(&L.n_sc, 1) & 3; L.sc_idx[k] = t.c_scale; L.sc_val[k] = v; scales[t.c_scale] = (int16_t)v; }
         return;
     }
-    const bool luma = t.kind == OVHIP_IT_LUMA;
-    Strip st; st.p0 = strip * STRIP; st.p1 = min(npx, st.p0 + STRIP);
-    const bool has_res = t.flags & (luma ? OVHIP_IF_RES_Y : (comp ? OVHIP_IF_RES_CR : OVHIP_IF_RES_CB));
-    const bool res_only = t.kind == OVHIP_IT_RES_C;
-    if (res_only && !has_res) return;
-    const bool scaled = !luma && (t.flags & OVHIP_IF_RES_SCALE);
+    if (it.skip()) return;
     int scale = 0;
-    if (scaled) {
-        if (t.flags & OVHIP_IF_SCALE_IDX) {
-            int found = -1;
+    if (it.scale_idx) {
+        int found = -1;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) if (k < min(L.n_sc, 4) && L.sc_idx[k] == t.c_scale) found = L.sc_val[k];
-            scale = found >= 0 ? found : scales[t.c_scale];          // not from this CTU: k_lmcs_scale wrote it before this launch
-        } else scale = t.c_scale;
-    }
-    const int tx = (luma ? t.x - X0 : t.x - (X0 >> 1)) + 4, ty = luma ? t.y - Y0 : t.y - (Y0 >> 1);
-    uint16_t *dst = luma ? &L.ty[ty][tx] : &L.tc[comp][ty][tx];
-    const int16_t *rp = luma ? &L.ry[ty][tx - 4] : &L.rc[comp][ty][tx - 4];
-    const int dstride = luma ? CT_YS : CT_CS, rstride = luma ? CT_S : CT_S / 2;
-    const int res_mask = (t.flags & OVHIP_IF_ISP) ? t.isp_res_mask : 0xff, res_l2pb = (t.flags & OVHIP_IF_ISP) ? t.isp_log2_pb : 6;
-    const int ciip_wt = res_only ? 0 : t.ciip_wt;
-    if (!res_only) {
-        if (luma) {
-            if (t.flags & OVHIP_IF_ISP) fetch_refs_isp(s, ya, t, lane);
-            else fetch_refs(s, ya, t.x, t.y, w, h, 4, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, (t.flags & OVHIP_IF_MIP) ? 0 : t.mrl_idx, lane);
-            wave_sync();
-            if (t.flags & OVHIP_IF_MIP) pred_mip(s, t, st, lane);
-            else pred_regular(s, t, true, st, lane);
-        } else {
-            const TileAcc ca = { &L.tc[comp][0][0], L.top_c[comp], CT_CS, X0 >> 1, Y0 >> 1 };
-            if (t.mode >= 67) pred_cclm<NPL>(s, ya, ca, t, log2_ctu, st, lane);
-            else {
-                fetch_refs(s, ca, t.x, t.y, w, h, 2, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, 0, lane);
-                wave_sync();
-                pred_regular(s, t, false, st, lane);
-            }
-        }
-        wave_sync();
-    }
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int p = st.p0 + lane + 64 * i, x = p & (w - 1), y = p >> l2w;
-        if (p >= st.p1) break;
-        uint16_t *d = dst + y * dstride + x;
-        int v = res_only ? (int)*d : (int)s.pred[p - st.p0];
-        if (ciip_wt) v = (v * ciip_wt + (int)*d * (4 - ciip_wt) + 2) >> 2;
-        if (has_res && ((res_mask >> (x >> res_l2pb)) & 1)) { const int r = rp[y * rstride + x]; v = ov_clip_bd(v + (scaled ? res_scale(r, scale) : r)); }
-        *d = (uint16_t)v;
-    }
+        for (int k = 0; k < 4; ++k) if (k < min(L.n_sc, 4) && L.sc_idx[k] == t.c_scale) found = L.sc_val[k];
+        scale = found >= 0 ? found : scales[t.c_scale];          // not from this CTU: k_lmcs_scale wrote it before this launch
+    } else if (it.scaled) scale = t.c_scale;
+    const int tx = (it.luma ? t.x - X0 : t.x - (X0 >> 1)) + 4, ty = it.luma ? t.y - Y0 : t.y - (Y0 >> 1);
+    uint16_t *dst = it.luma ? &L.ty[ty][tx] : &L.tc[comp][ty][tx];
+    const int16_t *rp = it.luma ? &L.ry[ty][tx - 4] : &L.rc[comp][ty][tx - 4];
+    const int dstride = it.luma ? CT_YS : CT_CS, rstride = it.luma ? CT_S : CT_S / 2;
+    const TileAcc ca = { &L.tc[comp][0][0], L.top_c[comp], CT_CS, X0 >> 1, Y0 >> 1 };
+    if (!it.res_only) predict_item<NPL>(s, t, it, ya, ca, log2_ctu, DirectRefs(), lane);
+    int rv[NPL], dv[NPL];
+    epilogue_load(rv, dv, it, dst, dstride, rp, rstride, t.log2_w, lane);
+    epilogue_store(s, rv, dv, it, scale, dst, dstride, t.log2_w, lane);
 }
 
 __global__ __launch_bounds__(256) void k_intra_ctu(ovhip_pic pic, ovhip_pic res, const ovhip_itask *__restrict__ tasks,
@@ -717,13 +754,7 @@ __global__ __launch_bounds__(256) void k_intra_ctu(ovhip_pic pic, ovhip_pic res,
                     __builtin_amdgcn_s_sleep(8);
                 }
             }
-            if (!__all(ok)) {
-                if (lane == 0) {
-                    __hip_atomic_store(sync, 1u + blockIdx.x, RLX_AGENT);
-                    if (abort_mirror) __hip_atomic_store(abort_mirror, 1u + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    L.abort = 1;
-                }
-            }
+            if (!__all(ok)) { flow_give_up(sync, abort_mirror, lane); if (lane == 0) L.abort = 1; }
             else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         }
         __syncthreads();
@@ -942,7 +973,6 @@ __device__ __forceinline__ bool fetch_refs_tagged(IntraLds &s, const uint16_t *p
 #define FNPL   (FSTRIP / 64)
 #define FJ8    ((FSTRIP + 511) / 512)        // runs of 8 / of 4 samples per lane
 #define FJ4    ((FSTRIP + 255) / 256)
-#define FREG   (8 * FJ8 > FNPL ? 8 * FJ8 : FNPL)
 
 // 16 lanes per task, 16 tasks per workgroup (one 64-lane workgroup per task was 16k tiny workgroups for a B picture: 10 us)
 __global__ __launch_bounds__(256) void k_intra_flow_prepare(const ovhip_itask *__restrict__ tasks, uint32_t n, FlowState fs, unsigned epoch)
@@ -985,15 +1015,121 @@ __global__ __launch_bounds__(256) void k_flow_untag(ovhip_pic pic, const ovhip_i
     }
 }
 
-// (fp: the state words an item polls, as word offsets from the state block: 7 KB of LDS per workgroup instead of 8.9.  The 109 VGPRs
-//  hold the kernel at 16 workgroups per compute unit; amdgpu_waves_per_eu(5, 8) gives 96 VGPRs = 20 per compute unit = room for
+// How the flow kernel gets the arms of a regular block: out of tagged samples.  Plain pointers and integers BY VALUE: the same
+// members as references to the kernel's argument structs cost k_intra_flow 48 bytes of scratch per lane and 6 VGPRs.
+struct TaggedRefs {
+    const unsigned *state_y, *state_c;      // state words of the luma plane and of the item's chroma plane
+    int w4; unsigned epoch; unsigned *sync;
+#ifdef OVHIP_CTU_PROBE
+    u64 *stamp;
+    __device__ __forceinline__ void arms_ready() const { *stamp = wall_clock64(); }
+#else
+    __device__ __forceinline__ void arms_ready() const { }
+#endif
+    __device__ __forceinline__ bool operator()(IntraLds &s, const AgentAcc acc, int unit, const ovhip_itask &t, int mrl, int lane) const
+    {
+        return fetch_refs_tagged(s, acc.p, acc.stride, unit == 4 ? state_y : state_c, w4, epoch, sync, unit, t.x, t.y, 1 << t.log2_w, 1 << t.log2_h,
+                                 t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, mrl, lane);
+    }
+};
+
+// The tail of an item of the flow launch.  A lane owns runs of G consecutive samples of a row (G = 8, 4 or 1 by block width):
+// residual and output move as 16- / 8-byte accesses -- a write-through store is one fabric write whatever its size, and 2-byte ones
+// cost 12x the time per byte.  The loads go out before the dependency wait and land in raw dwords (FlowRaw: FDW per operand, shared
+// by the three widths; unpacked in the epilogue, so that nothing waits for them before the wait has ended); flow_store finishes
+// and stores behind the prediction.  Both ends are selected by the same wave-uniform run length.
+#define FDW (4 * FJ8 > FNPL ? 4 * FJ8 : FNPL)
+struct FlowRaw { uint32_t r[FDW], d[FDW]; };                 // residual, old sample: G / 2 dwords per run (G = 1: one sample per dword)
+template <int G> struct FlowRun {
+    static constexpr int N = G == 8 ? FJ8 : (G == 4 ? FJ4 : FNPL), DW = G == 1 ? 1 : G / 2;
+    typedef uint32_t vec __attribute__((ext_vector_type(DW), aligned(4)));
+    static __device__ __forceinline__ int p_of(const Item &it, int j, int lane) { return it.p0 + (lane + 64 * j) * G; }
+};
+
+template <int G>
+__device__ __forceinline__ void flow_load(FlowRaw &q, const Item &it, const uint16_t *dst, int dstride, const int16_t *rp, int rstride, int l2w, int lane)
+{
+    typedef FlowRun<G> R;
+#pragma unroll
+    for (int j = 0; j < R::N; ++j) {
+        const int p = min(R::p_of(it, j, lane), it.p1 - G), x = p & ((1 << l2w) - 1), y = p >> l2w;      // lanes past the strip re-read its last run
+        if constexpr (G == 1) {
+            if (it.has_res) q.r[j] = (uint32_t)(int)rp[y * rstride + x];                       // residuals: the launches before
+            if (it.need_d()) q.d[j] = dst[y * dstride + x];                                    // inter prediction: likewise
+        } else {
+            typename R::vec r = 0, d = 0;
+            if (it.has_res) r = *reinterpret_cast<const typename R::vec *>(rp + y * rstride + x);
+            if (it.need_d()) d = *reinterpret_cast<const typename R::vec *>(dst + y * dstride + x);
+#pragma unroll
+            for (int e = 0; e < R::DW; ++e) { q.r[R::DW * j + e] = r[e]; q.d[R::DW * j + e] = d[e]; }
+        }
+    }
+}
+
+// clip(pred + res) = min(max(sat16(pred + res), 0), 1023) on a sample PAIR: a saturating packed add and two packed min / max
+__device__ __forceinline__ uint32_t pk_clip_add(uint32_t pred2, uint32_t res2)
+{
+    uint32_t r;
+    asm("v_pk_add_i16 %0, %1, %2 clamp\n\tv_pk_max_i16 %0, %0, 0\n\tv_pk_min_i16 %0, %0, %3" : "=&v"(r) : "v"(pred2), "v"(res2), "v"(0x03ff03ffu));
+    return r;
+}
+
+template <int G>
+__device__ __forceinline__ void flow_store(const IntraLds &s, const FlowRaw &q, const Item &it, int scale, uint16_t *dst, int dstride, int l2w, int lane)
+{
+    typedef FlowRun<G> R;
+    const uint32_t tag2 = FLOW_TAG | (FLOW_TAG << 16);                         // every sample leaves tagged (see FLOW_TAG)
+    // The plain case -- prediction (+ residual), no blend, no residual scale, every sample of the run carries the residual -- on
+    // sample PAIRS (pk_clip_add: 4 instructions per pair against ~20 unpacked ones: a lone wave issues an instruction every ~4.5 ns
+    // and this is the chain's tail)
+    const bool plain = G > 1 && !it.ciip_wt && !it.res_only && !it.scaled && it.res_mask == 0xff;
+#pragma unroll
+    for (int j = 0; j < R::N; ++j) {
+        const int p = R::p_of(it, j, lane), x = p & ((1 << l2w) - 1), y = p >> l2w;
+        if (p >= it.p1) break;
+        typename R::vec pq = 0, out;
+        // the prediction out of LDS in ONE read
+        if constexpr (G == 1) pq = s.pred[p - it.p0];
+        else if (!it.res_only) pq = *reinterpret_cast<const typename R::vec *>(&s.pred[p - it.p0]);
+        if (plain) {
+#pragma unroll
+            for (int e = 0; e < R::DW; ++e) out[e] = (it.has_res ? pk_clip_add(pq[e], q.r[R::DW * j + e]) : pq[e]) | tag2;
+        } else {
+            // blend / residual / clip with the wave-uniform decisions outside the per-sample work (a chain of read-wait-branch per
+            // sample cost 0.8 us of the hop)
+            int v[G], rv[G], dv[G];
+#pragma unroll
+            for (int e = 0; e < G; ++e) {
+                const int sh = 16 * (e & 1), k = R::DW * j + (e >> 1);
+                rv[e] = it.res_at(x + e) ? (int)(int16_t)(q.r[k] >> sh) : 0;
+                dv[e] = (int)((q.d[k] >> sh) & 0xffff);
+                v[e] = it.res_only ? dv[e] : (int)((pq[e >> 1] >> sh) & 0xffff);
+            }
+            if (it.ciip_wt) for (int e = 0; e < G; ++e) v[e] = (v[e] * it.ciip_wt + dv[e] * (4 - it.ciip_wt) + 2) >> 2;
+            if (it.has_res) {
+                if (it.scaled) for (int e = 0; e < G; ++e) v[e] = ov_clip_bd(v[e] + res_scale(rv[e], scale));
+                else           for (int e = 0; e < G; ++e) v[e] = ov_clip_bd(v[e] + rv[e]);
+            }
+#pragma unroll
+            for (int e = 0; e < R::DW; ++e) out[e] = ((uint32_t)v[2 * e] | (G > 1 ? (uint32_t)v[G > 1 ? 2 * e + 1 : 0] << 16 : 0u)) | tag2;
+        }
+        uint16_t *o = dst + y * dstride + x;                                                  // write-through
+        if constexpr (G == 8) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(o), "v"(out) : "memory");
+        else if constexpr (G == 4) asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(o), "v"(out) : "memory");
+        else __hip_atomic_store(o, (uint16_t)out[0], RLX_AGENT);
+    }
+}
+
+// (fp: the state words an item polls, as word offsets from the state block: 7 KB of LDS per workgroup instead of 8.9.  The worker
+//  budget of the launch rests on 4 waves per SIMD = 16 one-wave workgroups per compute unit, which the kernel's 106 VGPRs as
+//  built (up to 128) and 16 x 7088 bytes of LDS allow; amdgpu_waves_per_eu(5, 8) gave 96 VGPRs = 20 per compute unit = room for
 //  1280 workers per launch, measured: the B picture's pass 157 -> 142 us alone, the I picture's 2.32 -> 2.44 us per level, the stream
 //  the same within its noise -- not taken)
 struct FlowLds { IntraLds s; uint32_t fp[FLOW_MAX_FP]; int abort; };
 
 __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res, const ovhip_itask *__restrict__ tasks, const uint32_t *__restrict__ items,
                                                    uint32_t n_items, const ovhip_lmcs_region *__restrict__ regs, LmcsWnd wnd, int16_t *scales,
-                                                   int log2_ctu, FlowState fs, unsigned epoch, unsigned *sync, unsigned *abort_mirror, int nap)
+                                                   int log2_ctu, FlowState fs, unsigned epoch, unsigned *sync, unsigned *abort_mirror)
 {
     __shared__ FlowLds L;
     IntraLds &s = L.s;
@@ -1014,63 +1150,27 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
     for (uint32_t bid = blockIdx.x; bid < n_items; bid += gridDim.x) {
     if (bid != blockIdx.x) wave_sync();                    // the tiles of the item before are dead
     FPROBE_DECL;
-    const uint32_t item = items[bid];
-    const ovhip_itask t = tasks[item & 0xffffff];
-    const int strip = (item >> 24) & 0x1f, comp = (item >> 29) & 1;
-    const int l2w = t.log2_w, w = 1 << l2w, h = 1 << t.log2_h, npx = w * h;
-    const bool luma = t.kind == OVHIP_IT_LUMA, region = t.kind == OVHIP_IT_REGION, res_only = t.kind == OVHIP_IT_RES_C;
-    const bool lm = t.kind == OVHIP_IT_CHROMA && t.mode >= 67 && !(t.flags & OVHIP_IF_BDPCM);
+    const FlowItem fi = flow_item_unpack(items[bid]);
+    const ovhip_itask t = tasks[fi.task];
+    const int comp = fi.plane;
+    const Item it = item_of<FSTRIP>(t, fi.strip, comp);
+    const int l2w = t.log2_w, w = 1 << l2w, h = 1 << t.log2_h;
+    const bool luma = it.luma;
     const unsigned pending = 2 * epoch;
     const int w4 = fs.w4;
-    Strip st; st.p0 = strip * FSTRIP; st.p1 = min(npx, st.p0 + FSTRIP);
-    const bool has_res = t.flags & (luma ? OVHIP_IF_RES_Y : (comp ? OVHIP_IF_RES_CR : OVHIP_IF_RES_CB));
-    if (res_only && !has_res) continue;
+    if (it.skip()) continue;
 
     // ---- what does not depend on the other ordered tasks (residual, inter prediction): requested before the wait ----
     uint16_t *pl = luma ? pic.y : (comp ? pic.cr : pic.cb);
     const int dstride = luma ? pic.stride_y : pic.stride_c, rstride = luma ? res.stride_y : res.stride_c;
     uint16_t *dst = pl + t.y * dstride + t.x;
     const int16_t *rp = reinterpret_cast<const int16_t *>(luma ? res.y : (comp ? res.cr : res.cb)) + t.y * rstride + t.x;
-    const int ciip_wt = res_only ? 0 : t.ciip_wt;
-    const bool need_d = ciip_wt || res_only;
-    const int res_mask = (t.flags & OVHIP_IF_ISP) ? t.isp_res_mask : 0xff, res_l2pb = (t.flags & OVHIP_IF_ISP) ? t.isp_log2_pb : 6;
-    // A lane owns runs of G consecutive samples of a row (G = 8, 4 or 1 by block width): residual and output move as 16- / 8-byte
-    // accesses -- a write-through store is one fabric write whatever its size, and 2-byte ones cost 12x the time per byte
-    const int l2g = w >= 8 ? 3 : (w == 4 ? 2 : 0);
-    auto p_of = [&](int i) { return st.p0 + (((lane + 64 * (i >> l2g)) << l2g) | (i & ((1 << l2g) - 1))); };
-    // (raw vectors: unpacked in the epilogue, so that nothing waits for these loads before the dependency wait has ended)
-    flow_u4 rq8[FJ8], dq8[FJ8];
-    flow_u2 rq4[FJ4], dq4[FJ4];
-    int rv1[FNPL], dv1[FNPL];
-#pragma unroll
-    for (int j = 0; j < FJ8; ++j) { rq8[j] = 0; dq8[j] = 0; }
-#pragma unroll
-    for (int j = 0; j < FJ4; ++j) { rq4[j] = 0; dq4[j] = 0; }
-#pragma unroll
-    for (int i = 0; i < FNPL; ++i) { rv1[i] = 0; dv1[i] = 0; }
-    if (!region && (has_res || need_d)) {
-        if (l2g == 3) {
-#pragma unroll
-            for (int j = 0; j < FJ8; ++j) {
-                const int p = min(p_of(8 * j), st.p1 - 8), x = p & (w - 1), y = p >> l2w;       // lanes past the strip re-read its last run
-                if (has_res) rq8[j] = *reinterpret_cast<const flow_u4 *>(rp + y * rstride + x);
-                if (need_d) dq8[j] = *reinterpret_cast<const flow_u4 *>(dst + y * dstride + x);
-            }
-        } else if (l2g == 2) {
-#pragma unroll
-            for (int j = 0; j < FJ4; ++j) {
-                const int p = min(p_of(4 * j), st.p1 - 4), x = p & (w - 1), y = p >> l2w;
-                if (has_res) rq4[j] = *reinterpret_cast<const flow_u2 *>(rp + y * rstride + x);
-                if (need_d) dq4[j] = *reinterpret_cast<const flow_u2 *>(dst + y * dstride + x);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < FNPL; ++i) {
-                const int p = min(p_of(i), st.p1 - 1), x = p & (w - 1), y = p >> l2w;
-                if (has_res) rv1[i] = rp[y * rstride + x];                       // residuals: the launches before
-                if (need_d) dv1[i] = dst[y * dstride + x];                       // inter prediction: likewise
-            }
-        }
+    const int run = w >= 8 ? 8 : (w == 4 ? 4 : 1);         // samples per access, see flow_load
+    FlowRaw raw = { };
+    if (!it.region) {
+        if (run == 8) flow_load<8>(raw, it, dst, dstride, rp, rstride, l2w, lane);
+        else if (run == 4) flow_load<4>(raw, it, dst, dstride, rp, rstride, l2w, lane);
+        else flow_load<1>(raw, it, dst, dstride, rp, rstride, l2w, lane);
     }
     // ---- nap before the first poll (VERDICT r3 #5b).  An item of level L reads what an item of level L - 1 writes, and that one what
     // level L - 2 wrote: when this worker finished an item of level P just now, the inputs of its next item cannot exist before
@@ -1095,7 +1195,7 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
         for (int i = lane; i < count; i += 64) L.fp[nfp + i] = (uint32_t)(base - sync) + (uint32_t)((uy + i * dy) * w4 + ux + i * dx);
         nfp += max(count, 0);
     };
-    if (region) {
+    if (it.region) {
         const ovhip_lmcs_region g = regs[t.c_scale];
         if (g.n_abv) add_run(fs.y, g.x >> 2, (g.y >> 2) - 1, g.n_abv, 1, 0);
         if (g.n_lft) add_run(fs.y, (g.x >> 2) - 1, g.y >> 2, g.n_lft, 0, 1);
@@ -1119,8 +1219,8 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
     } else {
         unsigned *fc = fs.c[comp];
         const int ux = t.x >> 1, uy = t.y >> 1, nux = max(1, w >> 1), nuy = max(1, h >> 1);
-        if (!res_only) {
-            if (lm) {
+        if (!it.res_only) {
+            if (it.lm) {
                 // co-located luma, its left / above margin, and the chroma + luma neighbours the parameters are derived from
                 const int na = t.mode == 69 ? t.avl_abv : (t.avl_abv ? nux : 0), nl = t.mode == 68 ? t.avl_lft : (t.avl_lft ? nuy : 0);
                 for (int r = 0; r < nuy && nfp < FLOW_MAX_FP; ++r) add_run(fs.y, ux, uy + r, nux, 1, 0);
@@ -1128,7 +1228,7 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
                 if (t.avl_abv) { add_run(fs.y, ux, uy - 1, max(na, nux), 1, 0); add_run(fc, ux, uy - 1, na, 1, 0); }
             }      // (the other chroma modes wait on their tagged reference samples, like luma)
         }
-        if ((t.flags & OVHIP_IF_RES_SCALE) && (t.flags & OVHIP_IF_SCALE_IDX)) add_run(fs.reg, t.c_scale, 0, 1, 1, 0);
+        if (it.scale_idx) add_run(fs.reg, t.c_scale, 0, 1, 1, 0);
     }
     wave_sync();
     FPROBE(1);
@@ -1140,28 +1240,19 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
             unsigned cur = __hip_atomic_load(f, RLX_AGENT);
             while (cur == pending) {
                 if (++spins > SPIN_LIMIT) { ok = false; break; }
-                if (nap == 0) __builtin_amdgcn_s_sleep(4);
-                else if (nap == 1) __builtin_amdgcn_s_sleep(16);
-                else if (nap == 2) __builtin_amdgcn_s_sleep(64);
-                else { if (spins < 8) __builtin_amdgcn_s_sleep(4); else if (spins < 32) __builtin_amdgcn_s_sleep(16); else __builtin_amdgcn_s_sleep(64); }
+                __builtin_amdgcn_s_sleep(4);            // (16 the same; 64 and exponential back-off measured 6 % slower)
                 // (the abort word and the state word in ONE round trip)
                 const unsigned stop = __hip_atomic_load(sync, RLX_AGENT);
                 cur = __hip_atomic_load(f, RLX_AGENT);
                 if (stop != 0) { ok = false; break; }
             }
         }
-        if (!__all(ok)) {
-            if (lane == 0) {
-                __hip_atomic_store(sync, 1u + blockIdx.x, RLX_AGENT);
-                if (abort_mirror) __hip_atomic_store(abort_mirror, 1u + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            return;
-        }
+        if (!__all(ok)) { flow_give_up(sync, abort_mirror, lane); return; }
     }
     FPROBE(2);
 
     const AgentAcc ya = { pic.y, pic.stride_y };
-    if (region) {
+    if (it.region) {
         const int v = region_scale(ya, regs[t.c_scale], wnd, lane);
         if (lane == 0) {
             __hip_atomic_store(scales + t.c_scale, (int16_t)v, RLX_AGENT);
@@ -1170,169 +1261,50 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
         }
         continue;
     }
-    const bool scaled = !luma && (t.flags & OVHIP_IF_RES_SCALE);
     // (the derived scale is requested here and first looked at in the epilogue: no wait in front of the reference fetch)
-    const bool scale_idx = scaled && (t.flags & OVHIP_IF_SCALE_IDX);
     int scale_ld = 0;
-    if (scale_idx) scale_ld = (int)__hip_atomic_load(scales + t.c_scale, RLX_AGENT);
-    if (!res_only) {
-        if (luma) {
-            if ((t.flags & OVHIP_IF_ISP) && (t.y & 3)) {
-                // thin_row: the last row of the partition above (same coding unit, same 4x4 units as this block) arrives TAGGED -- every
-                // luma item stores its samples with FLOW_TAG -- and is polled itself, as fetch_refs_tagged polls a regular block's arms
-                //  EVERY row the earlier partitions wrote into this partition's unit row, not only the last one: the partition
-                // holding the unit's last row marks the unit "written" for the word readers (CCLM items, chroma-scale regions, ISP arms of
-                // other coding units), who then read all four rows -- so all of them must have been observed by the marker
-                const int cbw = 1 << t.isp_log2_cb_w;
-                const int ry0 = (int)t.y & ~3, nry = (int)t.y - ry0;          // 1 .. 3 rows
-                const uint16_t *row = pic.y + ry0 * pic.stride_y + (t.x - t.isp_off_x);
-                unsigned spins = 0;
-                bool ok = true;
-                for (;;) {
-                    unsigned v = FLOW_TAG;
-                    for (int rr = 0; rr < nry; ++rr) v &= lane < cbw ? (unsigned)__hip_atomic_load(row + rr * pic.stride_y + lane, RLX_AGENT) : FLOW_TAG;
-                    if (!__any(!(v & FLOW_TAG))) break;
-                    const unsigned stop = __hip_atomic_load(sync, RLX_AGENT);
-                    if (__any(++spins > SPIN_LIMIT || stop != 0)) { ok = false; break; }
-                    __builtin_amdgcn_s_sleep(FLOW_POLL_GAP);
-                }
-                if (!ok) {
-                    if (lane == 0) {
-                        __hip_atomic_store(sync, 1u + blockIdx.x, RLX_AGENT);
-                        if (abort_mirror) __hip_atomic_store(abort_mirror, 1u + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    return;
-                }
+    if (it.scale_idx) scale_ld = (int)__hip_atomic_load(scales + t.c_scale, RLX_AGENT);
+    if (!it.res_only) {
+        if (luma && (t.flags & OVHIP_IF_ISP) && (t.y & 3)) {
+            // thin_row: the last row of the partition above (same coding unit, same 4x4 units as this block) arrives TAGGED -- every
+            // luma item stores its samples with FLOW_TAG -- and is polled itself, as fetch_refs_tagged polls a regular block's arms
+            //  EVERY row the earlier partitions wrote into this partition's unit row, not only the last one: the partition
+            // holding the unit's last row marks the unit "written" for the word readers (CCLM items, chroma-scale regions, ISP arms of
+            // other coding units), who then read all four rows -- so all of them must have been observed by the marker
+            const int cbw = 1 << t.isp_log2_cb_w;
+            const int ry0 = (int)t.y & ~3, nry = (int)t.y - ry0;          // 1 .. 3 rows
+            const uint16_t *row = pic.y + ry0 * pic.stride_y + (t.x - t.isp_off_x);
+            unsigned spins = 0;
+            bool ok = true;
+            for (;;) {
+                unsigned v = FLOW_TAG;
+                for (int rr = 0; rr < nry; ++rr) v &= lane < cbw ? (unsigned)__hip_atomic_load(row + rr * pic.stride_y + lane, RLX_AGENT) : FLOW_TAG;
+                if (!__any(!(v & FLOW_TAG))) break;
+                const unsigned stop = __hip_atomic_load(sync, RLX_AGENT);
+                if (__any(++spins > SPIN_LIMIT || stop != 0)) { ok = false; break; }
+                __builtin_amdgcn_s_sleep(FLOW_POLL_GAP);
             }
-            if (t.flags & OVHIP_IF_ISP) fetch_refs_isp(s, ya, t, lane);
-            else if (!fetch_refs_tagged(s, pic.y, pic.stride_y, fs.y, w4, epoch, sync, 4, t.x, t.y, w, h, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft,
-                                        (t.flags & OVHIP_IF_MIP) ? 0 : t.mrl_idx, lane)) {
-                if (lane == 0) {
-                    __hip_atomic_store(sync, 1u + blockIdx.x, RLX_AGENT);
-                    if (abort_mirror) __hip_atomic_store(abort_mirror, 1u + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                return;
-            }
-            wave_sync();
-            FPROBE(3);
-            if (t.flags & OVHIP_IF_MIP) pred_mip(s, t, st, lane);
-            else pred_regular(s, t, true, st, lane);
-        } else {
-            const AgentAcc ca = { pl, pic.stride_c };
-            if (lm) pred_cclm<FNPL>(s, ya, ca, t, log2_ctu, st, lane);
-            else {
-                if (!fetch_refs_tagged(s, pl, pic.stride_c, fs.c[comp], w4, epoch, sync, 2, t.x, t.y, w, h, t.flags & OVHIP_IF_CORNER, t.avl_abv, t.avl_lft, 0, lane)) {
-                    if (lane == 0) {
-                        __hip_atomic_store(sync, 1u + blockIdx.x, RLX_AGENT);
-                        if (abort_mirror) __hip_atomic_store(abort_mirror, 1u + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                    return;
-                }
-                wave_sync();
-                pred_regular(s, t, false, st, lane);
-            }
+            if (!ok) { flow_give_up(sync, abort_mirror, lane); return; }
         }
-        wave_sync();
+        // (regular blocks, luma and chroma, wait on their tagged reference samples: TaggedRefs)
+        TaggedRefs refs = { fs.y, fs.c[comp], w4, epoch, sync };
+#ifdef OVHIP_CTU_PROBE
+        refs.stamp = &fprobe_[3];
+#endif
+        const AgentAcc ca = { pl, pic.stride_c };
+        if (!predict_item<FNPL>(s, t, it, ya, ca, log2_ctu, refs, lane)) { flow_give_up(sync, abort_mirror, lane); return; }
     }
     FPROBE(4);
-    // epilogue of a run of n samples (registers i0 .. i0 + n - 1): prediction out of LDS in ONE read, then blend / residual / clip
-    // with the wave-uniform decisions outside the per-sample work (a chain of read-wait-branch per sample cost 0.8 us of the hop)
-    const int scale = scale_idx ? scale_ld : (scaled ? (int)t.c_scale : 0);
-    const uint32_t tag2 = FLOW_TAG | (FLOW_TAG << 16);                         // every sample leaves tagged (see FLOW_TAG)
-    // (j: the run's index among the lane's runs; x: its first column, for the ISP partitions' residual mask)
-    auto finish = [&](int j, int p, int x, int n, int *v) {
-        int rv[8], dv[8];
-        for (int e = 0; e < n; ++e) {
-            const uint32_t rw = n == 8 ? rq8[j][e >> 1] : (n == 4 ? rq4[j][e >> 1] : (uint32_t)rv1[j]);
-            const uint32_t dw = n == 8 ? dq8[j][e >> 1] : (n == 4 ? dq4[j][e >> 1] : (uint32_t)dv1[j]);
-            const int r = n == 1 ? (int)(int16_t)rw : (int)(int16_t)(rw >> (16 * (e & 1)));
-            rv[e] = ((res_mask >> ((x + e) >> res_l2pb)) & 1) ? r : 0;
-            dv[e] = n == 1 ? (int)(dw & 0xffff) : (int)((dw >> (16 * (e & 1))) & 0xffff);
-        }
-        if (res_only) {
-            for (int e = 0; e < n; ++e) v[e] = dv[e];
-        } else if (n == 8) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(&s.pred[p - st.p0]);
-            const uint32_t qq[4] = { q.x, q.y, q.z, q.w };
-            for (int e = 0; e < 8; ++e) v[e] = (int)((qq[e >> 1] >> (16 * (e & 1))) & 0xffff);
-        } else if (n == 4) {
-            const uint2 q = *reinterpret_cast<const uint2 *>(&s.pred[p - st.p0]);
-            const uint32_t qq[2] = { q.x, q.y };
-            for (int e = 0; e < 4; ++e) v[e] = (int)((qq[e >> 1] >> (16 * (e & 1))) & 0xffff);
-        } else v[0] = s.pred[p - st.p0];
-        if (ciip_wt) for (int e = 0; e < n; ++e) v[e] = (v[e] * ciip_wt + dv[e] * (4 - ciip_wt) + 2) >> 2;
-        if (has_res) {
-            if (scaled) for (int e = 0; e < n; ++e) v[e] = ov_clip_bd(v[e] + res_scale(rv[e], scale));
-            else        for (int e = 0; e < n; ++e) v[e] = ov_clip_bd(v[e] + rv[e]);
-        }
-    };
-    // The plain case -- prediction (+ residual), no blend, no residual scale, every sample of the run carries the residual -- on
-    // sample PAIRS: clip(pred + res) = min(max(sat16(pred + res), 0), 1023) is a saturating packed add and two packed min / max
-    // (4 instructions per pair against ~20 unpacked ones: a lone wave issues an instruction every ~4.5 ns and this is the chain's tail)
-    const bool plain = !ciip_wt && !res_only && !scaled && res_mask == 0xff;
-    auto pk_clip_add = [&](uint32_t pred2, uint32_t res2) {
-        uint32_t r;
-        asm("v_pk_add_i16 %0, %1, %2 clamp\n\tv_pk_max_i16 %0, %0, 0\n\tv_pk_min_i16 %0, %0, %3" : "=&v"(r) : "v"(pred2), "v"(res2), "v"(0x03ff03ffu));
-        return r;
-    };
-    if (l2g == 3) {
-#pragma unroll
-        for (int j = 0; j < FJ8; ++j) {
-            const int p = p_of(8 * j), x = p & (w - 1), y = p >> l2w;
-            if (p >= st.p1) break;
-            flow_u4 q;
-            if (plain) {
-                const uint4 pq = *reinterpret_cast<const uint4 *>(&s.pred[p - st.p0]);
-                q[0] = pq.x; q[1] = pq.y; q[2] = pq.z; q[3] = pq.w;
-                if (has_res) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) q[e] = pk_clip_add(q[e], rq8[j][e]);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) q[e] |= tag2;
-            } else {
-                int v[8];
-                finish(j, p, x, 8, v);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) q[e] = ((uint32_t)v[2 * e] | ((uint32_t)v[2 * e + 1] << 16)) | tag2;
-            }
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst + y * dstride + x), "v"(q) : "memory");      // write-through
-        }
-    } else if (l2g == 2) {
-#pragma unroll
-        for (int j = 0; j < FJ4; ++j) {
-            const int p = p_of(4 * j), x = p & (w - 1), y = p >> l2w;
-            if (p >= st.p1) break;
-            flow_u2 q;
-            if (plain) {
-                const uint2 pq = *reinterpret_cast<const uint2 *>(&s.pred[p - st.p0]);
-                q[0] = pq.x; q[1] = pq.y;
-                if (has_res) { q[0] = pk_clip_add(q[0], rq4[j][0]); q[1] = pk_clip_add(q[1], rq4[j][1]); }
-                q[0] |= tag2; q[1] |= tag2;
-            } else {
-                int v[4];
-                finish(j, p, x, 4, v);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) q[e] = ((uint32_t)v[2 * e] | ((uint32_t)v[2 * e + 1] << 16)) | tag2;
-            }
-            asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(dst + y * dstride + x), "v"(q) : "memory");
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < FNPL; ++i) {
-            const int p = p_of(i), x = p & (w - 1), y = p >> l2w;
-            if (p >= st.p1) break;
-            int v[1];
-            finish(i, p, x, 1, v);
-            __hip_atomic_store(dst + y * dstride + x, (uint16_t)(v[0] | (tag2 & 0xffff)), RLX_AGENT);
-        }
-    }
+    const int scale = it.scale_idx ? scale_ld : (it.scaled ? (int)t.c_scale : 0);
+    if (run == 8) flow_store<8>(s, raw, it, scale, dst, dstride, l2w, lane);
+    else if (run == 4) flow_store<4>(s, raw, it, scale, dst, dstride, l2w, lane);
+    else flow_store<1>(s, raw, it, scale, dst, dstride, l2w, lane);
     FPROBE(5);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FPROBE(6);
     // ---- this strip's units are written ----
     {
-        const int sh = luma ? 2 : 1, y0s = st.p0 >> l2w, y1s = (st.p1 + w - 1) >> l2w;
+        const int sh = luma ? 2 : 1, y0s = it.p0 >> l2w, y1s = (it.p1 + w - 1) >> l2w;
         const int ux0 = t.x >> sh, uy0 = (t.y + y0s) >> sh, nx = max(1, w >> sh), ny = max(1, (y1s - y0s) >> sh);
         unsigned *fb = luma ? fs.y : fs.c[comp];
         const int l2nx = ilog2(nx);                                             // block widths are powers of two
@@ -1373,9 +1345,7 @@ extern "C" int ovhip_intra_level_launch(ovhip_ctx *ctx, const ovhip_pic *pic, co
     if (!n) return OVHIP_OK;
     if (!d_tasks || log2_ctu_s < 5 || log2_ctu_s > 7 || (geom & 3) == 3)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_intra_level_launch: bad arguments", hipSuccess);
-    LmcsWnd wnd;
-    memset(&wnd, 0, sizeof(wnd));
-    if (luts) { memcpy(wnd.bnd, luts->wnd_bnd, sizeof(wnd.bnd)); wnd.min_idx = luts->min_idx; wnd.max_idx = luts->max_idx; wnd.crs_offset = luts->crs_offset; }
+    const LmcsWnd wnd = lmcs_wnd_of(luts);
     hipLaunchKernelGGL(k_intra_level, dim3(n, 1u << (geom & 3), (geom & 16) ? 2 : 1), dim3(64), 0, ctx->stream, *pic, *res, d_tasks, n, d_regions, wnd,
                        d_scales, log2_ctu_s);
     OV_LAUNCH_CHECK(ctx, "k_intra_level");
@@ -1411,9 +1381,7 @@ extern "C" int ovhip_intra_ctu_launch(ovhip_ctx *ctx, const ovhip_pic *pic, cons
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_intra_ctu_launch: bad arguments", hipSuccess);
     if ((pic->w & 7) || (pic->h & 1) || (pic->stride_y & 3) || (pic->stride_c & 3) || ((uintptr_t)pic->y & 7) || ((uintptr_t)pic->cb & 7) || ((uintptr_t)pic->cr & 7))
         return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_intra_ctu_launch: picture width must be a multiple of 8 and the planes 8-byte aligned", hipSuccess);
-    LmcsWnd wnd;
-    memset(&wnd, 0, sizeof(wnd));
-    if (luts) { memcpy(wnd.bnd, luts->wnd_bnd, sizeof(wnd.bnd)); wnd.min_idx = luts->min_idx; wnd.max_idx = luts->max_idx; wnd.crs_offset = luts->crs_offset; }
+    const LmcsWnd wnd = lmcs_wnd_of(luts);
     const int ncx = (pic->w + (1 << log2_ctu_s) - 1) >> log2_ctu_s;
     hipLaunchKernelGGL(k_intra_ctu, dim3(n_ctus), dim3(256), 0, ctx->stream, *pic, *res, d_tasks, d_ctus, d_regions, wnd, d_scales, log2_ctu_s, d_sync, epoch, ncx,
                        abort_mirror);
@@ -1425,19 +1393,18 @@ extern "C" int ovhip_intra_ctu_launch(ovhip_ctx *ctx, const ovhip_pic *pic, cons
 // (<= cap) or 0 when the picture cannot take this path (more tasks or strips than an item word holds).  (Until round 5 a prediction
 // block less than a unit high -- horizontal ISP partitions of 1 or 2 rows, which share a state word with the partitions around them --
 // sent the whole picture to the per-level launches; they now hand over inside the unit by tagged samples, see k_intra_flow.)
-// ovhip_intra_flow_items_ (internal, ovvc_picture.hip): the count even where it exceeds cap -- only the first cap items are written,
-// items may be null with cap 0 -- and 0 only where the path is refused.  The count does not depend on the order of the tasks.
+// (ovhip_intra_flow_items_: flow_state.hip.h)
 extern "C" size_t ovhip_intra_flow_items_(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap)
 {
     size_t k = 0;
     for (size_t i = 0; sorted && i < n; ++i) {
         const ovhip_itask &t = sorted[i];
-        if (i >= (1u << 24)) return 0;
-        if (t.kind == OVHIP_IT_REGION) { if (k < cap) items[k] = (uint32_t)i; ++k; continue; }
+        if (i >= FLOW_ITEM_MAX_TASKS) return 0;
+        if (t.kind == OVHIP_IT_REGION) { if (k < cap) items[k] = flow_item_pack((uint32_t)i, 0, 0); ++k; continue; }
         const int npx = 1 << (t.log2_w + t.log2_h), strips = (npx + FSTRIP - 1) / FSTRIP, comps = t.kind == OVHIP_IT_LUMA ? 1 : 2;
-        if (strips > 32) return 0;                                   // the item word has five bits for the strip (a 64x64 block: 16)
+        if (strips > FLOW_ITEM_MAX_STRIPS) return 0;
         for (int st = 0; st < strips; ++st)
-            for (int c = 0; c < comps; ++c) { if (k < cap) items[k] = (uint32_t)i | ((uint32_t)st << 24) | ((uint32_t)c << 29); ++k; }
+            for (int c = 0; c < comps; ++c) { if (k < cap) items[k] = flow_item_pack((uint32_t)i, st, c); ++k; }
     }
     return k;
 }
@@ -1468,9 +1435,7 @@ extern "C" int ovhip_intra_flow_launch(ovhip_ctx *ctx, const ovhip_pic *pic, con
     if (!n_items) return OVHIP_OK;
     if (!d_tasks || !d_items || !d_state || !epoch || epoch >= 0x7fffffffu || log2_ctu_s < 5 || log2_ctu_s > 7)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_intra_flow_launch: bad arguments", hipSuccess);
-    LmcsWnd wnd;
-    memset(&wnd, 0, sizeof(wnd));
-    if (luts) { memcpy(wnd.bnd, luts->wnd_bnd, sizeof(wnd.bnd)); wnd.min_idx = luts->min_idx; wnd.max_idx = luts->max_idx; wnd.crs_offset = luts->crs_offset; }
+    const LmcsWnd wnd = lmcs_wnd_of(luts);
     const FlowState fs = flow_state_of(d_state, pic->w, pic->h);
     if (prepare) {
         hipLaunchKernelGGL(k_intra_flow_prepare, dim3((n_tasks + 15) / 16), dim3(256), 0, ctx->stream, d_tasks, n_tasks, fs, epoch);
@@ -1479,11 +1444,10 @@ extern "C" int ovhip_intra_flow_launch(ovhip_ctx *ctx, const ovhip_pic *pic, con
 #ifdef OVHIP_CTU_PROBE
     if (hipMemcpyToSymbolAsync(HIP_SYMBOL(g_probe_items), &d_items, sizeof(d_items), 0, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return OVHIP_ELAUNCH;
 #endif
-    const int nap = 0;          // poll back-off variant: 0 = s_sleep 4 between polls (16 the same; 64 and exponential back-off measured 6 % slower)
     // n_workers workgroups take the items in turn (k_intra_flow); 0 or >= n_items: one workgroup per item
     const uint32_t grid = (n_workers > 0 && (uint32_t)n_workers < n_items) ? (uint32_t)n_workers : n_items;
     hipLaunchKernelGGL(k_intra_flow, dim3(grid), dim3(64), 0, ctx->stream, *pic, *res, d_tasks, d_items, n_items, d_regions, wnd, d_scales, log2_ctu_s, fs,
-                       epoch, d_state, abort_mirror, nap);
+                       epoch, d_state, abort_mirror);
     OV_LAUNCH_CHECK(ctx, "k_intra_flow");
     return OVHIP_OK;
 }

@@ -12,10 +12,10 @@
 //                    read + 2 bytes written per luma sample.
 #include "ovvc_common.hip.h"
 #include "flow_state.hip.h"
+#include "lmcs_wnd.hip.h"
 
 namespace {
 
-struct LmcsWnd { uint16_t bnd[17]; int min_idx, max_idx, crs_offset; };
 #ifndef LMCS_ROWS
 #define LMCS_ROWS 4
 #endif
@@ -47,18 +47,7 @@ __global__ __launch_bounds__(64) void k_lmcs_scale(ovhip_pic pic, const ovhip_lm
     int sum = (g.n_abv ? va : 0) + (g.n_lft ? vl : 0);
 #pragma unroll
     for (int m = 32; m; m >>= 1) sum += __shfl_xor(sum, m);
-    if (lane == 0) {
-        const int nb_units = (g.n_abv ? 16 : 0) + (g.n_lft ? 16 : 0);
-        int log2_nb = 0;
-        for (int v = nb_units; v; v >>= 1) ++log2_nb;         // 16 -> 5, 32 -> 6, as the reference counts
-        const int avg = log2_nb ? (sum + (1 << log2_nb)) >> (log2_nb + 1) : 512;
-        int idx = wnd.min_idx;                                // get_bwd_idx (rcn_lmcs.c:83-93)
-        for (; idx < wnd.max_idx; ++idx)
-            if (avg < wnd.bnd[idx + 1]) break;
-        idx = min(idx, 15);
-        const int wnd_sz = (int)wnd.bnd[idx + 1] - (int)wnd.bnd[idx];
-        scales[bid] = (int16_t)(wnd_sz == 0 ? 1 << 11 : (1 << (OV_BD - 4 + 11)) / (wnd_sz + wnd.crs_offset));
-    }
+    if (lane == 0) scales[bid] = (int16_t)lmcs_scale_of_sum(wnd, sum, g.n_abv, g.n_lft);
 }
 
 typedef uint32_t lm_u2 __attribute__((ext_vector_type(2), aligned(4)));
@@ -178,9 +167,7 @@ static int lmcs_scale_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_l
     if (!n_regions && !n_tasks) return OVHIP_OK;
     if (n_regions && (!d_regions || !d_scales)) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_lmcs_scale_launch: null buffer", hipSuccess);
     if (n_tasks && (!d_tasks || !d_state || !epoch)) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_lmcs_scale_prepare_launch: bad arguments", hipSuccess);
-    LmcsWnd w;
-    for (int i = 0; i < 17; ++i) w.bnd[i] = luts->wnd_bnd[i];
-    w.min_idx = luts->min_idx; w.max_idx = luts->max_idx; w.crs_offset = luts->crs_offset;
+    const LmcsWnd w = lmcs_wnd_of(luts);
     FlowState fs;
     memset(&fs, 0, sizeof(fs));
     if (n_tasks) fs = flow_state_of(d_state, pic->w, pic->h);

@@ -7,6 +7,7 @@
 // the D2H of the motion vectors DMVR refined (the `OVMV *mv0, *mv1` in/out contract of rcn_dmvr_mv_refine,
 // rcn_structures.h:628-632).  Host code above the launches is plain C; nothing here falls back to a CPU path.
 #include "ovvc_common.hip.h"
+#include "flow_state.hip.h"
 #include <stdlib.h>
 
 extern "C" int ovhip_dmvr_search_launch(ovhip_ctx *ctx, const ovhip_pic *geom, const ovhip_pic *refs, uint32_t n_refs,
@@ -201,7 +202,6 @@ extern "C" int ovhip_itx_launch_ex_(ovhip_ctx *ctx, const ovhip_pic *dst, const 
 
 extern "C" int ovhip_sao_launch_rows(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *src, const ovhip_sao_ctu *d_params, int32_t log2_ctu_s, int32_t row0, int32_t row1);
 extern "C" int ovhip_alf_launch_rows(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *src, const ovhip_alf_pic *alf, int32_t row0, int32_t row1);
-extern "C" size_t ovhip_intra_flow_items_(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap);
 
 #define CHK(x) do { int r__ = (x); if (r__ != OVHIP_OK) return r__; } while (0)
 
@@ -289,7 +289,7 @@ int flow_widest(const ovhip_itask *sorted, const uint32_t *items, size_t n_items
 {
     size_t widest = 0, run = 0;
     for (size_t q = 0; q < n_items; ++q) {
-        run = (q && sorted[items[q] & 0xffffff].level == sorted[items[q - 1] & 0xffffff].level) ? run + 1 : 1;
+        run = (q && sorted[flow_item_unpack(items[q]).task].level == sorted[flow_item_unpack(items[q - 1]).task].level) ? run + 1 : 1;
         if (run > widest) widest = run;
     }
     return (int)((2 * widest + 63) & ~(size_t)63);
@@ -800,7 +800,7 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
     if ((dst->w != j->w || dst->h != j->h)) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_flush: picture size differs from the job's", hipSuccess);
     // an eager pass nobody collected (ovhip_job_dmvr_rows_begin): its copies land in arrays this flush may re-allocate
     { const int64_t c_ = ovhip_job_dmvr_rows_collect(j); if (c_ < 0) return (int)c_; }
-    const uint32_t stages = pr->stages ? pr->stages : 0xffffffffu;
+    const uint32_t stages = pr->stages ? pr->stages : UINT32_MAX;
     const int log2_ctu = pr->log2_ctu_s ? pr->log2_ctu_s : 7;
     if (log2_ctu < 5 || log2_ctu > 7) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_job_flush: log2_ctu_s", hipSuccess);
     const size_t n_ctu = (size_t)((j->w + (1 << log2_ctu) - 1) >> log2_ctu) * ((j->h + (1 << log2_ctu) - 1) >> log2_ctu);
@@ -1029,8 +1029,9 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
         } else {
             // ONE launch of W persistent workers (k_intra_flow): worker b takes the items b, b + W, ... in level order.  W bounds the
             // pollers of the launch, and the launches in flight together must fit the device for the forward-progress argument (an item
-            // waits only for lower items; the lowest unfinished item's worker is resident or will be): the kernel holds 109 VGPRs = 16
-            // waves per compute unit, HIP runs the process's streams on 4 hardware queues, so W = 16 CUs / 4 = 1024 on MI355X.
+            // waits only for lower items; the lowest unfinished item's worker is resident or will be): the kernel runs at 4 waves per
+            // SIMD = 16 one-wave workgroups per compute unit (106 VGPRs as built), HIP runs the process's streams on 4 hardware queues,
+            // so W = 16 CUs / 4 = 1024 on MI355X.
             // Measured on the stream of bench.py (pictures/s, second passes): one workgroup per item 2834-2890 / 0 (the device full of
             // the pollers of levels far ahead); W = 512 3280-3320 / 0; 1024 3353-3490 / 0; 2048 1561 / 9; 4096 35 / 1168 -- above
             // the bound the launches starve each other, exactly as the argument says.  Alone, a B picture's wide levels want more
@@ -1382,7 +1383,7 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
         bs->dst = *dst; bs->row_prev = 0; bs->dbf_rows = bs->sao_rows = bs->alf_rows = bs->rows_final = 0;
         memset(&bs->cur, 0, sizeof(bs->cur));
         bs->log2_ctu = log2_ctu; bs->filters_latched = 0; bs->lmcs_up = 0; bs->alf_up = 0; bs->have_luts = 0;
-        bs->stages = pr->stages ? pr->stages : 0xffffffffu;
+        bs->stages = pr->stages ? pr->stages : UINT32_MAX;
         bs->last_event = nullptr; bs->last_rows = 0; bs->keep_valid = 0;
         j->again.valid = 0; j->n_retries = 0;       // (n_mv / n_tmvp: the eager DMVR rows' -- a pass may have run before the first band)
         CHK(ordered_arm(j, &j->d_flow, ovhip_intra_flow_words(j->w, j->h)));
