@@ -1106,6 +1106,37 @@ void ovhip_md5_update(ovhip_md5_state *st, const void *data, size_t n);
 void ovhip_md5_final(ovhip_md5_state *st, uint8_t out[16]);
 
 /* ------------------------------------------------------------------------------------
+ * Output resampling: a stream that changes its coded size (RPR) can leave the device at ONE size.  Replaces pp_sample_rate_conv
+ * (pp_pic_scale.c:250-377), called once per plane by pp_process_frame (post_proc.c:116-126) when the decoder's `upscale` option is
+ * on (ovdec.c:562; ovdec.c:479 / :523 are the call sites), for up-sampling and equal size, bit-exactly -- including its phase, which
+ * is the LOW 4 (luma) / 5 (chroma) bits of the 13- / 14-bit fixed-point position.  The decoded picture is only read:
+ * references keep predicting from it at its coded size.  Film grain and SL-HDR, the other branches of pp_process_frame, are not here.
+ *
+ * `ovhip_scale_info` = struct ScalingInfo (ovdpb.h:85-93): the scaling window in chroma sample units and the SPS chroma collocation
+ * flags; what the reference passes is the picture's own (pic->scale_info).
+ *
+ * Refused: OVHIP_EUNSUP (reason in ovhip_last_error) when a scale factor of luma or chroma exceeds 1 << bits on either axis --
+ * down-sampling, where the reference switches to 12-tap tables and, for chroma phases >= 16, indexes past them; OVHIP_EINVAL when
+ * the scaling window leaves nothing, a size is not a multiple of 4 (or above 16384), a plane is missing or dst aliases src.
+ * ---------------------------------------------------------------------------------- */
+typedef struct ovhip_scale_info { uint16_t win_left, win_right, win_top, win_bottom; uint8_t chroma_hor_col, chroma_ver_col; } ovhip_scale_info;
+/* Host only (no device needed): the argument check the launch uses.  scale[4] = luma horizontal / vertical, chroma horizontal /
+ * vertical factors, ((src - window) << bits) / dst with bits = 13 (luma) / 14 (chroma); written whenever they could be derived. */
+int  ovhip_output_scale_check(int32_t src_w, int32_t src_h, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h, int32_t scale[4]);
+/* Every sample of dst (its own w x h) from src.  One launch (k_output_scale), asynchronous on the ctx stream. */
+int  ovhip_output_scale_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_scale_info *info, const ovhip_pic *dst);
+/* Synchronous conveniences: resample into a grow-only scratch picture of the context (no allocation once a size has been seen), then
+ * exactly ovhip_pic_output / ovhip_pic_digest on it; `win` applies to the resampled picture.  out_w x out_h equal to the picture's
+ * size with an empty scaling window still runs the resampler (an identity copy by its arithmetic). */
+int  ovhip_pic_output_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h,
+                             const ovhip_window *win, void *host_dst);
+int  ovhip_pic_digest_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h,
+                             const ovhip_window *win, uint8_t out16[16]);
+/* Device + page-locked bytes the context's grow-only scratch buffers hold (the synchronous conveniences above and of the output path):
+ * constant from call to call once the sizes have been seen. */
+size_t ovhip_ctx_scratch_bytes(const ovhip_ctx *ctx);
+
+/* ------------------------------------------------------------------------------------
  * TMVP motion plane.  The reference's caller stores what rcn_dmvr_mv_refine returned into the CTU-local
  * 16x16 array of 8x8 cells tmvp_mv[l].mvs (vcl_coding_unit.c:2629-2645: cell ((x0 + 7) >> 3, (y0 + 7) >> 3) of the <= 16x16
  * block, its right neighbour for 16-wide and lower neighbour(s) for 16-high blocks), and tmvp_store_mv copies rows
@@ -1320,6 +1351,12 @@ int  ovhip_frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t ro
  * parsed, row by row as they arrive, so that ITS rows reach ITS readers as early (never the picture's last band: use ovhip_frame_band). */
 int  ovhip_frame_band_upto(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, const ovhip_band_counts *upto, int32_t block);
 int  ovhip_frame_band_stats(const ovhip_frame *f, int32_t *n_bands, int32_t *n_deferred);
+/* Output at one size (what pp_process_frame does for the application when `upscale` is on, ovdec.c:479 / :523): while set, the DIGEST,
+ * PACKED and PLANES outputs of ovhip_frame_submit and of the last ovhip_frame_band deliver the picture resampled to out_w x out_h
+ * (the output's window applies to the resampled picture; for PLANES the caller's pointers describe planes of the output size).  What is
+ * published to the DPB is the decoded picture, unchanged.  (0, 0) switches it off, which is the default; info is copied (NULL: no
+ * scaling window, flags 0).  Refusals as ovhip_output_scale_check against the frame's size; a dry frame accepts the call and does nothing. */
+int  ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_scale_info *info);
 int  ovhip_frame_fail(ovhip_frame *f, int status);
 const char *ovhip_frame_last_error(const ovhip_frame *f);
 
@@ -1445,6 +1482,10 @@ int  ovhip_stream_run(ovhip_stream *s, const ovhip_stream_pic *pics, uint32_t n_
 ovhip_frame *ovhip_stream_frame(ovhip_stream *s, int dev, int thread);
 /* ahead_own_queue: streams replaced at creation / in-order streams that still share the look-ahead thread's hardware queue */
 int  ovhip_stream_queue_info(const ovhip_stream *s, int *moved, int *sharing);
+/* Output at one size: call it before a run.  The output thread's PACKED frames (its page-locked buffer, out_bytes, the file MD5) and the
+ * frame threads' DIGEST fingerprints are those of the pictures resampled to out_w x out_h; (0, 0) switches it off.  The driver still
+ * decodes pictures of one coded size (cfg.w x cfg.h). */
+int  ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, const ovhip_scale_info *info);
 /* The DPB key of picture idx of the current stream (valid while the run that decoded it kept it: OVHIP_STREAM_KEEP). */
 const void *ovhip_stream_key(const ovhip_stream *s, uint32_t idx);
 /* test hook: the next flush of `job` that has a flow launch is ABORTED for real (the device's abort word is set before the

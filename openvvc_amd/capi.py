@@ -318,6 +318,12 @@ def lmcs_build(data: "LmcsData") -> "LmcsLuts":
     return out
 
 
+class ScaleInfo(C.Structure):
+    """ovhip_scale_info = struct ScalingInfo: scaling window in chroma sample units + the chroma collocation flags"""
+    _fields_ = [("win_left", C.c_uint16), ("win_right", C.c_uint16), ("win_top", C.c_uint16), ("win_bottom", C.c_uint16),
+                ("chroma_hor_col", C.c_uint8), ("chroma_ver_col", C.c_uint8)]
+
+
 class Window(C.Structure):
     """ovhip_window = OVFrame.output_window: offsets in chroma sample units"""
     _fields_ = [("offset_lft", C.c_uint16), ("offset_rgt", C.c_uint16), ("offset_abv", C.c_uint16), ("offset_blw", C.c_uint16)]
@@ -611,6 +617,13 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_stream_frame": (vp, [vp, C.c_int, C.c_int]),
         "ovhip_stream_queue_info": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
         "ovhip_stream_key": (vp, [vp, u32]),
+        "ovhip_output_scale_check": (C.c_int, [i32, i32, P(ScaleInfo), i32, i32, P(i32 * 4)]),
+        "ovhip_output_scale_launch": (C.c_int, [vp, P(Pic), P(ScaleInfo), P(Pic)]),
+        "ovhip_pic_output_scaled": (C.c_int, [vp, P(Pic), P(ScaleInfo), i32, i32, P(Window), vp]),
+        "ovhip_pic_digest_scaled": (C.c_int, [vp, P(Pic), P(ScaleInfo), i32, i32, P(Window), vp]),
+        "ovhip_ctx_scratch_bytes": (C.c_size_t, [vp]),
+        "ovhip_frame_set_output_scale": (C.c_int, [vp, i32, i32, P(ScaleInfo)]),
+        "ovhip_stream_set_output_scale": (C.c_int, [vp, i32, i32, P(ScaleInfo)]),
     }
     ab_build = "OVVC_HIP_LIB_NAME" in os.environ       # tools/ab_lib.sh: an OLDER build of the library beside the current one (its newer entry points are not called)
     for name, (res, args) in sigs.items():
@@ -649,6 +662,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_frame_ref_at", "ovhip_frame_dmvr_rows", "ovhip_frame_dmvr_rows_begin", "ovhip_frame_dmvr_rows_collect", "ovhip_frame_submit", "ovhip_frame_fail", "ovhip_frame_last_error",
     "ovhip_calllog_create", "ovhip_calllog_destroy", "ovhip_calllog_reset", "ovhip_calllog_data", "ovhip_rec_set_calllog", "ovhip_calllog_replay",
     "ovhip_stream_create", "ovhip_stream_destroy", "ovhip_stream_run", "ovhip_stream_frame", "ovhip_stream_key", "ovhip_stream_queue_info",
+    "ovhip_output_scale_check", "ovhip_output_scale_launch", "ovhip_pic_output_scaled", "ovhip_pic_digest_scaled",
+    "ovhip_frame_set_output_scale", "ovhip_stream_set_output_scale", "ovhip_ctx_scratch_bytes",
 ]
 
 

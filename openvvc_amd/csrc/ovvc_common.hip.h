@@ -29,6 +29,7 @@ struct ovhip_ctx {
     // synchronise the whole device every time a picture is output
     void *scratch_d; size_t scratch_d_cap;
     void *scratch_h; size_t scratch_h_cap;       // page-locked
+    void *scale_d; size_t scale_d_cap;           // the scratch PICTURE of the scaled outputs (kernels_scale.hip), grow-only likewise
     hipEvent_t ev_sync;            // the synchronous conveniences wait for an event behind their last command (measured in round 4: hipStreamSynchronize from
                                    // 16 frame threads cost the stream a fifth of its rate, an event wait nothing)
     char err[256];

@@ -12,6 +12,9 @@ void ovhip_dpb_rearm_(ovhip_dpb *d);
 /* CLOCK_MONOTONIC seconds at which the frame's last picture was complete on the device / published (the stream driver's timeline) */
 double ovhip_frame_published_at(const ovhip_frame *f);
 double ovhip_frame_done_at(const ovhip_frame *f);
+/* kernels_scale.hip: `pic` resampled to out_w x out_h in the context's scratch picture, which is handed out in *scaled (valid until the
+ * context's next scaled output); asynchronous on the context's stream */
+int  ovhip_scaled_scratch_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h, ovhip_pic *scaled);
 #ifdef __cplusplus
 }
 #endif

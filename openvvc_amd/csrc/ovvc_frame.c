@@ -44,6 +44,9 @@ struct ovhip_frame {
     ovhip_band_counts band_prev;
     int32_t band_row_prev, band_rows_posted, dry_row_prev2;
     int n_bands, n_deferred;
+    /* ovhip_frame_set_output_scale: the outputs deliver the picture resampled to out_w x out_h (0: off) */
+    int32_t out_w, out_h;
+    ovhip_scale_info out_info;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -367,6 +370,47 @@ ovhip_frame_fail(ovhip_frame *f, int status)
 }
 
 int
+ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_scale_info *info)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (f->dry) return OVHIP_OK;          /* a dry frame has no output */
+    if (!out_w && !out_h) { f->out_w = f->out_h = 0; return OVHIP_OK; }
+    ovhip_scale_info si;
+    int32_t scale[4];
+    memset(&si, 0, sizeof(si));
+    if (info) si = *info;
+    const int r = ovhip_output_scale_check(f->w, f->h, &si, out_w, out_h, scale);
+    if (r != OVHIP_OK) return r;
+    f->out_w = out_w; f->out_h = out_h; f->out_info = si;
+    return OVHIP_OK;
+}
+
+/* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the decoded picture as it is, or
+ * (ovhip_frame_set_output_scale) resampled into the context's scratch picture first -- f->dst itself is only read */
+static int
+frame_output(ovhip_frame *f, ovhip_frame_output *out)
+{
+    if (!f->out_w) {
+        switch (out->mode) {
+        case OVHIP_OUT_DIGEST: return ovhip_pic_digest(f->ctx, &f->dst, &out->window, out->digest);
+        case OVHIP_OUT_PLANES: return ovhip_pic_download(f->ctx, &f->dst, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
+        case OVHIP_OUT_PACKED: return ovhip_pic_output(f->ctx, &f->dst, &out->window, out->packed);
+        default: return OVHIP_EINVAL;
+        }
+    }
+    switch (out->mode) {
+    case OVHIP_OUT_DIGEST: return ovhip_pic_digest_scaled(f->ctx, &f->dst, &f->out_info, f->out_w, f->out_h, &out->window, out->digest);
+    case OVHIP_OUT_PLANES: {
+        ovhip_pic scaled;
+        const int r = ovhip_scaled_scratch_(f->ctx, &f->dst, &f->out_info, f->out_w, f->out_h, &scaled);
+        return r != OVHIP_OK ? r : ovhip_pic_download(f->ctx, &scaled, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
+    }
+    case OVHIP_OUT_PACKED: return ovhip_pic_output_scaled(f->ctx, &f->dst, &f->out_info, f->out_w, f->out_h, &out->window, out->packed);
+    default: return OVHIP_EINVAL;
+    }
+}
+
+int
 ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const ovhip_job_params *params, ovhip_frame_output *out)
 {
     if (!f || !params || !f->live) return OVHIP_EINVAL;
@@ -409,12 +453,7 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
     (void)publish(f, r);
     if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
         const double to0 = PT_ON() ? mono_s() : 0.0;
-        switch (out->mode) {
-        case OVHIP_OUT_DIGEST: r = ovhip_pic_digest(f->ctx, &f->dst, &out->window, out->digest); break;
-        case OVHIP_OUT_PLANES: r = ovhip_pic_download(f->ctx, &f->dst, out->y, out->cb, out->cr, out->stride_y, out->stride_c); break;
-        case OVHIP_OUT_PACKED: r = ovhip_pic_output(f->ctx, &f->dst, &out->window, out->packed); break;
-        default: r = OVHIP_EINVAL;
-        }
+        r = frame_output(f, out);
         if (PT_ON()) f->pt_output += mono_s() - to0;
         if (r != OVHIP_OK) fail(f, r, "picture output");
     }
@@ -591,12 +630,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     f->pn_pics++;
     if (r == OVHIP_OK && !f->dry && out && out->mode != OVHIP_OUT_NONE) {
         PT0();
-        switch (out->mode) {
-        case OVHIP_OUT_DIGEST: r = ovhip_pic_digest(f->ctx, &f->dst, &out->window, out->digest); break;
-        case OVHIP_OUT_PLANES: r = ovhip_pic_download(f->ctx, &f->dst, out->y, out->cb, out->cr, out->stride_y, out->stride_c); break;
-        case OVHIP_OUT_PACKED: r = ovhip_pic_output(f->ctx, &f->dst, &out->window, out->packed); break;
-        default: r = OVHIP_EINVAL;
-        }
+        r = frame_output(f, out);
         PT(f->pt_output);
         if (r != OVHIP_OK) fail(f, r, "picture output");
     }

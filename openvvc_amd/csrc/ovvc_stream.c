@@ -48,6 +48,7 @@ struct ovhip_stream {
                                            * ask the DPB for it: a key the DPB never saw is an error there, not a wait) */
     pthread_mutex_t begun_mtx; pthread_cond_t begun_cnd;
     int n_moved, n_sharing;               /* streams replaced to clear the look-ahead thread's hardware queue / still sharing it */
+    int32_t out_w, out_h; ovhip_scale_info out_info;     /* ovhip_stream_set_output_scale (0: off) */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -328,7 +329,8 @@ output_thread(void *argp)
         int r = ovhip_dpb_acquire(s->dpb, key_of(s, idx), p->device, &pic, NULL);
         if (r != OVHIP_OK) { if (!rs->abort) run_fail(rs, r, "output: picture not available", ""); break; }
         ovhip_ctx *ctx = s->out_ctx[p->device];
-        r = ovhip_pic_output(ctx, &pic, &s->cfg.window, s->out_host);
+        r = s->out_w ? ovhip_pic_output_scaled(ctx, &pic, &s->out_info, s->out_w, s->out_h, &s->cfg.window, s->out_host)
+                     : ovhip_pic_output(ctx, &pic, &s->cfg.window, s->out_host);
         if (r == OVHIP_OK) {
             if (rs->flags & OVHIP_STREAM_FILE_MD5) ovhip_md5_update(&rs->md5, s->out_host, s->out_host_bytes);
             rs->res->out_bytes += s->out_host_bytes;
@@ -450,6 +452,39 @@ int ovhip_stream_queue_info(const ovhip_stream *s, int *moved, int *sharing)
     if (!s) return OVHIP_EINVAL;
     if (moved) *moved = s->n_moved;
     if (sharing) *sharing = s->n_sharing;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, const ovhip_scale_info *info)
+{
+    if (!s) return OVHIP_EINVAL;
+    const int on = out_w || out_h;
+    ovhip_scale_info si;
+    memset(&si, 0, sizeof(si));
+    if (on) {
+        int32_t scale[4];
+        if (info) si = *info;
+        const int r = ovhip_output_scale_check(s->cfg.w, s->cfg.h, &si, out_w, out_h, scale);
+        if (r != OVHIP_OK) return r;
+    }
+    if (s->cfg.output == OVHIP_OUT_PACKED) {
+        /* the output thread's page-locked frame follows the output size */
+        const size_t bytes = on ? ovhip_output_bytes(out_w, out_h, &s->cfg.window) : ovhip_output_bytes(s->cfg.w, s->cfg.h, &s->cfg.window);
+        if (!bytes) return OVHIP_EINVAL;
+        if (bytes != s->out_host_bytes) {
+            void *p = ovhip_host_alloc(bytes);
+            if (!p) return OVHIP_ENOMEM;
+            ovhip_host_free(s->out_host);
+            s->out_host = p; s->out_host_bytes = bytes;
+        }
+    }
+    /* the frame threads' DIGEST path */
+    for (int i = 0; i < s->n_dev * s->tpd; ++i) {
+        const int r = ovhip_frame_set_output_scale(s->frames[i], out_w, out_h, &si);
+        if (r != OVHIP_OK) return r;
+    }
+    s->out_w = on ? out_w : 0; s->out_h = on ? out_h : 0; s->out_info = si;
     return OVHIP_OK;
 }
 

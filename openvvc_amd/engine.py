@@ -29,6 +29,10 @@ class Context:
         if r != 0:
             raise EngineError(f"{what}: {r}: {self.lib.ovhip_last_error(self.h).decode()}")
 
+    def scratch_bytes(self) -> int:
+        """bytes held by the context's grow-only scratch buffers (ovhip_ctx_scratch_bytes)"""
+        return int(self.lib.ovhip_ctx_scratch_bytes(self.h))
+
     def sync(self):
         self._chk(self.lib.ovhip_ctx_sync(self.h), "sync")
 
@@ -279,6 +283,33 @@ class DevPic:
         win = capi.Window(*window)
         out = (C.c_uint8 * 16)()
         self.ctx._chk(self.ctx.lib.ovhip_pic_digest(self.ctx.h, C.byref(self.s), C.byref(win), out), "pic_digest")
+        return bytes(out)
+
+    def scale_into(self, dst: "DevPic", scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
+        """Resample this picture into dst (its own size) as the reference's output resampler does (ovhip_output_scale_launch);
+        scale_window = (left, right, top, bottom) in chroma sample units, col = the chroma collocation flags.  Asynchronous."""
+        info = capi.ScaleInfo(*scale_window, *col)
+        r = self.ctx.lib.ovhip_output_scale_launch(self.ctx.h, C.byref(self.s), C.byref(info), C.byref(dst.s))
+        if check:
+            self.ctx._chk(r, "output_scale")
+        return r
+
+    def output_scaled(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), window=(0, 0, 0, 0)) -> np.ndarray:
+        """output() of the picture resampled to out_w x out_h; `window` crops the resampled picture"""
+        info, win = capi.ScaleInfo(*scale_window, *col), capi.Window(*window)
+        n = self.ctx.lib.ovhip_output_bytes(out_w, out_h, C.byref(win))
+        if not n:
+            raise EngineError("output window leaves nothing")
+        out = np.empty(n // 2, np.uint16)
+        self.ctx._chk(self.ctx.lib.ovhip_pic_output_scaled(self.ctx.h, C.byref(self.s), C.byref(info), out_w, out_h, C.byref(win), out.ctypes.data),
+                      "pic_output_scaled")
+        return out
+
+    def digest_scaled(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), window=(0, 0, 0, 0)) -> bytes:
+        info, win = capi.ScaleInfo(*scale_window, *col), capi.Window(*window)
+        out = (C.c_uint8 * 16)()
+        self.ctx._chk(self.ctx.lib.ovhip_pic_digest_scaled(self.ctx.h, C.byref(self.s), C.byref(info), out_w, out_h, C.byref(win), out),
+                      "pic_digest_scaled")
         return bytes(out)
 
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
@@ -711,6 +742,14 @@ class Frame:
     def fail(self, status: int = -3):
         self.lib.ovhip_frame_fail(self.f, status)
 
+    def set_output_scale(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
+        """the frame's outputs deliver the picture resampled to out_w x out_h; (0, 0) switches it off"""
+        info = capi.ScaleInfo(*scale_window, *col)
+        r = self.lib.ovhip_frame_set_output_scale(self.f, out_w, out_h, C.byref(info))
+        if r < 0 and check:
+            raise EngineError(f"frame_set_output_scale: {r}")
+        return r
+
     def job(self) -> "Job":
         """the frame's own job as an engine.Job view (not owned)"""
         j = Job.__new__(Job)
@@ -759,6 +798,14 @@ class Stream:
         if self.s:
             self.lib.ovhip_stream_destroy(self.s)
             self.s = None
+
+    def set_output_scale(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
+        """before a run: the PACKED frames / DIGEST fingerprints are those of the pictures resampled to out_w x out_h; (0, 0): off"""
+        info = capi.ScaleInfo(*scale_window, *col)
+        r = self.lib.ovhip_stream_set_output_scale(self.s, out_w, out_h, C.byref(info))
+        if r < 0 and check:
+            raise EngineError(f"stream_set_output_scale: {r}")
+        return r
 
     def queue_info(self):
         """(streams replaced to clear the look-ahead thread's hardware queue, in-order streams still sharing it)"""

@@ -1540,6 +1540,52 @@ ovhip_shim_frame_digest(const OVCTUDec *c, const OVFrame *frame, uint8_t out[16]
     return ovhip_pic_digest(ctx, &pic, &w, out);
 }
 
+/* The same at ONE output size, for a stream that changes its coded size: what pp_process_frame (post_proc.c:116-126, called at
+ * ovdec.c:479 / :523 when the decoder's `upscale` option is on) does on the host with pp_sample_rate_conv, on the device picture instead.
+ * scale_info = the picture's own (pic->scale_info), out_w x out_h = the frame pool's size.  The whole resampled frame is delivered: the
+ * frame's output_window describes the coded picture, and the reference's post-processed frame does not carry it over (post_proc.c:89-129). */
+static ovhip_scale_info
+scale_info_of(const struct ScalingInfo *si)
+{
+    ovhip_scale_info o;
+    memset(&o, 0, sizeof(o));
+    if (si) {
+        o.win_left = si->scaling_win_left; o.win_right = si->scaling_win_right;
+        o.win_top = si->scaling_win_top; o.win_bottom = si->scaling_win_bottom;
+        o.chroma_hor_col = si->chroma_hor_col_flag; o.chroma_ver_col = si->chroma_ver_col_flag;
+    }
+    return o;
+}
+
+size_t
+ovhip_shim_frame_bytes_scaled(const OVFrame *frame, int out_w, int out_h)
+{
+    (void)frame;
+    return ovhip_output_bytes(out_w, out_h, NULL);
+}
+
+int
+ovhip_shim_frame_output_scaled(const OVCTUDec *c, const OVFrame *frame, const struct ScalingInfo *scale_info, int out_w, int out_h, void *dst)
+{
+    (void)c;
+    ovhip_pic pic;
+    ovhip_ctx *ctx = dst ? out_ctx_of(frame, &pic) : NULL;
+    if (!ctx) return OVHIP_EINVAL;
+    const ovhip_scale_info si = scale_info_of(scale_info);
+    return ovhip_pic_output_scaled(ctx, &pic, &si, out_w, out_h, NULL, dst);
+}
+
+int
+ovhip_shim_frame_digest_scaled(const OVCTUDec *c, const OVFrame *frame, const struct ScalingInfo *scale_info, int out_w, int out_h, uint8_t out[16])
+{
+    (void)c;
+    ovhip_pic pic;
+    ovhip_ctx *ctx = out ? out_ctx_of(frame, &pic) : NULL;
+    if (!ctx) return OVHIP_EINVAL;
+    const ovhip_scale_info si = scale_info_of(scale_info);
+    return ovhip_pic_digest_scaled(ctx, &pic, &si, out_w, out_h, NULL, out);
+}
+
 /* picture-level side information of the flush / of a band.  by_flags: the filters are on when the slice says so (a band is submitted
  * before every row's hooks have run; the parameter arrays hold what the hooks have delivered, which is what the band's filters reach) */
 static void

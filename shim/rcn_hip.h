@@ -85,5 +85,12 @@ size_t ovhip_shim_frame_bytes(const struct Frame *frame);
 int  ovhip_shim_frame_output(const struct OVCTUDec *ctudec, const struct Frame *frame, void *dst);
 /* MD5 over the per-row MD5 digests of the cropped frame (include/ovvc_hip.h, "Output path"): only 16 bytes leave the device. */
 int  ovhip_shim_frame_digest(const struct OVCTUDec *ctudec, const struct Frame *frame, uint8_t out[16]);
+/* The same resampled on the device to out_w x out_h (the frame pool's size): what pp_process_frame does with pp_sample_rate_conv when the
+ * decoder's `upscale` option is on (ovdec.c:479 / :523, post_proc.c:116-126).  scale_info: the picture's own (pic->scale_info).  The
+ * whole resampled frame is delivered, no window; down-sampling is refused (OVHIP_EUNSUP). */
+struct ScalingInfo;
+size_t ovhip_shim_frame_bytes_scaled(const struct Frame *frame, int out_w, int out_h);
+int  ovhip_shim_frame_output_scaled(const struct OVCTUDec *ctudec, const struct Frame *frame, const struct ScalingInfo *scale_info, int out_w, int out_h, void *dst);
+int  ovhip_shim_frame_digest_scaled(const struct OVCTUDec *ctudec, const struct Frame *frame, const struct ScalingInfo *scale_info, int out_w, int out_h, uint8_t out[16]);
 
 #endif
