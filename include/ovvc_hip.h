@@ -241,6 +241,55 @@ typedef struct ovhip_rpr_unit {
 } ovhip_rpr_unit;
 
 /* ------------------------------------------------------------------------------------
+ * Affine unit that reads a reference of another size: <= 16x16 luma samples of an affine CU of which at
+ * least one used list is scaled -- ovhip_aff_unit's shape with the per-list data of ovhip_rpr_side.  Every
+ * 4x4 luma sub-block is a 4x4 PU of its own to the reference (rcn_mcp_b_l(2,2) / rcn_prof_mcp_b_l into
+ * rcn_mcp_rpr_l / rcn_mc_rpr_b_l / rcn_mc_rpr_prof_b_l, rcn_inter.c:2815-2918, :2524-2649): its own anchor
+ * after clip_rpr_position, the 4x4 filter sets 3..5; every 4x4 chroma block of an 8x8 luma area is
+ * rcn_mcp_b_c(3,3) into rcn_mcp_rpr_c / rcn_mc_rpr_b_c (:2920-2966) with sets 0..2.  PROF refines the
+ * unscaled side of a mixed bi-prediction only (rcn_prof_mcp_bi_l, :1729-1819).  Produced by
+ * ovhip_rec_affine_cu() on a recorder with OVHIP_RPR_TOOL_AFFINE; replaces the same calls of
+ * drv_affine_mvp.c:3264-3411 as ovhip_aff_unit.  48 bytes.
+ *
+ * Side arena (int32, the arena of ovhip_rec_aff_side): at side_off, for each luma sub-block in raster order
+ * 4 words {a0, b0, a1, b1}: a scaled list's clipped luma anchor (ref_pos x, y; 1/2^18 sample), an unscaled
+ * list's clip_mv()'d vector (4x4 block), an unused list's zeros; then for each 8x8-luma chroma block 4 words:
+ * the clipped chroma anchor (1/2^19 chroma sample) or the clip_mv()'d averaged vector (8x8 block).  At
+ * prof_off (only read with OVHIP_AFFR_PROF): struct PROFInfo as for ovhip_aff_unit.
+ * ---------------------------------------------------------------------------------- */
+enum {                        /* ovhip_aff_rpr_unit.flags */
+    OVHIP_AFFR_S0        = 1, /* list 0 is scaled                                                 */
+    OVHIP_AFFR_S1        = 2, /* list 1 is scaled                                                 */
+    OVHIP_AFFR_PROF      = 4, /* the CU went through rcn_affine_prof_mcp_b_l                      */
+    OVHIP_AFFR_NO_CHROMA = 8, /* = OVHIP_MC_NO_CHROMA                                             */
+    OVHIP_AFFR_LMCS      = 16 /* = OVHIP_MC_LMCS                                                  */
+};
+
+typedef struct ovhip_aff_rpr_list {
+    uint16_t step_x, step_y;  /* scaled: ((scale + 8) >> 4) << 4; unscaled: 0                          */
+    uint8_t  filt;            /* scaled: luma filter set, horizontal | vertical << 4 (3..5: flag_4x4)  */
+    uint8_t  filt_c;          /* scaled: chroma filter set, horizontal | vertical << 4 (0..2)          */
+    uint8_t  ref;             /* slot in the launch's reference table                                  */
+    uint8_t  pad;
+} ovhip_aff_rpr_list;
+
+typedef struct ovhip_aff_rpr_unit {
+    uint16_t x, y;            /* luma position in the picture                                    */
+    uint8_t  w, h;            /* luma size, multiples of 8, <= 16; 4x4 (with OVHIP_AFFR_NO_CHROMA): a lone 4x4 luma PU */
+    uint8_t  dir;             /* 1, 2, 3                                                         */
+    uint8_t  flags;           /* OVHIP_AFFR_*                                                    */
+    int8_t   w0, w1;          /* bi weights as in ovhip_mc_unit                                  */
+    uint8_t  prof_dir;        /* bi-prediction: lists PROF is applied to (bit0 L0, bit1 L1): unscaled ones only */
+    uint8_t  ident_c;         /* per chroma block: identical motion -> uni-prediction from L1    */
+    uint16_t ident_l;         /* per luma sub-block (no PROF only): same                          */
+    uint16_t pad0;
+    uint32_t side_off;        /* int32 index of the unit's anchors / vectors in the side arena   */
+    uint32_t prof_off;        /* int32 index of the CU's PROFInfo in the side arena              */
+    ovhip_aff_rpr_list s[2];
+    uint32_t pad[2];
+} ovhip_aff_rpr_unit;
+
+/* ------------------------------------------------------------------------------------
  * CIIP blend unit: dst = (intra * wt + inter * (4 - wt) + 2) >> 2 over one CU, luma and chroma
  * (put_weighted_ciip_pixels rcn_mc.c:1611-1628 driven by rcn_ciip_weighted_sum rcn_inter.c:2968-3009).
  * The inter prediction is what the MC launch left in `dst` (rcn_ciip / rcn_ciip_b record the PU
@@ -662,10 +711,25 @@ int   ovhip_rec_affine_cu(ovhip_recorder *rec, const ovhip_affine_desc *cu);
 int   ovhip_rec_cu_inter(ovhip_recorder *rec, const ovhip_pu_desc *pu, const ovhip_affine_desc *aff);
 /* Reference picture resampling: the scale of reference-table slot `slot` (0..255) for the picture being recorded; NULL
  * restores the default (unscaled, what every slot is after ovhip_rec_create / ovhip_rec_reset).  ovhip_rec_pu and
- * ovhip_rec_cu_inter then emit ovhip_rpr_unit for PUs that read a scaled slot.  Still refused with OVHIP_EUNSUP (the
+ * ovhip_rec_cu_inter then emit ovhip_rpr_unit for PUs that read a scaled slot.  Refused with OVHIP_EUNSUP (the
  * reason in ovhip_rec_refusal): DMVR / BDOF with a scaled reference, affine CUs with a scaled reference, 4x4 PUs with a
- * scaled reference, a slot whose scale is 1 but whose size differs from the picture's.  Returns 0 or <0. */
+ * scaled reference (these two unless ovhip_rec_set_rpr_tools opted in), a slot whose scale is 1 but whose size differs from
+ * the picture's.  Returns 0 or <0. */
 int   ovhip_rec_set_ref_scale(ovhip_recorder *rec, int32_t slot, const ovhip_ref_scale *scale);
+/* Opt-in to the prediction tools under reference picture resampling that need arrays a caller of the plain v9 interface does
+ * not know (it would leave their CUs unpredicted): a property of the caller, it survives ovhip_rec_reset.  mask = 0 (the
+ * default) refuses as described above.
+ *   OVHIP_RPR_TOOL_AFFINE  affine CUs with a scaled reference become ovhip_aff_rpr_unit: read with ovhip_rec_aff_rpr_units,
+ *                          launched by ovhip_mca_rpr_launch: rcn_affine_mcp_b_l / _prof_mcp_b_l / _mcp_b_c on scaled lists
+ *   OVHIP_RPR_TOOL_PU4x4   a 4x4 luma-only PU (planes == 1: rcn_mcp_b_l(2,2), the unpatched caller's affine fallback) with a
+ *                          scaled reference becomes an ovhip_rpr_unit with the filter sets 3..5 -- or, where its bi-prediction
+ *                          mixes a scaled and an unscaled list, a one-sub-block ovhip_aff_rpr_unit: the reference filters the
+ *                          unscaled side of a 4x4 block with the 6-tap set (rcn_mc.c:457), which k_mc_rpr does not hold.
+ *                          With chroma it stays refused
+ * Returns 0 or <0 (unknown bits). */
+#define OVHIP_RPR_TOOL_AFFINE 1u
+#define OVHIP_RPR_TOOL_PU4x4  2u
+int   ovhip_rec_set_rpr_tools(ovhip_recorder *rec, uint32_t mask);
 /* Why the last OVHIP_EUNSUP of this recorder was returned ("" when none since create / reset). */
 const char *ovhip_rec_refusal(const ovhip_recorder *rec);
 /* rcn_ciip_weighted_sum: mode_abv / mode_lft = part_map.cu_mode_x[x_right >> log2_min_cb] /
@@ -719,7 +783,7 @@ int   ovhip_rec_dbf_mv_prepass_view(const ovhip_dbf_view *ctu, uint64_t *bs1_ver
 int   ovhip_rec_dbf_planes(const ovhip_recorder *rec, ovhip_dbf_planes *out);
 /* Bulk append of already-recorded commands to an EMPTY recorder (replay of a stored command stream). */
 enum { OVHIP_REC_TB = 0, OVHIP_REC_COEF, OVHIP_REC_MC, OVHIP_REC_MCX, OVHIP_REC_AFF, OVHIP_REC_SIDE, OVHIP_REC_REGION,
-       OVHIP_REC_CIIP, OVHIP_REC_EDGE_V, OVHIP_REC_EDGE_H, OVHIP_REC_ITASK, OVHIP_REC_RPR };
+       OVHIP_REC_CIIP, OVHIP_REC_EDGE_V, OVHIP_REC_EDGE_H, OVHIP_REC_ITASK, OVHIP_REC_RPR, OVHIP_REC_AFF_RPR };
 int   ovhip_rec_append_raw(ovhip_recorder *rec, int which, const void *data, size_t n);
 int   ovhip_rec_set_dbf_offsets(ovhip_recorder *rec, const ovhip_dbf_offsets *offsets, int n);
 /* Access to the recorded (host) buffers. */
@@ -736,6 +800,8 @@ const ovhip_mc_unit *ovhip_rec_mc_units(const ovhip_recorder *rec, size_t *n);
 const ovhip_mc_unit *ovhip_rec_mcx_units(const ovhip_recorder *rec, size_t *n);
 const ovhip_aff_unit *ovhip_rec_aff_units(const ovhip_recorder *rec, size_t *n);
 const ovhip_rpr_unit *ovhip_rec_rpr_units(const ovhip_recorder *rec, size_t *n);
+/* The affine units that read a scaled reference (OVHIP_RPR_TOOL_AFFINE); their side data lies in ovhip_rec_aff_side(). */
+const ovhip_aff_rpr_unit *ovhip_rec_aff_rpr_units(const ovhip_recorder *rec, size_t *n);
 const ovhip_ciip_unit *ovhip_rec_ciip_units(const ovhip_recorder *rec, size_t *n);
 const int32_t        *ovhip_rec_aff_side(const ovhip_recorder *rec, size_t *n_int32);
 
@@ -819,6 +885,12 @@ int  ovhip_dmvr_search_launch(ovhip_ctx *ctx, const ovhip_pic *geom, const ovhip
 int  ovhip_mc_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs,
                          const ovhip_rpr_unit *d_units, uint32_t n_units, const uint16_t *d_lmcs_fwd_lut,
                          const ovhip_pic *intra);
+/* Affine units that read a reference of another size (ovhip_aff_rpr_unit); d_side: the DEVICE copy of ovhip_rec_aff_side().
+ * References with their OWN geometry as in ovhip_mc_rpr_launch.  Replaces the per-sub-block calls of rcn_affine_mcp_b_l /
+ * rcn_affine_prof_mcp_b_l / rcn_affine_mcp_b_c (drv_affine_mvp.c:3264-3411) where a list is scaled. */
+int  ovhip_mca_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs,
+                          const ovhip_aff_rpr_unit *d_units, uint32_t n_units, const int32_t *d_side,
+                          const uint16_t *d_lmcs_fwd_lut);
 /* CIIP: blends the intra prediction held in `intra` into `dst` (which holds the inter prediction). */
 int  ovhip_ciip_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *intra,
                        const ovhip_ciip_unit *d_units, uint32_t n_units);
@@ -1372,7 +1444,9 @@ void   ovhip_calllog_destroy(ovhip_calllog *log);
 void   ovhip_calllog_reset(ovhip_calllog *log);
 const void *ovhip_calllog_data(const ovhip_calllog *log, size_t *bytes);
 /* While a log is attached every ovhip_rec_tu / _tu_intra / _isp_cu / _pu / _affine_cu / _lmcs_region / _dbf_ctu /
- * _set_ctu_size call on `rec` is appended to it (NULL detaches). */
+ * _set_ctu_size call on `rec` is appended to it (NULL detaches).  The recorder's ovhip_rec_set_rpr_tools mask is written once per
+ * log, right before the first call that takes a path it opens (an affine CU / a lone 4x4 luma PU on a scaled slot): a replay
+ * opts its recorder in there, and the log of a stream without such calls holds no such record. */
 void   ovhip_rec_set_calllog(ovhip_recorder *rec, ovhip_calllog *log);
 /* Re-issues the calls of a serialised log on rec.  Returns the number of calls or <0 (first failing call's code). */
 int64_t ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec);

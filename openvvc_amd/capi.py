@@ -107,6 +107,22 @@ class RprUnit(C.Structure):
                 ("s", RprSide * 2)]
 
 
+class AffRprList(C.Structure):
+    _fields_ = [("step_x", C.c_uint16), ("step_y", C.c_uint16), ("filt", C.c_uint8), ("filt_c", C.c_uint8),
+                ("ref", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class AffRprUnit(C.Structure):
+    """ovhip_aff_rpr_unit: <= 16x16 luma samples of an affine CU that reads a scaled reference (48 bytes)"""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint8), ("h", C.c_uint8), ("dir", C.c_uint8), ("flags", C.c_uint8),
+                ("w0", C.c_int8), ("w1", C.c_int8), ("prof_dir", C.c_uint8), ("ident_c", C.c_uint8), ("ident_l", C.c_uint16),
+                ("pad0", C.c_uint16), ("side_off", C.c_uint32), ("prof_off", C.c_uint32), ("s", AffRprList * 2),
+                ("pad", C.c_uint32 * 2)]
+
+
+AFFR_S0, AFFR_S1, AFFR_PROF, AFFR_NO_CHROMA, AFFR_LMCS = 1, 2, 4, 8, 16
+RPR_TOOL_AFFINE, RPR_TOOL_PU4x4 = 1, 2
+OVHIP_REC_AFF_RPR = 12
 RPR_UNSCALED = 1 << 14
 RPR_S0, RPR_S1, RPR_NO_LUMA, RPR_NO_CHROMA, RPR_LMCS, RPR_HPEL_FILT, RPR_GPM = 1, 2, 4, 8, 16, 32, 128
 OVHIP_REC_RPR = 11
@@ -435,6 +451,9 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_rec_refusal": (C.c_char_p, [vp]),
         "ovhip_rec_rpr_units": (vp, [vp, P(C.c_size_t)]),
         "ovhip_mc_rpr_launch": (C.c_int, [vp, P(Pic), P(Pic), u32, vp, u32, vp, P(Pic)]),
+        "ovhip_rec_set_rpr_tools": (C.c_int, [vp, u32]),
+        "ovhip_rec_aff_rpr_units": (vp, [vp, P(C.c_size_t)]),
+        "ovhip_mca_rpr_launch": (C.c_int, [vp, P(Pic), P(Pic), u32, vp, u32, vp, vp]),
         "ovhip_rec_dbf_ctu": (C.c_int, [vp, vp]),
         "ovhip_rec_dbf_row": (C.c_int, [vp, vp, C.c_size_t]),
         "ovhip_rec_dbf_mv_prepass_view": (C.c_int, [vp, vp, vp, vp]),
@@ -645,6 +664,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_free", "ovhip_h2d", "ovhip_d2h", "ovhip_pic_alloc", "ovhip_pic_free", "ovhip_pic_upload",
     "ovhip_pic_download", "ovhip_itx_launch", "ovhip_mc_launch",
     "ovhip_rec_set_ref_scale", "ovhip_rec_refusal", "ovhip_rec_rpr_units", "ovhip_mc_rpr_launch",
+    "ovhip_rec_set_rpr_tools", "ovhip_rec_aff_rpr_units", "ovhip_mca_rpr_launch",
     "ovhip_rec_create_ex", "ovhip_rec_set_dense_dbf_planes", "ovhip_rec_dbf_edges", "ovhip_dbf_launch_edges_ex",
     "ovhip_dmvr_search_launch", "ovhip_rec_append_raw", "ovhip_rec_set_dbf_offsets", "ovhip_rec_tu_intra", "ovhip_rec_itasks", "ovhip_rec_itasks_sorted", "ovhip_itx_launch_classes_res", "ovhip_intra_level_launch", "ovhip_intra_level_geom", "ovhip_intra_sync_words", "ovhip_intra_ctu_launch", "ovhip_intra_flow_words", "ovhip_intra_flow_items", "ovhip_intra_flow_launch",
     "ovhip_rec_itask_levels", "ovhip_rec_isp_cu", "ovhip_isp_geometry", "ovhip_rec_itasks_by_ctu", "ovhip_rec_set_ctu_size", "ovhip_job_bind", "ovhip_job_create", "ovhip_job_destroy", "ovhip_job_recorder", "ovhip_job_begin",
@@ -675,6 +695,16 @@ def rpr_units(lib, rec) -> list:
         return []
     raw = C.string_at(ptr, n.value * C.sizeof(RprUnit))
     return [RprUnit.from_buffer_copy(raw, i * C.sizeof(RprUnit)) for i in range(n.value)]
+
+
+def aff_rpr_units(lib, rec) -> list:
+    """Copies of the ovhip_aff_rpr_unit array a recorder holds (affine CUs on scaled references)."""
+    n = C.c_size_t(0)
+    ptr = lib.ovhip_rec_aff_rpr_units(rec, C.byref(n))
+    if not ptr or not n.value:
+        return []
+    raw = C.string_at(ptr, n.value * C.sizeof(AffRprUnit))
+    return [AffRprUnit.from_buffer_copy(raw, i * C.sizeof(AffRprUnit)) for i in range(n.value)]
 
 
 def set_ref_scale(lib, rec, slot: int, scale_hor: int | None = None, scale_ver: int | None = None, ref_w: int = 0, ref_h: int = 0,

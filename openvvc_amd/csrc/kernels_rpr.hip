@@ -12,6 +12,8 @@
 // >> shift_mv, phase & (2^shift_mv - 1).  Unscaled side of a mixed bi unit (rcn_mcp_bidir0_l / _c): the regular 14-bit
 // prediction with the regular filters of vvc_mc_taps.h (integer phase = identity row).  Combined as rpr_sum /
 // rpr_w / gpm_weighted (rcn_mc.c:649-700, :1630-1655), then lmcs_reshape_forward.  int16 x int8 on the VALU, no MFMA.
+//
+// k_mca_rpr (second half of the file): the affine coding units that read a scaled reference, sub-block by sub-block.
 #include "mc_common.hip.h"
 #include "vvc_rpr_taps.h"
 
@@ -189,7 +191,213 @@ __global__ __launch_bounds__(64) void k_mc_rpr(ovhip_pic dst, RefTable refs, con
     }
 }
 
+// =====================================================================================================
+// Affine units that read a scaled reference (ovhip_aff_rpr_unit).  One wavefront per <= 16x16 luma area, lane = (sub-block,
+// column) as in k_mca.  To the reference every 4x4 luma sub-block is a 4x4 PU of its own (rcn_mcp_b_l(2,2) / rcn_prof_mcp_b_l,
+// rcn_inter.c:2815-2918): the recorder left its anchor after clip_rpr_position (scaled list) or its clip_mv()'d vector (unscaled
+// list) in the side arena.  Per list: the lane runs the horizontal pass of its column over the sub-block's own reference rows
+// (at most (3 * step >> 14) + 1 + 7 = 14 at 2:1, one more when the phase carries) into the sub-block's int16 LDS tile and the
+// vertical pass from it -- the lane reads back what it wrote, so the luma passes need no barrier.  Scaled lists take the "4x4"
+// filter sets 3..5 (flag_4x4), the unscaled side of a mixed bi-prediction the 6-tap filters of 4x4 blocks (put_vvc_qpel_*
+// with width == height == 4, rcn_mc.c:457, as rcn_mcp_bidir0_l / rcn_prof_mcp_bi_l call them) and, with its PROF bit, the
+// refinement on a 6x6 tile (extend_prof_buff / compute_prof_grad / rcn_prof, rcn_prof_bdof.c:152-290).  Chroma: the 4x4 blocks
+// of each 8x8 luma area (rcn_mcp_b_c(3,3): sets 0..2, the put_vvc_pel_rpr_clip uint16 quirk included), lanes 0..31.
+// =====================================================================================================
+#define MCAR_ROWS 16
+
+struct Rpr4Taps { int8_t l4[16][8]; };
+constexpr Rpr4Taps build_rpr4_taps()
+{
+    Rpr4Taps t{};
+    for (int p = 0; p < 16; ++p) for (int k = 0; k < 8; ++k) t.l4[p][k] = ovt_mc_luma4[p][k];
+    return t;
+}
+__device__ const Rpr4Taps __attribute__((aligned(16))) g_rpr4 = build_rpr4_taps();
+
+// One list of one 4x4 block (luma sub-block: NT 8, chroma block: NT 4), the lane's column c: 14-bit intermediates of its 4
+// samples in out[]; *quirk: the vertical pass of sample j is put_vvc_pel_rpr_clip's (bit j; uni-prediction reads q[] instead).
+template <int NT>
+__device__ __forceinline__ void mcar_block(const uint16_t *__restrict__ ref, int rstride, int rw, int rh, const Axis &axx, const Axis &axy,
+                                           int fh, int fv, int c, int16_t *tile /* [MCAR_ROWS][4] */, int out[4], int q[4])
+{
+    constexpr int B = NT / 2 - 1;
+    int iy[4], phy[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) axis_pos(axy, j, j, iy[j], phy[j]);
+    const int rb = iy[0] - B;
+    const int nrows = clampi(iy[3] - iy[0] + NT, 0, MCAR_ROWS);
+    int ix, phx;
+    axis_pos(axx, c, c, ix, phx);
+    const int8_t *tp;
+    if (NT == 8) tp = axx.scaled ? g_rpr.rl[fh][phx] : g_rpr4.l4[phx];
+    else         tp = axx.scaled ? g_rpr.rc[fh][phx] : g_rpr.c[phx];
+    int t[NT], xo[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) { t[k] = tp[k]; xo[k] = clampi(ix - B + k, 0, rw - 1); }
+    for (int r = 0; r < nrows; ++r) {
+        const uint16_t *row = ref + (size_t)clampi(rb + r, 0, rh - 1) * rstride;
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) acc += t[k] * (int)row[xo[k]];
+        tile[r * 4 + c] = (int16_t)(acc >> (OV_BD - 8));
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int8_t *tv;
+        if (NT == 8) tv = axy.scaled ? g_rpr.rl[fv][phy[j]] : g_rpr4.l4[phy[j]];
+        else         tv = axy.scaled ? g_rpr.rc[fv][phy[j]] : g_rpr.c[phy[j]];
+        const int base = iy[j] - iy[0];
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) acc += (int)tv[k] * (int)tile[clampi(base + k, 0, MCAR_ROWS - 1) * 4 + c];
+        out[j] = acc >> 6;
+        q[j] = (axy.scaled && fv == 0 && phy[j] == 0) ? (int)(uint16_t)tile[clampi(base + B, 0, MCAR_ROWS - 1) * 4 + c] : -1;
+    }
+}
+
+__device__ __forceinline__ int mcar_combine(int dir, int w0, int w1, int p0, int p1)
+{
+    if (dir != 3)           return ov_clip_bd(((dir == 1 ? p0 : p1) + 8) >> 4);
+    if (w0 == 4 && w1 == 4) return ov_clip_bd((p0 + p1 + 16) >> 5);
+    return ov_clip_bd((p0 * w0 + p1 * w1 + 64) >> 7);
+}
+
+__global__ __launch_bounds__(64) void k_mca_rpr(ovhip_pic dst, RefTable refs, const ovhip_aff_rpr_unit *__restrict__ units, uint32_t n_units,
+                                                const int32_t *__restrict__ side, const uint16_t *__restrict__ lmcs_fwd)
+{
+    __shared__ int16_t s_tile[16][MCAR_ROWS * 4];
+    __shared__ int16_t s_t[16][36];
+    if (blockIdx.x >= n_units) return;
+    const ovhip_aff_rpr_unit u = units[blockIdx.x];
+    const int lane = threadIdx.x;
+    const int udir = u.dir & 3;
+    if (!udir || u.w < 4 || u.h < 4 || u.w > 16 || u.h > 16 || ((u.w | u.h) & 3)) return;
+    const int nsx = u.w >> 2, nsb = nsx * (u.h >> 2), ncx = u.w >> 3, ncb = ncx * (u.h >> 3);
+    const bool do_c = !(u.flags & OVHIP_AFFR_NO_CHROMA) && !((u.w | u.h) & 7);        // (a lone 4x4 luma block has none)
+    const int32_t *mvs = side + u.side_off;
+
+    // ---- luma: lane = (sub-block sb, column c) ----
+    {
+        const int sb = lane >> 2, c = lane & 3;
+        const bool act = sb < nsb;
+        const int bx = u.x + 4 * (sb % nsx), by = u.y + 4 * (sb / nsx);
+        const int dir = ((u.ident_l >> sb) & 1) ? 2 : udir;
+        int P[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+            const bool on = act && (dir & (1 << l));
+            const bool sc = (u.flags & (l ? OVHIP_AFFR_S1 : OVHIP_AFFR_S0)) != 0;
+            const bool prof = (u.flags & OVHIP_AFFR_PROF) && udir == 3 && !sc && ((u.prof_dir >> l) & 1);      // uniform
+            const ovhip_aff_rpr_list s = u.s[l];
+            const ovhip_pic &rp = refs.p[min((int)s.ref, MC_MAX_REFS - 1)];
+            int a = 0, b = 0;
+            if (on) { a = mvs[4 * sb + 2 * l]; b = mvs[4 * sb + 2 * l + 1]; }
+            if (on) {
+                const Axis ax = { a, s.step_x, 4, bx + (a >> 4), a & 15, sc };
+                const Axis ay = { b, s.step_y, 4, by + (b >> 4), b & 15, sc };
+                int q[4];
+                mcar_block<8>(rp.y, rp.stride_y, rp.w, rp.h, ax, ay, min(s.filt & 15, 5), min(s.filt >> 4, 5), c, s_tile[sb], P[l], q);
+            }
+            if (prof) {
+                // 6x6 tile: interior = the lane's prediction column, ring = integer reference samples << 4 (5 ring samples per lane)
+                if (on) {
+                    int16_t *t = s_t[sb];
+                    const int rx = bx + (a >> 4) - 1 + ((a & 15) >> 3), ry = by + (b >> 4) - 1 + ((b & 15) >> 3);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) t[(j + 1) * 6 + c + 1] = (int16_t)P[l][j];
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) {
+                        const int e = 5 * c + k;
+                        int i, j;
+                        if (e < 6)       { i = e; j = 0; }
+                        else if (e < 12) { i = e - 6; j = 5; }
+                        else if (e < 16) { i = 0; j = e - 11; }
+                        else             { i = 5; j = e - 15; }
+                        t[j * 6 + i] = (int16_t)(rp.y[(size_t)clampi(ry + j, 0, rp.h - 1) * rp.stride_y + clampi(rx + i, 0, rp.w - 1)] << 4);
+                    }
+                }
+                __syncthreads();
+                if (on) {
+                    const int16_t *t = s_t[sb];
+                    const int16_t *pt = reinterpret_cast<const int16_t *>(side + u.prof_off) + 32 * l;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int o = (j + 1) * 6 + c + 1;
+                        const int gx = (t[o + 1] >> 6) - (t[o - 1] >> 6), gy = (t[o + 6] >> 6) - (t[o - 6] >> 6);
+                        const int add = ov_clip3((int)pt[4 * j + c] * gx + (int)pt[16 + 4 * j + c] * gy, -(1 << 13), (1 << 13) - 1);
+                        P[l][j] = (int)(int16_t)(P[l][j] + add);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (act) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int v = mcar_combine(dir, u.w0, u.w1, P[0][j], P[1][j]);
+                if ((u.flags & OVHIP_AFFR_LMCS) && lmcs_fwd) v = lmcs_fwd[v];
+                const int px = bx + c, py = by + j;
+                if (px < dst.w && py < dst.h) dst.y[(size_t)py * dst.stride_y + px] = (uint16_t)v;
+            }
+        }
+    }
+    // ---- chroma: lanes 0..31 = (plane, block, column), both lists; the tiles are the lane's own again ----
+    if (do_c && lane < 32) {
+        const int comp = lane >> 4, blk = (lane >> 2) & 3, c = lane & 3;
+        if (blk < ncb) {
+            const int cbx = (u.x >> 1) + 4 * (blk % ncx), cby = (u.y >> 1) + 4 * (blk / ncx);
+            const int dir = ((u.ident_c >> blk) & 1) ? 2 : udir;
+            int P[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } }, Q[2][4] = { { -1, -1, -1, -1 }, { -1, -1, -1, -1 } };
+#pragma unroll
+            for (int l = 0; l < 2; ++l) {
+                if (!(dir & (1 << l))) continue;
+                const bool sc = (u.flags & (l ? OVHIP_AFFR_S1 : OVHIP_AFFR_S0)) != 0;
+                const ovhip_aff_rpr_list s = u.s[l];
+                const ovhip_pic &rp = refs.p[min((int)s.ref, MC_MAX_REFS - 1)];
+                const int a = mvs[4 * (nsb + blk) + 2 * l], b = mvs[4 * (nsb + blk) + 2 * l + 1];
+                const Axis ax = { a, s.step_x, 5, cbx + (a >> 5), a & 31, sc };
+                const Axis ay = { b, s.step_y, 5, cby + (b >> 5), b & 31, sc };
+                mcar_block<4>(comp ? rp.cr : rp.cb, rp.stride_c, rp.w >> 1, rp.h >> 1, ax, ay, min(s.filt_c & 15, 2), min(s.filt_c >> 4, 2), c,
+                              s_tile[comp * 4 + blk], P[l], Q[l]);
+            }
+            uint16_t *d = comp ? dst.cr : dst.cb;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int v = mcar_combine(dir, u.w0, u.w1, P[0][j], P[1][j]);
+                // put_vvc_pel_rpr_clip reads the horizontal intermediate as uint16: a negative one clips to the maximum
+                const int qv = dir == 1 ? Q[0][j] : Q[1][j];
+                if (dir != 3 && qv >= 0) v = ov_clip_bd((qv + 8) >> 4);
+                const int px = cbx + c, py = cby + j;
+                if (px < (dst.w >> 1) && py < (dst.h >> 1)) d[(size_t)py * dst.stride_c + px] = (uint16_t)v;
+            }
+        }
+    }
+}
+
 } // namespace
+
+extern "C" int ovhip_mca_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs,
+                                    const ovhip_aff_rpr_unit *d_units, uint32_t n_units, const int32_t *d_side,
+                                    const uint16_t *d_lmcs_fwd_lut)
+{
+    if (!ctx || !dst) return OVHIP_EINVAL;
+    OV_DEVICE(ctx);
+    if (!n_units) return OVHIP_OK;
+    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_side)
+        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_rpr_launch: bad reference table / units / side arena", hipSuccess);
+    RefTable t;
+    memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < n_refs; ++i) {
+        if (!refs[i].y || !refs[i].cb || !refs[i].cr || refs[i].w < 8 || refs[i].h < 8 || refs[i].stride_y < refs[i].w ||
+            refs[i].stride_c < (refs[i].w >> 1))
+            return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_rpr_launch: bad reference picture", hipSuccess);
+        t.p[i] = refs[i];
+    }
+    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    hipLaunchKernelGGL(k_mca_rpr, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_side, d_lmcs_fwd_lut);
+    OV_LAUNCH_CHECK(ctx, "k_mca_rpr");
+    return OVHIP_OK;
+}
 
 extern "C" int ovhip_mc_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *refs, uint32_t n_refs,
                                    const ovhip_rpr_unit *d_units, uint32_t n_units, const uint16_t *d_lmcs_fwd_lut,

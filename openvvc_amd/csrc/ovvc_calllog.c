@@ -11,9 +11,9 @@
 #include "ovvc_hip.h"
 #include "ovvc_record_priv.h"
 
-enum { CL_CTU_SIZE = 1, CL_TU, CL_ISP, CL_PU, CL_AFF, CL_REGION, CL_DBF, CL_CIIP, CL_REF_SCALE };
+enum { CL_CTU_SIZE = 1, CL_TU, CL_ISP, CL_PU, CL_AFF, CL_REGION, CL_DBF, CL_CIIP, CL_REF_SCALE, CL_RPR_TOOLS };
 
-struct ovhip_calllog { unsigned char *data; size_t n, cap; int oom; };   /* oom: the log is unusable (allocation failed or a call could not be written down): _data returns NULL */
+struct ovhip_calllog { unsigned char *data; size_t n, cap; int oom; int tools_logged; };   /* oom: the log is unusable (allocation failed or a call could not be written down): _data returns NULL */
 
 struct cl_tu {
     ovhip_tu_state st;
@@ -28,7 +28,7 @@ struct cl_ref_scale { int32_t slot; uint32_t has; ovhip_ref_scale sc; };   /* ha
 
 ovhip_calllog *ovhip_calllog_create(void) { return (ovhip_calllog *)calloc(1, sizeof(ovhip_calllog)); }
 void ovhip_calllog_destroy(ovhip_calllog *l) { if (l) { free(l->data); free(l); } }
-void ovhip_calllog_reset(ovhip_calllog *l) { if (l) { l->n = 0; l->oom = 0; } }
+void ovhip_calllog_reset(ovhip_calllog *l) { if (l) { l->n = 0; l->oom = 0; l->tools_logged = 0; } }
 
 const void *
 ovhip_calllog_data(const ovhip_calllog *l, size_t *bytes)
@@ -175,6 +175,14 @@ ovhip_calllog_ref_scale_(ovhip_calllog *l, int32_t slot, const ovhip_ref_scale *
     if (p) memcpy(p, &g, sizeof(g));
 }
 
+void
+ovhip_calllog_rpr_tools_(ovhip_calllog *l, uint32_t mask)
+{
+    if (l->tools_logged) return;
+    unsigned char *p = cl_open(l, CL_RPR_TOOLS, sizeof(mask));
+    if (p) { memcpy(p, &mask, sizeof(mask)); l->tools_logged = 1; }
+}
+
 int64_t
 ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec)
 {
@@ -247,6 +255,7 @@ ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec)
             r = ovhip_rec_set_ref_scale(rec, g->slot, g->has ? &g->sc : NULL);
             break;
         }
+        case CL_RPR_TOOLS: { uint32_t v; CL_NEED(4) memcpy(&v, q, 4); r = ovhip_rec_set_rpr_tools(rec, v); break; }
         default: r = OVHIP_EINVAL;
         }
 #undef CL_NEED

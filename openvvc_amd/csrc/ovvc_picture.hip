@@ -18,7 +18,7 @@ namespace {
 
 struct DevBuf { void *p; size_t cap; };
 
-enum { B_TB, B_COEF, B_MC, B_MCX, B_MV, B_AFF, B_SIDE, B_REG, B_SCALE, B_EV, B_EH, B_PARAM, B_CLASS, B_CIIP, B_ITASK, B_ICTU, B_IITEM, B_TMVP, B_RPR, B_COUNT };
+enum { B_TB, B_COEF, B_MC, B_MCX, B_MV, B_AFF, B_SIDE, B_REG, B_SCALE, B_EV, B_EH, B_PARAM, B_CLASS, B_CIIP, B_ITASK, B_ICTU, B_IITEM, B_TMVP, B_RPR, B_AFFR, B_COUNT };
 
 // Reference picture resampling: k_mc2 / k_mcxa / the DMVR search take the window geometry from the picture and refuse a reference
 // of another size.  Their units never read such a slot (the recorder sends every unit that reads a scaled reference to the RPR
@@ -350,6 +350,7 @@ struct Chain {
     const ovhip_mc_unit *d_mc, *d_mcx; uint32_t n_mc, n_mcx;
     const ovhip_aff_unit *d_aff; uint32_t n_aff; const int32_t *d_side;
     const ovhip_rpr_unit *d_rpr; uint32_t n_rpr;                      // units that read a reference of another size (k_mc_rpr)
+    const ovhip_aff_rpr_unit *d_affr; uint32_t n_affr;                // affine units that do (k_mca_rpr; their side data in d_side)
     const ovhip_tb_cmd *d_tb; size_t cls[4], tiny[4][4]; const int16_t *d_coef;
     const ovhip_lmcs_region *d_reg; uint32_t reg0, n_reg;             // this submission's regions: [reg0, reg0 + n_reg)
     const ovhip_itask *d_it, *h_it; uint32_t n_it;                    // the level-sorted tasks (h_it: host copy, level geometry)
@@ -373,6 +374,12 @@ int chain_predict(const Chain &c, const ovhip_pic *refs_same, const ovhip_pic *r
     if (c.n_mcx || c.n_aff) {
         StageTimer t_(c.timer, OVHIP_TIME_MCXA);
         CHK(ovhip_mcxa_launch(j->ctx, c.dst, refs_same, n_refs, c.d_mcx, c.n_mcx, d_mv, c.d_aff, c.n_aff, c.d_side, c.d_fwd));
+        j->st.n_launches++;
+    }
+    if (c.n_affr) {
+        // like k_mc_rpr: the real reference table, blocks disjoint from every other unit's
+        StageTimer t_(c.timer, OVHIP_TIME_MCXA);
+        CHK(ovhip_mca_rpr_launch(j->ctx, c.dst, refs, n_refs, c.d_affr, c.n_affr, c.d_side, c.d_fwd));
         j->st.n_launches++;
     }
     return OVHIP_OK;
@@ -829,6 +836,8 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
         return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_flush: CIIP blend units recorded but no picture with their intra prediction", hipSuccess);
     size_t n_rpr = 0;
     const ovhip_rpr_unit *rpr = ovhip_rec_rpr_units(rec, &n_rpr);     // units that read a reference of another size (k_mc_rpr)
+    size_t n_affr = 0;
+    const ovhip_aff_rpr_unit *affr = ovhip_rec_aff_rpr_units(rec, &n_affr);   // affine units that do (k_mca_rpr)
     // ordered tasks: grouped by CTU for the one-launch pass, or sorted by level for one launch per level
     size_t n_it = 0, n_ictu = 0; uint32_t n_lv = 0; const uint32_t *lv_start = nullptr; const ovhip_ictu *ictu = nullptr;
     const int by_ctu = pr->stages && (stages & OVHIP_STAGE_INTRA_CTU);
@@ -887,7 +896,7 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
         { j->items_host, by_flow ? n_items * sizeof(uint32_t) : 0, B_IITEM, 0 },
         { mcx, n_mcx * sizeof(*mcx), B_MCX, 0 }, { ciip, n_ciip * sizeof(*ciip), B_CIIP, 0 }, { aff, n_aff * sizeof(*aff), B_AFF, 0 },
         { side, n_side * sizeof(*side), B_SIDE, 0 }, { reg, n_reg * sizeof(*reg), B_REG, 0 },
-        { rpr, n_rpr * sizeof(*rpr), B_RPR, 0 },
+        { rpr, n_rpr * sizeof(*rpr), B_RPR, 0 }, { affr, n_affr * sizeof(*affr), B_AFFR, 0 },
         { ev, (stages & OVHIP_STAGE_DBF) ? n_ev * sizeof(*ev) : 0, B_EV, 0 }, { eh, (stages & OVHIP_STAGE_DBF) ? n_eh * sizeof(*eh) : 0, B_EH, 0 },
     };
     static_assert(B_COUNT <= 24, "packed_prev");
@@ -972,6 +981,7 @@ static int job_flush_impl(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *r
     c.d_mc = (const ovhip_mc_unit *)DEV(B_MC); c.n_mc = (uint32_t)n_mc; c.d_mcx = (const ovhip_mc_unit *)DEV(B_MCX); c.n_mcx = (uint32_t)n_mcx;
     c.d_aff = (const ovhip_aff_unit *)DEV(B_AFF); c.n_aff = (uint32_t)n_aff; c.d_side = (const int32_t *)DEV(B_SIDE);
     c.d_rpr = (const ovhip_rpr_unit *)DEV(B_RPR); c.n_rpr = (uint32_t)n_rpr;
+    c.d_affr = (const ovhip_aff_rpr_unit *)DEV(B_AFFR); c.n_affr = (uint32_t)n_affr;
     c.d_tb = (const ovhip_tb_cmd *)DEV(B_TB); memcpy(c.cls, cls, sizeof(cls)); memcpy(c.tiny, tiny, sizeof(tiny)); c.d_coef = (const int16_t *)DEV(B_COEF);
     c.d_reg = (const ovhip_lmcs_region *)DEV(B_REG); c.n_reg = (uint32_t)n_reg;
     c.d_it = (const ovhip_itask *)DEV(B_ITASK); c.h_it = it; c.n_it = (uint32_t)n_it; c.lv_start = lv_start; c.n_lv = n_lv;
@@ -1415,6 +1425,7 @@ extern "C" int ovhip_job_band(ovhip_job *j, const ovhip_pic *dst, const ovhip_pi
     size_t dummy = 0;
     if (ovhip_rec_ciip_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: stand-alone CIIP blend units (a second picture with the caller's intra prediction)", hipSuccess);
     if (ovhip_rec_rpr_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: reference picture resampling units", hipSuccess);
+    if (ovhip_rec_aff_rpr_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: reference picture resampling units (affine)", hipSuccess);
     const size_t n_tb = c1.n_tb - c0.n_tb, n_coef = c1.n_coef - c0.n_coef, n_mc = c1.n_mc - c0.n_mc, n_mcx = c1.n_mcx - c0.n_mcx,
                  n_aff = c1.n_aff - c0.n_aff, n_side = c1.n_side - c0.n_side, n_reg = c1.n_reg - c0.n_reg, n_it_all = c1.n_itask - c0.n_itask,
                  n_ev = (stages & OVHIP_STAGE_DBF) ? c1.n_edge_v - c0.n_edge_v : 0, n_eh = (stages & OVHIP_STAGE_DBF) ? c1.n_edge_h - c0.n_edge_h : 0;

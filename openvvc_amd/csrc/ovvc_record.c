@@ -57,7 +57,7 @@ ovhip_rec_destroy(ovhip_recorder *r)
 {
     if (!r) return;
     void *bufs[] = { r->tb, r->coef, r->mc, r->mcx, r->aff, r->aff_side, r->reg, r->tb_split, r->ciip, r->edge_v, r->edge_h,
-                     r->itask, r->itask_sorted, r->itask_ctu, r->ictu, r->rpr };
+                     r->itask, r->itask_sorted, r->itask_ctu, r->ictu, r->rpr, r->affr };
     free(r->ilevel_start); free(r->ctu_count);
     ovhip_rec_intra_free_(r);
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); ++i) ovhip_rec_free_(r, bufs[i]);
@@ -114,6 +114,7 @@ ACCESSOR(ovhip_mc_unit, ovhip_rec_mcx_units, mcx, n_mcx)
 ACCESSOR(ovhip_aff_unit, ovhip_rec_aff_units, aff, n_aff)
 ACCESSOR(int32_t, ovhip_rec_aff_side, aff_side, n_side)
 ACCESSOR(ovhip_rpr_unit, ovhip_rec_rpr_units, rpr, n_rpr)
+ACCESSOR(ovhip_aff_rpr_unit, ovhip_rec_aff_rpr_units, affr, n_affr)
 
 /* lengths of the arrays a band of CTU rows is cut from (ovhip_job_band) */
 void
@@ -171,6 +172,7 @@ ovhip_rec_append_raw(ovhip_recorder *r, int which, const void *data, size_t n)
     case OVHIP_REC_EDGE_H: p = (void **)&r->edge_h;   cnt = &r->n_edge_h; cap = &r->cap_edge_h; elem = sizeof(ovhip_dbf_edge); break;
     case OVHIP_REC_ITASK:  p = (void **)&r->itask;    cnt = &r->n_itask;  cap = &r->cap_itask;  elem = sizeof(ovhip_itask); break;
     case OVHIP_REC_RPR:    p = (void **)&r->rpr;      cnt = &r->n_rpr;    cap = &r->cap_rpr;    elem = sizeof(ovhip_rpr_unit); break;
+    case OVHIP_REC_AFF_RPR: p = (void **)&r->affr;    cnt = &r->n_affr;   cap = &r->cap_affr;   elem = sizeof(ovhip_aff_rpr_unit); break;
     default: return OVHIP_EINVAL;
     }
     if (grow(p, cap, *cnt + n, elem)) return OVHIP_ENOMEM;
@@ -855,6 +857,7 @@ void
 ovhip_rec_rpr_reset_(ovhip_recorder *r)
 {
     r->n_rpr = 0;
+    r->n_affr = 0;
     r->refusal = "";
     if (r->n_scaled || !r->ref_scale[0].scale_hor) {
         for (int i = 0; i < 256; ++i) r->ref_scale[i] = rpr_default;
@@ -881,6 +884,14 @@ ovhip_rec_set_ref_scale(ovhip_recorder *r, int32_t slot, const ovhip_ref_scale *
     return OVHIP_OK;
 }
 
+int
+ovhip_rec_set_rpr_tools(ovhip_recorder *r, uint32_t mask)
+{
+    if (!r || (mask & ~(OVHIP_RPR_TOOL_AFFINE | OVHIP_RPR_TOOL_PU4x4))) return OVHIP_EINVAL;
+    r->rpr_tools = mask;
+    return OVHIP_OK;
+}
+
 const char *ovhip_rec_refusal(const ovhip_recorder *r) { return r ? r->refusal : ""; }
 
 static int
@@ -899,6 +910,16 @@ slot_scaled(ovhip_recorder *r, int slot)
     if ((s->ref_w && s->ref_w != r->pic_w) || (s->ref_h && s->ref_h != r->pic_h))
         return refuse(r, "reference picture resampling: scale 1 on a reference of another size");
     return 0;
+}
+
+/* the same without touching the refusal: does a call with these lists take a path ovhip_rec_set_rpr_tools opened? */
+static int
+reads_scaled(const ovhip_recorder *r, int dir, int ref0, int ref1)
+{
+    if (!r->n_scaled) return 0;
+    const ovhip_ref_scale *a = &r->ref_scale[ref0], *b = &r->ref_scale[ref1];
+    return ((dir & 1) && (a->scale_hor != OVHIP_RPR_UNSCALED || a->scale_ver != OVHIP_RPR_UNSCALED)) ||
+           ((dir & 2) && (b->scale_hor != OVHIP_RPR_UNSCALED || b->scale_ver != OVHIP_RPR_UNSCALED));
 }
 
 /* compute_rpr_filter_idx (rcn_inter.c:1991-2006) */
@@ -962,13 +983,51 @@ rpr_side(const ovhip_recorder *r, const ovhip_pu_desc *pu, int l, int scaled, in
     s->cpos_y = rpr_anchor(pu->y0 >> 1, mvy, sc->scale_ver, add_y, ph >> 1, (sc->ref_h ? sc->ref_h : r->pic_h) >> 1, 5, 1);
 }
 
+/* A lone 4x4 luma block (rcn_mcp_b_l(2,2)) whose bi-prediction mixes a scaled and an unscaled list: rcn_mcp_bidir0_l runs the 6-tap
+ * filters of 4x4 blocks on the unscaled side (put_vvc_qpel_*, rcn_mc.c:457), which k_mc_rpr's regular table is not -- the block
+ * becomes a one-sub-block ovhip_aff_rpr_unit without chroma, whose kernel has that path. */
+static int
+rec_pu4_mixed(ovhip_recorder *r, const ovhip_pu_desc *pu, int s0, int s1)
+{
+    if (pu->prec_amvr_half || (pu->refine & OVHIP_PU_GPM) || pu->ciip_wt)
+        return refuse(r, "reference picture resampling: 4x4 prediction unit with a scaled reference");
+    int8_t w0 = 4, w1 = 4;
+    if (pu->bcw_idx_plus1 != 0 && pu->bcw_idx_plus1 != 3) {
+        static const int8_t bcw[5] = { -2, 3, 4, 5, 10 };
+        if (pu->bcw_idx_plus1 > 5) return OVHIP_EINVAL;
+        w1 = bcw[pu->bcw_idx_plus1 - 1];
+        w0 = (int8_t)(8 - w1);
+    }
+    if (grow((void **)&r->affr, &r->cap_affr, r->n_affr + 1, sizeof(ovhip_aff_rpr_unit))) return OVHIP_ENOMEM;
+    if (grow((void **)&r->aff_side, &r->cap_side, r->n_side + 4, sizeof(int32_t))) return OVHIP_ENOMEM;
+    ovhip_aff_rpr_unit *u = &r->affr[r->n_affr++];
+    memset(u, 0, sizeof(*u));
+    u->x = pu->x0; u->y = pu->y0; u->w = u->h = 4; u->dir = 3;
+    u->flags = (uint8_t)((s0 ? OVHIP_AFFR_S0 : 0) | (s1 ? OVHIP_AFFR_S1 : 0) | OVHIP_AFFR_NO_CHROMA | (pu->lmcs ? OVHIP_AFFR_LMCS : 0));
+    u->w0 = w0; u->w1 = w1;
+    u->side_off = (uint32_t)r->n_side;
+    int32_t *o = r->aff_side + r->n_side;
+    for (int l = 0; l < 2; ++l) {
+        ovhip_rpr_side sd;
+        rpr_side(r, pu, l, l ? s1 : s0, l ? pu->mv1x : pu->mv0x, l ? pu->mv1y : pu->mv0y, &sd);
+        u->s[l].step_x = sd.step_x; u->s[l].step_y = sd.step_y; u->s[l].filt = sd.filt; u->s[l].ref = sd.ref;
+        o[2 * l] = sd.pos_x; o[2 * l + 1] = sd.pos_y;
+    }
+    r->n_side += 4;
+    return 1;
+}
+
 /* A PU with at least one scaled list used (rcn_mcp_b / _l / _c, rcn_gpm_b and CIIP's rcn_mcp_b into RPR paths,
  * rcn_inter.c:2750-2960, :3118-3143): cut into <=16x16 tiles that share the PU's anchors. */
 static int
 rec_pu_rpr(ovhip_recorder *r, const ovhip_pu_desc *pu, int dir, int s0, int s1)
 {
     const int pw = 1 << pu->log2_w, ph = 1 << pu->log2_h;
-    if (pw == 4 && ph == 4) return refuse(r, "reference picture resampling: 4x4 prediction unit with a scaled reference");
+    /* a lone 4x4 luma block (rcn_mcp_b_l(2,2): flag_4x4, filter sets 3..5) is what k_mc_rpr takes as it is; opt-in, and never with
+     * chroma (no 2x2 chroma block in the reference) */
+    if (pw == 4 && ph == 4 && (!(r->rpr_tools & OVHIP_RPR_TOOL_PU4x4) || pu->planes != 1))
+        return refuse(r, "reference picture resampling: 4x4 prediction unit with a scaled reference");
+    if (pw == 4 && ph == 4 && dir == 3 && s0 != s1) return rec_pu4_mixed(r, pu, s0, s1);
     const int gpm = (pu->refine & OVHIP_PU_GPM) != 0;
     int K = 0, A = 0, B = 0;
     if (gpm) gpm_plane(pu, &K, &A, &B);
@@ -1025,9 +1084,15 @@ ovhip_rec_cu_inter(ovhip_recorder *r, const ovhip_pu_desc *pu, const ovhip_affin
 int
 ovhip_rec_pu(ovhip_recorder *r, const ovhip_pu_desc *pu)
 {
-    if (r->log) ovhip_calllog_pu_(r->log, pu);
     int pw = 1 << pu->log2_w, ph = 1 << pu->log2_h;
     int dir = pu->inter_dir & 3;
+    if (r->log) {
+        if ((r->rpr_tools & OVHIP_RPR_TOOL_PU4x4) && pw == 4 && ph == 4 && pu->planes == 1 && !pu->refine &&
+            reads_scaled(r, dir == 3 ? (pu->poc0 == pu->poc1 && pu->mv0x == pu->mv1x && pu->mv0y == pu->mv1y ? 2 : 3) : (dir & 2) ? 2 : 1,
+                         pu->ref0, pu->ref1))
+            ovhip_calllog_rpr_tools_(r->log, r->rpr_tools);
+        ovhip_calllog_pu_(r->log, pu);
+    }
     if (!dir) return OVHIP_EINVAL;
     if (pu->ciip_wt > 3 || (pu->ciip_wt && pu->refine)) return OVHIP_EINVAL;
     if (r->n_scaled && (pu->refine & OVHIP_PU_GPM || (pu->refine && (dir & 3) == 3))) {
@@ -1107,18 +1172,27 @@ ovhip_rec_pu(ovhip_recorder *r, const ovhip_pu_desc *pu)
  * rcn_affine_mcp_b_l / rcn_affine_prof_mcp_b_l / rcn_affine_mcp_b_c (drv_affine_mvp.c:3264-3411):
  * every 4x4 luma sub-block is predicted with its own motion vector, every 4x4 chroma block with
  * the average of the top-left and bottom-right sub-block vectors of its 8x8 luma area. */
+static int rec_affine_rpr(ovhip_recorder *r, const ovhip_affine_desc *cu, int dir, int s0, int s1);
+
 int
 ovhip_rec_affine_cu(ovhip_recorder *r, const ovhip_affine_desc *cu)
 {
     const int cw = 1 << cu->log2_w, ch = 1 << cu->log2_h;
     int dir = cu->inter_dir & 3;
     if (!dir || cw < 8 || ch < 8 || !cu->mv0 || !cu->mv1 || cu->mv_stride < (cw >> 2)) return OVHIP_EINVAL;
-    if (r->log) ovhip_calllog_affine_(r->log, cu);
     if (dir != 3 && (dir & 2)) dir = 2;
+    if (r->log) {
+        if ((r->rpr_tools & OVHIP_RPR_TOOL_AFFINE) && reads_scaled(r, dir, cu->ref0, cu->ref1)) ovhip_calllog_rpr_tools_(r->log, r->rpr_tools);
+        ovhip_calllog_affine_(r->log, cu);
+    }
     if (r->n_scaled) {
         const int s0 = (dir & 1) ? slot_scaled(r, cu->ref0) : 0, s1 = (dir & 2) && s0 >= 0 ? slot_scaled(r, cu->ref1) : 0;
         if (s0 < 0 || s1 < 0) return OVHIP_EUNSUP;
-        if (s0 || s1) return refuse(r, "reference picture resampling: affine coding unit with a scaled reference");
+        if (s0 || s1) {
+            if (!(r->rpr_tools & OVHIP_RPR_TOOL_AFFINE))
+                return refuse(r, "reference picture resampling: affine coding unit with a scaled reference");
+            return rec_affine_rpr(r, cu, dir, s0, s1);
+        }
     }
 
     int8_t w0 = 4, w1 = 4;
@@ -1188,6 +1262,125 @@ ovhip_rec_affine_cu(ovhip_recorder *r, const ovhip_affine_desc *cu)
                         u->ident_c |= (uint8_t)(1u << ((sy >> 3) * (uw >> 3) + (sx >> 3)));
                     clip_mv(r, u->x + sx, u->y + sy, 8, 8, &m[0], &m[1]);
                     clip_mv(r, u->x + sx, u->y + sy, 8, 8, &m[2], &m[3]);
+                    memcpy(o, m, sizeof(m));
+                    o += 4;
+                }
+            }
+            r->n_side += 4 * (size_t)(nl + nc);
+            ++n;
+        }
+    }
+    return n;
+}
+
+/* An affine CU with at least one scaled list used (OVHIP_RPR_TOOL_AFFINE).  To the reference every 4x4 luma sub-block is a 4x4 PU
+ * (rcn_mcp_b_l(2,2) / rcn_prof_mcp_b_l, rcn_inter.c:2815-2918) and every 4x4 chroma block the chroma of an 8x8 PU (rcn_mcp_b_c(3,3),
+ * :2920-2966): each with its OWN anchor after clip_rpr_position, computed here (rpr_anchor) from the unclipped vector; the unscaled
+ * side of a mixed bi-prediction keeps its clip_mv()'d vector and is the only one PROF refines (rcn_mc_rpr_prof_b_l, :2594-2649; a
+ * uni-predicted block on a scaled list goes through plain rcn_mcp_rpr_l). */
+static int
+rec_affine_rpr(ovhip_recorder *r, const ovhip_affine_desc *cu, int dir, int s0, int s1)
+{
+    const int cw = 1 << cu->log2_w, ch = 1 << cu->log2_h;
+    const int scaled[2] = { (dir & 1) && s0, (dir & 2) && s1 };
+    int8_t w0 = 4, w1 = 4;
+    if (dir == 3 && cu->bcw_idx_plus1 != 0 && cu->bcw_idx_plus1 != 3) {
+        static const int8_t bcw[5] = { -2, 3, 4, 5, 10 };
+        if (cu->bcw_idx_plus1 > 5) return OVHIP_EINVAL;
+        w1 = bcw[cu->bcw_idx_plus1 - 1];
+        w0 = (int8_t)(8 - w1);
+    }
+    /* apply_prof (rcn_inter.c:2880): bi-prediction only here, and only the lists that are not scaled */
+    const int prof = dir == 3 ? (cu->prof_dir & 3 & ((scaled[0] ? 0 : 1) | (scaled[1] ? 0 : 2))) : 0;
+    uint32_t prof_off = 0;
+    if (prof) {
+        if (grow((void **)&r->aff_side, &r->cap_side, r->n_side + 32, sizeof(int32_t))) return OVHIP_ENOMEM;
+        prof_off = (uint32_t)r->n_side;
+        memcpy(r->aff_side + r->n_side, cu->dmv_scale, 128);
+        if (!(prof & 1)) memset(r->aff_side + r->n_side, 0, 64);
+        if (!(prof & 2)) memset(r->aff_side + r->n_side + 16, 0, 64);
+        r->n_side += 32;
+    }
+    ovhip_aff_rpr_list ls[2];
+    int32_t add_x[2] = { 0, 0 }, add_y[2] = { 0, 0 }, ref_w[2] = { 0, 0 }, ref_h[2] = { 0, 0 };
+    const ovhip_ref_scale *sc[2] = { &r->ref_scale[cu->ref0], &r->ref_scale[cu->ref1] };
+    memset(ls, 0, sizeof(ls));
+    for (int l = 0; l < 2; ++l) {
+        if (!(dir & (1 << l))) continue;
+        ls[l].ref = l ? cu->ref1 : cu->ref0;
+        if (!scaled[l]) continue;
+        ls[l].step_x = (uint16_t)(((sc[l]->scale_hor + 8) >> 4) << 4);
+        ls[l].step_y = (uint16_t)(((sc[l]->scale_ver + 8) >> 4) << 4);
+        ls[l].filt = (uint8_t)(rpr_filter_idx(sc[l]->scale_hor, 1) | rpr_filter_idx(sc[l]->scale_ver, 1) << 4);
+        ls[l].filt_c = (uint8_t)(rpr_filter_idx(sc[l]->scale_hor, 0) | rpr_filter_idx(sc[l]->scale_ver, 0) << 4);
+        add_x[l] = (1 - sc[l]->chroma_hor_col_flag) * 8 * (sc[l]->scale_hor - OVHIP_RPR_UNSCALED);
+        add_y[l] = (1 - sc[l]->chroma_ver_col_flag) * 8 * (sc[l]->scale_ver - OVHIP_RPR_UNSCALED);
+        ref_w[l] = sc[l]->ref_w ? sc[l]->ref_w : r->pic_w;
+        ref_h[l] = sc[l]->ref_h ? sc[l]->ref_h : r->pic_h;
+    }
+
+    const int uw = cw > 16 ? 16 : cw, uh = ch > 16 ? 16 : ch;
+    int n = 0;
+    for (int uy = 0; uy < ch; uy += uh) {
+        for (int ux = 0; ux < cw; ux += uw) {
+            const int nl = (uw >> 2) * (uh >> 2), nc = (uw >> 3) * (uh >> 3);
+            if (grow((void **)&r->affr, &r->cap_affr, r->n_affr + 1, sizeof(ovhip_aff_rpr_unit))) return OVHIP_ENOMEM;
+            if (grow((void **)&r->aff_side, &r->cap_side, r->n_side + 4 * (size_t)(nl + nc), sizeof(int32_t))) return OVHIP_ENOMEM;
+            ovhip_aff_rpr_unit *u = &r->affr[r->n_affr++];
+            memset(u, 0, sizeof(*u));
+            u->x = (uint16_t)(cu->x0 + ux); u->y = (uint16_t)(cu->y0 + uy);
+            u->w = (uint8_t)uw; u->h = (uint8_t)uh;
+            u->dir = (uint8_t)dir;
+            u->flags = (uint8_t)((scaled[0] ? OVHIP_AFFR_S0 : 0) | (scaled[1] ? OVHIP_AFFR_S1 : 0) | (prof ? OVHIP_AFFR_PROF : 0) |
+                                 (cu->lmcs ? OVHIP_AFFR_LMCS : 0));
+            u->w0 = w0; u->w1 = w1;
+            u->prof_dir = (uint8_t)prof;
+            u->side_off = (uint32_t)r->n_side;
+            u->prof_off = prof_off;
+            u->s[0] = ls[0]; u->s[1] = ls[1];
+            int32_t *o = r->aff_side + r->n_side;
+            for (int sy = 0; sy < uh; sy += 4) {
+                for (int sx = 0; sx < uw; sx += 4) {
+                    const int k = ((uy + sy) >> 2) * cu->mv_stride + ((ux + sx) >> 2);
+                    int32_t m[4] = { cu->mv0[2 * k], cu->mv0[2 * k + 1], cu->mv1[2 * k], cu->mv1[2 * k + 1] };
+                    if (!(dir & 1)) m[0] = m[1] = 0;      /* the list a uni-predicted CU does not use: never recorded */
+                    if (!(dir & 2)) m[2] = m[3] = 0;
+                    /* rcn_mcp_b_l's identical-motion shortcut; rcn_prof_mcp_b_l has none */
+                    if (!cu->prof_dir && dir == 3 && cu->poc0 == cu->poc1 && m[0] == m[2] && m[1] == m[3])
+                        u->ident_l |= (uint16_t)(1u << ((sy >> 2) * (uw >> 2) + (sx >> 2)));
+                    for (int l = 0; l < 2; ++l) {
+                        if (!(dir & (1 << l))) continue;
+                        if (scaled[l]) {
+                            const int32_t mx = m[2 * l], my = m[2 * l + 1];
+                            m[2 * l]     = rpr_anchor(u->x + sx, mx, sc[l]->scale_hor, 0, 4, ref_w[l], 4, 0);
+                            m[2 * l + 1] = rpr_anchor(u->y + sy, my, sc[l]->scale_ver, 0, 4, ref_h[l], 4, 1);
+                        } else {
+                            clip_mv(r, u->x + sx, u->y + sy, 4, 4, &m[2 * l], &m[2 * l + 1]);
+                        }
+                    }
+                    memcpy(o, m, sizeof(m));
+                    o += 4;
+                }
+            }
+            for (int sy = 0; sy < uh; sy += 8) {
+                for (int sx = 0; sx < uw; sx += 8) {
+                    const int k = ((uy + sy) >> 2) * cu->mv_stride + ((ux + sx) >> 2), k2 = k + cu->mv_stride + 1;
+                    int32_t m[4] = { 0, 0, 0, 0 };
+                    if (dir & 1) { m[0] = cu->mv0[2 * k] + cu->mv0[2 * k2]; m[1] = cu->mv0[2 * k + 1] + cu->mv0[2 * k2 + 1]; }
+                    if (dir & 2) { m[2] = cu->mv1[2 * k] + cu->mv1[2 * k2]; m[3] = cu->mv1[2 * k + 1] + cu->mv1[2 * k2 + 1]; }
+                    for (int c = 0; c < 4; ++c) { m[c] += m[c] < 0; m[c] >>= 1; }
+                    if (dir == 3 && cu->poc0 == cu->poc1 && m[0] == m[2] && m[1] == m[3])
+                        u->ident_c |= (uint8_t)(1u << ((sy >> 3) * (uw >> 3) + (sx >> 3)));
+                    for (int l = 0; l < 2; ++l) {
+                        if (!(dir & (1 << l))) continue;
+                        if (scaled[l]) {
+                            const int32_t mx = m[2 * l], my = m[2 * l + 1];
+                            m[2 * l]     = rpr_anchor((u->x + sx) >> 1, mx, sc[l]->scale_hor, add_x[l], 4, ref_w[l] >> 1, 5, 0);
+                            m[2 * l + 1] = rpr_anchor((u->y + sy) >> 1, my, sc[l]->scale_ver, add_y[l], 4, ref_h[l] >> 1, 5, 1);
+                        } else {
+                            clip_mv(r, u->x + sx, u->y + sy, 8, 8, &m[2 * l], &m[2 * l + 1]);
+                        }
+                    }
                     memcpy(o, m, sizeof(m));
                     o += 4;
                 }
@@ -1309,4 +1502,5 @@ ACCESSOR(ovhip_ciip_unit, ovhip_rec_ciip_units, ciip, n_ciip)
 
 _Static_assert(sizeof(ovhip_rpr_side) == 24, "ovhip_rpr_side is 24 bytes");
 _Static_assert(sizeof(ovhip_rpr_unit) == 64, "ovhip_rpr_unit is 64 bytes");
+_Static_assert(sizeof(ovhip_aff_rpr_unit) == 48 && sizeof(ovhip_aff_rpr_list) == 8, "ovhip_aff_rpr_unit is 48 bytes");
 _Static_assert(sizeof(ovhip_ref_scale) == 20, "ovhip_ref_scale is 20 bytes");

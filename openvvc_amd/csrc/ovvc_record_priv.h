@@ -40,6 +40,8 @@ struct ovhip_recorder {
     /* reference picture resampling (ovhip_rec_set_ref_scale): per reference-table slot; n_scaled = slots not at the default */
     ovhip_ref_scale ref_scale[256]; uint32_t n_scaled;
     ovhip_rpr_unit *rpr; size_t n_rpr, cap_rpr;
+    ovhip_aff_rpr_unit *affr; size_t n_affr, cap_affr;   /* affine units that read a scaled slot (OVHIP_RPR_TOOL_AFFINE) */
+    uint32_t rpr_tools;                 /* ovhip_rec_set_rpr_tools: the caller's opt-in, survives ovhip_rec_reset */
     const char *refusal;                /* reason of the last OVHIP_EUNSUP (ovhip_rec_refusal) */
 };
 
@@ -53,6 +55,8 @@ void ovhip_calllog_dbf_(ovhip_calllog *l, const ovhip_dbf_ctu *c);
 void ovhip_calllog_ciip_(ovhip_calllog *l, int32_t x0, int32_t y0, int32_t log2_w, int32_t log2_h, int32_t mode_abv, int32_t mode_lft);
 void ovhip_calllog_ctu_size_(ovhip_calllog *l, int32_t log2_ctu_s);
 void ovhip_calllog_ref_scale_(ovhip_calllog *l, int32_t slot, const ovhip_ref_scale *sc);
+/* the recorder's opt-in, written once per log right before the first record that takes a path it opens */
+void ovhip_calllog_rpr_tools_(ovhip_calllog *l, uint32_t mask);
 
 int  ovhip_rec_intra_reset_(ovhip_recorder *r);
 void ovhip_rec_rpr_reset_(ovhip_recorder *r);

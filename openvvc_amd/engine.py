@@ -178,6 +178,14 @@ class Context:
         self._chk(self.lib.ovhip_mca_launch(self.h, C.byref(dst.s), arr, len(refs), units.ptr, n, side.ptr,
                                             lmcs_fwd.ptr if lmcs_fwd else None), "mca_launch")
 
+    def mca_rpr(self, dst: "DevPic", refs: list, units: "DevBuf", side: "DevBuf", lmcs_fwd: "DevBuf | None" = None,
+                n: int | None = None):
+        """Affine units that read references of another size (ovhip_aff_rpr_unit); each reference keeps its own geometry."""
+        n = units.count if n is None else n
+        arr = (capi.Pic * len(refs))(*[r.s for r in refs])
+        self._chk(self.lib.ovhip_mca_rpr_launch(self.h, C.byref(dst.s), arr, len(refs), units.ptr, n, side.ptr,
+                                                lmcs_fwd.ptr if lmcs_fwd else None), "mca_rpr_launch")
+
     def mcxa(self, dst: "DevPic", refs: list, xunits: "DevBuf", aunits: "DevBuf", side: "DevBuf",
              lmcs_fwd: "DevBuf | None" = None, mv_out: "DevBuf | None" = None):
         """BDOF / DMVR units and affine units in one launch (ovhip_mcxa_launch)."""

@@ -185,7 +185,7 @@ latch(struct hip_entry *e, int code, const char *what)
 {
     if (code >= 0 || e->err) return;
     e->err = code;
-    /* the recorder says which case of a tool it refused (reference picture resampling with DMVR / BDOF, affine, ...) */
+    /* the recorder says which case of a tool it refused (reference picture resampling with DMVR / BDOF, a 4x4 block with chroma, ...) */
     if (code == OVHIP_EUNSUP && e->rec && *ovhip_rec_refusal(e->rec)) what = ovhip_rec_refusal(e->rec);
     if (code == OVHIP_EUNSUP) {
         /* a coding tool outside the device set (IBC, reference picture resampling, entry threads > 1): the picture is FAILED -- published
@@ -708,7 +708,8 @@ pend_close(struct hip_entry *e, OVCTUDec *c)
         while ((1 << log2_w) < cols * 4) ++log2_w;
         while ((1 << log2_h) < rows * 4) ++log2_h;
         if (cols * rows != e->pend.n || (4 << (log2_w - 2)) != cols * 4 || (4 << (log2_h - 2)) != rows * 4 || cols < 2 || rows < 2) {
-            /* not the affine drivers' pattern: each call is what the slot says it is, a 4x4 luma prediction */
+            /* not the affine drivers' pattern: each call is what the slot says it is, a 4x4 luma prediction (on a scaled reference:
+             * an ovhip_rpr_unit with the 4x4 filter sets, OVHIP_RPR_TOOL_PU4x4) */
             if (e->pend.prof_dir) { latch(e, OVHIP_EINVAL, "PROF sub-block calls do not form a CU"); return; }
             for (int i = 0; i < e->pend.n; ++i) {
                 const int row = cols ? i / cols : 0, col = cols ? i % cols : i, k = (row * 32 + col) * 2;
@@ -1789,6 +1790,9 @@ begin_picture(struct hip_entry *e, const OVFrame *f, const struct RectEntryInfo 
     PROF_DEVICE_END(e);
     if (!e->rec) { latch(e, OVHIP_ENOMEM, "ovhip_frame_recorder"); return; }
     (void)ovhip_rec_set_ctu_size(e->rec, e->key->part_ctx ? e->key->part_ctx->log2_ctu_s : 7);
+    /* this caller submits through the picture job, which launches every array the recorder fills: affine CUs and lone 4x4 luma
+     * blocks on scaled references are recorded instead of refused */
+    (void)ovhip_rec_set_rpr_tools(e->rec, OVHIP_RPR_TOOL_AFFINE | OVHIP_RPR_TOOL_PU4x4);
     /* the slice's reference lists are known now (slicedec.c:1250-1256): a device that did not decode them asks for them before
      * the first prediction unit is parsed */
     const struct InterDRVCtx *ic = &e->key->drv_ctx.inter_ctx;
@@ -1936,6 +1940,7 @@ ovhip_shim_bind_recorder(const OVCTUDec *c, ovhip_recorder *rec, int pic_w, int 
     if (!e || !rec || e->fr) return OVHIP_EINVAL;
     e->rec = rec; e->record_only = 1; e->pic_w = pic_w; e->pic_h = pic_h;
     if (c->part_ctx) (void)ovhip_rec_set_ctu_size(rec, c->part_ctx->log2_ctu_s);
+    (void)ovhip_rec_set_rpr_tools(rec, OVHIP_RPR_TOOL_AFFINE | OVHIP_RPR_TOOL_PU4x4);     /* as for the shim's own recorders */
     e->err = 0; e->n_refs = 0; e->pend.kind = PEND_NONE;
     return OVHIP_OK;
 }
