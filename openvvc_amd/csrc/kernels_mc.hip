@@ -339,14 +339,7 @@ extern "C" int ovhip_mc_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_launch: bad reference table / units", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        // k_mc2 takes the window geometry from dst: references of another size are RPR, outside this path
-        if (refs[i].w != dst->w || refs[i].h != dst->h || refs[i].stride_y != dst->stride_y || refs[i].stride_c != dst->stride_c)
-            return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_mc_launch: reference picture geometry differs from dst (RPR)", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mc_launch: reference picture geometry differs from dst (RPR)")) return e;
     static int cfg_xcd = -1;
 #ifdef OVHIP_TUNING
     if (cfg_xcd < 0) { const char *x = getenv("OVHIP_MC_XCD"); cfg_xcd = x ? atoi(x) : 1; }   // experiment knob: XCD-aware unit order

@@ -808,13 +808,7 @@ extern "C" int ovhip_mcx_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhi
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mcx_launch: bad reference table / units", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        if (refs[i].w != dst->w || refs[i].h != dst->h || refs[i].stride_y != dst->stride_y || refs[i].stride_c != dst->stride_c)
-            return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_mcx_launch: reference picture geometry differs from dst (RPR)", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mcx_launch: reference picture geometry differs from dst (RPR)")) return e;
     hipLaunchKernelGGL(k_mcx, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut, d_mv_out);
     OV_LAUNCH_CHECK(ctx, "k_mcx");
     return OVHIP_OK;
@@ -829,13 +823,7 @@ extern "C" int ovhip_dmvr_search_launch(ovhip_ctx *ctx, const ovhip_pic *geom, c
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_mv_out)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_dmvr_search_launch: bad reference table / units", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        if (refs[i].w != geom->w || refs[i].h != geom->h || refs[i].stride_y != geom->stride_y || refs[i].stride_c != geom->stride_c)
-            return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_dmvr_search_launch: reference picture geometry differs (RPR)", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, geom, "ovhip_dmvr_search_launch: reference picture geometry differs (RPR)")) return e;
     hipLaunchKernelGGL(k_dmvr_search, dim3(n_units), dim3(64), 0, ctx->stream, *geom, t, d_units, n_units, d_mv_out);
     OV_LAUNCH_CHECK(ctx, "k_dmvr_search");
     return OVHIP_OK;
@@ -851,13 +839,7 @@ extern "C" int ovhip_mca_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhi
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_side)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_launch: bad reference table / units / side arena", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        if (refs[i].w != dst->w || refs[i].h != dst->h || refs[i].stride_y != dst->stride_y || refs[i].stride_c != dst->stride_c)
-            return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_mca_launch: reference picture geometry differs from dst (RPR)", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mca_launch: reference picture geometry differs from dst (RPR)")) return e;
     hipLaunchKernelGGL(k_mca, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_side, d_lmcs_fwd_lut);
     OV_LAUNCH_CHECK(ctx, "k_mca");
     return OVHIP_OK;
@@ -875,13 +857,7 @@ extern "C" int ovhip_mcxa_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovh
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_xunits || !d_aunits || !d_side)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mcxa_launch: bad reference table / units / side arena", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        if (refs[i].w != dst->w || refs[i].h != dst->h || refs[i].stride_y != dst->stride_y || refs[i].stride_c != dst->stride_c)
-            return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_mcxa_launch: reference picture geometry differs from dst (RPR)", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mcxa_launch: reference picture geometry differs from dst (RPR)")) return e;
     hipLaunchKernelGGL(k_mcxa, dim3(n_aunits + n_xunits), dim3(64), 0, ctx->stream, *dst, t, d_xunits, n_xunits, d_mv_out,
                        d_aunits, n_aunits, d_side, d_lmcs_fwd_lut);
     OV_LAUNCH_CHECK(ctx, "k_mcxa");

@@ -386,14 +386,7 @@ extern "C" int ovhip_mca_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const 
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_side)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_rpr_launch: bad reference table / units / side arena", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        if (!refs[i].y || !refs[i].cb || !refs[i].cr || refs[i].w < 8 || refs[i].h < 8 || refs[i].stride_y < refs[i].w ||
-            refs[i].stride_c < (refs[i].w >> 1))
-            return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_rpr_launch: bad reference picture", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, nullptr, "ovhip_mca_rpr_launch: bad reference picture")) return e;
     hipLaunchKernelGGL(k_mca_rpr, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_side, d_lmcs_fwd_lut);
     OV_LAUNCH_CHECK(ctx, "k_mca_rpr");
     return OVHIP_OK;
@@ -409,15 +402,7 @@ extern "C" int ovhip_mc_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const o
     if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_rpr_launch: bad reference table / units", hipSuccess);
     RefTable t;
-    memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        // every reference is read with its own geometry; only a plane that is not there is refused
-        if (!refs[i].y || !refs[i].cb || !refs[i].cr || refs[i].w < 8 || refs[i].h < 8 || refs[i].stride_y < refs[i].w ||
-            refs[i].stride_c < (refs[i].w >> 1))
-            return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_rpr_launch: bad reference picture", hipSuccess);
-        t.p[i] = refs[i];
-    }
-    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t.p[i] = refs[0];
+    if (int e = ref_table(ctx, &t, refs, n_refs, nullptr, "ovhip_mc_rpr_launch: bad reference picture")) return e;
     hipLaunchKernelGGL(k_mc_rpr, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut,
                        intra ? *intra : *dst);
     OV_LAUNCH_CHECK(ctx, "k_mc_rpr");

@@ -11,6 +11,24 @@ namespace {
 #define MC_MAX_REFS 16
 struct RefTable { ovhip_pic p[MC_MAX_REFS]; };
 
+// Host: the reference table of a launch from the caller's (refs, n_refs), 1 <= n_refs <= MC_MAX_REFS (the launcher has checked
+// that); unused entries repeat refs[0].  geom: the picture whose window geometry the kernel applies to every reference -- one of
+// another size is RPR, outside such a kernel (OVHIP_EUNSUP); nullptr: every reference is read with its own geometry, and only a
+// plane that is not there is refused (OVHIP_EINVAL).  `what`: the message of that failure, led by the entry point's name.
+static inline int ref_table(ovhip_ctx *ctx, RefTable *t, const ovhip_pic *refs, uint32_t n_refs, const ovhip_pic *geom, const char *what)
+{
+    memset(t, 0, sizeof(*t));
+    for (uint32_t i = 0; i < n_refs; ++i) {
+        const ovhip_pic &p = refs[i];
+        if (geom ? p.w != geom->w || p.h != geom->h || p.stride_y != geom->stride_y || p.stride_c != geom->stride_c
+                 : !p.y || !p.cb || !p.cr || p.w < 8 || p.h < 8 || p.stride_y < p.w || p.stride_c < (p.w >> 1))
+            return ov_fail(ctx, geom ? OVHIP_EUNSUP : OVHIP_EINVAL, what, hipSuccess);
+        t->p[i] = p;
+    }
+    for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t->p[i] = refs[0];
+    return OVHIP_OK;
+}
+
 typedef short short2v __attribute__((ext_vector_type(2)));
 
 #define WIN_STRIDE 28   /* luma window row in LDS: 7 aligned qwords (<= 3 + 23 samples) = 56 B            */

@@ -1,4 +1,4 @@
-/* ovvc_record_priv.h -- recorder state shared by ovvc_record.c / ovvc_record_dbf.c (private). */
+/* ovvc_record_priv.h -- recorder state shared by ovvc_record.c / ovvc_record_inter.c / ovvc_record_intra.c / ovvc_record_dbf.c / ovvc_calllog.c (private). */
 #ifndef OVVC_RECORD_PRIV_H
 #define OVVC_RECORD_PRIV_H
 #include <stddef.h>
@@ -66,6 +66,9 @@ int  ovhip_rec_itask_add_(ovhip_recorder *r, const ovhip_itask *t, uint16_t extr
 uint16_t ovhip_rec_region_level_(ovhip_recorder *r, int32_t x0, int32_t y0, int n_abv, int n_lft);
 
 int  ovhip_rec_grow_(ovhip_recorder *r, void **p, size_t *cap, size_t need, size_t elem);
+/* (the capacity test inline, on the recorder `r` of the calling function: the call is the rare path -- it used to be a PLT call per
+ * appended element) */
+#define grow(p, cap, need, elem) ((need) <= *(cap) ? 0 : ovhip_rec_grow_(r, p, cap, need, elem))
 void ovhip_rec_free_(ovhip_recorder *r, void *p);
 
 /* band-wise submission (ovvc_picture.hip): class split / level sort of a RANGE of the recorded commands into the caller's buffer */

@@ -14,10 +14,10 @@ R=$(cd "$(dirname "$0")/.." && pwd); REF=${REF:-/root/reference}/libovvc; T=${TM
 make -s -C $R/openvvc_amd/csrc && make -s -C $R/oracle
 rm -rf $T && mkdir -p $T && cd $T
 C=$R/openvvc_amd/csrc
-for f in ovvc_record ovvc_record_dbf ovvc_record_intra ovvc_lmcs ovvc_md5 ovvc_calllog ovvc_dpb ovvc_frame ovvc_stream; do
+for f in ovvc_record ovvc_record_inter ovvc_record_dbf ovvc_record_intra ovvc_lmcs ovvc_md5 ovvc_calllog ovvc_dpb ovvc_frame ovvc_stream; do
   gcc -O1 -g -fPIC -fsanitize=$SAN -fno-omit-frame-pointer -pthread -I$R/include -I$C -c $C/$f.c -o $f.o
 done
-HIPOBJS=$(ls $C/build/*.o | grep -v -E "/ovvc_(record|record_dbf|record_intra|lmcs|md5|calllog|dpb|frame|stream)\.o")
+HIPOBJS=$(ls $C/build/*.o | grep -v -E "/ovvc_(record|record_inter|record_dbf|record_intra|lmcs|md5|calllog|dpb|frame|stream)\.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=$SAN -o libovvc_hip.so $HIPOBJS *.o -lpthread -ldl 2>&1 | grep -v "not currently supported" || true
 gcc -O1 -g -w -fPIC -shared -fsanitize=$SAN -pthread -I$REF -I$R/include -I$R/shim -DBITDEPTH=10 -o librcn_hip.so $R/shim/rcn_hip.c -L. -lovvc_hip -Wl,--allow-shlib-undefined
 gcc -O1 -g -w -fPIC -shared -fsanitize=$SAN -I$REF -I$R/include -I$R/shim -DBITDEPTH=10 -o libgenpipe.so $R/oracle/ref_harness/gen_pipe.c \
