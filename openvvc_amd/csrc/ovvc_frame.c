@@ -541,7 +541,7 @@ refs_rows_ready(ovhip_frame *f, const int32_t *need, int block)
     return 1;
 }
 
-/* rows a band-wise job has made final once the band ending at `end` has had its filters (ovvc_picture.hip: deblocking leaves
+/* rows a band-wise job has made final once the band ending at `end` has had its filters (ovvc_band.hip: deblocking leaves
  * the 8 rows above a band's end to the next band, SAO and ALF follow in steps of 8 rows) -- what a dry frame posts */
 static int32_t
 dry_rows_after(int32_t end)
