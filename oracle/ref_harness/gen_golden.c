@@ -649,7 +649,6 @@ gen_mcx(const char *dir)
                     }
                     shim_case_end(c, &S, "mcx");
                     /* next case: fresh patch list, as a new picture would */
-                    extern void ovhip_shim_new_picture_for_test(OVCTUDec *);
                     ovhip_shim_new_picture_for_test(c);
                 }
 

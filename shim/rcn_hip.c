@@ -11,32 +11,9 @@
  *   rcn_attach_frame_buff -> per CTU { coding_tree -> prediction / transform slots ; rcn_write_ctu_to_frame ;
  *   lmcs_reshape_backward ; df.rcn_dbf_ctu } -> per CTU row { sao lines ; alf.rcn_alf_filter_line } -> publish row.
  */
-#include <pthread.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include <time.h>
 
-#include "ovdefs.h"
-#include "ovframe.h"
-#include "ovdpb.h"
-#include "dec_structures.h"
-#include "ctudec.h"
-#include "rcn_structures.h"
-#include "rcn.h"
-#include "drv.h"
-#include "drv_utils.h"
-#include "dbf_utils.h"
-#include "slicedec.h"
-#include "nvcl_structures.h"
-#include "ovdec_internal.h"          /* struct MVPlane */
-#include "ovlog.h"
-
-#include "ovvc_hip.h"
-#include "rcn_hip.h"
-
-#ifndef BITDEPTH
-#error "compile with -DBITDEPTH=10 (the table's sample type is a compile-time macro, bitdepth.h:36-40)"
-#endif
+#include "rcn_hip_priv.h"
 
 /* ------------------------------------------------------------------------------------ ABI check
  * The table is embedded by value in OVCTUDec; a back-end compiled against another layout would scribble over the
@@ -62,108 +39,16 @@ _Static_assert(offsetof(struct DBFQPMap, hor) == 0 || sizeof(((struct DBFQPMap *
 _Static_assert(sizeof(struct DBFQPMap) == sizeof(((ovhip_dbf_ctu *)0)->qp_y), "DBFInfo QP maps");
 _Static_assert(sizeof(struct DBFMap) == 2 * 33 * sizeof(uint64_t), "DBFMap = ver[33] + hor[33]");
 
-/* struct TUInfo / struct PROFInfo are private to the reference's .c files (rcn_transform_tree.c:51-66 and
- * vcl_transform_unit.c:47-75; drv_affine_mvp.c:3303-3308 and rcn_inter.c:1128-1134): the slot prototypes only
- * forward-declare them, a back-end has to restate the layout. */
-struct TBInfo { uint16_t last_pos; uint64_t sig_sb_map; };
-struct TUInfo {
-    uint8_t is_sbt; uint8_t cbf_mask; uint16_t pos_offset; uint8_t tr_skip_mask;
-    uint8_t cu_mts_flag; uint8_t cu_mts_idx; uint8_t lfnst_flag; uint8_t lfnst_idx;
-    struct TBInfo tb_info[3];
-};
-struct ISPTUInfo { uint8_t cbf_mask, tr_skip_mask, cu_mts_flag, cu_mts_idx, lfnst_flag, lfnst_idx; struct TBInfo tb_info[4]; };   /* rcn_transform_tree.c:68-76 */
-struct PROFInfo { int16_t dmv_scale_h_0[16], dmv_scale_v_0[16], dmv_scale_h_1[16], dmv_scale_v_1[16]; };
-
-extern uint64_t residual_coding_dpq(OVCTUDec *const, int16_t *const, uint8_t, uint8_t, uint16_t);
-extern int transform_unit_st(OVCTUDec *const, unsigned int, unsigned int, unsigned int, unsigned int, uint8_t, CUFlags, uint8_t, struct TUInfo *const);
-extern int transform_unit_l(OVCTUDec *const, unsigned int, unsigned int, unsigned int, unsigned int, uint8_t, CUFlags, uint8_t, struct TUInfo *const);
-extern int transform_unit_c(OVCTUDec *const, unsigned int, unsigned int, unsigned int, unsigned int, uint8_t, CUFlags, uint8_t, struct TUInfo *const);
-
-#ifndef LOG2_MIN_CU_S
-#define LOG2_MIN_CU_S 2                             /* rcn_transform_tree.c:45 */
-#endif
-#define MV_POS(xu, yu) (35 + (xu) + (yu) * 34)          /* PB_POS_IN_BUF, rcn_df.c:1524 */
-
 /* ------------------------------------------------------------------------------------ side table */
-enum { PEND_NONE = 0, PEND_AFFINE, PEND_BDOF };
-
-
-#define MAX_MARKS 136          /* CTU rows of a picture: 8192 / 64 + some */
-struct hip_entry {
-    const OVCTUDec *key;
-    struct RCNFunctions scalar;          /* the table as the scalar fill left it */
-    uint8_t ict_type, lmcs_flag;
-    ovhip_recorder *rec;                 /* the frame thread's recorder, or the bound one in record-only mode */
-    int record_only;
-    ovhip_frame *fr; int dev;            /* this OVCTUDec's frame thread on the device path (include/ovvc_hip.h) and its logical device */
-    int pic_w, pic_h, log2_ctu, nb_ctu_w, nb_ctu_h;
-    const OVFrame *frame;                /* picture being decoded */
-    int ctus_left;                       /* CTUs of that picture whose rect entries (tiles) have not ended yet: 0 = no picture open      */
-    int whole_pic_entry;                 /* the entry being decoded covers the picture (no tile borders inside)                          */
-    int err;
-    const OVPicture *refs[16]; int n_refs;
-    uint32_t scale_set;                 /* reference-table slots whose scale this picture already handed to the recorder */
-    ovhip_lmcs_luts luts; int have_luts, lmcs_region_live;
-    ovhip_sao_ctu *sao; ovhip_alf_ctu *alf; size_t n_ctu; int sao_on, alf_on;
-    int16_t alf_cc[2][4][8];
-    size_t n_refined;                    /* refined units recorded (BDOF and DMVR: the index space of the device's results)      */
-    size_t dmvr_done;                    /* ... whose vectors are already in the picture's TMVP planes                            */
-    size_t row_mark;                     /* ... recorded when the last row-end hook ran                                           */
-    int band_on;                         /* this picture goes to the device band by band (ovhip_frame_band), not at its end        */
-    uint32_t n_bands_sent, n_bands_deferred;
-    /* what had been recorded when CTU row y had just been parsed (y = index: rows_parsed - 1): the picture's last hook works through
-     * the rows its reference pictures had not reached during the parse with these (final_progressive) */
-    struct { ovhip_band_counts counts; size_t n_refined; } marks[MAX_MARKS]; int n_marks, rows_sent;
-    /* prediction calls being collected into one CU */
-    struct {
-        int kind, x0, y0, n, cols, rows_done, cur_col;
-        uint8_t inter_dir, prof_dir, bcw, ref_idx0, ref_idx1;
-        int32_t mv0[32 * 32 * 2], mv1[32 * 32 * 2];       /* affine: sub-block field, row stride 32 */
-        struct PROFInfo prof;
-        OVMV bmv0, bmv1; int bx[64], by[64], bl2w, bl2h;  /* BDOF blocks */
-    } pend;
-    /* the luma of an affine CU has been recorded (with its chroma): the rcn_mcp_b_c(3,3) calls of the SAME CU that follow
-     * carry nothing new.  Rectangle in CTU-local luma samples; any other slot call ends it. */
-    int aff_c_live, aff_c_x0, aff_c_y0, aff_c_x1, aff_c_y1;
-    struct { int depth; uint64_t t0, ticks_hooks, ticks_device, n_calls; } prof;
-#ifdef OVVC_HIP_CALLER_PATCH
-    /* CTU-row reports held back until the row's collocated motion vectors are final (rcn_report_ctu_line, shim/caller.patch) */
-    struct { OVPicture *pic; int y, x0, x1; size_t need; } reports[160];
-    int n_reports; size_t report_need; uint64_t n_reports_deferred;
-#endif
-    /* a CIIP CU whose planar tasks wait for the CU's transform unit (which carries their residual); closed without one by
-     * the next slot call that is not that transform unit */
-    struct { int live, x0, y0, log2_w, log2_h, has_c; ovhip_itask tl, tc; } ciip;
-};
-
-/* ---- where a frame thread's time goes inside the back-end (ovhip_shim_set_profile): every installed hook brackets itself; the
- * device half (begin_picture, dmvr_rows_step, flush_picture: waits for reference pictures, launches, ovhip_job_wait, the copy into the
- * OVFrame) is counted apart from the recording.  Off: one predictable branch per hook. */
-static int g_prof_on;
-#if defined(__x86_64__)
-static inline uint64_t prof_tick(void) { return __builtin_ia32_rdtsc(); }
-#else
-#include <time.h>
-static inline uint64_t prof_tick(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (uint64_t)t.tv_sec * 1000000000ull + (uint64_t)t.tv_nsec; }
-#endif
-#include <time.h>
-static uint64_t g_prof_tick0; static double g_prof_s0;
-static double prof_now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
-
 static struct hip_entry *g_entries[256];
 static pthread_mutex_t g_mtx = PTHREAD_MUTEX_INITIALIZER;
+unsigned g_entries_gen;
+__thread struct hip_tls tls_last;
 
-/* Every slot call starts here (the table has no user pointer).  The common case -- the same OVCTUDec as this thread's last call,
- * no entry released since -- is two thread-local compares; only a miss takes the mutex and scans (r2: mutex + scan on every call). */
-static unsigned g_entries_gen;
-static __thread const OVCTUDec *tls_key;
-static __thread struct hip_entry *tls_entry;
-static __thread unsigned tls_gen;
-
-static struct hip_entry *
-entry_of(const OVCTUDec *c, int create)
+/* entry_of (rcn_hip_priv.h) missed this thread's cached entry */
+struct hip_entry *
+entry_miss(const OVCTUDec *c, int create)
 {
-    if (tls_key == c && tls_entry && tls_gen == __atomic_load_n(&g_entries_gen, __ATOMIC_ACQUIRE)) return tls_entry;
     struct hip_entry *e = NULL;
     int free_slot = -1;
     pthread_mutex_lock(&g_mtx);
@@ -175,12 +60,12 @@ entry_of(const OVCTUDec *c, int create)
         e = calloc(1, sizeof(*e));
         if (e) { e->key = c; e->dev = -1; g_entries[free_slot] = e; }
     }
-    tls_key = c; tls_entry = e; tls_gen = g_entries_gen;
+    tls_last.key = c; tls_last.entry = e; tls_last.gen = g_entries_gen;
     pthread_mutex_unlock(&g_mtx);
     return e;
 }
 
-static void
+void
 latch(struct hip_entry *e, int code, const char *what)
 {
     if (code >= 0 || e->err) return;
@@ -204,1604 +89,7 @@ latch(struct hip_entry *e, int code, const char *what)
     ov_log(NULL, OVLOG_ERROR, "rcn_hip: %s failed (%d)%s%s\n", what, code, e->fr ? ": " : "", e->fr ? ovhip_frame_last_error(e->fr) : "");
 }
 
-struct prof_scope { struct hip_entry *e; };
-static inline struct prof_scope
-prof_enter(struct hip_entry *e)
-{
-    struct prof_scope p = { NULL };
-    if (g_prof_on && e) { p.e = e; if (e->prof.depth++ == 0) { e->prof.t0 = prof_tick(); e->prof.n_calls++; } }
-    return p;
-}
-static inline void prof_leave(struct prof_scope *p) { if (p->e && --p->e->prof.depth == 0) p->e->prof.ticks_hooks += prof_tick() - p->e->prof.t0; }
-#define PROF(e) struct prof_scope prof_scope_ __attribute__((cleanup(prof_leave))) = prof_enter(e)
-/* the device half inside a hook */
-#define PROF_DEVICE_BEGIN(e) const uint64_t prof_dev_t0_ = g_prof_on ? prof_tick() : 0
-#define PROF_DEVICE_END(e)   do { if (g_prof_on) (e)->prof.ticks_device += prof_tick() - prof_dev_t0_; } while (0)
-
-static inline OVCTUDec *ctudec_of_lmcs(struct LMCSInfo *li) { return (OVCTUDec *)((char *)li - offsetof(OVCTUDec, lmcs_info)); }
-
-/* ------------------------------------------------------------------------------------ helpers */
-/* Identity of a picture for the device DPB, beside its OVFrame pointer (which the frame pool hands to one picture after another):
- * coded video sequence + picture order count, never 0 (include/ovvc_hip.h, ovhip_dpb_begin_tag) */
-static inline uint64_t pic_tag(const OVPicture *p) { return (((uint64_t)p->cvs_id << 32) | (uint32_t)p->poc) + 1; }
-
-static int
-ref_slot(struct hip_entry *e, const OVPicture *p)
-{
-    for (int i = 0; i < e->n_refs; ++i) if (e->refs[i] == p) return i;
-    if (e->n_refs >= 16) { latch(e, OVHIP_EUNSUP, "more than 16 distinct reference pictures"); return 0; }
-    e->refs[e->n_refs] = p;
-    /* the frame thread keeps the same table (order of first use), keyed by the OVFrame: the device DPB hands the picture over */
-    if (e->fr && !e->record_only) {
-        const int k = ovhip_frame_ref_tag(e->fr, p->frame, pic_tag(p));
-        if (k != e->n_refs) latch(e, k < 0 ? k : OVHIP_EINVAL, "ovhip_frame_ref");
-    }
-    return e->n_refs++;
-}
-
-/* ref_slot, plus the slot's scale for reference picture resampling: scale_fact_rpl{list}[ref_idx] (ctudec_compute_refs_scaling,
- * ctudec.c:43-86), the reference's size and its chroma collocation flags -- read from rpl0[ref_idx] whatever the list, as
- * rcn_mcp_rpr_c does (rcn_inter.c:2322-2323; the flags are SPS-level).  Unscaled slots of the picture's size keep the recorder's
- * default; the recorder emits RPR units for the others or refuses what the device path does not take. */
-static int
-ref_slot_scaled(struct hip_entry *e, const OVCTUDec *c, const OVPicture *p, int list, int ref_idx)
-{
-    const int k = ref_slot(e, p);
-    const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    const uint16_t *sf = list ? ic->scale_fact_rpl1[ref_idx & 15] : ic->scale_fact_rpl0[ref_idx & 15];
-    const OVFrame *f = p->frame;
-    if (k < 0 || k >= 32 || ((e->scale_set >> k) & 1) || !f) return k;
-    if (sf[0] != (1 << RPR_SCALE_BITS) || sf[1] != (1 << RPR_SCALE_BITS) || (int)f->width != e->pic_w || (int)f->height != e->pic_h) {
-        const OVPicture *q = ic->rpl0[ref_idx & 15] ? ic->rpl0[ref_idx & 15] : p;
-        ovhip_ref_scale s;
-        memset(&s, 0, sizeof(s));
-        s.scale_hor = sf[0]; s.scale_ver = sf[1];
-        s.ref_w = (int32_t)f->width; s.ref_h = (int32_t)f->height;
-        s.chroma_hor_col_flag = q->scale_info.chroma_hor_col_flag; s.chroma_ver_col_flag = q->scale_info.chroma_ver_col_flag;
-        latch(e, ovhip_rec_set_ref_scale(e->rec, k, &s), "ovhip_rec_set_ref_scale");
-    }
-    e->scale_set |= 1u << k;
-    return k;
-}
-
-static void
-fill_pu_lists(struct hip_entry *e, const OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0, int log2_w, int log2_h, int inter_dir,
-              OVMV mv0, OVMV mv1, const OVPicture *p0, const OVPicture *p1, int list0, int list1)
-{
-    const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    const int l2 = c->part_ctx->log2_ctu_s;
-    memset(d, 0, sizeof(*d));
-    d->x0 = (uint16_t)((c->ctb_x << l2) + x0); d->y0 = (uint16_t)((c->ctb_y << l2) + y0);
-    d->log2_w = (uint8_t)log2_w; d->log2_h = (uint8_t)log2_h;
-    d->inter_dir = (uint8_t)inter_dir;
-    d->ref_idx0 = (uint8_t)mv0.ref_idx; d->ref_idx1 = (uint8_t)mv1.ref_idx;
-    d->bcw_idx_plus1 = mv0.bcw_idx_plus1;
-    d->prec_amvr_half = ic->prec_amvr == MV_PRECISION_HALF;
-    d->planes = 3;
-    d->lmcs = c->lmcs_info.lmcs_enabled_flag;
-    d->mv0x = mv0.x; d->mv0y = mv0.y; d->mv1x = mv1.x; d->mv1y = mv1.y;
-    /* reference picture resampling (rcn_mcp_rpr_*, rcn_inter.c:2769-2800): the slot's scale goes to the recorder with the slot */
-    if (p0 && (inter_dir & 1)) { d->poc0 = p0->poc; d->ref0 = (uint8_t)ref_slot_scaled(e, c, p0, list0, mv0.ref_idx); }
-    if (p1 && (inter_dir & 2)) { d->poc1 = p1->poc; d->ref1 = (uint8_t)ref_slot_scaled(e, c, p1, list1, mv1.ref_idx); }
-    if (inter_dir == 1) { d->ref1 = d->ref0; d->poc1 = d->poc0 + 1; }      /* keep the identical-motion test off */
-    if (inter_dir == 2) { d->ref0 = d->ref1; d->poc0 = d->poc1 + 1; }
-}
-
-static void
-fill_pu(struct hip_entry *e, const OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0, int log2_w, int log2_h, int inter_dir,
-        OVMV mv0, OVMV mv1, const OVPicture *p0, const OVPicture *p1)
-{
-    fill_pu_lists(e, c, d, x0, y0, log2_w, log2_h, inter_dir, mv0, mv1, p0, p1, 0, 1);
-}
-
-static void pend_close(struct hip_entry *e, OVCTUDec *c);
-static void ciip_close(struct hip_entry *e, OVCTUDec *c);
-
-/* every hook that is not part of the CU being collected closes it first */
-#define ENTER(c)                                               \
-    struct hip_entry *e = entry_of((c), 0);                    \
-    if (!e || !e->rec) return;                                 \
-    PROF(e);                                                   \
-    e->aff_c_live = 0;                                         \
-    if (e->ciip.live) ciip_close(e, (OVCTUDec *)(c));          \
-    if (e->pend.kind) pend_close(e, (OVCTUDec *)(c))
-
-/* ------------------------------------------------------------------------------------ transform units */
-static void
-fill_tu_state(const struct hip_entry *e, const OVCTUDec *c, ovhip_tu_state *st)
-{
-    memset(st, 0, sizeof(*st));
-    st->qp_y = c->dequant_luma.qp; st->qp_cb = c->dequant_cb.qp; st->qp_cr = c->dequant_cr.qp;
-    st->qp_jcbcr = c->dequant_joint_cb_cr.qp;
-    st->qp_y_skip = c->dequant_luma_skip.qp; st->qp_cb_skip = c->dequant_cb_skip.qp;
-    st->qp_cr_skip = c->dequant_cr_skip.qp; st->qp_jcbcr_skip = c->dequant_jcbcr_skip.qp;
-    st->dep_quant = c->residual_coding_l == &residual_coding_dpq;          /* rcn_transform_tree.c:399 */
-    st->mts_implicit = c->mts_implicit;
-    st->sh_ts_disabled = c->sh_ts_disabled;
-    st->ict_type = e->ict_type;
-    /* scale derived on the device from the region the last rcn_lmcs_compute_chroma_scale call recorded */
-    st->lmcs_scale_c = c->lmcs_info.scale_c_flag ? (e->lmcs_region_live ? 2 : 1) : 0;
-    st->lmcs_chroma_scale = (int16_t)c->lmcs_info.lmcs_chroma_scale;
-    st->intra_mode = (int8_t)c->intra_mode;
-}
-
-/* derive_lfnst_mode_c (drv_lfnst.c:94-121): DM / LM chroma modes take the co-located luma mode; then the wide-angle
- * remap of the CHROMA block shape */
-static int8_t
-lfnst_mode_c(const OVCTUDec *c, int log2_w, int log2_h, int x0, int y0)
-{
-    static const uint8_t shift_lut[6] = { 0, 6, 10, 12, 14, 15 };
-    const int l2 = c->part_ctx_c->log2_min_cb_s;
-    const int xu = x0 >> l2, yu = y0 >> l2, nw = (1 << log2_w) >> l2, nh = (1 << log2_h) >> l2;
-    int m = c->intra_mode_c;
-    if (m == OVINTRA_DM_CHROMA || (m >= OVINTRA_LM_CHROMA && m <= OVINTRA_MDLM_TOP))
-        m = c->drv_ctx.intra_info.luma_modes[xu + ((yu + (nh >> 1)) << 5) + (nw >> 1)];
-    if (m > OVINTRA_DC) {
-        const int d = log2_w - log2_h, ms = shift_lut[d < 0 ? -d : d];
-        if (log2_w > log2_h && m < 2 + ms) m += OVINTRA_VDIA - 1;
-        else if (log2_h > log2_w && m > OVINTRA_VDIA - ms) m -= OVINTRA_VDIA + 1;
-    }
-    return (int8_t)(m < 0 ? m + 14 + 67 : m >= 67 ? m + 14 : m);
-}
-
-
-/* ------------------------------------------------------------------------------------ ordered (intra) tasks */
-/* Availability of the two reference arms as the reference's fill_ref_* read it out of the progress bit-fields
- * (rcn_fill_ref.h:41-64; rcn_fill_ref.c:71-100, :166-190, :228-260): bit 0 of the shifted map = the corner unit, the
- * highest set bit = how far the arm is read. */
-static inline int top_bit(uint64_t m) { return m ? 64 - __builtin_clzll(m) : 0; }
-
-static void
-task_avl(const struct CTUBitField *pf, int x0, int y0, int log2_w, int log2_h, int log2_unit, ovhip_itask *t)
-{
-    const int nb_a = ((1 << (log2_w + 1)) >> log2_unit) + 1, nb_l = ((1 << (log2_h + 1)) >> log2_unit) + 1;
-    const uint64_t ma = (pf->hfield[y0 >> log2_unit] >> (x0 >> log2_unit)) & ((1llu << (nb_a + 1)) - 1);
-    const uint64_t ml = (pf->vfield[x0 >> log2_unit] >> (y0 >> log2_unit)) & ((1llu << (nb_l + 1)) - 1);
-    t->avl_abv = (uint8_t)top_bit(ma >> 1); t->avl_lft = (uint8_t)top_bit(ml >> 1);
-    if ((ma | ml) & 1) t->flags |= OVHIP_IF_CORNER;
-}
-
-static void
-luma_task(const OVCTUDec *c, int x0, int y0, int log2_w, int log2_h, CUFlags cu_flags, int mode, int ciip_wt, ovhip_itask *t)
-{
-    const int l2 = c->part_ctx->log2_ctu_s;
-    memset(t, 0, sizeof(*t));
-    t->kind = OVHIP_IT_LUMA;
-    t->x = (uint16_t)((c->ctb_x << l2) + x0); t->y = (uint16_t)((c->ctb_y << l2) + y0);
-    t->log2_w = (uint8_t)log2_w; t->log2_h = (uint8_t)log2_h;
-    t->mode = (uint8_t)mode; t->ciip_wt = (uint8_t)ciip_wt;
-    if (cu_flags & flg_mip_flag) {                                   /* rcn_intra_mip.c:388-402 */
-        t->flags |= OVHIP_IF_MIP | ((c->cu_opaque >> 7) & 1 ? OVHIP_IF_MIP_TR : 0);
-        t->mode = c->cu_opaque & 0x3f;
-    } else if (cu_flags & flg_intra_bdpcm_luma_flag) {
-        t->flags |= OVHIP_IF_BDPCM | ((cu_flags & flg_intra_bdpcm_luma_dir) ? OVHIP_IF_BDPCM_VER : 0);
-        t->mode = 0;
-    } else if (cu_flags & flg_mrl_flag) {
-        t->mrl_idx = c->cu_opaque;
-    }
-    task_avl(&c->rcn_ctx.progress_field, x0, y0, log2_w, log2_h, 2, t);
-}
-
-/* x0, y0, size in CHROMA samples */
-static void
-chroma_task(const OVCTUDec *c, int x0, int y0, int log2_w, int log2_h, CUFlags cu_flags, int mode, int ciip_wt, ovhip_itask *t)
-{
-    const int l2 = c->part_ctx->log2_ctu_s - 1;
-    const struct CTUBitField *pf = &c->rcn_ctx.progress_field_c;
-    memset(t, 0, sizeof(*t));
-    t->kind = OVHIP_IT_CHROMA;
-    t->x = (uint16_t)((c->ctb_x << l2) + x0); t->y = (uint16_t)((c->ctb_y << l2) + y0);
-    t->log2_w = (uint8_t)log2_w; t->log2_h = (uint8_t)log2_h;
-    t->mode = (uint8_t)mode; t->ciip_wt = (uint8_t)ciip_wt;
-    if (cu_flags & flg_intra_bdpcm_chroma_flag) {
-        t->flags |= OVHIP_IF_BDPCM | ((cu_flags & flg_intra_bdpcm_chroma_dir) ? OVHIP_IF_BDPCM_VER : 0);
-        t->mode = 0;
-    }
-    if (!(t->flags & OVHIP_IF_BDPCM) && mode >= OVINTRA_LM_CHROMA && mode <= OVINTRA_MDLM_TOP) {
-        /* the linear-model modes read their own availability (rcn_intra_cclm.c:56-68, :770-776, :843-849) */
-        const int w = 1 << log2_w, h = 1 << log2_h, ext = w < h ? w : h;
-        const uint64_t abv = pf->hfield[y0 >> 1] >> ((x0 >> 1) + 1), lft = pf->vfield[x0 >> 1] >> ((y0 >> 1) + 1);
-        const int any_abv = !!(abv & ((1llu << (w >> 1)) - 1)), any_lft = !!(lft & ((1llu << (h >> 1)) - 1));
-        t->mode = (uint8_t)(67 + (mode - OVINTRA_LM_CHROMA));
-        t->avl_abv = (uint8_t)any_abv; t->avl_lft = (uint8_t)any_lft;
-        if (mode == OVINTRA_MDLM_TOP && any_abv) t->avl_abv = (uint8_t)__builtin_ctzll(~(abv & ((1llu << ((w + ext) >> 1)) - 1)));
-        if (mode == OVINTRA_MDLM_LEFT && any_lft) t->avl_lft = (uint8_t)__builtin_ctzll(~(lft & ((1llu << ((h + ext) >> 1)) - 1)));
-        return;
-    }
-    task_avl(pf, x0, y0, log2_w, log2_h, 1, t);
-}
-
-static void
-record_tu(struct hip_entry *e, OVCTUDec *c, int tree, int x0, int y0, int log2_w, int log2_h, CUFlags cu_flags, uint8_t cbf_mask,
-          const struct TUInfo *tu, const ovhip_itask *task_l, const ovhip_itask *task_c)
-{
-    const int l2 = c->part_ctx->log2_ctu_s;
-    ovhip_tu_state st;
-    ovhip_tu_desc d;
-    fill_tu_state(e, c, &st);
-    memset(&d, 0, sizeof(d));
-    /* tree 2 (rcn_tu_c): x0, y0 and the size are in chroma samples; the picture offset likewise */
-    d.x0 = (uint16_t)(((c->ctb_x << l2) >> (tree == 2)) + x0); d.y0 = (uint16_t)(((c->ctb_y << l2) >> (tree == 2)) + y0);
-    d.log2_tb_w = (uint8_t)log2_w; d.log2_tb_h = (uint8_t)log2_h; d.tree = (uint8_t)tree;
-    d.cbf_mask = cbf_mask; d.cu_flags = (uint16_t)cu_flags;
-    d.tr_skip_mask = tu->tr_skip_mask; d.cu_mts_flag = tu->cu_mts_flag; d.cu_mts_idx = tu->cu_mts_idx;
-    d.lfnst_flag = tu->lfnst_flag; d.lfnst_idx = tu->lfnst_idx;
-    for (int k = 0; k < 3; ++k) { d.last_pos[k] = tu->tb_info[k].last_pos; d.sig_sb_map[k] = tu->tb_info[k].sig_sb_map; }
-    d.coef[0] = c->residual_cb + tu->pos_offset; d.coef[1] = c->residual_cr + tu->pos_offset; d.coef[2] = c->residual_y + tu->pos_offset;
-    if (tree == 2 && tu->lfnst_flag) st.lfnst_mode_c = lfnst_mode_c(c, log2_w, log2_h, x0, y0);
-    latch(e, ovhip_rec_tu_intra(e->rec, &st, &d, task_l, task_c), "ovhip_rec_tu_intra");
-}
-
-/* rcn_jcbcr (rcn_transform_tree.c:840-847): a joint Cb-Cr block with both cbf bits set is deblocked with the JOINT chroma QP --
- * the scalar orchestrator overwrites the two chroma QP maps the caller filled (vcl_transform_unit.c:1110-1112) for the block's area
- * (x0, y0, size in LUMA samples).  Found by the chained stream fixture (tests/golden/pipe_b.ovg: pps_cb_qp_offset != pps_cr_qp_offset). */
-static void
-jcbcr_qp_maps(OVCTUDec *c, int x0, int y0, int log2_w, int log2_h, uint8_t cbf_mask)
-{
-    if ((cbf_mask & 0x8) && (cbf_mask & 0x3) == 0x3) {
-        const uint8_t qp = (uint8_t)(c->dequant_joint_cb_cr.qp - c->qp_ctx.qp_bd_offset);
-        dbf_fill_qp_map(&c->dbf_info.qp_map_cb, x0, y0, log2_w, log2_h, qp);
-        dbf_fill_qp_map(&c->dbf_info.qp_map_cr, x0, y0, log2_w, log2_h, qp);
-    }
-}
-
-/* rcn_tu_st (rcn_transform_tree.c:1228-1301) with the luma task rcn_intra_tu made before it (or a CIIP CU's two tasks) */
-static void
-tu_st_common(struct hip_entry *e, OVCTUDec *c, int x0, int y0, int log2_tb_w, int log2_tb_h, CUFlags cu_flags, uint8_t cbf_mask,
-             const struct TUInfo *const tu, const ovhip_itask *task_l, const ovhip_itask *task_c)
-{
-    ovhip_itask tc;
-    if (cu_flags & flg_pred_mode_flag) {
-        /* :1270-1287: the chroma prediction of an intra CU sits between the TU's luma and chroma residuals */
-        ctu_field_set_rect_bitfield(&c->rcn_ctx.progress_field_c, x0 >> LOG2_MIN_CU_S, y0 >> LOG2_MIN_CU_S,
-                                    (1 << log2_tb_w) >> LOG2_MIN_CU_S, (1 << log2_tb_h) >> LOG2_MIN_CU_S);
-        if (!(cu_flags & flg_intra_bdpcm_chroma_flag)) fill_bs_map(&c->dbf_info.bs2_map_c, x0, y0, log2_tb_w, log2_tb_h);
-        chroma_task(c, x0 >> 1, y0 >> 1, log2_tb_w - 1, log2_tb_h - 1, cu_flags, c->intra_mode_c, 0, &tc);
-        task_c = &tc;
-    }
-    record_tu(e, c, 0, x0, y0, log2_tb_w, log2_tb_h, cu_flags, cbf_mask, tu, task_l, task_c);
-    /* what the scalar orchestrator leaves behind for deblocking (:1262-1267, :1299-1300; rcn_res_c / rcn_jcbcr
-     * :757-759, :793-795, :860-866) */
-    if (cbf_mask & 0x10) {
-        fill_bs_map(&c->dbf_info.bs1_map, x0, y0, log2_tb_w, log2_tb_h);
-        if ((cu_flags & flg_pred_mode_flag) && !(cu_flags & flg_intra_bdpcm_luma_flag)) fill_bs_map(&c->dbf_info.bs2_map, x0, y0, log2_tb_w, log2_tb_h);
-    }
-    if (!(cu_flags & flg_intra_bdpcm_chroma_flag)) {
-        if (cbf_mask & 0x8) {
-            fill_bs_map(&c->dbf_info.bs1_map_cb, x0, y0, log2_tb_w, log2_tb_h);
-            fill_bs_map(&c->dbf_info.bs1_map_cr, x0, y0, log2_tb_w, log2_tb_h);
-        } else {
-            if (cbf_mask & 0x2) fill_bs_map(&c->dbf_info.bs1_map_cb, x0, y0, log2_tb_w, log2_tb_h);
-            if (cbf_mask & 0x1) fill_bs_map(&c->dbf_info.bs1_map_cr, x0, y0, log2_tb_w, log2_tb_h);
-        }
-    }
-    fill_ctb_bound(&c->dbf_info, x0, y0, log2_tb_w, log2_tb_h);
-    fill_ctb_bound_c(&c->dbf_info, x0, y0, log2_tb_w, log2_tb_h);
-    jcbcr_qp_maps(c, x0, y0, log2_tb_w, log2_tb_h, cbf_mask);
-}
-
-/* tmp.rcn_tu_st (rcn_structures.h:481-486): called through the table by the SBT paths (vcl_transform_unit.c:1113-1299) */
-static void
-hip_rcn_tu_st(OVCTUDec *const c, uint8_t x0, uint8_t y0, uint8_t log2_tb_w, uint8_t log2_tb_h, CUFlags cu_flags, uint8_t cbf_mask,
-              const struct TUInfo *const tu)
-{
-    ENTER(c);
-    tu_st_common(e, c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, cbf_mask, tu, NULL, NULL);
-}
-
-/* tmp.rcn_tu_c (rcn_structures.h:475-479; rcn_transform_tree.c:1349-1382): dual-tree chroma and the chroma of an ISP CU,
- * always intra (x0, y0, size in chroma samples) */
-static void
-hip_rcn_tu_c(OVCTUDec *const c, uint8_t x0, uint8_t y0, uint8_t log2_tb_w, uint8_t log2_tb_h, CUFlags cu_flags, uint8_t cbf_mask,
-             const struct TUInfo *const tu)
-{
-    ENTER(c);
-    ovhip_itask tc;
-    ctu_field_set_rect_bitfield(&c->rcn_ctx.progress_field_c, (x0 << 1) >> LOG2_MIN_CU_S, (y0 << 1) >> LOG2_MIN_CU_S,
-                                (2 << log2_tb_w) >> LOG2_MIN_CU_S, (2 << log2_tb_h) >> LOG2_MIN_CU_S);
-    chroma_task(c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, c->intra_mode_c, 0, &tc);
-    fill_ctb_bound_c(&c->dbf_info, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1);
-    if (!(cu_flags & flg_intra_bdpcm_chroma_flag)) fill_bs_map(&c->dbf_info.bs2_map_c, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1);
-    record_tu(e, c, 2, x0, y0, log2_tb_w, log2_tb_h, cu_flags, cbf_mask, tu, NULL, &tc);
-    if (!(cu_flags & flg_intra_bdpcm_chroma_flag)) {
-        if (cbf_mask & 0x8) {
-            fill_bs_map(&c->dbf_info.bs1_map_cb, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1);
-            fill_bs_map(&c->dbf_info.bs1_map_cr, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1);
-        } else {
-            if (cbf_mask & 0x2) fill_bs_map(&c->dbf_info.bs1_map_cb, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1);
-            if (cbf_mask & 0x1) fill_bs_map(&c->dbf_info.bs1_map_cr, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1);
-        }
-    }
-    jcbcr_qp_maps(c, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1, cbf_mask);
-}
-
-/* tmp.rcn_transform_tree (rcn_structures.h:464-468; rcn_transform_tree.c:1454-1518): the walker calls its leaves
- * directly, not through the table, so the whole walk is restated here around the leaf hooks. */
-static void
-hip_rcn_transform_tree(OVCTUDec *const c, uint8_t x0, uint8_t y0, uint8_t log2_tb_w, uint8_t log2_tb_h, uint8_t log2_max_tb_s,
-                       uint8_t tr_depth, CUFlags cu_flags, const struct TUInfo *const tu)
-{
-    const int split_v = log2_tb_w > log2_max_tb_s, split_h = log2_tb_h > log2_max_tb_s;
-    const int nsub = tr_depth ? 1 : (1 << (split_v + split_h));
-    if (log2_tb_w > 6 && log2_tb_h < 7) {
-        hip_rcn_transform_tree(c, x0, y0, 6, log2_tb_h, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[0]);
-        hip_rcn_transform_tree(c, x0 + 64, y0, 6, log2_tb_h, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[8]);
-        return;
-    }
-    if (log2_tb_h > 6 && log2_tb_w < 7) {
-        hip_rcn_transform_tree(c, x0, y0, log2_tb_w, 6, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[0]);
-        hip_rcn_transform_tree(c, x0, y0 + 64, log2_tb_w, 6, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[8]);
-        return;
-    }
-    if (split_v || split_h) {
-        const int w1 = (1 << log2_tb_w) >> split_v, h1 = (1 << log2_tb_h) >> split_h;
-        const int l2w1 = log2_tb_w - split_v, l2h1 = log2_tb_h - split_h;
-        hip_rcn_transform_tree(c, x0, y0, l2w1, l2h1, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[0]);
-        if (split_v) hip_rcn_transform_tree(c, x0 + w1, y0, l2w1, l2h1, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[1 * nsub]);
-        if (split_h) hip_rcn_transform_tree(c, x0, y0 + h1, l2w1, l2h1, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[2 * nsub]);
-        if (split_h && split_v) hip_rcn_transform_tree(c, x0 + w1, y0 + h1, l2w1, l2h1, log2_max_tb_s, tr_depth + 1, cu_flags, &tu[3 * nsub]);
-        return;
-    }
-    /* leaf: rcn_res_wrap (:1432-1451) */
-    if (c->transform_unit == (void *)&transform_unit_c) {
-        hip_rcn_tu_c(c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, tu->cbf_mask, tu);
-    } else {
-        struct hip_entry *e = entry_of(c, 0);
-        PROF(e);
-        if (e && e->rec) {
-            ovhip_itask tl;
-            const ovhip_itask *task_l = NULL, *task_c = NULL;
-            e->aff_c_live = 0;
-            if (e->pend.kind) pend_close(e, c);
-            if (e->ciip.live) {
-                /* the transform unit of the CIIP CU recorded last carries the residual of its two planar tasks */
-                if (c->tmp_ciip && e->ciip.x0 == x0 && e->ciip.y0 == y0 && e->ciip.log2_w == log2_tb_w && e->ciip.log2_h == log2_tb_h) {
-                    task_l = &e->ciip.tl; task_c = e->ciip.has_c ? &e->ciip.tc : NULL;
-                    e->ciip.live = 0;
-                } else {
-                    ciip_close(e, c);
-                }
-            }
-            if (cu_flags & flg_pred_mode_flag) {
-                /* rcn_intra_tu (:1384-1430): the prediction reads the progress field, then extends it */
-                if (!(cu_flags & flg_isp_flag)) { luma_task(c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, c->intra_mode, 0, &tl); task_l = &tl; }
-                if (!(cu_flags & flg_intra_bdpcm_luma_flag)) fill_bs_map(&c->dbf_info.bs2_map, x0, y0, log2_tb_w, log2_tb_h);
-                ctu_field_set_rect_bitfield(&c->rcn_ctx.progress_field, x0 >> LOG2_MIN_CU_S, y0 >> LOG2_MIN_CU_S,
-                                            (1 << log2_tb_w) >> LOG2_MIN_CU_S, (1 << log2_tb_h) >> LOG2_MIN_CU_S);
-            }
-            if (c->transform_unit == (void *)&transform_unit_st) {
-                tu_st_common(e, c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, tu->cbf_mask, tu, task_l, task_c);
-            } else {
-                /* dual-tree luma: rcn_tu_l (:1305-1346) = the luma half of rcn_tu_st */
-                if (tu->cbf_mask || task_l) record_tu(e, c, 1, x0, y0, log2_tb_w, log2_tb_h, cu_flags, tu->cbf_mask ? 0x10 : 0, tu, task_l, NULL);
-                if (tu->cbf_mask) {
-                    fill_bs_map(&c->dbf_info.bs1_map, x0, y0, log2_tb_w, log2_tb_h);
-                    if ((cu_flags & flg_pred_mode_flag) && !(cu_flags & flg_intra_bdpcm_luma_flag)) fill_bs_map(&c->dbf_info.bs2_map, x0, y0, log2_tb_w, log2_tb_h);
-                }
-                fill_ctb_bound(&c->dbf_info, x0, y0, log2_tb_w, log2_tb_h);
-            }
-        }
-    }
-    if (c->tmp_ciip) {
-        fill_bs_map(&c->dbf_info.bs2_map, x0, y0, log2_tb_w, log2_tb_h);
-        fill_bs_map(&c->dbf_info.bs2_map_c, x0, y0, log2_tb_w, log2_tb_h);
-    }
-}
-
-/* tmp.recon_isp_subtree_v / _h (rcn_structures.h:480-491; rcn_transform_tree.c:1087-1205).  The caller has already marked the
- * whole CU in the progress field (vcl_transform_unit.c:1878), so the partitions see each other as available. */
-static void
-isp_subtree(OVCTUDec *const c, unsigned int x0, unsigned int y0, unsigned int log2_cb_w, unsigned int log2_cb_h, uint8_t intra_mode,
-            const struct ISPTUInfo *const tu, int vertical)
-{
-    ENTER(c);
-    const int l2 = c->part_ctx->log2_ctu_s;
-    const struct CTUBitField *pf = &c->rcn_ctx.progress_field;
-    ovhip_tu_state st;
-    ovhip_isp_desc d;
-    int32_t l2p, n_pb, l2pred, n_pred;
-    fill_tu_state(e, c, &st);
-    memset(&d, 0, sizeof(d));
-    ovhip_isp_geometry((int32_t)log2_cb_w, (int32_t)log2_cb_h, vertical, &l2p, &n_pb, &l2pred, &n_pred);
-    d.x0 = (uint16_t)((c->ctb_x << l2) + x0); d.y0 = (uint16_t)((c->ctb_y << l2) + y0);
-    d.log2_cb_w = (uint8_t)log2_cb_w; d.log2_cb_h = (uint8_t)log2_cb_h; d.vertical = (uint8_t)vertical; d.intra_mode = intra_mode;
-    d.cbf_mask = tu->cbf_mask; d.lfnst_flag = tu->lfnst_flag; d.lfnst_idx = tu->lfnst_idx; d.mts_enabled = c->mts_enabled;
-    d.coef = c->residual_y;
-    for (int i = 0; i < n_pb && i < 4; ++i) { d.last_pos[i] = tu->tb_info[i].last_pos; d.sig_sb_map[i] = tu->tb_info[i].sig_sb_map; }
-    const int nb_a = ((2 << log2_cb_w) >> 2) + 1, nb_l = ((2 << log2_cb_h) >> 2) + 1;
-    for (int k = 0; k < n_pred && k < 4; ++k) {
-        /* the maps intra_pred_isp hands to fill_ref_above_0 / fill_ref_left_0 for this call (rcn_intra.c:584-594) */
-        const int off = k << l2pred, px = (int)x0 + (vertical ? off : 0), py = (int)y0 + (vertical ? 0 : off), off_y = vertical ? 0 : off;
-        const uint64_t ma = (pf->hfield[(py >> 2) + !!(off_y % 4)] >> (x0 >> 2)) & ((1llu << (nb_a + 1)) - 1);
-        const uint64_t ml = (pf->vfield[px >> 2] >> (y0 >> 2)) & ((1llu << (nb_l + 1)) - 1);
-        d.corner[k] = (uint8_t)((ma & 1) | ((ml & 1) << 1));
-        d.avl_abv[k] = (uint8_t)top_bit(ma >> 1); d.avl_lft[k] = (uint8_t)top_bit(ml >> 1);
-        /* deblocking bookkeeping of the scalar orchestrator (:1136-1137, :1189-1192) */
-        if (vertical) {
-            fill_ctb_bound(&c->dbf_info, px, py, l2pred, log2_cb_h);
-            fill_bs_map(&c->dbf_info.bs2_map, px, py, l2pred, log2_cb_h);
-        } else if (!(off_y & 3)) {
-            fill_ctb_bound(&c->dbf_info, px, py, log2_cb_w, l2p >= 2 ? l2p : 2);
-            fill_bs_map(&c->dbf_info.bs2_map, px, py, log2_cb_w, l2p >= 2 ? l2p : 2);
-        }
-    }
-    latch(e, ovhip_rec_isp_cu(e->rec, &st, &d), "ovhip_rec_isp_cu");
-}
-
-static void
-hip_recon_isp_subtree_v(OVCTUDec *const c, unsigned int x0, unsigned int y0, unsigned int log2_cb_w, unsigned int log2_cb_h, uint8_t intra_mode,
-                        const struct ISPTUInfo *const tu)
-{ isp_subtree(c, x0, y0, log2_cb_w, log2_cb_h, intra_mode, tu, 1); }
-
-static void
-hip_recon_isp_subtree_h(OVCTUDec *const c, unsigned int x0, unsigned int y0, unsigned int log2_cb_w, unsigned int log2_cb_h, uint8_t intra_mode,
-                        const struct ISPTUInfo *const tu)
-{ isp_subtree(c, x0, y0, log2_cb_w, log2_cb_h, intra_mode, tu, 0); }
-
-/* Tools the device path does not implement.  The scalar slots would reconstruct into the CTU scratch, which this back-end never
- * copies to the frame: the picture would be silently wrong.  Latch an error instead (the picture is then not flushed and
- * ovhip_shim_last_error() / the decoder log say why). */
-static void
-hip_rcn_ibc(OVCTUDec *const c, int16_t x0, int16_t y0, uint8_t log2_cu_w, uint8_t log2_cu_h, uint8_t log2_ctu_s, IBCMV mv)
-{
-    (void)x0; (void)y0; (void)log2_cu_w; (void)log2_cu_h; (void)log2_ctu_s; (void)mv;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (e) latch(e, OVHIP_EUNSUP, "intra block copy (IBC) coding unit");
-}
-
-/* a CIIP CU without residual (no transform unit followed): its planar tasks alone */
-static void
-ciip_close(struct hip_entry *e, OVCTUDec *c)
-{
-    ovhip_tu_state st;
-    ovhip_tu_desc d;
-    e->ciip.live = 0;
-    fill_tu_state(e, c, &st);
-    memset(&d, 0, sizeof(d));
-    d.x0 = e->ciip.tl.x; d.y0 = e->ciip.tl.y; d.log2_tb_w = (uint8_t)e->ciip.log2_w; d.log2_tb_h = (uint8_t)e->ciip.log2_h;
-    latch(e, ovhip_rec_tu_intra(e->rec, &st, &d, &e->ciip.tl, e->ciip.has_c ? &e->ciip.tc : NULL), "ovhip_rec_tu_intra(ciip)");
-}
-
-/* ------------------------------------------------------------------------------------ prediction units */
-/* rcn_mcp_b (rcn_structures.h:640-646; rcn_inter.c:2769-2813) */
-static void
-hip_rcn_mcp_b(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx,
-              const OVMV mv0, const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int log2_pb_w, unsigned int log2_pb_h,
-              uint8_t inter_dir, uint8_t ref_idx0, uint8_t ref_idx1)
-{
-    (void)dst; (void)part_ctx;
-    ENTER(c);
-    ovhip_pu_desc d;
-    OVMV m0 = mv0, m1 = mv1;
-    m0.ref_idx = (int8_t)ref_idx0; m1.ref_idx = (int8_t)ref_idx1;
-    fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, inter_dir, m0, m1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-    latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu");
-}
-
-/* rcn_mcp (rcn_structures.h:636-638; rcn_inter.c:2750-2767): uni-prediction, type 0 = list 0 */
-static void
-hip_rcn_mcp(OVCTUDec *const c, struct OVBuffInfo dst, int x0, int y0, int log2_pu_w, int log2_pu_h, OVMV mv, uint8_t type, uint8_t ref_idx)
-{
-    (void)dst;
-    ENTER(c);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    ovhip_pu_desc d;
-    mv.ref_idx = (int8_t)ref_idx;
-    fill_pu(e, c, &d, x0, y0, log2_pu_w, log2_pu_h, type ? 2 : 1, mv, mv, type ? NULL : ic->rpl0[ref_idx], type ? ic->rpl1[ref_idx] : NULL);
-    d.bcw_idx_plus1 = 0;
-    latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu");
-}
-
-#ifndef OVVC_HIP_CALLER_PATCH
-/* ---- CUs the reference's callers cut into sub-block calls: collected back into one descriptor ---- */
-static void
-pend_close(struct hip_entry *e, OVCTUDec *c)
-{
-    const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    const int kind = e->pend.kind;
-    e->pend.kind = PEND_NONE;
-    if (kind == PEND_AFFINE) {
-        /* luma sub-blocks arrived in raster order: cols x rows of 4x4 */
-        const int cols = e->pend.cols ? e->pend.cols : e->pend.cur_col, rows = e->pend.n / (cols ? cols : 1);
-        int log2_w = 2, log2_h = 2;
-        while ((1 << log2_w) < cols * 4) ++log2_w;
-        while ((1 << log2_h) < rows * 4) ++log2_h;
-        if (cols * rows != e->pend.n || (4 << (log2_w - 2)) != cols * 4 || (4 << (log2_h - 2)) != rows * 4 || cols < 2 || rows < 2) {
-            /* not the affine drivers' pattern: each call is what the slot says it is, a 4x4 luma prediction (on a scaled reference:
-             * an ovhip_rpr_unit with the 4x4 filter sets, OVHIP_RPR_TOOL_PU4x4) */
-            if (e->pend.prof_dir) { latch(e, OVHIP_EINVAL, "PROF sub-block calls do not form a CU"); return; }
-            for (int i = 0; i < e->pend.n; ++i) {
-                const int row = cols ? i / cols : 0, col = cols ? i % cols : i, k = (row * 32 + col) * 2;
-                OVMV m0 = { .x = e->pend.mv0[k], .y = e->pend.mv0[k + 1], .ref_idx = (int8_t)e->pend.ref_idx0, .bcw_idx_plus1 = e->pend.bcw };
-                OVMV m1 = { .x = e->pend.mv1[k], .y = e->pend.mv1[k + 1], .ref_idx = (int8_t)e->pend.ref_idx1, .bcw_idx_plus1 = e->pend.bcw };
-                ovhip_pu_desc d;
-                fill_pu(e, c, &d, e->pend.x0 + 4 * col, e->pend.y0 + 4 * row, 2, 2, e->pend.inter_dir, m0, m1,
-                        ic->rpl0[e->pend.ref_idx0], ic->rpl1[e->pend.ref_idx1]);
-                d.planes = 1;
-                latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(4x4 luma)");
-            }
-            return;
-        }
-        ovhip_affine_desc d;
-        const int l2 = c->part_ctx->log2_ctu_s;
-        memset(&d, 0, sizeof(d));
-        d.x0 = (uint16_t)((c->ctb_x << l2) + e->pend.x0); d.y0 = (uint16_t)((c->ctb_y << l2) + e->pend.y0);
-        d.log2_w = (uint8_t)log2_w; d.log2_h = (uint8_t)log2_h;
-        d.inter_dir = e->pend.inter_dir; d.bcw_idx_plus1 = e->pend.bcw; d.prof_dir = e->pend.prof_dir;
-        d.lmcs = c->lmcs_info.lmcs_enabled_flag;
-        const OVPicture *p0 = (e->pend.inter_dir & 1) ? ic->rpl0[e->pend.ref_idx0] : NULL;
-        const OVPicture *p1 = (e->pend.inter_dir & 2) ? ic->rpl1[e->pend.ref_idx1] : NULL;
-        if (p0) { d.ref0 = (uint8_t)ref_slot_scaled(e, c, p0, 0, e->pend.ref_idx0); d.poc0 = p0->poc; }
-        if (p1) { d.ref1 = (uint8_t)ref_slot_scaled(e, c, p1, 1, e->pend.ref_idx1); d.poc1 = p1->poc; }
-        if (!p0) { d.ref0 = d.ref1; d.poc0 = d.poc1 + 1; }
-        if (!p1) { d.ref1 = d.ref0; d.poc1 = d.poc0 + 1; }
-        d.mv_stride = 32; d.mv0 = e->pend.mv0; d.mv1 = e->pend.mv1;
-        memcpy(d.dmv_scale[0], e->pend.prof.dmv_scale_h_0, 32); memcpy(d.dmv_scale[1], e->pend.prof.dmv_scale_v_0, 32);
-        memcpy(d.dmv_scale[2], e->pend.prof.dmv_scale_h_1, 32); memcpy(d.dmv_scale[3], e->pend.prof.dmv_scale_v_1, 32);
-        latch(e, ovhip_rec_affine_cu(e->rec, &d), "ovhip_rec_affine_cu");
-    } else if (kind == PEND_BDOF) {
-        /* BDOF blocks without the CU's chroma call (never issued by the reference's callers): luma only */
-        for (int i = 0; i < e->pend.n; ++i) {
-            ovhip_pu_desc d;
-            fill_pu(e, c, &d, e->pend.bx[i], e->pend.by[i], e->pend.bl2w, e->pend.bl2h, 3, e->pend.bmv0, e->pend.bmv1,
-                    ic->rpl0[e->pend.ref_idx0], ic->rpl1[e->pend.ref_idx1]);
-            d.refine = OVHIP_PU_BDOF; d.planes = 1;
-            latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(bdof block)");
-        }
-    }
-}
-
-static void
-pend_affine_add(struct hip_entry *e, OVCTUDec *c, int x0, int y0, OVMV mv0, OVMV mv1, uint8_t inter_dir, uint8_t ref_idx0,
-                uint8_t ref_idx1, uint8_t prof_dir, const struct PROFInfo *prof)
-{
-    e->aff_c_live = 0;
-    if (e->pend.kind == PEND_AFFINE) {
-        /* next sub-block in raster order?  (x advances by 4; a row ends when x returns to the CU's left edge) */
-        const int exp_x = e->pend.x0 + 4 * e->pend.cur_col, exp_y = e->pend.y0 + 4 * e->pend.rows_done;
-        const int wrap = x0 == e->pend.x0 && y0 == exp_y + 4 && e->pend.cur_col >= 2 && (!e->pend.cols || e->pend.cols == e->pend.cur_col);
-        if (wrap) { e->pend.cols = e->pend.cur_col; e->pend.rows_done++; e->pend.cur_col = 0; }
-        else if (!(x0 == exp_x && y0 == exp_y && (!e->pend.cols || e->pend.cur_col < e->pend.cols)) || prof_dir != e->pend.prof_dir
-                 || inter_dir != e->pend.inter_dir || e->pend.n >= 1024)
-            pend_close(e, c);
-    } else if (e->pend.kind) {
-        pend_close(e, c);
-    }
-    if (!e->pend.kind) {
-        e->pend.kind = PEND_AFFINE; e->pend.x0 = x0; e->pend.y0 = y0; e->pend.n = 0; e->pend.cols = 0; e->pend.rows_done = 0;
-        e->pend.cur_col = 0;
-        e->pend.inter_dir = inter_dir; e->pend.prof_dir = prof_dir; e->pend.bcw = mv0.bcw_idx_plus1;
-        e->pend.ref_idx0 = ref_idx0; e->pend.ref_idx1 = ref_idx1;
-        if (prof) e->pend.prof = *prof; else memset(&e->pend.prof, 0, sizeof(e->pend.prof));
-    }
-    const int k = (e->pend.rows_done * 32 + e->pend.cur_col) * 2;
-    e->pend.mv0[k] = mv0.x; e->pend.mv0[k + 1] = mv0.y; e->pend.mv1[k] = mv1.x; e->pend.mv1[k + 1] = mv1.y;
-    e->pend.cur_col++; e->pend.n++;
-}
-
-/* rcn_mcp_b_l (rcn_structures.h:648-654; rcn_inter.c:2815-2862).  The reference's only callers are the affine drivers,
- * one 4x4 sub-block per call (drv_affine_mvp.c:3264-3300). */
-static void
-hip_rcn_mcp_b_l(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx,
-                const OVMV mv0, const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int log2_pb_w, unsigned int log2_pb_h,
-                uint8_t inter_dir, uint8_t ref_idx0, uint8_t ref_idx1)
-{
-    (void)dst; (void)part_ctx;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (!e || !e->rec) return;
-    if (log2_pb_w == 2 && log2_pb_h == 2) { pend_affine_add(e, c, x0, y0, mv0, mv1, inter_dir, ref_idx0, ref_idx1, 0, NULL); return; }
-    if (e->pend.kind) pend_close(e, c);
-    ovhip_pu_desc d;
-    OVMV m0 = mv0, m1 = mv1;
-    m0.ref_idx = (int8_t)ref_idx0; m1.ref_idx = (int8_t)ref_idx1;
-    fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, inter_dir, m0, m1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-    d.planes = 1;
-    latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(luma)");
-}
-
-/* rcn_prof_mcp_b_l (rcn_structures.h:656-663; rcn_inter.c:2864-2918): 4x4 affine sub-block with PROF */
-static void
-hip_rcn_prof_mcp_b_l(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx,
-                     const OVMV mv0, const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int log2_pb_w, unsigned int log2_pb_h,
-                     uint8_t inter_dir, uint8_t ref_idx0, uint8_t ref_idx1, uint8_t prof_dir, const struct PROFInfo *const prof_info)
-{
-    (void)dst; (void)ic; (void)part_ctx; (void)log2_pb_w; (void)log2_pb_h;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (!e || !e->rec) return;
-    pend_affine_add(e, c, x0, y0, mv0, mv1, inter_dir, ref_idx0, ref_idx1, prof_dir, prof_info);
-}
-
-/* rcn_mcp_b_c (rcn_structures.h:665-671 region; rcn_inter.c:2920-2966): the chroma of an affine CU (8x8 luma area per
- * call, drv_affine_mvp.c:3371-3411), of a BDOF CU (whole CU, vcl_coding_unit.c:2469, :2664), or stand-alone */
-static void
-hip_rcn_mcp_b_c(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx,
-                const OVMV mv0, const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int log2_pb_w, unsigned int log2_pb_h,
-                uint8_t inter_dir, uint8_t ref_idx0, uint8_t ref_idx1)
-{
-    (void)dst; (void)part_ctx;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (!e || !e->rec) return;
-    if (e->pend.kind == PEND_AFFINE && log2_pb_w == 3 && log2_pb_h == 3 && (int)x0 == e->pend.x0 && (int)y0 == e->pend.y0) {
-        /* first chroma call of the affine CU being collected closes its luma; the recorder derives the chroma vectors
-         * of the whole CU itself (same averaging), so the remaining (3,3) calls inside the CU carry nothing new */
-        const int cols = e->pend.cols ? e->pend.cols : e->pend.cur_col, rows = e->pend.n / (cols ? cols : 1);
-        e->aff_c_x0 = e->pend.x0; e->aff_c_y0 = e->pend.y0; e->aff_c_x1 = e->pend.x0 + 4 * cols; e->aff_c_y1 = e->pend.y0 + 4 * rows;
-        pend_close(e, c);
-        e->aff_c_live = 1;
-        return;
-    }
-    if (e->aff_c_live && log2_pb_w == 3 && log2_pb_h == 3 && (int)x0 >= e->aff_c_x0 && (int)x0 < e->aff_c_x1
-        && (int)y0 >= e->aff_c_y0 && (int)y0 < e->aff_c_y1)
-        return;
-    e->aff_c_live = 0;
-    if (e->pend.kind == PEND_BDOF) {
-        /* the CU's chroma call: now the CU size is known -> one descriptor for the whole BDOF CU */
-        const int w = 1 << log2_pb_w, h = 1 << log2_pb_h, bw = w > 16 ? 16 : w, bh = h > 16 ? 16 : h;
-        int ok = (int)x0 == e->pend.bx[0] && (int)y0 == e->pend.by[0] && e->pend.n == (w / bw) * (h / bh) && (1 << e->pend.bl2w) == bw
-                 && (1 << e->pend.bl2h) == bh && mv0.x == e->pend.bmv0.x && mv0.y == e->pend.bmv0.y && mv1.x == e->pend.bmv1.x
-                 && mv1.y == e->pend.bmv1.y;
-        if (ok) {
-            e->pend.kind = PEND_NONE;
-            ovhip_pu_desc d;
-            fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, 3, e->pend.bmv0, e->pend.bmv1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-            d.refine = OVHIP_PU_BDOF;
-            latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(bdof cu)");
-            return;
-        }
-        pend_close(e, c);
-    } else if (e->pend.kind) {
-        pend_close(e, c);
-    }
-    ovhip_pu_desc d;
-    OVMV m0 = mv0, m1 = mv1;
-    m0.ref_idx = (int8_t)ref_idx0; m1.ref_idx = (int8_t)ref_idx1;
-    fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, inter_dir, m0, m1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-    d.planes = 2;
-    latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(chroma)");
-}
-
-/* rcn_bdof_mcp_l (rcn_structures.h:634-636 region; rcn_inter.c:1136-1250): one <=16x16 luma block of a BDOF CU */
-static void
-hip_rcn_bdof_mcp_l(OVCTUDec *const c, struct OVBuffInfo dst, uint8_t x0, uint8_t y0, uint8_t log2_pu_w, uint8_t log2_pu_h,
-                   OVMV mv0, OVMV mv1, uint8_t ref_idx0, uint8_t ref_idx1)
-{
-    (void)dst;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (!e || !e->rec) return;
-    e->aff_c_live = 0;
-    if (e->pend.kind == PEND_BDOF && (e->pend.n >= 64 || log2_pu_w != e->pend.bl2w || log2_pu_h != e->pend.bl2h || mv0.x != e->pend.bmv0.x
-                                      || mv0.y != e->pend.bmv0.y || mv1.x != e->pend.bmv1.x || mv1.y != e->pend.bmv1.y))
-        pend_close(e, c);
-    else if (e->pend.kind && e->pend.kind != PEND_BDOF)
-        pend_close(e, c);
-    if (!e->pend.kind) {
-        e->pend.kind = PEND_BDOF; e->pend.n = 0; e->pend.bl2w = log2_pu_w; e->pend.bl2h = log2_pu_h;
-        e->pend.bmv0 = mv0; e->pend.bmv1 = mv1; e->pend.bmv0.ref_idx = (int8_t)ref_idx0; e->pend.bmv1.ref_idx = (int8_t)ref_idx1;
-        e->pend.ref_idx0 = ref_idx0; e->pend.ref_idx1 = ref_idx1;
-    }
-    e->pend.bx[e->pend.n] = x0; e->pend.by[e->pend.n] = y0; e->pend.n++;
-}
-
-/* rcn_dmvr_mv_refine (rcn_structures.h:628-632; rcn_inter.c:872-1126).
- *
- * The `OVMV *mv0, *mv1` in/out contract: the reference refines synchronously and its caller copies the result into the
- * CTU's TMVP storage (vcl_coding_unit.c:2629-2645), which store_inter_maps moves into the picture's MV plane at the end
- * of the CTU (drv_lines.c:270-330).  Here the search runs on the device at the end of the CTU ROW (the
- * alf.rcn_alf_filter_line hook below -> ovhip_job_dmvr_rows): the slot returns the vectors unrefined and remembers
- * where the caller's stores end up in the picture's MV plane; the hook patches those entries BEFORE the row is published
- * (ovdpb_report_decoded_ctu_line, slicedec.c:940-955), so every reader of the collocated motion field (tmvp of later
- * pictures, drv_mvp.c:281-345) sees refined vectors exactly when the reference guarantees them. */
-static uint8_t
-hip_rcn_dmvr_mv_refine(OVCTUDec *const c, struct OVBuffInfo dst, uint8_t x0, uint8_t y0, uint8_t log2_pu_w, uint8_t log2_pu_h,
-                       OVMV *mv0, OVMV *mv1, uint8_t ref_idx0, uint8_t ref_idx1, uint8_t apply_bdof)
-{
-    (void)dst;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (!e || !e->rec) return 0;
-    e->aff_c_live = 0;
-    if (e->pend.kind) pend_close(e, c);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    ovhip_pu_desc d;
-    OVMV m0 = *mv0, m1 = *mv1;
-    m0.ref_idx = (int8_t)ref_idx0; m1.ref_idx = (int8_t)ref_idx1;
-    fill_pu(e, c, &d, x0, y0, log2_pu_w, log2_pu_h, 3, m0, m1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-    d.refine = OVHIP_PU_DMVR | (apply_bdof ? OVHIP_PU_BDOF : 0);
-    size_t n_before = 0, n_after = 0;
-    ovhip_rec_mcx_units(e->rec, &n_before);
-    int r = ovhip_rec_pu(e->rec, &d);
-    latch(e, r, "ovhip_rec_pu(dmvr)");
-    ovhip_rec_mcx_units(e->rec, &n_after);
-    if (r < 0 || n_after != n_before + 1) return 0;
-    /* where the unit's vectors live in the picture's TMVP planes (8x8 grid) is derived on the device from the unit itself
-     * (ovhip_tmvp_cells_launch: the caller writes tmvp_mv[l].mvs[((x0 + 7) >> 3) + ((y0 + 7) >> 3) * 16] and its right / lower
-     * neighbours for 16-wide / 16-high blocks, tmvp_store_mv copies row i of that array to plane->mvs + ctb_offset + i * pln_stride);
-     * r2 kept eight host pointers per unit here */
-    e->n_refined = n_after;
-    return 0;      /* disable_bdof: unused by the caller (vcl_coding_unit.c:2621) */
-}
-
-#else  /* OVVC_HIP_CALLER_PATCH: the caller hands over whole coding units (shim/caller.patch) -- nothing to stitch */
-static void pend_close(struct hip_entry *e, OVCTUDec *c) { (void)e; (void)c; }
-
-/* rcn_cu_inter_b (shim/caller.patch): a bi-predicted coding unit with BDOF and / or DMVR, where the unpatched caller makes one
- * rcn_bdof_mcp_l / rcn_dmvr_mv_refine call per <= 16x16 block and one rcn_mcp_b_c call (vcl_coding_unit.c:2450-2472, :2598-2668).
- * The recorder cuts it the same way (ovhip_rec_cu_inter -> rec_pu_refined).  DMVR: the caller stores nothing into its collocated
- * motion arrays here (the unrefined vectors drv_merge_mvp_b wrote stay); the refined ones are patched into the picture's planes by
- * the row-end hooks, exactly as on the unpatched path (dmvr_rows_step). */
-static void
-hip_rcn_cu_inter_b(OVCTUDec *const c, const OVMV mv0, const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int log2_cb_w,
-                   unsigned int log2_cb_h, uint8_t inter_dir, uint8_t ref_idx0, uint8_t ref_idx1, uint8_t refine)
-{
-    ENTER(c);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    ovhip_pu_desc d;
-    OVMV m0 = mv0, m1 = mv1;
-    m0.ref_idx = (int8_t)ref_idx0; m1.ref_idx = (int8_t)ref_idx1;
-    fill_pu(e, c, &d, x0, y0, log2_cb_w, log2_cb_h, inter_dir, m0, m1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-    d.refine = (uint8_t)(((refine & 1) ? OVHIP_PU_BDOF : 0) | ((refine & 2) ? OVHIP_PU_DMVR : 0));
-    const int r = ovhip_rec_cu_inter(e->rec, &d, NULL);
-    latch(e, r, "ovhip_rec_cu_inter");
-    if (r >= 0 && (refine & 2)) { size_t n = 0; ovhip_rec_mcx_units(e->rec, &n); e->n_refined = n; }
-}
-
-/* rcn_affine_cu (shim/caller.patch): an affine coding unit, where the unpatched drivers make one rcn_mcp_b_l / rcn_prof_mcp_b_l call
- * per 4x4 luma block and one rcn_mcp_b_c call per 8x8 luma area (drv_affine_mvp.c:3264-3411): the sub-block motion field is read
- * where the driver left it (inter_ctx->mv_ctx0 / mv_ctx1, 34 vectors per row). */
-static void
-hip_rcn_affine_cu(OVCTUDec *const c, struct InterDRVCtx *const ic, uint8_t x0, uint8_t y0, uint8_t log2_cu_w, uint8_t log2_cu_h,
-                  uint8_t inter_dir, uint8_t prof_dir, const struct PROFInfo *const prof)
-{
-    ENTER(c);
-    const int l2 = c->part_ctx->log2_ctu_s, cols = (1 << log2_cu_w) >> 2, rows = (1 << log2_cu_h) >> 2;
-    const OVMV *b0 = &ic->mv_ctx0.mvs[MV_POS(x0 >> 2, y0 >> 2)], *b1 = &ic->mv_ctx1.mvs[MV_POS(x0 >> 2, y0 >> 2)];
-    const uint8_t ref_idx0 = (uint8_t)b0->ref_idx, ref_idx1 = (uint8_t)b1->ref_idx;
-    for (int i = 0; i < rows; ++i)
-        for (int j = 0; j < cols; ++j) {
-            const int k = (i * 32 + j) * 2;
-            e->pend.mv0[k] = b0[i * 34 + j].x; e->pend.mv0[k + 1] = b0[i * 34 + j].y;
-            e->pend.mv1[k] = b1[i * 34 + j].x; e->pend.mv1[k + 1] = b1[i * 34 + j].y;
-        }
-    ovhip_affine_desc d;
-    memset(&d, 0, sizeof(d));
-    d.x0 = (uint16_t)((c->ctb_x << l2) + x0); d.y0 = (uint16_t)((c->ctb_y << l2) + y0);
-    d.log2_w = log2_cu_w; d.log2_h = log2_cu_h;
-    d.inter_dir = inter_dir; d.bcw_idx_plus1 = b0->bcw_idx_plus1; d.prof_dir = prof_dir;
-    d.lmcs = c->lmcs_info.lmcs_enabled_flag;
-    const OVPicture *p0 = (inter_dir & 1) ? ic->rpl0[ref_idx0] : NULL, *p1 = (inter_dir & 2) ? ic->rpl1[ref_idx1] : NULL;
-    if (p0) { d.ref0 = (uint8_t)ref_slot_scaled(e, c, p0, 0, ref_idx0); d.poc0 = p0->poc; }
-    if (p1) { d.ref1 = (uint8_t)ref_slot_scaled(e, c, p1, 1, ref_idx1); d.poc1 = p1->poc; }
-    if (!p0) { d.ref0 = d.ref1; d.poc0 = d.poc1 + 1; }
-    if (!p1) { d.ref1 = d.ref0; d.poc1 = d.poc0 + 1; }
-    d.mv_stride = 32; d.mv0 = e->pend.mv0; d.mv1 = e->pend.mv1;
-    if (prof) {
-        memcpy(d.dmv_scale[0], prof->dmv_scale_h_0, 32); memcpy(d.dmv_scale[1], prof->dmv_scale_v_0, 32);
-        memcpy(d.dmv_scale[2], prof->dmv_scale_h_1, 32); memcpy(d.dmv_scale[3], prof->dmv_scale_v_1, 32);
-    }
-    latch(e, ovhip_rec_cu_inter(e->rec, NULL, &d), "ovhip_rec_cu_inter(affine)");
-}
-
-/* the five slots only the unpatched callers reach (sub-block calls of affine / BDOF / DMVR coding units) */
-static void
-hip_unreached(OVCTUDec *const c, const char *slot)
-{
-    struct hip_entry *e = entry_of(c, 0);
-    if (e) latch(e, OVHIP_EINVAL, slot);
-}
-static void hip_rcn_mcp_b_l(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx, const OVMV mv0,
-                            const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int l2w, unsigned int l2h, uint8_t dir, uint8_t r0, uint8_t r1)
-{ (void)dst; (void)ic; (void)part_ctx; (void)mv0; (void)mv1; (void)x0; (void)y0; (void)l2w; (void)l2h; (void)dir; (void)r0; (void)r1; hip_unreached(c, "rcn_mcp_b_l called by a patched caller"); }
-static void hip_rcn_mcp_b_c(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx, const OVMV mv0,
-                            const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int l2w, unsigned int l2h, uint8_t dir, uint8_t r0, uint8_t r1)
-{ (void)dst; (void)ic; (void)part_ctx; (void)mv0; (void)mv1; (void)x0; (void)y0; (void)l2w; (void)l2h; (void)dir; (void)r0; (void)r1; hip_unreached(c, "rcn_mcp_b_c called by a patched caller"); }
-static void hip_rcn_prof_mcp_b_l(OVCTUDec *const c, struct OVBuffInfo dst, struct InterDRVCtx *const ic, const OVPartInfo *const part_ctx, const OVMV mv0,
-                                 const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int l2w, unsigned int l2h, uint8_t dir, uint8_t r0, uint8_t r1,
-                                 uint8_t prof_dir, const struct PROFInfo *const prof)
-{ (void)dst; (void)ic; (void)part_ctx; (void)mv0; (void)mv1; (void)x0; (void)y0; (void)l2w; (void)l2h; (void)dir; (void)r0; (void)r1; (void)prof_dir; (void)prof; hip_unreached(c, "rcn_prof_mcp_b_l called by a patched caller"); }
-static void hip_rcn_bdof_mcp_l(OVCTUDec *const c, struct OVBuffInfo dst, uint8_t x0, uint8_t y0, uint8_t l2w, uint8_t l2h, OVMV mv0, OVMV mv1, uint8_t r0, uint8_t r1)
-{ (void)dst; (void)x0; (void)y0; (void)l2w; (void)l2h; (void)mv0; (void)mv1; (void)r0; (void)r1; hip_unreached(c, "rcn_bdof_mcp_l called by a patched caller"); }
-static uint8_t hip_rcn_dmvr_mv_refine(OVCTUDec *const c, struct OVBuffInfo dst, uint8_t x0, uint8_t y0, uint8_t l2w, uint8_t l2h, OVMV *mv0, OVMV *mv1,
-                                      uint8_t r0, uint8_t r1, uint8_t apply_bdof)
-{ (void)dst; (void)x0; (void)y0; (void)l2w; (void)l2h; (void)mv0; (void)mv1; (void)r0; (void)r1; (void)apply_bdof; hip_unreached(c, "rcn_dmvr_mv_refine called by a patched caller"); return 0; }
-#endif /* OVVC_HIP_CALLER_PATCH */
-
-/* Entries of the picture's collocated motion planes as the device derived them (ovhip_job_tmvp_cells: 4 per refined unit, cell =
- * index into MVPlane.mvs, OVHIP_TMVP_NONE = unused / not a DMVR unit / outside what tmvp_store_mv copies): x and y of both lists. */
-int
-ovhip_shim_apply_tmvp_cells(OVCTUDec *c, const ovhip_tmvp_cell *cells, size_t n_entries)
-{
-    if (!c || (!cells && n_entries)) return OVHIP_EINVAL;
-    const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    const struct MVPlane *pl0 = ic->tmvp_ctx.plane0, *pl1 = ic->tmvp_ctx.plane1;
-    if (!pl0 || !pl1 || !pl0->mvs || !pl1->mvs) return OVHIP_OK;         /* the picture keeps no motion field */
-#ifdef OVVC_HIP_DEBUG_TMVP          /* debug scaffolding: compiled out of the product (it used to getenv() in every row hook) */
-    {
-        size_t nz = 0, nn = 0;
-        for (size_t i = 0; i < n_entries; ++i) { nn += cells[i].cell != OVHIP_TMVP_NONE; nz += cells[i].cell != OVHIP_TMVP_NONE && !cells[i].mv0x && !cells[i].mv0y && !cells[i].mv1x && !cells[i].mv1y; }
-        fprintf(stderr, "    tmvp patch ctudec %p: %zu entries, %zu used, %zu of them all-zero; first used:", (void *)c, n_entries, nn, nz);
-        for (size_t i = 0, k = 0; i < n_entries && k < 3; ++i) if (cells[i].cell != OVHIP_TMVP_NONE) { fprintf(stderr, " [%u: %d %d %d %d]", cells[i].cell, cells[i].mv0x, cells[i].mv0y, cells[i].mv1x, cells[i].mv1y); ++k; }
-        fprintf(stderr, "\n");
-    }
-#endif
-    for (size_t i = 0; i < n_entries; ++i) {
-        const ovhip_tmvp_cell *q = &cells[i];
-        if (q->cell == OVHIP_TMVP_NONE) continue;
-        pl0->mvs[q->cell].x = q->mv0x; pl0->mvs[q->cell].y = q->mv0y;
-        pl1->mvs[q->cell].x = q->mv1x; pl1->mvs[q->cell].y = q->mv1y;
-    }
-    return OVHIP_OK;
-}
-
-/* rcn_gpm_b (rcn_structures.h:687-688; rcn_inter.c:3118-3143) */
-static void
-hip_rcn_gpm_b(OVCTUDec *const c, struct VVCGPM *g, int x0, int y0, int log2_pb_w, int log2_pb_h)
-{
-    ENTER(c);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    const OVPicture *p0 = g->inter_dir0 == 1 ? ic->rpl0[g->mv0.ref_idx] : ic->rpl1[g->mv0.ref_idx];
-    const OVPicture *p1 = g->inter_dir1 == 1 ? ic->rpl0[g->mv1.ref_idx] : ic->rpl1[g->mv1.ref_idx];
-    ovhip_pu_desc d;
-    fill_pu_lists(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, 3, g->mv0, g->mv1, p0, p1, g->inter_dir0 == 1 ? 0 : 1, g->inter_dir1 == 1 ? 0 : 1);
-    d.bcw_idx_plus1 = 0;
-    d.refine = OVHIP_PU_GPM; d.gpm_split_dir = (uint8_t)g->split_dir;
-    latch(e, ovhip_rec_pu(e->rec, &d), "ovhip_rec_pu(gpm)");
-}
-
-/* rcn_ciip_b / rcn_ciip (rcn_structures.h:673-683; rcn_inter.c:3011-3067): inter part + planar intra + blend */
-static void
-ciip_common(struct hip_entry *e, OVCTUDec *c, ovhip_pu_desc *d, int x0, int y0, int log2_pb_w, int log2_pb_h)
-{
-    const int l2 = c->part_ctx->log2_min_cb_s;
-    const int mode_abv = c->part_map.cu_mode_x[(x0 + (1 << log2_pb_w) - 1) >> l2];
-    const int mode_lft = c->part_map.cu_mode_y[(y0 + (1 << log2_pb_h) - 1) >> l2];
-    const int wt = 1 + (mode_abv == OV_INTRA || mode_abv == OV_MIP) + (mode_lft == OV_INTRA || mode_lft == OV_MIP);    /* rcn_inter.c:2975-2981 */
-    latch(e, ovhip_rec_pu(e->rec, d), "ovhip_rec_pu(ciip)");
-    /* the planar predictions (intra_pred / intra_pred_c with mode 0 and no CU flags, rcn_inter.c:3026-3028) and the blend
-     * belong to the ordered pass: two tasks with the CU's weight, the references read out of the progress fields as they
-     * are now; chroma blocks 2 samples wide keep the inter prediction (:2997-2999) */
-    e->ciip.live = 1; e->ciip.x0 = x0; e->ciip.y0 = y0; e->ciip.log2_w = log2_pb_w; e->ciip.log2_h = log2_pb_h;
-    luma_task(c, x0, y0, log2_pb_w, log2_pb_h, 0, OVINTRA_PLANAR, wt, &e->ciip.tl);
-    e->ciip.has_c = log2_pb_w > 2;
-    if (e->ciip.has_c) chroma_task(c, x0 >> 1, y0 >> 1, log2_pb_w - 1, log2_pb_h - 1, 0, OVINTRA_PLANAR, wt, &e->ciip.tc);
-}
-
-static void
-hip_rcn_ciip_b(OVCTUDec *const c, const OVMV mv0, const OVMV mv1, unsigned int x0, unsigned int y0, unsigned int log2_pb_w,
-               unsigned int log2_pb_h, uint8_t inter_dir, uint8_t ref_idx0, uint8_t ref_idx1)
-{
-    ENTER(c);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    ovhip_pu_desc d;
-    OVMV m0 = mv0, m1 = mv1;
-    m0.ref_idx = (int8_t)ref_idx0; m1.ref_idx = (int8_t)ref_idx1;
-    fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, inter_dir, m0, m1, ic->rpl0[ref_idx0], ic->rpl1[ref_idx1]);
-    ciip_common(e, c, &d, x0, y0, log2_pb_w, log2_pb_h);
-}
-
-static void
-hip_rcn_ciip(OVCTUDec *const c, int x0, int y0, int log2_pb_w, int log2_pb_h, OVMV mv, uint8_t ref_idx)
-{
-    ENTER(c);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    ovhip_pu_desc d;
-    mv.ref_idx = (int8_t)ref_idx;
-    fill_pu(e, c, &d, x0, y0, log2_pb_w, log2_pb_h, 1, mv, mv, ic->rpl0[ref_idx], NULL);
-    d.bcw_idx_plus1 = 0;
-    ciip_common(e, c, &d, x0, y0, log2_pb_w, log2_pb_h);
-}
-
-/* ------------------------------------------------------------------------------------ LMCS */
-/* rcn_init_lmcs (rcn_structures.h:540; rcn_lmcs.c:345-361): the scalar one keeps filling lmcs_info (the parse loop
- * reads it); the device tables are built from the same APS data */
-static void
-hip_rcn_init_lmcs(struct LMCSInfo *li, const struct OVLMCSData *const ld)
-{
-    OVCTUDec *c = ctudec_of_lmcs(li);
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (!e) return;
-    e->scalar.rcn_init_lmcs(li, ld);
-    ovhip_lmcs_data hd;
-    memset(&hd, 0, sizeof(hd));
-    hd.min_bin_idx = ld->lmcs_min_bin_idx; hd.delta_max_bin_idx = ld->lmcs_delta_max_bin_idx;
-    hd.crs_offset = (int16_t)(ld->lmcs_delta_sign_crs_flag ? -ld->lmcs_delta_abs_crs : ld->lmcs_delta_abs_crs);
-    for (int i = 0; i < 16; ++i) hd.cw_delta[i] = (int16_t)(ld->lmcs_delta_sign_cw_flag[i] ? -ld->lmcs_delta_abs_cw[i] : ld->lmcs_delta_abs_cw[i]);
-    latch(e, ovhip_lmcs_build(&hd, &e->luts), "ovhip_lmcs_build");
-    e->have_luts = 1;
-}
-
-/* rcn_lmcs_compute_chroma_scale (rcn_structures.h:535-538; rcn_lmcs.c:320-343): needs RECONSTRUCTED luma around the
- * 64x64 region, which only exists on the device -> record the region; the TUs that follow refer to it */
-static void
-hip_lmcs_chroma_scale(struct LMCSInfo *const li, int16_t stride, const struct CTUBitField *const pf, const OVSample *ctu_y,
-                      uint8_t x0, uint8_t y0)
-{
-    (void)stride; (void)ctu_y;
-    OVCTUDec *c = ctudec_of_lmcs(li);
-    ENTER(c);
-    const int l2 = c->part_ctx->log2_ctu_s;
-    const uint32_t abv = (uint32_t)((pf->hfield[y0 >> 2] >> ((x0 >> 2) + 1)) & 0xffff);
-    const uint32_t lft = (uint32_t)((pf->vfield[x0 >> 2] >> ((y0 >> 2) + 1)) & 0xffff);
-    int r = ovhip_rec_lmcs_region(e->rec, (c->ctb_x << l2) + x0, (c->ctb_y << l2) + y0, abv, lft);
-    latch(e, r, "ovhip_rec_lmcs_region");
-    e->lmcs_region_live = r >= 0;
-}
-
-/* lmcs_reshape_backward per CTU (slicedec.c:746-750): one launch per picture in the flush instead */
-static void hip_noop_reshape(OVSample *dst, ptrdiff_t stride, const struct LMCSLUTs *const luts, int w, int h)
-{ (void)dst; (void)stride; (void)luts; (void)w; (void)h; }
-
-/* ------------------------------------------------------------------------------------ deblocking */
-/* The CTU's maps are read where they lie in the decoder's struct DBFInfo (ovhip_dbf_view: same element layout, include/ovvc_hip.h); r3 / r4
- * filled and copied a 9 KB descriptor per CTU. */
-static void
-view_dbf(ovhip_dbf_view *o, const struct DBFInfo *d)
-{
-    o->ctb_bound_ver = d->ctb_bound_ver; o->ctb_bound_hor = d->ctb_bound_hor; o->ctb_bound_ver_c = d->ctb_bound_ver_c; o->ctb_bound_hor_c = d->ctb_bound_hor_c;
-    o->aff_edg_ver = d->aff_edg_ver; o->aff_edg_hor = d->aff_edg_hor;
-    o->bs2_ver = d->bs2_map.ver; o->bs2_hor = d->bs2_map.hor; o->bs2c_ver = d->bs2_map_c.ver; o->bs2c_hor = d->bs2_map_c.hor;
-    o->bs1_ver = d->bs1_map.ver; o->bs1_hor = d->bs1_map.hor; o->bs1cb_ver = d->bs1_map_cb.ver; o->bs1cb_hor = d->bs1_map_cb.hor;
-    o->bs1cr_ver = d->bs1_map_cr.ver; o->bs1cr_hor = d->bs1_map_cr.hor; o->affine_ver = d->affine_map.ver; o->affine_hor = d->affine_map.hor;
-    o->qp_y = d->qp_map_y.hor; o->qp_cb = d->qp_map_cb.hor; o->qp_cr = d->qp_map_cr.hor;
-    o->beta_offset = d->beta_offset; o->tc_offset = d->tc_offset;
-    o->disable_v = d->disable_v; o->disable_h = d->disable_h;
-    o->pad = 0;
-}
-
-static void
-dbf_ctu(const struct OVRCNCtx *const r, struct DBFInfo *const dbf, uint8_t log2_ctu_s, uint8_t last_x, uint8_t last_y, int ctu_w, int ctu_h)
-{
-    OVCTUDec *c = r->ctudec;
-    ENTER(c);
-    ovhip_dbf_view s;
-    view_dbf(&s, dbf);
-    s.log2_ctu_s = log2_ctu_s; s.last_x = last_x; s.last_y = last_y;
-    s.ctu_lft = !!(c->ctu_ngh_flags & CTU_LFT_FLG); s.ctu_abv = !!(c->ctu_ngh_flags & CTU_UP_FLG);
-    s.ctu_w = (uint16_t)ctu_w; s.ctu_h = (uint16_t)ctu_h;
-    s.ctb_x = c->ctb_x; s.ctb_y = c->ctb_y;
-    if (c->tmp_slice_type != 2) {
-        /* P / B slices: the slot's own MV-based boundary-strength pre-pass (dbf_ctu_preproc_v/_h, rcn_df.c:1821-1874;
-         * static there) on the CTU's motion grids, straight into dbf_info->bs1_map as the scalar slot leaves it:
-         * dbf_store_info() carries it to the neighbouring CTUs (slicedec.c:872-877). */
-        const struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-        ovhip_dbf_mv_ctx mc;
-        memset(&mc, 0, sizeof(mc));
-        memcpy(mc.cu_edge_ver, dbf->cu_edge.ver, sizeof(mc.cu_edge_ver)); memcpy(mc.cu_edge_hor, dbf->cu_edge.hor, sizeof(mc.cu_edge_hor));
-        memcpy(mc.map0_h, ic->mv_ctx0.map.hfield, sizeof(mc.map0_h)); memcpy(mc.map0_v, ic->mv_ctx0.map.vfield, sizeof(mc.map0_v));
-        memcpy(mc.map1_h, ic->mv_ctx1.map.hfield, sizeof(mc.map1_h)); memcpy(mc.map1_v, ic->mv_ctx1.map.vfield, sizeof(mc.map1_v));
-        if (dbf->ibc_ctx) { memcpy(mc.ibc_h, dbf->ibc_ctx->ctu_map.hfield, sizeof(mc.ibc_h)); memcpy(mc.ibc_v, dbf->ibc_ctx->ctu_map.vfield, sizeof(mc.ibc_v)); }
-        memcpy(mc.dist_ref0, ic->dist_ref_0, sizeof(mc.dist_ref0)); memcpy(mc.dist_ref1, ic->dist_ref_1, sizeof(mc.dist_ref1));
-        mc.mvs0 = ic->mv_ctx0.mvs; mc.mvs1 = ic->mv_ctx1.mvs; mc.mv_bytes = sizeof(OVMV);
-        latch(e, ovhip_rec_dbf_mv_prepass_view(&s, dbf->bs1_map.ver, dbf->bs1_map.hor, &mc), "ovhip_rec_dbf_mv_prepass");
-    }
-    latch(e, ovhip_rec_dbf_row(e->rec, &s, 1), "ovhip_rec_dbf_row");
-}
-
-/* df.rcn_dbf_ctu / df.rcn_dbf_truncated_ctu (rcn_structures.h:408-413; rcn_df.c:2169-2231) */
-static void hip_rcn_dbf_ctu(const struct OVRCNCtx *const r, struct DBFInfo *const dbf, uint8_t log2_ctu_s, uint8_t last_x, uint8_t last_y)
-{ dbf_ctu(r, dbf, log2_ctu_s, last_x, last_y, 0, 0); }
-static void hip_rcn_dbf_truncated_ctu(const struct OVRCNCtx *const r, struct DBFInfo *const dbf, uint8_t log2_ctu_s, uint8_t last_x,
-                                      uint8_t last_y, uint8_t ctu_w, uint8_t ctu_h)
-{ dbf_ctu(r, dbf, log2_ctu_s, last_x, last_y, ctu_w, ctu_h); }
-
-/* ------------------------------------------------------------------------------------ SAO / ALF: parameter capture */
-static int
-params_alloc(struct hip_entry *e, const OVCTUDec *c, const struct RectEntryInfo *einfo)
-{
-    /* the arrays cover the PICTURE; a rect entry (tile) fills its own CTUs (slicedec.c:484-514: ctb_x / ctb_y = its origin) */
-    const int l2 = c->part_ctx->log2_ctu_s;
-    const int nw = (e->pic_w + (1 << l2) - 1) >> l2, nh = (e->pic_h + (1 << l2) - 1) >> l2;
-    if (einfo->ctb_x + einfo->nb_ctu_w > nw || einfo->ctb_y + einfo->nb_ctu_h > nh) {
-        latch(e, OVHIP_EINVAL, "rect entry outside the picture");
-        return -1;
-    }
-    e->log2_ctu = l2; e->nb_ctu_w = nw; e->nb_ctu_h = nh;
-    e->whole_pic_entry = !einfo->ctb_x && !einfo->ctb_y && einfo->nb_ctu_w == nw && einfo->nb_ctu_h == nh;
-    if (e->n_ctu != (size_t)nw * nh) {
-        free(e->sao); free(e->alf);
-        e->n_ctu = (size_t)nw * nh;
-        e->sao = calloc(e->n_ctu, sizeof(*e->sao)); e->alf = calloc(e->n_ctu, sizeof(*e->alf));
-        if (!e->sao || !e->alf) { latch(e, OVHIP_ENOMEM, "filter parameter arrays"); return -1; }
-    }
-    return 0;
-}
-
-/* The in-loop filters of a rect entry stop at its borders: SAO leaves the samples whose neighbour lies outside alone and ALF pads
- * (is_border from the ENTRY-local CTU index, rcn_sao.c:211-214, rcn_alf.c:1313-1318; rcn_extend_filter_region, rcn_ctu.c:361-508).
- * The device filters the whole picture at once: every CTU carries which of its sides are such borders.  A picture of one entry
- * carries none (its borders are the picture's, which the kernels know). */
-static uint8_t
-entry_borders(const struct hip_entry *e, const struct RectEntryInfo *einfo, int x, int y)
-{
-    if (e->whole_pic_entry) return 0;
-    return (uint8_t)((x == 0 ? OVHIP_BORDER_LEFT : 0) | (x == einfo->nb_ctu_w - 1 ? OVHIP_BORDER_RIGHT : 0) |
-                     (y == 0 ? OVHIP_BORDER_UPPER : 0) | (y == einfo->nb_ctu_h - 1 ? OVHIP_BORDER_BOTTOM : 0) |
-                     (einfo->nb_ctu_h == 1 ? OVHIP_BORDER_ONE_ROW : 0));
-}
-
-static void
-sao_row(struct hip_entry *e, const OVCTUDec *c, const struct RectEntryInfo *einfo, int ctb_y)
-{
-    if (ctb_y < 0 || ctb_y >= einfo->nb_ctu_h || params_alloc(e, c, einfo)) return;
-    const struct SAOInfo *si = &c->sao_info;
-    for (int x = 0; x < einfo->nb_ctu_w; ++x) {
-        const SAOParamsCtu *s = &si->sao_params[ctb_y * einfo->nb_ctu_w + x];
-        ovhip_sao_ctu *o = &e->sao[(einfo->ctb_y + ctb_y) * e->nb_ctu_w + einfo->ctb_x + x];
-        memset(o, 0, sizeof(*o));
-        o->border = entry_borders(e, einfo, x, ctb_y);
-        for (int k = 0; k < (si->chroma_format_idc ? 3 : 1); ++k) {
-            o->type[k] = s->type_idx[k]; o->band_position[k] = s->band_position[k]; o->eo_class[k] = s->eo_class[k];
-            memcpy(o->offset_val[k], s->offset_val[k], sizeof(o->offset_val[k]));
-        }
-    }
-    e->sao_on = 1;
-}
-
-/* sao.rcn_sao_filter_line / rcn_sao_first_pix_rows (rcn_structures.h:344-350; rcn_sao.c:190-293): line ctb_y filters
- * the band [128 ctb_y + 6, 128 (ctb_y + 1) + 6) with the parameters of rows ctb_y and ctb_y + 1; on the device every
- * sample takes the parameters of the CTU that contains it (same result) */
-static void
-hip_sao_filter_line(OVCTUDec *const c, const struct RectEntryInfo *const einfo, uint16_t ctb_y)
-{
-    ENTER(c);
-    if (!c->sao_info.sao_luma_flag && !c->sao_info.sao_chroma_flag) return;
-    sao_row(e, c, einfo, ctb_y);
-    sao_row(e, c, einfo, ctb_y + 1);
-}
-
-static void dmvr_rows_step(struct hip_entry *e, OVCTUDec *c, int final);
-static void band_step(struct hip_entry *e, OVCTUDec *c, const struct RectEntryInfo *einfo, int rows_parsed);
-static void final_progressive(struct hip_entry *e, OVCTUDec *c);
-
-static void
-hip_sao_first_pix_rows(OVCTUDec *const c, const struct RectEntryInfo *const einfo, uint16_t ctb_y)
-{
-    ENTER(c);
-    /* the only hook that runs at the end of row 0 (slicedec.c:934-941): the eager DMVR pass over that row starts here */
-    if (!e->record_only && einfo->nb_ctu_h > 1) dmvr_rows_step(e, c, 0);
-    if (c->sao_info.sao_luma_flag || c->sao_info.sao_chroma_flag) sao_row(e, c, einfo, ctb_y);
-    if (!e->record_only && einfo->nb_ctu_h > 1) band_step(e, c, einfo, 1);
-}
-
-static void flush_picture(struct hip_entry *e, OVCTUDec *c);
-
-/* Eager DMVR, one step per row-end hook.  decode_ctu_line reports row y - 1 after row y has been parsed (slicedec.c:934-956), and
- * every reader of the collocated motion field (TMVP of later pictures, drv_mvp.c:281-345) must find refined vectors in a reported
- * row.  So: collect the pass enqueued at the end of the row before (search + vectors + plane entries: one asynchronous D2H each, it
- * ran while this row was parsed), patch the planes, enqueue the pass over the row just parsed.  The last row, and rows no hook ran
- * after, are refined synchronously.  ovhip_frame_dmvr_rows_begin waits for the picture's references on the host the first time a
- * row holds a DMVR unit (rcn_inter_synchronization waits per block, rcn_inter.c:131-146). */
-#ifndef OVVC_HIP_CALLER_PATCH
-static void
-dmvr_rows_step(struct hip_entry *e, OVCTUDec *c, int final)
-{
-    if (!e->fr || e->err) return;
-    const size_t now = e->n_refined;
-    if (now == e->dmvr_done) { e->row_mark = now; return; }
-    PROF_DEVICE_BEGIN(e);
-    int64_t done = ovhip_frame_dmvr_rows_collect(e->fr);
-    if (done >= 0 && (size_t)done < now && (final || (size_t)done < e->row_mark)) {
-        done = ovhip_frame_dmvr_rows_begin(e->fr, e->log2_ctu);
-        if (done >= 0) done = ovhip_frame_dmvr_rows_collect(e->fr);
-    }
-    PROF_DEVICE_END(e);
-    if (done < 0) { latch(e, (int)done, "ovhip_frame_dmvr_rows"); return; }
-    if ((size_t)done > e->dmvr_done) {
-        size_t n = 0;
-        ovhip_job *job = ovhip_frame_job(e->fr);                 /* (NULL: a dry frame -- nothing computes, nothing to patch) */
-        const ovhip_tmvp_cell *cells = job ? ovhip_job_tmvp_cells(job, &n) : NULL;
-        if (job && (!cells || n < 4 * (size_t)done)) { latch(e, OVHIP_EINVAL, "the eager DMVR pass delivered no collocated-motion entries"); return; }
-        if (cells) ovhip_shim_apply_tmvp_cells(c, cells + 4 * e->dmvr_done, 4 * ((size_t)done - e->dmvr_done));
-        e->dmvr_done = (size_t)done;
-    }
-    if (!final && now > (size_t)done) {
-        PROF_DEVICE_BEGIN(e);
-        const int64_t r = ovhip_frame_dmvr_rows_begin(e->fr, e->log2_ctu);
-        PROF_DEVICE_END(e);
-        if (r < 0) latch(e, (int)r, "ovhip_frame_dmvr_rows_begin");
-    }
-    e->row_mark = now;
-}
-
-#else
-/* With the caller patch the back-end owns the CTU-row reports (rcn_report_ctu_line), so the parse does NOT stop at the first row that
- * holds a DMVR unit until every reference picture has been reconstructed: a row pass is started only when the references are complete
- * (ovhip_frame_refs_ready never waits for a decode), the reports of rows whose vectors are not final yet are queued, and every later
- * hook -- and the picture's last one, which does wait -- issues what has become final.  The parse of a picture then overlaps the
- * reconstruction of its reference pictures, as the reference's row-granular synchronisation lets it (rcn_inter.c:131-146): the frame
- * threads' critical path is no longer the SUM of the parses along the GOP's dependency chain. */
-static void
-apply_done_cells(struct hip_entry *e, OVCTUDec *c, int64_t done)
-{
-    if (done < 0) { latch(e, (int)done, "ovhip_frame_dmvr_rows"); return; }
-    if ((size_t)done <= e->dmvr_done) return;
-    size_t n = 0;
-    ovhip_job *job = ovhip_frame_job(e->fr);                 /* (NULL: a dry frame -- nothing computes, nothing to patch) */
-    const ovhip_tmvp_cell *cells = job ? ovhip_job_tmvp_cells(job, &n) : NULL;
-    if (job && (!cells || n < 4 * (size_t)done)) { latch(e, OVHIP_EINVAL, "the eager DMVR pass delivered no collocated-motion entries"); return; }
-    if (cells) ovhip_shim_apply_tmvp_cells(c, cells + 4 * e->dmvr_done, 4 * ((size_t)done - e->dmvr_done));
-    e->dmvr_done = (size_t)done;
-}
-
-static void
-issue_reports(struct hip_entry *e, int all)
-{
-    int k = 0;
-    while (k < e->n_reports && (all || e->reports[k].need <= e->dmvr_done)) {
-        ovdpb_report_decoded_ctu_line(e->reports[k].pic, e->reports[k].y, e->reports[k].x0, e->reports[k].x1);
-        ++k;
-    }
-    if (k) { memmove(e->reports, e->reports + k, (size_t)(e->n_reports - k) * sizeof(e->reports[0])); e->n_reports -= k; }
-}
-
-static int g_blocking_rows;          /* OVVC_HIP_BLOCKING_ROWS: the decoder reports its rows itself, every row hook waits (the A / B of the above) */
-
-static void
-dmvr_rows_step(struct hip_entry *e, OVCTUDec *c, int final)
-{
-    if (!e->fr) return;
-    final |= g_blocking_rows;
-    /* the report(s) that follow this hook publish the rows parsed before the PREVIOUS hook ran: their refined units */
-    e->report_need = e->row_mark;
-    const size_t now = e->n_refined;
-    if (!e->err && now != e->dmvr_done) {
-        PROF_DEVICE_BEGIN(e);
-        /* (a pass in flight began when its references were complete: this waits for device time only) */
-        int64_t done = ovhip_frame_dmvr_rows_collect(e->fr);
-        if (done >= 0 && (size_t)done < now) {
-            const int ready = final ? 1 : ovhip_frame_refs_ready(e->fr);
-            if (ready < 0) done = ready;
-            else if (ready) {
-                done = ovhip_frame_dmvr_rows_begin(e->fr, e->log2_ctu);      /* final: waits for the reference pictures here */
-                if (done >= 0) done = final ? ovhip_frame_dmvr_rows_collect(e->fr) : (int64_t)e->dmvr_done;     /* else: collected by the next hook */
-            }
-        }
-        PROF_DEVICE_END(e);
-        apply_done_cells(e, c, done);
-    }
-    e->row_mark = now;
-    issue_reports(e, e->err != 0 || final);        /* (a failed picture's rows are reported: nobody may hang on it) */
-}
-
-/* rcn_report_ctu_line (shim/caller.patch; slicedec.c:934-956, :1058-1073): the decoder's ovdpb_report_decoded_ctu_line, made when the
- * row's collocated motion vectors are final -- at once in pictures without DMVR units and whenever the device has already answered */
-static void
-hip_rcn_report_ctu_line(OVCTUDec *const c, OVPicture *const pic, int y_ctu, int xmin_ctu, int xmax_ctu)
-{
-    struct hip_entry *e = entry_of(c, 0);
-    if (!e || e->record_only || !e->fr || e->err || (!e->n_reports && e->report_need <= e->dmvr_done)
-        || e->n_reports == (int)(sizeof(e->reports) / sizeof(e->reports[0]))) {
-        if (e && e->n_reports) { dmvr_rows_step(e, c, 1); issue_reports(e, 1); }       /* (queue full: wait, as the unpatched path does) */
-        ovdpb_report_decoded_ctu_line(pic, y_ctu, xmin_ctu, xmax_ctu);
-        return;
-    }
-    e->reports[e->n_reports].pic = pic; e->reports[e->n_reports].y = y_ctu; e->reports[e->n_reports].x0 = xmin_ctu; e->reports[e->n_reports].x1 = xmax_ctu;
-    e->reports[e->n_reports].need = e->report_need;
-    e->n_reports++; e->n_reports_deferred++;
-}
-#endif
-
-/* the ALF parameters of CTU row ctb_y of the entry (parsed with the row's CTUs: valid once the row has been parsed) */
-static void
-alf_row(struct hip_entry *e, const OVCTUDec *c, const struct RectEntryInfo *einfo, int ctb_y)
-{
-    const struct ALFInfo *ai = &c->alf_info;
-    if (ctb_y < 0 || ctb_y >= einfo->nb_ctu_h || !(ai->alf_luma_enabled_flag || ai->alf_cb_enabled_flag || ai->alf_cr_enabled_flag)) return;
-    for (int x = 0; x < einfo->nb_ctu_w; ++x) {
-        const int i = ctb_y * einfo->nb_ctu_w + x;
-        const ALFParamsCtu *p = &ai->ctb_alf_params[i];
-        ovhip_alf_ctu *o = &e->alf[(einfo->ctb_y + ctb_y) * e->nb_ctu_w + einfo->ctb_x + x];
-        o->flags = p->ctb_alf_flag; o->luma_set = p->ctb_alf_idx; o->cb_alt = p->cb_alternative; o->cr_alt = p->cr_alternative;
-        o->cc_cb_idx = ai->cc_alf_cb_enabled_flag ? ai->ctb_cc_alf_filter_idx[0][i] : 0;
-        o->cc_cr_idx = ai->cc_alf_cr_enabled_flag ? ai->ctb_cc_alf_filter_idx[1][i] : 0;
-        o->border = entry_borders(e, einfo, x, ctb_y);
-    }
-    if (ai->aps_cc_alf_data_cb) memcpy(e->alf_cc[0], ai->aps_cc_alf_data_cb->alf_cc_mapped_coeff[0], sizeof(e->alf_cc[0]));
-    if (ai->aps_cc_alf_data_cr) memcpy(e->alf_cc[1], ai->aps_cc_alf_data_cr->alf_cc_mapped_coeff[1], sizeof(e->alf_cc[1]));
-    e->alf_on = 1;
-}
-
-/* alf.rcn_alf_filter_line (rcn_structures.h:333; rcn_alf.c:1285-1433): the LAST slot call before a CTU row is published
- * (slicedec.c:934-956).  Captures the row's ALF parameters, refines the DMVR vectors recorded so far (so that the row's
- * TMVP field is final), and for the last row of the picture runs the flush. */
-static void
-hip_alf_filter_line(OVCTUDec *const c, const struct RectEntryInfo *const einfo, uint16_t ctb_y)
-{
-    ENTER(c);
-    if (params_alloc(e, c, einfo)) return;
-    alf_row(e, c, einfo, ctb_y);
-    /* the entry's last row: with it the last of the picture's rect entries ends the picture (ovthreads.c:93-114: the last entry
-     * job to finish calls slicedec_finish_decoding) */
-    int last = 0;
-    if (ctb_y == einfo->nb_ctu_h - 1) {
-        e->ctus_left -= einfo->nb_ctu_w * einfo->nb_ctu_h;
-        last = e->ctus_left <= 0;
-        if (last) e->ctus_left = 0;
-    }
-    if (e->record_only) return;
-    if (last) final_progressive(e, c);
-    dmvr_rows_step(e, c, last);
-    if (last) flush_picture(e, c);
-    /* this hook runs at the end of CTU row ctb_y + 1 (decode_ctu_line, slicedec.c:934-956) -- except for the picture's last two lines,
-     * which both run at its end: the band of the second to last is left to the flush that follows at once */
-    else if (ctb_y + 2 < einfo->nb_ctu_h) band_step(e, c, einfo, ctb_y + 2);
-}
-
-/* ------------------------------------------------------------------------------------ picture begin / flush / plumbing */
-/* The device half lives in libovvc_hip.so (ovvc_dpb.c, ovvc_frame.c): a process-wide device DPB keyed by the OVFrame pointer and
- * one ovhip_frame (context + job) per OVCTUDec.  This file only maps the decoder's events onto it:
- *   rcn_attach_frame_buff            -> ovhip_frame_begin(frame)
- *   first use of a reference picture -> ovhip_frame_ref(ref->frame)          (ref_slot above)
- *   alf.rcn_alf_filter_line, per row -> ovhip_frame_dmvr_rows
- *   ... of the picture's last row    -> ovhip_frame_submit: uploads, wait for the references, launches, ovhip_job_wait, publish, output
- *   latched error                    -> ovhip_frame_fail: the picture's readers are released with an error, nobody hangs
- * Devices: OVVC_HIP_DEVICES="0,1,..." (default: OVVC_HIP_DEVICE or 0).  Frame thread k decodes on device k mod N -- pictures shard
- * one per GPU as the sub-decoders take them (ovdec_select_subdec, ovdec.c:188-248); a reference picture decoded on another device
- * arrives by an event-ordered peer copy the DPB starts as soon as it is done. */
-static ovhip_dpb *g_dpb;
-static int g_n_dev = 1, g_next_dev, g_n_entries, g_out_mode = OVHIP_OUT_PLANES, g_dpb_external;
-static ovhip_ctx *g_out_ctx[OVHIP_MAX_DEVICES];
-static pthread_mutex_t g_dpb_mtx = PTHREAD_MUTEX_INITIALIZER;
-
-static int
-dpb_get(struct hip_entry *e)
-{
-    int r = OVHIP_OK;
-    pthread_mutex_lock(&g_dpb_mtx);
-    if (!g_dpb) {
-        int devs[OVHIP_MAX_DEVICES], n = 0;
-        const char *list = getenv("OVVC_HIP_DEVICES"), *one = getenv("OVVC_HIP_DEVICE"), *om = getenv("OVVC_HIP_OUTPUT");
-        if (list) { for (const char *p = list; *p && n < OVHIP_MAX_DEVICES;) { devs[n++] = atoi(p); while (*p && *p != ',') ++p; if (*p) ++p; } }
-        if (!n) devs[n++] = one ? atoi(one) : 0;
-        /* OVVC_HIP_OUTPUT=none: the application takes its frames through ovhip_shim_frame_output / _digest and the 24.9 MB copy of
-         * every 4K picture into the OVFrame is skipped; default: the OVFrame is filled, an unmodified dectest.c:372-409 works */
-        if (om && !strcmp(om, "none")) g_out_mode = OVHIP_OUT_NONE;
-        r = ovhip_dpb_create(&g_dpb, devs, n);
-        if (r == OVHIP_OK) g_n_dev = n; else g_dpb = NULL;
-    }
-    if (r == OVHIP_OK && e->dev < 0) { e->dev = g_next_dev++ % g_n_dev; g_n_entries++; }
-    pthread_mutex_unlock(&g_dpb_mtx);
-    return r;
-}
-
-/* The application owns the device DPB (several decoders sharing one; a test back-end made with ovhip_dpb_create_ex): call before the
- * first picture.  NULL: back to the DPB the shim creates itself from OVVC_HIP_DEVICES. */
-void
-ovhip_shim_set_dpb(struct ovhip_dpb *dpb)
-{
-    pthread_mutex_lock(&g_dpb_mtx);
-    g_dpb = dpb; g_dpb_external = dpb != NULL;
-    g_n_dev = dpb ? ovhip_dpb_n_devices(dpb) : 1;
-    g_next_dev = 0;
-    pthread_mutex_unlock(&g_dpb_mtx);
-}
-
-void ovhip_shim_set_output(int mode) { g_out_mode = mode == OVHIP_OUT_NONE ? OVHIP_OUT_NONE : OVHIP_OUT_PLANES; }
-
-/* The host DPB dropped its last reference to the frame (ovframe_unref reaching zero): the device picture goes back to the pool.
- * Frees device memory earlier; not needed for correctness -- a frame pointer that comes back for a new picture recycles its slot,
- * and readers name the picture they mean by its tag (pic_tag above), so a slot that still shows the previous owner of the
- * OVFrame is waited past, never read. */
-void ovhip_shim_frame_released(const OVFrame *frame) { if (g_dpb && frame) (void)ovhip_dpb_release(g_dpb, frame); }
-
-/* Output path: what examples/dectest.c:372-409 (write_decoded_frame_to_file) copies out of the OVFrame plane by plane, taken
- * from the device picture of that frame instead -- cropped to frame->output_window and packed by one launch, fetched with
- * one D2H; or only fingerprinted (MD5 over the per-row MD5 digests computed on the device), nothing but 16 bytes leaving. */
-static ovhip_window
-frame_window(const OVFrame *f)
-{
-    ovhip_window w = { f->output_window.offset_lft, f->output_window.offset_rgt, f->output_window.offset_abv, f->output_window.offset_blw };
-    return w;
-}
-
-static ovhip_ctx *
-out_ctx_of(const OVFrame *frame, ovhip_pic *pic)
-{
-    int dev = 0;
-    if (!g_dpb || !frame || ovhip_dpb_lookup(g_dpb, frame, &dev, pic) != OVHIP_OK) return NULL;
-    pthread_mutex_lock(&g_dpb_mtx);
-    if (!g_out_ctx[dev] && ovhip_ctx_create(&g_out_ctx[dev], ovhip_dpb_device(g_dpb, dev), NULL) != OVHIP_OK) g_out_ctx[dev] = NULL;
-    ovhip_ctx *ctx = g_out_ctx[dev];
-    pthread_mutex_unlock(&g_dpb_mtx);
-    return ctx;
-}
-
-size_t
-ovhip_shim_frame_bytes(const OVFrame *frame)
-{
-    const ovhip_window w = frame_window(frame);
-    return ovhip_output_bytes(frame->width, frame->height, &w);
-}
-
-/* (one application thread at a time per device: the output contexts are not locked) */
-int
-ovhip_shim_frame_output(const OVCTUDec *c, const OVFrame *frame, void *dst)
-{
-    (void)c;
-    ovhip_pic pic;
-    ovhip_ctx *ctx = dst ? out_ctx_of(frame, &pic) : NULL;
-    if (!ctx) return OVHIP_EINVAL;
-    const ovhip_window w = frame_window(frame);
-    return ovhip_pic_output(ctx, &pic, &w, dst);
-}
-
-int
-ovhip_shim_frame_digest(const OVCTUDec *c, const OVFrame *frame, uint8_t out[16])
-{
-    (void)c;
-    ovhip_pic pic;
-    ovhip_ctx *ctx = out ? out_ctx_of(frame, &pic) : NULL;
-    if (!ctx) return OVHIP_EINVAL;
-    const ovhip_window w = frame_window(frame);
-    return ovhip_pic_digest(ctx, &pic, &w, out);
-}
-
-/* The same at ONE output size, for a stream that changes its coded size: what pp_process_frame (post_proc.c:116-126, called at
- * ovdec.c:479 / :523 when the decoder's `upscale` option is on) does on the host with pp_sample_rate_conv, on the device picture instead.
- * scale_info = the picture's own (pic->scale_info), out_w x out_h = the frame pool's size.  The whole resampled frame is delivered: the
- * frame's output_window describes the coded picture, and the reference's post-processed frame does not carry it over (post_proc.c:89-129). */
-static ovhip_scale_info
-scale_info_of(const struct ScalingInfo *si)
-{
-    ovhip_scale_info o;
-    memset(&o, 0, sizeof(o));
-    if (si) {
-        o.win_left = si->scaling_win_left; o.win_right = si->scaling_win_right;
-        o.win_top = si->scaling_win_top; o.win_bottom = si->scaling_win_bottom;
-        o.chroma_hor_col = si->chroma_hor_col_flag; o.chroma_ver_col = si->chroma_ver_col_flag;
-    }
-    return o;
-}
-
-size_t
-ovhip_shim_frame_bytes_scaled(const OVFrame *frame, int out_w, int out_h)
-{
-    (void)frame;
-    return ovhip_output_bytes(out_w, out_h, NULL);
-}
-
-int
-ovhip_shim_frame_output_scaled(const OVCTUDec *c, const OVFrame *frame, const struct ScalingInfo *scale_info, int out_w, int out_h, void *dst)
-{
-    (void)c;
-    ovhip_pic pic;
-    ovhip_ctx *ctx = dst ? out_ctx_of(frame, &pic) : NULL;
-    if (!ctx) return OVHIP_EINVAL;
-    const ovhip_scale_info si = scale_info_of(scale_info);
-    return ovhip_pic_output_scaled(ctx, &pic, &si, out_w, out_h, NULL, dst);
-}
-
-int
-ovhip_shim_frame_digest_scaled(const OVCTUDec *c, const OVFrame *frame, const struct ScalingInfo *scale_info, int out_w, int out_h, uint8_t out[16])
-{
-    (void)c;
-    ovhip_pic pic;
-    ovhip_ctx *ctx = out ? out_ctx_of(frame, &pic) : NULL;
-    if (!ctx) return OVHIP_EINVAL;
-    const ovhip_scale_info si = scale_info_of(scale_info);
-    return ovhip_pic_digest_scaled(ctx, &pic, &si, out_w, out_h, NULL, out);
-}
-
-/* picture-level side information of the flush / of a band.  by_flags: the filters are on when the slice says so (a band is submitted
- * before every row's hooks have run; the parameter arrays hold what the hooks have delivered, which is what the band's filters reach) */
-static void
-picture_params(struct hip_entry *e, OVCTUDec *c, ovhip_job_params *pr, int by_flags)
-{
-    memset(pr, 0, sizeof(*pr));
-    pr->lmcs = (c->lmcs_info.lmcs_enabled_flag && e->have_luts) ? &e->luts : NULL;
-    const struct ALFInfo *ai = &c->alf_info;
-    const int sao_on = by_flags ? (c->sao_info.sao_luma_flag || c->sao_info.sao_chroma_flag) && e->sao : e->sao_on;
-    const int alf_on = by_flags ? (ai->alf_luma_enabled_flag || ai->alf_cb_enabled_flag || ai->alf_cr_enabled_flag) && e->alf : e->alf_on;
-    pr->sao = sao_on ? e->sao : NULL;
-    if (alf_on) {
-        const RCNALF *ra = &c->alf_info.rcn_alf;
-        if (by_flags) {
-            if (ai->aps_cc_alf_data_cb) memcpy(e->alf_cc[0], ai->aps_cc_alf_data_cb->alf_cc_mapped_coeff[0], sizeof(e->alf_cc[0]));
-            if (ai->aps_cc_alf_data_cr) memcpy(e->alf_cc[1], ai->aps_cc_alf_data_cr->alf_cc_mapped_coeff[1], sizeof(e->alf_cc[1]));
-        }
-        pr->alf_ctus = e->alf;
-        pr->alf_luma_coeff = &ra->filter_coeff_dec[0][0]; pr->alf_luma_clip = &ra->filter_clip_dec[0][0];
-        pr->alf_chroma_coeff = &ra->chroma_coeff_final[0][0]; pr->alf_chroma_clip = &ra->chroma_clip_final[0][0];
-        pr->alf_cc_coeff = &e->alf_cc[0][0][0];
-    }
-    pr->log2_ctu_s = e->log2_ctu;
-}
-
-/* Band-wise submission (ovhip_frame_band; OVVC_HIP_BANDS = CTU rows per band; 0 = off, the DEFAULT: measured on the live decoder at 4K
- * -- DESIGN 12 -- whole-picture submission is faster at every band size: a band is ~13 launches, a picture of 17 bands ~220 instead of
- * 11, and the host side of a launch is what a frame thread's device half consists of): at the end of every g_band_rows-th CTU row
- * what has been recorded since the last band goes to the device -- upload, prediction, residuals, ordered pass at once; the filters one
- * band late -- while the parse goes on; the rows the band's filters made final are posted to the device DPB, where the frame threads
- * that reference this picture see them (slicedec.c:815-975 + dpb.c:1309-1323 do this per CTU row on the host).  A band whose
- * reference rows are not there yet is left to the next hook; only the picture's end waits. */
-static int g_band_rows = 0, g_band_rows_set, g_band_intra = 1, g_band_inter = 1;
-/* CTU rows per band; 0: every picture is submitted at its end (ovhip_frame_submit).  Overrides OVVC_HIP_BANDS. */
-void ovhip_shim_set_bands(int ctu_rows_per_band) { g_band_rows = ctu_rows_per_band < 0 ? 0 : ctu_rows_per_band; g_band_rows_set = 1; }
-void
-ovhip_shim_band_stats(const OVCTUDec *c, uint32_t *sent, uint32_t *deferred)
-{
-    struct hip_entry *e = entry_of(c, 0);
-    if (sent) *sent = e ? e->n_bands_sent : 0;
-    if (deferred) *deferred = e ? e->n_bands_deferred : 0;
-}
-
-static void
-band_step(struct hip_entry *e, OVCTUDec *c, const struct RectEntryInfo *einfo, int rows_parsed)
-{
-    if (!e->band_on || !e->fr || e->err || g_band_rows <= 0) return;
-    if (rows_parsed >= 1 && rows_parsed <= MAX_MARKS && e->n_marks == rows_parsed - 1) {
-        ovhip_rec_counts(e->rec, &e->marks[rows_parsed - 1].counts);
-        e->marks[rows_parsed - 1].n_refined = e->n_refined;
-        e->n_marks = rows_parsed;
-    }
-    if (rows_parsed % g_band_rows) return;
-    /* the band's filters reach into the row just parsed: its ALF parameters (the row's own hook runs a row later, slicedec.c:934-956)
-     * and, for row 0, the SAO parameters are there -- parsed with the row's CTUs */
-    if (params_alloc(e, c, einfo)) return;
-    for (int y = rows_parsed - g_band_rows; y < rows_parsed; ++y) alf_row(e, c, einfo, y);
-    if (c->sao_info.sao_luma_flag || c->sao_info.sao_chroma_flag) sao_row(e, c, einfo, rows_parsed - 1);
-    ovhip_job_params pr;
-    picture_params(e, c, &pr, 1);
-    PROF_DEVICE_BEGIN(e);
-    const int r = ovhip_frame_band(e->fr, &pr, rows_parsed << e->log2_ctu, 0, NULL);
-    PROF_DEVICE_END(e);
-    if (r < 0) latch(e, r, "ovhip_frame_band");
-    else if (r) { e->n_bands_sent++; e->rows_sent = rows_parsed; } else e->n_bands_deferred++;
-}
-
-#ifdef OVVC_HIP_CALLER_PATCH
-static void apply_done_cells(struct hip_entry *e, OVCTUDec *c, int64_t done);
-static void issue_reports(struct hip_entry *e, int all);
-/* The picture's last hook, when its parse ran AHEAD of its reference pictures (with the caller patch the parse never waits for a
- * reference: the rows' reports were queued, their bands left to later hooks).  Instead of waiting for the reference pictures to be
- * complete and then doing everything at once, the rows are worked through in order as the references' rows arrive (ovhip_dpb_rows_tag
- * blocks per row): the DMVR vectors of the row's units, the row's report (its readers' parse goes on), the row's band (its readers'
- * bands go on) -- so that a chain of pictures that each trail their references by a few rows stays a chain of a few rows per link,
- * whatever the parse speeds (rcn_inter.c:131-146 + dpb.c:1309-1323 give the reference's frame threads the same behaviour). */
-static void
-final_progressive(struct hip_entry *e, OVCTUDec *c)
-{
-    if (!e->band_on || !e->fr || e->err || !e->n_refs) return;
-    ovhip_job_params pr;
-    picture_params(e, c, &pr, 1);
-    PROF_DEVICE_BEGIN(e);
-    for (int y = e->rows_sent; y < e->n_marks && !e->err; ++y) {
-        const size_t units = e->marks[y].n_refined;
-        if (units > e->dmvr_done) {
-            int64_t done = ovhip_frame_dmvr_rows_collect(e->fr);
-            if (done >= 0 && (size_t)done < units) {
-                done = ovhip_frame_dmvr_rows_begin_upto(e->fr, e->log2_ctu, units);        /* waits for the rows these units read */
-                if (done >= 0) done = ovhip_frame_dmvr_rows_collect(e->fr);
-            }
-            apply_done_cells(e, c, done);
-        }
-        issue_reports(e, 0);
-        if ((y + 1) % g_band_rows == 0 && !e->err) {
-            const int r = ovhip_frame_band_upto(e->fr, &pr, (y + 1) << e->log2_ctu, &e->marks[y].counts, 1);
-            if (r < 0) latch(e, r, "ovhip_frame_band_upto");
-            else { e->n_bands_sent++; e->rows_sent = y + 1; }
-        }
-    }
-    PROF_DEVICE_END(e);
-}
-#else
-static void final_progressive(struct hip_entry *e, OVCTUDec *c) { (void)e; (void)c; }
-#endif
-
-static void
-flush_picture(struct hip_entry *e, OVCTUDec *c)
-{
-    if (!e->fr) return;
-    if (e->err) {
-        /*  every exit path publishes: a picture that cannot be decoded releases its readers with an error */
-        (void)ovhip_frame_fail(e->fr, e->err);
-        return;
-    }
-    ovhip_job_params pr;
-    picture_params(e, c, &pr, e->band_on);
-    /* the decoder's own output path and any host-side reader expect the samples in the OVFrame (dectest.c:372-409): copied out
-     * AFTER ovhip_job_wait (which may decode the picture a second time) and after the picture was published to its readers */
-    ovhip_frame_output out;
-    memset(&out, 0, sizeof(out));
-    const OVFrame *f = e->frame;
-    out.mode = g_out_mode;
-    out.y = (uint16_t *)f->data[0]; out.cb = (uint16_t *)f->data[1]; out.cr = (uint16_t *)f->data[2];
-    out.stride_y = (int32_t)(f->linesize[0] / 2); out.stride_c = (int32_t)(f->linesize[1] / 2);
-    /* (every refined vector is in the TMVP planes already: dmvr_rows_step(final) ran in the hook that called this) */
-    PROF_DEVICE_BEGIN(e);
-    if (e->band_on) { const int r = ovhip_frame_band(e->fr, &pr, e->pic_h, 1, &out); latch(e, r < 0 ? r : OVHIP_OK, "ovhip_frame_band (last)"); e->n_bands_sent++; }
-    else latch(e, ovhip_frame_submit(e->fr, NULL, NULL, &pr, &out), "ovhip_frame_submit");
-    PROF_DEVICE_END(e);
-}
-
-static void
-begin_picture(struct hip_entry *e, const OVFrame *f, const struct RectEntryInfo *einfo)
-{
-    /* One device job = one picture.  A picture cut into rect entries (tiles; slicedec.c:636-657) attaches the frame once per entry:
-     * the entries that follow the first on the SAME OVCTUDec (one entry thread: slicedec.c:649-653 runs them in turn) go on recording
-     * into the picture's job, and the last one to end submits it (hip_alf_filter_line).  Entries of one picture on SEVERAL OVCTUDecs
-     * (`-e 2`, ovthreads.c:93-114) would need their recorders merged: refused, the picture fails loudly. */
-    int nw = 0, nh = 0, first = 1;
-    e->whole_pic_entry = 1;
-    if (einfo && e->key->part_ctx) {
-        const int l2 = e->key->part_ctx->log2_ctu_s;
-        const int pw = e->record_only ? e->pic_w : (int)f->width, ph = e->record_only ? e->pic_h : (int)f->height;
-        nw = (pw + (1 << l2) - 1) >> l2; nh = (ph + (1 << l2) - 1) >> l2;
-        first = !einfo->ctb_x && !einfo->ctb_y;
-        e->whole_pic_entry = first && einfo->nb_ctu_w == nw && einfo->nb_ctu_h == nh;
-    }
-    if (!first) {
-        if (e->frame != f || e->ctus_left <= 0 || !e->rec) {
-            latch(e, OVHIP_EUNSUP, "rect entry of a picture whose first entry this OVCTUDec did not decode (entry threads > 1)");
-            if (!e->record_only && e->fr) { ovhip_frame_destroy(e->fr); e->fr = NULL; e->rec = NULL; }
-            return;
-        }
-        e->lmcs_region_live = 0;
-        e->pend.kind = PEND_NONE; e->aff_c_live = 0; e->ciip.live = 0;
-        return;
-    }
-    e->frame = f;
-    /* the CTU size is needed by the first row-end hook already (dmvr_rows_step -> the plane entries of the row's refined units): found by
-     * the live decode on several frame threads -- a frame thread whose FIRST picture had DMVR units in CTU row 0 asked for the entries
-     * with log2_ctu_s == 0, got none, and left that row's collocated motion vectors unrefined (params_alloc used to be the only writer) */
-    if (e->key->part_ctx) e->log2_ctu = e->key->part_ctx->log2_ctu_s;
-    e->ctus_left = nw * nh;
-    e->err = 0;
-    e->n_refs = 0;
-    e->scale_set = 0;
-    e->sao_on = e->alf_on = 0;
-    e->lmcs_region_live = 0;
-    e->n_refined = 0; e->dmvr_done = 0; e->row_mark = 0;
-#ifdef OVVC_HIP_CALLER_PATCH
-    if (e->n_reports) issue_reports(e, 1);             /* (a picture that never reached its last row: its readers must not hang) */
-    e->report_need = 0;
-#endif
-    e->pend.kind = PEND_NONE; e->aff_c_live = 0; e->ciip.live = 0;
-    if (e->rec && e->key->part_ctx) (void)ovhip_rec_set_ctu_size(e->rec, e->key->part_ctx->log2_ctu_s);
-    if (e->n_ctu) { memset(e->sao, 0, e->n_ctu * sizeof(*e->sao)); memset(e->alf, 0, e->n_ctu * sizeof(*e->alf)); }
-    if (e->record_only) { ovhip_rec_reset(e->rec); return; }
-    PROF_DEVICE_BEGIN(e);
-    int r = dpb_get(e);
-    if (r != OVHIP_OK) { latch(e, r, "ovhip_dpb_create (the HIP back-end has no CPU fallback)"); return; }
-    if (e->fr && (e->pic_w != (int)f->width || e->pic_h != (int)f->height)) { ovhip_frame_destroy(e->fr); e->fr = NULL; e->rec = NULL; }
-    e->pic_w = f->width; e->pic_h = f->height;
-    if (!e->fr) {
-        r = ovhip_frame_create(g_dpb, e->dev, e->pic_w, e->pic_h, &e->fr);
-        if (r != OVHIP_OK) { e->fr = NULL; latch(e, r, "ovhip_frame_create"); return; }
-    }
-    /* the OVPicture being decoded: tmvp_entry_init (slicedec.c:1085-1099, called before rcn_attach_frame_buff) left pointers to its
-     * motion planes in the CTU decoder -- the table's prototypes never hand the picture itself over */
-    const struct MVPlane *pl0 = e->key->drv_ctx.inter_ctx.tmvp_ctx.plane0;
-    const OVPicture *cur = pl0 ? (const OVPicture *)((const char *)pl0 - offsetof(OVPicture, mv_plane0)) : NULL;
-    latch(e, ovhip_frame_begin_tag(e->fr, f, cur && cur->frame == f ? pic_tag(cur) : 0), "ovhip_frame_begin");
-    e->rec = ovhip_frame_recorder(e->fr);
-    /* band by band: pictures of one rect entry.  (An I picture's ordered pass is one dependency chain per band, so its bands follow each
-     * other on the device; ovhip_frame_band leaves a band to the next hook while the one before is still being reconstructed, so the
-     * bands of a picture that is parsed faster than the device decodes it grow until the wavefront spans the rows again.)
-     * OVVC_HIP_BANDS_INTRA=0: I pictures whole. */
-    e->band_on = g_band_rows > 0 && e->whole_pic_entry && (e->key->tmp_slice_type == 2 ? g_band_intra : g_band_inter);
-    e->n_marks = 0; e->rows_sent = 0;
-    (void)ovhip_frame_set_band_mode(e->fr, e->band_on);
-    PROF_DEVICE_END(e);
-    if (!e->rec) { latch(e, OVHIP_ENOMEM, "ovhip_frame_recorder"); return; }
-    (void)ovhip_rec_set_ctu_size(e->rec, e->key->part_ctx ? e->key->part_ctx->log2_ctu_s : 7);
-    /* this caller submits through the picture job, which launches every array the recorder fills: affine CUs and lone 4x4 luma
-     * blocks on scaled references are recorded instead of refused */
-    (void)ovhip_rec_set_rpr_tools(e->rec, OVHIP_RPR_TOOL_AFFINE | OVHIP_RPR_TOOL_PU4x4);
-    /* the slice's reference lists are known now (slicedec.c:1250-1256): a device that did not decode them asks for them before
-     * the first prediction unit is parsed */
-    const struct InterDRVCtx *ic = &e->key->drv_ctx.inter_ctx;
-    if (g_n_dev > 1 && e->key->tmp_slice_type != 2) {
-        for (int i = 0; i < ic->nb_active_ref0 && i < 16; ++i) if (ic->rpl0[i] && ic->rpl0[i]->frame) (void)ovhip_dpb_want_tag(g_dpb, ic->rpl0[i]->frame, pic_tag(ic->rpl0[i]), e->dev);
-        for (int i = 0; i < ic->nb_active_ref1 && i < 16; ++i) if (ic->rpl1[i] && ic->rpl1[i]->frame) (void)ovhip_dpb_want_tag(g_dpb, ic->rpl1[i]->frame, pic_tag(ic->rpl1[i]), e->dev);
-    }
-}
-
+/* ------------------------------------------------------------------------------------ the picture's frame buffer */
 /* rcn_attach_frame_buff (rcn_structures.h:622-623; rcn_ctu.c:570-594) = begin picture for this entry thread */
 static void
 hip_attach_frame_buff(struct OVRCNCtx *const rcn_ctx, const OVFrame *const f, const struct RectEntryInfo *const einfo, uint8_t log2_ctb_s)
@@ -1847,41 +135,9 @@ rcn_init_functions_hip(struct RCNFunctions *f, uint8_t ict_type, uint8_t lm_chro
     e->scalar = *f;
     e->ict_type = ict_type; e->lmcs_flag = lmcs_flag;
 
-    f->tmp.rcn_transform_tree = &hip_rcn_transform_tree;
-    f->tmp.rcn_tu_st = &hip_rcn_tu_st;
-    f->tmp.rcn_tu_c  = &hip_rcn_tu_c;
-    f->tmp.recon_isp_subtree_h = &hip_recon_isp_subtree_h;
-    f->tmp.recon_isp_subtree_v = &hip_recon_isp_subtree_v;
-    f->rcn_ibc_l = &hip_rcn_ibc;
-    f->rcn_ibc_c = &hip_rcn_ibc;
-    f->rcn_mcp = &hip_rcn_mcp;
-    f->rcn_mcp_b = &hip_rcn_mcp_b;
-    f->rcn_mcp_b_l = &hip_rcn_mcp_b_l;
-    f->rcn_mcp_b_c = &hip_rcn_mcp_b_c;
-    f->rcn_prof_mcp_b_l = &hip_rcn_prof_mcp_b_l;
-    f->rcn_bdof_mcp_l = &hip_rcn_bdof_mcp_l;
-    f->rcn_dmvr_mv_refine = &hip_rcn_dmvr_mv_refine;
-    if (!g_band_rows_set && getenv("OVVC_HIP_BANDS")) g_band_rows = atoi(getenv("OVVC_HIP_BANDS"));
-    if (getenv("OVVC_HIP_BANDS_INTRA")) g_band_intra = atoi(getenv("OVVC_HIP_BANDS_INTRA"));
-    if (getenv("OVVC_HIP_BANDS_INTER")) g_band_inter = atoi(getenv("OVVC_HIP_BANDS_INTER"));
-#ifdef OVVC_HIP_CALLER_PATCH
-    f->rcn_cu_inter_b = &hip_rcn_cu_inter_b;
-    f->rcn_affine_cu = &hip_rcn_affine_cu;
-    g_blocking_rows = getenv("OVVC_HIP_BLOCKING_ROWS") != NULL;
-    f->rcn_report_ctu_line = g_blocking_rows ? NULL : &hip_rcn_report_ctu_line;      /* (NULL: the decoder reports by itself, the row hooks wait) */
-#endif
-    f->rcn_gpm_b = &hip_rcn_gpm_b;
-    f->rcn_ciip_b = &hip_rcn_ciip_b;
-    f->rcn_ciip = &hip_rcn_ciip;
-    f->rcn_init_lmcs = &hip_rcn_init_lmcs;
-    f->rcn_lmcs_compute_chroma_scale = &hip_lmcs_chroma_scale;
-    f->lmcs_reshape_backward = &hip_noop_reshape;
-    f->df.rcn_dbf_ctu = &hip_rcn_dbf_ctu;
-    f->df.rcn_dbf_truncated_ctu = &hip_rcn_dbf_truncated_ctu;
-    f->sao.rcn_sao_filter_line = &hip_sao_filter_line;
-    f->sao.rcn_sao_first_pix_rows = &hip_sao_first_pix_rows;
-    f->alf.rcn_alf_filter_line = &hip_alf_filter_line;
-    /* alf.rcn_alf_reconstruct_coeff_APS stays scalar: host-side expansion of the APS into RCNALF, read by the flush */
+    rec_install(f);
+    mode_install(f);
+    pic_knobs();
     f->rcn_attach_frame_buff = &hip_attach_frame_buff;
     f->rcn_write_ctu_to_frame = &hip_noop_rcn_u8;
     f->rcn_write_ctu_to_frame_border = &hip_noop_write_border;
@@ -1895,6 +151,9 @@ rcn_init_functions_hip(struct RCNFunctions *f, uint8_t ict_type, uint8_t lm_chro
 }
 
 /* ------------------------------------------------------------------------------------ management */
+int g_prof_on;
+static uint64_t g_prof_tick0; static double g_prof_s0;
+static double prof_now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 static double g_prof_call_ticks;          /* what one bracketed (outermost) hook call adds: measured when the profile is switched on */
 
 void
@@ -2006,15 +265,7 @@ ovhip_shim_release(const OVCTUDec *c)
     __atomic_add_fetch(&g_entries_gen, 1, __ATOMIC_RELEASE);        /* every thread's cached entry pointer is void now */
     pthread_mutex_unlock(&g_mtx);
     if (!e) return;
-    if (e->fr) ovhip_frame_destroy(e->fr);
+    pic_release(e);
     free(e->sao); free(e->alf);
-    /* the last frame thread of the process takes the device DPB (every device picture) with it */
-    pthread_mutex_lock(&g_dpb_mtx);
-    if (e->dev >= 0 && --g_n_entries == 0 && g_dpb && !g_dpb_external) {
-        for (int k = 0; k < OVHIP_MAX_DEVICES; ++k) if (g_out_ctx[k]) { ovhip_ctx_destroy(g_out_ctx[k]); g_out_ctx[k] = NULL; }
-        ovhip_dpb_destroy(g_dpb);
-        g_dpb = NULL; g_next_dev = 0;
-    }
-    pthread_mutex_unlock(&g_dpb_mtx);
     free(e);
 }

@@ -1,9 +1,11 @@
 /* rcn_hip.h -- the MI355X back-end's override block for OpenVVC's reconstruction dispatch table.
  *
- * This is the file a maintainer adds to the reference tree: it is compiled WITH the reference's own
- * headers (ctudec.h, rcn_structures.h, ...) and linked against libovvc_hip.so.  It replaces the orchestrator slots of
- * struct RCNFunctions (libovvc/rcn_structures.h:499-694) -- the same boundary the SSE4/AVX2/NEON back-ends bind to
- * (rcn.c:214-299) -- with recorders, and the last alf.rcn_alf_filter_line of a picture with the device flush.
+ * The public header of what a maintainer adds to the reference tree: rcn_hip.c, rcn_hip_rec.c, rcn_hip_pic.c and
+ * ONE caller-mode unit -- rcn_hip_sub.c for the reference as it is, rcn_hip_cu.c for a tree with shim/caller.patch applied -- which
+ * share rcn_hip_priv.h, are compiled WITH the reference's own headers (ctudec.h, rcn_structures.h, ...) and linked against
+ * libovvc_hip.so.  The block replaces the orchestrator slots of struct RCNFunctions (libovvc/rcn_structures.h:499-694) -- the same
+ * boundary the SSE4/AVX2/NEON back-ends bind to (rcn.c:214-299) -- with recorders, and the last alf.rcn_alf_filter_line of a picture
+ * with the device flush.  The library exports exactly what is declared here.
  */
 #ifndef OVVC_RCN_HIP_H
 #define OVVC_RCN_HIP_H
@@ -34,6 +36,8 @@ int  ovhip_shim_ref_pictures(const struct OVCTUDec *ctudec, const void **out, in
 /* Close the prediction calls still being collected into one CU (affine sub-blocks, BDOF blocks): done implicitly by
  * every other slot, needed explicitly only before reading the recorder directly. */
 void ovhip_shim_flush_pending(struct OVCTUDec *ctudec);
+/* Record-only harness: forget the refined-unit bookkeeping of the case before (the decoder's picture begin does it otherwise). */
+void ovhip_shim_new_picture_for_test(struct OVCTUDec *ctudec);
 /* First error latched since the picture began (0 = none; negative OVHIP_E*): the slots return void. */
 int  ovhip_shim_last_error(const struct OVCTUDec *ctudec);
 /* Entries of the picture's collocated motion planes (ovhip_job_tmvp_cells(): 4 per refined unit, derived on the device from the

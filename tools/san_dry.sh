@@ -1,5 +1,5 @@
 #!/bin/bash
-# Sanitizers over the host C code that runs under the reference's slice decoder -- the shim (shim/rcn_hip.c), the device DPB, the frame
+# Sanitizers over the host C code that runs under the reference's slice decoder -- the shim (shim/rcn_hip*.c), the device DPB, the frame
 # layer, the stream driver, the recorder -- and over the harness itself, driven on DRY frames (no GPU: the HIP half is the same object
 # code, its device calls are not reached).  Build container only (needs /root/reference and oracle/_ref).
 #   tools/san_dry.sh thread        8 frame threads, 33 pictures, twice on warm threads      -> "sanitizer reports: 0"
@@ -19,7 +19,7 @@ for f in ovvc_record ovvc_record_inter ovvc_record_dbf ovvc_record_intra ovvc_lm
 done
 HIPOBJS=$(ls $C/build/*.o | grep -v -E "/ovvc_(record|record_inter|record_dbf|record_intra|lmcs|md5|calllog|dpb|frame|stream)\.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=$SAN -o libovvc_hip.so $HIPOBJS *.o -lpthread -ldl 2>&1 | grep -v "not currently supported" || true
-gcc -O1 -g -w -fPIC -shared -fsanitize=$SAN -pthread -I$REF -I$R/include -I$R/shim -DBITDEPTH=10 -o librcn_hip.so $R/shim/rcn_hip.c -L. -lovvc_hip -Wl,--allow-shlib-undefined
+make -s -C $R/shim INC=$REF OUT=$T/librcn_hip.so LIB=$T OPT="-O1 -g -w -fsanitize=$SAN"          # (the shim's sources and flags: shim/Makefile)
 gcc -O1 -g -w -fPIC -shared -fsanitize=$SAN -I$REF -I$R/include -I$R/shim -DBITDEPTH=10 -o libgenpipe.so $R/oracle/ref_harness/gen_pipe.c \
     -L$R/oracle/_ref -lovvcref -L. -lrcn_hip -lovvc_hip -Wl,-z,lazy -lm -lpthread
 gcc -O1 -fsanitize=$SAN -o gen_pipe $R/oracle/ref_harness/gen_pipe_main.c -L. -lgenpipe -Wl,--allow-shlib-undefined -Wl,-z,lazy
