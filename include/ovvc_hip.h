@@ -482,7 +482,10 @@ typedef struct ovhip_alf_pic {
 enum { OVHIP_IT_LUMA = 0,     /* luma block                                                                          */
        OVHIP_IT_CHROMA = 1,   /* Cb + Cr block (x, y, size in chroma samples)                                        */
        OVHIP_IT_REGION = 2,   /* rcn_lmcs_compute_chroma_scale of region c_scale (needs ordered luma around it)      */
-       OVHIP_IT_RES_C = 3 };  /* chroma residual add of an already predicted block whose scale is an ordered region's */
+       OVHIP_IT_RES_C = 3,    /* chroma residual add of an already predicted block whose scale is an ordered region's */
+       OVHIP_IT_IBC_L = 4,    /* intra block copy, luma block: the block at (x + pad[0], y + pad[1]) of this picture, before */
+       OVHIP_IT_IBC_C = 5 };  /* any loop filter (+ residual); Cb + Cr block likewise, offsets in chroma samples.  Produced */
+                              /* by ovhip_rec_tu_ibc only (rcn_ibc_l / rcn_ibc_c, rcn_ibc.c:8-139)                        */
 enum {                        /* ovhip_itask.flags */
     OVHIP_IF_CORNER = 1,      /* the above-left neighbour unit is available                                          */
     OVHIP_IF_MIP = 2,         /* matrix-based intra prediction, mode = mip mode; OVHIP_IF_MIP_TR: transposed          */
@@ -492,6 +495,8 @@ enum {                        /* ovhip_itask.flags */
     OVHIP_IF_RES_Y = 32, OVHIP_IF_RES_CB = 64, OVHIP_IF_RES_CR = 128,   /* a STOREd residual exists for that plane    */
     OVHIP_IF_RES_SCALE = 256, /* chroma residual is LMCS-scaled with c_scale ...                                     */
     OVHIP_IF_SCALE_IDX = 512, /* ... which is the index of a chroma-scale region                                      */
+    OVHIP_IF_IBC_FREE = 4096, /* OVHIP_IT_IBC_*: no unit of the source block is written by an ordered task (its level is 1): the
+                               * item waits for nothing                                                                   */
     OVHIP_IF_CORNER_L = 2048, /* ISP only: the corner unit as the LEFT arm's progress map sees it (OVHIP_IF_CORNER: as the above
                                * arm's map sees it; for every other task the two coincide)                                */
     OVHIP_IF_ISP = 1024       /* a prediction call of an intra-sub-partition CU (intra_pred_isp, rcn_intra.c:566-640): the
@@ -524,8 +529,12 @@ typedef struct ovhip_itask {
     uint8_t  isp_log2_pb;     /* OVHIP_IF_ISP: width of one partition inside this block (vertical partitions narrower than 4 are
                                * predicted 4 columns at a time) and ...                                                  */
     uint8_t  isp_res_mask;    /* ... which of them carry a residual (bit = x >> isp_log2_pb); the others add nothing        */
-    uint16_t pad[3];
+    uint16_t pad[3];          /* OVHIP_IT_IBC_*: pad[0], pad[1] = (int16_t) offset from the block to its source, in samples of the
+                               * task's plane (chroma: the luma vector >> 1, arithmetic: the floor the reference takes, CU
+                               * positions being even); else 0                                                            */
 } ovhip_itask;
+#define OVHIP_ITASK_IBC_DX(t) ((int)(int16_t)(t).pad[0])
+#define OVHIP_ITASK_IBC_DY(t) ((int)(int16_t)(t).pad[1])
 
 /* ------------------------------------------------------------------------------------
  * Recorder (host side, pure C, usable without a GPU).
@@ -657,6 +666,41 @@ int   ovhip_rec_tu(ovhip_recorder *rec, const ovhip_tu_state *st, const ovhip_tu
  * Returns the number of transform-block commands appended or <0. */
 int   ovhip_rec_tu_intra(ovhip_recorder *rec, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *intra_l,
                          const ovhip_itask *intra_c);
+/* Intra block copy.  One IBC coding unit as rcn_ibc_l / rcn_ibc_c receive it (the last two slots of struct RCNFunctions,
+ * rcn_structures.h; rcn_ibc.c:8-139; callers vcl_coding_unit.c:1032-1066, :1088-1133, :1155-1205, :1257-1311): position and size in luma samples of
+ * the picture, the block vector in whole luma samples (IBCMV), the CTU size the reference's ring ctu_buff is laid out for and
+ * the left edge of the rect entry / tile the CU lies in.  The reference copies out of a per-CTU-row ring of
+ * (256 * 128) >> log2_ctu luma columns (rcn_ctu.c:554-568); the device reads the PICTURE at (x0 + mv_x, y0 + mv_y), which is the
+ * same sample exactly when (ovhip_rec_ibc_check)
+ *   - the source lies in the CU's CTU row and inside the picture,
+ *   - its left edge is not left of win_x0 nor of the ring's oldest CTU ((x0 >> log2_ctu) - (ring CTUs - 1)),
+ *   - its right edge is not right of the CU's CTU,
+ *   - it does not intersect the CU,
+ *   - it is decoded already (the caller's guarantee: the recorder cannot know).
+ * H.266 forbids every other vector; for those the reference reads stale ring content and no parity is claimed. */
+typedef struct ovhip_ibc_desc {
+    uint16_t x0, y0;          /* luma position of the CU in the picture                                                */
+    uint8_t  log2_w, log2_h;  /* CU size in luma samples                                                                */
+    uint8_t  log2_ctu;        /* 5..7                                                                                  */
+    uint8_t  has_chroma;      /* rcn_ibc_c follows rcn_ibc_l (single tree and not `share`); 0: luma only                */
+    int16_t  mv_x, mv_y;      /* IBCMV, whole luma samples                                                             */
+    uint16_t win_x0;          /* left edge (luma samples) of the rect entry / tile                                     */
+    uint16_t pad;
+} ovhip_ibc_desc;
+/* 0 when the picture holds the sample the reference's ring would deliver for every sample of the CU's source block, else
+ * OVHIP_EUNSUP with the violated rule in ovhip_rec_refusal.  Records nothing. */
+int   ovhip_rec_ibc_check(ovhip_recorder *rec, const ovhip_ibc_desc *cu);
+/* A TU of an IBC CU, shaped like ovhip_rec_tu_intra: what rcn_ibc_l (+ rcn_ibc_c) followed by tmp.rcn_transform_tree do to the
+ * TU's blocks.  tu lies inside cu (tree 0: luma + chroma when cu->has_chroma, tree 1: luma only); cu_flags carries flg_ibc_flag and
+ * no flg_pred_mode_flag (vcl_transform_unit.c:1826-1959: the inter branch, no LFNST, no SBT).  One OVHIP_IT_IBC_L task per luma
+ * block and one OVHIP_IT_IBC_C task per chroma block pair, each with the CU's vector: prediction and residual together, so that
+ * every 4x4 unit has ONE ordered writer.  level = 1 + the highest level among the units the source block touches; the TU's
+ * transform blocks are marked OVHIP_RES_STORE, the tasks get OVHIP_IF_RES_* / the chroma-scale fields as intra tasks do; a cbf of 0
+ * gives a task without residual.  cu is checked first (ovhip_rec_ibc_check): a refusal leaves the recorder as it was.
+ * Returns the number of transform-block commands appended or <0. */
+int   ovhip_rec_tu_ibc(ovhip_recorder *rec, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_ibc_desc *cu);
+/* Number of OVHIP_IT_IBC_* tasks recorded since the last reset: pictures without any run the kernels built without the IBC path. */
+size_t ovhip_rec_ibc_tasks(const ovhip_recorder *rec);
 /* tmp.recon_isp_subtree_v / _h (rcn_structures.h:480-491; rcn_transform_tree.c:1087-1205): an intra-sub-partition CU -- 2 or
  * 4 partitions side by side (vertical) or stacked; prediction and residual alternate partition by partition, so every
  * prediction call becomes an ordered task and every partition's transform block a STORE-mode command.  The partition
@@ -911,6 +955,7 @@ int  ovhip_mcxa_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip_pic *re
  * colour planes) from ovhip_intra_level_geom() on the HOST copy of the same tasks, or OVHIP_INTRA_GEOM_ANY (always valid,
  * launches up to 8x the workgroups, most of which leave at once). */
 #define OVHIP_INTRA_GEOM_ANY 0x12u
+#define OVHIP_INTRA_GEOM_IBC 0x20u       /* OR-ed into geom: the tasks may hold OVHIP_IT_IBC_* (ovhip_intra_level_geom sets it) */
 uint32_t ovhip_intra_level_geom(const ovhip_itask *tasks, size_t n);
 int  ovhip_intra_level_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_pic *res, const ovhip_itask *d_tasks, uint32_t n,
                               const ovhip_lmcs_region *d_regions, const ovhip_lmcs_luts *luts, int16_t *d_scales, int32_t log2_ctu_s,
@@ -937,7 +982,9 @@ int  ovhip_intra_ctu_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_pi
  * units of ALL n_tasks tasks.  n_workers: the launch has that many workgroups and workgroup b takes the items b, b + n_workers, ...
  * in turn -- the bound on the pollers of this launch (wave slots the kernels of the other pictures in flight do not get, and what
  * has to fit the device beside the other flow launches for the forward-progress argument to hold); 0 or >= n_items: one workgroup
- * per item. */
+ * per item.  prepare | OVHIP_FLOW_IBC: the list holds OVHIP_IT_IBC_* tasks (ovhip_rec_ibc_tasks) -- the launch then takes the
+ * kernel built with the block-copy path; without the bit such a task is an error of the caller. */
+#define OVHIP_FLOW_IBC 2
 size_t ovhip_intra_flow_words(int32_t width, int32_t height);
 size_t ovhip_intra_flow_items(const ovhip_itask *sorted, size_t n, uint32_t *items, size_t cap);
 int  ovhip_intra_flow_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_pic *res, const ovhip_itask *d_tasks, uint32_t n_tasks,

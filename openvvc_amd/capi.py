@@ -67,6 +67,15 @@ class TuDesc(C.Structure):
                 ("coef", C.c_void_p * 3)]
 
 
+class IbcDesc(C.Structure):
+    """ovhip_ibc_desc: one intra-block-copy coding unit (rcn_ibc_l / rcn_ibc_c)"""
+    _fields_ = [("x0", C.c_uint16), ("y0", C.c_uint16), ("log2_w", C.c_uint8), ("log2_h", C.c_uint8), ("log2_ctu", C.c_uint8),
+                ("has_chroma", C.c_uint8), ("mv_x", C.c_int16), ("mv_y", C.c_int16), ("win_x0", C.c_uint16), ("pad", C.c_uint16)]
+
+
+assert C.sizeof(IbcDesc) == 16
+
+
 class TuInfo(C.Structure):
     _fields_ = [("cbf_mask", C.c_uint8), ("tr_skip_mask", C.c_uint8), ("cu_mts_flag", C.c_uint8), ("cu_mts_idx", C.c_uint8),
                 ("lfnst_flag", C.c_uint8), ("lfnst_idx", C.c_uint8), ("pos_offset", C.c_uint16),
@@ -168,8 +177,14 @@ ITASK_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("log2_w", "u1"), ("log2_h",
 assert ITASK_DTYPE.itemsize == 32
 ICTU_DTYPE = np.dtype([("cx", "<u2"), ("cy", "<u2"), ("first", "<u4"), ("n", "<u4"), ("deps", "<u4")])
 assert ICTU_DTYPE.itemsize == 16
-IT_LUMA, IT_CHROMA, IT_REGION, IT_RES_C = 0, 1, 2, 3
-IF_CORNER, IF_MIP, IF_MIP_TR, IF_BDPCM, IF_BDPCM_VER, IF_RES_Y, IF_RES_CB, IF_RES_CR, IF_RES_SCALE, IF_SCALE_IDX, IF_ISP, IF_CORNER_L = (1 << k for k in range(12))
+IT_LUMA, IT_CHROMA, IT_REGION, IT_RES_C, IT_IBC_L, IT_IBC_C = 0, 1, 2, 3, 4, 5
+IF_CORNER, IF_MIP, IF_MIP_TR, IF_BDPCM, IF_BDPCM_VER, IF_RES_Y, IF_RES_CB, IF_RES_CR, IF_RES_SCALE, IF_SCALE_IDX, IF_ISP, IF_CORNER_L, IF_IBC_FREE = (1 << k for k in range(13))
+INTRA_GEOM_IBC, FLOW_IBC = 0x20, 2      # OVHIP_INTRA_GEOM_IBC, OVHIP_FLOW_IBC
+
+
+def itask_ibc_offset(tasks: np.ndarray):
+    """(dx, dy) of OVHIP_IT_IBC_* tasks: ovhip_itask.pad[0], pad[1] as int16 (OVHIP_ITASK_IBC_DX / _DY)"""
+    return tasks["pad"][..., 0].astype(np.int16), tasks["pad"][..., 1].astype(np.int16)
 
 
 class ITask(C.Structure):
@@ -529,6 +544,9 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_rec_itasks_by_ctu": (vp, [vp, i32, P(C.c_size_t), P(vp), P(C.c_size_t)]),
         "ovhip_rec_tu_intra": (C.c_int, [vp, P(TuState), P(TuDesc), P(ITask), P(ITask)]),
         "ovhip_rec_itasks": (vp, [vp, P(C.c_size_t)]),
+        "ovhip_rec_ibc_check": (C.c_int, [vp, P(IbcDesc)]),
+        "ovhip_rec_tu_ibc": (C.c_int, [vp, P(TuState), P(TuDesc), P(IbcDesc)]),
+        "ovhip_rec_ibc_tasks": (C.c_size_t, [vp]),
         "ovhip_rec_itasks_sorted": (vp, [vp, P(C.c_size_t), P(P(C.c_uint32)), P(C.c_uint32)]),
         "ovhip_rec_set_dbf_offsets": (C.c_int, [vp, P(DbfOffsets), C.c_int]),
         "ovhip_job_create": (C.c_int, [vp, i32, i32, P(vp)]),
@@ -684,6 +702,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_stream_create", "ovhip_stream_destroy", "ovhip_stream_run", "ovhip_stream_frame", "ovhip_stream_key", "ovhip_stream_queue_info",
     "ovhip_output_scale_check", "ovhip_output_scale_launch", "ovhip_pic_output_scaled", "ovhip_pic_digest_scaled",
     "ovhip_frame_set_output_scale", "ovhip_stream_set_output_scale", "ovhip_ctx_scratch_bytes",
+    "ovhip_rec_ibc_check", "ovhip_rec_tu_ibc", "ovhip_rec_ibc_tasks",
 ]
 
 
@@ -775,6 +794,21 @@ class Recorder:
         if r < 0:
             raise ValueError(f"ovhip_rec_tu_intra -> {r}")
         return r
+
+    def ibc_check(self, cu: IbcDesc) -> int:
+        """ovhip_rec_ibc_check: 0, or OVHIP_EUNSUP with the violated rule in refusal()"""
+        return self.lib.ovhip_rec_ibc_check(self.h, C.byref(cu))
+
+    def tu_ibc(self, st: TuState, d: TuDesc, cu: IbcDesc) -> int:
+        """A TU of an intra-block-copy CU (ovhip_rec_tu_ibc): the commands appended, or the error code (< 0) -- OVHIP_EUNSUP leaves
+        the recorder as it was, the reason in refusal()"""
+        return self.lib.ovhip_rec_tu_ibc(self.h, C.byref(st), C.byref(d), C.byref(cu))
+
+    def ibc_tasks(self) -> int:
+        return int(self.lib.ovhip_rec_ibc_tasks(self.h))
+
+    def refusal(self) -> str:
+        return (self.lib.ovhip_rec_refusal(self.h) or b"").decode()
 
     def itasks(self) -> np.ndarray:
         return self._arr(self.lib.ovhip_rec_itasks, ITASK_DTYPE)

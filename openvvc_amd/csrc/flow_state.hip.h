@@ -48,7 +48,8 @@ __device__ __forceinline__ void flow_prepare_task(const ovhip_itask &t, const Fl
 {
     const unsigned mark = 2 * epoch;
     if (t.kind == OVHIP_IT_REGION) { if (lane16 == 0) fs.reg[t.c_scale] = mark; return; }
-    const bool luma = t.kind == OVHIP_IT_LUMA;
+    const bool luma = t.kind == OVHIP_IT_LUMA || t.kind == OVHIP_IT_IBC_L;
+    const bool both = t.kind == OVHIP_IT_CHROMA || t.kind == OVHIP_IT_IBC_C;          // a prediction task writes both chroma planes
     const int sh = luma ? 2 : 1, w = 1 << t.log2_w, h = 1 << t.log2_h;
     const int ux0 = t.x >> sh, uy0 = t.y >> sh, nx = max(1, w >> sh), ny = max(1, h >> sh);
     const int l2nx = 31 - __clz(nx);
@@ -56,8 +57,8 @@ __device__ __forceinline__ void flow_prepare_task(const ovhip_itask &t, const Fl
         const int u = (uy0 + (i >> l2nx)) * fs.w4 + ux0 + (i & (nx - 1));
         if (luma) fs.y[u] = mark;
         else {
-            if (t.kind == OVHIP_IT_CHROMA || (t.flags & OVHIP_IF_RES_CB)) fs.c[0][u] = mark;
-            if (t.kind == OVHIP_IT_CHROMA || (t.flags & OVHIP_IF_RES_CR)) fs.c[1][u] = mark;
+            if (both || (t.flags & OVHIP_IF_RES_CB)) fs.c[0][u] = mark;
+            if (both || (t.flags & OVHIP_IF_RES_CR)) fs.c[1][u] = mark;
         }
     }
 }

@@ -14,6 +14,9 @@
 //   k_intra_level one launch PER LEVEL, the launch boundary orders the levels: the stand-alone entry point, and the second pass
 //                 that decodes a picture again whose flow launch gave up;
 //   k_intra_ctu   (on request) one launch, a workgroup per CTU with the CTU's samples in LDS, neighbour CTUs chained by flags.
+// Intra block copy (OVHIP_IT_IBC_L / _C; rcn_ibc_l / rcn_ibc_c, rcn_ibc.c:8-139) is an item of the same pass whose "prediction" is
+// the block at a vector's distance in the same picture: k_intra_level and k_intra_flow exist twice, built from one source with and
+// without that path (template <bool IBC>); pictures without such a task run the build without it, which is the kernel as it was.
 // What an item IS is written once for the three: its decode (Item / item_of), the prediction dispatch (predict_item) and, for
 // the two kernels that finish sample by sample, the epilogue (epilogue_load / epilogue_store).  The kernels supply the strip size,
 // where the samples and residuals live (accessors, dst / rp) and how the reference arms arrive (the fetch policy).
@@ -500,11 +503,11 @@ struct Item {
     __device__ __forceinline__ bool res_at(int x) const { return (res_mask >> (x >> res_l2pb)) & 1; }
 };
 
-template <int STRIP_>
+template <int STRIP_, bool IBC = false>
 __device__ __forceinline__ Item item_of(const ovhip_itask &t, int strip, int plane)
 {
     Item it;
-    it.luma = t.kind == OVHIP_IT_LUMA; it.region = t.kind == OVHIP_IT_REGION; it.res_only = t.kind == OVHIP_IT_RES_C;
+    it.luma = t.kind == OVHIP_IT_LUMA || (IBC && t.kind == OVHIP_IT_IBC_L); it.region = t.kind == OVHIP_IT_REGION; it.res_only = t.kind == OVHIP_IT_RES_C;
     // (a block-DPCM task is recorded with mode 0; the flag is part of the predicate so that no kernel depends on that)
     it.lm = t.kind == OVHIP_IT_CHROMA && t.mode >= 67 && !(t.flags & OVHIP_IF_BDPCM);
     it.has_res = t.flags & (it.luma ? OVHIP_IF_RES_Y : (plane ? OVHIP_IF_RES_CR : OVHIP_IF_RES_CB));
@@ -554,6 +557,26 @@ __device__ __forceinline__ bool predict_item(IntraLds &s, const ovhip_itask &t, 
     return true;
 }
 
+// Intra block copy: the strip's "prediction" is the block (dx, dy) away in the item's own plane, as it stands before any loop filter --
+// acc reads the picture (the flow launch: past the caches, the hand-over bit dropped from every sample, luma and chroma).  Source
+// rows start at any sample (odd vectors, and the chroma vector is the luma one halved), so a 16- / 8-byte load would need a case
+// split by row alignment; the NP 2-byte loads of a lane are independent and go out together -- ONE round trip on the item's critical
+// path either way, which is what a hop costs.
+template <int NP, class Acc>
+__device__ __forceinline__ void ibc_copy(IntraLds &s, const ovhip_itask &t, const Item &it, const Acc acc, int lane)
+{
+    const int l2w = t.log2_w, sx = t.x + OVHIP_ITASK_IBC_DX(t), sy = t.y + OVHIP_ITASK_IBC_DY(t);
+    int v[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int p = min(it.p0 + lane + 64 * i, it.p1 - 1);                  // lanes past the strip re-read its last sample
+        v[i] = acc.ld(sx + (p & ((1 << l2w) - 1)), sy + (p >> l2w)) & 0x7fff;
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) { const int p = it.p0 + lane + 64 * i; if (p < it.p1) s.pred[p - it.p0] = (uint16_t)v[i]; }
+    wave_sync();
+}
+
 // The sample-by-sample epilogue of the level and the CTU kernel: prediction or old sample -> CIIP blend -> (scaled) residual ->
 // clip -> store.  What it needs from dst / rp is read by epilogue_load: in front of the prediction where that is a memory round
 // trip (the level kernel), right before the store where it is LDS (the CTU kernel).
@@ -584,6 +607,7 @@ __device__ __forceinline__ void epilogue_store(const IntraLds &s, const int (&rv
     }
 }
 
+template <bool IBC>
 __global__ __launch_bounds__(64) void k_intra_level(ovhip_pic pic, ovhip_pic res, const ovhip_itask *__restrict__ tasks, uint32_t n,
                                                     const ovhip_lmcs_region *__restrict__ regs, LmcsWnd wnd, int16_t *__restrict__ scales,
                                                     int log2_ctu)
@@ -595,7 +619,7 @@ __global__ __launch_bounds__(64) void k_intra_level(ovhip_pic pic, ovhip_pic res
     const int lane = threadIdx.x;
     load_tables(s, lane);
     const ovhip_itask t = tasks[bid];
-    const Item it = item_of<STRIP>(t, strip, comp);
+    const Item it = item_of<STRIP, IBC>(t, strip, comp);
     const PlaneAcc ya = { pic.y, pic.stride_y };
     if (it.region) {
         if (!strip && !comp) { const int v = region_scale(ya, regs[t.c_scale], wnd, lane); if (lane == 0) scales[t.c_scale] = (int16_t)v; }
@@ -611,7 +635,8 @@ __global__ __launch_bounds__(64) void k_intra_level(ovhip_pic pic, ovhip_pic res
     epilogue_load(rv, dv, it, dst, dstride, rp, rstride, t.log2_w, lane);
     const int scale = it.scaled ? (it.scale_idx ? scales[t.c_scale] : t.c_scale) : 0;
     const PlaneAcc ca = { pl, pic.stride_c };
-    if (!it.res_only) predict_item<NPL>(s, t, it, ya, ca, log2_ctu, DirectRefs(), lane);
+    if (IBC && t.kind >= OVHIP_IT_IBC_L) ibc_copy<NPL>(s, t, it, PlaneAcc{ pl, dstride }, lane);
+    else if (!it.res_only) predict_item<NPL>(s, t, it, ya, ca, log2_ctu, DirectRefs(), lane);
     epilogue_store(s, rv, dv, it, scale, dst, dstride, t.log2_w, lane);
 }
 
@@ -991,10 +1016,10 @@ __global__ __launch_bounds__(256) void k_flow_untag(ovhip_pic pic, const ovhip_i
     const uint32_t ti = blockIdx.x * 16 + (threadIdx.x >> 4);
     if (ti >= n) return;
     const ovhip_itask t = tasks[ti];
-    if (t.kind == OVHIP_IT_REGION || (t.kind == OVHIP_IT_LUMA && !with_luma)) return;
+    const bool luma = t.kind == OVHIP_IT_LUMA || t.kind == OVHIP_IT_IBC_L;
+    if (t.kind == OVHIP_IT_REGION || (luma && !with_luma)) return;
     const int lane = threadIdx.x & 15;
     const int l2w = t.log2_w, w = 1 << l2w, npx = w << t.log2_h;
-    const bool luma = t.kind == OVHIP_IT_LUMA;
     const int stride = luma ? pic.stride_y : pic.stride_c;
     for (int c = 0; c < (luma ? 1 : 2); ++c) {
         if (!luma && t.kind == OVHIP_IT_RES_C && !(t.flags & (c ? OVHIP_IF_RES_CR : OVHIP_IF_RES_CB))) continue;
@@ -1127,6 +1152,7 @@ __device__ __forceinline__ void flow_store(const IntraLds &s, const FlowRaw &q, 
 //  the same within its noise -- not taken)
 struct FlowLds { IntraLds s; uint32_t fp[FLOW_MAX_FP]; int abort; };
 
+template <bool IBC>
 __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res, const ovhip_itask *__restrict__ tasks, const uint32_t *__restrict__ items,
                                                    uint32_t n_items, const ovhip_lmcs_region *__restrict__ regs, LmcsWnd wnd, int16_t *scales,
                                                    int log2_ctu, FlowState fs, unsigned epoch, unsigned *sync, unsigned *abort_mirror)
@@ -1153,9 +1179,10 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
     const FlowItem fi = flow_item_unpack(items[bid]);
     const ovhip_itask t = tasks[fi.task];
     const int comp = fi.plane;
-    const Item it = item_of<FSTRIP>(t, fi.strip, comp);
+    const Item it = item_of<FSTRIP, IBC>(t, fi.strip, comp);
     const int l2w = t.log2_w, w = 1 << l2w, h = 1 << t.log2_h;
     const bool luma = it.luma;
+    const bool ibc = IBC && t.kind >= OVHIP_IT_IBC_L;
     const unsigned pending = 2 * epoch;
     const int w4 = fs.w4;
     if (it.skip()) continue;
@@ -1230,6 +1257,20 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
         }
         if (it.scale_idx) add_run(fs.reg, t.c_scale, 0, 1, 1, 0);
     }
+    if constexpr (IBC) {
+        // intra block copy: the units the strip's source rows touch, one run per unit row (the recorder found the flag where none of
+        // them has an ordered writer).  At most 85 words: a 256-sample strip of a 4-wide luma block is 64 rows = 17 unit rows of 2
+        // units, a 64-wide one 2 x 17; chroma units are 2 samples, so a strip of an 8-wide chroma block (32 rows) is 17 unit rows of 5
+        // and one of a 32-wide block (8 rows) 5 x 17 -- FLOW_MAX_FP is 448.  An item waits only for tasks of a lower level, and
+        // bounded, like every other.
+        if (ibc && !(t.flags & OVHIP_IF_IBC_FREE)) {
+            const int sh = luma ? 2 : 1, y0s = it.p0 >> l2w, y1s = (it.p1 + w - 1) >> l2w;
+            const int sx = t.x + OVHIP_ITASK_IBC_DX(t), sy = t.y + OVHIP_ITASK_IBC_DY(t);
+            const int ux0 = sx >> sh, nux = ((sx + w - 1) >> sh) - ux0 + 1;
+            unsigned *fb = luma ? fs.y : fs.c[comp];
+            for (int uy = (sy + y0s) >> sh; uy <= (sy + y1s - 1) >> sh; ++uy) add_run(fb, ux0, uy, nux, 1, 0);
+        }
+    }
     wave_sync();
     FPROBE(1);
     {
@@ -1264,7 +1305,8 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
     // (the derived scale is requested here and first looked at in the epilogue: no wait in front of the reference fetch)
     int scale_ld = 0;
     if (it.scale_idx) scale_ld = (int)__hip_atomic_load(scales + t.c_scale, RLX_AGENT);
-    if (!it.res_only) {
+    if (IBC && ibc) ibc_copy<FNPL>(s, t, it, AgentAcc{ pl, dstride }, lane);
+    else if (!it.res_only) {
         if (luma && (t.flags & OVHIP_IF_ISP) && (t.y & 3)) {
             // thin_row: the last row of the partition above (same coding unit, same 4x4 units as this block) arrives TAGGED -- every
             // luma item stores its samples with FLOW_TAG -- and is polled itself, as fetch_refs_tagged polls a regular block's arms
@@ -1320,17 +1362,18 @@ __global__ __launch_bounds__(64) void k_intra_flow(ovhip_pic pic, ovhip_pic res,
 } // namespace
 
 // Launch geometry of a level from its tasks (HOST memory): bits 0-1 = log2 of the strips of the largest block (1024 samples
-// each), bit 4 = some task covers both chroma planes.
+// each), bit 4 = some task covers both chroma planes, bit 5 (OVHIP_INTRA_GEOM_IBC) = some task is an intra block copy.
 extern "C" uint32_t ovhip_intra_level_geom(const ovhip_itask *tasks, size_t n)
 {
-    uint32_t l2s = 0, two = 0;
+    uint32_t l2s = 0, two = 0, ibc = 0;
     for (size_t i = 0; tasks && i < n; ++i) {
         if (tasks[i].kind == OVHIP_IT_REGION) continue;
         const int l2 = tasks[i].log2_w + tasks[i].log2_h;
         if (l2 > 10 && (uint32_t)(l2 - 10) > l2s) l2s = (uint32_t)(l2 - 10);
-        two |= tasks[i].kind != OVHIP_IT_LUMA;
+        two |= tasks[i].kind != OVHIP_IT_LUMA && tasks[i].kind != OVHIP_IT_IBC_L;
+        ibc |= tasks[i].kind >= OVHIP_IT_IBC_L;
     }
-    return (l2s > 2 ? 2 : l2s) | (two << 4);
+    return (l2s > 2 ? 2 : l2s) | (two << 4) | (ibc ? OVHIP_INTRA_GEOM_IBC : 0);
 }
 
 // One level of the ordered pass.  d_tasks: DEVICE, the n tasks of this level.  res: residual picture written by
@@ -1346,8 +1389,11 @@ extern "C" int ovhip_intra_level_launch(ovhip_ctx *ctx, const ovhip_pic *pic, co
     if (!d_tasks || log2_ctu_s < 5 || log2_ctu_s > 7 || (geom & 3) == 3)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_intra_level_launch: bad arguments", hipSuccess);
     const LmcsWnd wnd = lmcs_wnd_of(luts);
-    hipLaunchKernelGGL(k_intra_level, dim3(n, 1u << (geom & 3), (geom & 16) ? 2 : 1), dim3(64), 0, ctx->stream, *pic, *res, d_tasks, n, d_regions, wnd,
-                       d_scales, log2_ctu_s);
+    const dim3 grid(n, 1u << (geom & 3), (geom & 16) ? 2 : 1);
+    if (geom & OVHIP_INTRA_GEOM_IBC)
+        hipLaunchKernelGGL(k_intra_level<true>, grid, dim3(64), 0, ctx->stream, *pic, *res, d_tasks, n, d_regions, wnd, d_scales, log2_ctu_s);
+    else
+        hipLaunchKernelGGL(k_intra_level<false>, grid, dim3(64), 0, ctx->stream, *pic, *res, d_tasks, n, d_regions, wnd, d_scales, log2_ctu_s);
     OV_LAUNCH_CHECK(ctx, "k_intra_level");
     return OVHIP_OK;
 }
@@ -1401,7 +1447,7 @@ extern "C" size_t ovhip_intra_flow_items_(const ovhip_itask *sorted, size_t n, u
         const ovhip_itask &t = sorted[i];
         if (i >= FLOW_ITEM_MAX_TASKS) return 0;
         if (t.kind == OVHIP_IT_REGION) { if (k < cap) items[k] = flow_item_pack((uint32_t)i, 0, 0); ++k; continue; }
-        const int npx = 1 << (t.log2_w + t.log2_h), strips = (npx + FSTRIP - 1) / FSTRIP, comps = t.kind == OVHIP_IT_LUMA ? 1 : 2;
+        const int npx = 1 << (t.log2_w + t.log2_h), strips = (npx + FSTRIP - 1) / FSTRIP, comps = (t.kind == OVHIP_IT_LUMA || t.kind == OVHIP_IT_IBC_L) ? 1 : 2;
         if (strips > FLOW_ITEM_MAX_STRIPS) return 0;
         for (int st = 0; st < strips; ++st)
             for (int c = 0; c < comps; ++c) { if (k < cap) items[k] = flow_item_pack((uint32_t)i, st, c); ++k; }
@@ -1437,7 +1483,7 @@ extern "C" int ovhip_intra_flow_launch(ovhip_ctx *ctx, const ovhip_pic *pic, con
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_intra_flow_launch: bad arguments", hipSuccess);
     const LmcsWnd wnd = lmcs_wnd_of(luts);
     const FlowState fs = flow_state_of(d_state, pic->w, pic->h);
-    if (prepare) {
+    if (prepare & 1) {
         hipLaunchKernelGGL(k_intra_flow_prepare, dim3((n_tasks + 15) / 16), dim3(256), 0, ctx->stream, d_tasks, n_tasks, fs, epoch);
         OV_LAUNCH_CHECK(ctx, "k_intra_flow_prepare");
     }
@@ -1446,8 +1492,13 @@ extern "C" int ovhip_intra_flow_launch(ovhip_ctx *ctx, const ovhip_pic *pic, con
 #endif
     // n_workers workgroups take the items in turn (k_intra_flow); 0 or >= n_items: one workgroup per item
     const uint32_t grid = (n_workers > 0 && (uint32_t)n_workers < n_items) ? (uint32_t)n_workers : n_items;
-    hipLaunchKernelGGL(k_intra_flow, dim3(grid), dim3(64), 0, ctx->stream, *pic, *res, d_tasks, d_items, n_items, d_regions, wnd, d_scales, log2_ctu_s, fs,
-                       epoch, d_state, abort_mirror);
+    // (the build with the block-copy path only for lists that hold such tasks: every path added to k_intra_flow slowed every hop)
+    if (prepare & OVHIP_FLOW_IBC)
+        hipLaunchKernelGGL(k_intra_flow<true>, dim3(grid), dim3(64), 0, ctx->stream, *pic, *res, d_tasks, d_items, n_items, d_regions, wnd, d_scales, log2_ctu_s, fs,
+                           epoch, d_state, abort_mirror);
+    else
+        hipLaunchKernelGGL(k_intra_flow<false>, dim3(grid), dim3(64), 0, ctx->stream, *pic, *res, d_tasks, d_items, n_items, d_regions, wnd, d_scales, log2_ctu_s, fs,
+                           epoch, d_state, abort_mirror);
     OV_LAUNCH_CHECK(ctx, "k_intra_flow");
     return OVHIP_OK;
 }

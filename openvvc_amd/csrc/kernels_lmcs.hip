@@ -62,7 +62,7 @@ __device__ __forceinline__ void untag_chroma_tasks(const ovhip_pic &pic, const o
     const uint32_t ti = wg * UNTAG_TASKS_PER_WG + (threadIdx.x >> 6);
     if (ti >= n) return;
     const ovhip_itask t = tasks[ti];
-    if (t.kind == OVHIP_IT_REGION || t.kind == OVHIP_IT_LUMA) return;          // (the mapping itself drops the bit of every luma sample)
+    if (t.kind == OVHIP_IT_REGION || t.kind == OVHIP_IT_LUMA || t.kind == OVHIP_IT_IBC_L) return;          // (the mapping itself drops the bit of every luma sample)
     const int lane = threadIdx.x & 63;
     const int l2w = t.log2_w, w = 1 << l2w, npx = w << t.log2_h, stride = pic.stride_c;
     const bool res_only = t.kind == OVHIP_IT_RES_C;

@@ -283,6 +283,7 @@ static int band_plan(ovhip_job *j, const ovhip_pic *dst, const ovhip_job_params 
     if (ovhip_rec_ciip_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: stand-alone CIIP blend units (a second picture with the caller's intra prediction)", hipSuccess);
     if (ovhip_rec_rpr_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: reference picture resampling units", hipSuccess);
     if (ovhip_rec_aff_rpr_units(rec, &dummy) && dummy) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: reference picture resampling units (affine)", hipSuccess);
+    if (ovhip_rec_ibc_tasks(rec)) return ov_fail(ctx, OVHIP_EUNSUP, "ovhip_job_band: intra block copy tasks (the whole-picture flush runs them)", hipSuccess);
     {
         const uint32_t *hi = &c1.n_tb, *lo = &c0.n_tb; uint32_t *n = &k.n.n_tb;
         for (int i = 0; i < 10; ++i) n[i] = hi[i] - lo[i];

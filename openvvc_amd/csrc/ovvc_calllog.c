@@ -11,7 +11,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_record_priv.h"
 
-enum { CL_CTU_SIZE = 1, CL_TU, CL_ISP, CL_PU, CL_AFF, CL_REGION, CL_DBF, CL_CIIP, CL_REF_SCALE, CL_RPR_TOOLS };
+enum { CL_CTU_SIZE = 1, CL_TU, CL_ISP, CL_PU, CL_AFF, CL_REGION, CL_DBF, CL_CIIP, CL_REF_SCALE, CL_RPR_TOOLS, CL_TU_IBC };
 
 struct ovhip_calllog { unsigned char *data; size_t n, cap; int oom; int tools_logged; };   /* oom: the log is unusable (allocation failed or a call could not be written down): _data returns NULL */
 
@@ -21,6 +21,7 @@ struct cl_tu {
     ovhip_itask tl, tc;
     uint32_t has_l, has_c;
 };
+struct cl_tu_ibc { ovhip_tu_state st; ovhip_tu_desc tu; ovhip_ibc_desc cu; uint32_t pad; };   /* st, tu, coefficients as cl_tu */
 struct cl_isp { ovhip_tu_state st; ovhip_isp_desc cu; };
 struct cl_region { int32_t x0, y0; uint32_t abv, lft; };
 struct cl_ciip { int32_t x0, y0, log2_w, log2_h, mode_abv, mode_lft; };
@@ -77,19 +78,19 @@ tu_coef_extent(const ovhip_tu_desc *tu, int comp)
     return (size_t)stride * (need_rows < rows ? need_rows : rows);
 }
 
-void
-ovhip_calllog_tu_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *il, const ovhip_itask *ic)
+/* a record that starts with { ovhip_tu_state, ovhip_tu_desc } and ends with the TU's coefficient blocks behind its fixed part of
+ * `head` bytes (zeroed past the two): returns the payload */
+static unsigned char *
+cl_open_tu(ovhip_calllog *l, uint32_t type, size_t head, const ovhip_tu_state *st, const ovhip_tu_desc *tu)
 {
     size_t ext[3], tot = 0;
     for (int c = 0; c < 3; ++c) { ext[c] = tu->coef[c] ? tu_coef_extent(tu, c) : 0; tot += (ext[c] + 3) & ~(size_t)3; }
-    unsigned char *p = cl_open(l, CL_TU, sizeof(struct cl_tu) + 2 * tot);
-    if (!p) return;
-    struct cl_tu *q = (struct cl_tu *)p;
-    memset(q, 0, sizeof(*q));
+    unsigned char *p = cl_open(l, type, head + 2 * tot);
+    if (!p) return NULL;
+    struct cl_tu *q = (struct cl_tu *)p;          /* (every such record starts like cl_tu) */
+    memset(p, 0, head);
     q->st = *st; q->tu = *tu;
-    if (il) { q->tl = *il; q->has_l = 1; }
-    if (ic) { q->tc = *ic; q->has_c = 1; }
-    int16_t *dst = (int16_t *)(p + sizeof(*q));
+    int16_t *dst = (int16_t *)(p + head);
     size_t off = 0;
     for (int c = 0; c < 3; ++c) {
         q->tu.coef[c] = NULL;
@@ -98,6 +99,24 @@ ovhip_calllog_tu_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_tu_des
         q->tu.coef[c] = (const int16_t *)(uintptr_t)(off + 1);
         off += (ext[c] + 3) & ~(size_t)3;
     }
+    return p;
+}
+
+void
+ovhip_calllog_tu_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *il, const ovhip_itask *ic)
+{
+    struct cl_tu *q = (struct cl_tu *)cl_open_tu(l, CL_TU, sizeof(struct cl_tu), st, tu);
+    if (!q) return;
+    if (il) { q->tl = *il; q->has_l = 1; }
+    if (ic) { q->tc = *ic; q->has_c = 1; }
+}
+
+/* ovhip_rec_tu_ibc: a record kind of its own, written only by that call (logs of pictures without IBC keep their bytes) */
+void
+ovhip_calllog_tu_ibc_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_ibc_desc *cu)
+{
+    struct cl_tu_ibc *q = (struct cl_tu_ibc *)cl_open_tu(l, CL_TU_IBC, sizeof(struct cl_tu_ibc), st, tu);
+    if (q) { q->cu = *cu; q->cu.pad = 0; }
 }
 
 void
@@ -204,13 +223,15 @@ ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec)
 #define CL_NEED(bytes_) if (len < (size_t)(bytes_)) { r = OVHIP_EINVAL; break; }
         switch (hdr[0]) {
         case CL_CTU_SIZE: { int32_t v; CL_NEED(4) memcpy(&v, q, 4); r = ovhip_rec_set_ctu_size(rec, v); break; }
-        case CL_TU: {
-            CL_NEED(sizeof(struct cl_tu))
-            const struct cl_tu *t = (const struct cl_tu *)q;
+        case CL_TU:
+        case CL_TU_IBC: {
+            const size_t head = hdr[0] == CL_TU ? sizeof(struct cl_tu) : sizeof(struct cl_tu_ibc);
+            CL_NEED(head)
+            const struct cl_tu *t = (const struct cl_tu *)q;          /* (cl_tu_ibc starts with the same two members) */
             ovhip_tu_desc d = t->tu;
-            if (d.log2_tb_w > 7 || d.log2_tb_h > 7 || t->has_l > 1 || t->has_c > 1) { r = OVHIP_EINVAL; break; }
-            const int16_t *coefs = (const int16_t *)(q + sizeof(*t));
-            const size_t have = (len - sizeof(*t)) / 2;
+            if (d.log2_tb_w > 7 || d.log2_tb_h > 7 || (hdr[0] == CL_TU && (t->has_l > 1 || t->has_c > 1))) { r = OVHIP_EINVAL; break; }
+            const int16_t *coefs = (const int16_t *)(q + head);
+            const size_t have = (len - head) / 2;
             int ok = 1;
             for (int c = 0; c < 3; ++c) {
                 const uintptr_t o = (uintptr_t)t->tu.coef[c];
@@ -219,7 +240,8 @@ ovhip_calllog_replay(const void *data, size_t bytes, ovhip_recorder *rec)
                 d.coef[c] = coefs + (o - 1);
             }
             if (!ok) { r = OVHIP_EINVAL; break; }
-            r = ovhip_rec_tu_intra(rec, &t->st, &d, t->has_l ? &t->tl : NULL, t->has_c ? &t->tc : NULL);
+            if (hdr[0] == CL_TU) r = ovhip_rec_tu_intra(rec, &t->st, &d, t->has_l ? &t->tl : NULL, t->has_c ? &t->tc : NULL);
+            else r = ovhip_rec_tu_ibc(rec, &t->st, &d, &((const struct cl_tu_ibc *)q)->cu);
             break;
         }
         case CL_ISP: {

@@ -122,6 +122,7 @@ struct Chain {
     const uint32_t *lv_start; uint32_t n_lv;
     const uint32_t *d_items; uint32_t n_items;                        // n_items != 0: a flow launch runs the ordered pass
     int prepared;                                                     // (chain_residual) the chroma-scale launch prepared the flow state
+    int ibc;                                                          // the tasks hold intra block copies: the flow kernel built with that path
 };
 
 #pragma GCC visibility push(hidden)

@@ -465,7 +465,7 @@ int chain_ordered(const Chain &c, int n_workers)
     ovhip_job *j = c.j;
     if (c.n_items) {
         CHK(ovhip_intra_flow_launch(j->ctx, c.dst, c.res, c.d_it, c.n_it, c.d_items, c.n_items, c.d_reg, c.luts, c.d_scales, c.log2_ctu,
-                                    j->d_flow, j->epoch, j->abort_host, !c.prepared, n_workers));
+                                    j->d_flow, j->epoch, j->abort_host, (c.prepared ? 0 : 1) | (c.ibc ? OVHIP_FLOW_IBC : 0), n_workers));
         j->st.n_launches += 1 + !c.prepared;
         return OVHIP_OK;
     }
@@ -540,6 +540,7 @@ struct Gathered {
     ovhip_band_counts n;                          // (n_itask: 0 without OVHIP_STAGE_INTRA)
     size_t n_ciip, n_rpr, n_affr, n_ictu;
     size_t n_items;                               // the flow launch's items in j->items_host; 0: the ordered pass cannot run as one
+    bool ibc;                                     // the ordered tasks hold intra block copies
     int by_ctu; bool ordered, flow;               // the ordered pass: grouped by CTU for the one-launch pass, as ONE flow launch, else per level
 };
 
@@ -578,8 +579,11 @@ int flush_gather(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *intra, con
     g.affr = ovhip_rec_aff_rpr_units(rec, &g.n_affr);         // affine units that do (k_mca_rpr)
     // ---- ordered tasks: grouped by CTU for the one-launch pass, or sorted by level for one launch per level ----
     size_t n_it = 0;
-    g.by_ctu = pr->stages && (stages & OVHIP_STAGE_INTRA_CTU);
-    int by_flow = !g.by_ctu && !(pr->stages && (stages & OVHIP_STAGE_INTRA_LEVELS));
+    // (k_intra_ctu does not know intra block copy: a picture with such tasks asked for as the CTU pass runs one launch per level)
+    const int want_ctu = pr->stages && (stages & OVHIP_STAGE_INTRA_CTU);
+    g.ibc = ovhip_rec_ibc_tasks(rec) != 0;
+    g.by_ctu = want_ctu && !g.ibc;
+    int by_flow = !want_ctu && !(pr->stages && (stages & OVHIP_STAGE_INTRA_LEVELS));
     // a resident replay runs from what the last FULL flush left on the device: after a second pass (ovhip_job_wait: per-level launches,
     // no item list in the parameter block) that is a picture without the flow launch's items
     if (j->resident && by_flow && !j->flow_on_device) by_flow = 0;
@@ -758,7 +762,7 @@ int flush_launch(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *refs, uint
     c.luts = pr->lmcs; c.d_fwd = pr->lmcs ? (const uint16_t *)(p.block + p.tabs.at[T_FWD]) : nullptr; c.d_scales = (int16_t *)j->dev[B_SCALE].p;
     chain_bind(c, p, ovhip_band_counts{}, g.n, (uint32_t)g.n_rpr, (uint32_t)g.n_affr);
     memcpy(c.cls, g.cls, sizeof(c.cls)); memcpy(c.tiny, g.tiny, sizeof(c.tiny));
-    c.h_it = g.it; c.lv_start = g.lv_start; c.n_lv = g.n_lv; c.n_items = g.flow ? (uint32_t)g.n_items : 0;
+    c.h_it = g.it; c.lv_start = g.lv_start; c.n_lv = g.n_lv; c.n_items = g.flow ? (uint32_t)g.n_items : 0; c.ibc = g.ibc;
 
     if (stages & OVHIP_STAGE_MC) CHK(launch_predict(j, c, refs, n_refs, intra, pr, g, p));
     // ---- the flow launch's state (before the residual stage: the chroma-scale launch prepares the state words as a rider) ----

@@ -174,6 +174,8 @@ ovhip_rec_append_raw(ovhip_recorder *r, int which, const void *data, size_t n)
     }
     if (grow(p, cap, *cnt + n, elem)) return OVHIP_ENOMEM;
     if (n) memcpy((char *)*p + *cnt * elem, data, n * elem);
+    if (which == OVHIP_REC_ITASK)
+        for (size_t i = 0; i < n; ++i) { const uint8_t k = ((const ovhip_itask *)data)[i].kind; r->n_ibc += k == OVHIP_IT_IBC_L || k == OVHIP_IT_IBC_C; }
     *cnt += n;
     return OVHIP_OK;
 }
@@ -528,17 +530,15 @@ fail:
     return ret;
 }
 
-int
-ovhip_rec_tu_intra(ovhip_recorder *r, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *intra_l, const ovhip_itask *intra_c)
+/* One TU with the ordered tasks (intra prediction, or intra block copy) that run right before its luma / chroma residual */
+static int
+tu_ordered(ovhip_recorder *r, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *intra_l, const ovhip_itask *intra_c)
 {
-    if (!r || !st || !tu) return OVHIP_EINVAL;
-    if (r->log) ovhip_calllog_tu_(r->log, st, tu, intra_l, intra_c);
-    const size_t n0 = r->n_tb, c0 = r->n_coef, t0 = r->n_itask;
+    const size_t n0 = r->n_tb, c0 = r->n_coef, t0 = r->n_itask, i0 = r->n_ibc;
     int ret;
     ovhip_tb_cmd *c;
     int ti_l = -1, ti_c = -1;
-    if ((intra_l && (intra_l->kind != OVHIP_IT_LUMA || tu->tree == 2)) || (intra_c && (intra_c->kind != OVHIP_IT_CHROMA || tu->tree == 1)))
-        return OVHIP_EINVAL;
+    if ((intra_l && tu->tree == 2) || (intra_c && tu->tree == 1)) return OVHIP_EINVAL;
     /* the luma prediction comes first (rcn_intra_tu before rcn_tu_st, rcn_transform_tree.c:1437-1441) */
     if (intra_l) {
         if ((ti_l = ovhip_rec_itask_add_(r, intra_l, 0)) < 0) return ti_l;
@@ -652,7 +652,71 @@ fail:
     r->n_tb = n0;
     r->n_coef = c0;
     r->n_itask = t0;          /* (the level maps keep the marks of the dropped tasks: harmless, levels only grow) */
+    r->n_ibc = i0;
     return ret;
+}
+
+int
+ovhip_rec_tu_intra(ovhip_recorder *r, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *intra_l, const ovhip_itask *intra_c)
+{
+    if (!r || !st || !tu) return OVHIP_EINVAL;
+    if (r->log) ovhip_calllog_tu_(r->log, st, tu, intra_l, intra_c);
+    if ((intra_l && intra_l->kind != OVHIP_IT_LUMA) || (intra_c && intra_c->kind != OVHIP_IT_CHROMA)) return OVHIP_EINVAL;
+    return tu_ordered(r, st, tu, intra_l, intra_c);
+}
+
+/* ---------------------------------------------------------------- intra block copy (rcn_ibc_l / rcn_ibc_c, rcn_ibc.c:8-139)
+ * The reference copies inside a ring of (256 * 128) >> log2_ctu luma columns per CTU row (rcn_ctu.c:554-568): column
+ * (ctb_pos + x0 + mv.x) & (ring_w - 1), row (y0 + mv.y) & (ctu - 1).  The ring holds the PICTURE's sample at (x0 + mv.x, y0 + mv.y)
+ * exactly inside the window tested here; the device reads the picture. */
+static int
+ibc_refuse(ovhip_recorder *r, const char *why)
+{
+    r->refusal = why;
+    return OVHIP_EUNSUP;
+}
+
+int
+ovhip_rec_ibc_check(ovhip_recorder *r, const ovhip_ibc_desc *cu)
+{
+    if (!r || !cu || cu->log2_ctu < 5 || cu->log2_ctu > 7 || cu->log2_w < 2 || cu->log2_h < 2 || cu->log2_w > cu->log2_ctu || cu->log2_h > cu->log2_ctu)
+        return OVHIP_EINVAL;
+    const int l2c = cu->log2_ctu, w = 1 << cu->log2_w, h = 1 << cu->log2_h, x0 = cu->x0, y0 = cu->y0;
+    if (x0 >= r->pic_w || y0 >= r->pic_h) return OVHIP_EINVAL;
+    const int sx = x0 + cu->mv_x, sy = y0 + cu->mv_y;
+    const int cx = x0 >> l2c, n_ctb = ((256 * 128) >> l2c) >> l2c;
+    if (sy < 0 || (sy >> l2c) != (y0 >> l2c) || ((sy + h - 1) >> l2c) != (y0 >> l2c))
+        return ibc_refuse(r, "IBC: the source block leaves the coding unit's CTU row");
+    if (sx < (int)cu->win_x0) return ibc_refuse(r, "IBC: the source block starts left of the rect entry / tile");
+    if (sx < 0 || sx < ((cx - (n_ctb - 1)) << l2c)) return ibc_refuse(r, "IBC: the source block starts left of the CTUs the reference's ring still holds");
+    if (sx + w > ((cx + 1) << l2c)) return ibc_refuse(r, "IBC: the source block ends right of the coding unit's CTU");
+    if (sx + w > r->pic_w || sy + h > r->pic_h) return ibc_refuse(r, "IBC: the source block leaves the picture");
+    if (sx < x0 + w && sx + w > x0 && sy < y0 + h && sy + h > y0) return ibc_refuse(r, "IBC: the source block overlaps the coding unit");
+    return OVHIP_OK;
+}
+
+int
+ovhip_rec_tu_ibc(ovhip_recorder *r, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_ibc_desc *cu)
+{
+    if (!r || !st || !tu || !cu) return OVHIP_EINVAL;
+    /* the TU is a transform block of the CU; luma-only CUs (dual tree, `share`) come through the luma tree */
+    if (tu->tree == 2 || (tu->tree == 0) != !!cu->has_chroma || tu->lfnst_flag || (tu->cu_flags & CUF_PRED_MODE_INTRA)) return OVHIP_EINVAL;
+    const int tw = 1 << tu->log2_tb_w, th = 1 << tu->log2_tb_h;
+    if (tu->x0 < cu->x0 || tu->y0 < cu->y0 || tu->x0 + tw > cu->x0 + (1 << cu->log2_w) || tu->y0 + th > cu->y0 + (1 << cu->log2_h)) return OVHIP_EINVAL;
+    if (tu->x0 + tw > r->pic_w || tu->y0 + th > r->pic_h) return OVHIP_EINVAL;
+    const int chk = ovhip_rec_ibc_check(r, cu);
+    if (chk) return chk;
+    if (r->log) ovhip_calllog_tu_ibc_(r->log, st, tu, cu);
+    ovhip_itask tl, tc;
+    memset(&tl, 0, sizeof(tl)); memset(&tc, 0, sizeof(tc));
+    tl.kind = OVHIP_IT_IBC_L; tl.x = tu->x0; tl.y = tu->y0; tl.log2_w = tu->log2_tb_w; tl.log2_h = tu->log2_tb_h;
+    tl.pad[0] = (uint16_t)cu->mv_x; tl.pad[1] = (uint16_t)cu->mv_y;
+    if (cu->has_chroma) {
+        /* (ref_x - ctb_pos) >> 1 and ref_y >> 1 (rcn_ibc.c): the floor of the luma position; CU positions are even */
+        tc.kind = OVHIP_IT_IBC_C; tc.x = tu->x0 >> 1; tc.y = tu->y0 >> 1; tc.log2_w = (uint8_t)(tu->log2_tb_w - 1); tc.log2_h = (uint8_t)(tu->log2_tb_h - 1);
+        tc.pad[0] = (uint16_t)(int16_t)(cu->mv_x >> 1); tc.pad[1] = (uint16_t)(int16_t)(cu->mv_y >> 1);
+    }
+    return tu_ordered(r, st, tu, &tl, cu->has_chroma ? &tc : NULL);
 }
 
 /* ---------------------------------------------------------------- transform tree of one CU

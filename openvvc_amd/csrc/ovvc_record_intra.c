@@ -34,7 +34,7 @@ maps_ready(ovhip_recorder *r)
 int
 ovhip_rec_intra_reset_(ovhip_recorder *r)
 {
-    r->n_itask = 0; r->n_ilevels = 0; r->max_ilevel = 0;
+    r->n_itask = 0; r->n_ibc = 0; r->n_ilevels = 0; r->max_ilevel = 0;
     if (r->lvl_y) r->lvl_dirty = 1;          /* cleared lazily: pictures without ordered tasks never touch the maps */
     return 0;
 }
@@ -115,7 +115,7 @@ ovhip_rec_itask_add_(ovhip_recorder *r, const ovhip_itask *in, uint16_t extra_le
     ovhip_itask t = *in;
     const int w = 1 << t.log2_w, h = 1 << t.log2_h;
     int m = extra_level, k;
-    const int cs = t.kind == OVHIP_IT_CHROMA || t.kind == OVHIP_IT_RES_C;
+    const int cs = t.kind == OVHIP_IT_CHROMA || t.kind == OVHIP_IT_RES_C || t.kind == OVHIP_IT_IBC_C;
     scan_begin(r, t.x << cs, t.y << cs);
     if (t.kind == OVHIP_IT_REGION) r->scan_deps = r->region_deps;
     if (t.kind == OVHIP_IT_LUMA) {
@@ -153,6 +153,21 @@ ovhip_rec_itask_add_(ovhip_recorder *r, const ovhip_itask *in, uint16_t extra_le
         if (m >= 65534) return OVHIP_EUNSUP;
         t.level = (uint16_t)(m + 1);
         set_level(r, r->lvl_c, ux, uy, nx, ny, t.level);
+    } else if (t.kind == OVHIP_IT_IBC_L || t.kind == OVHIP_IT_IBC_C) {
+        /* intra block copy: reads the source block, rounded out to whole units (a unit has one writer, so a unit any sample of which
+         * is decoded is decoded as a whole), through max_level like every other reader: ctu_deps gets the left CTU */
+        const int sh = cs ? 1 : 2, rnd = (1 << sh) - 1;
+        uint16_t *map = cs ? r->lvl_c : r->lvl_y;
+        const int sx = t.x + OVHIP_ITASK_IBC_DX(t), sy = t.y + OVHIP_ITASK_IBC_DY(t);
+        if (sx < 0 || sy < 0) return OVHIP_EINVAL;
+        const int ux0 = sx >> sh, uy0 = sy >> sh, ux1 = (sx + w - 1) >> sh, uy1 = (sy + h - 1) >> sh;
+        k = max_level(r, map, ux0, uy0, ux1 - ux0 + 1, uy1 - uy0 + 1);
+        if (!k) t.flags |= OVHIP_IF_IBC_FREE;      /* every source unit comes from the unordered launches: nothing to wait for */
+        if (k > m) m = k;
+        if (m >= 65534) return OVHIP_EUNSUP;
+        t.level = (uint16_t)(m + 1);
+        set_level(r, map, t.x >> sh, t.y >> sh, (w + rnd) >> sh, (h + rnd) >> sh, t.level);
+        ++r->n_ibc;
     } else if (t.kind == OVHIP_IT_REGION) {
         if (m >= 65534) return OVHIP_EUNSUP;
         t.level = (uint16_t)(m + 1);          /* extra_level = what ovhip_rec_region_level_ found, minus one */
@@ -164,6 +179,8 @@ ovhip_rec_itask_add_(ovhip_recorder *r, const ovhip_itask *in, uint16_t extra_le
     if (t.level > r->max_ilevel) r->max_ilevel = t.level;
     return (int)r->n_itask++;
 }
+
+size_t ovhip_rec_ibc_tasks(const ovhip_recorder *r) { return r ? r->n_ibc : 0; }
 
 int
 ovhip_rec_set_ctu_size(ovhip_recorder *r, int32_t log2_ctu_s)
@@ -277,8 +294,8 @@ ovhip_rec_itasks_by_ctu(ovhip_recorder *r, int32_t log2_ctu_s, size_t *n, const 
     if (ovhip_rec_grow_(r, (void **)&r->itask_ctu, &r->cap_itask_ctu, nt, sizeof(ovhip_itask))) return NULL;
     uint32_t *start = r->ctu_count, *fill = r->ctu_count + nctu + 1;
     memset(start, 0, (nctu + 1) * sizeof(uint32_t));
-#define CTU_OF(t) ((size_t)(((t).kind == OVHIP_IT_CHROMA || (t).kind == OVHIP_IT_RES_C ? (t).y * 2 : (t).y) >> log2_ctu_s) * ncx \
-                   + (((t).kind == OVHIP_IT_CHROMA || (t).kind == OVHIP_IT_RES_C ? (t).x * 2 : (t).x) >> log2_ctu_s))
+#define CHROMA_OF(t) ((t).kind == OVHIP_IT_CHROMA || (t).kind == OVHIP_IT_RES_C || (t).kind == OVHIP_IT_IBC_C)
+#define CTU_OF(t) ((size_t)((CHROMA_OF(t) ? (t).y * 2 : (t).y) >> log2_ctu_s) * ncx + ((CHROMA_OF(t) ? (t).x * 2 : (t).x) >> log2_ctu_s))
     size_t used = 0;
     int precise = 1;                 /* every task carries the CTUs it reads ordered samples from, for this CTU size */
     for (size_t i = 0; i < nt; ++i) {
@@ -318,6 +335,7 @@ ovhip_rec_itasks_by_ctu(ovhip_recorder *r, int32_t log2_ctu_s, size_t *n, const 
             for (uint32_t k = 0; k < d->n; ++k) d->deps |= r->itask_ctu[d->first + k].ctu_deps & 0xf;
         }
 #undef CTU_OF
+#undef CHROMA_OF
     *n = nt; *ctus = r->ictu; *n_ctus = used;
     return r->itask_ctu;
 }

@@ -26,6 +26,7 @@ struct ovhip_recorder {
     ovhip_dbf_offsets dbf_off; int n_dbf_off;   /* distinct (beta, tc) offset pairs of the picture's slices */
     /* ordered tasks (ovvc_record_intra.c) */
     ovhip_itask *itask; size_t n_itask, cap_itask;
+    size_t n_ibc;                       /* OVHIP_IT_IBC_* among them: the picture job then takes the kernels built with the block-copy path */
     ovhip_itask *itask_sorted; size_t cap_isorted;
     uint32_t *ilevel_start; size_t cap_ilevel; uint32_t n_ilevels, max_ilevel;
     ovhip_itask *itask_ctu; size_t cap_itask_ctu;       /* grouped by CTU (ovhip_rec_itasks_by_ctu) */
@@ -47,6 +48,7 @@ struct ovhip_recorder {
 
 /* ovvc_calllog.c */
 void ovhip_calllog_tu_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_itask *il, const ovhip_itask *ic);
+void ovhip_calllog_tu_ibc_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_tu_desc *tu, const ovhip_ibc_desc *cu);
 void ovhip_calllog_isp_(ovhip_calllog *l, const ovhip_tu_state *st, const ovhip_isp_desc *cu);
 void ovhip_calllog_pu_(ovhip_calllog *l, const ovhip_pu_desc *pu);
 void ovhip_calllog_affine_(ovhip_calllog *l, const ovhip_affine_desc *cu);

@@ -229,6 +229,7 @@ ovhip_shim_flush_pending(OVCTUDec *c)
 {
     struct hip_entry *e = entry_of(c, 0);
     if (e && e->rec && e->ciip.live) ciip_close(e, c);
+    if (e && e->rec && e->ibc.live) ibc_orphan(e);
     if (e && e->rec && e->pend.kind) pend_close(e, c);
     if (e) e->aff_c_live = 0;
 }

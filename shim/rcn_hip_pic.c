@@ -335,12 +335,13 @@ begin_picture(struct hip_entry *e, const OVFrame *f, const struct RectEntryInfo 
      * into the picture's job, and the last one to end submits it (hip_alf_filter_line).  Entries of one picture on SEVERAL OVCTUDecs
      * (`-e 2`, ovthreads.c:93-114) would need their recorders merged: refused, the picture fails loudly. */
     int nw = 0, nh = 0, first = 1;
-    e->whole_pic_entry = 1;
+    e->whole_pic_entry = 1; e->entry_x0 = 0;
     if (einfo && e->key->part_ctx) {
         const int l2 = e->key->part_ctx->log2_ctu_s;
         const int pw = e->record_only ? e->pic_w : (int)f->width, ph = e->record_only ? e->pic_h : (int)f->height;
         nw = (pw + (1 << l2) - 1) >> l2; nh = (ph + (1 << l2) - 1) >> l2;
         first = !einfo->ctb_x && !einfo->ctb_y;
+        e->entry_x0 = einfo->ctb_x << l2;
         e->whole_pic_entry = first && einfo->nb_ctu_w == nw && einfo->nb_ctu_h == nh;
     }
     if (!first) {
@@ -350,7 +351,7 @@ begin_picture(struct hip_entry *e, const OVFrame *f, const struct RectEntryInfo 
             return;
         }
         e->lmcs_region_live = 0;
-        e->pend.kind = PEND_NONE; e->aff_c_live = 0; e->ciip.live = 0;
+        e->pend.kind = PEND_NONE; e->aff_c_live = 0; e->ciip.live = 0; e->ibc.live = 0;
         return;
     }
     e->frame = f;
@@ -366,7 +367,7 @@ begin_picture(struct hip_entry *e, const OVFrame *f, const struct RectEntryInfo 
     e->lmcs_region_live = 0;
     e->n_refined = 0; e->dmvr_done = 0; e->row_mark = 0;
     mode_begin(e);
-    e->ciip.live = 0;
+    e->ciip.live = 0; e->ibc.live = 0;
     if (e->rec && e->key->part_ctx) (void)ovhip_rec_set_ctu_size(e->rec, e->key->part_ctx->log2_ctu_s);
     if (e->n_ctu) { memset(e->sao, 0, e->n_ctu * sizeof(*e->sao)); memset(e->alf, 0, e->n_ctu * sizeof(*e->alf)); }
     if (e->record_only) { ovhip_rec_reset(e->rec); return; }

@@ -91,6 +91,11 @@ struct hip_entry {
     /* a CIIP CU whose planar tasks wait for the CU's transform unit (which carries their residual); closed without one by
      * the next slot call that is not that transform unit */
     struct { int live, x0, y0, log2_w, log2_h, has_c; ovhip_itask tl, tc; } ciip;
+    /* an intra-block-copy CU (rcn_ibc_l, then rcn_ibc_c unless luma only) whose blocks wait for the CU's transform tree, which always
+     * follows (vcl_transform_unit.c:1889-1959) and records prediction and residual as ONE ordered task per block; x0, y0: CTU-local.
+     * Any other slot call in between, or a tree of another CU, latches an error: no CU is left unpredicted silently */
+    struct { int live, x0, y0; ovhip_ibc_desc cu; } ibc;
+    int entry_x0;                        /* left edge (luma samples) of the rect entry being decoded                                     */
 };
 
 /* ---- where a frame thread's time goes inside the back-end (ovhip_shim_set_profile): every installed hook brackets itself; the
@@ -142,6 +147,7 @@ static inline uint64_t pic_tag(const OVPicture *p) { return (((uint64_t)p->cvs_i
 
 HIP_PRIV void pend_close(struct hip_entry *e, OVCTUDec *c);          /* the caller mode's */
 HIP_PRIV void ciip_close(struct hip_entry *e, OVCTUDec *c);          /* rcn_hip_rec.c */
+HIP_PRIV void ibc_orphan(struct hip_entry *e);                       /* rcn_hip_rec.c: the stashed IBC CU got no transform tree */
 
 /* every hook that is not part of the CU being collected closes it first */
 #define ENTER(c)                                               \
@@ -150,6 +156,7 @@ HIP_PRIV void ciip_close(struct hip_entry *e, OVCTUDec *c);          /* rcn_hip_
     PROF(e);                                                   \
     e->aff_c_live = 0;                                         \
     if (e->ciip.live) ciip_close(e, (OVCTUDec *)(c));          \
+    if (e->ibc.live) ibc_orphan(e);                            \
     if (e->pend.kind) pend_close(e, (OVCTUDec *)(c))
 
 /* ---- rcn_hip_rec.c */

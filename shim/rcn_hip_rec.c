@@ -267,6 +267,8 @@ jcbcr_qp_maps(OVCTUDec *c, int x0, int y0, int log2_w, int log2_h, uint8_t cbf_m
     }
 }
 
+static void tu_st_books(OVCTUDec *c, int x0, int y0, int log2_tb_w, int log2_tb_h, CUFlags cu_flags, uint8_t cbf_mask);
+
 /* rcn_tu_st (rcn_transform_tree.c:1228-1301) with the luma task rcn_intra_tu made before it (or a CIIP CU's two tasks) */
 static void
 tu_st_common(struct hip_entry *e, OVCTUDec *c, int x0, int y0, int log2_tb_w, int log2_tb_h, CUFlags cu_flags, uint8_t cbf_mask,
@@ -282,8 +284,14 @@ tu_st_common(struct hip_entry *e, OVCTUDec *c, int x0, int y0, int log2_tb_w, in
         task_c = &tc;
     }
     record_tu(e, c, 0, x0, y0, log2_tb_w, log2_tb_h, cu_flags, cbf_mask, tu, task_l, task_c);
-    /* what the scalar orchestrator leaves behind for deblocking (:1262-1267, :1299-1300; rcn_res_c / rcn_jcbcr
-     * :757-759, :793-795, :860-866) */
+    tu_st_books(c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, cbf_mask);
+}
+
+/* what the scalar orchestrator's rcn_tu_st leaves behind for deblocking (:1262-1267, :1299-1300; rcn_res_c / rcn_jcbcr
+ * :757-759, :793-795, :860-866) */
+static void
+tu_st_books(OVCTUDec *c, int x0, int y0, int log2_tb_w, int log2_tb_h, CUFlags cu_flags, uint8_t cbf_mask)
+{
     if (cbf_mask & 0x10) {
         fill_bs_map(&c->dbf_info.bs1_map, x0, y0, log2_tb_w, log2_tb_h);
         if ((cu_flags & flg_pred_mode_flag) && !(cu_flags & flg_intra_bdpcm_luma_flag)) fill_bs_map(&c->dbf_info.bs2_map, x0, y0, log2_tb_w, log2_tb_h);
@@ -337,6 +345,68 @@ hip_rcn_tu_c(OVCTUDec *const c, uint8_t x0, uint8_t y0, uint8_t log2_tb_w, uint8
     jcbcr_qp_maps(c, x0 << 1, y0 << 1, log2_tb_w + 1, log2_tb_h + 1, cbf_mask);
 }
 
+/* rcn_ibc_l / rcn_ibc_c (rcn_structures.h; rcn_ibc.c:8-139; callers vcl_coding_unit.c:1032-1066, :1088-1133, :1155-1205, :1257-1311):
+ * the slots only stash the CU.  Its blocks are recorded by the leaves of the transform tree that follows, one ordered task per block
+ * with the block's residual (ovhip_rec_tu_ibc): a prediction task of the whole CU followed by residual tasks would give a 4x4 unit
+ * two ordered writers.  Neither slot keeps any of the decoder's books in the reference (progress fields: the caller,
+ * vcl_coding_unit.c:953-991; bS / QP maps: the transform unit, restated by tu_st_common). */
+void
+ibc_orphan(struct hip_entry *e)
+{
+    e->ibc.live = 0;
+    latch(e, OVHIP_EINVAL, "an intra block copy (IBC) coding unit was not followed by its transform tree");
+}
+
+static void
+hip_rcn_ibc_l(OVCTUDec *const c, int16_t x0, int16_t y0, uint8_t log2_cu_w, uint8_t log2_cu_h, uint8_t log2_ctu_s, IBCMV mv)
+{
+    ENTER(c);
+    ovhip_ibc_desc *d = &e->ibc.cu;
+    memset(d, 0, sizeof(*d));
+    d->x0 = (uint16_t)((c->ctb_x << log2_ctu_s) + x0); d->y0 = (uint16_t)((c->ctb_y << log2_ctu_s) + y0);
+    d->log2_w = log2_cu_w; d->log2_h = log2_cu_h; d->log2_ctu = log2_ctu_s;
+    d->mv_x = (int16_t)mv.x; d->mv_y = (int16_t)mv.y; d->win_x0 = (uint16_t)e->entry_x0;
+    e->ibc.x0 = x0; e->ibc.y0 = y0; e->ibc.live = 1;
+    /* refused vectors fail the picture here, with the recorder's reason */
+    if (ovhip_rec_ibc_check(e->rec, d)) { e->ibc.live = 0; latch(e, OVHIP_EUNSUP, ovhip_rec_refusal(e->rec)); }
+}
+
+static void
+hip_rcn_ibc_c(OVCTUDec *const c, int16_t x0, int16_t y0, uint8_t log2_cu_w, uint8_t log2_cu_h, uint8_t log2_ctu_s, IBCMV mv)
+{
+    struct hip_entry *e = entry_of(c, 0);
+    if (!e || !e->rec) return;
+    PROF(e);
+    (void)log2_ctu_s;
+    if (e->err) return;
+    if (!e->ibc.live || e->ibc.x0 != x0 || e->ibc.y0 != y0 || e->ibc.cu.log2_w != log2_cu_w || e->ibc.cu.log2_h != log2_cu_h ||
+        e->ibc.cu.mv_x != mv.x || e->ibc.cu.mv_y != mv.y) {
+        e->ibc.live = 0;
+        latch(e, OVHIP_EINVAL, "rcn_ibc_c without the rcn_ibc_l call of the same coding unit before it");
+        return;
+    }
+    e->ibc.cu.has_chroma = 1;
+}
+
+/* a leaf of the stashed IBC CU's transform tree: the block's copy and its residual as one call (tree 0: rcn_tu_st, 1: rcn_tu_l) */
+static void
+record_tu_ibc(struct hip_entry *e, OVCTUDec *c, int tree, int x0, int y0, int log2_w, int log2_h, CUFlags cu_flags, uint8_t cbf_mask, const struct TUInfo *tu)
+{
+    const int l2 = c->part_ctx->log2_ctu_s;
+    ovhip_tu_state st;
+    ovhip_tu_desc d;
+    fill_tu_state(e, c, &st);
+    memset(&d, 0, sizeof(d));
+    d.x0 = (uint16_t)((c->ctb_x << l2) + x0); d.y0 = (uint16_t)((c->ctb_y << l2) + y0);
+    d.log2_tb_w = (uint8_t)log2_w; d.log2_tb_h = (uint8_t)log2_h; d.tree = (uint8_t)tree;
+    d.cbf_mask = cbf_mask; d.cu_flags = (uint16_t)cu_flags;
+    d.tr_skip_mask = tu->tr_skip_mask; d.cu_mts_flag = tu->cu_mts_flag; d.cu_mts_idx = tu->cu_mts_idx;
+    for (int k = 0; k < 3; ++k) { d.last_pos[k] = tu->tb_info[k].last_pos; d.sig_sb_map[k] = tu->tb_info[k].sig_sb_map; }
+    d.coef[0] = c->residual_cb + tu->pos_offset; d.coef[1] = c->residual_cr + tu->pos_offset; d.coef[2] = c->residual_y + tu->pos_offset;
+    const int r = ovhip_rec_tu_ibc(e->rec, &st, &d, &e->ibc.cu);
+    latch(e, r, r == OVHIP_EUNSUP ? ovhip_rec_refusal(e->rec) : "ovhip_rec_tu_ibc");
+}
+
 /* tmp.rcn_transform_tree (rcn_structures.h:464-468; rcn_transform_tree.c:1454-1518): the walker calls its leaves
  * directly, not through the table, so the whole walk is restated here around the leaf hooks. */
 static void
@@ -383,6 +453,33 @@ hip_rcn_transform_tree(OVCTUDec *const c, uint8_t x0, uint8_t y0, uint8_t log2_t
                 } else {
                     ciip_close(e, c);
                 }
+            }
+            /* the transform tree of the IBC CU stashed by rcn_ibc_l (+ rcn_ibc_c): every leaf inside the CU records its block; the
+             * stash ends with the leaf that holds the CU's last sample.  A tree of any other CU while one is stashed is an error */
+            int ibc_leaf = 0;
+            if (e->ibc.live) {
+                const int cw = 1 << e->ibc.cu.log2_w, ch = 1 << e->ibc.cu.log2_h;
+                if ((cu_flags & flg_ibc_flag) && x0 >= e->ibc.x0 && y0 >= e->ibc.y0 && x0 + (1 << log2_tb_w) <= e->ibc.x0 + cw &&
+                    y0 + (1 << log2_tb_h) <= e->ibc.y0 + ch) {
+                    ibc_leaf = 1;
+                } else ibc_orphan(e);
+            } else if ((cu_flags & flg_ibc_flag) && !e->err) {
+                latch(e, OVHIP_EINVAL, "transform tree of an intra block copy (IBC) coding unit without its rcn_ibc_l call");
+            }
+            if (ibc_leaf) {
+                /* an IBC CU takes the inter branch of the transform unit: rcn_tu_st, or rcn_tu_l for the luma-only CUs of a dual tree /
+                 * `share` (a cbf of 0 still records the block: it carries the prediction) */
+                if (c->transform_unit == (void *)&transform_unit_st) {
+                    record_tu_ibc(e, c, 0, x0, y0, log2_tb_w, log2_tb_h, cu_flags, tu->cbf_mask, tu);
+                    tu_st_books(c, x0, y0, log2_tb_w, log2_tb_h, cu_flags, tu->cbf_mask);
+                } else {
+                    record_tu_ibc(e, c, 1, x0, y0, log2_tb_w, log2_tb_h, cu_flags, tu->cbf_mask ? 0x10 : 0, tu);
+                    if (tu->cbf_mask) fill_bs_map(&c->dbf_info.bs1_map, x0, y0, log2_tb_w, log2_tb_h);
+                    fill_ctb_bound(&c->dbf_info, x0, y0, log2_tb_w, log2_tb_h);
+                }
+                if (x0 + (1 << log2_tb_w) == e->ibc.x0 + (1 << e->ibc.cu.log2_w) && y0 + (1 << log2_tb_h) == e->ibc.y0 + (1 << e->ibc.cu.log2_h))
+                    e->ibc.live = 0;
+                return;
             }
             if (cu_flags & flg_pred_mode_flag) {
                 /* rcn_intra_tu (:1384-1430): the prediction reads the progress field, then extends it */
@@ -459,18 +556,6 @@ static void
 hip_recon_isp_subtree_h(OVCTUDec *const c, unsigned int x0, unsigned int y0, unsigned int log2_cb_w, unsigned int log2_cb_h, uint8_t intra_mode,
                         const struct ISPTUInfo *const tu)
 { isp_subtree(c, x0, y0, log2_cb_w, log2_cb_h, intra_mode, tu, 0); }
-
-/* Tools the device path does not implement.  The scalar slots would reconstruct into the CTU scratch, which this back-end never
- * copies to the frame: the picture would be silently wrong.  Latch an error instead (the picture is then not flushed and
- * ovhip_shim_last_error() / the decoder log say why). */
-static void
-hip_rcn_ibc(OVCTUDec *const c, int16_t x0, int16_t y0, uint8_t log2_cu_w, uint8_t log2_cu_h, uint8_t log2_ctu_s, IBCMV mv)
-{
-    (void)x0; (void)y0; (void)log2_cu_w; (void)log2_cu_h; (void)log2_ctu_s; (void)mv;
-    struct hip_entry *e = entry_of(c, 0);
-    PROF(e);
-    if (e) latch(e, OVHIP_EUNSUP, "intra block copy (IBC) coding unit");
-}
 
 /* a CIIP CU without residual (no transform unit followed): its planar tasks alone */
 void
@@ -793,8 +878,8 @@ rec_install(struct RCNFunctions *f)
     f->tmp.rcn_tu_c  = &hip_rcn_tu_c;
     f->tmp.recon_isp_subtree_h = &hip_recon_isp_subtree_h;
     f->tmp.recon_isp_subtree_v = &hip_recon_isp_subtree_v;
-    f->rcn_ibc_l = &hip_rcn_ibc;
-    f->rcn_ibc_c = &hip_rcn_ibc;
+    f->rcn_ibc_l = &hip_rcn_ibc_l;
+    f->rcn_ibc_c = &hip_rcn_ibc_c;
     f->rcn_mcp = &hip_rcn_mcp;
     f->rcn_mcp_b = &hip_rcn_mcp_b;
     f->rcn_gpm_b = &hip_rcn_gpm_b;
