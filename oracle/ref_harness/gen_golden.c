@@ -1448,15 +1448,37 @@ harness_frame(int w, int h)
     return p->frame;
 }
 
-static void
-gen_sao(const char *dir)
+/* the pictures of sao*.ovg / alf*.ovg per CTU size: at 128 the three of the first fixtures; at 64 and 32 (reference mode only) three
+ * full CTU rows and a truncated one with a ragged width, a second ragged picture, a single truncated CTU row and a single row of
+ * exactly one CTU (the single-row quirk of rcn_sao_first_pix_rows).  No width is a multiple of the CTU or of a device tile. */
+enum { FLT_NPIC_MAX = 4 };
+struct flt_pics { int n; int w[FLT_NPIC_MAX], h[FLT_NPIC_MAX]; const char *name; };
+
+static const struct flt_pics *
+flt_pics_for(int alf, int log2_ctu)
 {
-    enum { NPIC = 3 };
-    static const int PW[NPIC] = { 304, 264, 136 }, PH[NPIC] = { 200, 264, 72 };
-    gfile g = gfile_open(dir, g_shim ? "shim_sao.ovg" : "sao.ovg");
+    static const struct flt_pics sao[3] = {
+        { 4, { 152, 104, 72, 72 },  { 104, 64, 24, 32 },  "sao_ctu32.ovg" },
+        { 4, { 304, 200, 136, 136 }, { 200, 136, 56, 64 }, "sao_ctu64.ovg" },
+        { 3, { 304, 264, 136 },      { 200, 264, 72 },     "sao.ovg" } };
+    static const struct flt_pics al[3] = {
+        { 4, { 152, 104, 72, 72 },  { 104, 64, 24, 32 },  "alf_ctu32.ovg" },
+        { 4, { 304, 200, 136, 136 }, { 200, 128, 56, 64 }, "alf_ctu64.ovg" },
+        { 3, { 304, 264, 136 },      { 200, 256, 72 },     "alf.ovg" } };
+    if (log2_ctu < 5 || log2_ctu > 7 || (g_shim && log2_ctu != 7)) { fprintf(stderr, "sao / alf: CTU size 2^%d is not generated%s\n", log2_ctu, g_shim ? " in shim mode" : ""); exit(1); }
+    return alf ? &al[log2_ctu - 5] : &sao[log2_ctu - 5];
+}
+
+static void
+gen_sao(const char *dir, int log2_ctu)
+{
+    const struct flt_pics *P = flt_pics_for(0, log2_ctu);
+    const int NPIC = P->n, *PW = P->w, *PH = P->h, ctu = 1 << log2_ctu;
+    gfile g = gfile_open(dir, g_shim ? "shim_sao.ovg" : P->name);
     g_seed = 0x266 + 3;
+    g_part.log2_ctu_s = log2_ctu;
     for (int pi = 0; pi < NPIC; ++pi) {
-        const int W = PW[pi], H = PH[pi], nx = (W + 127) / 128, ny = (H + 127) / 128;
+        const int W = PW[pi], H = PH[pi], nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu;
         OVFrame *f = harness_frame(W, H);
         /* sprinkle extremes so clipping and every band are hit */
         uint16_t *py = f->data[0];
@@ -1474,7 +1496,7 @@ gen_sao(const char *dir)
         if (g_shim) shim_bind(c, W, H, 0, 0);
         c->pic_w = W; c->pic_h = H;
         c->rcn_ctx.frame_start = f;
-        harness_alloc_filter_buffers(&c->rcn_ctx, nx, 3, 7);
+        harness_alloc_filter_buffers(&c->rcn_ctx, nx, 3, log2_ctu);
         c->sao_info.sao_luma_flag = 1; c->sao_info.sao_chroma_flag = 1; c->sao_info.chroma_format_idc = 1;
         SAOParamsCtu *prm = calloc(nx * ny, sizeof(*prm));
         ovhip_sao_ctu *mine = calloc(nx * ny, sizeof(*mine));
@@ -1523,8 +1545,9 @@ gen_sao(const char *dir)
         snprintf(nm, 32, "p%d_exp_cr", pi); gfile_array(&g, nm, T_U16, f->data[2], 2, d2);
         d2[0] = nx * ny; d2[1] = sizeof(ovhip_sao_ctu);
         snprintf(nm, 32, "p%d_params", pi); gfile_array(&g, nm, T_U8, mine, 2, d2);
-        fprintf(stderr, "sao.ovg: picture %d %dx%d (%d CTUs)\n", pi, W, H, nx * ny);
+        fprintf(stderr, "%s: picture %d %dx%d (%d CTUs of %d)\n", P->name, pi, W, H, nx * ny, ctu);
     }
+    g_part.log2_ctu_s = 7;
     if (g_shim) {
         /* a picture cut into TWO rect entries (tile columns) with each entry on its OWN OVCTUDec (entry threads: ovthreads.c:112-114),
          * record-only: the shim keeps one recorder per OVCTUDec.  The entry that starts the picture is taken; the one whose
@@ -1586,14 +1609,15 @@ rand_alf_aps(OVALFData *a)
 }
 
 static void
-gen_alf(const char *dir)
+gen_alf(const char *dir, int log2_ctu)
 {
-    enum { NPIC = 3 };
-    static const int PW[NPIC] = { 304, 264, 136 }, PH[NPIC] = { 200, 256, 72 };
-    gfile g = gfile_open(dir, g_shim ? "shim_alf.ovg" : "alf.ovg");
+    const struct flt_pics *P = flt_pics_for(1, log2_ctu);
+    const int NPIC = P->n, *PW = P->w, *PH = P->h, ctu = 1 << log2_ctu;
+    gfile g = gfile_open(dir, g_shim ? "shim_alf.ovg" : P->name);
     g_seed = 0x266 + 4;
+    g_part.log2_ctu_s = log2_ctu;
     for (int pi = 0; pi < NPIC; ++pi) {
-        const int W = PW[pi], H = PH[pi], nx = (W + 127) / 128, ny = (H + 127) / 128;
+        const int W = PW[pi], H = PH[pi], nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu;
         OVFrame *f = harness_frame(W, H);
         uint16_t *py = f->data[0];
         for (int i = 0; i < W * H; i += 13) py[i] = (uint16_t)rnd_range(0, 1023);
@@ -1610,10 +1634,15 @@ gen_alf(const char *dir)
         if (g_shim) shim_bind(c, W, H, 0, 0);
         c->pic_w = W; c->pic_h = H;
         c->rcn_ctx.frame_start = f;
-        harness_alloc_filter_buffers(&c->rcn_ctx, nx, 3, 7);
+        harness_alloc_filter_buffers(&c->rcn_ctx, nx, 3, log2_ctu);
         struct ALFInfo *ai = &c->alf_info;
         static OVALFData aps[5];
-        for (int i = 0; i < 5; ++i) rand_alf_aps(&aps[i]);
+        /* the first fixture draws five APSs per picture; the smaller-CTU ones draw them once and store the tables once (p0_*): the
+         * two luma tables are 125 KB a picture, and a committed file stays below 1 MiB */
+        const int own_aps = log2_ctu == 7 || pi == 0;
+        if (own_aps) for (int i = 0; i < 5; ++i) rand_alf_aps(&aps[i]);
+        /* one draw has to cover what three cover in the first fixture: a luma APS with and one without non-linear clipping, clipped chroma */
+        if (log2_ctu != 7) { aps[0].alf_luma_clip_flag = 1; aps[1].alf_luma_clip_flag = 0; aps[2].alf_chroma_clip_flag = 1; }
         ai->alf_luma_enabled_flag = ai->alf_cb_enabled_flag = ai->alf_cr_enabled_flag = 1;
         ai->cc_alf_cb_enabled_flag = ai->cc_alf_cr_enabled_flag = 1;
         ai->num_alf_aps_ids_luma = 2;
@@ -1627,6 +1656,7 @@ gen_alf(const char *dir)
             ALFParamsCtu *p = &ai->ctb_alf_params[i];
             p->ctb_alf_flag = rnd_range(0, 9) < 8 ? (rnd_range(0, 7) | (rnd_range(0, 2) ? 4 : 0)) : 0;
             p->ctb_alf_idx = rnd_range(0, 17);
+            if (log2_ctu != 7 && i % 3 == 0) p->ctb_alf_idx = 16 + ((i / 3) & 1);      /* every third CTU filters with an APS set, not a fixed one */
             p->cb_alternative = rnd_range(0, aps[2].alf_chroma_num_alt_filters_minus1);
             p->cr_alternative = rnd_range(0, aps[2].alf_chroma_num_alt_filters_minus1);
             ai->ctb_cc_alf_filter_idx[0][i] = rnd_range(0, 4);
@@ -1661,6 +1691,7 @@ gen_alf(const char *dir)
         snprintf(nm, 32, "p%d_exp_cr", pi); gfile_array(&g, nm, T_U16, f->data[2], 2, d2);
         d2[0] = nx * ny; d2[1] = sizeof(ovhip_alf_ctu);
         snprintf(nm, 32, "p%d_ctus", pi); gfile_array(&g, nm, T_U8, mine, 2, d2);
+        if (own_aps) {
         d2[0] = 24; d2[1] = OVHIP_ALF_LUMA_SET_SIZE;
         snprintf(nm, 32, "p%d_luma_coeff", pi); gfile_array(&g, nm, T_I16, ai->rcn_alf.filter_coeff_dec, 2, d2);
         snprintf(nm, 32, "p%d_luma_clip", pi); gfile_array(&g, nm, T_I16, ai->rcn_alf.filter_clip_dec, 2, d2);
@@ -1672,8 +1703,10 @@ gen_alf(const char *dir)
         memcpy(cc[1], aps[4].alf_cc_mapped_coeff[1], sizeof(cc[1]));
         uint32_t d3[3] = { 2, 4, 8 };
         snprintf(nm, 32, "p%d_cc_coeff", pi); gfile_array(&g, nm, T_I16, cc, 3, d3);
-        fprintf(stderr, "alf.ovg: picture %d %dx%d (%d CTUs)\n", pi, W, H, nx * ny);
+        }
+        fprintf(stderr, "%s: picture %d %dx%d (%d CTUs of %d)\n", P->name, pi, W, H, nx * ny, ctu);
     }
+    g_part.log2_ctu_s = 7;
     gfile_close(&g);
 }
 
@@ -2128,7 +2161,7 @@ main(int argc, char **argv)
         g_time = 1;
         for (int pass = 0; pass < 5; ++pass) {
             memset(g_ts, 0, sizeof(g_ts));
-            gen_itx(dir); gen_mc(dir); gen_dbf(dir); gen_sao(dir); gen_alf(dir); gen_intra(dir);
+            gen_itx(dir); gen_mc(dir); gen_dbf(dir); gen_sao(dir, 7); gen_alf(dir, 7); gen_intra(dir);
             for (int k = 0; k < TS_N; ++k) if (g_ts[k] > 0 && g_ts[k] < best[k]) best[k] = g_ts[k];
         }
         printf("{");
@@ -2144,8 +2177,13 @@ main(int argc, char **argv)
     if (!only || !strcmp(only, "lmcs")) gen_lmcs(dir);
     if (!only || !strcmp(only, "gpm")) gen_gpm(dir);
     if (!only || !strcmp(only, "dbf")) gen_dbf(dir);
-    if (!only || !strcmp(only, "sao")) gen_sao(dir);
-    if (!only || !strcmp(only, "alf")) gen_alf(dir);
+    if (!only || !strcmp(only, "sao")) gen_sao(dir, 7);
+    if (!only || !strcmp(only, "alf")) gen_alf(dir, 7);
+    /* SAO and ALF at the smaller CTU sizes: asked for by name only, each a run of its own (a generator seeds itself) */
+    if (only && !strcmp(only, "sao_ctu64")) gen_sao(dir, 6);
+    if (only && !strcmp(only, "sao_ctu32")) gen_sao(dir, 5);
+    if (only && !strcmp(only, "alf_ctu64")) gen_alf(dir, 6);
+    if (only && !strcmp(only, "alf_ctu32")) gen_alf(dir, 5);
     if ((!only || !strcmp(only, "intra")) && !g_shim) gen_intra(dir);
     if (!only || !strcmp(only, "intra_ctu")) gen_intra_ctu(dir);
     if (!only || !strcmp(only, "isp")) gen_isp(dir);

@@ -161,9 +161,9 @@ def dbf_cases():
     return out
 
 
-def sao_cases():
-    """[(deblocked HostPic, SAO params (structured array), expected HostPic)] from sao.ovg."""
-    g = golden_io.load("sao.ovg")
+def sao_cases(name="sao.ovg"):
+    """[(deblocked HostPic, SAO params (structured array), expected HostPic)] from sao.ovg (CTU 128), sao_ctu64.ovg or sao_ctu32.ovg."""
+    g = golden_io.load(name)
     out, pi = [], 0
     while f"p{pi}_in_y" in g:
         y = g[f"p{pi}_in_y"]
@@ -175,16 +175,17 @@ def sao_cases():
     return out
 
 
-def alf_cases():
-    """[(post-SAO HostPic, ALF tables dict, expected HostPic)] from alf.ovg."""
-    g = golden_io.load("alf.ovg")
+def alf_cases(name="alf.ovg"):
+    """[(post-SAO HostPic, ALF tables dict, expected HostPic)] from alf.ovg (CTU 128), alf_ctu64.ovg or alf_ctu32.ovg; the smaller-CTU
+    files hold one set of filter tables (p0_*) that all their pictures use."""
+    g = golden_io.load(name)
     out, pi = [], 0
     while f"p{pi}_in_y" in g:
         y = g[f"p{pi}_in_y"]
         h, w = y.shape
         alf = {"ctus": np.frombuffer(g[f"p{pi}_ctus"].tobytes(), dtype=capi.ALF_CTU_DTYPE).copy()}
         for k in ("luma_coeff", "luma_clip", "chroma_coeff", "chroma_clip", "cc_coeff"):
-            alf[k] = g[f"p{pi}_{k}"]
+            alf[k] = g[f"p{pi}_{k}"] if f"p{pi}_{k}" in g else g[f"p0_{k}"]
         out.append((HostPic(w, h, y, g[f"p{pi}_in_cb"], g[f"p{pi}_in_cr"]), alf,
                     HostPic(w, h, g[f"p{pi}_exp_y"], g[f"p{pi}_exp_cb"], g[f"p{pi}_exp_cr"])))
         pi += 1

@@ -2,6 +2,7 @@
 on the committed golden fixtures (tests/golden/*.ovg, made by oracle/ref_harness/gen_golden.c from
 the reference's own rcn_tu_st / rcn_tu_c / rcn_mcp_b* slots)."""
 import numpy as np
+import pytest
 
 import golden_cases
 import oracle_lib
@@ -199,6 +200,46 @@ def test_alf_oracle_matches_reference(built_lib):
             assert len(bad) == 0, f"alf picture {i} plane {name}: {len(bad)} samples differ, first at (y,x) {bad[:6].tolist()}"
 
 
+# (file, log2_ctu, picture sizes): three full CTU rows and a truncated one, a second ragged picture, a single truncated CTU row, a single
+# row of exactly one CTU; no width (luma or chroma) is a multiple of the CTU, the SAO tile (64) or the ALF tile (32)
+SAO_SMALL_CTU = (("sao_ctu64.ovg", 6, [(304, 200), (200, 136), (136, 56), (136, 64)]),
+                 ("sao_ctu32.ovg", 5, [(152, 104), (104, 64), (72, 24), (72, 32)]))
+ALF_SMALL_CTU = (("alf_ctu64.ovg", 6, [(304, 200), (200, 128), (136, 56), (136, 64)]),
+                 ("alf_ctu32.ovg", 5, [(152, 104), (104, 64), (72, 24), (72, 32)]))
+
+
+@pytest.mark.parametrize("name,log2_ctu,sizes", SAO_SMALL_CTU, ids=["ctu64", "ctu32"])
+def test_sao_oracle_matches_reference_small_ctu(built_lib, name, log2_ctu, sizes):
+    """The reference's SAO slots run with 64- and 32-sample CTUs (rcn_sao_first_pix_rows / rcn_sao_filter_line)."""
+    cases = golden_cases.sao_cases(name)
+    assert [(p.w, p.h) for p, _, _ in cases] == sizes
+    for i, (pic, prm, exp) in enumerate(cases):
+        ctu = 1 << log2_ctu
+        assert len(prm) == -(-pic.w // ctu) * -(-pic.h // ctu)
+        out = HostPic(pic.w, pic.h)
+        oracle_lib.sao(out, pic, prm, log2_ctu)
+        for name_, a, b, c in (("Y", out.y, exp.y, pic.y), ("Cb", out.cb, exp.cb, pic.cb), ("Cr", out.cr, exp.cr, pic.cr)):
+            assert (b != c).sum() > 20, "fixture does not exercise SAO"
+            bad = np.argwhere(a != b)
+            assert len(bad) == 0, f"{name} picture {i} plane {name_}: {len(bad)} samples differ, first at (y,x) {bad[:6].tolist()}"
+
+
+@pytest.mark.parametrize("name,log2_ctu,sizes", ALF_SMALL_CTU, ids=["ctu64", "ctu32"])
+def test_alf_oracle_matches_reference_small_ctu(built_lib, name, log2_ctu, sizes):
+    """The reference's rcn_alf_filter_line with 64- and 32-sample CTUs (virtual boundary at CTU row ctu - 4, chroma ctu / 2 - 2)."""
+    cases = golden_cases.alf_cases(name)
+    assert [(p.w, p.h) for p, _, _ in cases] == sizes
+    for i, (pic, alf, exp) in enumerate(cases):
+        ctu = 1 << log2_ctu
+        assert len(alf["ctus"]) == -(-pic.w // ctu) * -(-pic.h // ctu)
+        out = HostPic(pic.w, pic.h)
+        oracle_lib.alf(out, pic, alf, log2_ctu)
+        for name_, a, b, c in (("Y", out.y, exp.y, pic.y), ("Cb", out.cb, exp.cb, pic.cb), ("Cr", out.cr, exp.cr, pic.cr)):
+            assert (b != c).sum() > 100, "fixture does not exercise ALF"
+            bad = np.argwhere(a != b)
+            assert len(bad) == 0, f"{name} picture {i} plane {name_}: {len(bad)} samples differ, first at (y,x) {bad[:6].tolist()}"
+
+
 def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     """Where the compiled reference is available (this container: oracle/_ref built from /root/reference),
     re-running the harness reproduces every committed fixture byte for byte."""
@@ -210,9 +251,11 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     if not gen.exists() or not (root / "oracle" / "_ref" / "libovvcref.so").exists():
         pytest.skip("compiled reference not present")
     subprocess.check_call([str(gen), str(tmp_path)], stderr=subprocess.DEVNULL)
+    for only in ("sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32"):        # the smaller CTU sizes are runs of their own
+        subprocess.check_call([str(gen), str(tmp_path), only], stderr=subprocess.DEVNULL)
     # shim_*: test_shim_cpu.py; pipe* / tiles*: the chained streams of gen_pipe, test_pipe_cpu.py
     names = sorted(p.name for p in (root / "tests" / "golden").glob("*.ovg") if not p.name.startswith(("shim_", "pipe", "tiles")))
-    assert len(names) >= 9
+    assert len(names) >= 13
     for n in names:
         assert (tmp_path / n).read_bytes() == (root / "tests" / "golden" / n).read_bytes(), f"{n} differs from a fresh run of the reference"
 
