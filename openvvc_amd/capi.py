@@ -910,12 +910,22 @@ class Recorder:
         if r < 0:
             raise ValueError(f"ovhip_rec_append_raw({which}) -> {r}")
 
-    def dbf_planes(self) -> dict:
-        """Host copies of the picture-level edge planes + offsets."""
+    def dbf_planes_status(self):
+        """(status of ovhip_rec_dbf_planes, host copies of the planes or None): OVHIP_EUNSUP when the picture's CTUs carried
+        more than one (beta, tc) offset pair -- the dense planes hold one, the edge lists are the way then"""
         pl = DbfPlanes()
         r = self.lib.ovhip_rec_dbf_planes(self.h, C.byref(pl))
+        return r, (self._dbf_planes_copy(pl) if r >= 0 else None)
+
+    def dbf_planes(self) -> dict:
+        """Host copies of the picture-level edge planes + offsets."""
+        r, planes = self.dbf_planes_status()
         if r < 0:
             raise ValueError(f"ovhip_rec_dbf_planes -> {r}")
+        return planes
+
+    @staticmethod
+    def _dbf_planes_copy(pl) -> dict:
         out = {"w4": pl.w4, "h4": pl.h4, "beta_offset": pl.beta_offset, "tc_offset": pl.tc_offset}
         for name, shape in dbf_plane_shapes(pl.w4, pl.h4).items():
             n = shape[0] * shape[1]

@@ -143,6 +143,11 @@ class Context:
         self._chk(self.lib.ovhip_dbf_launch_edges(self.h, C.byref(pic.s), edges_v.ptr, edges_v.count, edges_h.ptr,
                                                   edges_h.count, beta_offset, tc_offset), "dbf_launch_edges")
 
+    def dbf_edges_ex(self, pic: "DevPic", edges_v: "DevBuf", edges_h: "DevBuf", offsets: "capi.DbfOffsets"):
+        """The same with the per-slice offset table of the recorder (capi.Recorder.dbf_edges): edge.pad selects the pair."""
+        self._chk(self.lib.ovhip_dbf_launch_edges_ex(self.h, C.byref(pic.s), edges_v.ptr, edges_v.count, edges_h.ptr,
+                                                     edges_h.count, C.byref(offsets)), "dbf_launch_edges_ex")
+
     def sao(self, dst: "DevPic", src: "DevPic", params: "DevBuf", log2_ctu: int = 7):
         self._chk(self.lib.ovhip_sao_launch(self.h, C.byref(dst.s), C.byref(src.s), params.ptr, log2_ctu), "sao_launch")
 

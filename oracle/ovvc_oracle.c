@@ -1010,6 +1010,31 @@ void oracle_dbf(const oracle_pic *pic, const ovhip_dbf_planes *pl)
     }
 }
 
+/* The same over the compact edge lists, in list order, each edge with the (beta, tc) offset pair its `pad` selects
+ * (ovhip_dbf_offsets): what a picture whose CTUs carry several pairs needs -- the dense planes hold one pair. */
+void oracle_dbf_edges(const oracle_pic *pic, const ovhip_dbf_edge *ev, uint32_t n_v, const ovhip_dbf_edge *eh, uint32_t n_h,
+                      const ovhip_dbf_offsets *offs)
+{
+    for (int dir = 0; dir < 2; ++dir) {
+        const ovhip_dbf_edge *e = dir ? eh : ev;
+        const uint32_t n = dir ? n_h : n_v;
+        for (uint32_t k = 0; k < n; ++k, ++e) {
+            const int v = e->word, oi = e->pad & (OVHIP_DBF_MAX_OFFSETS - 1);
+            if (e->comp == 0) {
+                dbf_lim lim = dbf_limits(v >> 8, v & 3, offs->tc[oi], offs->beta[oi]);
+                if (!(lim.tc || lim.beta)) continue;
+                uint16_t *p = pic->y + (e->uy * 4) * pic->stride_y + e->ux * 4;
+                dbf_luma_segment(p, dir ? pic->stride_y : 1, dir ? 1 : pic->stride_y, lim, (v >> 2) & 7, (v >> 5) & 7);
+            } else {
+                dbf_lim lim = dbf_limits(v >> 8, 1 + !!(v & OVHIP_DBF_C_BS2), offs->tc[oi], offs->beta[oi]);
+                uint16_t *p = (e->comp == 1 ? pic->cb : pic->cr) + (e->uy * 2) * pic->stride_c + e->ux * 2;
+                dbf_chroma_segment(p, dir ? pic->stride_c : 1, dir ? 1 : pic->stride_c, lim,
+                                   !!(v & OVHIP_DBF_C_LARGE), !!(v & OVHIP_DBF_C_CTB_B));
+            }
+        }
+    }
+}
+
 /* ====================================================================================
  * K13: sample adaptive offset
  * ================================================================================== */

@@ -1167,7 +1167,51 @@ snapshot_dbf(ovhip_dbf_ctu *o, const struct DBFInfo *d)
  * decoder's parse loop does (vcl_coding_unit.c:742, vcl_transform_unit.c:1093-1146, :1934-1957,
  * rcn_transform_tree.c fill_bs_map calls, drv_affine_mvp.c:3052-3082) and paints a DC offset per CU
  * into the unfiltered picture so that block edges are visible to the filter decisions */
-struct dbf_gen { struct DBFInfo *d; uint16_t *y, *cb, *cr; int stride, stride_c; int px, py; OVCTUDec *c; int bmode; struct IBCMVCtx *ibc; };
+struct dbf_gen { struct DBFInfo *d; uint16_t *y, *cb, *cr; int stride, stride_c; int px, py; OVCTUDec *c; int bmode; struct IBCMVCtx *ibc; int pic_w, pic_h; };
+
+/* second profile ("dbf_ends" -> dbf_ends.ovg): content, QPs, offsets and partition chosen so that the reference takes the long luma
+ * filters, both ends of the threshold tables, the bit-depth clips and the CTU-boundary strong chroma filter.  The first profile
+ * draws exactly the random numbers it always drew: every draw the second one adds sits behind this flag. */
+static int g_dbf_ends;
+
+static inline int clip_pix(int v) { return v < 0 ? 0 : v > 1023 ? 1023 : v; }
+
+/* "ends" content of one CU: absolute sample values, not an offset on a textured picture.  Most CUs are flat or a gentle ramp
+ * around a level that drifts slowly over the picture, so neighbouring CUs differ by a few codes (the long / strong decisions
+ * pass); some are noisy (off / weak); inside two vertical bands of the picture most CUs are pinned at 0..8 or 1015..1023. */
+static int
+paint_cu_ends(struct dbf_gen *g, int x, int y, int w, int h)
+{
+    const int ax = g->px + x, ay = g->py + y;
+    int mode = rnd_range(0, 99);                       /* < 75 flat, < 85 ramp, else noise */
+    if ((w >= 32 || h >= 32) && rnd_range(0, 9) < 7) mode = 0;     /* the blocks the long filters apply to: flat more often */
+    int pin = 0;
+    if (ax >= g->pic_w * 5 / 8 && ax < g->pic_w * 7 / 8 && rnd_range(0, 9) < 8) pin = ax < g->pic_w * 3 / 4 ? 1 : 2;
+    const int big = rnd_range(0, 7) == 0;              /* a step large enough for the tc gates of high QPs */
+    const int level = 420 + (ax >> 5) - (ay >> 5) + (big ? rnd_range(-70, 70) : rnd_range(-3, 3));
+    const int level_c = 500 - (ax >> 5) + (ay >> 4) + (big ? rnd_range(-40, 40) : rnd_range(-4, 4));
+    const int sx = rnd_range(-2, 2), sy = rnd_range(-2, 2), amp = rnd_range(4, 70);
+    const int pin_flat = rnd_range(0, 1), pin_v = rnd_range(0, 3);
+    for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
+        int v;
+        if (pin)            v = pin_flat ? pin_v : rnd_range(0, 8);
+        else if (mode < 75) v = level;
+        else if (mode < 85) v = level + ((i * sx + j * sy) >> 2);
+        else                v = level + rnd_range(-amp, amp);
+        if (pin == 2) v = 1023 - v;
+        g->y[(ay + j) * g->stride + ax + i] = clip_pix(v);
+    }
+    for (int j = 0; j < h / 2; ++j) for (int i = 0; i < w / 2; ++i) {
+        int o = (ay / 2 + j) * g->stride_c + ax / 2 + i, v, u;
+        if (pin)            { v = pin_flat ? pin_v : rnd_range(0, 8); u = pin_flat ? 3 - pin_v : rnd_range(0, 8); }
+        else if (mode < 75) { v = level_c; u = 1023 - level_c; }
+        else if (mode < 85) { v = level_c + ((i * sx + j * sy) >> 1); u = 1023 - v; }
+        else                { v = level_c + rnd_range(-amp / 2, amp / 2); u = 1023 - level_c + rnd_range(-amp / 2, amp / 2); }
+        if (pin == 2) { v = 1023 - v; u = 1023 - u; }
+        g->cb[o] = clip_pix(v); g->cr[o] = clip_pix(u);
+    }
+    return pin;
+}
 
 /* B-slice mode: the CU's motion goes into inter_ctx->mv_ctx0/1 (maps + 34x34 vectors, PB_POS_IN_BUF layout) the way
  * update_mv_ctx_b does; the MV-based bS pre-pass inside rcn_dbf_ctu then derives bS 1 itself */
@@ -1200,15 +1244,18 @@ gen_cu(struct dbf_gen *g, int x, int y, int w, int h)
 {
     struct DBFInfo *d = g->d;
     int l2w = 31 - __builtin_clz(w), l2h = 31 - __builtin_clz(h);
-    int qp = rnd_range(18, 50);
-    int intra = rnd_range(0, 9) == 0;
-    int affine = !intra && w >= 16 && h >= 16 && rnd_range(0, 5) == 0;
+    const int ends = g_dbf_ends;
+    int qp = ends ? (rnd_range(0, 2) ? rnd_range(28, 63) : rnd_range(0, 63)) : rnd_range(18, 50);   /* ends: all of 0..63, the upper part more often */
+    int intra = ends ? rnd_range(0, 4) == 0 : rnd_range(0, 9) == 0;
+    int affine = !intra && w >= 16 && h >= 16 && rnd_range(0, 5) <= (ends && g->px + x < g->pic_w / 2 ? 4 : 0);   /* ends: affine CUs side by side in the left part: (5, 5) */
     int off_y = rnd_range(-40, 40), off_c = rnd_range(-24, 24);
-    for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
+    if (ends && (w >= 32 || h >= 32) && rnd_range(0, 9) < 6) qp = rnd_range(30, 63);   /* large blocks: more often a QP with tc > 0 */
+    if (ends && paint_cu_ends(g, x, y, w, h)) qp = rnd_range(40, 63);      /* pinned CUs: a QP at which the weak filter is on */
+    else for (int j = 0; j < h; ++j) for (int i = 0; i < w; ++i) {
         int v = g->y[(g->py + y + j) * g->stride + g->px + x + i] + off_y;
         g->y[(g->py + y + j) * g->stride + g->px + x + i] = v < 0 ? 0 : v > 1023 ? 1023 : v;
     }
-    for (int j = 0; j < h / 2; ++j) for (int i = 0; i < w / 2; ++i) {
+    if (!ends) for (int j = 0; j < h / 2; ++j) for (int i = 0; i < w / 2; ++i) {
         int o = ((g->py + y) / 2 + j) * g->stride_c + (g->px + x) / 2 + i;
         int v = g->cb[o] + off_c; g->cb[o] = v < 0 ? 0 : v > 1023 ? 1023 : v;
         v = g->cr[o] - off_c;     g->cr[o] = v < 0 ? 0 : v > 1023 ? 1023 : v;
@@ -1234,8 +1281,11 @@ gen_cu(struct dbf_gen *g, int x, int y, int w, int h)
         fill_ctb_bound(d, x + tx, y + ty, tl2w, tl2h);
         fill_ctb_bound_c(d, x + tx, y + ty, tl2w, tl2h);
         dbf_fill_qp_map(&d->qp_map_y, x + tx, y + ty, tl2w, tl2h, qp);
-        dbf_fill_qp_map(&d->qp_map_cb, x + tx, y + ty, tl2w, tl2h, qp - rnd_range(0, 3));
-        dbf_fill_qp_map(&d->qp_map_cr, x + tx, y + ty, tl2w, tl2h, qp - rnd_range(0, 3));
+        /* "ends": the chroma QPs cover 0..63 as well, up to 9 away from the luma QP on either side */
+        int qp_cb = ends ? qp + rnd_range(-9, 9) : qp - rnd_range(0, 3), qp_cr = ends ? qp + rnd_range(-9, 9) : qp - rnd_range(0, 3);
+        if (ends) { qp_cb = qp_cb < 0 ? 0 : qp_cb > 63 ? 63 : qp_cb; qp_cr = qp_cr < 0 ? 0 : qp_cr > 63 ? 63 : qp_cr; }
+        dbf_fill_qp_map(&d->qp_map_cb, x + tx, y + ty, tl2w, tl2h, qp_cb);
+        dbf_fill_qp_map(&d->qp_map_cr, x + tx, y + ty, tl2w, tl2h, qp_cr);
         if (rnd_range(0, 1)) fill_bs_map(&d->bs1_map, x + tx, y + ty, tl2w, tl2h);          /* cbf luma */
         if (rnd_range(0, 2) == 0) fill_bs_map(&d->bs1_map_cb, x + tx, y + ty, tl2w, tl2h);  /* cbf cb   */
         if (rnd_range(0, 2) == 0) fill_bs_map(&d->bs1_map_cr, x + tx, y + ty, tl2w, tl2h);  /* cbf cr   */
@@ -1255,7 +1305,8 @@ gen_part(struct dbf_gen *g, int x, int y, int w, int h, int lim_w, int lim_h)
     }
     int m = w > h ? w : h;
     static const int p_split[8] = { 0, 0, 0, 15, 45, 65, 85, 95 };   /* % by log2(max dim): 8->15 .. 128->95 */
-    if (m > 4 && rnd_range(0, 99) < p_split[31 - __builtin_clz(m)]) {
+    static const int p_split_ends[8] = { 0, 0, 0, 10, 25, 40, 80, 97 };   /* blocks of 32 and more on both sides of many edges */
+    if (m > 4 && rnd_range(0, 99) < (g_dbf_ends ? p_split_ends : p_split)[31 - __builtin_clz(m)]) {
         int k = rnd_range(0, 3);
         if (k < 2 && w == h && w > 4) { gen_part(g, x, y, w / 2, h / 2, lim_w, lim_h); gen_part(g, x + w / 2, y, w / 2, h / 2, lim_w, lim_h);
                                         gen_part(g, x, y + h / 2, w / 2, h / 2, lim_w, lim_h); gen_part(g, x + w / 2, y + h / 2, w / 2, h / 2, lim_w, lim_h); }
@@ -1266,13 +1317,28 @@ gen_part(struct dbf_gen *g, int x, int y, int w, int h, int lim_w, int lim_h)
     gen_cu(g, x, y, w, h);
 }
 
+/* ends = 1: the second profile (g_dbf_ends above), reference mode only.  Its pictures are smaller (a fixture file stays below
+ * 1 MiB) and their CTUs carry (beta, tc) offset pairs from a per-picture table, as if every CTU began a new slice: picture 0 has
+ * 3 x 3 CTUs with 8 distinct pairs (the 9th CTU has the first one's again), picture 1 2 x 2 CTUs with 3, picture 2 (B slice) a single pair so that the dense planes exist. */
 static void
-gen_dbf(const char *dir)
+gen_dbf(const char *dir, int ends)
 {
     enum { NPIC = 3 };
-    static const int PW[NPIC] = { 304, 264, 256 }, PH[NPIC] = { 200, 136, 192 };     /* picture 2: B slice, motion-derived bS */
-    gfile g = gfile_open(dir, g_shim ? "shim_dbf.ovg" : "dbf.ovg");
-    g_seed = 0x266 + 2;
+    static const int PW0[NPIC] = { 304, 264, 256 }, PH0[NPIC] = { 200, 136, 192 };     /* picture 2: B slice, motion-derived bS */
+    static const int PW1[NPIC] = { 264, 136, 136 }, PH1[NPIC] = { 264, 200, 136 };
+    /* (beta_offset, tc_offset) = sh_luma_{beta,tc}_offset_div2 * 2: both ends of -24..24, mixed signs.  Every pair leaves a window of
+     * QPs in which both limits are above 0 (with the reference's tables (24, -24) has none, (-24, 24) only QP 40 and 41: beta is 0 from
+     * index 64 on), so that every pair index can be seen to change samples */
+    static const int8_t pairs[NPIC][8][2] = {
+        { { -24, 12 }, { 20, -20 }, { 0, 0 }, { 24, 24 }, { -24, -24 }, { 6, -2 }, { -10, 14 }, { 12, -24 } },
+        { { 24, 24 }, { -12, 8 }, { 4, -20 } },
+        { { 2, 4 } } };
+    static const int n_pairs[NPIC] = { 8, 3, 1 };
+    const int *PW = ends ? PW1 : PW0, *PH = ends ? PH1 : PH0;
+    if (ends && g_shim) return;
+    g_dbf_ends = ends;
+    gfile g = gfile_open(dir, ends ? "dbf_ends.ovg" : g_shim ? "shim_dbf.ovg" : "dbf.ovg");
+    g_seed = 0x266 + 2 + 47 * ends;     /* ends: a seed at which the reference's pictures meet the census tests/test_dbf_spec_cpu.py asserts */
     for (int pi = 0; pi < NPIC; ++pi) {
         const int W = PW[pi], H = PH[pi], nx = (W + 127) / 128, ny = (H + 127) / 128;
         uint16_t *y = malloc(W * H * 2), *cb = malloc(W * H / 2), *cr = malloc(W * H / 2);
@@ -1323,7 +1389,8 @@ gen_dbf(const char *dir)
                 dbf_load_info(d, &L, 7, 0);
                 for (int cx = 0; cx < nx; ++cx) {
                     int ctu_w = W - cx * 128 < 128 ? W - cx * 128 : 128, ctu_h = H - cy * 128 < 128 ? H - cy * 128 : 128;
-                    struct dbf_gen gg = { d, ty, tcb, tcr, W, W / 2, cx * 128, cy * 128, c, bmode, &ibc };
+                    struct dbf_gen gg = { d, ty, tcb, tcr, W, W / 2, cx * 128, cy * 128, c, bmode, &ibc, W, H };
+                    if (ends) { const int8_t *pr = pairs[pi][(cy * nx + cx) % n_pairs[pi]]; d->beta_offset = pr[0]; d->tc_offset = pr[1]; }
                     if (bmode) {
                         /* fresh CTU motion context; the 1-unit border (row above / column left) stands in for what
                          * the line buffers would bring in from the neighbouring CTUs */
@@ -1408,9 +1475,10 @@ gen_dbf(const char *dir)
         if (bmode) { d2[1] = (uint32_t)(b_mv.n / n_ctu); snprintf(nm, 32, "p%d_mvctx", pi); gfile_array(&g, nm, T_U8, b_mv.data, 2, d2); }
         size_t diff = 0;
         for (int i = 0; i < W * H; ++i) diff += y[i] != y0[i];
-        fprintf(stderr, "dbf.ovg: picture %d %dx%d, %u CTUs, %zu luma samples changed by the reference\n", pi, W, H, n_ctu, diff);
+        fprintf(stderr, "%s: picture %d %dx%d, %u CTUs, %zu luma samples changed by the reference\n", ends ? "dbf_ends.ovg" : "dbf.ovg", pi, W, H, n_ctu, diff);
     }
     gfile_close(&g);
+    g_dbf_ends = 0;
 }
 
 
@@ -2161,7 +2229,7 @@ main(int argc, char **argv)
         g_time = 1;
         for (int pass = 0; pass < 5; ++pass) {
             memset(g_ts, 0, sizeof(g_ts));
-            gen_itx(dir); gen_mc(dir); gen_dbf(dir); gen_sao(dir, 7); gen_alf(dir, 7); gen_intra(dir);
+            gen_itx(dir); gen_mc(dir); gen_dbf(dir, 0); gen_sao(dir, 7); gen_alf(dir, 7); gen_intra(dir);
             for (int k = 0; k < TS_N; ++k) if (g_ts[k] > 0 && g_ts[k] < best[k]) best[k] = g_ts[k];
         }
         printf("{");
@@ -2176,7 +2244,9 @@ main(int argc, char **argv)
     if (!only || !strcmp(only, "mca")) gen_mca(dir);
     if (!only || !strcmp(only, "lmcs")) gen_lmcs(dir);
     if (!only || !strcmp(only, "gpm")) gen_gpm(dir);
-    if (!only || !strcmp(only, "dbf")) gen_dbf(dir);
+    if (!only || !strcmp(only, "dbf")) gen_dbf(dir, 0);
+    /* deblocking's second profile (table ends, long filters, several offset pairs): by name only, like the CTU sizes below */
+    if (only && !strcmp(only, "dbf_ends")) gen_dbf(dir, 1);
     if (!only || !strcmp(only, "sao")) gen_sao(dir, 7);
     if (!only || !strcmp(only, "alf")) gen_alf(dir, 7);
     /* SAO and ALF at the smaller CTU sizes: asked for by name only, each a run of its own (a generator seeds itself) */

@@ -141,9 +141,12 @@ def check_rects(pic: HostPic, rects, exp, what=""):
     assert not bad, f"{what}: {len(bad)} / {len(rects)} rectangles differ, first: {bad[:5]}"
 
 
-def dbf_cases():
-    """[(unfiltered HostPic, planes dict from the recorder, expected HostPic)] from dbf.ovg."""
-    g = golden_io.load("dbf.ovg")
+def dbf_cases(name="dbf.ovg"):
+    """[(unfiltered HostPic, planes dict from the recorder, expected HostPic)] from dbf.ovg or dbf_ends.ovg.  Beside the planes
+    the dict holds "edges" (the lists the recorder emitted + its offset table) and "meta": {"planes_status": what
+    ovhip_rec_dbf_planes returned, "ctu_offsets": [(ctb_x, ctb_y, beta_offset, tc_offset)]}.  A picture whose CTUs carry several
+    (beta, tc) offset pairs has no dense planes (ovhip_rec_dbf_planes refuses them): its dict holds "edges" and "meta" only."""
+    g = golden_io.load(name)
     out = []
     pi = 0
     while f"p{pi}_in_y" in g:
@@ -151,9 +154,13 @@ def dbf_cases():
         h, w = y.shape
         rec = capi.Recorder(w, h)
         mv = g.get(f"p{pi}_mvctx")                    # B-slice picture: motion contexts for the MV-based bS pre-pass
+        ctus = np.frombuffer(g[f"p{pi}_ctus"].tobytes(), capi.DBF_CTU_DTYPE)
         for k, raw in enumerate(g[f"p{pi}_ctus"]):
             rec.dbf_ctu(raw.tobytes(), mv[k].tobytes() if mv is not None else None)
-        planes = rec.dbf_planes()
+        status, planes = rec.dbf_planes_status()
+        planes = planes if planes is not None else {}
+        planes["meta"] = {"planes_status": status,
+                          "ctu_offsets": [(int(c["ctb_x"]), int(c["ctb_y"]), int(c["beta_offset"]), int(c["tc_offset"])) for c in ctus]}
         planes["edges"] = [rec.dbf_edges(0), rec.dbf_edges(1)]        # what the per-CTU recorder emitted directly
         out.append((HostPic(w, h, y, g[f"p{pi}_in_cb"], g[f"p{pi}_in_cr"]), planes,
                     HostPic(w, h, g[f"p{pi}_exp_y"], g[f"p{pi}_exp_cb"], g[f"p{pi}_exp_cr"])))

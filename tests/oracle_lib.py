@@ -48,6 +48,8 @@ def lib():
         _lib.oracle_mca.restype = None
         _lib.oracle_dbf.argtypes = [C.POINTER(OPic), vp]
         _lib.oracle_dbf.restype = None
+        _lib.oracle_dbf_edges.argtypes = [C.POINTER(OPic), vp, C.c_uint32, vp, C.c_uint32, vp]
+        _lib.oracle_dbf_edges.restype = None
         _lib.oracle_sao.argtypes = [C.POINTER(OPic), C.POINTER(OPic), vp, C.c_int]
         _lib.oracle_sao.restype = None
         _lib.oracle_alf_run.argtypes = [C.POINTER(OPic), C.POINTER(OPic), vp]
@@ -197,6 +199,13 @@ def dbf(pic: HostPic, planes: dict):
     s = pic.struct()
     pl, keep = dbf_planes_struct(planes)
     lib().oracle_dbf(C.byref(s), C.addressof(pl))
+
+
+def dbf_edges(pic: HostPic, edges_v: np.ndarray, edges_h: np.ndarray, offsets):
+    """edges_*: capi.DBF_EDGE_DTYPE in the order to filter; offsets: capi.DbfOffsets."""
+    s = pic.struct()
+    edges_v, edges_h = np.ascontiguousarray(edges_v), np.ascontiguousarray(edges_h)
+    lib().oracle_dbf_edges(C.byref(s), edges_v.ctypes.data, len(edges_v), edges_h.ctypes.data, len(edges_h), C.addressof(offsets))
 
 
 def sao(dst: HostPic, src: HostPic, params: np.ndarray, log2_ctu: int = 7):

@@ -201,6 +201,29 @@ def test_dbf_gpu_matches_reference(ctx):
                 assert len(bad) == 0, f"dbf HIP ({mode}) vs reference, picture {i} plane {name}: {len(bad)} differ, first {bad[:6].tolist()}"
 
 
+def test_dbf_ends_gpu_matches_reference(ctx):
+    """dbf_ends.ovg (long filters, both ends of the threshold tables, 8 / 3 / 1 offset pairs per picture; the census is asserted
+    in test_dbf_spec_cpu.py): the recorder's edge lists with its offset table on every picture, the dense planes where the
+    picture has a single pair."""
+    n_dense = 0
+    for i, (pic, planes, exp) in enumerate(golden_cases.dbf_cases("dbf_ends.ovg")):
+        (ev, offs), (eh, _) = planes["edges"]
+        modes = ["edges"] + (["planes"] if planes["meta"]["planes_status"] == 0 else [])
+        for mode in modes:
+            d = ctx.upload_pic(pic.y, pic.cb, pic.cr)
+            if mode == "planes":
+                ctx.dbf(d, engine.DevDbfPlanes(ctx, planes))
+                n_dense += 1
+            else:
+                ctx.dbf_edges_ex(d, ctx.upload(ev), ctx.upload(eh), offs)
+            ctx.sync()
+            y, cb, cr = d.download()
+            for name, a, b in (("Y", y, exp.y), ("Cb", cb, exp.cb), ("Cr", cr, exp.cr)):
+                bad = np.argwhere(a != b)
+                assert len(bad) == 0, f"dbf_ends HIP ({mode}) vs reference, picture {i} plane {name}: {len(bad)} differ, first {bad[:6].tolist()}"
+    assert n_dense == 1
+
+
 def test_sao_gpu_matches_reference(ctx):
     for i, (pic, prm, exp) in enumerate(golden_cases.sao_cases()):
         src = ctx.upload_pic(pic.y, pic.cb, pic.cr)
