@@ -48,7 +48,10 @@ __device__ __attribute__((aligned(4))) const signed char g_fc[32][4] = {
     { -2, 10, 58, -2 }, { -1, 7, 60, -2 }, { 0, 4, 62, -2 }, { 0, 2, 63, -1 } };
 
 #define IR_NEG  64                       // room for the negative-angle extension of the main arm
-#define IR_LEN  (IR_NEG + 2 * 64 + 4 + 24)   // + reference line offset + wide-angle tail
+// wide-angle tail: a 1:16 block on reference line 2 reads (long side / short side) * (mrl + 1) = 48 samples past its main arm, all copies
+// of the arm's last sample (fill_ref_*_0_mref, "Padding for wide angle": 4x64 mode 53 / 64x4 mode 15, angle 512); 24 covered 1:8 only
+#define IR_TAIL 48
+#define IR_LEN  (IR_NEG + 2 * 64 + 4 + IR_TAIL)   // + reference line offset + wide-angle tail
 struct IntraLds {
     uint16_t abv[IR_LEN], lft[IR_LEN];   // index IR_NEG = outermost corner sample of the reference line
     uint16_t fabv[IR_LEN], flft[IR_LEN]; // [1 2 1]-smoothed copies
@@ -109,7 +112,7 @@ __device__ __forceinline__ void fetch_refs(IntraLds &s, const Acc acc, int x0, i
     const bool none = !corner && !avl_abv && !avl_lft;
     const int la = min(mrl + avl_abv * unit, na - 1), ll = min(mrl + avl_lft * unit, nl - 1);   // last available sample per arm
     const int ax1 = cx + mrl + 1, ay1 = cy, lx1 = cx, ly1 = cy + mrl + 1;   // first sample of each arm's block part
-    // (na + 24 and nl + 24 are at most 2 * 64 + 4 + 24 = 156: three samples per lane and arm.)  ALL loads of both arms go out before the
+    // (na + IR_TAIL and nl + IR_TAIL are at most 2 * 64 + 3 + 48 = 179: three samples per lane and arm.)  ALL loads of both arms go out before the
     // first one is waited for -- a loop that loads, waits and stores per iteration costs one memory round trip per iteration and arm
     // Lanes past the end of an arm load its last sample again: every load is unconditional (a load inside a divergent branch is
     // waited for at the branch's end, which serialises the round trips), the coordinates are selected without branches.
@@ -141,8 +144,8 @@ __device__ __forceinline__ void fetch_refs(IntraLds &s, const Acc acc, int x0, i
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int k = lane + 64 * i;
-        if (k < na + 24) s.abv[IR_NEG + k] = (uint16_t)va[i];
-        if (k < nl + 24) s.lft[IR_NEG + k] = (uint16_t)vl[i];
+        if (k < na + IR_TAIL) s.abv[IR_NEG + k] = (uint16_t)va[i];
+        if (k < nl + IR_TAIL) s.lft[IR_NEG + k] = (uint16_t)vl[i];
     }
 }
 
@@ -985,8 +988,8 @@ __device__ __forceinline__ bool fetch_refs_tagged(IntraLds &s, const uint16_t *p
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int k = lane + 64 * i;
-        if (k < na + 24) s.abv[IR_NEG + k] = (uint16_t)(v[2 * i] & 0x7fff);
-        if (k < nl + 24) s.lft[IR_NEG + k] = (uint16_t)(v[2 * i + 1] & 0x7fff);
+        if (k < na + IR_TAIL) s.abv[IR_NEG + k] = (uint16_t)(v[2 * i] & 0x7fff);
+        if (k < nl + IR_TAIL) s.lft[IR_NEG + k] = (uint16_t)(v[2 * i + 1] & 0x7fff);
     }
     return ok;
 }

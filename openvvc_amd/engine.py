@@ -127,6 +127,45 @@ class Context:
                                                   regions.ptr if regions else None, C.byref(luts) if luts is not None else None,
                                                   scales.ptr if scales else None, log2_ctu, sync.ptr, epoch, None), "intra_ctu_launch")
 
+    def intra_flow_words(self, w: int, h: int) -> int:
+        """uint32 words of the state block of intra_flow() for a w x h picture"""
+        return int(self.lib.ovhip_intra_flow_words(w, h))
+
+    def intra_flow_items(self, tasks: np.ndarray) -> np.ndarray:
+        """Items of the flow launch (ovhip_intra_flow_items) of the LEVEL-SORTED host task list: one uint32 per (task, strip, plane).
+        A list the flow path refuses is an error, never an empty launch."""
+        tasks = np.ascontiguousarray(tasks)
+        items = np.zeros(32 * len(tasks), np.uint32)                  # at most 16 strips x 2 planes per task
+        n = int(self.lib.ovhip_intra_flow_items(tasks.ctypes.data, len(tasks), items.ctypes.data, len(items)))
+        if len(tasks) and not n:
+            raise EngineError("intra_flow_items: the flow launch cannot take this task list")
+        return items[:n]
+
+    def intra_flow(self, pic: "DevPic", res: "DevPic", tasks: "DevBuf", n_tasks: int, items: "DevBuf", n_items: int, state: "DevBuf",
+                   epoch: int, regions: "DevBuf | None" = None, luts=None, scales: "DevBuf | None" = None, log2_ctu: int = 7,
+                   prepare: int = 1, n_workers: int = 0):
+        """The ordered pass as a flow launch (k_intra_flow).  tasks / items: device copies of the level-sorted list and of its
+        intra_flow_items().  state: a zeroed device buffer of intra_flow_words() uint32 that the caller owns; epoch: fresh and
+        != 0 for every launch on the same state.  n_workers: 0 = one workgroup per item.  Word 0 of `state` is the abort code:
+        the owner looks at it after the launch (intra_flow_abort)."""
+        self._chk(self.lib.ovhip_intra_flow_launch(self.h, C.byref(pic.s), C.byref(res.s), tasks.ptr, n_tasks, items.ptr, n_items,
+                                                   regions.ptr if regions else None, C.byref(luts) if luts is not None else None,
+                                                   scales.ptr if scales else None, log2_ctu, state.ptr, epoch, None, prepare, n_workers),
+                  "intra_flow_launch")
+
+    def intra_flow_abort(self, state: "DevBuf") -> int:
+        """Word 0 of a flow launch's state block: 0, or the code of the wait that expired (the picture is then incomplete)."""
+        self.sync()
+        word = np.zeros(1, np.uint32)
+        self._chk(self.lib.ovhip_d2h(self.h, word.ctypes.data, state.ptr, 4), "d2h")
+        self.sync()
+        return int(word[0])
+
+    def intra_flow_untag(self, pic: "DevPic", tasks: "DevBuf", n: int, with_luma: int = 1):
+        """Clears the hand-over bit (bit 15) in the blocks the n ordered tasks wrote (k_flow_untag): after the picture's flow
+        launches, before anything else reads the picture.  with_luma = 0: chroma blocks only."""
+        self._chk(self.lib.ovhip_intra_flow_untag_launch(self.h, C.byref(pic.s), tasks.ptr, n, with_luma), "intra_flow_untag_launch")
+
     def tmvp_cells(self, units: "DevBuf", n: int, refined: "DevBuf", log2_ctu: int, nb_ctb_w: int) -> np.ndarray:
         out = self.alloc(4 * n * capi.TMVP_CELL_DTYPE.itemsize)
         self._chk(self.lib.ovhip_tmvp_cells_launch(self.h, units.ptr, n, refined.ptr, log2_ctu, nb_ctb_w, out.ptr), "tmvp_cells")

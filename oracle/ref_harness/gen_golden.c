@@ -1792,25 +1792,129 @@ gen_alf(const char *dir, int log2_ctu)
 #define IN_OX 128
 #define IN_OY 128
 
+/* what gen_intra and gen_intra_cells share: the decoder context, the picture and one case through a slot */
+struct intra_gen {
+    OVCTUDec *c;
+    struct OVRCNCtx *r;
+    const struct OVBuffInfo *cb;
+    gbuf b_task, b_eoff, b_exp;
+    uint32_t n_cases;
+};
+static uint16_t g_in_py[IN_W * IN_H], g_in_pcb[(IN_W / 2) * (IN_H / 2)], g_in_pcr[(IN_W / 2) * (IN_H / 2)];
+
+/* the picture of intra.ovg (its seed): both generators predict on the same samples */
+static void
+intra_gen_init(struct intra_gen *G)
+{
+    memset(G, 0, sizeof(*G));
+    G->b_task.type = T_U8; G->b_eoff.type = T_U32; G->b_exp.type = T_U16;
+    g_seed = 0x266 + 555;
+    G->c = ref_new_ctudec(0, 0);
+    G->c->rcn_funcs.rcn_attach_ctu_buff(&G->c->rcn_ctx, 7, 1);
+    G->cb = &G->c->rcn_ctx.ctu_buff;
+    G->r = &G->c->rcn_ctx;
+    fill_plane(g_in_py, IN_W, IN_H, IN_W); fill_plane(g_in_pcb, IN_W / 2, IN_H / 2, IN_W / 2); fill_plane(g_in_pcr, IN_W / 2, IN_H / 2, IN_W / 2);
+    for (int i = 0; i < IN_W * IN_H; i += 41) g_in_py[i] = (i & 1) ? 1023 : 0;
+}
+
+/* kind: 0 luma regular, 1 luma MRL, 2 MIP, 3 chroma regular, 4 chroma LM, 5 luma BDPCM, 6 chroma BDPCM (dir: vertical).
+ * (x0, y0): inside the CTU, in samples of the plane; corner / avl_abv / avl_lft: what the progress bit-fields say (units from the corner) */
+static void
+intra_case(struct intra_gen *G, int kind, int l2w, int l2h, int mode, int dir, int mrl, int mip_tr, int x0, int y0, int corner, int avl_abv, int avl_lft)
+{
+    OVCTUDec *c = G->c;
+    struct OVRCNCtx *r = G->r;
+    const struct OVBuffInfo *cb = G->cb;
+    const uint16_t *py = g_in_py, *pcb = g_in_pcb, *pcr = g_in_pcr;
+    const int chroma = kind == 3 || kind == 4 || kind == 6;
+    const int w = 1 << l2w, h = 1 << l2h, unit = chroma ? 2 : 4;
+    ovhip_itask t;
+    memset(&t, 0, sizeof(t));
+    /* progress bit-fields: bit (unit + 1) of hfield[row above] / vfield[column left]; bit `unit` = the corner */
+    struct CTUBitField *pf = chroma ? &r->progress_field_c : &r->progress_field;
+    memset(pf, 0, sizeof(*pf));
+    const int xu = x0 / unit, yu = y0 / unit;
+    pf->hfield[yu] = (((uint64_t)corner) | ((((uint64_t)1 << avl_abv) - 1) << 1)) << xu;
+    pf->vfield[xu] = (((uint64_t)corner) | ((((uint64_t)1 << avl_lft) - 1) << 1)) << yu;
+    /* CTU scratch <- picture: rows -1 .. 131, columns -128 .. 195 (what the buffer holds around the CTU) */
+    for (int j = -1; j < 132; ++j) for (int i = -128; i < 196; ++i) cb->y[j * cb->stride + i] = py[(IN_OY + j) * IN_W + IN_OX + i];
+    for (int j = -1; j < 66; ++j) for (int i = -64; i < 98; ++i) {
+        cb->cb[j * cb->stride_c + i] = pcb[(IN_OY / 2 + j) * (IN_W / 2) + IN_OX / 2 + i];
+        cb->cr[j * cb->stride_c + i] = pcr[(IN_OY / 2 + j) * (IN_W / 2) + IN_OX / 2 + i]; }
+    CUFlags fl = flg_pred_mode_flag;
+    t.x = (uint16_t)((chroma ? IN_OX / 2 : IN_OX) + x0); t.y = (uint16_t)((chroma ? IN_OY / 2 : IN_OY) + y0);
+    t.log2_w = l2w; t.log2_h = l2h; t.kind = chroma ? OVHIP_IT_CHROMA : OVHIP_IT_LUMA;
+    t.mode = (uint8_t)mode; t.flags = corner ? OVHIP_IF_CORNER : 0;
+    t.avl_lft = avl_lft; t.avl_abv = avl_abv; t.mrl_idx = mrl; t.level = 1;
+    const double t_in = g_time ? now_s() : 0.0;
+    switch (kind) {
+    case 0: c->rcn_funcs.intra_pred(r, cb, mode, x0, y0, l2w, l2h, fl); break;
+    case 1: c->rcn_funcs.intra_pred_mrl(c, cb->y, cb->stride, mode, x0, y0, l2w, l2h, mrl); break;
+    case 2: t.flags |= OVHIP_IF_MIP | (mip_tr ? OVHIP_IF_MIP_TR : 0);
+            c->rcn_funcs.mip.rcn_intra_mip(r, x0, y0, l2w, l2h, (uint8_t)(mode | (mip_tr << 7))); break;
+    case 5: fl |= flg_intra_bdpcm_luma_flag | (dir ? flg_intra_bdpcm_luma_dir : 0);
+            t.flags |= OVHIP_IF_BDPCM | (dir ? OVHIP_IF_BDPCM_VER : 0); t.mode = 0;
+            c->rcn_funcs.intra_pred(r, cb, 0, x0, y0, l2w, l2h, fl); break;
+    case 6: fl |= flg_intra_bdpcm_chroma_flag | (dir ? flg_intra_bdpcm_chroma_dir : 0);
+            t.flags |= OVHIP_IF_BDPCM | (dir ? OVHIP_IF_BDPCM_VER : 0); t.mode = 0;
+            c->rcn_funcs.intra_pred_c(r, 0, x0, y0, l2w, l2h, fl); break;
+    case 4: {
+        /* the LM modes read their own availability: abv / lft "any unit" flags, MDLM: contiguous units
+         * over w + min(w, h) (h + min(w, h)) samples (rcn_intra_cclm.c:56-68, :770-776, :843-849) */
+        const int any_abv = avl_abv > 0, any_lft = avl_lft > 0;
+        int need_a = (w + (w < h ? w : h)) / 2, need_l = (h + (w < h ? w : h)) / 2;
+        t.avl_abv = mode == 69 ? (avl_abv < need_a ? avl_abv : need_a) : any_abv;
+        t.avl_lft = mode == 68 ? (avl_lft < need_l ? avl_lft : need_l) : any_lft;
+        c->rcn_funcs.intra_pred_c(r, mode, x0, y0, l2w, l2h, fl); break; }
+    default: c->rcn_funcs.intra_pred_c(r, mode, x0, y0, l2w, l2h, fl); break;
+    }
+    if (g_time) g_ts[TS_INTRA] += now_s() - t_in;
+    uint32_t eoff[2] = { 0, 0 };
+    if (!chroma) { eoff[0] = (uint32_t)G->b_exp.n; dump_rect(&G->b_exp, cb->y, cb->stride, x0, y0, w, h); }
+    else { eoff[0] = (uint32_t)G->b_exp.n; dump_rect(&G->b_exp, cb->cb, cb->stride_c, x0, y0, w, h);
+           eoff[1] = (uint32_t)G->b_exp.n; dump_rect(&G->b_exp, cb->cr, cb->stride_c, x0, y0, w, h); }
+    gbuf_push(&G->b_task, &t, sizeof(t)); gbuf_push(&G->b_eoff, eoff, 2);
+    G->n_cases++;
+}
+
+/* intra.ovg is kept small: big blocks take every third (fifth) mode plus the structurally special ones, big MIP blocks every other
+ * matrix.  != 0: gen_intra leaves the cell (kind, shape, mi) out -- gen_intra_cells then writes it. */
+static int
+intra_thinned(int kind, int l2w, int l2h, int mi)
+{
+    const int w = 1 << l2w, h = 1 << l2h;
+    const int key_mode = mi <= 2 || mi == 18 || mi == 34 || mi == 50 || mi == 66;
+    const int thin = w * h >= 2048 ? 5 : w * h >= 512 ? 3 : (kind == 1 && w * h >= 128 ? 2 : 1);
+    if ((kind == 0 || kind == 1 || kind == 3) && !key_mode && (mi % thin) != ((l2w * 3 + l2h) % thin)) return 1;
+    if (kind == 2 && w * h >= 1024 && (mi & 1) != ((l2w + l2h) & 1)) return 1;
+    return 0;
+}
+
+/* matrices of a MIP block (the standard's three size classes) */
+static int mip_matrices(int l2w, int l2h) { return (l2w == 2 && l2h == 2) ? 16 : (l2h == 2 || l2w == 2 || (l2h <= 3 && l2w <= 3)) ? 8 : 6; }
+
+static void
+intra_write(struct intra_gen *G, const char *dir, const char *name, int with_pic)
+{
+    gfile g = gfile_open(dir, name);
+    uint32_t d2[2] = { IN_H, IN_W };
+    if (with_pic) {
+        gfile_array(&g, "pic_y", T_U16, g_in_py, 2, d2);
+        d2[0] = IN_H / 2; d2[1] = IN_W / 2;
+        gfile_array(&g, "pic_cb", T_U16, g_in_pcb, 2, d2); gfile_array(&g, "pic_cr", T_U16, g_in_pcr, 2, d2);
+    }
+    d2[0] = G->n_cases; d2[1] = sizeof(ovhip_itask); gfile_array(&g, "task", T_U8, G->b_task.data, 2, d2);
+    d2[1] = 2; gfile_array(&g, "exp_off", T_U32, G->b_eoff.data, 2, d2);
+    gfile_buf(&g, "exp", &G->b_exp);
+    gfile_close(&g);
+    fprintf(stderr, "%s: %u cases, %zu expected samples\n", name, G->n_cases, G->b_exp.n);
+}
+
 static void
 gen_intra(const char *dir)
 {
-    gbuf b_task = { .type = T_U8 }, b_eoff = { .type = T_U32 }, b_exp = { .type = T_U16 };
-    uint32_t n_cases = 0;
-    g_seed = 0x266 + 555;
-    OVCTUDec *c = ref_new_ctudec(0, 0);
-    c->rcn_funcs.rcn_attach_ctu_buff(&c->rcn_ctx, 7, 1);
-    const struct OVBuffInfo *cb = &c->rcn_ctx.ctu_buff;
-    struct OVRCNCtx *r = &c->rcn_ctx;
-    static uint16_t py[IN_W * IN_H], pcb[(IN_W / 2) * (IN_H / 2)], pcr[(IN_W / 2) * (IN_H / 2)];
-    fill_plane(py, IN_W, IN_H, IN_W); fill_plane(pcb, IN_W / 2, IN_H / 2, IN_W / 2); fill_plane(pcr, IN_W / 2, IN_H / 2, IN_W / 2);
-    for (int i = 0; i < IN_W * IN_H; i += 41) py[i] = (i & 1) ? 1023 : 0;
-    /* CTU scratch <- picture: rows -1 .. 131, columns -128 .. 195 (what the buffer holds around the CTU) */
-    #define LOAD_SCRATCH() do { \
-        for (int j = -1; j < 132; ++j) for (int i = -128; i < 196; ++i) cb->y[j * cb->stride + i] = py[(IN_OY + j) * IN_W + IN_OX + i]; \
-        for (int j = -1; j < 66; ++j) for (int i = -64; i < 98; ++i) { \
-            cb->cb[j * cb->stride_c + i] = pcb[(IN_OY / 2 + j) * (IN_W / 2) + IN_OX / 2 + i]; \
-            cb->cr[j * cb->stride_c + i] = pcr[(IN_OY / 2 + j) * (IN_W / 2) + IN_OX / 2 + i]; } } while (0)
+    struct intra_gen G;
+    intra_gen_init(&G);
 
     /* kind: 0 luma regular, 1 luma MRL, 2 MIP, 3 chroma regular, 4 chroma LM, 5 luma BDPCM, 6 chroma BDPCM */
     for (int kind = 0; kind < 7; ++kind) {
@@ -1825,18 +1929,12 @@ gen_intra(const char *dir)
                 int n_modes = kind == 0 || kind == 3 ? 67 : kind == 1 ? 67 : kind == 2 ? 32 : kind == 4 ? 3 : 2;
                 int reps = kind == 0 ? (w * h <= 256 ? 3 : 2) : kind == 4 ? (w * h >= 256 ? 3 : 6) : 1;
                 for (int mi = 0; mi < n_modes; ++mi) {
-                    /* keep the fixture small: big blocks take every third (fifth) mode plus the structurally special ones */
-                    const int key_mode = mi <= 2 || mi == 18 || mi == 34 || mi == 50 || mi == 66;
-                    const int thin = w * h >= 2048 ? 5 : w * h >= 512 ? 3 : (kind == 1 && w * h >= 128 ? 2 : 1);
-                    if ((kind == 0 || kind == 1 || kind == 3) && !key_mode && (mi % thin) != ((l2w * 3 + l2h) % thin)) continue;
-                    if (kind == 2 && w * h >= 1024 && (mi & 1) != ((l2w + l2h) & 1)) continue;
+                    if (intra_thinned(kind, l2w, l2h, mi)) continue;
                     for (int rep = 0; rep < (w * h >= 512 && kind != 4 ? 1 : reps); ++rep) {
-                        ovhip_itask t;
-                        memset(&t, 0, sizeof(t));
                         int mode = mi, mrl = 0, mip_tr = 0;
                         if (kind == 1) { if (mode == 0 || mode == 1) { if (rep) continue; } mrl = 1 + ((mi + rep) & 1); }
                         if (kind == 2) {
-                            const int n_mip = (l2w == 2 && l2h == 2) ? 16 : (l2h == 2 || l2w == 2 || (l2h <= 3 && l2w <= 3)) ? 8 : 6;
+                            const int n_mip = mip_matrices(l2w, l2h);
                             mode = mi % n_mip; mip_tr = (mi / n_mip) & 1;
                             if (mi >= 2 * n_mip) continue;
                         }
@@ -1862,64 +1960,106 @@ gen_intra(const char *dir)
                                              avl_lft = rnd_range(h / unit < max_lft ? h / unit : max_lft, max_lft); }
                         else if (pat == 6) { avl_abv = w / unit < max_abv ? w / unit : max_abv; avl_lft = h / unit < max_lft ? h / unit : max_lft; }
                         else if (pat == 7 && kind != 1) { corner = 0; }                          /* a slice starts at the CTU above */
-                        /* progress bit-fields: bit (unit + 1) of hfield[row above] / vfield[column left]; bit `unit` = the corner */
-                        struct CTUBitField *pf = chroma ? &r->progress_field_c : &r->progress_field;
-                        memset(pf, 0, sizeof(*pf));
-                        const int xu = x0 / unit, yu = y0 / unit;
-                        pf->hfield[yu] = (((uint64_t)corner) | ((((uint64_t)1 << avl_abv) - 1) << 1)) << xu;
-                        pf->vfield[xu] = (((uint64_t)corner) | ((((uint64_t)1 << avl_lft) - 1) << 1)) << yu;
-                        LOAD_SCRATCH();
-                        CUFlags fl = flg_pred_mode_flag;
-                        t.x = (uint16_t)((chroma ? IN_OX / 2 : IN_OX) + x0); t.y = (uint16_t)((chroma ? IN_OY / 2 : IN_OY) + y0);
-                        t.log2_w = l2w; t.log2_h = l2h; t.kind = chroma ? OVHIP_IT_CHROMA : OVHIP_IT_LUMA;
-                        t.mode = (uint8_t)mode; t.flags = corner ? OVHIP_IF_CORNER : 0;
-                        t.avl_lft = avl_lft; t.avl_abv = avl_abv; t.mrl_idx = mrl; t.level = 1;
-                        const double t_in = g_time ? now_s() : 0.0;
-                        switch (kind) {
-                        case 0: c->rcn_funcs.intra_pred(r, cb, mode, x0, y0, l2w, l2h, fl); break;
-                        case 1: c->rcn_funcs.intra_pred_mrl(c, cb->y, cb->stride, mode, x0, y0, l2w, l2h, mrl); break;
-                        case 2: t.flags |= OVHIP_IF_MIP | (mip_tr ? OVHIP_IF_MIP_TR : 0);
-                                c->rcn_funcs.mip.rcn_intra_mip(r, x0, y0, l2w, l2h, (uint8_t)(mode | (mip_tr << 7))); break;
-                        case 5: fl |= flg_intra_bdpcm_luma_flag | (mi ? flg_intra_bdpcm_luma_dir : 0);
-                                t.flags |= OVHIP_IF_BDPCM | (mi ? OVHIP_IF_BDPCM_VER : 0); t.mode = 0;
-                                c->rcn_funcs.intra_pred(r, cb, 0, x0, y0, l2w, l2h, fl); break;
-                        case 6: fl |= flg_intra_bdpcm_chroma_flag | (mi ? flg_intra_bdpcm_chroma_dir : 0);
-                                t.flags |= OVHIP_IF_BDPCM | (mi ? OVHIP_IF_BDPCM_VER : 0); t.mode = 0;
-                                c->rcn_funcs.intra_pred_c(r, 0, x0, y0, l2w, l2h, fl); break;
-                        case 4: {
-                            /* the LM modes read their own availability: abv / lft "any unit" flags, MDLM: contiguous units
-                             * over w + min(w, h) (h + min(w, h)) samples (rcn_intra_cclm.c:56-68, :770-776, :843-849) */
-                            const int any_abv = avl_abv > 0, any_lft = avl_lft > 0;
-                            int need_a = (w + (w < h ? w : h)) / 2, need_l = (h + (w < h ? w : h)) / 2;
-                            t.avl_abv = mode == 69 ? (avl_abv < need_a ? avl_abv : need_a) : any_abv;
-                            t.avl_lft = mode == 68 ? (avl_lft < need_l ? avl_lft : need_l) : any_lft;
-                            c->rcn_funcs.intra_pred_c(r, mode, x0, y0, l2w, l2h, fl); break; }
-                        default: c->rcn_funcs.intra_pred_c(r, mode, x0, y0, l2w, l2h, fl); break;
-                        }
-                        if (g_time) g_ts[TS_INTRA] += now_s() - t_in;
-                        uint32_t eoff[2] = { 0, 0 };
-                        if (!chroma) { eoff[0] = (uint32_t)b_exp.n; dump_rect(&b_exp, cb->y, cb->stride, x0, y0, w, h); }
-                        else { eoff[0] = (uint32_t)b_exp.n; dump_rect(&b_exp, cb->cb, cb->stride_c, x0, y0, w, h);
-                               eoff[1] = (uint32_t)b_exp.n; dump_rect(&b_exp, cb->cr, cb->stride_c, x0, y0, w, h); }
-                        gbuf_push(&b_task, &t, sizeof(t)); gbuf_push(&b_eoff, eoff, 2);
-                        n_cases++;
+                        intra_case(&G, kind, l2w, l2h, mode, mi, mrl, mip_tr, x0, y0, corner, avl_abv, avl_lft);
                     }
                 }
             }
         }
     }
-    gfile g = gfile_open(dir, "intra.ovg");
-    uint32_t d2[2] = { IN_H, IN_W };
-    gfile_array(&g, "pic_y", T_U16, py, 2, d2);
-    d2[0] = IN_H / 2; d2[1] = IN_W / 2;
-    gfile_array(&g, "pic_cb", T_U16, pcb, 2, d2); gfile_array(&g, "pic_cr", T_U16, pcr, 2, d2);
-    d2[0] = n_cases; d2[1] = sizeof(ovhip_itask); gfile_array(&g, "task", T_U8, b_task.data, 2, d2);
-    d2[1] = 2; gfile_array(&g, "exp_off", T_U32, b_eoff.data, 2, d2);
-    gfile_buf(&g, "exp", &b_exp);
-    gfile_close(&g);
-    fprintf(stderr, "intra.ovg: %u cases, %zu expected samples\n", n_cases, b_exp.n);
+    intra_write(&G, dir, "intra.ovg", 1);
 }
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * intra_cells_*.ovg : the cells intra.ovg does not reach, from the same slots on the same picture (the files hold tasks and
+ * expected blocks only; the picture is intra.ovg's).  Everything is enumerated, positions included -- nothing is drawn:
+ *   - every (shape, mode) of luma regular, MRL (modes 1..66) and chroma regular, every (shape, matrix, transposed) of MIP that
+ *     gen_intra thinned out (intra_thinned), at full availability;
+ *   - every (kind, shape, class) of luma regular, chroma regular, MIP and LM / MDLM over the five availability classes
+ *     0 none, 1 above only, 2 left only, 3 both without the corner, 4 both with the corner -- with modes that READ the arm in
+ *     question (planar: both arms; 34: the corner sample on the block's diagonal), so that the expected block differs from what
+ *     full availability predicts;
+ *   - every (mode, class) of luma regular (8x8) and chroma regular (4x4);
+ *   - MRL at the left edge of a picture, tile or slice: avl_lft = 0, no corner, rows above available (not the CTU's first row),
+ *     every shape with mrl_idx 1 and 2, modes 18 (reads only the left arm) and 34.  fill_ref_left_0_mref pads that arm with the
+ *     first sample of the row above (rcn_fill_ref.c:290-310), all of it written.
+ * Left out: MRL WITHOUT the rows above (classes 0 and 2).  fill_ref_above_0_mref writes 2w + 1 samples there (its "FIXME",
+ * rcn_fill_ref.c:558-582) and the prediction reads up to mrl_idx + 1 past them: stack memory nothing wrote.  A decoder never
+ * gets there (MRL is not signalled on a CTU's first row; rows above inside the CTU are decoded).
+ * Files are cut below 1 MiB: <kind>_<nn>. */
+#define CELLS_MAX_EXP 480000          /* expected samples per file */
+struct cells_out { struct intra_gen *G; const char *dir, *kind; int part; };
+
+static void
+cells_flush(struct cells_out *o)
+{
+    char name[64];
+    if (!o->G->n_cases) return;
+    snprintf(name, sizeof(name), "intra_cells_%s_%02d.ovg", o->kind, o->part++);
+    intra_write(o->G, o->dir, name, 0);
+    o->G->b_task.n = o->G->b_eoff.n = o->G->b_exp.n = 0; o->G->n_cases = 0;
+}
+
+/* one enumerated case: class cls, arms as long as they get (ext 0) or as long as the block (ext 1), position k of the shape */
+static void
+cells_case(struct cells_out *o, int kind, int l2w, int l2h, int mode, int mrl, int mip_tr, int cls, int ext, int k)
+{
+    const int chroma = kind == 3 || kind == 4;
+    const int w = 1 << l2w, h = 1 << l2h, unit = chroma ? 2 : 4, ctu = chroma ? 64 : 128;
+    const int nx = (ctu - w) / unit + 1, ny = (ctu - h) / unit + 1;
+    int x0 = unit * ((7 * k + 3 * l2w + 5 * l2h + 11 * cls) % nx), y0 = unit * ((5 * k + 7 * l2w + 3 * l2h + 13 * cls + 1) % ny);
+    if (kind == 1) y0 = 4 * (1 + (5 * k + l2w + cls) % ((ctu - h) / 4));         /* MRL: not the CTU's first row, rows above inside the picture */
+    if (kind == 4) {
+        /* LM: half of the cases on the CTU's first line (one luma row above instead of two); the others on no row that starts a
+         * CTU of 32 or 64 either (tests place the cases at those CTU sizes) */
+        if ((k + cls + l2w + l2h) & 1) y0 = 0;
+        else if ((2 * y0) % 32 == 0) y0 += y0 + 2 + h <= ctu ? 2 : -2;
+    }
+    int max_abv = 2 * w / unit, max_lft = 2 * h / unit;
+    const int cap_abv = ((chroma ? 96 : 192) - x0) / unit, cap_lft = ((chroma ? 64 : 128) - y0) / unit;
+    if (max_abv > cap_abv) max_abv = cap_abv;
+    if (max_lft > cap_lft) max_lft = cap_lft;
+    if (ext) { if (max_abv > w / unit) max_abv = w / unit; if (max_lft > h / unit) max_lft = h / unit; }
+    const int corner = cls == 4, avl_abv = (cls == 1 || cls >= 3) ? max_abv : 0, avl_lft = cls >= 2 ? max_lft : 0;
+    if (o->G->b_exp.n + (size_t)(chroma ? 2 : 1) * w * h > CELLS_MAX_EXP) cells_flush(o);
+    intra_case(o->G, kind, l2w, l2h, mode, 0, mrl, mip_tr, x0, y0, corner, avl_abv, avl_lft);
+}
+
+static void
+gen_intra_cells(const char *dir)
+{
+    struct intra_gen G;
+    intra_gen_init(&G);                       /* intra.ovg's picture */
+    g_seed = 0x266 + 556;                     /* (this generator's own; it draws nothing) */
+    static const char *names[5] = { "luma", "mrl", "mip", "chroma", "lm" };
+    for (int kind = 0; kind < 5; ++kind) {
+        struct cells_out o = { &G, dir, names[kind], 0 };
+        const int chroma = kind >= 3, lmin = chroma ? 1 : 2, lmax = chroma ? 5 : 6;
+        for (int l2w = lmin; l2w <= lmax; ++l2w) {
+            for (int l2h = lmin; l2h <= lmax; ++l2h) {
+                if (chroma && l2w + l2h < 3) continue;                   /* no 2x2 chroma blocks */
+                /* (a) the cells gen_intra thinned out */
+                if (kind == 0 || kind == 3) for (int m = 0; m < 67; ++m) { if (intra_thinned(kind, l2w, l2h, m)) cells_case(&o, kind, l2w, l2h, m, 0, 0, 4, m & 1, m); }
+                if (kind == 1) for (int m = 1; m < 67; ++m) { if (intra_thinned(kind, l2w, l2h, m)) cells_case(&o, kind, l2w, l2h, m, 1 + (m & 1), 0, 4, (m >> 1) & 1, m); }
+                if (kind == 2) {
+                    const int n_mip = mip_matrices(l2w, l2h);
+                    for (int mi = 0; mi < 2 * n_mip; ++mi) if (intra_thinned(kind, l2w, l2h, mi)) cells_case(&o, kind, l2w, l2h, mi % n_mip, 0, mi / n_mip, 4, mi & 1, mi);
+                }
+                /* (b), (d) every availability class, with modes that read the arm in question */
+                for (int cls = 0; cls < 5; ++cls) {
+                    if (kind == 0 || kind == 3) { cells_case(&o, kind, l2w, l2h, 0, 0, 0, cls, 0, cls); cells_case(&o, kind, l2w, l2h, 34, 0, 0, cls, 1, cls + 5); }
+                    if (kind == 2) cells_case(&o, kind, l2w, l2h, (l2w + 2 * l2h + cls) % mip_matrices(l2w, l2h), 0, cls & 1, cls, cls & 1, cls);
+                    if (kind == 4) for (int m = 67; m < 70; ++m) cells_case(&o, kind, l2w, l2h, m, 0, 0, cls, 0, m - 67 + 3 * cls);
+                }
+                /* (c) MRL at a left edge */
+                if (kind == 1) for (int mrl = 1; mrl <= 2; ++mrl) { cells_case(&o, kind, l2w, l2h, 18, mrl, 0, 1, 0, mrl); cells_case(&o, kind, l2w, l2h, 34, mrl, 0, 1, 1, mrl + 2); }
+            }
+        }
+        /* (b) every (mode, class) */
+        if (kind == 0) for (int m = 0; m < 67; ++m) for (int cls = 0; cls < 5; ++cls) cells_case(&o, kind, 3, 3, m, 0, 0, cls, (m + cls) & 1, m + cls);
+        if (kind == 3) for (int m = 0; m < 67; ++m) for (int cls = 0; cls < 5; ++cls) cells_case(&o, kind, 2, 2, m, 0, 0, cls, (m + cls) & 1, m + cls);
+        cells_flush(&o);
+    }
+}
 /* ---------------------------------------------------------------------------------------------------------------------
  * K12  whole intra CTUs through tmp.rcn_transform_tree (rcn_transform_tree.c:1454-1518 -> rcn_res_wrap -> rcn_intra_tu /
  *      rcn_tu_st / rcn_tu_l / rcn_tu_c): a random partition of the CTU at (128, 128), CUs in decoding order, every CU intra
@@ -2255,6 +2395,8 @@ main(int argc, char **argv)
     if (only && !strcmp(only, "alf_ctu64")) gen_alf(dir, 6);
     if (only && !strcmp(only, "alf_ctu32")) gen_alf(dir, 5);
     if ((!only || !strcmp(only, "intra")) && !g_shim) gen_intra(dir);
+    /* the cells intra.ovg does not reach: by name only, a run of its own */
+    if (only && !strcmp(only, "intra_cells") && !g_shim) gen_intra_cells(dir);
     if (!only || !strcmp(only, "intra_ctu")) gen_intra_ctu(dir);
     if (!only || !strcmp(only, "isp")) gen_isp(dir);
     return 0;

@@ -10,6 +10,7 @@ import pytest
 
 import golden_cases
 import golden_io
+import intra_cases
 import oracle_lib
 from oracle_lib import HostPic
 from openvvc_amd import capi, engine
@@ -160,47 +161,9 @@ def test_alf_refuses_ctu32(ctx, sao_small, alf_small):
 
 
 # ---------------------------------------------------------------------------------------------------------------- ordered intra pass
-BAND = 384            # a multiple of 128: a band's first row is a CTU row at every CTU size
-NB = 160              # cases per launch (ovhip_itask.y is 16 bits)
-
-
-def _intra_small_ctu(S):
-    """intra.ovg placed S luma rows lower in each band.  The reference's prediction slots depend on the CTU size only through CCLM's
-    ctu_first_line = !y0 (y0 relative to the fixture's 128-CTU at luma row 128): a block is on the first line of a CTU of size S iff its
-    row relative to that CTU is a multiple of S.  LM / MDLM cases for which the two differ are left out; those at y0 = 0 stay, and are
-    on a first line (row 128 + S) ONLY for a CTU of size S -- a kernel that ignores log2_ctu takes the two-row path there.
-    -> (tasks with y moved, exp_off, exp, base planes of one band, number left out, number of LM cases on such a first line)"""
-    g = golden_io.load("intra.ovg")
-    tasks = np.frombuffer(g["task"].tobytes(), dtype=capi.ITASK_DTYPE).copy()
-    H, W = g["pic_y"].shape
-    lm = (tasks["kind"] == capi.IT_CHROMA) & (tasks["mode"] >= 67)
-    y0 = 2 * tasks["y"].astype(np.int64) - 128                      # luma row relative to the fixture's CTU
-    keep = ~(lm & ((y0 == 0) != (y0 % S == 0)))
-    n_first = int((lm & (y0 == 0))[keep].sum())
-    tasks["y"] += np.where(tasks["kind"] == capi.IT_LUMA, S, S // 2).astype(np.uint16)
-    base = [np.zeros((BAND, W), np.uint16), np.zeros((BAND // 2, W // 2), np.uint16), np.zeros((BAND // 2, W // 2), np.uint16)]
-    base[0][S:S + H] = g["pic_y"]; base[1][S // 2:(S + H) // 2] = g["pic_cb"]; base[2][S // 2:(S + H) // 2] = g["pic_cr"]
-    return tasks[keep], g["exp_off"][keep], g["exp"], base, int((~keep).sum()), n_first
-
-
-def _in_bands(t):
-    t = t.copy()
-    k = np.arange(len(t))
-    t["y"] += np.where(t["kind"] == capi.IT_LUMA, k * BAND, k * (BAND // 2)).astype(np.uint16)
-    return t
-
-
-def _case_ok(tt, planes, eo, exp):
-    w, h, x, yy = 1 << int(tt["log2_w"]), 1 << int(tt["log2_h"]), int(tt["x"]), int(tt["y"])
-    if tt["kind"] == capi.IT_LUMA:
-        return np.array_equal(planes[0][yy:yy + h, x:x + w], exp[eo[0]:eo[0] + w * h].reshape(h, w))
-    return (np.array_equal(planes[1][yy:yy + h, x:x + w], exp[eo[0]:eo[0] + w * h].reshape(h, w))
-            and np.array_equal(planes[2][yy:yy + h, x:x + w], exp[eo[1]:eo[1] + w * h].reshape(h, w)))
-
-
-def _describe(i, tt):
-    return (i, int(tt["kind"]), int(tt["mode"]), 1 << int(tt["log2_w"]), 1 << int(tt["log2_h"]), int(tt["x"]), int(tt["y"]) % BAND,
-            int(tt["flags"]), int(tt["avl_lft"]), int(tt["avl_abv"]), int(tt["mrl_idx"]))
+# (the placement of intra.ovg at a smaller CTU size: intra_cases.small_ctu, shared with test_gpu_intra_flow.py)
+BAND, NB = intra_cases.BAND, intra_cases.NB
+_intra_small_ctu, _in_bands, _case_ok, _describe = intra_cases.small_ctu, intra_cases.in_bands, intra_cases.case_ok, intra_cases.describe
 
 
 @pytest.mark.parametrize("log2_ctu", [6, 5])

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import golden_io
+import intra_cases
 import oracle_pipeline
 from openvvc_amd import capi, engine, synth
 
@@ -18,39 +19,41 @@ def ctx(built_lib):
     c.close()
 
 
-def test_intra_tasks_gpu_match_reference(ctx):
-    """6506 cases of intra_pred / intra_pred_mrl / mip.rcn_intra_mip / intra_pred_c (+ cclm.*): every case predicts on its own
-    copy of the picture (one band of a tall picture), 160 cases per launch (ovhip_itask.y is 16 bits)."""
-    g = golden_io.load("intra.ovg")
-    tasks = np.frombuffer(g["task"].tobytes(), dtype=capi.ITASK_DTYPE)
-    H, W = g["pic_y"].shape
-    base = [np.zeros((BAND, W), np.uint16), np.zeros((BAND // 2, W // 2), np.uint16), np.zeros((BAND // 2, W // 2), np.uint16)]
-    base[0][:H] = g["pic_y"]; base[1][:H // 2] = g["pic_cb"]; base[2][:H // 2] = g["pic_cr"]
+def _level_kernel_vs_reference(ctx, fixture):
+    """every case predicts on its own copy of the picture (one band of a tall picture), 160 cases per launch (ovhip_itask.y is 16 bits)"""
+    tasks, exp_off, exp, pic_planes = intra_cases.load(fixture)
+    base = intra_cases.band_planes(pic_planes)
+    W = base[0].shape[1]
     NB = 160
     tall_planes = [np.tile(p, (NB, 1)) for p in base]
     res = ctx.new_pic(W, BAND * NB)
     bad = []
     for b0 in range(0, len(tasks), NB):
-        t = tasks[b0:b0 + NB].copy()
-        k = np.arange(len(t))
-        t["y"] += np.where(t["kind"] == capi.IT_LUMA, k * BAND, k * (BAND // 2)).astype(np.uint16)
+        t = intra_cases.in_bands(tasks[b0:b0 + NB])
         pic = ctx.upload_pic(*tall_planes)
         ctx.intra_level(pic, res, ctx.upload(t), 0, len(t))
         ctx.sync()
-        y, cb, cr = pic.download()
+        planes = pic.download()
         pic.free()
         for i in range(len(t)):
             tt = t[i]
-            w, h, x, yy = 1 << int(tt["log2_w"]), 1 << int(tt["log2_h"]), int(tt["x"]), int(tt["y"])
-            eo = g["exp_off"][b0 + i]
-            if tt["kind"] == capi.IT_LUMA:
-                ok = np.array_equal(y[yy:yy + h, x:x + w], g["exp"][eo[0]:eo[0] + w * h].reshape(h, w))
-            else:
-                ok = (np.array_equal(cb[yy:yy + h, x:x + w], g["exp"][eo[0]:eo[0] + w * h].reshape(h, w))
-                      and np.array_equal(cr[yy:yy + h, x:x + w], g["exp"][eo[1]:eo[1] + w * h].reshape(h, w)))
-            if not ok:
-                bad.append((b0 + i, int(tt["kind"]), int(tt["mode"]), w, h, int(tt["flags"]), int(tt["avl_lft"]), int(tt["avl_abv"]), int(tt["mrl_idx"])))
-    assert not bad, f"{len(bad)} / {len(tasks)} intra cases differ from the reference on the GPU, first: {bad[:8]}"
+            if not intra_cases.case_ok(tt, planes, exp_off[b0 + i], exp):
+                bad.append((b0 + i, int(tt["kind"]), int(tt["mode"]), 1 << int(tt["log2_w"]), 1 << int(tt["log2_h"]), int(tt["flags"]), int(tt["avl_lft"]), int(tt["avl_abv"]), int(tt["mrl_idx"])))
+    res.free()
+    assert not bad, f"{len(bad)} / {len(tasks)} intra cases of {fixture} differ from the reference on the GPU, first: {bad[:8]}"
+    return len(tasks)
+
+
+def test_intra_tasks_gpu_match_reference(ctx):
+    """6506 cases of intra_pred / intra_pred_mrl / mip.rcn_intra_mip / intra_pred_c (+ cclm.*): every case predicts on its own
+    copy of the picture (one band of a tall picture), 160 cases per launch (ovhip_itask.y is 16 bits)."""
+    assert _level_kernel_vs_reference(ctx, "intra.ovg") == 6506
+
+
+def test_intra_cells_gpu_match_reference(ctx):
+    """The cells intra.ovg does not reach (intra_cells_*.ovg: the thinned (shape, mode) cells, every availability class per kind and
+    shape, MRL at a left edge) through k_intra_level."""
+    assert _level_kernel_vs_reference(ctx, "cells") > 2500
 
 
 def _inside_ctu_geometry(t):
@@ -68,23 +71,19 @@ def _inside_ctu_geometry(t):
     return y0 + unit * int(t["avl_lft"]) <= Y0 + S
 
 
-def test_intra_tasks_ctu_kernel_match_reference(ctx):
-    """The same cases through the one-launch pass (k_intra_ctu): every case is the only task of its CTU (no waits), the
-    picture comes from / goes back through the CTU tile in LDS."""
-    g = golden_io.load("intra.ovg")
-    tasks = np.frombuffer(g["task"].tobytes(), dtype=capi.ITASK_DTYPE)
-    H, W = g["pic_y"].shape
-    base = [np.zeros((BAND, W), np.uint16), np.zeros((BAND // 2, W // 2), np.uint16), np.zeros((BAND // 2, W // 2), np.uint16)]
-    base[0][:H] = g["pic_y"]; base[1][:H // 2] = g["pic_cb"]; base[2][:H // 2] = g["pic_cr"]
+def _ctu_kernel_vs_reference(ctx, fixture):
+    """every case is the only task of its CTU (no waits), the picture comes from / goes back through the CTU tile in LDS
+    -> number of cases checked (those whose reads a decoder's CTU tile holds: _inside_ctu_geometry)"""
+    tasks, exp_off, exp, pic_planes = intra_cases.load(fixture)
+    base = intra_cases.band_planes(pic_planes)
+    W = base[0].shape[1]
     NB = 160
     tall_planes = [np.tile(p, (NB, 1)) for p in base]
     res = ctx.new_pic(W, BAND * NB)
     sync = ctx.upload(np.zeros(int(ctx.lib.ovhip_intra_sync_words(W, BAND * NB, 7)), np.uint32))
     bad, n_checked = [], 0
     for epoch, b0 in enumerate(range(0, len(tasks), NB), 1):
-        t = tasks[b0:b0 + NB].copy()
-        k = np.arange(len(t))
-        t["y"] += np.where(t["kind"] == capi.IT_LUMA, k * BAND, k * (BAND // 2)).astype(np.uint16)
+        t = intra_cases.in_bands(tasks[b0:b0 + NB])
         rec = capi.Recorder(W, BAND * NB)
         rec.append_raw(capi.REC_ITASK, t)
         ts, cs = rec.itasks_by_ctu(7)
@@ -97,15 +96,9 @@ def test_intra_tasks_ctu_kernel_match_reference(ctx):
         pic.free()
         for i in range(len(t)):
             tt = t[i]
-            w, h, x, yy = 1 << int(tt["log2_w"]), 1 << int(tt["log2_h"]), int(tt["x"]), int(tt["y"])
-            eo = g["exp_off"][b0 + i]
-            if tt["kind"] == capi.IT_LUMA:
-                ok = np.array_equal(y[yy:yy + h, x:x + w], g["exp"][eo[0]:eo[0] + w * h].reshape(h, w))
-            else:
-                ok = (np.array_equal(cb[yy:yy + h, x:x + w], g["exp"][eo[0]:eo[0] + w * h].reshape(h, w))
-                      and np.array_equal(cr[yy:yy + h, x:x + w], g["exp"][eo[1]:eo[1] + w * h].reshape(h, w)))
+            ok = intra_cases.case_ok(tt, (y, cb, cr), exp_off[b0 + i], exp)
             if not ok and _inside_ctu_geometry(tasks[b0 + i]):
-                bad.append((b0 + i, int(tt["kind"]), int(tt["mode"]), w, h, int(tt["flags"]), int(tt["avl_lft"]), int(tt["avl_abv"]), int(tt["mrl_idx"])))
+                bad.append((b0 + i, int(tt["kind"]), int(tt["mode"]), 1 << int(tt["log2_w"]), 1 << int(tt["log2_h"]), int(tt["flags"]), int(tt["avl_lft"]), int(tt["avl_abv"]), int(tt["mrl_idx"])))
             n_checked += int(_inside_ctu_geometry(tasks[b0 + i]))
         # nothing but the task's block may change
         if not bad:
@@ -116,8 +109,21 @@ def test_intra_tasks_ctu_kernel_match_reference(ctx):
                     if (tt["kind"] == capi.IT_LUMA) == (name == "Y"):
                         d[int(tt["y"]):int(tt["y"]) + (1 << int(tt["log2_h"])), int(tt["x"]):int(tt["x"]) + (1 << int(tt["log2_w"]))] = False
                 assert not d.any(), f"plane {name}: samples outside the tasks' blocks changed"
-    assert n_checked > 5500
-    assert not bad, f"{len(bad)} / {n_checked} intra cases differ from the reference through k_intra_ctu, first: {bad[:8]}"
+    res.free(); sync.free()
+    assert not bad, f"{len(bad)} / {n_checked} intra cases of {fixture} differ from the reference through k_intra_ctu, first: {bad[:8]}"
+    return n_checked
+
+
+def test_intra_tasks_ctu_kernel_match_reference(ctx):
+    """The same cases through the one-launch pass (k_intra_ctu): every case is the only task of its CTU (no waits), the
+    picture comes from / goes back through the CTU tile in LDS."""
+    assert _ctu_kernel_vs_reference(ctx, "intra.ovg") > 5500
+
+
+def test_intra_cells_ctu_kernel_match_reference(ctx):
+    """The enumerated cells through k_intra_ctu.  Their arms are as long as the picture lets them be, so fewer of them than of
+    intra.ovg's stay inside what a decoder's CTU tile holds; the count is what the generator's positions give."""
+    assert _ctu_kernel_vs_reference(ctx, "cells") == 2639          # of 3021, every kind and class among them
 
 
 @pytest.mark.parametrize("one_launch", [0, capi.STAGE_INTRA_CTU, capi.STAGE_INTRA_LEVELS])

@@ -251,18 +251,22 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     if not gen.exists() or not (root / "oracle" / "_ref" / "libovvcref.so").exists():
         pytest.skip("compiled reference not present")
     subprocess.check_call([str(gen), str(tmp_path)], stderr=subprocess.DEVNULL)
-    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32"):        # deblocking's second profile and the smaller CTU sizes are runs of their own
+    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra cells are runs of their own
         subprocess.check_call([str(gen), str(tmp_path), only], stderr=subprocess.DEVNULL)
     # shim_*: test_shim_cpu.py; pipe* / tiles*: the chained streams of gen_pipe, test_pipe_cpu.py
     names = sorted(p.name for p in (root / "tests" / "golden").glob("*.ovg") if not p.name.startswith(("shim_", "pipe", "tiles")))
     assert len(names) >= 14
     for n in names:
         assert (tmp_path / n).read_bytes() == (root / "tests" / "golden" / n).read_bytes(), f"{n} differs from a fresh run of the reference"
+    assert sorted(p.name for p in tmp_path.glob("intra_cells_*.ovg")) == [n for n in names if n.startswith("intra_cells_")], "the generator cuts the intra cells into other files than the committed ones"
 
 
 def test_intra_oracle_matches_reference(built_lib):
-    """Intra prediction: the reference's intra_pred / intra_pred_mrl / mip.rcn_intra_mip / intra_pred_c (+ cclm.*) slots on
-    every mode, block shape and neighbour-availability state vs the oracle's ordered-task executor."""
+    """Intra prediction: the reference's intra_pred / intra_pred_mrl / mip.rcn_intra_mip / intra_pred_c (+ cclm.*) slots vs the oracle's
+    ordered-task executor on intra.ovg: every block shape, but for blocks of 512 samples or more every third or fifth mode only (every
+    other MIP matrix from 1024), and ONE availability pattern per case, drawn at random; every MRL case has both arms and the corner.
+    test_intra_fixture_census pins what that reaches; the cells it does not reach are intra_cells_*.ovg
+    (test_intra_oracle_matches_reference_on_the_enumerated_cells)."""
     import golden_io
     g = golden_io.load("intra.ovg")
     tasks = np.frombuffer(g["task"].tobytes(), dtype=capi.ITASK_DTYPE)
@@ -287,3 +291,85 @@ def test_intra_oracle_matches_reference(built_lib):
             bad.append((i, k, int(t["mode"]), w, h, x, y, fl, int(t["avl_lft"]), int(t["avl_abv"])))
     assert not bad, f"{len(bad)} / {len(tasks)} intra cases differ from the reference, first: {bad[:6]}"
     assert kinds["luma"] > 2500 and kinds["mrl"] > 500 and kinds["mip"] > 200 and kinds["chroma"] > 1000 and kinds["lm"] > 200 and kinds["bdpcm"] > 50
+
+
+def test_intra_oracle_matches_reference_on_the_enumerated_cells(built_lib):
+    """intra_cells_*.ovg (gen_intra_cells: the (shape, mode) cells intra.ovg thins out, every availability class per kind and shape,
+    MRL at a left edge), same slots and picture as intra.ovg: the oracle equals the reference on every case."""
+    import golden_io
+    import intra_cases
+    import intra_census as ic
+    tasks, exp_off, exp, pic = intra_cases.load("cells")
+    assert len(tasks) > 2500 and all((golden_io.GOLDEN / n).stat().st_size < (1 << 20) for n in intra_cases.cell_files())
+    bad = [intra_cases.describe(i, t) for i, t in enumerate(tasks)
+           if not ic.blocks_equal(ic.expected_block(t, exp_off[i], exp), ic.oracle_block(pic, t))]
+    assert not bad, f"{len(bad)} / {len(tasks)} enumerated intra cases differ from the reference, first: {bad[:6]}"
+
+
+def test_intra_fixture_census(built_lib):
+    """What the intra slot fixtures reach, written down so that it cannot shrink unnoticed (tests/intra_census.py does the counting).
+
+    intra.ovg alone -- thinned modes for big blocks, one random availability pattern per case:
+      (shape, mode) cells: luma regular 1251 of 1675 (the 10 shapes of >= 512 samples have 19 or 27 of 67 modes), MRL 979 of 1675 (19 of
+      25 shapes have 19 to 39 modes), chroma regular 1488 of 1608 (16x32, 32x16, 32x32: 27 modes), MIP 320 of the 356 (shape, matrix,
+      transposed) cells; luma regular (shape, mode, class): 2297 of 8375; all 979 MRL cases have both arms and the corner; 696 cases
+      span several 256-sample strips of the flow launch, 132 several 1024-sample strips of the level launch; 90 of the 1335 luma
+      regular cases without full availability predict exactly what full availability predicts (the missing arm is not read).
+    With intra_cells_*.ovg, conditions (a) to (d) below hold.  Not reachable, by what the operations read: MIP and LM / MDLM never read
+    the corner sample, so their "both without the corner" cases equal full availability -- asserted as such; MRL without the rows
+    above is left out (the reference reads memory nothing wrote there)."""
+    import collections
+    import intra_cases
+    import intra_census as ic
+    tasks, exp_off, exp, pic = intra_cases.load("intra.ovg")
+    lb = ic.label(tasks)
+    big = {s for s in ic.LUMA_SHAPES if s[0] + s[1] >= 9}
+    n_modes = ic.modes_per_shape(lb, ic.LUMA)
+    assert len(ic.cells(lb, ic.LUMA, "shape", "mode")) == 1251 and len(big) == 10
+    assert all(n_modes[s] in (19, 27) for s in big) and all(n_modes[s] == 67 for s in set(ic.LUMA_SHAPES) - big)
+    n_modes = ic.modes_per_shape(lb, ic.MRL)
+    assert len(ic.cells(lb, ic.MRL, "shape", "mode")) == 979
+    assert sorted(n for n in n_modes.values() if n < 67)[::18] == [19, 39] and sum(n < 67 for n in n_modes.values()) == 19
+    n_modes = ic.modes_per_shape(lb, ic.CHROMA)
+    assert len(ic.cells(lb, ic.CHROMA, "shape", "mode")) == 1488 and {s: n for s, n in n_modes.items() if n < 67} == {(4, 5): 27, (5, 4): 27, (5, 5): 27}
+    assert len(ic.mip_cells()) == 356 and len(ic.cells(lb, ic.MIP, "shape", "mode", "tr")) == 320
+    assert len(ic.cells(lb, ic.LUMA, "shape", "mode", "cls")) == 2297
+    assert ic.cells(lb, ic.MRL, "cls") == {(4,)} and int((lb["kind"] == ic.MRL).sum()) == 979
+    assert int((lb["samples"] > 256).sum()) == 696 and int((lb["samples"] > 1024).sum()) == 132
+    sel = np.nonzero((lb["kind"] == ic.LUMA) & (lb["cls"] != 4))[0]
+    assert len(sel) == 1335 and int((~ic.sensitive(tasks, exp_off, exp, pic, sel)).sum()) == 90
+
+    # ---- both fixtures together
+    tc, eoc, expc, _ = intra_cases.load("cells")
+    n0 = len(tasks)
+    tasks, exp_off, exp = np.concatenate([tasks, tc]), np.concatenate([exp_off, eoc + len(exp)]), np.concatenate([exp, expc])
+    lb = ic.label(tasks)
+    # (a) every (shape, mode): luma regular 25 x 0..66, chroma regular 24 x 0..66, MRL 25 x 1..66, MIP every (shape, matrix, transposed)
+    assert ic.cells(lb, ic.LUMA, "shape", "mode") == {(s, m) for s in ic.LUMA_SHAPES for m in range(67)}
+    assert ic.cells(lb, ic.CHROMA, "shape", "mode") == {(s, m) for s in ic.CHROMA_SHAPES for m in range(67)}
+    assert ic.cells(lb, ic.MRL, "shape", "mode") >= {(s, m) for s in ic.LUMA_SHAPES for m in range(1, 67)}
+    assert ic.cells(lb, ic.MIP, "shape", "mode", "tr") == ic.mip_cells()
+    # (b) every (kind, shape, class); every (mode, class) of luma regular and chroma regular
+    for kind, shapes in ((ic.LUMA, ic.LUMA_SHAPES), (ic.CHROMA, ic.CHROMA_SHAPES), (ic.MIP, ic.LUMA_SHAPES), (ic.LM, ic.CHROMA_SHAPES)):
+        assert ic.cells(lb, kind, "shape", "cls") == {(s, c) for s in shapes for c in range(5)}, ic.KIND_NAMES[kind]
+    for kind in (ic.LUMA, ic.CHROMA):
+        assert ic.cells(lb, kind, "mode", "cls") == {(m, c) for m in range(67) for c in range(5)}, ic.KIND_NAMES[kind]
+    assert ic.cells(lb, ic.LM, "mode") == {(67,), (68,), (69,)}
+    # (c) MRL: every shape at a left edge (no left arm, no corner, rows above), every shape with both indices
+    assert {s for s, c in ic.cells(lb, ic.MRL, "shape", "cls") if c == 1} == set(ic.LUMA_SHAPES)
+    assert ic.cells(lb, ic.MRL, "shape", "mrl") == {(s, m) for s in ic.LUMA_SHAPES for m in (1, 2)}
+    assert {c for (c,) in ic.cells(lb, ic.MRL, "cls")} == {1, 4}, "MRL without the rows above has no defined result in the reference"
+    # (d) every (kind, shape, class != both with corner) has a case that full availability would predict differently
+    sel = np.nonzero((lb["cls"] != 4) & (lb["kind"] != ic.BDPCM))[0]
+    sens = ic.sensitive(tasks, exp_off, exp, pic, sel)
+    triples = collections.defaultdict(list)
+    for k, i in enumerate(sel):
+        triples[(int(lb["kind"][i]), (int(lb["l2w"][i]), int(lb["l2h"][i])), int(lb["cls"][i]))].append(bool(sens[k]))
+    no_corner_read = {t for t in triples if t[0] in (ic.MIP, ic.LM) and t[2] == 3}            # neither reads the corner sample
+    assert len(triples) == 4 * (25 + 24 + 25 + 24) + 25 and len(no_corner_read) == 25 + 24
+    dull = sorted(t for t, v in triples.items() if not any(v) and t not in no_corner_read)
+    assert not dull, f"(kind, shape, class) without a case that pins the availability logic: {dull[:8]}"
+    assert not any(any(triples[t]) for t in no_corner_read), "a MIP or LM case reads the corner sample?"
+    # (a figure, not a condition: the (mode, class) pairs hold modes that do not read the missing arm, and planar never reads the corner)
+    new = sel >= n0
+    print(f"enumerated cases without full availability that predict what full availability predicts: {int((new & ~sens).sum())} of {int(new.sum())}")
