@@ -1229,7 +1229,8 @@ void ovhip_md5_final(ovhip_md5_state *st, uint8_t out[16]);
  * (pp_pic_scale.c:250-377), called once per plane by pp_process_frame (post_proc.c:116-126) when the decoder's `upscale` option is
  * on (ovdec.c:562; ovdec.c:479 / :523 are the call sites), for up-sampling and equal size, bit-exactly -- including its phase, which
  * is the LOW 4 (luma) / 5 (chroma) bits of the 13- / 14-bit fixed-point position.  The decoded picture is only read:
- * references keep predicting from it at its coded size.  Film grain and SL-HDR, the other branches of pp_process_frame, are not here.
+ * references keep predicting from it at its coded size.  Film grain, the first branch of pp_process_frame, is the section after this
+ * one; SL-HDR, the third, is not built.
  *
  * `ovhip_scale_info` = struct ScalingInfo (ovdpb.h:85-93): the scaling window in chroma sample units and the SPS chroma collocation
  * flags; what the reference passes is the picture's own (pic->scale_info).
@@ -1254,6 +1255,92 @@ int  ovhip_pic_digest_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_s
 /* Device + page-locked bytes the context's grow-only scratch buffers hold (the synchronous conveniences above and of the output path):
  * constant from call to call once the sizes have been seen. */
 size_t ovhip_ctx_scratch_bytes(const ovhip_ctx *ctx);
+
+/* ------------------------------------------------------------------------------------
+ * Film grain synthesis (film grain characteristics SEI, frequency-filtering model): replaces fg_grain_apply_pic
+ * (pp_film_grain.c:814-978) as pp_process_frame calls it (post_proc.c:106-108: no IDR offset, edge smoothing on, 10 bit, 4:2:0),
+ * bit-exactly wherever the reference is defined.  Per 8x8 block of a plane: the average of the block's samples inside the plane
+ * (/ n, >> 2, clipped to 8 bits) selects an intensity interval; the interval's model values select a scale and one of 13 x 13
+ * cells (horizontal x vertical cut-off frequency 2..14) of a fixed database of 64 x 64 grain patterns; a 31-bit shift register,
+ * seeded per picture and component from the POC and stepped once per 16x16 block in raster order, picks the pattern's offset and
+ * sign; sample = (+-scale * pattern) >> (log2_scale + 6); the grain columns either side of every vertical 8x8 edge are smoothed
+ * inside a 16-row stripe; dst = clip(src + (grain << 2), 0..1023).  A component without a model is copied.  The decoded picture
+ * is only read: references keep predicting from it.
+ *
+ * Three steps, the first two on the host without a device:
+ *   ovhip_fg_params    the SEI's fields as the reference's function reads them
+ *   ovhip_fg_derive    ONE call's model derivation (fg_compute_model_values, :768-807) -> ovhip_fg_model.  The reference derives
+ *                      IN PLACE on every call: for chroma it halves value[..][0] and doubles value[..][1..2] (clamped to 2..14),
+ *                      so a caller that hands the same struct to consecutive pictures gets 100 / 4 / 6, then 50 / 8 / 12, then
+ *                      25 / 14 / 14.  `after` receives the fields as that one call leaves them: a caller that wants the
+ *                      reference's sequence for a persistent SEI feeds `after` back in (the shim does); ovhip_stream_set_film_grain
+ *                      and ovhip_frame_set_film_grain derive afresh from the params they were given, for every picture.
+ *                      All 8 intervals are walked whatever num_intervals says, later ones overwriting earlier ones: unused
+ *                      intervals with bounds 0..0 claim average 0, and the last one wins.
+ *   ovhip_film_grain_launch   one launch (k_film_grain) over the luma and both chroma planes, behind a small one that steps the shift
+ *                      register to every workgroup's first block (k_film_grain_seeds).
+ *
+ * Where the reference is undefined this back-end does not follow it:
+ *   - an interval that some block average selects, whose scale is not 0 and whose cut-off (after the derivation) lies outside
+ *     2..14, indexes far past the database there: OVHIP_EINVAL here.  With scale 0 the product is 0 whatever the cut-offs: such an
+ *     entry gives grain 0 (and is stored with cut-offs 2, 2).
+ *   - fg_model_id != 0 and fg_blending_mode_id != 0 are ignored there (H.274 gives them other semantics): OVHIP_EUNSUP here.
+ *   - fg_characteristics_cancel_flag = 1 leaves the destination unwritten there: here the model has no component, the picture is
+ *     copied.
+ *   - a plane whose width is 1..7 mod 16 makes the reference average and write an 8x8 block that lies outside the plane (its
+ *     samples are the next row's, its grain lands on the next row's columns 4..11 and, for luma, past the stripe buffer), a plane
+ *     width below 8 sends its smoothing loop over the whole address space, and a plane height of 1..7 mod 16 averages rows below
+ *     the plane.  Here only blocks inside the plane exist; parity is claimed for plane widths and heights of 0 or 8..15 mod 16.
+ *   - grain together with output resampling: the reference resamples the UNgrained frame over the grained one (post_proc.c:107-126).
+ * Sizes are multiples of 4 (at most 16384), as for the resampler: with that the smoothing never reads past a row's end.
+ * ---------------------------------------------------------------------------------- */
+typedef struct ovhip_fg_comp {
+    uint8_t  present;              /* fg_comp_model_present_flag                                    */
+    uint8_t  num_intervals;        /* fg_num_intensity_intervals_minus1 + 1 (not read: see above)   */
+    uint8_t  num_model_values;     /* fg_num_model_values_minus1 + 1                                */
+    uint8_t  pad_;
+    uint8_t  lower[8], upper[8];   /* fg_intensity_interval_lower_bound / _upper_bound              */
+    int16_t  value[8][3];          /* fg_comp_model_value: scale, horizontal, vertical cut-off      */
+} ovhip_fg_comp;
+typedef struct ovhip_fg_params {
+    uint8_t  cancel;               /* fg_characteristics_cancel_flag */
+    uint8_t  model_id;             /* fg_model_id                    */
+    uint8_t  blending_mode;        /* fg_blending_mode_id            */
+    uint8_t  log2_scale;           /* fg_log2_scale_factor           */
+    ovhip_fg_comp comp[3];         /* Y, Cb, Cr                      */
+} ovhip_fg_params;
+/* entry[c][block average]: 0 = no interval (grain 0); else OVHIP_FG_VALID | scale (int16, low half) | h << 16 | v << 20 with
+ * h, v = cut-off - 2 = the database cell.  The sign of the shift register's bit 0 is applied to the scale on the device. */
+#define OVHIP_FG_VALID      (1u << 24)
+#define OVHIP_FG_ENTRY(scale, h, v) (OVHIP_FG_VALID | (uint32_t)(uint16_t)(int16_t)(scale) | ((uint32_t)(h) << 16) | ((uint32_t)(v) << 20))
+#define OVHIP_FG_DB_BYTES   (13 * 13 * 64 * 64)
+typedef struct ovhip_fg_model {
+    uint8_t  log2_scale;
+    uint8_t  present[3];
+    uint32_t entry[3][256];
+} ovhip_fg_model;
+/* Host only.  OVHIP_OK, or a refusal as listed above, on which neither `model` nor `after` is written.  `after` may be NULL and may
+ * be `in`. */
+int  ovhip_fg_derive(const ovhip_fg_params *in, ovhip_fg_model *model, ovhip_fg_params *after);
+/* Host only: the grain database [h][v][row][column], OVHIP_FG_DB_BYTES of int8, as fg_data_base_generation (:666-765) builds it with
+ * smoothing of the horizontal 8x8 edges on.  Built on the first call (some tens of ms), from any number of threads at once. */
+const int8_t *ovhip_fg_database(void);
+/* The start value of a component's shift register (c = 0 Y, 1 Cb, 2 Cr) and one step of it; host only. */
+uint32_t ovhip_fg_seed(int32_t poc, int32_t idr_offset, int c);
+uint32_t ovhip_fg_prng(uint32_t x);
+/* out[k] = the register at the start of stripe k = `start` stepped k * blocks_per_stripe times (the register is never reset inside a
+ * picture), k < n_stripes; host only.  Jumps instead of stepping: the n-step map is affine over GF(2) and kept per thread. */
+void ovhip_fg_stripe_seeds(uint32_t start, int32_t blocks_per_stripe, int32_t n_stripes, uint32_t *out);
+/* dst = src with grain; src and dst of one size, planes apart.  Asynchronous on the ctx stream; the database is uploaded at a
+ * context's first launch (contexts that never use grain hold nothing), the model and the per-stripe seeds travel through a small
+ * page-locked ring of the context.  idr_offset: 0 for the reference's caller.  OVHIP_EINVAL for a size mismatch, sizes that are not
+ * multiples of 4 (or above 16384), a missing plane, dst aliasing src, or a model entry that points outside the database. */
+int  ovhip_film_grain_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_fg_model *model, int32_t poc, int32_t idr_offset,
+                             const ovhip_pic *dst);
+/* Synchronous conveniences: grain into the context's grow-only scratch picture (the one the scaled outputs use), then exactly
+ * ovhip_pic_output / ovhip_pic_digest on it. */
+int  ovhip_pic_output_grain(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, const ovhip_window *win, void *host_dst);
+int  ovhip_pic_digest_grain(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, const ovhip_window *win, uint8_t out16[16]);
 
 /* ------------------------------------------------------------------------------------
  * TMVP motion plane.  The reference's caller stores what rcn_dmvr_mv_refine returned into the CTU-local
@@ -1476,6 +1563,14 @@ int  ovhip_frame_band_stats(const ovhip_frame *f, int32_t *n_bands, int32_t *n_d
  * published to the DPB is the decoded picture, unchanged.  (0, 0) switches it off, which is the default; info is copied (NULL: no
  * scaling window, flags 0).  Refusals as ovhip_output_scale_check against the frame's size; a dry frame accepts the call and does nothing. */
 int  ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_scale_info *info);
+/* From now on the outputs OVHIP_OUT_DIGEST / _PLANES / _PACKED of this frame deliver the picture with film grain ("Film grain synthesis"
+ * above) for the picture order count `poc`; params NULL switches it off.  What is published to the DPB stays the decoded picture:
+ * references predict from it.  The model is derived afresh from a copy of *params for every picture (a non-persistent SEI); a caller
+ * that holds ONE SEI struct across pictures and wants the reference's drift derives with ovhip_fg_derive and hands `after` to the next
+ * call of this setter.  The refusals of ovhip_fg_derive come back from here.  OVHIP_EUNSUP while an output scale is set, and
+ * ovhip_frame_set_output_scale answers OVHIP_EUNSUP while grain is set: the reference resamples the ungrained frame over the grained one
+ * (post_proc.c:107-126).  A dry frame accepts the call and delivers nothing. */
+int  ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_t poc);
 int  ovhip_frame_fail(ovhip_frame *f, int status);
 const char *ovhip_frame_last_error(const ovhip_frame *f);
 
@@ -1607,6 +1702,10 @@ int  ovhip_stream_queue_info(const ovhip_stream *s, int *moved, int *sharing);
  * frame threads' DIGEST fingerprints are those of the pictures resampled to out_w x out_h; (0, 0) switches it off.  The driver still
  * decodes pictures of one coded size (cfg.w x cfg.h). */
 int  ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, const ovhip_scale_info *info);
+/* Film grain for every picture of the following runs, each with its own ovhip_stream_pic.poc and a model derived afresh from *params
+ * (ovhip_frame_set_film_grain); NULL: off.  The frames of OVHIP_OUT_PACKED -- and with them the MD5 of OVHIP_STREAM_FILE_MD5 -- and the
+ * fingerprints of OVHIP_OUT_DIGEST are those of the grained pictures.  Refusals as the frame's setter. */
+int  ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params);
 /* The DPB key of picture idx of the current stream (valid while the run that decoded it kept it: OVHIP_STREAM_KEEP). */
 const void *ovhip_stream_key(const ovhip_stream *s, uint32_t idx);
 /* test hook: the next flush of `job` that has a flow launch is ABORTED for real (the device's abort word is set before the

@@ -355,6 +355,57 @@ class ScaleInfo(C.Structure):
                 ("chroma_hor_col", C.c_uint8), ("chroma_ver_col", C.c_uint8)]
 
 
+class FgComp(C.Structure):
+    """ovhip_fg_comp: one component's fields of the film grain characteristics SEI"""
+    _fields_ = [("present", C.c_uint8), ("num_intervals", C.c_uint8), ("num_model_values", C.c_uint8), ("pad_", C.c_uint8),
+                ("lower", C.c_uint8 * 8), ("upper", C.c_uint8 * 8), ("value", (C.c_int16 * 3) * 8)]
+
+
+class FgParams(C.Structure):
+    """ovhip_fg_params: the SEI fields the reference's film grain synthesis reads"""
+    _fields_ = [("cancel", C.c_uint8), ("model_id", C.c_uint8), ("blending_mode", C.c_uint8), ("log2_scale", C.c_uint8), ("comp", FgComp * 3)]
+
+
+class FgModel(C.Structure):
+    """ovhip_fg_model: one call's derived model (ovhip_fg_derive)"""
+    _fields_ = [("log2_scale", C.c_uint8), ("present", C.c_uint8 * 3), ("entry", (C.c_uint32 * 256) * 3)]
+
+
+FG_DB_BYTES = 13 * 13 * 64 * 64
+FG_VALID = 1 << 24
+
+
+def fg_params(cancel=0, model_id=0, blending_mode=0, log2_scale=0, present=(0, 0, 0), num_intervals=(0, 0, 0), num_model_values=(0, 0, 0),
+              lower=None, upper=None, value=None) -> FgParams:
+    """FgParams from plain sequences: lower / upper [3][8], value [3][8][3]"""
+    p = FgParams(cancel, model_id, blending_mode, log2_scale)
+    for c in range(3):
+        k = p.comp[c]
+        k.present, k.num_intervals, k.num_model_values = int(present[c]), int(num_intervals[c]), int(num_model_values[c])
+        for i in range(8):
+            k.lower[i] = int(lower[c][i]) if lower is not None else 0
+            k.upper[i] = int(upper[c][i]) if upper is not None else 0
+            for n in range(3):
+                k.value[i][n] = int(value[c][i][n]) if value is not None else 0
+    return p
+
+
+def fg_params_dict(p: FgParams) -> dict:
+    """the inverse of fg_params(**d)"""
+    return {"cancel": p.cancel, "model_id": p.model_id, "blending_mode": p.blending_mode, "log2_scale": p.log2_scale,
+            "present": [p.comp[c].present for c in range(3)], "num_intervals": [p.comp[c].num_intervals for c in range(3)],
+            "num_model_values": [p.comp[c].num_model_values for c in range(3)],
+            "lower": [list(p.comp[c].lower) for c in range(3)], "upper": [list(p.comp[c].upper) for c in range(3)],
+            "value": [[list(p.comp[c].value[i]) for i in range(8)] for c in range(3)]}
+
+
+def fg_derive(lib, params: FgParams):
+    """ovhip_fg_derive -> (code, FgModel, FgParams after the call); model and after stay zero on a refusal"""
+    model, after = FgModel(), FgParams()
+    r = lib.ovhip_fg_derive(C.byref(params), C.byref(model), C.byref(after))
+    return r, model, after
+
+
 class Window(C.Structure):
     """ovhip_window = OVFrame.output_window: offsets in chroma sample units"""
     _fields_ = [("offset_lft", C.c_uint16), ("offset_rgt", C.c_uint16), ("offset_abv", C.c_uint16), ("offset_blw", C.c_uint16)]
@@ -661,6 +712,16 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_ctx_scratch_bytes": (C.c_size_t, [vp]),
         "ovhip_frame_set_output_scale": (C.c_int, [vp, i32, i32, P(ScaleInfo)]),
         "ovhip_stream_set_output_scale": (C.c_int, [vp, i32, i32, P(ScaleInfo)]),
+        "ovhip_frame_set_film_grain": (C.c_int, [vp, P(FgParams), i32]),
+        "ovhip_stream_set_film_grain": (C.c_int, [vp, P(FgParams)]),
+        "ovhip_fg_derive": (C.c_int, [P(FgParams), P(FgModel), P(FgParams)]),
+        "ovhip_fg_database": (vp, []),
+        "ovhip_fg_seed": (u32, [i32, i32, C.c_int]),
+        "ovhip_fg_prng": (u32, [u32]),
+        "ovhip_fg_stripe_seeds": (None, [u32, i32, i32, P(u32)]),
+        "ovhip_film_grain_launch": (C.c_int, [vp, P(Pic), P(FgModel), i32, i32, P(Pic)]),
+        "ovhip_pic_output_grain": (C.c_int, [vp, P(Pic), P(FgModel), i32, P(Window), vp]),
+        "ovhip_pic_digest_grain": (C.c_int, [vp, P(Pic), P(FgModel), i32, P(Window), vp]),
     }
     ab_build = "OVVC_HIP_LIB_NAME" in os.environ       # tools/ab_lib.sh: an OLDER build of the library beside the current one (its newer entry points are not called)
     for name, (res, args) in sigs.items():
@@ -703,6 +764,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_output_scale_check", "ovhip_output_scale_launch", "ovhip_pic_output_scaled", "ovhip_pic_digest_scaled",
     "ovhip_frame_set_output_scale", "ovhip_stream_set_output_scale", "ovhip_ctx_scratch_bytes",
     "ovhip_rec_ibc_check", "ovhip_rec_tu_ibc", "ovhip_rec_ibc_tasks",
+    "ovhip_frame_set_film_grain", "ovhip_stream_set_film_grain", "ovhip_fg_derive", "ovhip_fg_database", "ovhip_fg_seed", "ovhip_fg_prng", "ovhip_fg_stripe_seeds", "ovhip_film_grain_launch", "ovhip_pic_output_grain", "ovhip_pic_digest_grain",
 ]
 
 

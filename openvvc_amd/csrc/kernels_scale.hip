@@ -278,6 +278,9 @@ extern "C" int ovhip_output_scale_launch(ovhip_ctx *ctx, const ovhip_pic *src, c
     return OVHIP_OK;
 }
 
+// library-internal (ovvc_dpb_priv.h): the scratch picture at w x h for the other user of it, the grained outputs (kernels_grain.hip)
+extern "C" int ovhip_scratch_pic_(ovhip_ctx *ctx, int32_t w, int32_t h, ovhip_pic *pic) { return scale_scratch(ctx, w, h, pic); }
+
 // library-internal (ovvc_dpb_priv.h): resample `pic` into the context's scratch picture and hand that out; the picture stays valid until
 // the context's next scaled output.  Asynchronous on the context's stream.
 extern "C" int ovhip_scaled_scratch_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h, ovhip_pic *scaled)

@@ -15,6 +15,7 @@
 #define OV_PIX_MAX ((1 << OV_BD) - 1)
 
 #define OV_MAX_LANES 4
+#define OV_FG_SLOTS 4
 struct ovhip_ctx {
     int device;
     int num_cus;                   // compute units of the device (sizes the resident grids of the pipelined kernels)
@@ -29,7 +30,12 @@ struct ovhip_ctx {
     // synchronise the whole device every time a picture is output
     void *scratch_d; size_t scratch_d_cap;
     void *scratch_h; size_t scratch_h_cap;       // page-locked
-    void *scale_d; size_t scale_d_cap;           // the scratch PICTURE of the scaled outputs (kernels_scale.hip), grow-only likewise
+    void *scale_d; size_t scale_d_cap;           // the scratch PICTURE of the scaled and grained outputs (kernels_scale.hip), grow-only likewise
+    // film grain (kernels_grain.hip), allocated at the context's first grain launch: the database followed by OV_FG_SLOTS slots (model +
+    // stripe seeds of one launch, and the seeds k_film_grain_seeds makes of them per workgroup) on the device, the slots' page-locked staging, and per slot the event behind the launch that reads it
+    void *fg_d; size_t fg_d_cap;
+    void *fg_h; size_t fg_h_cap;
+    hipEvent_t fg_ev[OV_FG_SLOTS]; int fg_busy[OV_FG_SLOTS]; int fg_next;
     hipEvent_t ev_sync;            // the synchronous conveniences wait for an event behind their last command (measured in round 4: hipStreamSynchronize from
                                    // 16 frame threads cost the stream a fifth of its rate, an event wait nothing)
     char err[256];

@@ -47,6 +47,9 @@ struct ovhip_frame {
     /* ovhip_frame_set_output_scale: the outputs deliver the picture resampled to out_w x out_h (0: off) */
     int32_t out_w, out_h;
     ovhip_scale_info out_info;
+    /* ovhip_frame_set_film_grain: the outputs deliver the picture with film grain, derived afresh from fg for every picture */
+    int fg_on; int32_t fg_poc;
+    ovhip_fg_params fg;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -373,8 +376,9 @@ int
 ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_scale_info *info)
 {
     if (!f) return OVHIP_EINVAL;
-    if (f->dry) return OVHIP_OK;          /* a dry frame has no output */
     if (!out_w && !out_h) { f->out_w = f->out_h = 0; return OVHIP_OK; }
+    if (f->fg_on) return OVHIP_EUNSUP;    /* the reference resamples the UNgrained frame over the grained one: no parity to offer */
+    if (f->dry) { f->out_w = out_w; f->out_h = out_h; return OVHIP_OK; }          /* a dry frame has no output: only remembered */
     ovhip_scale_info si;
     int32_t scale[4];
     memset(&si, 0, sizeof(si));
@@ -385,11 +389,39 @@ ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const
     return OVHIP_OK;
 }
 
+int
+ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_t poc)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!params) { f->fg_on = 0; return OVHIP_OK; }
+    if (f->out_w) return OVHIP_EUNSUP;
+    ovhip_fg_model model;
+    const int r = ovhip_fg_derive(params, &model, NULL);      /* the refusals come back here, not from a picture's output */
+    if (r != OVHIP_OK) return r;
+    f->fg = *params; f->fg_poc = poc; f->fg_on = 1;           /* (a dry frame has no output: only remembered) */
+    return OVHIP_OK;
+}
+
 /* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the decoded picture as it is, or
- * (ovhip_frame_set_output_scale) resampled into the context's scratch picture first -- f->dst itself is only read */
+ * (ovhip_frame_set_output_scale / ovhip_frame_set_film_grain) resampled / grained into the context's scratch picture first -- f->dst
+ * itself is only read */
 static int
 frame_output(ovhip_frame *f, ovhip_frame_output *out)
 {
+    if (f->fg_on) {
+        ovhip_fg_model model;
+        ovhip_pic grained;
+        int r = ovhip_fg_derive(&f->fg, &model, NULL);
+        if (r != OVHIP_OK) return r;
+        switch (out->mode) {
+        case OVHIP_OUT_DIGEST: return ovhip_pic_digest_grain(f->ctx, &f->dst, &model, f->fg_poc, &out->window, out->digest);
+        case OVHIP_OUT_PLANES:
+            r = ovhip_grain_scratch_(f->ctx, &f->dst, &model, f->fg_poc, &grained);
+            return r != OVHIP_OK ? r : ovhip_pic_download(f->ctx, &grained, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
+        case OVHIP_OUT_PACKED: return ovhip_pic_output_grain(f->ctx, &f->dst, &model, f->fg_poc, &out->window, out->packed);
+        default: return OVHIP_EINVAL;
+        }
+    }
     if (!f->out_w) {
         switch (out->mode) {
         case OVHIP_OUT_DIGEST: return ovhip_pic_digest(f->ctx, &f->dst, &out->window, out->digest);

@@ -49,6 +49,7 @@ struct ovhip_stream {
     pthread_mutex_t begun_mtx; pthread_cond_t begun_cnd;
     int n_moved, n_sharing;               /* streams replaced to clear the look-ahead thread's hardware queue / still sharing it */
     int32_t out_w, out_h; ovhip_scale_info out_info;     /* ovhip_stream_set_output_scale (0: off) */
+    int fg_on; ovhip_fg_params fg;                       /* ovhip_stream_set_film_grain */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -222,6 +223,7 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         out.mode = ((rs->flags & OVHIP_STREAM_DIGESTS) || s->cfg.output == OVHIP_OUT_DIGEST) ? OVHIP_OUT_DIGEST : OVHIP_OUT_NONE;
         out.window = s->cfg.window;
         if (tr) tr[1] = now_s() - rs->t0;
+        if (s->fg_on) (void)ovhip_frame_set_film_grain(f, &s->fg, p->poc);      /* (validated by the stream's setter) */
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
@@ -329,8 +331,13 @@ output_thread(void *argp)
         int r = ovhip_dpb_acquire(s->dpb, key_of(s, idx), p->device, &pic, NULL);
         if (r != OVHIP_OK) { if (!rs->abort) run_fail(rs, r, "output: picture not available", ""); break; }
         ovhip_ctx *ctx = s->out_ctx[p->device];
-        r = s->out_w ? ovhip_pic_output_scaled(ctx, &pic, &s->out_info, s->out_w, s->out_h, &s->cfg.window, s->out_host)
-                     : ovhip_pic_output(ctx, &pic, &s->cfg.window, s->out_host);
+        if (s->fg_on) {
+            ovhip_fg_model model;
+            r = ovhip_fg_derive(&s->fg, &model, NULL);
+            if (r == OVHIP_OK) r = ovhip_pic_output_grain(ctx, &pic, &model, p->poc, &s->cfg.window, s->out_host);
+        } else
+            r = s->out_w ? ovhip_pic_output_scaled(ctx, &pic, &s->out_info, s->out_w, s->out_h, &s->cfg.window, s->out_host)
+                         : ovhip_pic_output(ctx, &pic, &s->cfg.window, s->out_host);
         if (r == OVHIP_OK) {
             if (rs->flags & OVHIP_STREAM_FILE_MD5) ovhip_md5_update(&rs->md5, s->out_host, s->out_host_bytes);
             rs->res->out_bytes += s->out_host_bytes;
@@ -460,6 +467,7 @@ ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, con
 {
     if (!s) return OVHIP_EINVAL;
     const int on = out_w || out_h;
+    if (on && s->fg_on) return OVHIP_EUNSUP;
     ovhip_scale_info si;
     memset(&si, 0, sizeof(si));
     if (on) {
@@ -485,6 +493,21 @@ ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, con
         if (r != OVHIP_OK) return r;
     }
     s->out_w = on ? out_w : 0; s->out_h = on ? out_h : 0; s->out_info = si;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params)
+{
+    if (!s) return OVHIP_EINVAL;
+    if (params && s->out_w) return OVHIP_EUNSUP;
+    /* the frame threads' DIGEST path; with params the first frame's answer is every frame's (each picture sets its own POC later) */
+    for (int i = 0; i < s->n_dev * s->tpd; ++i) {
+        const int r = ovhip_frame_set_film_grain(s->frames[i], params, 0);
+        if (r != OVHIP_OK) return r;
+    }
+    s->fg_on = params != NULL;
+    if (params) s->fg = *params;
     return OVHIP_OK;
 }
 

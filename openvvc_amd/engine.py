@@ -364,6 +364,38 @@ class DevPic:
                       "pic_digest_scaled")
         return bytes(out)
 
+    def _fg_model(self, params: capi.FgParams) -> capi.FgModel:
+        r, model, _ = capi.fg_derive(self.ctx.lib, params)
+        if r:
+            raise EngineError(f"fg_derive: {r}")
+        return model
+
+    def grain_into(self, dst: "DevPic", params: capi.FgParams, poc: int, check: bool = True) -> int:
+        """dst = this picture with the film grain `params` (the SEI's fields, derived once as for one picture) asks for at `poc`
+        (ovhip_fg_derive + ovhip_film_grain_launch).  Asynchronous."""
+        model = self._fg_model(params)
+        r = self.ctx.lib.ovhip_film_grain_launch(self.ctx.h, C.byref(self.s), C.byref(model), poc, 0, C.byref(dst.s))
+        if check:
+            self.ctx._chk(r, "film_grain")
+        return r
+
+    def output_grain(self, params: capi.FgParams, poc: int, window=(0, 0, 0, 0)) -> np.ndarray:
+        """output() of the picture with film grain"""
+        model, win = self._fg_model(params), capi.Window(*window)
+        n = self.ctx.lib.ovhip_output_bytes(self.w, self.h, C.byref(win))
+        if not n:
+            raise EngineError("output window leaves nothing")
+        out = np.empty(n // 2, np.uint16)
+        self.ctx._chk(self.ctx.lib.ovhip_pic_output_grain(self.ctx.h, C.byref(self.s), C.byref(model), poc, C.byref(win), out.ctypes.data),
+                      "pic_output_grain")
+        return out
+
+    def digest_grain(self, params: capi.FgParams, poc: int, window=(0, 0, 0, 0)) -> bytes:
+        model, win = self._fg_model(params), capi.Window(*window)
+        out = (C.c_uint8 * 16)()
+        self.ctx._chk(self.ctx.lib.ovhip_pic_digest_grain(self.ctx.h, C.byref(self.s), C.byref(model), poc, C.byref(win), out), "pic_digest_grain")
+        return bytes(out)
+
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
         win = capi.Window(*window)
         rows = self.ctx.lib.ovhip_output_rows(self.w, self.h, C.byref(win))
@@ -794,6 +826,13 @@ class Frame:
     def fail(self, status: int = -3):
         self.lib.ovhip_frame_fail(self.f, status)
 
+    def set_film_grain(self, params, poc: int = 0, check: bool = True) -> int:
+        """ovhip_frame_set_film_grain: the outputs deliver the picture with film grain at `poc`; params None switches it off"""
+        r = self.lib.ovhip_frame_set_film_grain(self.f, C.byref(params) if params is not None else None, poc)
+        if check and r:
+            raise EngineError(f"frame_set_film_grain: {r}")
+        return r
+
     def set_output_scale(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
         """the frame's outputs deliver the picture resampled to out_w x out_h; (0, 0) switches it off"""
         info = capi.ScaleInfo(*scale_window, *col)
@@ -850,6 +889,13 @@ class Stream:
         if self.s:
             self.lib.ovhip_stream_destroy(self.s)
             self.s = None
+
+    def set_film_grain(self, params, check: bool = True) -> int:
+        """ovhip_stream_set_film_grain: every picture of the following runs leaves with film grain at its own POC; None: off"""
+        r = self.lib.ovhip_stream_set_film_grain(self.s, C.byref(params) if params is not None else None)
+        if check and r:
+            raise EngineError(f"stream_set_film_grain: {r}")
+        return r
 
     def set_output_scale(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
         """before a run: the PACKED frames / DIGEST fingerprints are those of the pictures resampled to out_w x out_h; (0, 0): off"""
