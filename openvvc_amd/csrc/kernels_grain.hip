@@ -97,10 +97,10 @@ __global__ __launch_bounds__(64) void k_film_grain_seeds(FgArgs a)
 {
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= a.n_groups) return;
-    const int pl = b >= a.first[2] ? 2 : (b >= a.first[1] ? 1 : 0);
+    const int pl = ov_tile_plane(a, b);
     const FgPlane p = pl == 0 ? a.p[0] : (pl == 1 ? a.p[1] : a.p[2]);
     if (!p.present) return;
-    const int t = b - (pl == 0 ? a.first[0] : (pl == 1 ? a.first[1] : a.first[2]));
+    const int t = ov_tile_index(a, b, pl);
     const int ty = t / p.ntx, tx = t - ty * p.ntx;
     uint32_t sd = a.seeds[p.seed0 + ty];
     for (int i = 0; i < tx * (FG_TW / 16) - 1; ++i) sd = fg_prng(sd);
@@ -110,9 +110,9 @@ __global__ __launch_bounds__(64) void k_film_grain_seeds(FgArgs a)
 __global__ __launch_bounds__(FG_NT) void k_film_grain(FgArgs a)
 {
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const int pl = b >= a.first[2] ? 2 : (b >= a.first[1] ? 1 : 0);
+    const int pl = ov_tile_plane(a, b);
     const FgPlane p = pl == 0 ? a.p[0] : (pl == 1 ? a.p[1] : a.p[2]);
-    const int t = b - (pl == 0 ? a.first[0] : (pl == 1 ? a.first[1] : a.first[2]));
+    const int t = ov_tile_index(a, b, pl);
     const int ty = t / p.ntx, tx = t - ty * p.ntx;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int bx = lane >> 3, r = lane & 7;
@@ -186,13 +186,6 @@ __global__ __launch_bounds__(FG_NT) void k_film_grain(FgArgs a)
 }
 
 // ---- host ----
-bool fg_overlap(const uint16_t *a, const ovhip_pic *pa, int pla, const uint16_t *b, const ovhip_pic *pb, int plb)
-{
-    const size_t na = (size_t)((pla ? pa->h / 2 : pa->h) - 1) * (size_t)(pla ? pa->stride_c : pa->stride_y) + (size_t)(pla ? pa->w / 2 : pa->w);
-    const size_t nb = (size_t)((plb ? pb->h / 2 : pb->h) - 1) * (size_t)(plb ? pb->stride_c : pb->stride_y) + (size_t)(plb ? pb->w / 2 : pb->w);
-    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
-}
-
 // first grain launch of a context: the database on the device, and a ring of FG_SLOTS page-locked slots (model + stripe seeds of one
 // launch) with their device copies.  A slot is written again only after the launch that read it has completed (its event).
 int fg_prepare(ovhip_ctx *ctx)
@@ -216,7 +209,10 @@ int fg_prepare(ovhip_ctx *ctx)
     return OVHIP_OK;
 }
 
-int fg_check(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, const char *who)
+} // namespace
+
+// library-internal (ovvc_dpb_priv.h): the checker
+extern "C" int ovhip_grain_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *pic, const ovhip_fg_model *model)
 {
     if (pic->w <= 0 || pic->h <= 0 || ((pic->w | pic->h) & 3) || pic->w > FG_MAX_DIM || pic->h > FG_MAX_DIM) {
         snprintf(ctx->err, sizeof(ctx->err), "%s: %dx%d: sizes have to be multiples of 4 (at most %d)", who, pic->w, pic->h, FG_MAX_DIM);
@@ -232,26 +228,18 @@ int fg_check(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, 
     return OVHIP_OK;
 }
 
-} // namespace
-
 extern "C" int ovhip_film_grain_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_fg_model *model, int32_t poc, int32_t idr_offset,
                                        const ovhip_pic *dst)
 {
     if (!ctx || !src || !model || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
-    if (!src->y || !src->cb || !src->cr || !dst->y || !dst->cb || !dst->cr)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_film_grain_launch: missing plane", hipSuccess);
-    if (src->w != dst->w || src->h != dst->h) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_film_grain_launch: src and dst differ in size", hipSuccess);
-    int r = fg_check(ctx, src, model, "ovhip_film_grain_launch");
+    int r = ov_src_dst_check(ctx, "ovhip_film_grain_launch", src, dst);
     if (r != OVHIP_OK) return r;
-    if (src->stride_y < src->w || src->stride_c < src->w / 2 || dst->stride_y < dst->w || dst->stride_c < dst->w / 2)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_film_grain_launch: stride below the width", hipSuccess);
+    if (src->w != dst->w || src->h != dst->h) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_film_grain_launch: src and dst differ in size", hipSuccess);
+    if ((r = ovhip_grain_refusal_(ctx, "ovhip_film_grain_launch", src, model)) != OVHIP_OK) return r;
+    if ((r = fg_prepare(ctx)) != OVHIP_OK) return r;
     const uint16_t *sp[3] = { src->y, src->cb, src->cr };
     uint16_t *dp[3] = { dst->y, dst->cb, dst->cr };
-    for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k)
-            if (fg_overlap(sp[i], src, i, dp[k], dst, k)) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_film_grain_launch: dst aliases src", hipSuccess);
-    if ((r = fg_prepare(ctx)) != OVHIP_OK) return r;
 
     const int slot = ctx->fg_next;
     ctx->fg_next = (slot + 1) % FG_SLOTS;
@@ -289,35 +277,4 @@ extern "C" int ovhip_film_grain_launch(ovhip_ctx *ctx, const ovhip_pic *src, con
     OV_HIP(ctx, hipEventRecord(ctx->fg_ev[slot], ctx->stream));
     ctx->fg_busy[slot] = 1;
     return OVHIP_OK;
-}
-
-// library-internal (ovvc_dpb_priv.h): `pic` with grain in the context's scratch picture, which is handed out in *grained (valid until the
-// context's next scaled or grained output).  Asynchronous on the context's stream.
-extern "C" int ovhip_grain_scratch_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, ovhip_pic *grained)
-{
-    if (!ctx || !pic || !model || !grained) return OVHIP_EINVAL;
-    OV_DEVICE(ctx);
-    // refusals first: nothing is allocated for a request that will not run
-    int r = fg_check(ctx, pic, model, "grained output");
-    if (r != OVHIP_OK) return r;
-    if ((r = ovhip_scratch_pic_(ctx, pic->w, pic->h, grained)) != OVHIP_OK) return r;
-    return ovhip_film_grain_launch(ctx, pic, model, poc, 0, grained);
-}
-
-extern "C" int ovhip_pic_output_grain(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, const ovhip_window *win,
-                                      void *host_dst)
-{
-    if (!ctx || !pic || !model || !host_dst) return OVHIP_EINVAL;
-    ovhip_pic grained;
-    const int r = ovhip_grain_scratch_(ctx, pic, model, poc, &grained);
-    return r != OVHIP_OK ? r : ovhip_pic_output(ctx, &grained, win, host_dst);
-}
-
-extern "C" int ovhip_pic_digest_grain(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, const ovhip_window *win,
-                                      uint8_t out16[16])
-{
-    if (!ctx || !pic || !model || !out16) return OVHIP_EINVAL;
-    ovhip_pic grained;
-    const int r = ovhip_grain_scratch_(ctx, pic, model, poc, &grained);
-    return r != OVHIP_OK ? r : ovhip_pic_digest(ctx, &grained, win, out16);
 }

@@ -1,11 +1,13 @@
 // Output path: conformance-window crop + pack into the byte layout examples/dectest.c:372-409 writes, and per-row
-// MD5 digests on the device (see include/ovvc_hip.h, "Output path").
+// MD5 digests on the device (see include/ovvc_hip.h, "Output path"); and the one post-process step in front of every delivery
+// (ovhip_post_pic_ / ovhip_post_deliver_, ovvc_dpb_priv.h): none, resampled (kernels_scale.hip) or grained (kernels_grain.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 #include "ovvc_hip.h"
 #include "ovvc_common.hip.h"
+#include "ovvc_dpb_priv.h"
 
 namespace {
 
@@ -333,4 +335,91 @@ extern "C" int ovhip_pic_digest(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhi
     if (!r && ov_sync_stream(ctx) != hipSuccess) r = ov_fail(ctx, OVHIP_ELAUNCH, "ovhip_pic_digest", hipGetLastError());
     if (!r) { ovhip_md5_state st; ovhip_md5_init(&st); ovhip_md5_update(&st, hbuf, nb * 16); ovhip_md5_final(&st, out); }
     return r;
+}
+
+// ---- post-process, then deliver (ovvc_dpb_priv.h) ----
+// the context's grow-only scratch picture at w x h (three tight planes in one allocation, laid out as ovhip_pic_alloc does)
+static int post_scratch(ovhip_ctx *ctx, int32_t w, int32_t h, ovhip_pic *pic)
+{
+    const size_t ysz = ((size_t)w * h * 2 + 255) & ~(size_t)255;
+    const size_t csz = ((size_t)(w / 2) * (h / 2) * 2 + 255) & ~(size_t)255;
+    if (ysz + 2 * csz > ctx->post_d_cap) {
+        if (ctx->post_d) (void)hipFree(ctx->post_d);
+        ctx->post_d = nullptr; ctx->post_d_cap = 0;
+        hipError_t e = hipMalloc(&ctx->post_d, ysz + 2 * csz);
+        if (e != hipSuccess) return ov_fail(ctx, OVHIP_ENOMEM, "hipMalloc(scaled output picture)", e);
+        ctx->post_d_cap = ysz + 2 * csz;
+    }
+    pic->y = (uint16_t *)ctx->post_d;
+    pic->cb = (uint16_t *)((char *)ctx->post_d + ysz);
+    pic->cr = (uint16_t *)((char *)ctx->post_d + ysz + csz);
+    pic->w = w; pic->h = h; pic->stride_y = w; pic->stride_c = w / 2;
+    return OVHIP_OK;
+}
+
+extern "C" int ovhip_post_pic_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_pic *shown)
+{
+    if (!ctx || !pic || !post || !shown) return OVHIP_EINVAL;
+    if (post->kind == OVHIP_POST_NONE) { *shown = *pic; return OVHIP_OK; }
+    const bool scale = post->kind == OVHIP_POST_SCALE;
+    if (!scale && (post->kind != OVHIP_POST_GRAIN || !post->model)) return OVHIP_EINVAL;
+    OV_DEVICE(ctx);
+    // refusals first: nothing is allocated for a request that will not run
+    int r = scale ? ovhip_scale_refusal_(ctx, "scaled output", pic, &post->info, post->out_w, post->out_h)
+                  : ovhip_grain_refusal_(ctx, "grained output", pic, post->model);
+    if (r == OVHIP_OK) r = post_scratch(ctx, scale ? post->out_w : pic->w, scale ? post->out_h : pic->h, shown);
+    if (r != OVHIP_OK) return r;
+    return scale ? ovhip_output_scale_launch(ctx, pic, &post->info, shown) : ovhip_film_grain_launch(ctx, pic, post->model, post->poc, 0, shown);
+}
+
+extern "C" int ovhip_post_deliver_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_frame_output *out)
+{
+    if (!out || out->mode < OVHIP_OUT_DIGEST || out->mode > OVHIP_OUT_PACKED) return OVHIP_EINVAL;       // before anything is launched
+    ovhip_pic shown;
+    const int r = ovhip_post_pic_(ctx, pic, post, &shown);
+    if (r != OVHIP_OK) return r;
+    if (out->mode == OVHIP_OUT_DIGEST) return ovhip_pic_digest(ctx, &shown, &out->window, out->digest);
+    if (out->mode == OVHIP_OUT_PLANES) return ovhip_pic_download(ctx, &shown, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
+    return ovhip_pic_output(ctx, &shown, &out->window, out->packed);
+}
+
+// The four conveniences of the header: their argument checks, then one call of the above -- PACKED into `packed`, or (packed == NULL)
+// DIGEST into out16.  win == NULL is the empty window.
+static int post_convenience(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ &post, const ovhip_window *win, void *packed, uint8_t *out16)
+{
+    ovhip_frame_output out = {};
+    out.mode = packed ? OVHIP_OUT_PACKED : OVHIP_OUT_DIGEST;
+    if (win) out.window = *win;
+    out.packed = packed;
+    const int r = ovhip_post_deliver_(ctx, pic, &post, &out);
+    if (r == OVHIP_OK && out16) memcpy(out16, out.digest, 16);
+    return r;
+}
+
+extern "C" int ovhip_pic_output_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h,
+                                       const ovhip_window *win, void *host_dst)
+{
+    if (!ctx || !pic || !info || !host_dst) return OVHIP_EINVAL;
+    return post_convenience(ctx, pic, { OVHIP_POST_SCALE, out_w, out_h, *info, nullptr, 0 }, win, host_dst, nullptr);
+}
+
+extern "C" int ovhip_pic_digest_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h,
+                                       const ovhip_window *win, uint8_t out16[16])
+{
+    if (!ctx || !pic || !info || !out16) return OVHIP_EINVAL;
+    return post_convenience(ctx, pic, { OVHIP_POST_SCALE, out_w, out_h, *info, nullptr, 0 }, win, nullptr, out16);
+}
+
+extern "C" int ovhip_pic_output_grain(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, const ovhip_window *win,
+                                      void *host_dst)
+{
+    if (!ctx || !pic || !model || !host_dst) return OVHIP_EINVAL;
+    return post_convenience(ctx, pic, { OVHIP_POST_GRAIN, 0, 0, {}, model, poc }, win, host_dst, nullptr);
+}
+
+extern "C" int ovhip_pic_digest_grain(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, const ovhip_window *win,
+                                      uint8_t out16[16])
+{
+    if (!ctx || !pic || !model || !out16) return OVHIP_EINVAL;
+    return post_convenience(ctx, pic, { OVHIP_POST_GRAIN, 0, 0, {}, model, poc }, win, nullptr, out16);
 }

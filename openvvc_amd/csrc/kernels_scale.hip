@@ -154,9 +154,9 @@ __global__ __launch_bounds__(SC_NT) void k_output_scale(ScaleArgs a)
     __shared__ __attribute__((aligned(16))) uint16_t s_src[SC_ROWS * SC_SRCW];
     __shared__ __attribute__((aligned(16))) int s_tmp[SC_ROWS * SC_TMPS];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const int pl = b >= a.first[2] ? 2 : (b >= a.first[1] ? 1 : 0);
+    const int pl = ov_tile_plane(a, b);
     const ScalePlane p = pl == 0 ? a.p[0] : (pl == 1 ? a.p[1] : a.p[2]);
-    const int t = b - (pl == 0 ? a.first[0] : (pl == 1 ? a.first[1] : a.first[2]));
+    const int t = ov_tile_index(a, b, pl);
     const int ty = t / p.ntx, tx = t - ty * p.ntx;
     if (pl == 0) scale_tile<8>(p, tx, ty, s_src, s_tmp, tid);
     else         scale_tile<4>(p, tx, ty, s_src, s_tmp, tid);
@@ -193,39 +193,14 @@ int scale_check(int32_t src_w, int32_t src_h, const ovhip_scale_info *info, int3
     return OVHIP_OK;
 }
 
-bool overlap(const uint16_t *a, const ovhip_pic *pa, int pla, const uint16_t *b, const ovhip_pic *pb, int plb)
+// scale_check with the reason of a refusal in the context's error text
+int scale_check_said(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h, PlaneScale ps[2])
 {
-    const size_t na = (size_t)((pla ? pa->h / 2 : pa->h) - 1) * (size_t)(pla ? pa->stride_c : pa->stride_y) + (size_t)(pla ? pa->w / 2 : pa->w);
-    const size_t nb = (size_t)((plb ? pb->h / 2 : pb->h) - 1) * (size_t)(plb ? pb->stride_c : pb->stride_y) + (size_t)(plb ? pb->w / 2 : pb->w);
-    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
-}
-
-// the context's grow-only scratch picture at w x h (three tight planes in one allocation, laid out as ovhip_pic_alloc does)
-int scale_scratch(ovhip_ctx *ctx, int32_t w, int32_t h, ovhip_pic *pic)
-{
-    const size_t ysz = ((size_t)w * h * 2 + 255) & ~(size_t)255;
-    const size_t csz = ((size_t)(w / 2) * (h / 2) * 2 + 255) & ~(size_t)255;
-    if (ysz + 2 * csz > ctx->scale_d_cap) {
-        if (ctx->scale_d) (void)hipFree(ctx->scale_d);
-        ctx->scale_d = nullptr; ctx->scale_d_cap = 0;
-        hipError_t e = hipMalloc(&ctx->scale_d, ysz + 2 * csz);
-        if (e != hipSuccess) return ov_fail(ctx, OVHIP_ENOMEM, "hipMalloc(scaled output picture)", e);
-        ctx->scale_d_cap = ysz + 2 * csz;
-    }
-    pic->y = (uint16_t *)ctx->scale_d;
-    pic->cb = (uint16_t *)((char *)ctx->scale_d + ysz);
-    pic->cr = (uint16_t *)((char *)ctx->scale_d + ysz + csz);
-    pic->w = w; pic->h = h; pic->stride_y = w; pic->stride_c = w / 2;
-    return OVHIP_OK;
-}
-
-// the refusals of scale_check with their reason in the context's error text
-int scale_refuse(ovhip_ctx *ctx, int r, const char *who, const ovhip_pic *src, int32_t dst_w, int32_t dst_h, const PlaneScale ps[2])
-{
+    const int r = scale_check(src->w, src->h, info, dst_w, dst_h, ps);
     if (r == OVHIP_EUNSUP)
         snprintf(ctx->err, sizeof(ctx->err), "%s: %dx%d -> %dx%d is down-sampling (luma factors %d, %d of %d; chroma %d, %d of %d): the reference's 12-tap "
                  "path is not supported", who, src->w, src->h, dst_w, dst_h, ps[0].scale_hor, ps[0].scale_ver, 1 << 13, ps[1].scale_hor, ps[1].scale_ver, 1 << 14);
-    else
+    else if (r != OVHIP_OK)
         snprintf(ctx->err, sizeof(ctx->err), "%s: %dx%d -> %dx%d: sizes have to be multiples of 4 (at most %d) and the scaling window has to leave samples",
                  who, src->w, src->h, dst_w, dst_h, SC_MAX_DIM);
     return r;
@@ -242,22 +217,23 @@ extern "C" int ovhip_output_scale_check(int32_t src_w, int32_t src_h, const ovhi
     return r;
 }
 
+// library-internal (ovvc_dpb_priv.h)
+extern "C" int ovhip_scale_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h)
+{
+    PlaneScale ps[2] = {};
+    return scale_check_said(ctx, who, src, info, dst_w, dst_h, ps);
+}
+
 extern "C" int ovhip_output_scale_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_scale_info *info, const ovhip_pic *dst)
 {
     if (!ctx || !src || !info || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
-    if (!src->y || !src->cb || !src->cr || !dst->y || !dst->cb || !dst->cr)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_output_scale_launch: missing plane", hipSuccess);
     PlaneScale ps[2] = {};
-    const int r = scale_check(src->w, src->h, info, dst->w, dst->h, ps);
-    if (r != OVHIP_OK) return scale_refuse(ctx, r, "ovhip_output_scale_launch", src, dst->w, dst->h, ps);
-    if (src->stride_y < src->w || src->stride_c < src->w / 2 || dst->stride_y < dst->w || dst->stride_c < dst->w / 2)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_output_scale_launch: stride below the width", hipSuccess);
+    int r = ov_src_dst_check(ctx, "ovhip_output_scale_launch", src, dst);
+    if (r == OVHIP_OK) r = scale_check_said(ctx, "ovhip_output_scale_launch", src, info, dst->w, dst->h, ps);
+    if (r != OVHIP_OK) return r;
     const uint16_t *sp[3] = { src->y, src->cb, src->cr };
     uint16_t *dp[3] = { dst->y, dst->cb, dst->cr };
-    for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k)
-            if (overlap(sp[i], src, i, dp[k], dst, k)) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_output_scale_launch: dst aliases src", hipSuccess);
     ScaleArgs a;
     int n = 0;
     for (int i = 0; i < 3; ++i) {
@@ -276,39 +252,4 @@ extern "C" int ovhip_output_scale_launch(ovhip_ctx *ctx, const ovhip_pic *src, c
     hipLaunchKernelGGL(k_output_scale, dim3((unsigned)n), dim3(SC_NT), 0, ctx->stream, a);
     OV_LAUNCH_CHECK(ctx, "k_output_scale");
     return OVHIP_OK;
-}
-
-// library-internal (ovvc_dpb_priv.h): the scratch picture at w x h for the other user of it, the grained outputs (kernels_grain.hip)
-extern "C" int ovhip_scratch_pic_(ovhip_ctx *ctx, int32_t w, int32_t h, ovhip_pic *pic) { return scale_scratch(ctx, w, h, pic); }
-
-// library-internal (ovvc_dpb_priv.h): resample `pic` into the context's scratch picture and hand that out; the picture stays valid until
-// the context's next scaled output.  Asynchronous on the context's stream.
-extern "C" int ovhip_scaled_scratch_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h, ovhip_pic *scaled)
-{
-    if (!ctx || !pic || !info || !scaled) return OVHIP_EINVAL;
-    OV_DEVICE(ctx);
-    // refusals first: nothing is allocated for a request that will not run
-    PlaneScale ps[2] = {};
-    int r = scale_check(pic->w, pic->h, info, out_w, out_h, ps);
-    if (r != OVHIP_OK) return scale_refuse(ctx, r, "scaled output", pic, out_w, out_h, ps);
-    if ((r = scale_scratch(ctx, out_w, out_h, scaled)) != OVHIP_OK) return r;
-    return ovhip_output_scale_launch(ctx, pic, info, scaled);
-}
-
-extern "C" int ovhip_pic_output_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h,
-                                       const ovhip_window *win, void *host_dst)
-{
-    if (!ctx || !pic || !info || !host_dst) return OVHIP_EINVAL;
-    ovhip_pic scaled;
-    const int r = ovhip_scaled_scratch_(ctx, pic, info, out_w, out_h, &scaled);
-    return r != OVHIP_OK ? r : ovhip_pic_output(ctx, &scaled, win, host_dst);
-}
-
-extern "C" int ovhip_pic_digest_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h,
-                                       const ovhip_window *win, uint8_t out16[16])
-{
-    if (!ctx || !pic || !info || !out16) return OVHIP_EINVAL;
-    ovhip_pic scaled;
-    const int r = ovhip_scaled_scratch_(ctx, pic, info, out_w, out_h, &scaled);
-    return r != OVHIP_OK ? r : ovhip_pic_digest(ctx, &scaled, win, out16);
 }

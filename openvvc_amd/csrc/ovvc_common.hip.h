@@ -30,7 +30,7 @@ struct ovhip_ctx {
     // synchronise the whole device every time a picture is output
     void *scratch_d; size_t scratch_d_cap;
     void *scratch_h; size_t scratch_h_cap;       // page-locked
-    void *scale_d; size_t scale_d_cap;           // the scratch PICTURE of the scaled and grained outputs (kernels_scale.hip), grow-only likewise
+    void *post_d; size_t post_d_cap;             // the scratch PICTURE of the post-processed outputs (ovhip_post_pic_, kernels_output.hip), grow-only likewise
     // film grain (kernels_grain.hip), allocated at the context's first grain launch: the database followed by OV_FG_SLOTS slots (model +
     // stripe seeds of one launch, and the seeds k_film_grain_seeds makes of them per workgroup) on the device, the slots' page-locked staging, and per slot the event behind the launch that reads it
     void *fg_d; size_t fg_d_cap;
@@ -136,4 +136,37 @@ __device__ __forceinline__ uint16_t *ov_plane(const ovhip_pic &p, int plane, int
 {
     stride = plane ? p.stride_c : p.stride_y;
     return plane == 0 ? p.y : (plane == 1 ? p.cb : p.cr);
+}
+
+// ---- the plumbing of the kernels that take a picture's three planes in one grid (k_output_scale, k_film_grain) ----
+// item b of a grid in which the planes' tiles begin at a.first[0..2] (a: the kernel's argument struct): its plane, its tile there
+template <class Args> __device__ __forceinline__ int ov_tile_plane(const Args &a, int b) { return b >= a.first[2] ? 2 : (b >= a.first[1] ? 1 : 0); }
+template <class Args> __device__ __forceinline__ int ov_tile_index(const Args &a, int b, int pl)
+{
+    const int f0 = a.first[0], f1 = a.first[1], f2 = a.first[2];      // values, not a choice between three addresses
+    return b - (pl == 0 ? f0 : (pl == 1 ? f1 : f2));
+}
+
+// do the sample ranges of plane pla of pa (at a) and plane plb of pb (at b) overlap?
+static inline bool ov_planes_overlap(const uint16_t *a, const ovhip_pic *pa, int pla, const uint16_t *b, const ovhip_pic *pb, int plb)
+{
+    const size_t na = (size_t)((pla ? pa->h / 2 : pa->h) - 1) * (size_t)(pla ? pa->stride_c : pa->stride_y) + (size_t)(pla ? pa->w / 2 : pa->w);
+    const size_t nb = (size_t)((plb ? pb->h / 2 : pb->h) - 1) * (size_t)(plb ? pb->stride_c : pb->stride_y) + (size_t)(plb ? pb->w / 2 : pb->w);
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+// what a launch from src into dst refuses whatever it computes, under the entry point's name `who`.  Asked before the kernel's own
+// checker, so the sizes may still be anything: without samples nothing overlaps, and the checker refuses next.
+static inline int ov_src_dst_check(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_pic *dst)
+{
+    const char *what = nullptr;
+    const uint16_t *sp[3] = { src->y, src->cb, src->cr }, *dp[3] = { dst->y, dst->cb, dst->cr };
+    if (!src->y || !src->cb || !src->cr || !dst->y || !dst->cb || !dst->cr) what = "missing plane";
+    else if (src->stride_y < src->w || src->stride_c < src->w / 2 || dst->stride_y < dst->w || dst->stride_c < dst->w / 2) what = "stride below the width";
+    const bool sized = src->w > 0 && src->h > 0 && dst->w > 0 && dst->h > 0;
+    for (int i = 0; i < 3 && sized && !what; ++i)
+        for (int k = 0; k < 3 && !what; ++k)
+            if (ov_planes_overlap(sp[i], src, i, dp[k], dst, k)) what = "dst aliases src";
+    if (what) snprintf(ctx->err, sizeof(ctx->err), "%s: %s: invalid argument", who, what);       // (as ov_fail words it)
+    return what ? OVHIP_EINVAL : OVHIP_OK;
 }

@@ -1,5 +1,5 @@
-/* ovvc_dpb_priv.h -- library-internal links between the DPB state machine (ovvc_dpb.c), its HIP back-end (ovvc_dpb_hip.hip)
- * and the stream driver (ovvc_stream.c). */
+/* ovvc_dpb_priv.h -- library-internal links between the DPB state machine (ovvc_dpb.c), its HIP back-end (ovvc_dpb_hip.hip),
+ * the frame and stream drivers (ovvc_frame.c, ovvc_stream.c) and the output path's .hip files. */
 #ifndef OVVC_DPB_PRIV_H
 #define OVVC_DPB_PRIV_H
 #include "ovvc_hip.h"
@@ -12,13 +12,26 @@ void ovhip_dpb_rearm_(ovhip_dpb *d);
 /* CLOCK_MONOTONIC seconds at which the frame's last picture was complete on the device / published (the stream driver's timeline) */
 double ovhip_frame_published_at(const ovhip_frame *f);
 double ovhip_frame_done_at(const ovhip_frame *f);
-/* kernels_scale.hip: `pic` resampled to out_w x out_h in the context's scratch picture, which is handed out in *scaled (valid until the
- * context's next scaled output); asynchronous on the context's stream */
-int  ovhip_scaled_scratch_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_scale_info *info, int32_t out_w, int32_t out_h, ovhip_pic *scaled);
-/* kernels_scale.hip: that scratch picture at w x h, no launch; kernels_grain.hip: `pic` with film grain in it (valid until the context's
- * next scaled or grained output); asynchronous on the context's stream */
-int  ovhip_scratch_pic_(ovhip_ctx *ctx, int32_t w, int32_t h, ovhip_pic *pic);
-int  ovhip_grain_scratch_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_fg_model *model, int32_t poc, ovhip_pic *grained);
+/* ---- the post-process step of the output path (kernels_output.hip): what happens to a finished picture on its way out.  One kind at
+ * a time: the reference resamples the UNgrained frame over the grained one, so there is no parity to offer for both. */
+enum { OVHIP_POST_NONE = 0, OVHIP_POST_SCALE, OVHIP_POST_GRAIN };
+typedef struct ovhip_post_ {
+    int kind;
+    int32_t out_w, out_h; ovhip_scale_info info;       /* SCALE: the output size and the scaling window / chroma collocation */
+    const ovhip_fg_model *model; int32_t poc;          /* GRAIN: an already derived model (ovhip_fg_derive) and the picture's POC */
+} ovhip_post_;
+/* *shown = the picture the output shows.  NONE: *pic itself, nothing launched, nothing allocated.  Otherwise the refusals of the kind's
+ * launcher come first (same codes, reasons in the context's error text), then `pic` is resampled / grained into the context's
+ * grow-only scratch picture, asynchronously on the context's stream, and that is handed out: it stays valid until the context's next
+ * post-processed output.  `pic` is only read. */
+int  ovhip_post_pic_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_pic *shown);
+/* ovhip_post_pic_, then the delivery out->mode names: DIGEST -> ovhip_pic_digest (into out->digest: why `out` is not const), PLANES ->
+ * ovhip_pic_download, PACKED -> ovhip_pic_output; any other mode is OVHIP_EINVAL.  out->window applies to the picture shown. */
+int  ovhip_post_deliver_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_frame_output *out);
+/* the launchers' own refusals (kernels_scale.hip, kernels_grain.hip) under the name `who`: ovhip_post_pic_ asks before it allocates */
+#define OVHIP_HIDDEN_ __attribute__((visibility("hidden")))
+OVHIP_HIDDEN_ int ovhip_scale_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h);
+OVHIP_HIDDEN_ int ovhip_grain_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *pic, const ovhip_fg_model *model);
 #ifdef __cplusplus
 }
 #endif

@@ -44,11 +44,9 @@ struct ovhip_frame {
     ovhip_band_counts band_prev;
     int32_t band_row_prev, band_rows_posted, dry_row_prev2;
     int n_bands, n_deferred;
-    /* ovhip_frame_set_output_scale: the outputs deliver the picture resampled to out_w x out_h (0: off) */
-    int32_t out_w, out_h;
-    ovhip_scale_info out_info;
-    /* ovhip_frame_set_film_grain: the outputs deliver the picture with film grain, derived afresh from fg for every picture */
-    int fg_on; int32_t fg_poc;
+    /* what the outputs do to the picture first (ovvc_dpb_priv.h).  SCALE (ovhip_frame_set_output_scale): resampled to post.out_w x
+     * post.out_h; GRAIN (ovhip_frame_set_film_grain): with film grain at post.poc, the model derived afresh from fg for every picture */
+    ovhip_post_ post;
     ovhip_fg_params fg;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
@@ -376,16 +374,17 @@ int
 ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_scale_info *info)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!out_w && !out_h) { f->out_w = f->out_h = 0; return OVHIP_OK; }
-    if (f->fg_on) return OVHIP_EUNSUP;    /* the reference resamples the UNgrained frame over the grained one: no parity to offer */
-    if (f->dry) { f->out_w = out_w; f->out_h = out_h; return OVHIP_OK; }          /* a dry frame has no output: only remembered */
+    if (!out_w && !out_h) { if (f->post.kind == OVHIP_POST_SCALE) f->post.kind = OVHIP_POST_NONE; return OVHIP_OK; }
+    if (f->post.kind == OVHIP_POST_GRAIN) return OVHIP_EUNSUP;    /* the reference resamples the UNgrained frame over the grained one: no parity to offer */
     ovhip_scale_info si;
-    int32_t scale[4];
     memset(&si, 0, sizeof(si));
     if (info) si = *info;
-    const int r = ovhip_output_scale_check(f->w, f->h, &si, out_w, out_h, scale);
-    if (r != OVHIP_OK) return r;
-    f->out_w = out_w; f->out_h = out_h; f->out_info = si;
+    if (!f->dry) {                                                /* (a dry frame has no output: only remembered) */
+        int32_t scale[4];
+        const int r = ovhip_output_scale_check(f->w, f->h, &si, out_w, out_h, scale);
+        if (r != OVHIP_OK) return r;
+    }
+    f->post.kind = OVHIP_POST_SCALE; f->post.out_w = out_w; f->post.out_h = out_h; f->post.info = si;
     return OVHIP_OK;
 }
 
@@ -393,53 +392,28 @@ int
 ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_t poc)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!params) { f->fg_on = 0; return OVHIP_OK; }
-    if (f->out_w) return OVHIP_EUNSUP;
+    if (!params) { if (f->post.kind == OVHIP_POST_GRAIN) f->post.kind = OVHIP_POST_NONE; return OVHIP_OK; }
+    if (f->post.kind == OVHIP_POST_SCALE) return OVHIP_EUNSUP;
     ovhip_fg_model model;
     const int r = ovhip_fg_derive(params, &model, NULL);      /* the refusals come back here, not from a picture's output */
     if (r != OVHIP_OK) return r;
-    f->fg = *params; f->fg_poc = poc; f->fg_on = 1;           /* (a dry frame has no output: only remembered) */
+    f->post.kind = OVHIP_POST_GRAIN; f->post.poc = poc; f->fg = *params;      /* (a dry frame has no output: only remembered) */
     return OVHIP_OK;
 }
 
-/* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the decoded picture as it is, or
- * (ovhip_frame_set_output_scale / ovhip_frame_set_film_grain) resampled / grained into the context's scratch picture first -- f->dst
- * itself is only read */
+/* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the frame's post-process step (if any:
+ * into the context's scratch picture -- f->dst itself is only read), then the delivery `out` names */
 static int
 frame_output(ovhip_frame *f, ovhip_frame_output *out)
 {
-    if (f->fg_on) {
-        ovhip_fg_model model;
-        ovhip_pic grained;
-        int r = ovhip_fg_derive(&f->fg, &model, NULL);
+    ovhip_post_ post = f->post;
+    ovhip_fg_model model;
+    if (post.kind == OVHIP_POST_GRAIN) {
+        const int r = ovhip_fg_derive(&f->fg, &model, NULL);
         if (r != OVHIP_OK) return r;
-        switch (out->mode) {
-        case OVHIP_OUT_DIGEST: return ovhip_pic_digest_grain(f->ctx, &f->dst, &model, f->fg_poc, &out->window, out->digest);
-        case OVHIP_OUT_PLANES:
-            r = ovhip_grain_scratch_(f->ctx, &f->dst, &model, f->fg_poc, &grained);
-            return r != OVHIP_OK ? r : ovhip_pic_download(f->ctx, &grained, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
-        case OVHIP_OUT_PACKED: return ovhip_pic_output_grain(f->ctx, &f->dst, &model, f->fg_poc, &out->window, out->packed);
-        default: return OVHIP_EINVAL;
-        }
+        post.model = &model;
     }
-    if (!f->out_w) {
-        switch (out->mode) {
-        case OVHIP_OUT_DIGEST: return ovhip_pic_digest(f->ctx, &f->dst, &out->window, out->digest);
-        case OVHIP_OUT_PLANES: return ovhip_pic_download(f->ctx, &f->dst, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
-        case OVHIP_OUT_PACKED: return ovhip_pic_output(f->ctx, &f->dst, &out->window, out->packed);
-        default: return OVHIP_EINVAL;
-        }
-    }
-    switch (out->mode) {
-    case OVHIP_OUT_DIGEST: return ovhip_pic_digest_scaled(f->ctx, &f->dst, &f->out_info, f->out_w, f->out_h, &out->window, out->digest);
-    case OVHIP_OUT_PLANES: {
-        ovhip_pic scaled;
-        const int r = ovhip_scaled_scratch_(f->ctx, &f->dst, &f->out_info, f->out_w, f->out_h, &scaled);
-        return r != OVHIP_OK ? r : ovhip_pic_download(f->ctx, &scaled, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
-    }
-    case OVHIP_OUT_PACKED: return ovhip_pic_output_scaled(f->ctx, &f->dst, &f->out_info, f->out_w, f->out_h, &out->window, out->packed);
-    default: return OVHIP_EINVAL;
-    }
+    return ovhip_post_deliver_(f->ctx, &f->dst, &post, out);
 }
 
 int

@@ -48,8 +48,7 @@ struct ovhip_stream {
                                            * ask the DPB for it: a key the DPB never saw is an error there, not a wait) */
     pthread_mutex_t begun_mtx; pthread_cond_t begun_cnd;
     int n_moved, n_sharing;               /* streams replaced to clear the look-ahead thread's hardware queue / still sharing it */
-    int32_t out_w, out_h; ovhip_scale_info out_info;     /* ovhip_stream_set_output_scale (0: off) */
-    int fg_on; ovhip_fg_params fg;                       /* ovhip_stream_set_film_grain */
+    ovhip_post_ post; ovhip_fg_params fg;  /* what the outputs do to a picture first (ovvc_dpb_priv.h): ovhip_stream_set_output_scale / _set_film_grain */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -223,7 +222,7 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         out.mode = ((rs->flags & OVHIP_STREAM_DIGESTS) || s->cfg.output == OVHIP_OUT_DIGEST) ? OVHIP_OUT_DIGEST : OVHIP_OUT_NONE;
         out.window = s->cfg.window;
         if (tr) tr[1] = now_s() - rs->t0;
-        if (s->fg_on) (void)ovhip_frame_set_film_grain(f, &s->fg, p->poc);      /* (validated by the stream's setter) */
+        if (s->post.kind == OVHIP_POST_GRAIN) (void)ovhip_frame_set_film_grain(f, &s->fg, p->poc);      /* (validated by the stream's setter) */
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
@@ -331,13 +330,11 @@ output_thread(void *argp)
         int r = ovhip_dpb_acquire(s->dpb, key_of(s, idx), p->device, &pic, NULL);
         if (r != OVHIP_OK) { if (!rs->abort) run_fail(rs, r, "output: picture not available", ""); break; }
         ovhip_ctx *ctx = s->out_ctx[p->device];
-        if (s->fg_on) {
-            ovhip_fg_model model;
-            r = ovhip_fg_derive(&s->fg, &model, NULL);
-            if (r == OVHIP_OK) r = ovhip_pic_output_grain(ctx, &pic, &model, p->poc, &s->cfg.window, s->out_host);
-        } else
-            r = s->out_w ? ovhip_pic_output_scaled(ctx, &pic, &s->out_info, s->out_w, s->out_h, &s->cfg.window, s->out_host)
-                         : ovhip_pic_output(ctx, &pic, &s->cfg.window, s->out_host);
+        ovhip_post_ post = s->post;
+        ovhip_fg_model model;
+        ovhip_frame_output out = { .mode = OVHIP_OUT_PACKED, .window = s->cfg.window, .packed = s->out_host };
+        if (post.kind == OVHIP_POST_GRAIN) { r = ovhip_fg_derive(&s->fg, &model, NULL); post.model = &model; post.poc = p->poc; }      /* afresh per picture */
+        if (r == OVHIP_OK) r = ovhip_post_deliver_(ctx, &pic, &post, &out);
         if (r == OVHIP_OK) {
             if (rs->flags & OVHIP_STREAM_FILE_MD5) ovhip_md5_update(&rs->md5, s->out_host, s->out_host_bytes);
             rs->res->out_bytes += s->out_host_bytes;
@@ -462,53 +459,61 @@ int ovhip_stream_queue_info(const ovhip_stream *s, int *moved, int *sharing)
     return OVHIP_OK;
 }
 
+/* the output thread's page-locked frame follows the size the pictures leave at under `post` (PACKED only) */
+static int
+out_host_follows(ovhip_stream *s, const ovhip_post_ *post)
+{
+    if (s->cfg.output != OVHIP_OUT_PACKED) return OVHIP_OK;
+    const int scaled = post->kind == OVHIP_POST_SCALE;
+    const size_t bytes = ovhip_output_bytes(scaled ? post->out_w : s->cfg.w, scaled ? post->out_h : s->cfg.h, &s->cfg.window);
+    if (!bytes) return OVHIP_EINVAL;
+    if (bytes != s->out_host_bytes) {
+        void *p = ovhip_host_alloc(bytes);
+        if (!p) return OVHIP_ENOMEM;
+        ovhip_host_free(s->out_host);
+        s->out_host = p; s->out_host_bytes = bytes;
+    }
+    return OVHIP_OK;
+}
+
 int
 ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, const ovhip_scale_info *info)
 {
     if (!s) return OVHIP_EINVAL;
-    const int on = out_w || out_h;
-    if (on && s->fg_on) return OVHIP_EUNSUP;
-    ovhip_scale_info si;
-    memset(&si, 0, sizeof(si));
-    if (on) {
+    ovhip_post_ post = s->post;
+    int r = OVHIP_OK;
+    if (out_w || out_h) {
+        if (post.kind == OVHIP_POST_GRAIN) return OVHIP_EUNSUP;
         int32_t scale[4];
-        if (info) si = *info;
-        const int r = ovhip_output_scale_check(s->cfg.w, s->cfg.h, &si, out_w, out_h, scale);
-        if (r != OVHIP_OK) return r;
-    }
-    if (s->cfg.output == OVHIP_OUT_PACKED) {
-        /* the output thread's page-locked frame follows the output size */
-        const size_t bytes = on ? ovhip_output_bytes(out_w, out_h, &s->cfg.window) : ovhip_output_bytes(s->cfg.w, s->cfg.h, &s->cfg.window);
-        if (!bytes) return OVHIP_EINVAL;
-        if (bytes != s->out_host_bytes) {
-            void *p = ovhip_host_alloc(bytes);
-            if (!p) return OVHIP_ENOMEM;
-            ovhip_host_free(s->out_host);
-            s->out_host = p; s->out_host_bytes = bytes;
-        }
-    }
+        post.kind = OVHIP_POST_SCALE; post.out_w = out_w; post.out_h = out_h;
+        memset(&post.info, 0, sizeof(post.info));
+        if (info) post.info = *info;
+        r = ovhip_output_scale_check(s->cfg.w, s->cfg.h, &post.info, out_w, out_h, scale);
+    } else if (post.kind == OVHIP_POST_SCALE)
+        post.kind = OVHIP_POST_NONE;
+    if (r == OVHIP_OK) r = out_host_follows(s, &post);
     /* the frame threads' DIGEST path */
-    for (int i = 0; i < s->n_dev * s->tpd; ++i) {
-        const int r = ovhip_frame_set_output_scale(s->frames[i], out_w, out_h, &si);
-        if (r != OVHIP_OK) return r;
-    }
-    s->out_w = on ? out_w : 0; s->out_h = on ? out_h : 0; s->out_info = si;
-    return OVHIP_OK;
+    for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_output_scale(s->frames[i], out_w, out_h, &post.info);
+    if (r == OVHIP_OK) s->post = post;
+    return r;
 }
 
 int
 ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params)
 {
     if (!s) return OVHIP_EINVAL;
-    if (params && s->out_w) return OVHIP_EUNSUP;
+    ovhip_post_ post = s->post;
+    if (params) {
+        if (post.kind == OVHIP_POST_SCALE) return OVHIP_EUNSUP;
+        post.kind = OVHIP_POST_GRAIN;
+    } else if (post.kind == OVHIP_POST_GRAIN)
+        post.kind = OVHIP_POST_NONE;
     /* the frame threads' DIGEST path; with params the first frame's answer is every frame's (each picture sets its own POC later) */
-    for (int i = 0; i < s->n_dev * s->tpd; ++i) {
-        const int r = ovhip_frame_set_film_grain(s->frames[i], params, 0);
-        if (r != OVHIP_OK) return r;
-    }
-    s->fg_on = params != NULL;
-    if (params) s->fg = *params;
-    return OVHIP_OK;
+    int r = OVHIP_OK;
+    for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_film_grain(s->frames[i], params, 0);
+    if (r == OVHIP_OK) r = out_host_follows(s, &post);          /* (grain leaves the size alone: nothing moves today) */
+    if (r == OVHIP_OK) { s->post = post; if (params) s->fg = *params; }
+    return r;
 }
 
 ovhip_frame *

@@ -319,23 +319,29 @@ class DevPic:
                                                       cr.ctypes.data, self.w, self.w // 2), "pic_download")
         return y, cb, cr
 
-    def output(self, window=(0, 0, 0, 0)) -> np.ndarray:
-        """The cropped frame in the byte layout dectest.c:372-409 writes (uint16 LE: Y rows, Cb rows, Cr rows), packed on the
-        device and fetched with one D2H.  window = (lft, rgt, abv, blw) in chroma sample units."""
+    def _packed(self, w: int, h: int, window, fn: str, *args) -> np.ndarray:
+        """size the array for a w x h picture cropped by `window`, call lib.ovhip_<fn>(ctx, pic, *args, window, array), check"""
         win = capi.Window(*window)
-        n = self.ctx.lib.ovhip_output_bytes(self.w, self.h, C.byref(win))
+        n = self.ctx.lib.ovhip_output_bytes(w, h, C.byref(win))
         if not n:
             raise EngineError("output window leaves nothing")
         out = np.empty(n // 2, np.uint16)
-        self.ctx._chk(self.ctx.lib.ovhip_pic_output(self.ctx.h, C.byref(self.s), C.byref(win), out.ctypes.data), "pic_output")
+        self.ctx._chk(getattr(self.ctx.lib, "ovhip_" + fn)(self.ctx.h, C.byref(self.s), *args, C.byref(win), out.ctypes.data), fn)
         return out
+
+    def _digest16(self, window, fn: str, *args) -> bytes:
+        win, out = capi.Window(*window), (C.c_uint8 * 16)()
+        self.ctx._chk(getattr(self.ctx.lib, "ovhip_" + fn)(self.ctx.h, C.byref(self.s), *args, C.byref(win), out), fn)
+        return bytes(out)
+
+    def output(self, window=(0, 0, 0, 0)) -> np.ndarray:
+        """The cropped frame in the byte layout dectest.c:372-409 writes (uint16 LE: Y rows, Cb rows, Cr rows), packed on the
+        device and fetched with one D2H.  window = (lft, rgt, abv, blw) in chroma sample units."""
+        return self._packed(self.w, self.h, window, "pic_output")
 
     def digest(self, window=(0, 0, 0, 0)) -> bytes:
         """the picture's fingerprint: an MD5 tree over the cropped frame computed on the device (include/ovvc_hip.h, "Digest")"""
-        win = capi.Window(*window)
-        out = (C.c_uint8 * 16)()
-        self.ctx._chk(self.ctx.lib.ovhip_pic_digest(self.ctx.h, C.byref(self.s), C.byref(win), out), "pic_digest")
-        return bytes(out)
+        return self._digest16(window, "pic_digest")
 
     def scale_into(self, dst: "DevPic", scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
         """Resample this picture into dst (its own size) as the reference's output resampler does (ovhip_output_scale_launch);
@@ -348,21 +354,10 @@ class DevPic:
 
     def output_scaled(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), window=(0, 0, 0, 0)) -> np.ndarray:
         """output() of the picture resampled to out_w x out_h; `window` crops the resampled picture"""
-        info, win = capi.ScaleInfo(*scale_window, *col), capi.Window(*window)
-        n = self.ctx.lib.ovhip_output_bytes(out_w, out_h, C.byref(win))
-        if not n:
-            raise EngineError("output window leaves nothing")
-        out = np.empty(n // 2, np.uint16)
-        self.ctx._chk(self.ctx.lib.ovhip_pic_output_scaled(self.ctx.h, C.byref(self.s), C.byref(info), out_w, out_h, C.byref(win), out.ctypes.data),
-                      "pic_output_scaled")
-        return out
+        return self._packed(out_w, out_h, window, "pic_output_scaled", C.byref(capi.ScaleInfo(*scale_window, *col)), out_w, out_h)
 
     def digest_scaled(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), window=(0, 0, 0, 0)) -> bytes:
-        info, win = capi.ScaleInfo(*scale_window, *col), capi.Window(*window)
-        out = (C.c_uint8 * 16)()
-        self.ctx._chk(self.ctx.lib.ovhip_pic_digest_scaled(self.ctx.h, C.byref(self.s), C.byref(info), out_w, out_h, C.byref(win), out),
-                      "pic_digest_scaled")
-        return bytes(out)
+        return self._digest16(window, "pic_digest_scaled", C.byref(capi.ScaleInfo(*scale_window, *col)), out_w, out_h)
 
     def _fg_model(self, params: capi.FgParams) -> capi.FgModel:
         r, model, _ = capi.fg_derive(self.ctx.lib, params)
@@ -381,20 +376,10 @@ class DevPic:
 
     def output_grain(self, params: capi.FgParams, poc: int, window=(0, 0, 0, 0)) -> np.ndarray:
         """output() of the picture with film grain"""
-        model, win = self._fg_model(params), capi.Window(*window)
-        n = self.ctx.lib.ovhip_output_bytes(self.w, self.h, C.byref(win))
-        if not n:
-            raise EngineError("output window leaves nothing")
-        out = np.empty(n // 2, np.uint16)
-        self.ctx._chk(self.ctx.lib.ovhip_pic_output_grain(self.ctx.h, C.byref(self.s), C.byref(model), poc, C.byref(win), out.ctypes.data),
-                      "pic_output_grain")
-        return out
+        return self._packed(self.w, self.h, window, "pic_output_grain", C.byref(self._fg_model(params)), poc)
 
     def digest_grain(self, params: capi.FgParams, poc: int, window=(0, 0, 0, 0)) -> bytes:
-        model, win = self._fg_model(params), capi.Window(*window)
-        out = (C.c_uint8 * 16)()
-        self.ctx._chk(self.ctx.lib.ovhip_pic_digest_grain(self.ctx.h, C.byref(self.s), C.byref(model), poc, C.byref(win), out), "pic_digest_grain")
-        return bytes(out)
+        return self._digest16(window, "pic_digest_grain", C.byref(self._fg_model(params)), poc)
 
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
         win = capi.Window(*window)

@@ -120,6 +120,78 @@ def test_conveniences_pack_and_fingerprint_the_grained_picture(built_lib):
     pic.free(); ctx.close()
 
 
+def test_scale_and_grain_alternate_on_one_scratch_picture_through_every_delivery(built_lib):
+    """Both post-process kinds on ONE context (a frame's, so that the frame's PLANES outputs share it), one after the other, through
+    the packed frame, the fingerprint, the plain output and the frame's planes: each result is what the same launch into a picture
+    of its own gives, and the scratch picture is allocated once, at the larger size.
+
+    ovhip_ctx_scratch_bytes sums every grow-only buffer of the context, so the explicit-destination results are taken FIRST: they
+    bring the packing buffer, the digest buffers and the grain database to their final sizes without touching the scratch picture,
+    and what step 1 adds afterwards is exactly that picture."""
+    w, h, ow, oh, poc = 64, 48, 128, 96, 9
+    win = (1, 0, 0, 1)
+    sei = sf.make_sei()
+    fg = c_params(sei)
+    rs = np.random.RandomState(64 * 48)
+    planes = (rs.randint(0, 1024, (h, w)).astype(np.uint16), rs.randint(0, 1024, (h // 2, w // 2)).astype(np.uint16),
+              rs.randint(0, 1024, (h // 2, w // 2)).astype(np.uint16))
+    wl = synth.make_workload(w, h, 77, tools=synth.INTRA_TOOLS, intra_frac=1.0, calllog=True)
+    o = oracle_pipeline.decode(wl)
+    dec = (o.y, o.cb, o.cr)
+    dpb = engine.Dpb((0,))
+    f = engine.Frame(dpb, 0, w, h)
+    ctx = f.job().ctx                                                                   # the frame's context: not owned
+    keep = _Keep()
+    params = engine.Job.make_params(keep, wl)
+    pic, dpic = ctx.upload_pic(*planes), ctx.upload_pic(*dec)
+
+    # with explicit destination pictures
+    scaled, grained, dscaled, dgrained = ctx.new_pic(ow, oh), ctx.new_pic(w, h), ctx.new_pic(ow, oh), ctx.new_pic(w, h)
+    pic.scale_into(scaled); pic.grain_into(grained, fg, poc)
+    dpic.scale_into(dscaled); dpic.grain_into(dgrained, fg, poc)
+    ctx.sync()
+    want = [scaled.output(win), grained.output(win), scaled.digest(win), grained.digest(win)]
+    want_planes = [dscaled.download(), dgrained.download()]
+    assert not np.array_equal(want_planes[1][0], dec[0])                                # (grain was added)
+    held0 = ctx.scratch_bytes()
+
+    # 1 .. 5 on the shared scratch picture
+    assert np.array_equal(pic.output_scaled(ow, oh, window=win), want[0])
+    held = ctx.scratch_bytes()
+    assert held - held0 == ow * oh * 3                                                  # the scratch picture at 128 x 96, nothing else
+    assert np.array_equal(pic.output_grain(fg, poc, win), want[1]) and ctx.scratch_bytes() == held      # the smaller picture in the larger scratch
+    assert pic.digest_scaled(ow, oh, window=win) == want[2] and ctx.scratch_bytes() == held
+    assert pic.digest_grain(fg, poc, win) == want[3] and ctx.scratch_bytes() == held
+    assert pic.output(win).tobytes() == oo.packed_frame(*planes, win) and ctx.scratch_bytes() == held
+
+    # 6, 7: a frame delivers PLANES into host planes with a stride above the width
+    def planes_of(fw, fh, key):
+        sy, sc = fw + 24, fw // 2 + 8
+        y, cb, cr = (np.full((fh, sy), 0xFFFF, np.uint16), np.full((fh // 2, sc), 0xFFFF, np.uint16), np.full((fh // 2, sc), 0xFFFF, np.uint16))
+        out = capi.FrameOutput()
+        out.mode, out.y, out.cb, out.cr, out.stride_y, out.stride_c = capi.OUT_PLANES, y.ctypes.data, cb.ctypes.data, cr.ctypes.data, sy, sc
+        f.begin(key)
+        f.recorder().replay(wl.calllog)
+        f.submit(params, out=out)
+        assert (y[:, fw:] == 0xFFFF).all() and (cb[:, fw // 2:] == 0xFFFF).all() and (cr[:, fw // 2:] == 0xFFFF).all()
+        return y[:, :fw], cb[:, :fw // 2], cr[:, :fw // 2]
+
+    f.set_output_scale(ow, oh)
+    assert all(np.array_equal(a, b) for a, b in zip(planes_of(ow, oh, 0x100), want_planes[0]))
+    f.set_output_scale(0, 0)
+    f.set_film_grain(fg, poc)
+    assert all(np.array_equal(a, b) for a, b in zip(planes_of(w, h, 0x200), want_planes[1]))
+    assert ctx.scratch_bytes() == held
+
+    # the sources are only read
+    assert all(np.array_equal(a, b) for a, b in zip(pic.download(), planes))
+    for key in (0x100, 0x200):
+        assert all(np.array_equal(a, b) for a, b in zip(engine.DevPic(ctx, dpb.lookup(key)[1], owns=False).download(), dec))
+    for p in (pic, dpic, scaled, grained, dscaled, dgrained):
+        p.free()
+    f.close(); dpb.close()
+
+
 def _packed_out(win, w, h):
     out = capi.FrameOutput()
     cwin = capi.Window(*win)
