@@ -1225,6 +1225,50 @@ void ovhip_md5_update(ovhip_md5_state *st, const void *data, size_t n);
 void ovhip_md5_final(ovhip_md5_state *st, uint8_t out[16]);
 
 /* ------------------------------------------------------------------------------------
+ * Decoded picture hash (SEI payload type 132, H.274 / H.266 Annex D): the one check a VVC stream carries about itself.  The reference
+ * knows the payload's number (nvcl_nal_sei.c) and never reads it.  The hash covers the WHOLE decoded picture at its coded size --
+ * ovhip_pic.w x h, chroma at half of each; no conformance window, before any post-processing (film grain, output resampling) -- each
+ * plane on its own in the order Y, Cb, Cr (only Y with dph_sei_single_component_flag).  A plane's byte string is its samples in
+ * raster order, low byte then high byte of the stored 16-bit word (bit depth 10: two bytes per sample).
+ *   MD5       RFC 1321 over that byte string; 16 bytes.
+ *   CRC       16-bit register, start 0xFFFF, polynomial 0x1021, every bit of the byte string most significant bit of a byte first:
+ *             crc = (((crc << 1) | bit) & 0xFFFF) ^ ((old crc >> 15) ? 0x1021 : 0), then 16 more steps with bit 0; 2 bytes, high first.
+ *             As polynomials over GF(2), P = x^16 + x^12 + x^5 + 1 and M the n-bit string: crc = (0xFFFF x^(n+16) + M x^16) mod P, so
+ *             with R(A) = A x^16 mod P pieces combine as R(A | B) = R(A) x^|B| + R(B) and the start value enters once at the end.
+ *   checksum  sum over the samples s at (x, y) of the plane of ((s & 0xFF) ^ m) + ((s >> 8) ^ m) modulo 2^32,
+ *             m = (x & 0xFF) ^ (y & 0xFF) ^ (x >> 8) ^ (y >> 8); 4 bytes, big endian.
+ * CRC and checksum are computed where the picture is, 12 bytes leaving the device: one launch over the three planes (k_pic_hash: one
+ * workgroup per row, a lane owns runs of 8 samples) and a second small one (k_pic_hash_rows) that combines the rows' sums or
+ * remainders -- lanes within a wave, waves within a row, rows within the plane, always in that order and without atomics: the result
+ * does not depend on scheduling.  MD5 is one serial chain per plane (~0.2 s per 4K luma plane on one lane, by ovhip_output_row_md5_launch's 12 KB per
+ * 200 us): it is not a device method.  ovhip_pic_hash with OVHIP_HASH_MD5 is the CONFORMANCE route: the planes are copied into the
+ * context's page-locked scratch and hashed on the calling thread, ~40 ms per 4K picture at the 0.6 GB/s quoted below for
+ * OVHIP_STREAM_FILE_MD5.  No 8-bit pictures.
+ * ---------------------------------------------------------------------------------- */
+enum { OVHIP_HASH_MD5 = 0, OVHIP_HASH_CRC = 1, OVHIP_HASH_CHECKSUM = 2 };         /* = dph_sei_hash_type */
+/* value[c]: the bytes of plane c as they stand in the SEI payload (16, 2 or 4 of them); the rest of each row, and the rows of absent
+ * planes, are zero. */
+typedef struct ovhip_pic_hash_value { uint8_t method, n_planes, rsv[2]; uint8_t value[3][16]; } ovhip_pic_hash_value;
+/* Host only, no device: tests, and callers that hold the picture in host memory (an OVFrame).  Strides in samples; n_planes 1 (cb, cr
+ * are not read) or 3.  OVHIP_EINVAL for an unknown method, a missing plane, odd or non-positive sizes, a stride below the width. */
+int  ovhip_pic_hash_host(int method, int n_planes, const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h,
+                         int32_t stride_y, int32_t stride_c, ovhip_pic_hash_value *out);
+/* The payload of SEI message 132: dph_sei_hash_type u(8), dph_sei_single_component_flag u(1), 7 reserved bits, then per plane (1 with
+ * the flag, else 3) 16 bytes of MD5, u(16) of CRC or u(32) of checksum.  OVHIP_EINVAL for a payload that is too short or a hash type
+ * above 2; bytes behind the last value are ignored.  Host only. */
+int  ovhip_pic_hash_parse_sei(const uint8_t *payload, size_t n, ovhip_pic_hash_value *out);
+/* 1: same method, same plane count, same significant bytes of every plane's value; else 0.  Host only. */
+int  ovhip_pic_hash_equal(const ovhip_pic_hash_value *a, const ovhip_pic_hash_value *b);
+/* CRC and checksum only.  Asynchronous on the ctx stream.  d_out: DEVICE, one 32-bit word per plane (the CRC in its low 16 bits),
+ * each written whole: nothing accumulates in it, it needs no reset.  One word per row is kept in a grow-only buffer of the context,
+ * allocated at the first launch of a height (ovhip_ctx_scratch_bytes counts it).  OVHIP_EINVAL for OVHIP_HASH_MD5 (not a device method), n_planes other than
+ * 1 or 3, a missing plane, odd sizes or sizes above 16384, a stride below the width. */
+int  ovhip_pic_hash_launch(ovhip_ctx *ctx, const ovhip_pic *pic, int method, int n_planes, uint32_t *d_out);
+/* Synchronous.  CRC / checksum: the launch, then a D2H of at most 12 bytes through the context's grow-only scratch (no allocation
+ * once a size has been seen).  MD5: see above. */
+int  ovhip_pic_hash(ovhip_ctx *ctx, const ovhip_pic *pic, int method, int n_planes, ovhip_pic_hash_value *out);
+
+/* ------------------------------------------------------------------------------------
  * Output resampling: a stream that changes its coded size (RPR) can leave the device at ONE size.  Replaces pp_sample_rate_conv
  * (pp_pic_scale.c:250-377), called once per plane by pp_process_frame (post_proc.c:116-126) when the decoder's `upscale` option is
  * on (ovdec.c:562; ovdec.c:479 / :523 are the call sites), for up-sampling and equal size, bit-exactly -- including its phase, which
@@ -1571,6 +1615,17 @@ int  ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, 
  * ovhip_frame_set_output_scale answers OVHIP_EUNSUP while grain is set: the reference resamples the ungrained frame over the grained one
  * (post_proc.c:107-126).  A dry frame accepts the call and delivers nothing. */
 int  ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_t poc);
+/* Decoded picture hash ("Decoded picture hash" above) of every following picture: taken in ovhip_frame_submit and in the last
+ * ovhip_frame_band AFTER ovhip_job_wait (a second pass of the ordered pass rewrites the picture), on the decoded picture as it is
+ * published -- whatever the output mode, the output scale or the film grain setting are (those post-process a copy).  expected: what
+ * the picture's SEI says (copied; NULL: compute only); it applies to the NEXT picture completed, so a caller sets it per picture.
+ * method < 0 switches it off, which is the default.  A mismatch does NOT fail the picture: it is published as decoded and the caller
+ * reads the verdict.  OVHIP_EINVAL for a method above 2, n_planes other than 1 or 3, an expectation of another method or plane count.
+ * A dry frame accepts the call and computes nothing.  The frame trace has no event for it. */
+int  ovhip_frame_set_picture_hash(ovhip_frame *f, int method, int n_planes, const ovhip_pic_hash_value *expected);
+/* The last completed picture's hash into *computed (may be NULL).  1: computed, and equal to the expectation or none was given;
+ * 0: it differs; OVHIP_EINVAL: nothing computed (yet). */
+int  ovhip_frame_picture_hash(const ovhip_frame *f, ovhip_pic_hash_value *computed);
 int  ovhip_frame_fail(ovhip_frame *f, int status);
 const char *ovhip_frame_last_error(const ovhip_frame *f);
 
@@ -1706,6 +1761,13 @@ int  ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h
  * (ovhip_frame_set_film_grain); NULL: off.  The frames of OVHIP_OUT_PACKED -- and with them the MD5 of OVHIP_STREAM_FILE_MD5 -- and the
  * fingerprints of OVHIP_OUT_DIGEST are those of the grained pictures.  Refusals as the frame's setter. */
 int  ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params);
+/* Decoded picture hashes for the following runs: every frame thread hashes its own picture (ovhip_frame_set_picture_hash; nothing
+ * goes through the output thread).  expected: one entry per picture of the stream (index in pics; the caller's array, read during the
+ * runs) or NULL: compute only.  method < 0: off.  A mismatch leaves ovhip_stream_result.status at 0. */
+int  ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, const ovhip_pic_hash_value *expected);
+/* Of the last run: computed (NULL, or room for its n pictures, in the order of pics), the number of pictures whose hash differed from
+ * the expectation and the index in pics of the first of them (-1: none).  OVHIP_EINVAL when the last run computed none. */
+int  ovhip_stream_picture_hashes(const ovhip_stream *s, ovhip_pic_hash_value *computed, uint32_t *n_mismatch, int32_t *first_mismatch);
 /* The DPB key of picture idx of the current stream (valid while the run that decoded it kept it: OVHIP_STREAM_KEEP). */
 const void *ovhip_stream_key(const ovhip_stream *s, uint32_t idx);
 /* test hook: the next flush of `job` that has a flow launch is ABORTED for real (the device's abort word is set before the

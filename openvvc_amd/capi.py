@@ -474,6 +474,19 @@ class StreamResult(C.Structure):
                 ("trace", C.c_void_p)]
 
 
+HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2          # = dph_sei_hash_type
+HASH_VALUE_BYTES = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
+
+
+class PicHashValue(C.Structure):
+    """ovhip_pic_hash_value: per plane the bytes as they stand in the decoded picture hash SEI"""
+    _fields_ = [("method", C.c_uint8), ("n_planes", C.c_uint8), ("rsv", C.c_uint8 * 2), ("value", (C.c_uint8 * 16) * 3)]
+
+    def planes(self) -> list:
+        """the significant bytes of each present plane's value"""
+        return [bytes(self.value[c])[:HASH_VALUE_BYTES[self.method]] for c in range(self.n_planes)]
+
+
 class Md5State(C.Structure):
     _fields_ = [("h", C.c_uint32 * 4), ("n_bytes", C.c_uint64), ("buf", C.c_uint8 * 64)]
 
@@ -722,6 +735,15 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_film_grain_launch": (C.c_int, [vp, P(Pic), P(FgModel), i32, i32, P(Pic)]),
         "ovhip_pic_output_grain": (C.c_int, [vp, P(Pic), P(FgModel), i32, P(Window), vp]),
         "ovhip_pic_digest_grain": (C.c_int, [vp, P(Pic), P(FgModel), i32, P(Window), vp]),
+        "ovhip_pic_hash_host": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, i32, i32, i32, i32, P(PicHashValue)]),
+        "ovhip_pic_hash_parse_sei": (C.c_int, [vp, C.c_size_t, P(PicHashValue)]),
+        "ovhip_pic_hash_equal": (C.c_int, [P(PicHashValue), P(PicHashValue)]),
+        "ovhip_pic_hash_launch": (C.c_int, [vp, P(Pic), C.c_int, C.c_int, vp]),
+        "ovhip_pic_hash": (C.c_int, [vp, P(Pic), C.c_int, C.c_int, P(PicHashValue)]),
+        "ovhip_frame_set_picture_hash": (C.c_int, [vp, C.c_int, C.c_int, P(PicHashValue)]),
+        "ovhip_frame_picture_hash": (C.c_int, [vp, P(PicHashValue)]),
+        "ovhip_stream_set_picture_hashes": (C.c_int, [vp, C.c_int, C.c_int, P(PicHashValue)]),
+        "ovhip_stream_picture_hashes": (C.c_int, [vp, P(PicHashValue), P(u32), P(i32)]),
     }
     ab_build = "OVVC_HIP_LIB_NAME" in os.environ       # tools/ab_lib.sh: an OLDER build of the library beside the current one (its newer entry points are not called)
     for name, (res, args) in sigs.items():
@@ -765,6 +787,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_frame_set_output_scale", "ovhip_stream_set_output_scale", "ovhip_ctx_scratch_bytes",
     "ovhip_rec_ibc_check", "ovhip_rec_tu_ibc", "ovhip_rec_ibc_tasks",
     "ovhip_frame_set_film_grain", "ovhip_stream_set_film_grain", "ovhip_fg_derive", "ovhip_fg_database", "ovhip_fg_seed", "ovhip_fg_prng", "ovhip_fg_stripe_seeds", "ovhip_film_grain_launch", "ovhip_pic_output_grain", "ovhip_pic_digest_grain",
+    "ovhip_pic_hash_host", "ovhip_pic_hash_parse_sei", "ovhip_pic_hash_equal", "ovhip_pic_hash_launch", "ovhip_pic_hash",
+    "ovhip_frame_set_picture_hash", "ovhip_frame_picture_hash", "ovhip_stream_set_picture_hashes", "ovhip_stream_picture_hashes",
 ]
 
 

@@ -31,6 +31,7 @@ struct ovhip_ctx {
     void *scratch_d; size_t scratch_d_cap;
     void *scratch_h; size_t scratch_h_cap;       // page-locked
     void *post_d; size_t post_d_cap;             // the scratch PICTURE of the post-processed outputs (ovhip_post_pic_, kernels_output.hip), grow-only likewise
+    void *hash_d; size_t hash_d_cap;             // the rows' CRC remainders of ovhip_pic_hash_launch (kernels_pichash.hip), grow-only likewise
     // film grain (kernels_grain.hip), allocated at the context's first grain launch: the database followed by OV_FG_SLOTS slots (model +
     // stripe seeds of one launch, and the seeds k_film_grain_seeds makes of them per workgroup) on the device, the slots' page-locked staging, and per slot the event behind the launch that reads it
     void *fg_d; size_t fg_d_cap;

@@ -129,6 +129,7 @@ void ovhip_ctx_destroy(ovhip_ctx *ctx)
     if (ctx->fg_d) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->scratch_d) (void)hipFree(ctx->scratch_d);
     if (ctx->post_d) (void)hipFree(ctx->post_d);
+    if (ctx->hash_d) (void)hipFree(ctx->hash_d);
     if (ctx->fg_d) (void)hipFree(ctx->fg_d);
     if (ctx->fg_h) (void)hipHostFree(ctx->fg_h);
     for (int i = 0; i < OV_FG_SLOTS; ++i) if (ctx->fg_ev[i]) (void)hipEventDestroy(ctx->fg_ev[i]);
@@ -188,7 +189,7 @@ int ovhip_ctx_sync(ovhip_ctx *ctx)
     return OVHIP_OK;
 }
 
-size_t ovhip_ctx_scratch_bytes(const ovhip_ctx *ctx) { return ctx ? ctx->scratch_d_cap + ctx->scratch_h_cap + ctx->post_d_cap + ctx->fg_d_cap + ctx->fg_h_cap : 0; }
+size_t ovhip_ctx_scratch_bytes(const ovhip_ctx *ctx) { return ctx ? ctx->scratch_d_cap + ctx->scratch_h_cap + ctx->post_d_cap + ctx->fg_d_cap + ctx->fg_h_cap + ctx->hash_d_cap : 0; }
 const char *ovhip_last_error(const ovhip_ctx *ctx) { return ctx ? ctx->err : "no context"; }
 void *ovhip_ctx_stream(ovhip_ctx *ctx) { return ctx ? (void *)ctx->main_stream : nullptr; }
 

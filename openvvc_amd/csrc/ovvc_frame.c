@@ -48,6 +48,10 @@ struct ovhip_frame {
      * post.out_h; GRAIN (ovhip_frame_set_film_grain): with film grain at post.poc, the model derived afresh from fg for every picture */
     ovhip_post_ post;
     ovhip_fg_params fg;
+    /* decoded picture hash (ovhip_frame_set_picture_hash): what to take of every completed picture, what the caller expects of the next
+     * one, what the last one gave */
+    int hash_on, hash_method, hash_planes, hash_expect, hash_done;
+    ovhip_pic_hash_value hash_expected, hash_computed;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -183,7 +187,7 @@ ovhip_frame_begin_tag(ovhip_frame *f, const void *key, uint64_t tag)
     if (!f || !key) return OVHIP_EINVAL;
     /* a picture that was begun and never submitted must not leave its readers waiting */
     if (f->live) (void)ovhip_frame_fail(f, OVHIP_EINVAL);
-    f->status = 0; f->err[0] = 0; f->n_refs = 0;
+    f->status = 0; f->err[0] = 0; f->n_refs = 0; f->hash_done = 0;
     int r = ovhip_dpb_begin_tag(f->dpb, key, tag, f->dev, f->w, f->h, &f->dst);
     trace(f, OVHIP_FE_BEGIN, key, tag, f->dev, 0, r);
     if (r != OVHIP_OK) return fail(f, r, "ovhip_dpb_begin");
@@ -401,6 +405,41 @@ ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_
     return OVHIP_OK;
 }
 
+int
+ovhip_frame_set_picture_hash(ovhip_frame *f, int method, int n_planes, const ovhip_pic_hash_value *expected)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (method < 0) { f->hash_on = 0; f->hash_expect = 0; return OVHIP_OK; }
+    if (method > OVHIP_HASH_CHECKSUM || (n_planes != 1 && n_planes != 3)) return OVHIP_EINVAL;
+    if (expected && (expected->method != method || expected->n_planes != n_planes)) return OVHIP_EINVAL;
+    f->hash_on = 1; f->hash_method = method; f->hash_planes = n_planes;      /* (a dry frame has no picture to hash: only remembered) */
+    f->hash_expect = expected != NULL;
+    if (expected) f->hash_expected = *expected;
+    return OVHIP_OK;
+}
+
+int
+ovhip_frame_picture_hash(const ovhip_frame *f, ovhip_pic_hash_value *computed)
+{
+    if (!f || !f->hash_done) return OVHIP_EINVAL;
+    if (computed) *computed = f->hash_computed;
+    return f->hash_done > 0;
+}
+
+/* the hash of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: of f->dst, the decoded picture as it was
+ * published (its readers only read it, as this does), never of the post-processed copy an output makes.  A value that differs from
+ * the expectation is a verdict, not an error */
+static int
+frame_hash(ovhip_frame *f)
+{
+    f->hash_done = 0;
+    if (!f->hash_on) return OVHIP_OK;
+    const int r = ovhip_pic_hash(f->ctx, &f->dst, f->hash_method, f->hash_planes, &f->hash_computed);
+    if (r != OVHIP_OK) return r;
+    f->hash_done = !f->hash_expect || ovhip_pic_hash_equal(&f->hash_computed, &f->hash_expected) ? 1 : -1;
+    return OVHIP_OK;
+}
+
 /* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the frame's post-process step (if any:
  * into the context's scratch picture -- f->dst itself is only read), then the delivery `out` names */
 static int
@@ -457,6 +496,7 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
     /* the picture is complete: its readers go on while this thread copies it out (the output only reads; whoever keeps the key
      * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns) */
     (void)publish(f, r);
+    if (r == OVHIP_OK && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
     if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
         const double to0 = PT_ON() ? mono_s() : 0.0;
         r = frame_output(f, out);
@@ -634,6 +674,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     if (f->status) r = f->status;
     (void)publish(f, r);
     f->pn_pics++;
+    if (r == OVHIP_OK && !f->dry && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
     if (r == OVHIP_OK && !f->dry && out && out->mode != OVHIP_OUT_NONE) {
         PT0();
         r = frame_output(f, out);

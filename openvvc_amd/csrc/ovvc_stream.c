@@ -49,6 +49,11 @@ struct ovhip_stream {
     pthread_mutex_t begun_mtx; pthread_cond_t begun_cnd;
     int n_moved, n_sharing;               /* streams replaced to clear the look-ahead thread's hardware queue / still sharing it */
     ovhip_post_ post; ovhip_fg_params fg;  /* what the outputs do to a picture first (ovvc_dpb_priv.h): ovhip_stream_set_output_scale / _set_film_grain */
+    /* decoded picture hashes (ovhip_stream_set_picture_hashes): the setting, the caller's expectations (one per picture of the stream, or
+     * NULL), and of the last run its pictures' hashes and the verdict */
+    int hash_on, hash_method, hash_planes;
+    const ovhip_pic_hash_value *hash_expected;
+    ovhip_pic_hash_value *ph; uint32_t ph_n, ph_mismatch; int32_t ph_first_mismatch;
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -223,11 +228,23 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         out.window = s->cfg.window;
         if (tr) tr[1] = now_s() - rs->t0;
         if (s->post.kind == OVHIP_POST_GRAIN) (void)ovhip_frame_set_film_grain(f, &s->fg, p->poc);      /* (validated by the stream's setter) */
+        if (s->ph) (void)ovhip_frame_set_picture_hash(f, s->hash_method, s->hash_planes, s->hash_expected ? &s->hash_expected[idx] : NULL);
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
         if (tr) { tr[6] = now_s() - rs->t0; tr[2] = tr[6]; }
         if (r != OVHIP_OK) { run_fail(rs, r, "ovhip_frame_submit", ovhip_frame_last_error(f)); goto out; }
+        if (s->ph) {
+            /* the picture's own frame thread has hashed it (ovhip_frame_submit, after the wait); a hash that differs from the SEI's is
+             * counted, the run goes on */
+            const int v = ovhip_frame_picture_hash(f, &s->ph[idx - rs->first]);
+            if (v == 0) {
+                pthread_mutex_lock(&rs->mtx);
+                s->ph_mismatch++;
+                if (s->ph_first_mismatch < 0 || (int32_t)idx < s->ph_first_mismatch) s->ph_first_mismatch = (int32_t)idx;
+                pthread_mutex_unlock(&rs->mtx);
+            }
+        }
         if (out.mode == OVHIP_OUT_DIGEST) {
             if (rs->digests) memcpy(rs->digests + 16 * (size_t)(idx - rs->first), out.digest, 16);
             pthread_mutex_lock(&s->begun_mtx);
@@ -445,6 +462,7 @@ ovhip_stream_destroy(ovhip_stream *s)
     for (int i = 0; s->frames && i < s->n_dev * s->tpd; ++i) ovhip_frame_destroy(s->frames[i]);
     for (int k = 0; s->out_ctx && k < s->n_dev; ++k) ovhip_ctx_destroy(s->out_ctx[k]);
     ovhip_host_free(s->out_host);
+    free(s->ph);
     for (uint32_t i = 0; s->job_mtx && i < s->n_jobs; ++i) pthread_mutex_destroy(&s->job_mtx[i]);
     free(s->frames); free(s->out_ctx); free(s->job_mtx);
     pthread_cond_destroy(&s->begun_cnd); pthread_mutex_destroy(&s->begun_mtx);
@@ -516,6 +534,29 @@ ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params)
     return r;
 }
 
+int
+ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, const ovhip_pic_hash_value *expected)
+{
+    if (!s) return OVHIP_EINVAL;
+    int r = OVHIP_OK;
+    /* the frames' answer to the setting; each picture's expectation is handed to its frame when the picture is taken */
+    for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_picture_hash(s->frames[i], method, n_planes, NULL);
+    if (r != OVHIP_OK) return r;
+    s->hash_on = method >= 0; s->hash_method = method; s->hash_planes = n_planes;
+    s->hash_expected = s->hash_on ? expected : NULL;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_picture_hashes(const ovhip_stream *s, ovhip_pic_hash_value *computed, uint32_t *n_mismatch, int32_t *first_mismatch)
+{
+    if (!s || !s->ph) return OVHIP_EINVAL;
+    if (computed) memcpy(computed, s->ph, (size_t)s->ph_n * sizeof(*computed));
+    if (n_mismatch) *n_mismatch = s->ph_mismatch;
+    if (first_mismatch) *first_mismatch = s->ph_first_mismatch;
+    return OVHIP_OK;
+}
+
 ovhip_frame *
 ovhip_stream_frame(ovhip_stream *s, int dev, int thread)
 {
@@ -552,6 +593,10 @@ ovhip_stream_run(ovhip_stream *s, const ovhip_stream_pic *pics, uint32_t n_total
     if (pics != s->pics || n_total != s->n_total || first == 0) {
         if ((r = adopt_stream(s, pics, n_total, flags)) != OVHIP_OK) { release_stream(s); return r; }
     }
+    free(s->ph);
+    s->ph = s->hash_on ? (ovhip_pic_hash_value *)calloc(n ? n : 1, sizeof(*s->ph)) : NULL;
+    s->ph_n = n; s->ph_mismatch = 0; s->ph_first_mismatch = -1;
+    if (s->hash_on && !s->ph) return OVHIP_ENOMEM;
     struct run_state rs;
     memset(&rs, 0, sizeof(rs));
     rs.s = s; rs.pics = pics; rs.first = first; rs.n = n; rs.flags = flags; rs.digests = digests; rs.res = res;

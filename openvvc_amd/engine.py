@@ -381,6 +381,23 @@ class DevPic:
     def digest_grain(self, params: capi.FgParams, poc: int, window=(0, 0, 0, 0)) -> bytes:
         return self._digest16(window, "pic_digest_grain", C.byref(self._fg_model(params)), poc)
 
+    def hash(self, method: int, n_planes: int = 3, check: bool = True):
+        """ovhip_pic_hash: the decoded picture hash SEI's value of this picture (CRC / checksum on the device, MD5 through the host) ->
+        capi.PicHashValue, or the error code with check=False"""
+        out = capi.PicHashValue()
+        r = self.ctx.lib.ovhip_pic_hash(self.ctx.h, C.byref(self.s), method, n_planes, C.byref(out))
+        if check:
+            self.ctx._chk(r, "pic_hash")
+        return out if r == 0 else r
+
+    def hash_launch(self, method: int, n_planes: int, d_out: "DevBuf", offset: int = 0, check: bool = True) -> int:
+        """ovhip_pic_hash_launch into d_out at byte `offset` (one uint32 per plane).  Asynchronous."""
+        r = self.ctx.lib.ovhip_pic_hash_launch(self.ctx.h, C.byref(self.s), method, n_planes,
+                                               C.c_void_p(d_out.ptr.value + offset) if d_out is not None else None)
+        if check:
+            self.ctx._chk(r, "pic_hash_launch")
+        return r
+
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
         win = capi.Window(*window)
         rows = self.ctx.lib.ovhip_output_rows(self.w, self.h, C.byref(win))
@@ -818,6 +835,18 @@ class Frame:
             raise EngineError(f"frame_set_film_grain: {r}")
         return r
 
+    def set_picture_hash(self, method: int, n_planes: int = 3, expected: "capi.PicHashValue | None" = None, check: bool = True) -> int:
+        """ovhip_frame_set_picture_hash: every following picture is hashed after its decode (method < 0: off); expected: the SEI's value"""
+        r = self.lib.ovhip_frame_set_picture_hash(self.f, method, n_planes, C.byref(expected) if expected is not None else None)
+        if check and r:
+            raise EngineError(f"frame_set_picture_hash: {r}")
+        return r
+
+    def picture_hash(self) -> "tuple[int, capi.PicHashValue]":
+        """(1 equal or nothing expected / 0 differs / OVHIP_EINVAL nothing computed, the last picture's hash)"""
+        out = capi.PicHashValue()
+        return self.lib.ovhip_frame_picture_hash(self.f, C.byref(out)), out
+
     def set_output_scale(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), check: bool = True) -> int:
         """the frame's outputs deliver the picture resampled to out_w x out_h; (0, 0) switches it off"""
         info = capi.ScaleInfo(*scale_window, *col)
@@ -889,6 +918,21 @@ class Stream:
         if r < 0 and check:
             raise EngineError(f"stream_set_output_scale: {r}")
         return r
+
+    def set_picture_hashes(self, method: int, n_planes: int = 3, expected=None, check: bool = True) -> int:
+        """ovhip_stream_set_picture_hashes; expected: a (capi.PicHashValue * n_total) array (kept alive here) or None"""
+        self._keep.append(expected)
+        r = self.lib.ovhip_stream_set_picture_hashes(self.s, method, n_planes, expected)
+        if check and r:
+            raise EngineError(f"stream_set_picture_hashes: {r}")
+        return r
+
+    def picture_hashes(self, n: int):
+        """of the last run of n pictures -> (status, [capi.PicHashValue] * n, n_mismatch, first_mismatch)"""
+        out = (capi.PicHashValue * max(1, n))()
+        nm, fm = C.c_uint32(), C.c_int32()
+        r = self.lib.ovhip_stream_picture_hashes(self.s, out, C.byref(nm), C.byref(fm))
+        return r, list(out)[:n], nm.value, fm.value
 
     def queue_info(self):
         """(streams replaced to clear the look-ahead thread's hardware queue, in-order streams still sharing it)"""
