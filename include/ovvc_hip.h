@@ -1269,6 +1269,55 @@ int  ovhip_pic_hash_launch(ovhip_ctx *ctx, const ovhip_pic *pic, int method, int
 int  ovhip_pic_hash(ovhip_ctx *ctx, const ovhip_pic *pic, int method, int n_planes, ovhip_pic_hash_value *out);
 
 /* ------------------------------------------------------------------------------------
+ * RGB output on the device: a finished 10-bit 4:2:0 picture as an RGB tensor (layout and dtype of the consumer) in DEVICE memory, for
+ * compute that sits next to the decoder; nothing is downloaded.  Nothing in the reference does this (dectest writes planes).  The
+ * definition is integer only, so every implementation of it (tests/spec_rgb.py, ovhip_rgb_host, k_rgb) is compared for equality.
+ *
+ *   Input    an ovhip_pic of w x h (multiples of 4) and a window in chroma units, read as the packed output reads it: the output
+ *            has W = w - 2 (lft + rgt) columns and H = h - 2 (abv + blw) rows and starts at luma (2 lft, 2 abv).
+ *   Chroma   at luma position (x, y) of the PICTURE (before the crop), with a = chroma_loc & 1 and b = 1 for chroma_loc 0, 1,
+ *            b = 0 for 2, 3, b = 2 for 4, 5 (H.273 Chroma420SampleLocType: horizontally co-sited / centred; vertically centred,
+ *            top, bottom):  U = 2x - a, V = 2y - b; i0 = U >> 2, fx = U & 3, j0 = V >> 2, fy = V & 3 (arithmetic shifts),
+ *            i1 = i0 + 1, j1 = j0 + 1, all four clamped to the chroma plane of the whole picture (not of the window);
+ *              c16 = (4-fx)(4-fy) c[j0][i0] + fx (4-fy) c[j0][i1] + (4-fx) fy c[j1][i0] + fx fy c[j1][i1]
+ *            -- 16 times the bilinear value, not rounded.
+ *   Matrix   N = 8 for U8, else 10; peak = 2^N - 1.  Limited range: sy = peak / 876, sc = peak / 896, yoff = 64; full range:
+ *            sy = sc = peak / 1023, yoff = 0.  With (Kr, Kb) of `matrix` and Kg = 1 - Kr - Kb the real factors are
+ *            cy = sy, rv = 2 sc (1 - Kr), bu = 2 sc (1 - Kb), gu = bu Kb / Kg, gv = rv Kr / Kg; each times 2^14, rounded to nearest on
+ *            the exact rational (no case is a tie), is the integer coefficient.  L = 16 cy (Y - yoff), u = c16(Cb) - 8192,
+ *            v = c16(Cr) - 8192:
+ *              R = clip((L + rv v + 2^17) >> 18), G = clip((L - gu u - gv v + 2^17) >> 18), B = clip((L + bu u + 2^17) >> 18)
+ *            clipped to 0..peak; every accumulator fits int32 for 10-bit input.
+ *   dtype    U8, U16: that integer.  F32: (float)value * (float)(1.0 / 1023), one multiplication, round to nearest.  F16: that
+ *            float converted round-to-nearest-even.
+ *   layout   PLANAR: the R plane, the G plane, the B plane, each H x W (CHW); PACKED: H x W x 3 (HWC).  Both tight.
+ * matrix = H.273 MatrixCoefficients: 1 (Kr 0.2126, Kb 0.0722), 5 and 6 (0.299, 0.114), 9 (0.2627, 0.0593); 2 (unspecified) is
+ * OVHIP_EINVAL -- the caller must decide --, every other value OVHIP_EUNSUP.  Not done: transfer functions, tone mapping,
+ * constant-luminance and ICtCp matrices, normalisation, resizing.
+ * ---------------------------------------------------------------------------------- */
+enum { OVHIP_RGB_U8 = 0, OVHIP_RGB_U16 = 1, OVHIP_RGB_F16 = 2, OVHIP_RGB_F32 = 3 };      /* ovhip_rgb_format.dtype */
+enum { OVHIP_RGB_PLANAR = 0, OVHIP_RGB_PACKED = 1 };                                       /* ovhip_rgb_format.layout */
+typedef struct ovhip_rgb_format { uint8_t matrix, full_range, chroma_loc, dtype, layout, rsv[3]; } ovhip_rgb_format;
+/* Bytes of the RGB picture of a w x h picture under win (NULL: no crop); 0 for sizes that are not positive multiples of 4, a window
+ * that leaves nothing or a bad dtype / layout.  Host only. */
+size_t ovhip_rgb_bytes(int32_t w, int32_t h, const ovhip_window *win, const ovhip_rgb_format *fmt);
+/* The integer coefficients (cy, rv, gu, gv, bu) and yoff of a format.  OVHIP_EINVAL / OVHIP_EUNSUP as above.  Host only. */
+int  ovhip_rgb_coefs(const ovhip_rgb_format *fmt, int32_t coef[5], int32_t *yoff);
+/* The definition on host planes into host memory (strides in samples): tests, and callers that hold the picture on the host.
+ * Refusals as the launch's; nothing is written when it refuses. */
+int  ovhip_rgb_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
+                    const ovhip_window *win, const ovhip_rgb_format *fmt, void *dst, size_t dst_bytes);
+/* d_dst: DEVICE, at least ovhip_rgb_bytes bytes, aligned to its element (a slice of a batch tensor is no more than that; k_rgb stores
+ * 16 bytes at a time where a run of 8 pixels lies so, narrower where it does not).  Asynchronous on the ctx stream; allocates nothing.
+ * Refused before anything is launched, the reason in the context's error text: a null destination, dst_bytes too small, a destination
+ * that is not element-aligned or overlaps the picture, a window that leaves nothing, a missing plane, a stride below the width,
+ * sizes that are not multiples of 4, bad enum values (OVHIP_EINVAL; a matrix that is not built: OVHIP_EUNSUP). */
+int  ovhip_rgb_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *d_dst, size_t dst_bytes);
+/* Synchronous convenience beside ovhip_pic_output: the launch into the context's grow-only scratch, then one D2H into host_dst
+ * (dst_bytes >= ovhip_rgb_bytes, pinned or pageable). */
+int  ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *host_dst, size_t dst_bytes);
+
+/* ------------------------------------------------------------------------------------
  * Output resampling: a stream that changes its coded size (RPR) can leave the device at ONE size.  Replaces pp_sample_rate_conv
  * (pp_pic_scale.c:250-377), called once per plane by pp_process_frame (post_proc.c:116-126) when the decoder's `upscale` option is
  * on (ovdec.c:562; ovdec.c:479 / :523 are the call sites), for up-sampling and equal size, bit-exactly -- including its phase, which
@@ -1626,6 +1675,14 @@ int  ovhip_frame_set_picture_hash(ovhip_frame *f, int method, int n_planes, cons
 /* The last completed picture's hash into *computed (may be NULL).  1: computed, and equal to the expectation or none was given;
  * 0: it differs; OVHIP_EINVAL: nothing computed (yet). */
 int  ovhip_frame_picture_hash(const ovhip_frame *f, ovhip_pic_hash_value *computed);
+/* RGB output ("RGB output on the device" above) of the NEXT picture completed -- the destination is per picture, so a caller sets it
+ * per picture; fmt NULL switches it off, which is the default.  The conversion runs in ovhip_frame_submit and in the last
+ * ovhip_frame_band after ovhip_job_wait, on the picture the output shows -- after the frame's post-process step, so film grain and
+ * the output scale compose with it (win is in chroma units of THAT picture) --, whatever out->mode is, OVHIP_OUT_NONE and a NULL out
+ * included, and is complete on the device when the call returns.  What is published to the DPB is unchanged.  fmt and win are copied.
+ * The format's refusals come back here, the launch's from the picture's last call: a failed conversion fails that call's return
+ * value, never the picture's publication.  A dry frame accepts the call and does nothing. */
+int  ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
 int  ovhip_frame_fail(ovhip_frame *f, int status);
 const char *ovhip_frame_last_error(const ovhip_frame *f);
 
@@ -1768,6 +1825,12 @@ int  ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, 
 /* Of the last run: computed (NULL, or room for its n pictures, in the order of pics), the number of pictures whose hash differed from
  * the expectation and the index in pics of the first of them (-1: none).  OVHIP_EINVAL when the last run computed none. */
 int  ovhip_stream_picture_hashes(const ovhip_stream *s, ovhip_pic_hash_value *computed, uint32_t *n_mismatch, int32_t *first_mismatch);
+/* RGB output for the following runs: picture idx of the stream (index in pics) lands at d_base + (idx % n_slots) * bytes_per_picture
+ * in DEVICE memory, written by the frame thread that completes it (ovhip_frame_set_rgb_output; nothing goes through the output
+ * thread), whatever the stream's output mode is.  fmt NULL: off.  OVHIP_EINVAL for a null base, n_slots 0 or a bytes_per_picture below
+ * ovhip_rgb_bytes for the size the stream outputs (its output scale's, else its pictures'); the format's refusals as
+ * ovhip_rgb_coefs.  A slot is the caller's to reuse once the picture n_slots later is decoded: the driver does not wait for a reader. */
+int  ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
 /* The DPB key of picture idx of the current stream (valid while the run that decoded it kept it: OVHIP_STREAM_KEEP). */
 const void *ovhip_stream_key(const ovhip_stream *s, uint32_t idx);
 /* test hook: the next flush of `job` that has a flow launch is ABORTED for real (the device's abort word is set before the

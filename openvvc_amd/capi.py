@@ -487,6 +487,17 @@ class PicHashValue(C.Structure):
         return [bytes(self.value[c])[:HASH_VALUE_BYTES[self.method]] for c in range(self.n_planes)]
 
 
+RGB_U8, RGB_U16, RGB_F16, RGB_F32 = 0, 1, 2, 3       # ovhip_rgb_format.dtype
+RGB_PLANAR, RGB_PACKED = 0, 1                        # ovhip_rgb_format.layout: CHW / HWC
+RGB_NP_DTYPE = {RGB_U8: "uint8", RGB_U16: "uint16", RGB_F16: "float16", RGB_F32: "float32"}
+
+
+class RgbFormat(C.Structure):
+    """ovhip_rgb_format: H.273 matrix coefficients (1, 5, 6, 9), range, Chroma420SampleLocType 0..5, element type, layout"""
+    _fields_ = [("matrix", C.c_uint8), ("full_range", C.c_uint8), ("chroma_loc", C.c_uint8), ("dtype", C.c_uint8), ("layout", C.c_uint8),
+                ("rsv", C.c_uint8 * 3)]
+
+
 class Md5State(C.Structure):
     _fields_ = [("h", C.c_uint32 * 4), ("n_bytes", C.c_uint64), ("buf", C.c_uint8 * 64)]
 
@@ -744,6 +755,13 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_frame_picture_hash": (C.c_int, [vp, P(PicHashValue)]),
         "ovhip_stream_set_picture_hashes": (C.c_int, [vp, C.c_int, C.c_int, P(PicHashValue)]),
         "ovhip_stream_picture_hashes": (C.c_int, [vp, P(PicHashValue), P(u32), P(i32)]),
+        "ovhip_rgb_bytes": (C.c_size_t, [i32, i32, P(Window), P(RgbFormat)]),
+        "ovhip_rgb_coefs": (C.c_int, [P(RgbFormat), P(i32), P(i32)]),
+        "ovhip_rgb_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(RgbFormat), vp, C.c_size_t]),
+        "ovhip_rgb_launch": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, C.c_size_t]),
+        "ovhip_pic_output_rgb": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, C.c_size_t]),
+        "ovhip_frame_set_rgb_output": (C.c_int, [vp, P(RgbFormat), P(Window), vp, C.c_size_t]),
+        "ovhip_stream_set_rgb_output": (C.c_int, [vp, P(RgbFormat), P(Window), vp, C.c_size_t, u32]),
     }
     ab_build = "OVVC_HIP_LIB_NAME" in os.environ       # tools/ab_lib.sh: an OLDER build of the library beside the current one (its newer entry points are not called)
     for name, (res, args) in sigs.items():
@@ -789,6 +807,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_frame_set_film_grain", "ovhip_stream_set_film_grain", "ovhip_fg_derive", "ovhip_fg_database", "ovhip_fg_seed", "ovhip_fg_prng", "ovhip_fg_stripe_seeds", "ovhip_film_grain_launch", "ovhip_pic_output_grain", "ovhip_pic_digest_grain",
     "ovhip_pic_hash_host", "ovhip_pic_hash_parse_sei", "ovhip_pic_hash_equal", "ovhip_pic_hash_launch", "ovhip_pic_hash",
     "ovhip_frame_set_picture_hash", "ovhip_frame_picture_hash", "ovhip_stream_set_picture_hashes", "ovhip_stream_picture_hashes",
+    "ovhip_rgb_bytes", "ovhip_rgb_coefs", "ovhip_rgb_host", "ovhip_rgb_launch", "ovhip_pic_output_rgb", "ovhip_frame_set_rgb_output", "ovhip_stream_set_rgb_output",
 ]
 
 

@@ -32,6 +32,23 @@ int  ovhip_post_deliver_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_
 #define OVHIP_HIDDEN_ __attribute__((visibility("hidden")))
 OVHIP_HIDDEN_ int ovhip_scale_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h);
 OVHIP_HIDDEN_ int ovhip_grain_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *pic, const ovhip_fg_model *model);
+/* ---- RGB output (ovvc_rgb.c, kernels_rgb.hip): what the host twin and the launcher share -- the refusals and everything a loop or a
+ * kernel needs beside the planes.  `pic` is only looked at (plane pointers for null and overlap, sizes, strides), so it may hold host
+ * pointers.  *why (may be NULL): the reason of a refusal, a string literal. */
+typedef struct ovhip_rgb_plan_ {
+    int32_t x0, y0, W, H;              /* first luma sample of the window in the picture, output size */
+    int32_t a, b;                      /* chroma location: U = 2x - a, V = 2y - b */
+    int32_t coef[5], yoff, peak;       /* cy, rv, gu, gv, bu */
+    int32_t es;                        /* bytes per element */
+    size_t bytes;
+} ovhip_rgb_plan_;
+OVHIP_HIDDEN_ int ovhip_rgb_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, const void *dst, size_t dst_bytes,
+                                       ovhip_rgb_plan_ *plan, const char **why);
+/* the context's grow-only device scratch of the synchronous conveniences, at least `bytes` large (kernels_rgb.hip) */
+OVHIP_HIDDEN_ int ovhip_rgb_scratch_(ovhip_ctx *ctx, size_t bytes, void **d);
+/* ovhip_post_pic_, ovhip_rgb_launch of the picture it shows, and the wait for both: complete on the device at return (the frame thread) */
+int  ovhip_rgb_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_rgb_format *fmt,
+                     void *d_dst, size_t dst_bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,9 @@ struct ovhip_frame {
      * one, what the last one gave */
     int hash_on, hash_method, hash_planes, hash_expect, hash_done;
     ovhip_pic_hash_value hash_expected, hash_computed;
+    /* RGB output (ovhip_frame_set_rgb_output) of the NEXT picture completed: the destination is that picture's, so the setting ends with it */
+    int rgb_on;
+    ovhip_rgb_format rgb_fmt; ovhip_window rgb_win; void *rgb_dst; size_t rgb_bytes;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -370,6 +373,7 @@ ovhip_frame_fail(ovhip_frame *f, int status)
 {
     if (!f) return OVHIP_EINVAL;
     if (!f->status) f->status = status ? status : OVHIP_EINVAL;
+    f->rgb_on = 0;                        /* (the picture that ends here takes its RGB destination with it) */
     trace(f, OVHIP_FE_FAIL, f->key, 0, f->status, 0, 0);
     return publish(f, f->status);
 }
@@ -440,19 +444,58 @@ frame_hash(ovhip_frame *f)
     return OVHIP_OK;
 }
 
+int
+ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!fmt) { f->rgb_on = 0; return OVHIP_OK; }
+    int32_t coef[5], yoff;
+    const int r = ovhip_rgb_coefs(fmt, coef, &yoff);          /* the format's refusals come back here, not from a picture's last call */
+    if (r != OVHIP_OK) return r;
+    if (fmt->layout > OVHIP_RGB_PACKED || fmt->chroma_loc > 5 || !d_dst) return OVHIP_EINVAL;
+    if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to convert) */
+    f->rgb_on = 1; f->rgb_fmt = *fmt; f->rgb_dst = d_dst; f->rgb_bytes = dst_bytes;
+    memset(&f->rgb_win, 0, sizeof(f->rgb_win));
+    if (win) f->rgb_win = *win;
+    return OVHIP_OK;
+}
+
+/* the frame's post-process step as ovhip_post_pic_ takes it: a grain model is derived afresh for every picture, into *model */
+static int
+frame_post(const ovhip_frame *f, ovhip_post_ *post, ovhip_fg_model *model)
+{
+    *post = f->post;
+    if (post->kind == OVHIP_POST_GRAIN) {
+        const int r = ovhip_fg_derive(&f->fg, model, NULL);
+        if (r != OVHIP_OK) return r;
+        post->model = model;
+    }
+    return OVHIP_OK;
+}
+
 /* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the frame's post-process step (if any:
  * into the context's scratch picture -- f->dst itself is only read), then the delivery `out` names */
 static int
 frame_output(ovhip_frame *f, ovhip_frame_output *out)
 {
-    ovhip_post_ post = f->post;
+    ovhip_post_ post;
     ovhip_fg_model model;
-    if (post.kind == OVHIP_POST_GRAIN) {
-        const int r = ovhip_fg_derive(&f->fg, &model, NULL);
-        if (r != OVHIP_OK) return r;
-        post.model = &model;
-    }
-    return ovhip_post_deliver_(f->ctx, &f->dst, &post, out);
+    const int r = frame_post(f, &post, &model);
+    return r != OVHIP_OK ? r : ovhip_post_deliver_(f->ctx, &f->dst, &post, out);
+}
+
+/* the RGB output of a complete picture, for the same two callers: of the picture the output shows (the same post-process step; a
+ * delivery that follows makes the step again, into the same scratch picture), complete on the device at return.  The setting was
+ * this picture's: it ends here whatever happens */
+static int
+frame_rgb(ovhip_frame *f)
+{
+    if (!f->rgb_on) return OVHIP_OK;
+    f->rgb_on = 0;
+    ovhip_post_ post;
+    ovhip_fg_model model;
+    const int r = frame_post(f, &post, &model);
+    return r != OVHIP_OK ? r : ovhip_rgb_post_(f->ctx, &f->dst, &post, &f->rgb_win, &f->rgb_fmt, f->rgb_dst, f->rgb_bytes);
 }
 
 int
@@ -497,6 +540,8 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
      * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns) */
     (void)publish(f, r);
     if (r == OVHIP_OK && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
+    if (r == OVHIP_OK && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
+    f->rgb_on = 0;                        /* (a picture that failed takes its destination with it) */
     if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
         const double to0 = PT_ON() ? mono_s() : 0.0;
         r = frame_output(f, out);
@@ -618,7 +663,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     if (r != OVHIP_OK) {
         /* a latched error: nothing more goes to the device; the last call publishes the picture as failed */
         trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, r);
-        if (last) (void)publish(f, r);
+        if (last) { (void)publish(f, r); f->rgb_on = 0; }
         return r;
     }
     if (last) row_end = f->h;
@@ -675,6 +720,8 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     (void)publish(f, r);
     f->pn_pics++;
     if (r == OVHIP_OK && !f->dry && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
+    if (r == OVHIP_OK && !f->dry && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
+    f->rgb_on = 0;
     if (r == OVHIP_OK && !f->dry && out && out->mode != OVHIP_OUT_NONE) {
         PT0();
         r = frame_output(f, out);

@@ -1,0 +1,162 @@
+/* RGB output on the host: the coefficients, the refusals the launcher shares, the definition over planes in host memory, and the
+ * synchronous convenience.  Definition: include/ovvc_hip.h, "RGB output on the device"; the device half is kernels_rgb.hip.
+ * Plain C, no HIP calls of its own. */
+#include <string.h>
+#include "ovvc_hip.h"
+#include "ovvc_dpb_priv.h"
+
+/* round(p / q) for p, q > 0 (no coefficient is a tie: tests/spec_rgb.py asserts it on the exact rationals) */
+static int32_t rnd_div(uint64_t p, uint64_t q) { return (int32_t)((2 * p + q) / (2 * q)); }
+
+int
+ovhip_rgb_coefs(const ovhip_rgb_format *fmt, int32_t coef[5], int32_t *yoff)
+{
+    if (!fmt || !coef || !yoff || fmt->full_range > 1 || fmt->dtype > OVHIP_RGB_F32) return OVHIP_EINVAL;
+    uint64_t kr, kb;                                       /* in 1 / 10000 */
+    switch (fmt->matrix) {
+    case 1: kr = 2126; kb = 722; break;
+    case 5: case 6: kr = 2990; kb = 1140; break;
+    case 9: kr = 2627; kb = 593; break;
+    case 2: return OVHIP_EINVAL;                           /* unspecified: the caller must decide */
+    default: return OVHIP_EUNSUP;
+    }
+    const uint64_t one = 10000, kg = one - kr - kb;
+    const uint64_t peak = fmt->dtype == OVHIP_RGB_U8 ? 255 : 1023;
+    const uint64_t dy = fmt->full_range ? 1023 : 876, dc = fmt->full_range ? 1023 : 896;
+    const uint64_t s = (uint64_t)1 << 14;
+    coef[0] = rnd_div(s * peak, dy);                                            /* cy = sy                  */
+    coef[1] = rnd_div(s * 2 * peak * (one - kr), dc * one);                     /* rv = 2 sc (1 - Kr)       */
+    coef[2] = rnd_div(s * 2 * peak * (one - kb) * kb, dc * one * kg);           /* gu = bu Kb / Kg          */
+    coef[3] = rnd_div(s * 2 * peak * (one - kr) * kr, dc * one * kg);           /* gv = rv Kr / Kg          */
+    coef[4] = rnd_div(s * 2 * peak * (one - kb), dc * one);                     /* bu = 2 sc (1 - Kb)       */
+    *yoff = fmt->full_range ? 0 : 64;
+    return OVHIP_OK;
+}
+
+static int elem_bytes(int dtype) { return dtype == OVHIP_RGB_U8 ? 1 : (dtype == OVHIP_RGB_F32 ? 4 : 2); }
+
+/* W x H and the first luma sample of the window; 0: the sizes are no positive multiples of 4 or the window leaves nothing */
+static int
+window_geom(int32_t w, int32_t h, const ovhip_window *win, ovhip_rgb_plan_ *p)
+{
+    if (w <= 0 || h <= 0 || (w & 3) || (h & 3)) return 0;
+    const int32_t l = win ? win->offset_lft : 0, r = win ? win->offset_rgt : 0, a = win ? win->offset_abv : 0, b = win ? win->offset_blw : 0;
+    p->x0 = 2 * l; p->y0 = 2 * a; p->W = w - 2 * (l + r); p->H = h - 2 * (a + b);
+    return p->W > 0 && p->H > 0;
+}
+
+size_t
+ovhip_rgb_bytes(int32_t w, int32_t h, const ovhip_window *win, const ovhip_rgb_format *fmt)
+{
+    ovhip_rgb_plan_ p;
+    if (!fmt || fmt->dtype > OVHIP_RGB_F32 || fmt->layout > OVHIP_RGB_PACKED || !window_geom(w, h, win, &p)) return 0;
+    return (size_t)3 * (size_t)p.W * (size_t)p.H * (size_t)elem_bytes(fmt->dtype);
+}
+
+static int
+ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+
+int
+ovhip_rgb_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, const void *dst, size_t dst_bytes,
+                     ovhip_rgb_plan_ *plan, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "null argument";
+    if (!pic || !fmt || !plan) return OVHIP_EINVAL;
+    memset(plan, 0, sizeof(*plan));
+    if (fmt->dtype > OVHIP_RGB_F32 || fmt->layout > OVHIP_RGB_PACKED || fmt->chroma_loc > 5 || fmt->full_range > 1) { *why = "bad dtype / layout / chroma location / range"; return OVHIP_EINVAL; }
+    const int r = ovhip_rgb_coefs(fmt, plan->coef, &plan->yoff);
+    if (r != OVHIP_OK) { *why = r == OVHIP_EUNSUP ? "matrix coefficients not built" : "matrix coefficients unspecified"; return r; }
+    if (!dst) { *why = "null destination"; return OVHIP_EINVAL; }
+    if (!pic->y || !pic->cb || !pic->cr) { *why = "missing plane"; return OVHIP_EINVAL; }
+    if (pic->w <= 0 || pic->h <= 0 || (pic->w & 3) || (pic->h & 3)) { *why = "sizes must be positive multiples of 4"; return OVHIP_EINVAL; }
+    if (pic->stride_y < pic->w || pic->stride_c < pic->w / 2) { *why = "stride below the width"; return OVHIP_EINVAL; }
+    if (!window_geom(pic->w, pic->h, win, plan)) { *why = "the window leaves nothing"; return OVHIP_EINVAL; }
+    plan->es = elem_bytes(fmt->dtype);
+    plan->bytes = (size_t)3 * (size_t)plan->W * (size_t)plan->H * (size_t)plan->es;
+    if (dst_bytes < plan->bytes) { *why = "destination too small"; return OVHIP_EINVAL; }
+    if ((uintptr_t)dst & (uintptr_t)(plan->es - 1)) { *why = "destination not aligned to its element"; return OVHIP_EINVAL; }
+    const size_t ny = ((size_t)(pic->h - 1) * (size_t)pic->stride_y + (size_t)pic->w) * 2;
+    const size_t nc = ((size_t)(pic->h / 2 - 1) * (size_t)pic->stride_c + (size_t)(pic->w / 2)) * 2;
+    if (ranges_overlap(dst, plan->bytes, pic->y, ny) || ranges_overlap(dst, plan->bytes, pic->cb, nc) || ranges_overlap(dst, plan->bytes, pic->cr, nc)) {
+        *why = "destination overlaps the picture"; return OVHIP_EINVAL;
+    }
+    plan->a = fmt->chroma_loc & 1;
+    plan->b = fmt->chroma_loc < 2 ? 1 : (fmt->chroma_loc < 4 ? 0 : 2);
+    plan->peak = fmt->dtype == OVHIP_RGB_U8 ? 255 : 1023;
+    *why = "";
+    return OVHIP_OK;
+}
+
+static inline int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+/* float32 -> float16 bits, round to nearest even, for the values that occur: 0 and [1 / 1023, 1] (normal in both formats) */
+static inline uint16_t
+half_bits(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if (!u) return 0;
+    u += 0xFFF + ((u >> 13) & 1);
+    return (uint16_t)((u >> 13) - ((127 - 15) << 10));
+}
+
+int
+ovhip_rgb_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
+               const ovhip_window *win, const ovhip_rgb_format *fmt, void *dst, size_t dst_bytes)
+{
+    const ovhip_pic pic = { (uint16_t *)y, (uint16_t *)cb, (uint16_t *)cr, w, h, stride_y, stride_c };
+    ovhip_rgb_plan_ p;
+    const int r = ovhip_rgb_plan_make_(&pic, win, fmt, dst, dst_bytes, &p, NULL);
+    if (r != OVHIP_OK) return r;
+    const int32_t cw = w / 2, ch = h / 2;
+    const int32_t cy = p.coef[0], rv = p.coef[1], gu = p.coef[2], gv = p.coef[3], bu = p.coef[4];
+    const float to_unit = (float)(1.0 / 1023);
+    const size_t plane = (size_t)p.W * (size_t)p.H;
+    for (int32_t oy = 0; oy < p.H; ++oy) {
+        const int32_t py = p.y0 + oy, V = 2 * py - p.b, fy = V & 3;
+        const int32_t j0 = clampi(V >> 2, 0, ch - 1), j1 = clampi((V >> 2) + 1, 0, ch - 1);
+        for (int32_t ox = 0; ox < p.W; ++ox) {
+            const int32_t px = p.x0 + ox, U = 2 * px - p.a, fx = U & 3;
+            const int32_t i0 = clampi(U >> 2, 0, cw - 1), i1 = clampi((U >> 2) + 1, 0, cw - 1);
+            const int32_t w00 = (4 - fx) * (4 - fy), w01 = fx * (4 - fy), w10 = (4 - fx) * fy, w11 = fx * fy;
+            const size_t a0 = (size_t)j0 * stride_c, a1 = (size_t)j1 * stride_c;
+            const int32_t u = w00 * cb[a0 + i0] + w01 * cb[a0 + i1] + w10 * cb[a1 + i0] + w11 * cb[a1 + i1] - 8192;
+            const int32_t v = w00 * cr[a0 + i0] + w01 * cr[a0 + i1] + w10 * cr[a1 + i0] + w11 * cr[a1 + i1] - 8192;
+            const int32_t L = 16 * cy * ((int32_t)y[(size_t)py * stride_y + px] - p.yoff) + (1 << 17);
+            const int32_t rgb[3] = { clampi((L + rv * v) >> 18, 0, p.peak), clampi((L - gu * u - gv * v) >> 18, 0, p.peak), clampi((L + bu * u) >> 18, 0, p.peak) };
+            for (int c = 0; c < 3; ++c) {
+                const size_t e = fmt->layout == OVHIP_RGB_PLANAR ? (size_t)c * plane + (size_t)oy * p.W + ox : ((size_t)oy * p.W + ox) * 3 + c;
+                const float f = (float)rgb[c] * to_unit;
+                switch (fmt->dtype) {
+                case OVHIP_RGB_U8:  ((uint8_t *)dst)[e] = (uint8_t)rgb[c]; break;
+                case OVHIP_RGB_U16: ((uint16_t *)dst)[e] = (uint16_t)rgb[c]; break;
+                case OVHIP_RGB_F16: ((uint16_t *)dst)[e] = half_bits(f); break;
+                default:            ((float *)dst)[e] = f; break;
+                }
+            }
+        }
+    }
+    return OVHIP_OK;
+}
+
+int
+ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *host_dst, size_t dst_bytes)
+{
+    if (!ctx || !pic || !fmt || !host_dst) return OVHIP_EINVAL;
+    const size_t bytes = ovhip_rgb_bytes(pic->w, pic->h, win, fmt);
+    if (!bytes || dst_bytes < bytes) {
+        /* no size, or a host_dst that is too small: the launch refuses both before it looks at the pointer, and words the reason */
+        const int q = ovhip_rgb_launch(ctx, pic, win, fmt, host_dst, dst_bytes);
+        return q != OVHIP_OK ? q : OVHIP_EINVAL;
+    }
+    void *d = NULL;
+    int r = ovhip_rgb_scratch_(ctx, bytes, &d);
+    if (r == OVHIP_OK) r = ovhip_rgb_launch(ctx, pic, win, fmt, d, bytes);
+    if (r == OVHIP_OK) r = ovhip_d2h(ctx, host_dst, d, bytes);
+    return r;
+}

@@ -54,6 +54,9 @@ struct ovhip_stream {
     int hash_on, hash_method, hash_planes;
     const ovhip_pic_hash_value *hash_expected;
     ovhip_pic_hash_value *ph; uint32_t ph_n, ph_mismatch; int32_t ph_first_mismatch;
+    /* RGB output (ovhip_stream_set_rgb_output): picture idx lands in slot idx % rgb_slots of the caller's device buffer */
+    int rgb_on;
+    ovhip_rgb_format rgb_fmt; ovhip_window rgb_win; char *rgb_base; size_t rgb_bpp; uint32_t rgb_slots;
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -229,6 +232,8 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         if (tr) tr[1] = now_s() - rs->t0;
         if (s->post.kind == OVHIP_POST_GRAIN) (void)ovhip_frame_set_film_grain(f, &s->fg, p->poc);      /* (validated by the stream's setter) */
         if (s->ph) (void)ovhip_frame_set_picture_hash(f, s->hash_method, s->hash_planes, s->hash_expected ? &s->hash_expected[idx] : NULL);
+        /* (validated by the stream's setter; the conversion is this frame thread's, after its wait: nothing goes through the output thread) */
+        if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, s->rgb_base + (size_t)(idx % s->rgb_slots) * s->rgb_bpp, s->rgb_bpp);
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
@@ -548,7 +553,26 @@ ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, const
 }
 
 int
-ovhip_stream_picture_hashes(const ovhip_stream *s, ovhip_pic_hash_value *computed, uint32_t *n_mismatch, int32_t *first_mismatch)
+ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots)
+{
+    if (!s) return OVHIP_EINVAL;
+    if (!fmt) { s->rgb_on = 0; return OVHIP_OK; }
+    int32_t coef[5], yoff;
+    const int r = ovhip_rgb_coefs(fmt, coef, &yoff);
+    if (r != OVHIP_OK) return r;
+    if (fmt->layout > OVHIP_RGB_PACKED || fmt->chroma_loc > 5 || !d_base || !n_slots) return OVHIP_EINVAL;
+    /* the size the stream outputs: its output scale's, else its pictures' */
+    const int scaled = s->post.kind == OVHIP_POST_SCALE;
+    const size_t need = ovhip_rgb_bytes(scaled ? s->post.out_w : s->cfg.w, scaled ? s->post.out_h : s->cfg.h, win, fmt);
+    if (!need || bytes_per_picture < need) return OVHIP_EINVAL;
+    s->rgb_on = 1; s->rgb_fmt = *fmt; s->rgb_base = (char *)d_base; s->rgb_bpp = bytes_per_picture; s->rgb_slots = n_slots;
+    memset(&s->rgb_win, 0, sizeof(s->rgb_win));
+    if (win) s->rgb_win = *win;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_picture_hashes(const ovhip_stream *s,ovhip_pic_hash_value *computed, uint32_t *n_mismatch, int32_t *first_mismatch)
 {
     if (!s || !s->ph) return OVHIP_EINVAL;
     if (computed) memcpy(computed, s->ph, (size_t)s->ph_n * sizeof(*computed));

@@ -15,6 +15,36 @@ class EngineError(RuntimeError):
     pass
 
 
+def rgb_format(matrix: int = 1, full_range: int = 0, chroma_loc: int = 0, dtype: int = capi.RGB_U8, layout: int = capi.RGB_PLANAR) -> capi.RgbFormat:
+    """an ovhip_rgb_format (include/ovvc_hip.h, "RGB output on the device")"""
+    return capi.RgbFormat(matrix, full_range, chroma_loc, dtype, layout)
+
+
+def rgb_shape(fmt: capi.RgbFormat, w: int, h: int, window=(0, 0, 0, 0)) -> tuple:
+    """the array shape of the RGB picture of a w x h picture under `window`: (3, H, W) planar, (H, W, 3) packed"""
+    W, H = w - 2 * (window[0] + window[1]), h - 2 * (window[2] + window[3])
+    return (3, H, W) if fmt.layout == capi.RGB_PLANAR else (H, W, 3)
+
+
+def _rgb_tensor(tensor, fmt: capi.RgbFormat, shape: tuple, n: "int | None" = None) -> "tuple[int, int]":
+    """(data_ptr, bytes per picture) of a torch tensor on the device that is to take RGB pictures of `shape` (n of them, one after the
+    other, with n given) -- after checking device, dtype, contiguity and shape.  The one place torch is more than a test import."""
+    import torch
+    want = {capi.RGB_U8: torch.uint8, capi.RGB_U16: torch.uint16, capi.RGB_F16: torch.float16, capi.RGB_F32: torch.float32}.get(fmt.dtype)
+    if want is None:
+        raise EngineError(f"rgb output: dtype {fmt.dtype}")
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise EngineError("rgb output: the destination must be a torch tensor on the device")
+    if tensor.dtype != want:
+        raise EngineError(f"rgb output: tensor dtype {tensor.dtype}, the format asks for {want}")
+    if not tensor.is_contiguous():
+        raise EngineError("rgb output: the destination tensor must be contiguous")
+    full = tuple(shape) if n is None else (n, *shape)
+    if tuple(tensor.shape) != full:
+        raise EngineError(f"rgb output: tensor shape {tuple(tensor.shape)}, the pictures need {full}")
+    return tensor.data_ptr(), shape[0] * shape[1] * shape[2] * tensor.element_size()
+
+
 class Context:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
@@ -396,6 +426,26 @@ class DevPic:
                                                C.c_void_p(d_out.ptr.value + offset) if d_out is not None else None)
         if check:
             self.ctx._chk(r, "pic_hash_launch")
+        return r
+
+    def rgb(self, fmt: capi.RgbFormat, window=(0, 0, 0, 0)) -> np.ndarray:
+        """ovhip_pic_output_rgb: this picture as RGB (include/ovvc_hip.h, "RGB output on the device"), converted on the device and
+        fetched with one D2H -> (3, H, W) or (H, W, 3) in the format's dtype"""
+        win = capi.Window(*window)
+        n = self.ctx.lib.ovhip_rgb_bytes(self.w, self.h, C.byref(win), C.byref(fmt))
+        if not n:
+            raise EngineError("rgb: bad size / window / format")
+        out = np.empty(rgb_shape(fmt, self.w, self.h, window), capi.RGB_NP_DTYPE[fmt.dtype])
+        self.ctx._chk(self.ctx.lib.ovhip_pic_output_rgb(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), out.ctypes.data, out.nbytes), "pic_output_rgb")
+        return out
+
+    def rgb_into(self, ptr: int, nbytes: int, fmt: capi.RgbFormat, window=(0, 0, 0, 0), check: bool = True) -> int:
+        """ovhip_rgb_launch into device memory at `ptr` (a DevBuf's address plus an offset, a tensor's data_ptr()).  Asynchronous."""
+        win = capi.Window(*window)
+        r = self.ctx.lib.ovhip_rgb_launch(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt) if fmt is not None else None,
+                                          C.c_void_p(ptr) if ptr else None, nbytes)
+        if check:
+            self.ctx._chk(r, "rgb_launch")
         return r
 
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
@@ -853,6 +903,25 @@ class Frame:
         r = self.lib.ovhip_frame_set_output_scale(self.f, out_w, out_h, C.byref(info))
         if r < 0 and check:
             raise EngineError(f"frame_set_output_scale: {r}")
+        if r >= 0:
+            self._out_size = (out_w, out_h) if out_w or out_h else None
+        return r
+
+    def set_rgb_output(self, dst, fmt: "capi.RgbFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
+        """ovhip_frame_set_rgb_output: the NEXT picture completed is also written as RGB into `dst` -- a torch tensor on the device of
+        shape (3, H, W) / (H, W, 3) for the size the frame outputs (checked here), or a device address with `nbytes`; fmt None: off"""
+        if fmt is None:
+            return self.lib.ovhip_frame_set_rgb_output(self.f, None, None, None, 0)
+        if isinstance(dst, int):
+            ptr = dst
+        else:
+            w, h = getattr(self, "_out_size", None) or (self.w, self.h)
+            ptr, nbytes = _rgb_tensor(dst, fmt, rgb_shape(fmt, w, h, window))
+            self._rgb_keep = dst
+        win = capi.Window(*window)
+        r = self.lib.ovhip_frame_set_rgb_output(self.f, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, nbytes or 0)
+        if check and r:
+            raise EngineError(f"frame_set_rgb_output: {r}")
         return r
 
     def job(self) -> "Job":
@@ -917,6 +986,28 @@ class Stream:
         r = self.lib.ovhip_stream_set_output_scale(self.s, out_w, out_h, C.byref(info))
         if r < 0 and check:
             raise EngineError(f"stream_set_output_scale: {r}")
+        if r >= 0:
+            self._out_size = (out_w, out_h) if out_w or out_h else None
+        return r
+
+    def set_rgb_output(self, dst, fmt: "capi.RgbFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
+                       n_slots: "int | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_rgb_output: picture idx of the following runs is also written as RGB into slot idx % n of `dst` -- a torch
+        tensor on the device of shape (n, 3, H, W) / (n, H, W, 3) for the size the stream outputs (checked here, kept alive here), or
+        a device address with bytes_per_picture and n_slots; fmt None: off"""
+        if fmt is None:
+            return self.lib.ovhip_stream_set_rgb_output(self.s, None, None, None, 0, 0)
+        if isinstance(dst, int):
+            ptr = dst
+        else:
+            w, h = getattr(self, "_out_size", None) or (self.cfg.w, self.cfg.h)
+            n_slots = int(dst.shape[0]) if getattr(dst, "ndim", 0) == 4 else 0
+            ptr, bytes_per_picture = _rgb_tensor(dst, fmt, rgb_shape(fmt, w, h, window), n_slots)
+            self._keep.append(dst)
+        win = capi.Window(*window)
+        r = self.lib.ovhip_stream_set_rgb_output(self.s, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, bytes_per_picture or 0, n_slots or 0)
+        if check and r:
+            raise EngineError(f"stream_set_rgb_output: {r}")
         return r
 
     def set_picture_hashes(self, method: int, n_planes: int = 3, expected=None, check: bool = True) -> int:
