@@ -1318,6 +1318,62 @@ int  ovhip_rgb_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *
 int  ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *host_dst, size_t dst_bytes);
 
 /* ------------------------------------------------------------------------------------
+ * Surface output on the device: a finished 10-bit 4:2:0 picture as a 4:2:0 SURFACE in DEVICE memory -- the picture's own samples in the
+ * pixel format and with the row pitch a hardware encoder, a display pipeline or a video library dictates; nothing is downloaded.
+ * Nothing in the reference does this (dectest writes 16-bit planes).  The definition is integer only, so every implementation of it
+ * (tests/spec_surface.py, ovhip_surface_host, k_surface) is compared for equality.
+ *
+ *   Input    an ovhip_pic of w x h (positive, even, at most 16384) and a window in chroma units, read exactly as the packed output
+ *            reads it: W = w - 2 (lft + rgt), H = h - 2 (abv + blw), the first luma sample is (2 lft, 2 abv), chroma is
+ *            W/2 x H/2 from (lft, abv); a NULL window means no crop.
+ *   Formats  NV12 (1-byte elements) and P010 (2 bytes, little endian): the Y plane, H rows of W elements, then ONE chroma plane of
+ *            H/2 rows of W elements, Cb and Cr interleaved, Cb first.  I420 (1 byte) and I010 (2 bytes, little endian): the Y plane,
+ *            the Cb plane, the Cr plane, the chroma planes H/2 rows of W/2 elements.
+ *   Values   s is the stored 10-bit sample.  I010: s.  P010: s << 6 (the low six bits zero).  NV12 and I420:
+ *              rounding OVHIP_SURF_ROUND    min(255, (s + 2) >> 2)
+ *              rounding OVHIP_SURF_DITHER   min(255, (s + D[y & 1][x & 1]) >> 2),  D = {{0, 2}, {3, 1}}
+ *            where (x, y) is the sample's column and row in its own OUTPUT plane, after the crop (the window's first sample is
+ *            (0, 0)), and the Cb and the Cr of an interleaved pair share the pair's column.  Property: on a flat area of value
+ *            s <= 1020 the four outputs of any 2 x 2 cell aligned to even output coordinates sum to exactly s (the thresholds are
+ *            0, 1, 2, 3: the cell keeps the two bits the shift drops).  The 16-bit formats take rounding 0 only.
+ *   Layout   linear.  pitch_y, pitch_c: bytes from one row to the next, 0 = tight (the row's own bytes); one pitch_c for both chroma
+ *            planes of a planar format.  offset_c[k]: byte offset of chroma plane k from the base, 0 = right behind the plane
+ *            before, that is pitch * rows of that plane behind its start -- so a tight surface is contiguous.  Semi-planar formats
+ *            use offset_c[0] only.  The size of the surface is the largest end of a plane's LAST ROW'S OWN BYTES (with planes in
+ *            their order: of the last plane's), not pitch * rows.  Bytes between a row's end and the next row's start and bytes
+ *            between planes are NEVER written.  Tiled or swizzled surfaces are not built.
+ * OVHIP_SURF_I010, tight, with offsets 0, is byte for byte the frame ovhip_output_pack_launch / ovhip_pic_output write.
+ * Refused (OVHIP_EINVAL) before anything is launched or written, the reason in the context's error text: a null picture, plane or
+ * destination; odd or non-positive sizes, or sizes above 16384; a picture stride below its width; a window that leaves nothing; an
+ * unknown format or rounding; a rounding other than 0 on a 16-bit format; non-zero rsv; a non-zero offset_c[1] on a semi-planar
+ * format; a pitch below the row's bytes; a pitch or offset that is not a multiple of the element size; a destination that is not
+ * element-aligned; planes that overlap one another; dst_bytes below the surface's size ("too small", with both numbers); a
+ * destination that overlaps the picture.  Not done: 4:2:2 and 4:4:4, NV21 / YV12 / P016, error diffusion, any colour conversion.
+ * ---------------------------------------------------------------------------------- */
+enum { OVHIP_SURF_NV12 = 0, OVHIP_SURF_P010 = 1, OVHIP_SURF_I420 = 2, OVHIP_SURF_I010 = 3 };      /* ovhip_surface_format.format */
+enum { OVHIP_SURF_ROUND = 0, OVHIP_SURF_DITHER = 1 };                                             /* ovhip_surface_format.rounding */
+typedef struct ovhip_surface_format {
+    uint8_t  format, rounding, rsv[2];   /* rsv must be 0 */
+    uint32_t pitch_y, pitch_c;           /* bytes from one row to the next; 0 = tight (the row's own bytes) */
+    uint64_t offset_c[2];                /* byte offset of the chroma plane(s) from the base; 0 = right behind the plane before */
+} ovhip_surface_format;                  /* 32 bytes */
+/* Bytes of the surface of a w x h picture under win (NULL: no crop): the end of the last plane's last row's own bytes; 0 for anything
+ * the launch would refuse on these arguments.  Host only. */
+size_t ovhip_surface_bytes(int32_t w, int32_t h, const ovhip_window *win, const ovhip_surface_format *fmt);
+/* The definition on host planes into host memory (strides in samples): tests, and callers that hold the picture on the host.
+ * Refusals as the launch's; nothing is written when it refuses. */
+int  ovhip_surface_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
+                        const ovhip_window *win, const ovhip_surface_format *fmt, void *dst, size_t dst_bytes);
+/* d_dst: DEVICE, at least ovhip_surface_bytes() bytes, aligned to its element (k_surface: one launch for all planes, a lane owns 16
+ * elements of a row; 16-byte loads and stores where a run's address allows, narrower where it does not -- a row tail, an odd pitch, a
+ * window offset).  Asynchronous on the ctx stream; allocates nothing. */
+int  ovhip_surface_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, void *d_dst, size_t dst_bytes);
+/* Synchronous convenience beside ovhip_pic_output: the launch into the context's grow-only scratch, then one D2H into host_dst
+ * (dst_bytes >= ovhip_surface_bytes(), pinned or pageable; a layout with gaps: one strided D2H per plane, so the gaps stay unwritten
+ * in host memory too). */
+int  ovhip_pic_output_surface(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, void *host_dst, size_t dst_bytes);
+
+/* ------------------------------------------------------------------------------------
  * Output resampling: a stream that changes its coded size (RPR) can leave the device at ONE size.  Replaces pp_sample_rate_conv
  * (pp_pic_scale.c:250-377), called once per plane by pp_process_frame (post_proc.c:116-126) when the decoder's `upscale` option is
  * on (ovdec.c:562; ovdec.c:479 / :523 are the call sites), for up-sampling and equal size, bit-exactly -- including its phase, which
@@ -1683,6 +1739,16 @@ int  ovhip_frame_picture_hash(const ovhip_frame *f, ovhip_pic_hash_value *comput
  * The format's refusals come back here, the launch's from the picture's last call: a failed conversion fails that call's return
  * value, never the picture's publication.  A dry frame accepts the call and does nothing. */
 int  ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
+/* Surface output ("Surface output on the device" above) of the NEXT picture completed, exactly as the RGB output beside it: per
+ * picture, fmt NULL switches it off (the default); the conversion runs in ovhip_frame_submit and in the last ovhip_frame_band after
+ * ovhip_job_wait, on the picture the output shows (after the frame's post-process step; win is in chroma units of THAT picture),
+ * whatever out->mode is, a NULL out included, and is complete on the device when the call returns.  What is published to the DPB is
+ * unchanged; fmt and win are copied.  The format's refusals that need no picture (enum values, rsv, rounding, offset_c[1], pitch and
+ * offset multiples, a null destination) come back here, the others from the picture's last call: a failed conversion fails that
+ * call's return value, never the picture's publication.  A dry frame accepts the call and does nothing.  RGB and surface output are
+ * independent: a frame with both set writes both.  Each of RGB output, surface output and delivery makes its own post-process step
+ * (into the same scratch picture): with two of them the step runs twice, with all three three times. */
+int  ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
 int  ovhip_frame_fail(ovhip_frame *f, int status);
 const char *ovhip_frame_last_error(const ovhip_frame *f);
 
@@ -1831,6 +1897,12 @@ int  ovhip_stream_picture_hashes(const ovhip_stream *s, ovhip_pic_hash_value *co
  * ovhip_rgb_bytes for the size the stream outputs (its output scale's, else its pictures'); the format's refusals as
  * ovhip_rgb_coefs.  A slot is the caller's to reuse once the picture n_slots later is decoded: the driver does not wait for a reader. */
 int  ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
+/* Surface output for the following runs, as the RGB output above and independent of it: picture idx lands at
+ * d_base + (idx % n_slots) * bytes_per_picture in DEVICE memory, written by the frame thread that completes it
+ * (ovhip_frame_set_surface_output), whatever the stream's output mode is.  fmt NULL: off.  OVHIP_EINVAL for a null base, n_slots 0, a
+ * format the frame's setter refuses, or a bytes_per_picture below ovhip_surface_bytes() for the size the stream outputs (its output
+ * scale's, else its pictures').  A slot is the caller's to reuse once the picture n_slots later is decoded. */
+int  ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
 /* The DPB key of picture idx of the current stream (valid while the run that decoded it kept it: OVHIP_STREAM_KEEP). */
 const void *ovhip_stream_key(const ovhip_stream *s, uint32_t idx);
 /* test hook: the next flush of `job` that has a flow launch is ABORTED for real (the device's abort word is set before the

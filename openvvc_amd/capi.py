@@ -498,6 +498,17 @@ class RgbFormat(C.Structure):
                 ("rsv", C.c_uint8 * 3)]
 
 
+SURF_NV12, SURF_P010, SURF_I420, SURF_I010 = 0, 1, 2, 3      # ovhip_surface_format.format
+SURF_ROUND, SURF_DITHER = 0, 1                                # ovhip_surface_format.rounding
+SURF_ELEM_BYTES = {SURF_NV12: 1, SURF_P010: 2, SURF_I420: 1, SURF_I010: 2}
+
+
+class SurfaceFormat(C.Structure):
+    """ovhip_surface_format: pixel format, rounding of the 8-bit formats, row pitches and chroma plane offsets in bytes (0: tight)"""
+    _fields_ = [("format", C.c_uint8), ("rounding", C.c_uint8), ("rsv", C.c_uint8 * 2), ("pitch_y", C.c_uint32), ("pitch_c", C.c_uint32),
+                ("offset_c", C.c_uint64 * 2)]
+
+
 class Md5State(C.Structure):
     _fields_ = [("h", C.c_uint32 * 4), ("n_bytes", C.c_uint64), ("buf", C.c_uint8 * 64)]
 
@@ -762,6 +773,12 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_rgb": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, C.c_size_t]),
         "ovhip_frame_set_rgb_output": (C.c_int, [vp, P(RgbFormat), P(Window), vp, C.c_size_t]),
         "ovhip_stream_set_rgb_output": (C.c_int, [vp, P(RgbFormat), P(Window), vp, C.c_size_t, u32]),
+        "ovhip_surface_bytes": (C.c_size_t, [i32, i32, P(Window), P(SurfaceFormat)]),
+        "ovhip_surface_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(SurfaceFormat), vp, C.c_size_t]),
+        "ovhip_surface_launch": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
+        "ovhip_pic_output_surface": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
+        "ovhip_frame_set_surface_output": (C.c_int, [vp, P(SurfaceFormat), P(Window), vp, C.c_size_t]),
+        "ovhip_stream_set_surface_output": (C.c_int, [vp, P(SurfaceFormat), P(Window), vp, C.c_size_t, u32]),
     }
     ab_build = "OVVC_HIP_LIB_NAME" in os.environ       # tools/ab_lib.sh: an OLDER build of the library beside the current one (its newer entry points are not called)
     for name, (res, args) in sigs.items():
@@ -808,6 +825,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_pic_hash_host", "ovhip_pic_hash_parse_sei", "ovhip_pic_hash_equal", "ovhip_pic_hash_launch", "ovhip_pic_hash",
     "ovhip_frame_set_picture_hash", "ovhip_frame_picture_hash", "ovhip_stream_set_picture_hashes", "ovhip_stream_picture_hashes",
     "ovhip_rgb_bytes", "ovhip_rgb_coefs", "ovhip_rgb_host", "ovhip_rgb_launch", "ovhip_pic_output_rgb", "ovhip_frame_set_rgb_output", "ovhip_stream_set_rgb_output",
+    "ovhip_surface_bytes", "ovhip_surface_host", "ovhip_surface_launch", "ovhip_pic_output_surface", "ovhip_frame_set_surface_output", "ovhip_stream_set_surface_output",
 ]
 
 

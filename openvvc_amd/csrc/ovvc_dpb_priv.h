@@ -49,6 +49,24 @@ OVHIP_HIDDEN_ int ovhip_rgb_scratch_(ovhip_ctx *ctx, size_t bytes, void **d);
 /* ovhip_post_pic_, ovhip_rgb_launch of the picture it shows, and the wait for both: complete on the device at return (the frame thread) */
 int  ovhip_rgb_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_rgb_format *fmt,
                      void *d_dst, size_t dst_bytes);
+/* ---- Surface output (ovvc_surface.c, kernels_surface.hip): what the host twin and the launcher share, as the RGB plan above.  Plane
+ * 0 is luma; a semi-planar format has ONE chroma plane (1: Cb and Cr interleaved), a planar one two (1: Cb, 2: Cr). */
+typedef struct ovhip_surface_plan_ {
+    int32_t x0, y0, W, H;              /* first luma sample of the window in the picture, output size */
+    int32_t es, n_planes, semi, dither;/* bytes per element; 2 or 3; interleaved chroma; OVHIP_SURF_DITHER */
+    int32_t shift;                     /* P010: 6, else 0 */
+    int32_t elems[3], rows[3];         /* elements of a row and rows, per plane */
+    size_t pitch[3], off[3];           /* bytes from row to row, byte offset from the base */
+    size_t bytes;                      /* the surface's size: the largest end of a plane's last row's own bytes */
+} ovhip_surface_plan_;
+/* the refusals that need no picture, no size and no destination: enum values, rsv, rounding, offset_c[1], pitch and offset multiples */
+OVHIP_HIDDEN_ int ovhip_surface_format_check_(const ovhip_surface_format *fmt, const char **why);
+/* on a refusal for "destination too small" plan->bytes holds the size needed */
+OVHIP_HIDDEN_ int ovhip_surface_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, const void *dst, size_t dst_bytes,
+                                           ovhip_surface_plan_ *plan, const char **why);
+/* ovhip_post_pic_, ovhip_surface_launch of the picture it shows, and the wait for both: complete on the device at return (the frame thread) */
+int  ovhip_surface_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_surface_format *fmt,
+                         void *d_dst, size_t dst_bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,9 @@ struct ovhip_frame {
     /* RGB output (ovhip_frame_set_rgb_output) of the NEXT picture completed: the destination is that picture's, so the setting ends with it */
     int rgb_on;
     ovhip_rgb_format rgb_fmt; ovhip_window rgb_win; void *rgb_dst; size_t rgb_bytes;
+    /* surface output (ovhip_frame_set_surface_output), the same way and independent of it */
+    int surf_on;
+    ovhip_surface_format surf_fmt; ovhip_window surf_win; void *surf_dst; size_t surf_bytes;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -373,7 +376,7 @@ ovhip_frame_fail(ovhip_frame *f, int status)
 {
     if (!f) return OVHIP_EINVAL;
     if (!f->status) f->status = status ? status : OVHIP_EINVAL;
-    f->rgb_on = 0;                        /* (the picture that ends here takes its RGB destination with it) */
+    f->rgb_on = 0; f->surf_on = 0;        /* (the picture that ends here takes its RGB and surface destinations with it) */
     trace(f, OVHIP_FE_FAIL, f->key, 0, f->status, 0, 0);
     return publish(f, f->status);
 }
@@ -499,6 +502,34 @@ frame_rgb(ovhip_frame *f)
 }
 
 int
+ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!fmt) { f->surf_on = 0; return OVHIP_OK; }
+    const int r = ovhip_surface_format_check_(fmt, NULL);      /* the format's refusals that need no picture come back here */
+    if (r != OVHIP_OK) return r;
+    if (!d_dst) return OVHIP_EINVAL;
+    if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to convert) */
+    f->surf_on = 1; f->surf_fmt = *fmt; f->surf_dst = d_dst; f->surf_bytes = dst_bytes;
+    memset(&f->surf_win, 0, sizeof(f->surf_win));
+    if (win) f->surf_win = *win;
+    return OVHIP_OK;
+}
+
+/* the surface output of a complete picture, as frame_rgb: a post-process step of its own, complete on the device at return, and the
+ * setting ends here whatever happens */
+static int
+frame_surface(ovhip_frame *f)
+{
+    if (!f->surf_on) return OVHIP_OK;
+    f->surf_on = 0;
+    ovhip_post_ post;
+    ovhip_fg_model model;
+    const int r = frame_post(f, &post, &model);
+    return r != OVHIP_OK ? r : ovhip_surface_post_(f->ctx, &f->dst, &post, &f->surf_win, &f->surf_fmt, f->surf_dst, f->surf_bytes);
+}
+
+int
 ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const ovhip_job_params *params, ovhip_frame_output *out)
 {
     if (!f || !params || !f->live) return OVHIP_EINVAL;
@@ -541,7 +572,8 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
     (void)publish(f, r);
     if (r == OVHIP_OK && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
     if (r == OVHIP_OK && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
-    f->rgb_on = 0;                        /* (a picture that failed takes its destination with it) */
+    if (r == OVHIP_OK && (r = frame_surface(f)) != OVHIP_OK) fail(f, r, "surface output");
+    f->rgb_on = 0; f->surf_on = 0;        /* (a picture that failed takes its destinations with it) */
     if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
         const double to0 = PT_ON() ? mono_s() : 0.0;
         r = frame_output(f, out);
@@ -663,7 +695,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     if (r != OVHIP_OK) {
         /* a latched error: nothing more goes to the device; the last call publishes the picture as failed */
         trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, r);
-        if (last) { (void)publish(f, r); f->rgb_on = 0; }
+        if (last) { (void)publish(f, r); f->rgb_on = 0; f->surf_on = 0; }
         return r;
     }
     if (last) row_end = f->h;
@@ -721,7 +753,8 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     f->pn_pics++;
     if (r == OVHIP_OK && !f->dry && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
     if (r == OVHIP_OK && !f->dry && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
-    f->rgb_on = 0;
+    if (r == OVHIP_OK && !f->dry && (r = frame_surface(f)) != OVHIP_OK) fail(f, r, "surface output");
+    f->rgb_on = 0; f->surf_on = 0;
     if (r == OVHIP_OK && !f->dry && out && out->mode != OVHIP_OUT_NONE) {
         PT0();
         r = frame_output(f, out);

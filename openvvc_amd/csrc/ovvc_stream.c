@@ -57,6 +57,9 @@ struct ovhip_stream {
     /* RGB output (ovhip_stream_set_rgb_output): picture idx lands in slot idx % rgb_slots of the caller's device buffer */
     int rgb_on;
     ovhip_rgb_format rgb_fmt; ovhip_window rgb_win; char *rgb_base; size_t rgb_bpp; uint32_t rgb_slots;
+    /* surface output (ovhip_stream_set_surface_output): the same way, in a buffer of its own */
+    int surf_on;
+    ovhip_surface_format surf_fmt; ovhip_window surf_win; char *surf_base; size_t surf_bpp; uint32_t surf_slots;
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -234,6 +237,7 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         if (s->ph) (void)ovhip_frame_set_picture_hash(f, s->hash_method, s->hash_planes, s->hash_expected ? &s->hash_expected[idx] : NULL);
         /* (validated by the stream's setter; the conversion is this frame thread's, after its wait: nothing goes through the output thread) */
         if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, s->rgb_base + (size_t)(idx % s->rgb_slots) * s->rgb_bpp, s->rgb_bpp);
+        if (s->surf_on) (void)ovhip_frame_set_surface_output(f, &s->surf_fmt, &s->surf_win, s->surf_base + (size_t)(idx % s->surf_slots) * s->surf_bpp, s->surf_bpp);
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
@@ -568,6 +572,24 @@ ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const 
     s->rgb_on = 1; s->rgb_fmt = *fmt; s->rgb_base = (char *)d_base; s->rgb_bpp = bytes_per_picture; s->rgb_slots = n_slots;
     memset(&s->rgb_win, 0, sizeof(s->rgb_win));
     if (win) s->rgb_win = *win;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots)
+{
+    if (!s) return OVHIP_EINVAL;
+    if (!fmt) { s->surf_on = 0; return OVHIP_OK; }
+    const int r = ovhip_surface_format_check_(fmt, NULL);
+    if (r != OVHIP_OK) return r;
+    if (!d_base || !n_slots) return OVHIP_EINVAL;
+    /* the size the stream outputs: its output scale's, else its pictures' */
+    const int scaled = s->post.kind == OVHIP_POST_SCALE;
+    const size_t need = ovhip_surface_bytes(scaled ? s->post.out_w : s->cfg.w, scaled ? s->post.out_h : s->cfg.h, win, fmt);
+    if (!need || bytes_per_picture < need) return OVHIP_EINVAL;
+    s->surf_on = 1; s->surf_fmt = *fmt; s->surf_base = (char *)d_base; s->surf_bpp = bytes_per_picture; s->surf_slots = n_slots;
+    memset(&s->surf_win, 0, sizeof(s->surf_win));
+    if (win) s->surf_win = *win;
     return OVHIP_OK;
 }
 

@@ -45,6 +45,34 @@ def _rgb_tensor(tensor, fmt: capi.RgbFormat, shape: tuple, n: "int | None" = Non
     return tensor.data_ptr(), shape[0] * shape[1] * shape[2] * tensor.element_size()
 
 
+def surface_format(format: int = capi.SURF_NV12, rounding: int = capi.SURF_ROUND, pitch_y: int = 0, pitch_c: int = 0, offset_c=(0, 0)) -> capi.SurfaceFormat:
+    """an ovhip_surface_format (include/ovvc_hip.h, "Surface output on the device"); pitches and offsets in bytes, 0: tight"""
+    fmt = capi.SurfaceFormat(format, rounding)
+    fmt.pitch_y, fmt.pitch_c = pitch_y, pitch_c
+    fmt.offset_c[0], fmt.offset_c[1] = offset_c
+    return fmt
+
+
+def _surface_tensor(tensor, fmt: capi.SurfaceFormat, need: int, slots: bool = False) -> "tuple[int, int, int]":
+    """(data_ptr, bytes of one slot, slots) of a torch tensor on the device that is to take surfaces of `need` bytes -- one, or with
+    `slots` one per index of its first dimension -- after checking device, dtype, contiguity and size"""
+    import torch
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise EngineError("surface output: the destination must be a torch tensor on the device")
+    allowed = (torch.uint8,) if capi.SURF_ELEM_BYTES.get(fmt.format) == 1 else (torch.uint8, torch.int16, torch.uint16)
+    if tensor.dtype not in allowed:
+        raise EngineError(f"surface output: tensor dtype {tensor.dtype}, the format takes {allowed}")
+    if not tensor.is_contiguous():
+        raise EngineError("surface output: the destination tensor must be contiguous")
+    if slots and tensor.ndim < 2:
+        raise EngineError("surface output: a stream's tensor has the slots as its first dimension")
+    n = int(tensor.shape[0]) if slots else 1
+    per = tensor.numel() * tensor.element_size() // n if n else 0
+    if not need or per < need:
+        raise EngineError(f"surface output: {per} bytes per picture, the surface needs {need}")
+    return tensor.data_ptr(), per, n
+
+
 class Context:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
@@ -446,6 +474,26 @@ class DevPic:
                                           C.c_void_p(ptr) if ptr else None, nbytes)
         if check:
             self.ctx._chk(r, "rgb_launch")
+        return r
+
+    def surface(self, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0)) -> np.ndarray:
+        """ovhip_pic_output_surface: this picture as a surface (include/ovvc_hip.h, "Surface output on the device"), written on the
+        device and fetched -> the surface's bytes (bytes the layout leaves out are 0)"""
+        win = capi.Window(*window)
+        n = self.ctx.lib.ovhip_surface_bytes(self.w, self.h, C.byref(win), C.byref(fmt))
+        if not n:
+            raise EngineError("surface: bad size / window / format")
+        out = np.zeros(n, np.uint8)
+        self.ctx._chk(self.ctx.lib.ovhip_pic_output_surface(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), out.ctypes.data, out.nbytes), "pic_output_surface")
+        return out
+
+    def surface_into(self, ptr: int, nbytes: int, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0), check: bool = True) -> int:
+        """ovhip_surface_launch into device memory at `ptr` (a DevBuf's address plus an offset, a tensor's data_ptr()).  Asynchronous."""
+        win = capi.Window(*window)
+        r = self.ctx.lib.ovhip_surface_launch(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt) if fmt is not None else None,
+                                              C.c_void_p(ptr) if ptr else None, nbytes)
+        if check:
+            self.ctx._chk(r, "surface_launch")
         return r
 
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
@@ -924,6 +972,24 @@ class Frame:
             raise EngineError(f"frame_set_rgb_output: {r}")
         return r
 
+    def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
+        """ovhip_frame_set_surface_output: the NEXT picture completed is also written as a surface into `dst` -- a contiguous torch
+        tensor on the device (uint8, or int16 / uint16 for the 16-bit formats) of at least the surface's bytes for the size the frame
+        outputs (checked here), or a device address with `nbytes`; fmt None: off"""
+        if fmt is None:
+            return self.lib.ovhip_frame_set_surface_output(self.f, None, None, None, 0)
+        win = capi.Window(*window)
+        if isinstance(dst, int):
+            ptr = dst
+        else:
+            w, h = getattr(self, "_out_size", None) or (self.w, self.h)
+            ptr, nbytes, _n = _surface_tensor(dst, fmt, self.lib.ovhip_surface_bytes(w, h, C.byref(win), C.byref(fmt)))
+            self._surface_keep = dst
+        r = self.lib.ovhip_frame_set_surface_output(self.f, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, nbytes or 0)
+        if check and r:
+            raise EngineError(f"frame_set_surface_output: {r}")
+        return r
+
     def job(self) -> "Job":
         """the frame's own job as an engine.Job view (not owned)"""
         j = Job.__new__(Job)
@@ -1008,6 +1074,26 @@ class Stream:
         r = self.lib.ovhip_stream_set_rgb_output(self.s, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, bytes_per_picture or 0, n_slots or 0)
         if check and r:
             raise EngineError(f"stream_set_rgb_output: {r}")
+        return r
+
+    def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
+                           n_slots: "int | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_surface_output: picture idx of the following runs is also written as a surface into slot idx % n of `dst` --
+        a contiguous torch tensor on the device whose first dimension is the slot count and whose slots hold at least the surface's
+        bytes for the size the stream outputs (checked here, kept alive here), or a device address with bytes_per_picture and n_slots;
+        fmt None: off"""
+        if fmt is None:
+            return self.lib.ovhip_stream_set_surface_output(self.s, None, None, None, 0, 0)
+        win = capi.Window(*window)
+        if isinstance(dst, int):
+            ptr = dst
+        else:
+            w, h = getattr(self, "_out_size", None) or (self.cfg.w, self.cfg.h)
+            ptr, bytes_per_picture, n_slots = _surface_tensor(dst, fmt, self.lib.ovhip_surface_bytes(w, h, C.byref(win), C.byref(fmt)), slots=True)
+            self._keep.append(dst)
+        r = self.lib.ovhip_stream_set_surface_output(self.s, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, bytes_per_picture or 0, n_slots or 0)
+        if check and r:
+            raise EngineError(f"stream_set_surface_output: {r}")
         return r
 
     def set_picture_hashes(self, method: int, n_planes: int = 3, expected=None, check: bool = True) -> int:
