@@ -1374,6 +1374,94 @@ int  ovhip_surface_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_wind
 int  ovhip_pic_output_surface(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, void *host_dst, size_t dst_bytes);
 
 /* ------------------------------------------------------------------------------------
+ * Motion field output on the device: the motion of a decoded picture -- vectors, reference slots and prediction kinds of every inter
+ * block -- as a dense field on the 4x4 luma grid in DEVICE memory, in the consumer's dtype and layout; nothing is downloaded.  What
+ * ffmpeg's export_mvs side data is for: compressed-domain analytics, re-encoder motion hints, temporal denoisers.  Nothing in the
+ * reference does this.  The definition is exact, so every implementation of it (tests/spec_mvfield.py, ovhip_mvfield_host,
+ * k_mvfield) is compared for equality.
+ *
+ *   Grid     W4 = (w + 3) >> 2, H4 = (h + 3) >> 2; cell (cx, cy) is luma [4cx, 4cx + 4) x [4cy, 4cy + 4).  The field is of the DECODED
+ *            picture at its coded size: no conformance window, no output scale, no film grain applies to it.
+ *   Sources  five unit lists, read in the recorder's order:
+ *              mc    ovhip_mc_unit        without the units that carry OVHIP_MC_NO_LUMA
+ *              mcx   ovhip_mc_unit        all
+ *              aff   ovhip_aff_unit       all, with the side arena
+ *              rpr   ovhip_rpr_unit       without the units that carry OVHIP_RPR_NO_LUMA
+ *              affr  ovhip_aff_rpr_unit   all, with the same side arena
+ *            A unit covers the cells x/4 .. (x + w)/4 - 1 by y/4 .. (y + h)/4 - 1, clipped to the grid.  Units that carry luma never
+ *            overlap: the recorder's property, which the kernel does not check (the host twin does).  A cell no unit covers is EMPTY:
+ *            intra, IBC, the intra part of CIIP, or nothing.
+ *   Info     one little-endian uint32 per cell, info[cy][cx] = ref0 | ref1 << 8 | kind << 16 | scaled << 24.
+ *            ref0, ref1: the unit's slot in the picture's reference table (the k of ovhip_frame_ref / ovhip_frame_ref_at; mc, mcx, aff:
+ *            the unit's ref0 / ref1; rpr and affr: s[l].ref), 0xFF where the unit's dir does not use the list and in empty cells (a uni
+ *            unit's unused ref field holds 0, not a marker: the rule comes from dir).
+ *            kind: 1 INTER; 2 AFFINE (aff, affr); 4 GPM (OVHIP_MC_GPM of mc and mcx, OVHIP_RPR_GPM); 8 DMVR and 16 BDOF (the flags of
+ *            an mcx unit); 32 BCW (dir == 3, not GPM, w0 != 4 || w1 != 4; every list); 64 PROF (OVHIP_AFF_PROF, OVHIP_AFFR_PROF); bit 7
+ *            is zero.
+ *            scaled: bit l is set when list l is used and reads a reference of another size (OVHIP_RPR_S0 / S1, OVHIP_AFFR_S0 / S1).
+ *            Such a list carries anchors, not vectors: its vector is exported as 0.
+ *            An empty cell is 0x0000FFFF.
+ *   Vectors  four channels per cell, mv0x, mv0y, mv1x, mv1y, in 1/16 luma sample: the vectors the prediction read with.
+ *              mc    mv0x, mv0y, mv1x, mv1y as stored (after clip_mv)
+ *              mcx   the same; with vectors == OVHIP_MVF_REFINED and OVHIP_MC_DMVR set, the unit's four words of the refined array
+ *                    (mv_out of ovhip_mcx_launch, 4 int32 per mcx unit) instead; units without the DMVR flag never read that array
+ *              aff, affr   the cell is one sub-block: k = (cy - y/4) * (w/4) + (cx - x/4), the words side[side_off + 4k .. + 3]; for
+ *                    affr only the words of an unscaled list.  ident_l, ident_c and PROF's per-sample refinement change nothing here
+ *              rpr   an unscaled list gives s[l].pos_x, s[l].pos_y
+ *            An unused list gives 0 (whatever the unit's fields or side words hold).  A vector v leaves as
+ *              OVHIP_MVF_I32   v
+ *              OVHIP_MVF_F32   (float)v * 0.0625f, in luma samples (exact: |v| < 2^24)
+ *              OVHIP_MVF_F16   that float rounded to nearest even (the conversion of the RGB output's F16)
+ *   Layout   both tight: OVHIP_MVF_PLANAR [4][H4][W4], OVHIP_MVF_CELLS [H4][W4][4].
+ *   Sizes    ovhip_mvfield_bytes: 4 * W4 * H4 * elem for the vectors and 4 * W4 * H4 for the info.  Either destination may be NULL (not
+ *            wanted); both NULL is an error.
+ * Refused (OVHIP_EINVAL) before anything is launched or written, the reason in the context's error text: a null context or format;
+ * both destinations NULL; non-positive sizes or sizes above 16384; an unknown dtype, layout or vectors value; non-zero rsv; a
+ * destination that is not element-aligned; a byte count below the size ("too small", with both numbers); destinations that overlap
+ * each other; a non-zero count with a NULL array; OVHIP_MVF_REFINED with mcx units and no refined array; and, from the host twin
+ * only: a unit that is not 4-aligned, or a cell that is covered twice.  Not done: intra modes and IBC block vectors; grids coarser
+ * than 4x4 (a consumer strides the tensor); vectors of scaled lists; POC distances (the caller owns the slot table); a window; an
+ * event hand-off instead of completion at return; a shim entry point.
+ * ---------------------------------------------------------------------------------- */
+enum { OVHIP_MVF_I32 = 0, OVHIP_MVF_F32 = 1, OVHIP_MVF_F16 = 2 };                                 /* ovhip_mvfield_format.dtype */
+enum { OVHIP_MVF_PLANAR = 0, OVHIP_MVF_CELLS = 1 };                                               /* ovhip_mvfield_format.layout */
+enum { OVHIP_MVF_UNIT = 0, OVHIP_MVF_REFINED = 1 };                                               /* ovhip_mvfield_format.vectors */
+enum { OVHIP_MVF_INTER = 1, OVHIP_MVF_AFFINE = 2, OVHIP_MVF_GPM = 4, OVHIP_MVF_DMVR = 8, OVHIP_MVF_BDOF = 16, OVHIP_MVF_BCW = 32, OVHIP_MVF_PROF = 64 };   /* kind */
+#define OVHIP_MVF_EMPTY 0x0000FFFFu
+typedef struct ovhip_mvfield_format {
+    uint8_t dtype, layout, vectors, rsv;  /* rsv must be 0 */
+} ovhip_mvfield_format;
+/* The five lists with their counts, the side arena of aff and affr, and the refined array of mcx (NULL unless vectors ==
+ * OVHIP_MVF_REFINED and n_mcx != 0).  HOST pointers for ovhip_mvfield_host, DEVICE pointers for ovhip_mvfield_launch. */
+typedef struct ovhip_mvfield_src {
+    const ovhip_mc_unit *mc, *mcx;
+    const ovhip_aff_unit *aff;
+    const ovhip_rpr_unit *rpr;
+    const ovhip_aff_rpr_unit *affr;
+    const int32_t *side;                  /* ovhip_rec_aff_side() */
+    const int32_t *refined;               /* 4 int32 per mcx unit */
+    uint32_t n_mc, n_mcx, n_aff, n_rpr, n_affr;
+} ovhip_mvfield_src;
+/* Bytes of the vectors of a w x h picture; *info_bytes (may be NULL): of the info.  0 (and *info_bytes = 0) for a size or a format
+ * the launch would refuse.  Host only. */
+size_t ovhip_mvfield_bytes(int32_t w, int32_t h, const ovhip_mvfield_format *fmt, size_t *info_bytes);
+/* The definition over lists in host memory into host memory.  Refusals as the launch's and the two of its own; nothing is written
+ * when it refuses. */
+int  ovhip_mvfield_host(int32_t w, int32_t h, const ovhip_mvfield_src *src, const ovhip_mvfield_format *fmt,
+                        void *vec, size_t vec_bytes, uint32_t *info, size_t info_bytes);
+/* d_vec, d_info: DEVICE.  Two steps in order on the ctx stream: a clear that writes the empty cell into every byte of the wanted
+ * destinations (16-byte stores where the address allows), then k_mvfield, one launch over all five lists (a lane owns one row of a
+ * unit's cells; 16-byte stores where the address allows, narrower ones otherwise).  Asynchronous; allocates nothing. */
+int  ovhip_mvfield_launch(ovhip_ctx *ctx, int32_t w, int32_t h, const ovhip_mvfield_src *d_src, const ovhip_mvfield_format *fmt,
+                          void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes);
+/* The motion field of the picture the job decoded last: valid after ovhip_job_wait of a whole-picture flush (ovhip_job_flush, a
+ * resident replay included), on the job's context.  Reads the device copies that flush placed -- the refined vectors where its
+ * k_mcxa left them -- and uploads nothing; asynchronous on the context's stream.  OVHIP_EUNSUP after a band-wise submission (the
+ * arrays live in band arenas), OVHIP_EINVAL before any flush or after ovhip_job_begin; OVHIP_MVF_REFINED needs a flush that ran
+ * the prediction stage. */
+int  ovhip_job_mvfield(ovhip_job *job, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes);
+
+/* ------------------------------------------------------------------------------------
  * Output resampling: a stream that changes its coded size (RPR) can leave the device at ONE size.  Replaces pp_sample_rate_conv
  * (pp_pic_scale.c:250-377), called once per plane by pp_process_frame (post_proc.c:116-126) when the decoder's `upscale` option is
  * on (ovdec.c:562; ovdec.c:479 / :523 are the call sites), for up-sampling and equal size, bit-exactly -- including its phase, which
@@ -1749,6 +1837,16 @@ int  ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, con
  * independent: a frame with both set writes both.  Each of RGB output, surface output and delivery makes its own post-process step
  * (into the same scratch picture): with two of them the step runs twice, with all three three times. */
 int  ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
+/* Motion field output ("Motion field output on the device" above) of the NEXT picture completed: per picture, fmt NULL switches it
+ * off (the default); either destination may be NULL.  ovhip_job_mvfield runs in ovhip_frame_submit after a successful
+ * ovhip_job_wait and after the picture's publication, on the job that decoded it -- a borrowed job goes back to its home context
+ * only after it -- and is complete on the device when the call returns.  ref0 / ref1 of a cell are the k of ovhip_frame_ref /
+ * ovhip_frame_ref_at.  The refusals that need no picture (format, both destinations NULL, alignment, overlap) come back here, the
+ * sizes' from the picture's submit: a failed field fails that call's return value, never the picture's publication.  The setting
+ * ends with the picture whatever happens, and a failed picture leaves the destinations untouched.  A dry frame accepts the call and
+ * does nothing; a frame in band mode returns OVHIP_EUNSUP (and a setting made before band mode was switched on ends, unwritten, with
+ * the band-wise picture). */
+int  ovhip_frame_set_mvfield_output(ovhip_frame *f, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes);
 int  ovhip_frame_fail(ovhip_frame *f, int status);
 const char *ovhip_frame_last_error(const ovhip_frame *f);
 
@@ -1903,6 +2001,14 @@ int  ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, c
  * format the frame's setter refuses, or a bytes_per_picture below ovhip_surface_bytes() for the size the stream outputs (its output
  * scale's, else its pictures').  A slot is the caller's to reuse once the picture n_slots later is decoded. */
 int  ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
+/* Motion field output for the following runs: the vectors of picture idx land at d_vec_base + (idx % n_slots) *
+ * vec_bytes_per_picture, its info at d_info_base + (idx % n_slots) * info_bytes_per_picture, in DEVICE memory, written by the frame
+ * thread that completes it (ovhip_frame_set_mvfield_output).  Either base may be NULL (not wanted).  fmt NULL: off.  OVHIP_EINVAL
+ * for both bases NULL, n_slots 0, a format the frame's setter refuses, or a wanted destination whose bytes per picture are below
+ * ovhip_mvfield_bytes() for the stream's picture size or no multiple of its element.  A slot is the caller's to reuse once the
+ * picture n_slots later is decoded. */
+int  ovhip_stream_set_mvfield_output(ovhip_stream *s, const ovhip_mvfield_format *fmt, void *d_vec_base, size_t vec_bytes_per_picture,
+                                     void *d_info_base, size_t info_bytes_per_picture, uint32_t n_slots);
 /* The DPB key of picture idx of the current stream (valid while the run that decoded it kept it: OVHIP_STREAM_KEEP). */
 const void *ovhip_stream_key(const ovhip_stream *s, uint32_t idx);
 /* test hook: the next flush of `job` that has a flow launch is ABORTED for real (the device's abort word is set before the

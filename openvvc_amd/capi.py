@@ -509,6 +509,25 @@ class SurfaceFormat(C.Structure):
                 ("offset_c", C.c_uint64 * 2)]
 
 
+MVF_I32, MVF_F32, MVF_F16 = 0, 1, 2                 # ovhip_mvfield_format.dtype
+MVF_PLANAR, MVF_CELLS = 0, 1                         # ovhip_mvfield_format.layout: [4][H4][W4] / [H4][W4][4]
+MVF_UNIT, MVF_REFINED = 0, 1                         # ovhip_mvfield_format.vectors
+MVF_INTER, MVF_AFFINE, MVF_GPM, MVF_DMVR, MVF_BDOF, MVF_BCW, MVF_PROF = 1, 2, 4, 8, 16, 32, 64       # kind bits of an info word
+MVF_EMPTY = 0x0000FFFF
+MVF_NP_DTYPE = {MVF_I32: "int32", MVF_F32: "float32", MVF_F16: "float16"}
+
+
+class MvfieldFormat(C.Structure):
+    """ovhip_mvfield_format: element type and layout of the vectors, and whether DMVR units export their refined vectors"""
+    _fields_ = [("dtype", C.c_uint8), ("layout", C.c_uint8), ("vectors", C.c_uint8), ("rsv", C.c_uint8)]
+
+
+class MvfieldSrc(C.Structure):
+    """ovhip_mvfield_src: the five unit lists, the side arena, the refined array (host or device addresses), the lists' counts"""
+    _fields_ = [("mc", C.c_void_p), ("mcx", C.c_void_p), ("aff", C.c_void_p), ("rpr", C.c_void_p), ("affr", C.c_void_p), ("side", C.c_void_p),
+                ("refined", C.c_void_p), ("n_mc", C.c_uint32), ("n_mcx", C.c_uint32), ("n_aff", C.c_uint32), ("n_rpr", C.c_uint32), ("n_affr", C.c_uint32)]
+
+
 class Md5State(C.Structure):
     _fields_ = [("h", C.c_uint32 * 4), ("n_bytes", C.c_uint64), ("buf", C.c_uint8 * 64)]
 
@@ -779,6 +798,12 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_surface": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
         "ovhip_frame_set_surface_output": (C.c_int, [vp, P(SurfaceFormat), P(Window), vp, C.c_size_t]),
         "ovhip_stream_set_surface_output": (C.c_int, [vp, P(SurfaceFormat), P(Window), vp, C.c_size_t, u32]),
+        "ovhip_mvfield_bytes": (C.c_size_t, [i32, i32, P(MvfieldFormat), P(C.c_size_t)]),
+        "ovhip_mvfield_host": (C.c_int, [i32, i32, P(MvfieldSrc), P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t]),
+        "ovhip_mvfield_launch": (C.c_int, [vp, i32, i32, P(MvfieldSrc), P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t]),
+        "ovhip_job_mvfield": (C.c_int, [vp, P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t]),
+        "ovhip_frame_set_mvfield_output": (C.c_int, [vp, P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t]),
+        "ovhip_stream_set_mvfield_output": (C.c_int, [vp, P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t, u32]),
     }
     ab_build = "OVVC_HIP_LIB_NAME" in os.environ       # tools/ab_lib.sh: an OLDER build of the library beside the current one (its newer entry points are not called)
     for name, (res, args) in sigs.items():
@@ -826,6 +851,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_frame_set_picture_hash", "ovhip_frame_picture_hash", "ovhip_stream_set_picture_hashes", "ovhip_stream_picture_hashes",
     "ovhip_rgb_bytes", "ovhip_rgb_coefs", "ovhip_rgb_host", "ovhip_rgb_launch", "ovhip_pic_output_rgb", "ovhip_frame_set_rgb_output", "ovhip_stream_set_rgb_output",
     "ovhip_surface_bytes", "ovhip_surface_host", "ovhip_surface_launch", "ovhip_pic_output_surface", "ovhip_frame_set_surface_output", "ovhip_stream_set_surface_output",
+    "ovhip_mvfield_bytes", "ovhip_mvfield_host", "ovhip_mvfield_launch", "ovhip_job_mvfield", "ovhip_frame_set_mvfield_output", "ovhip_stream_set_mvfield_output",
 ]
 
 

@@ -67,6 +67,9 @@ OVHIP_HIDDEN_ int ovhip_surface_plan_make_(const ovhip_pic *pic, const ovhip_win
 /* ovhip_post_pic_, ovhip_surface_launch of the picture it shows, and the wait for both: complete on the device at return (the frame thread) */
 int  ovhip_surface_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_surface_format *fmt,
                          void *d_dst, size_t dst_bytes);
+/* ---- Motion field output (ovvc_mvfield.c, kernels_mvfield.hip; what they share: ovvc_mvfield_priv.h).  ovhip_job_mvfield and the
+ * wait for it: complete on the device at return (the frame thread; ovvc_picture.hip) */
+int  ovhip_job_mvfield_done_(ovhip_job *job, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@
 #include <time.h>
 #include "ovvc_hip.h"
 #include "ovvc_dpb_priv.h"
+#include "ovvc_mvfield_priv.h"
 
 #define MAX_REFS 16
 
@@ -58,6 +59,9 @@ struct ovhip_frame {
     /* surface output (ovhip_frame_set_surface_output), the same way and independent of it */
     int surf_on;
     ovhip_surface_format surf_fmt; ovhip_window surf_win; void *surf_dst; size_t surf_bytes;
+    /* motion field output (ovhip_frame_set_mvfield_output), per picture likewise: written from the arrays of the job that decoded it */
+    int mvf_on;
+    ovhip_mvfield_format mvf_fmt; void *mvf_vec, *mvf_info; size_t mvf_vec_bytes, mvf_info_bytes;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -376,7 +380,7 @@ ovhip_frame_fail(ovhip_frame *f, int status)
 {
     if (!f) return OVHIP_EINVAL;
     if (!f->status) f->status = status ? status : OVHIP_EINVAL;
-    f->rgb_on = 0; f->surf_on = 0;        /* (the picture that ends here takes its RGB and surface destinations with it) */
+    f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0;     /* (the picture that ends here takes its RGB, surface and motion field destinations with it) */
     trace(f, OVHIP_FE_FAIL, f->key, 0, f->status, 0, 0);
     return publish(f, f->status);
 }
@@ -530,6 +534,29 @@ frame_surface(ovhip_frame *f)
 }
 
 int
+ovhip_frame_set_mvfield_output(ovhip_frame *f, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!fmt) { f->mvf_on = 0; return OVHIP_OK; }
+    const int r = ovhip_mvfield_dst_check_(fmt, d_vec, vec_bytes, d_info, info_bytes, NULL);   /* the refusals that need no picture come back here */
+    if (r != OVHIP_OK) return r;
+    if (f->dry) return OVHIP_OK;                               /* (a dry frame has no motion to export) */
+    if (f->band_mode) return OVHIP_EUNSUP;                     /* (a band-wise picture's arrays live in band arenas: ovhip_job_mvfield) */
+    f->mvf_on = 1; f->mvf_fmt = *fmt; f->mvf_vec = d_vec; f->mvf_vec_bytes = vec_bytes; f->mvf_info = d_info; f->mvf_info_bytes = info_bytes;
+    return OVHIP_OK;
+}
+
+/* the motion field of a complete picture, from the arrays of the job `j` that decoded it (still bound to this frame's context):
+ * complete on the device at return, and the setting ends here whatever happens */
+static int
+frame_mvfield(ovhip_frame *f, ovhip_job *j)
+{
+    if (!f->mvf_on) return OVHIP_OK;
+    f->mvf_on = 0;
+    return ovhip_job_mvfield_done_(j, &f->mvf_fmt, f->mvf_vec, f->mvf_vec_bytes, f->mvf_info, f->mvf_info_bytes);
+}
+
+int
 ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const ovhip_job_params *params, ovhip_frame_output *out)
 {
     if (!f || !params || !f->live) return OVHIP_EINVAL;
@@ -564,8 +591,10 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
         f->done_at = mono_s();
         if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_wait");
     }
-    /* a borrowed job goes back to its own context: this frame (and its context) may be destroyed before the job */
-    if (job) { int q = ovhip_job_bind(job, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
+    /* a borrowed job goes back to its own context: this frame (and its context) may be destroyed before the job -- behind the motion
+     * field step where one is set, which reads that job's arrays on this frame's stream */
+    const int keep_job = job && f->mvf_on && r == OVHIP_OK;
+    if (job && !keep_job) { int q = ovhip_job_bind(job, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
     if (f->status) r = f->status;         /* the first error, e.g. a failed reference rather than "callback failed" */
     /* the picture is complete: its readers go on while this thread copies it out (the output only reads; whoever keeps the key
      * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns) */
@@ -573,7 +602,9 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
     if (r == OVHIP_OK && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
     if (r == OVHIP_OK && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
     if (r == OVHIP_OK && (r = frame_surface(f)) != OVHIP_OK) fail(f, r, "surface output");
-    f->rgb_on = 0; f->surf_on = 0;        /* (a picture that failed takes its destinations with it) */
+    if (r == OVHIP_OK && (r = frame_mvfield(f, j)) != OVHIP_OK) fail(f, r, "motion field output");
+    f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0;      /* (a picture that failed takes its destinations with it) */
+    if (keep_job) { int q = ovhip_job_bind(job, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
     if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
         const double to0 = PT_ON() ? mono_s() : 0.0;
         r = frame_output(f, out);
@@ -695,7 +726,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     if (r != OVHIP_OK) {
         /* a latched error: nothing more goes to the device; the last call publishes the picture as failed */
         trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, r);
-        if (last) { (void)publish(f, r); f->rgb_on = 0; f->surf_on = 0; }
+        if (last) { (void)publish(f, r); f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0; }
         return r;
     }
     if (last) row_end = f->h;
@@ -754,7 +785,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     if (r == OVHIP_OK && !f->dry && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
     if (r == OVHIP_OK && !f->dry && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
     if (r == OVHIP_OK && !f->dry && (r = frame_surface(f)) != OVHIP_OK) fail(f, r, "surface output");
-    f->rgb_on = 0; f->surf_on = 0;
+    f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0;
     if (r == OVHIP_OK && !f->dry && out && out->mode != OVHIP_OUT_NONE) {
         PT0();
         r = frame_output(f, out);

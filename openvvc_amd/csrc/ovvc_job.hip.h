@@ -40,6 +40,10 @@ struct ovhip_job {
     int flushed;                         // ev_* recorded at least once
     const void *packed_prev[24];         // where the last full flush placed the arrays that rode in the parameter block
     int resident;                        // this flush reuses the device copies of the previous one (OVHIP_STAGE_RESIDENT)
+    // ovhip_job_mvfield: where the last whole-picture flush placed the five unit lists and the side arena, their counts, and where its
+    // k_mcxa left the refined vectors (device memory, or the page-locked array the device reads as well; nullptr: the prediction stage
+    // did not run).  valid from a successful flush to the next ovhip_job_begin
+    struct { int valid; ovhip_mvfield_src src; } mvf;
     ovhip_job_stats st;
     struct BandState *bs;                // band-wise submission (ovhip_job_band): allocated with the first band of the job's life
     // optional: HIP-event bracket around ONE launch group of the flush (ovhip_job_time_stage)

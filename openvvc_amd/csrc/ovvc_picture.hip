@@ -730,6 +730,7 @@ int launch_predict(ovhip_job *j, const Chain &c, const ovhip_pic *refs, uint32_t
     const bool mv_direct = n_mcx && !pr->tmvp_cells && !j->resident;
     ovhip_pic same[16];
     CHK(chain_predict(c, same_size_refs(c.dst, refs, n_refs, same), refs, n_refs, intra, mv_direct ? j->mv_host : (int32_t *)p.at[B_MV]));
+    j->mvf.src.refined = n_mcx ? (mv_direct ? j->mv_host : (const int32_t *)p.at[B_MV]) : nullptr;
     if (mv_direct) j->st.d2h_bytes += n_mcx * 16;
     else if (n_mcx && !j->resident) {
         // refined vectors back to the host as early as the stream allows (the decoder's TMVP field needs them), stored by a kernel
@@ -763,6 +764,7 @@ int flush_launch(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *refs, uint
     chain_bind(c, p, ovhip_band_counts{}, g.n, (uint32_t)g.n_rpr, (uint32_t)g.n_affr);
     memcpy(c.cls, g.cls, sizeof(c.cls)); memcpy(c.tiny, g.tiny, sizeof(c.tiny));
     c.h_it = g.it; c.lv_start = g.lv_start; c.n_lv = g.n_lv; c.n_items = g.flow ? (uint32_t)g.n_items : 0; c.ibc = g.ibc;
+    j->mvf.src = ovhip_mvfield_src{ c.d_mc, c.d_mcx, c.d_aff, c.d_rpr, c.d_affr, c.d_side, nullptr, c.n_mc, c.n_mcx, c.n_aff, c.n_rpr, c.n_affr };
 
     if (stages & OVHIP_STAGE_MC) CHK(launch_predict(j, c, refs, n_refs, intra, pr, g, p));
     // ---- the flow launch's state (before the residual stage: the chroma-scale launch prepares the state words as a rider) ----
@@ -894,6 +896,7 @@ int ovhip_job_begin(ovhip_job *j)
     { const int rb = band_reset(j); if (rb != OVHIP_OK) return rb; }
     ovhip_rec_reset(j->rec);
     j->dmvr_first = 0; j->n_mv = 0; j->n_tmvp = 0; j->rows_end = 0;
+    j->mvf.valid = 0;
     return OVHIP_OK;
 }
 
@@ -1080,7 +1083,9 @@ int ovhip_job_flush(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *refs, u
     // until ovhip_job_wait has returned)
     j->again.valid = 0;
     j->n_retries = 0;
+    j->mvf.valid = 0;
     const int r = job_flush_impl(j, dst, refs, n_refs, intra, pr);
+    j->mvf.valid = r == OVHIP_OK;
     // (after the flush: a before_launch callback may be what fills refs[] -- ovhip_frame_submit resolves the reference pictures
     // there, while the uploads already run)
     j->again.valid = r == OVHIP_OK && n_refs <= 16;
@@ -1090,6 +1095,22 @@ int ovhip_job_flush(ovhip_job *j, const ovhip_pic *dst, const ovhip_pic *refs, u
     j->again.has_intra = intra != nullptr;
     if (intra) j->again.intra = *intra;
     j->again.pr = *pr;
+    return r;
+}
+
+int ovhip_job_mvfield(ovhip_job *j, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes)
+{
+    if (!j) return OVHIP_EINVAL;
+    if (band_active(j)) return ov_fail(j->ctx, OVHIP_EUNSUP, "ovhip_job_mvfield: the picture was submitted band-wise (its arrays live in band arenas)", hipSuccess);
+    if (!j->mvf.valid) return ov_fail(j->ctx, OVHIP_EINVAL, "ovhip_job_mvfield: no whole-picture flush since ovhip_job_begin", hipSuccess);
+    return ovhip_mvfield_launch(j->ctx, j->w, j->h, &j->mvf.src, fmt, d_vec, vec_bytes, d_info, info_bytes);
+}
+
+/* ovhip_job_mvfield and the wait for it: complete on the device at return (the frame thread) */
+int ovhip_job_mvfield_done_(ovhip_job *j, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes)
+{
+    int r = ovhip_job_mvfield(j, fmt, d_vec, vec_bytes, d_info, info_bytes);
+    if (r == OVHIP_OK && ov_sync_stream(j->ctx) != hipSuccess) r = ov_fail(j->ctx, OVHIP_ELAUNCH, "motion field output", hipGetLastError());
     return r;
 }
 

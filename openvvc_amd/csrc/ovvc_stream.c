@@ -22,6 +22,7 @@
 #include <time.h>
 #include "ovvc_hip.h"
 #include "ovvc_dpb_priv.h"
+#include "ovvc_mvfield_priv.h"
 
 #define STAGE_ALL (OVHIP_STAGE_MC | OVHIP_STAGE_ITX | OVHIP_STAGE_DBF | OVHIP_STAGE_SAO | OVHIP_STAGE_ALF | OVHIP_STAGE_INTRA)
 
@@ -60,6 +61,9 @@ struct ovhip_stream {
     /* surface output (ovhip_stream_set_surface_output): the same way, in a buffer of its own */
     int surf_on;
     ovhip_surface_format surf_fmt; ovhip_window surf_win; char *surf_base; size_t surf_bpp; uint32_t surf_slots;
+    /* motion field output (ovhip_stream_set_mvfield_output): vectors and info in buffers of their own, either may be NULL */
+    int mvf_on;
+    ovhip_mvfield_format mvf_fmt; char *mvf_vec, *mvf_info; size_t mvf_vec_bpp, mvf_info_bpp; uint32_t mvf_slots;
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -238,6 +242,11 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         /* (validated by the stream's setter; the conversion is this frame thread's, after its wait: nothing goes through the output thread) */
         if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, s->rgb_base + (size_t)(idx % s->rgb_slots) * s->rgb_bpp, s->rgb_bpp);
         if (s->surf_on) (void)ovhip_frame_set_surface_output(f, &s->surf_fmt, &s->surf_win, s->surf_base + (size_t)(idx % s->surf_slots) * s->surf_bpp, s->surf_bpp);
+        if (s->mvf_on) {
+            const size_t slot = idx % s->mvf_slots;
+            (void)ovhip_frame_set_mvfield_output(f, &s->mvf_fmt, s->mvf_vec ? s->mvf_vec + slot * s->mvf_vec_bpp : NULL, s->mvf_vec_bpp,
+                                                 s->mvf_info ? s->mvf_info + slot * s->mvf_info_bpp : NULL, s->mvf_info_bpp);
+        }
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
@@ -590,6 +599,27 @@ ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt
     s->surf_on = 1; s->surf_fmt = *fmt; s->surf_base = (char *)d_base; s->surf_bpp = bytes_per_picture; s->surf_slots = n_slots;
     memset(&s->surf_win, 0, sizeof(s->surf_win));
     if (win) s->surf_win = *win;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_mvfield_output(ovhip_stream *s, const ovhip_mvfield_format *fmt, void *d_vec_base, size_t vec_bytes_per_picture,
+                                void *d_info_base, size_t info_bytes_per_picture, uint32_t n_slots)
+{
+    if (!s) return OVHIP_EINVAL;
+    if (!fmt) { s->mvf_on = 0; return OVHIP_OK; }
+    if (!n_slots) return OVHIP_EINVAL;
+    /* every slot's pair of destinations as the frame's setter sees it: slot 0's, with the whole buffers' extents for the overlap */
+    const int r = ovhip_mvfield_dst_check_(fmt, d_vec_base, vec_bytes_per_picture * n_slots, d_info_base, info_bytes_per_picture * n_slots, NULL);
+    if (r != OVHIP_OK) return r;
+    size_t need_info = 0;
+    const size_t need_vec = ovhip_mvfield_bytes(s->cfg.w, s->cfg.h, fmt, &need_info);
+    if (!need_vec) return OVHIP_EINVAL;
+    const size_t es = fmt->dtype == OVHIP_MVF_F16 ? 2 : 4;
+    if (d_vec_base && (vec_bytes_per_picture < need_vec || vec_bytes_per_picture % es)) return OVHIP_EINVAL;
+    if (d_info_base && (info_bytes_per_picture < need_info || info_bytes_per_picture % 4)) return OVHIP_EINVAL;
+    s->mvf_on = 1; s->mvf_fmt = *fmt; s->mvf_slots = n_slots;
+    s->mvf_vec = (char *)d_vec_base; s->mvf_vec_bpp = vec_bytes_per_picture; s->mvf_info = (char *)d_info_base; s->mvf_info_bpp = info_bytes_per_picture;
     return OVHIP_OK;
 }
 

@@ -73,6 +73,59 @@ def _surface_tensor(tensor, fmt: capi.SurfaceFormat, need: int, slots: bool = Fa
     return tensor.data_ptr(), per, n
 
 
+def mvfield_format(dtype: int = capi.MVF_I32, layout: int = capi.MVF_PLANAR, vectors: int = capi.MVF_UNIT) -> capi.MvfieldFormat:
+    """an ovhip_mvfield_format (include/ovvc_hip.h, "Motion field output on the device")"""
+    return capi.MvfieldFormat(dtype, layout, vectors, 0)
+
+
+def mvfield_shape(fmt: capi.MvfieldFormat, w: int, h: int) -> "tuple[tuple, tuple]":
+    """(shape of the vectors, shape of the info) of a w x h picture's motion field: (4, H4, W4) or (H4, W4, 4), and (H4, W4)"""
+    w4, h4 = (w + 3) >> 2, (h + 3) >> 2
+    return ((h4, w4, 4) if fmt.layout == capi.MVF_CELLS else (4, h4, w4)), (h4, w4)
+
+
+def _mvfield_tensor(tensor, dtypes: tuple, shape: tuple, what: str, slots: bool = False) -> "tuple[int, int, int]":
+    """(data_ptr, bytes of one slot, slots) of a torch tensor on the device that is to take `what` of a motion field -- one of `shape`, or
+    with `slots` one per index of its first dimension -- after checking device, dtype, contiguity and shape"""
+    import torch
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise EngineError(f"motion field output: the {what} must go to a torch tensor on the device")
+    if tensor.dtype not in dtypes:
+        raise EngineError(f"motion field output: {what} tensor of dtype {tensor.dtype}, the format takes {dtypes}")
+    if not tensor.is_contiguous():
+        raise EngineError(f"motion field output: the {what} tensor must be contiguous")
+    got = tuple(tensor.shape[1:]) if slots else tuple(tensor.shape)
+    if got != tuple(shape) or (slots and tensor.ndim != len(shape) + 1):
+        raise EngineError(f"motion field output: {what} tensor of shape {tuple(tensor.shape)}, the field is {'[slots] + ' if slots else ''}{tuple(shape)}")
+    n = int(tensor.shape[0]) if slots else 1
+    per = tensor.element_size()
+    for d in shape:
+        per *= d
+    return tensor.data_ptr(), per, n
+
+
+def _mvfield_dsts(vec, info, fmt: capi.MvfieldFormat, w: int, h: int, vec_bytes, info_bytes, slots: bool = False):
+    """(vec ptr, vec bytes, info ptr, info bytes, slots) of a pair of destinations, each a torch tensor (checked against the field's
+    shape), a device address with its byte count, or None"""
+    vshape, ishape = mvfield_shape(fmt, w, h)
+    n = None
+    if vec is None or isinstance(vec, int):
+        vp, vb = vec or 0, vec_bytes or 0
+    else:
+        import torch
+        tdt = {capi.MVF_I32: (torch.int32,), capi.MVF_F32: (torch.float32,), capi.MVF_F16: (torch.float16,)}.get(fmt.dtype, ())
+        vp, vb, n = _mvfield_tensor(vec, tdt, vshape, "vectors", slots)
+    if info is None or isinstance(info, int):
+        ip, ib = info or 0, info_bytes or 0
+    else:
+        import torch
+        ip, ib, ni = _mvfield_tensor(info, (torch.int32, torch.uint32), ishape, "info", slots)
+        if n is not None and ni != n:
+            raise EngineError(f"motion field output: {n} slots of vectors, {ni} of info")
+        n = ni
+    return vp, vb, ip, ib, n
+
+
 class Context:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
@@ -295,6 +348,25 @@ class Context:
         self._chk(self.lib.ovhip_mcxa_launch(self.h, C.byref(dst.s), arr, len(refs), xunits.ptr, xunits.count,
                                              mv_out.ptr if mv_out else None, aunits.ptr, aunits.count, side.ptr,
                                              lmcs_fwd.ptr if lmcs_fwd else None), "mcxa_launch")
+
+    def mvfield(self, w: int, h: int, fmt: "capi.MvfieldFormat | None", vec=None, info=None, mc: "DevBuf | None" = None, mcx: "DevBuf | None" = None,
+                aff: "DevBuf | None" = None, rpr: "DevBuf | None" = None, affr: "DevBuf | None" = None, side: "DevBuf | None" = None,
+                refined: "DevBuf | None" = None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None, check: bool = True) -> int:
+        """ovhip_mvfield_launch: the motion field of a w x h picture from unit lists the caller uploaded (DevBufs whose count is the
+        number of units) into `vec` and `info` -- torch tensors on the device of mvfield_shape(), device addresses with their byte
+        counts, or None for a destination that is not wanted.  Asynchronous."""
+        vp, vb, ip, ib, _n = _mvfield_dsts(vec, info, fmt, w, h, vec_bytes, info_bytes) if fmt is not None else (vec or 0, vec_bytes or 0, info or 0, info_bytes or 0, None)
+        src = capi.MvfieldSrc()
+        for name, b in (("mc", mc), ("mcx", mcx), ("aff", aff), ("rpr", rpr), ("affr", affr)):
+            setattr(src, name, b.ptr if b is not None and b.count else None)
+            setattr(src, "n_" + name, b.count if b is not None else 0)
+        src.side = side.ptr if side is not None else None
+        src.refined = refined.ptr if refined is not None else None
+        r = self.lib.ovhip_mvfield_launch(self.h, w, h, C.byref(src), C.byref(fmt) if fmt is not None else None,
+                                          C.c_void_p(vp) if vp else None, vb, C.c_void_p(ip) if ip else None, ib)
+        if check:
+            self._chk(r, "mvfield_launch")
+        return r
 
     def mcx(self, dst: "DevPic", refs: list, units: "DevBuf", lmcs_fwd: "DevBuf | None" = None,
             mv_out: "DevBuf | None" = None, n: int | None = None):
@@ -766,6 +838,16 @@ class Job:
             return np.zeros((0, 4), np.int32)
         return np.frombuffer((C.c_int32 * (4 * n.value)).from_address(p), dtype=np.int32).reshape(-1, 4).copy()
 
+    def mvfield(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None,
+                check: bool = True) -> int:
+        """ovhip_job_mvfield after wait() of a whole-picture flush: the picture's motion field into `vec` and `info` (as
+        Context.mvfield takes them), from the device copies the flush placed.  Asynchronous on the job's context."""
+        vp, vb, ip, ib, _n = _mvfield_dsts(vec, info, fmt, self.w, self.h, vec_bytes, info_bytes) if fmt is not None else (vec or 0, vec_bytes or 0, info or 0, info_bytes or 0, None)
+        r = self.lib.ovhip_job_mvfield(self.j, C.byref(fmt) if fmt is not None else None, C.c_void_p(vp) if vp else None, vb, C.c_void_p(ip) if ip else None, ib)
+        if check:
+            self.ctx._chk(r, "job_mvfield")
+        return r
+
     def tmvp_cells(self) -> np.ndarray:
         """ovhip_job_tmvp_cells after wait(): capi.TMVP_CELL_DTYPE, 4 entries per refined unit (cell == capi.TMVP_NONE: unused)"""
         n = C.c_size_t()
@@ -990,6 +1072,20 @@ class Frame:
             raise EngineError(f"frame_set_surface_output: {r}")
         return r
 
+    def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None,
+                           check: bool = True) -> int:
+        """ovhip_frame_set_mvfield_output: the motion field of the NEXT picture completed goes to `vec` and `info` -- torch tensors on
+        the device of mvfield_shape() for the frame's size (checked here, kept alive here), device addresses with their byte counts,
+        or None for a destination that is not wanted; fmt None: off"""
+        if fmt is None:
+            return self.lib.ovhip_frame_set_mvfield_output(self.f, None, None, 0, None, 0)
+        vp, vb, ip, ib, _n = _mvfield_dsts(vec, info, fmt, self.w, self.h, vec_bytes, info_bytes)
+        self._mvfield_keep = (vec, info)
+        r = self.lib.ovhip_frame_set_mvfield_output(self.f, C.byref(fmt), C.c_void_p(vp) if vp else None, vb, C.c_void_p(ip) if ip else None, ib)
+        if check and r:
+            raise EngineError(f"frame_set_mvfield_output: {r}")
+        return r
+
     def job(self) -> "Job":
         """the frame's own job as an engine.Job view (not owned)"""
         j = Job.__new__(Job)
@@ -1094,6 +1190,21 @@ class Stream:
         r = self.lib.ovhip_stream_set_surface_output(self.s, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, bytes_per_picture or 0, n_slots or 0)
         if check and r:
             raise EngineError(f"stream_set_surface_output: {r}")
+        return r
+
+    def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes_per_picture: "int | None" = None,
+                           info_bytes_per_picture: "int | None" = None, n_slots: "int | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_mvfield_output: the motion field of picture idx of the following runs goes to slot idx % n of `vec` and
+        `info` -- torch tensors on the device whose first dimension is the slot count and whose slots have mvfield_shape() for the
+        stream's size (checked here, kept alive here), device addresses with bytes per picture and n_slots, or None; fmt None: off"""
+        if fmt is None:
+            return self.lib.ovhip_stream_set_mvfield_output(self.s, None, None, 0, None, 0, 0)
+        vp, vb, ip, ib, n = _mvfield_dsts(vec, info, fmt, self.cfg.w, self.cfg.h, vec_bytes_per_picture, info_bytes_per_picture, slots=True)
+        self._keep.append((vec, info))
+        r = self.lib.ovhip_stream_set_mvfield_output(self.s, C.byref(fmt), C.c_void_p(vp) if vp else None, vb, C.c_void_p(ip) if ip else None, ib,
+                                                     n if n is not None else (n_slots or 0))
+        if check and r:
+            raise EngineError(f"stream_set_mvfield_output: {r}")
         return r
 
     def set_picture_hashes(self, method: int, n_planes: int = 3, expected=None, check: bool = True) -> int:

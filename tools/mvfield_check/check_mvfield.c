@@ -1,0 +1,185 @@
+/* tools/mvfield_check -- the host half of the motion field output (openvvc_amd/csrc/ovvc_mvfield.c) as a stand-alone program:
+ * ovhip_mvfield_host over generated unit lists that tile pictures of several sizes (sizes that are no multiple of 4 or of 16 among them,
+ * so that units are clipped at the right and bottom edges) with units of all five lists, in every dtype, layout and vectors setting,
+ * each destination alone and both; every list, the side arena, the refined array and every destination in a heap block of exactly its
+ * size, so that a read or a write one element outside is the sanitizer's to see; a field is checked against what the tiling says
+ * (every cell covered once, the info word's kind and references); and the refusals, which must write nothing.
+ * `make asan`.  Host code only. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "ovvc_hip.h"
+
+static uint32_t rng = 2463534242u;
+static uint32_t next(void) { rng ^= rng << 13; rng ^= rng >> 17; rng ^= rng << 5; return rng; }
+static int32_t next_mv(void) { return (int32_t)(next() % (1u << 18)) - (1 << 17) + 1; }
+
+typedef struct lists {
+    ovhip_mc_unit *mc, *mcx; ovhip_aff_unit *aff; ovhip_rpr_unit *rpr; ovhip_aff_rpr_unit *affr;
+    int32_t *side, *refined;
+    uint32_t n[5], n_side;
+} lists;
+
+static void *exact(size_t n, size_t elem) { void *p = malloc(n ? n * elem : 1); if (!p) exit(2); memset(p, 0, n * elem); return p; }
+
+/* tiles of 16x16 (8x8 in every fifth tile's place: four units), the kind of each drawn from the tile's index; two passes: count, fill */
+static void
+make_lists(int w, int h, lists *L)
+{
+    memset(L, 0, sizeof(*L));
+    for (int pass = 0; pass < 2; ++pass) {
+        uint32_t n[5] = { 0, 0, 0, 0, 0 }, n_side = 0;
+        int t = 0;
+        for (int y = 0; y < h; y += 16)
+            for (int x = 0; x < w; x += 16, ++t) {
+                const int kind = t % 7, dir = 1 + t % 3;
+                if (kind == 6) continue;                       /* an empty tile */
+                if (kind == 0 || kind == 5) {                  /* mc: one 16x16 or four 8x8, the second chroma only beside a luma-only twin */
+                    const int parts = kind == 5 ? 4 : 1, s = kind == 5 ? 8 : 16;
+                    for (int q = 0; q < parts; ++q) {
+                        if (pass) {
+                            ovhip_mc_unit *u = &L->mc[n[0]];
+                            u->x = (uint16_t)(x + (q & 1) * s); u->y = (uint16_t)(y + (q >> 1) * s); u->w = u->h = (uint8_t)s;
+                            u->dir = (uint8_t)dir; u->ref0 = (uint8_t)(t % 5); u->ref1 = (uint8_t)(t % 3); u->w0 = (int8_t)(q == 1 ? 3 : 4); u->w1 = (int8_t)(q == 1 ? 5 : 4);
+                            u->flags = (uint8_t)(q == 2 ? OVHIP_MC_GPM : 0);
+                            u->mv0x = next_mv(); u->mv0y = next_mv(); u->mv1x = next_mv(); u->mv1y = next_mv();
+                        }
+                        n[0]++;
+                    }
+                    if (pass) { ovhip_mc_unit *u = &L->mc[n[0]]; *u = L->mc[n[0] - 1]; u->flags = OVHIP_MC_NO_LUMA; }
+                    n[0]++;
+                } else if (kind == 1) {
+                    if (pass) {
+                        ovhip_mc_unit *u = &L->mcx[n[1]];
+                        u->x = (uint16_t)x; u->y = (uint16_t)y; u->w = u->h = 16; u->dir = 3; u->w0 = u->w1 = 4; u->ref1 = 1;
+                        u->flags = (uint8_t)((t & 8) ? OVHIP_MC_DMVR | OVHIP_MC_BDOF : OVHIP_MC_BDOF);
+                        u->mv0x = next_mv(); u->mv0y = next_mv(); u->mv1x = -u->mv0x; u->mv1y = -u->mv0y;
+                        for (int c = 0; c < 4; ++c) L->refined[4 * n[1] + c] = next_mv();
+                    }
+                    n[1]++;
+                } else if (kind == 2 || kind == 4) {           /* affine: 16 sub-blocks of 4 words, behind a gap as another unit's chroma words leave */
+                    n_side += (t & 2) ? 16 : 0;
+                    if (pass) {
+                        if (kind == 2) {
+                            ovhip_aff_unit *u = &L->aff[n[2]];
+                            u->x = (uint16_t)x; u->y = (uint16_t)y; u->w = u->h = 16; u->dir = (uint8_t)dir; u->ref0 = 2; u->ref1 = 3; u->w0 = u->w1 = 4;
+                            u->flags = (uint8_t)((t & 1) ? OVHIP_AFF_PROF : 0); u->side_off = n_side;
+                        } else {
+                            ovhip_aff_rpr_unit *u = &L->affr[n[4]];
+                            u->x = (uint16_t)x; u->y = (uint16_t)y; u->w = u->h = 16; u->dir = (uint8_t)dir; u->w0 = u->w1 = 4;
+                            u->flags = (uint8_t)(1 + t % 3) | ((t & 4) ? OVHIP_AFFR_PROF : 0); u->side_off = n_side;
+                            u->s[0].ref = 6; u->s[1].ref = 7;
+                        }
+                        for (int c = 0; c < 64; ++c) L->side[n_side + c] = next_mv();
+                    }
+                    n[kind == 2 ? 2 : 4]++;
+                    n_side += 64;
+                } else {                                       /* kind 3: rpr */
+                    if (pass) {
+                        ovhip_rpr_unit *u = &L->rpr[n[3]];
+                        u->x = (uint16_t)x; u->y = (uint16_t)y; u->w = u->h = 16; u->dir = (uint8_t)dir; u->w0 = u->w1 = 4;
+                        u->flags = (uint8_t)(1 + t % 3);
+                        for (int l = 0; l < 2; ++l) { u->s[l].pos_x = next_mv(); u->s[l].pos_y = next_mv(); u->s[l].ref = (uint8_t)(8 + l); }
+                    }
+                    n[3]++;
+                }
+            }
+        if (!pass) {
+            /* (the side arena ends with its last unit's 64 words: a read behind them is outside the block) */
+            L->mc = exact(n[0], sizeof(*L->mc)); L->mcx = exact(n[1], sizeof(*L->mcx)); L->aff = exact(n[2], sizeof(*L->aff));
+            L->rpr = exact(n[3], sizeof(*L->rpr)); L->affr = exact(n[4], sizeof(*L->affr));
+            L->side = exact(n_side, 4); L->refined = exact(4 * (size_t)n[1], 4);
+            memcpy(L->n, n, sizeof(n)); L->n_side = n_side;
+        }
+    }
+}
+
+static void free_lists(lists *L) { free(L->mc); free(L->mcx); free(L->aff); free(L->rpr); free(L->affr); free(L->side); free(L->refined); }
+
+static ovhip_mvfield_src
+src_of(const lists *L)
+{
+    ovhip_mvfield_src s;
+    memset(&s, 0, sizeof(s));
+    s.mc = L->n[0] ? L->mc : NULL; s.mcx = L->n[1] ? L->mcx : NULL; s.aff = L->n[2] ? L->aff : NULL; s.rpr = L->n[3] ? L->rpr : NULL;
+    s.affr = L->n[4] ? L->affr : NULL; s.side = L->n_side ? L->side : NULL; s.refined = L->n[1] ? L->refined : NULL;
+    s.n_mc = L->n[0]; s.n_mcx = L->n[1]; s.n_aff = L->n[2]; s.n_rpr = L->n[3]; s.n_affr = L->n[4];
+    return s;
+}
+
+#define FAIL(...) do { fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); return 1; } while (0)
+
+int
+main(void)
+{
+    static const int sizes[][2] = { { 4, 4 }, { 16, 16 }, { 20, 12 }, { 72, 40 }, { 70, 38 }, { 136, 72 }, { 264, 136 }, { 416, 240 } };
+    long n_fields = 0, n_refused = 0;
+    uint64_t sum = 0;
+    for (unsigned s = 0; s < sizeof(sizes) / sizeof(sizes[0]); ++s) {
+        const int w = sizes[s][0], h = sizes[s][1], W4 = (w + 3) >> 2, H4 = (h + 3) >> 2;
+        lists L;
+        make_lists(w, h, &L);
+        const ovhip_mvfield_src src = src_of(&L);
+        for (int dtype = 0; dtype < 3; ++dtype) for (int layout = 0; layout < 2; ++layout) for (int vectors = 0; vectors < 2; ++vectors)
+        for (int want = 1; want < 4; ++want) {
+            const ovhip_mvfield_format fmt = { (uint8_t)dtype, (uint8_t)layout, (uint8_t)vectors, 0 };
+            size_t ib = 0;
+            const size_t vb = ovhip_mvfield_bytes(w, h, &fmt, &ib);
+            if (vb != (size_t)4 * W4 * H4 * (dtype == OVHIP_MVF_F16 ? 2 : 4) || ib != (size_t)4 * W4 * H4) FAIL("sizes of %dx%d", w, h);
+            uint8_t *vec = (want & 1) ? malloc(vb) : NULL;
+            uint32_t *info = (want & 2) ? malloc(ib) : NULL;
+            if (((want & 1) && !vec) || ((want & 2) && !info)) return 2;
+            if (vec) memset(vec, 0xA5, vb);
+            if (info) memset(info, 0xA5, ib);
+            const int r = ovhip_mvfield_host(w, h, &src, &fmt, vec, vb, info, ib);
+            if (r != OVHIP_OK) FAIL("ovhip_mvfield_host: %d at %dx%d", r, w, h);
+            for (size_t i = 0; vec && i < vb; ++i) sum = sum * 31 + vec[i];
+            for (int cy = 0; info && cy < H4; ++cy)
+                for (int cx = 0; cx < W4; ++cx) {
+                    const int t = (cy / 4) * ((w + 15) / 16) + cx / 4, kind = t % 7;
+                    const uint32_t word = info[cy * W4 + cx], k = (word >> 16) & 0xFF;
+                    sum = sum * 31 + word;
+                    if (kind == 6 ? word != OVHIP_MVF_EMPTY : !(k & OVHIP_MVF_INTER)) FAIL("cell (%d, %d) of %dx%d: info %08x", cx, cy, w, h, word);
+                    if (((kind == 2 || kind == 4) != ((k & OVHIP_MVF_AFFINE) != 0)) && kind != 6) FAIL("cell (%d, %d): affine bit", cx, cy);
+                    /* (an rpr tile's flags and dir are both 1 + t % 3: every scaled list is a used one) */
+                    if (kind == 3 && (word >> 24) != (uint32_t)(1 + t % 3)) FAIL("cell (%d, %d): scaled bits", cx, cy);
+                }
+            /* one byte short: refused, nothing written (the blocks are one byte short too) */
+            for (int which = 0; which < 2; ++which) {
+                if (!((want >> which) & 1)) continue;
+                const size_t nv = vb - (which == 0), ni = ib - (which == 1);
+                uint8_t *sv = vec ? malloc(nv) : NULL, *si = info ? malloc(ni) : NULL;
+                if (sv) memset(sv, 0xA5, nv);
+                if (si) memset(si, 0xA5, ni);
+                if (ovhip_mvfield_host(w, h, &src, &fmt, sv, nv, (uint32_t *)si, ni) != OVHIP_EINVAL) FAIL("a short destination was taken");
+                for (size_t i = 0; sv && i < nv; ++i) if (sv[i] != 0xA5) FAIL("a refusal wrote");
+                for (size_t i = 0; si && i < ni; ++i) if (si[i] != 0xA5) FAIL("a refusal wrote");
+                free(sv); free(si);
+                ++n_refused;
+            }
+            free(vec); free(info);
+            ++n_fields;
+        }
+        /* a cell covered twice and a unit that is not 4-aligned: refused before anything is written */
+        if (L.n[0] >= 2 && L.n[1]) {
+            const ovhip_mvfield_format fmt = { OVHIP_MVF_I32, OVHIP_MVF_CELLS, 0, 0 };
+            size_t ib = 0;
+            const size_t vb = ovhip_mvfield_bytes(w, h, &fmt, &ib);
+            uint8_t *vec = malloc(vb);
+            if (!vec) return 2;
+            memset(vec, 0xA5, vb);
+            const ovhip_mc_unit keep = L.mcx[0];
+            L.mcx[0].x = L.mc[0].x; L.mcx[0].y = L.mc[0].y;
+            if (ovhip_mvfield_host(w, h, &src, &fmt, vec, vb, NULL, 0) != OVHIP_EINVAL) FAIL("a cell covered twice was taken");
+            L.mcx[0] = keep; L.mcx[0].w = 14;
+            if (ovhip_mvfield_host(w, h, &src, &fmt, vec, vb, NULL, 0) != OVHIP_EINVAL) FAIL("a unit that is not 4-aligned was taken");
+            L.mcx[0] = keep;
+            for (size_t i = 0; i < vb; ++i) if (vec[i] != 0xA5) FAIL("a refusal wrote");
+            free(vec);
+            n_refused += 2;
+        }
+        free_lists(&L);
+    }
+    printf("%ld fields, %ld refusals, checksum %016llx\n", n_fields, n_refused, (unsigned long long)sum);
+    return 0;
+}
