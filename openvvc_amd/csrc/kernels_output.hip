@@ -372,15 +372,26 @@ extern "C" int ovhip_post_pic_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip
     return scale ? ovhip_output_scale_launch(ctx, pic, &post->info, shown) : ovhip_film_grain_launch(ctx, pic, post->model, post->poc, 0, shown);
 }
 
+extern "C" int ovhip_deliver_(ovhip_ctx *ctx, const ovhip_pic *shown, ovhip_frame_output *out)
+{
+    if (!out || !shown) return OVHIP_EINVAL;
+    if (out->mode == OVHIP_OUT_DIGEST) return ovhip_pic_digest(ctx, shown, &out->window, out->digest);
+    if (out->mode == OVHIP_OUT_PLANES) return ovhip_pic_download(ctx, shown, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
+    return out->mode == OVHIP_OUT_PACKED ? ovhip_pic_output(ctx, shown, &out->window, out->packed) : OVHIP_EINVAL;
+}
+
 extern "C" int ovhip_post_deliver_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_frame_output *out)
 {
     if (!out || out->mode < OVHIP_OUT_DIGEST || out->mode > OVHIP_OUT_PACKED) return OVHIP_EINVAL;       // before anything is launched
     ovhip_pic shown;
     const int r = ovhip_post_pic_(ctx, pic, post, &shown);
-    if (r != OVHIP_OK) return r;
-    if (out->mode == OVHIP_OUT_DIGEST) return ovhip_pic_digest(ctx, &shown, &out->window, out->digest);
-    if (out->mode == OVHIP_OUT_PLANES) return ovhip_pic_download(ctx, &shown, out->y, out->cb, out->cr, out->stride_y, out->stride_c);
-    return ovhip_pic_output(ctx, &shown, &out->window, out->packed);
+    return r != OVHIP_OK ? r : ovhip_deliver_(ctx, &shown, out);
+}
+
+extern "C" int ovhip_wait_(ovhip_ctx *ctx, const char *what)
+{
+    if (!ctx) return OVHIP_EINVAL;
+    return ov_sync_stream(ctx) != hipSuccess ? ov_fail(ctx, OVHIP_ELAUNCH, what, hipGetLastError()) : OVHIP_OK;
 }
 
 // The four conveniences of the header: their argument checks, then one call of the above -- PACKED into `packed`, or (packed == NULL)

@@ -16,6 +16,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_common.hip.h"
 #include "ovvc_dpb_priv.h"
+#include "run_io.hip.h"
 
 namespace {
 
@@ -42,48 +43,6 @@ template <int DT> __device__ __forceinline__ uint32_t rgb_bits(int v)
         const float f = __fmul_rn((float)v, (float)(1.0 / 1023));          // one multiplication, round to nearest, nothing to contract with
         if constexpr (DT == OVHIP_RGB_F32) return __float_as_uint(f);
         else return (uint32_t)__half_as_ushort(__float2half_rn(f));
-    }
-}
-
-// element e (a compile-time index after unrolling) of a run kept as dwords
-template <int ES, int NW> __device__ __forceinline__ void run_put(uint32_t (&w)[NW], int e, uint32_t bits)
-{
-    if constexpr (ES == 4) w[e] = bits;
-    else if constexpr (ES == 2) w[e >> 1] |= bits << (16 * (e & 1));
-    else w[e >> 2] |= bits << (8 * (e & 3));
-}
-template <int ES, int NW> __device__ __forceinline__ uint32_t run_get(const uint32_t (&w)[NW], int e)
-{
-    if constexpr (ES == 4) return w[e];
-    else if constexpr (ES == 2) return (w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
-    else return (w[e >> 2] >> (8 * (e & 3))) & 0xFFu;
-}
-
-// NE elements of ES bytes at p, of which the first n exist (n < NE: a row's tail).  p is a multiple of ES.
-template <int ES, int NE> __device__ __forceinline__ void run_store(char *p, const uint32_t (&w)[NE * ES / 4], int n)
-{
-    constexpr int NB = NE * ES, NW = NB / 4;
-    const uintptr_t ad = (uintptr_t)p;
-    if (n == NE && (ad & 15) == 0) {
-#pragma unroll
-        for (int k = 0; k + 4 <= NW; k += 4) *reinterpret_cast<uint4 *>(p + 4 * k) = make_uint4(w[k], w[k + 1], w[k + 2], w[k + 3]);
-        if constexpr (NW & 2) *reinterpret_cast<uint2 *>(p + 4 * (NW & ~3)) = make_uint2(w[NW & ~3], w[(NW & ~3) + 1]);
-    } else if (n == NE && (ad & 7) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; k += 2) *reinterpret_cast<uint2 *>(p + 4 * k) = make_uint2(w[k], w[k + 1]);
-    } else if (n == NE && (ad & 3) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) *reinterpret_cast<uint32_t *>(p + 4 * k) = w[k];
-    } else {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const uint32_t v = run_get<ES, NW>(w, e);
-            if (e < n) {
-                if constexpr (ES == 4) *reinterpret_cast<uint32_t *>(p + 4 * e) = v;
-                else if constexpr (ES == 2) *reinterpret_cast<uint16_t *>(p + 2 * e) = (uint16_t)v;
-                else *reinterpret_cast<uint8_t *>(p + e) = (uint8_t)v;
-            }
-        }
     }
 }
 
@@ -223,21 +182,18 @@ extern "C" int ovhip_rgb_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhi
     return OVHIP_OK;
 }
 
-extern "C" int ovhip_rgb_scratch_(ovhip_ctx *ctx, size_t bytes, void **d)
+extern "C" int ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *host_dst, size_t dst_bytes)
 {
-    if (!ctx || !d) return OVHIP_EINVAL;
+    if (!ctx || !pic || !fmt || !host_dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
-    const int r = ov_scratch(ctx, bytes, 0);
-    *d = r == OVHIP_OK ? ctx->scratch_d : nullptr;
-    return r;
-}
-
-extern "C" int ovhip_rgb_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_rgb_format *fmt,
-                               void *d_dst, size_t dst_bytes)
-{
-    ovhip_pic shown;
-    int r = ovhip_post_pic_(ctx, pic, post, &shown);
-    if (r == OVHIP_OK) r = ovhip_rgb_launch(ctx, &shown, win, fmt, d_dst, dst_bytes);
-    if (r == OVHIP_OK && ov_sync_stream(ctx) != hipSuccess) r = ov_fail(ctx, OVHIP_ELAUNCH, "RGB output", hipGetLastError());
+    const size_t bytes = ovhip_rgb_bytes(pic->w, pic->h, win, fmt);
+    if (!bytes || dst_bytes < bytes) {
+        /* no size, or a host_dst that is too small: the launch refuses both before it looks at the pointer, and words the reason */
+        const int q = ovhip_rgb_launch(ctx, pic, win, fmt, host_dst, dst_bytes);
+        return q != OVHIP_OK ? q : OVHIP_EINVAL;
+    }
+    int r = ov_scratch(ctx, bytes, 0);
+    if (r == OVHIP_OK) r = ovhip_rgb_launch(ctx, pic, win, fmt, ctx->scratch_d, bytes);
+    if (r == OVHIP_OK) r = ovhip_d2h(ctx, host_dst, ctx->scratch_d, bytes);
     return r;
 }

@@ -15,6 +15,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_common.hip.h"
 #include "ovvc_dpb_priv.h"
+#include "run_io.hip.h"
 
 namespace {
 
@@ -31,60 +32,6 @@ struct SurfArgs {
     unsigned items_y, items_c;// runs of the luma plane / of ONE chroma plane
     unsigned n_items;
 };
-
-// NS samples at p, of which the first n exist (n < NS: a row's tail), two to a dword
-template <int NS> __device__ __forceinline__ void run_load(const uint16_t *p, uint32_t (&w)[NS / 2], int n)
-{
-    constexpr int NW = NS / 2;
-    const uintptr_t ad = (uintptr_t)p;
-    if (n == NS && (ad & 15) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; k += 4) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(p + 2 * k);
-            w[k] = v.x; w[k + 1] = v.y; w[k + 2] = v.z; w[k + 3] = v.w;
-        }
-    } else if (n == NS && (ad & 7) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; k += 2) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(p + 2 * k);
-            w[k] = v.x; w[k + 1] = v.y;
-        }
-    } else if (n == NS && (ad & 3) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) w[k] = *reinterpret_cast<const uint32_t *>(p + 2 * k);
-    } else {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const uint32_t lo = 2 * k < n ? p[2 * k] : 0u, hi = 2 * k + 1 < n ? p[2 * k + 1] : 0u;
-            w[k] = lo | (hi << 16);
-        }
-    }
-}
-
-// NE elements of ES bytes at p, of which the first n exist (n < NE: a row's tail).  p is a multiple of ES.  (run_store of kernels_rgb.hip)
-template <int ES, int NE> __device__ __forceinline__ void run_store(char *p, const uint32_t (&w)[NE * ES / 4], int n)
-{
-    constexpr int NW = NE * ES / 4;
-    const uintptr_t ad = (uintptr_t)p;
-    if (n == NE && (ad & 15) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; k += 4) *reinterpret_cast<uint4 *>(p + 4 * k) = make_uint4(w[k], w[k + 1], w[k + 2], w[k + 3]);
-    } else if (n == NE && (ad & 7) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; k += 2) *reinterpret_cast<uint2 *>(p + 4 * k) = make_uint2(w[k], w[k + 1]);
-    } else if (n == NE && (ad & 3) == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) *reinterpret_cast<uint32_t *>(p + 4 * k) = w[k];
-    } else {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            if (e < n) {
-                if constexpr (ES == 2) *reinterpret_cast<uint16_t *>(p + 2 * e) = (uint16_t)(w[e >> 1] >> (16 * (e & 1)));
-                else *reinterpret_cast<uint8_t *>(p + e) = (uint8_t)(w[e >> 2] >> (8 * (e & 3)));
-            }
-        }
-    }
-}
 
 // the stored values of two samples in one dword; thr: the two thresholds of the row, D[y & 1][0] | D[y & 1][1] << 16 (ROUND: 2 | 2 << 16)
 template <int FMT> __device__ __forceinline__ uint32_t surf_pair(uint32_t w, uint32_t thr)
@@ -228,14 +175,4 @@ extern "C" int ovhip_pic_output_surface(ovhip_ctx *ctx, const ovhip_pic *pic, co
     if (e != hipSuccess) return ov_fail(ctx, OVHIP_ENODEV, "ovhip_pic_output_surface: D2H", e);
     if (ov_sync_stream(ctx) != hipSuccess) return ov_fail(ctx, OVHIP_ELAUNCH, "ovhip_pic_output_surface", hipGetLastError());
     return OVHIP_OK;
-}
-
-extern "C" int ovhip_surface_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_surface_format *fmt,
-                                   void *d_dst, size_t dst_bytes)
-{
-    ovhip_pic shown;
-    int r = ovhip_post_pic_(ctx, pic, post, &shown);
-    if (r == OVHIP_OK) r = ovhip_surface_launch(ctx, &shown, win, fmt, d_dst, dst_bytes);
-    if (r == OVHIP_OK && ov_sync_stream(ctx) != hipSuccess) r = ov_fail(ctx, OVHIP_ELAUNCH, "surface output", hipGetLastError());
-    return r;
 }

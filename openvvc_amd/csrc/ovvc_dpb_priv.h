@@ -12,6 +12,7 @@ void ovhip_dpb_rearm_(ovhip_dpb *d);
 /* CLOCK_MONOTONIC seconds at which the frame's last picture was complete on the device / published (the stream driver's timeline) */
 double ovhip_frame_published_at(const ovhip_frame *f);
 double ovhip_frame_done_at(const ovhip_frame *f);
+#define OVHIP_HIDDEN_ __attribute__((visibility("hidden")))
 /* ---- the post-process step of the output path (kernels_output.hip): what happens to a finished picture on its way out.  One kind at
  * a time: the reference resamples the UNgrained frame over the grained one, so there is no parity to offer for both. */
 enum { OVHIP_POST_NONE = 0, OVHIP_POST_SCALE, OVHIP_POST_GRAIN };
@@ -25,11 +26,15 @@ typedef struct ovhip_post_ {
  * grow-only scratch picture, asynchronously on the context's stream, and that is handed out: it stays valid until the context's next
  * post-processed output.  `pic` is only read. */
 int  ovhip_post_pic_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_pic *shown);
-/* ovhip_post_pic_, then the delivery out->mode names: DIGEST -> ovhip_pic_digest (into out->digest: why `out` is not const), PLANES ->
- * ovhip_pic_download, PACKED -> ovhip_pic_output; any other mode is OVHIP_EINVAL.  out->window applies to the picture shown. */
+/* the delivery out->mode names, of a picture already shown: DIGEST -> ovhip_pic_digest (into out->digest: why `out` is not const),
+ * PLANES -> ovhip_pic_download, PACKED -> ovhip_pic_output; any other mode is OVHIP_EINVAL.  out->window applies to the picture shown. */
+OVHIP_HIDDEN_ int ovhip_deliver_(ovhip_ctx *ctx, const ovhip_pic *shown, ovhip_frame_output *out);
+/* ovhip_post_pic_, then ovhip_deliver_ of the picture it shows; a mode that is none of the three is refused before anything is launched */
 int  ovhip_post_deliver_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_frame_output *out);
+/* the wait for everything enqueued on the context's stream (the frame thread, behind an output's launch: complete on the device at
+ * return); `what` names the output in the error text */
+OVHIP_HIDDEN_ int ovhip_wait_(ovhip_ctx *ctx, const char *what);
 /* the launchers' own refusals (kernels_scale.hip, kernels_grain.hip) under the name `who`: ovhip_post_pic_ asks before it allocates */
-#define OVHIP_HIDDEN_ __attribute__((visibility("hidden")))
 OVHIP_HIDDEN_ int ovhip_scale_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h);
 OVHIP_HIDDEN_ int ovhip_grain_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *pic, const ovhip_fg_model *model);
 /* ---- RGB output (ovvc_rgb.c, kernels_rgb.hip): what the host twin and the launcher share -- the refusals and everything a loop or a
@@ -44,11 +49,6 @@ typedef struct ovhip_rgb_plan_ {
 } ovhip_rgb_plan_;
 OVHIP_HIDDEN_ int ovhip_rgb_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, const void *dst, size_t dst_bytes,
                                        ovhip_rgb_plan_ *plan, const char **why);
-/* the context's grow-only device scratch of the synchronous conveniences, at least `bytes` large (kernels_rgb.hip) */
-OVHIP_HIDDEN_ int ovhip_rgb_scratch_(ovhip_ctx *ctx, size_t bytes, void **d);
-/* ovhip_post_pic_, ovhip_rgb_launch of the picture it shows, and the wait for both: complete on the device at return (the frame thread) */
-int  ovhip_rgb_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_rgb_format *fmt,
-                     void *d_dst, size_t dst_bytes);
 /* ---- Surface output (ovvc_surface.c, kernels_surface.hip): what the host twin and the launcher share, as the RGB plan above.  Plane
  * 0 is luma; a semi-planar format has ONE chroma plane (1: Cb and Cr interleaved), a planar one two (1: Cb, 2: Cr). */
 typedef struct ovhip_surface_plan_ {
@@ -64,9 +64,6 @@ OVHIP_HIDDEN_ int ovhip_surface_format_check_(const ovhip_surface_format *fmt, c
 /* on a refusal for "destination too small" plan->bytes holds the size needed */
 OVHIP_HIDDEN_ int ovhip_surface_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, const void *dst, size_t dst_bytes,
                                            ovhip_surface_plan_ *plan, const char **why);
-/* ovhip_post_pic_, ovhip_surface_launch of the picture it shows, and the wait for both: complete on the device at return (the frame thread) */
-int  ovhip_surface_post_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, const ovhip_window *win, const ovhip_surface_format *fmt,
-                         void *d_dst, size_t dst_bytes);
 /* ---- Motion field output (ovvc_mvfield.c, kernels_mvfield.hip; what they share: ovvc_mvfield_priv.h).  ovhip_job_mvfield and the
  * wait for it: complete on the device at return (the frame thread; ovvc_picture.hip) */
 int  ovhip_job_mvfield_done_(ovhip_job *job, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes);

@@ -4,7 +4,7 @@
  * headers: context + job + the picture's place in the device DPB + its reference table, and the ORDER of a picture's end:
  *
  *     uploads enqueued -> wait for the reference pictures (host) -> launches -> ovhip_job_wait (incl. its second pass)
- *     -> publish + unpin the references -> output (optional; after the wait, never before: r2 downloaded first)
+ *     -> publish + unpin the references -> outputs (optional; after the wait, never before: r2 downloaded first): picture_end
  *
  * The reference's order for the same events: slicedec.c:934-956 (filters of the last rows, then ovdpb_report_decoded_ctu_line),
  * rcn_inter.c:131-146 (a reader waits for its reference's rows), dectest.c:372-409 (the application reads the frame after the
@@ -21,6 +21,16 @@
 #define MAX_REFS 16
 
 static double mono_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
+
+/* one per-picture output: RGB and surface write dst[0] through the window `win`; the motion field writes its vectors to dst[0] and its
+ * info to dst[1] (either may be NULL) from the arrays of the job that decoded the picture */
+enum { OUT_RGB, OUT_SURFACE, OUT_MVFIELD, N_OUTS };
+typedef struct frame_out {
+    int on;
+    union { ovhip_rgb_format rgb; ovhip_surface_format surf; ovhip_mvfield_format mvf; } fmt;
+    ovhip_window win;
+    void *dst[2]; size_t bytes[2];
+} frame_out;
 
 struct ovhip_frame {
     ovhip_dpb *dpb;
@@ -53,15 +63,9 @@ struct ovhip_frame {
      * one, what the last one gave */
     int hash_on, hash_method, hash_planes, hash_expect, hash_done;
     ovhip_pic_hash_value hash_expected, hash_computed;
-    /* RGB output (ovhip_frame_set_rgb_output) of the NEXT picture completed: the destination is that picture's, so the setting ends with it */
-    int rgb_on;
-    ovhip_rgb_format rgb_fmt; ovhip_window rgb_win; void *rgb_dst; size_t rgb_bytes;
-    /* surface output (ovhip_frame_set_surface_output), the same way and independent of it */
-    int surf_on;
-    ovhip_surface_format surf_fmt; ovhip_window surf_win; void *surf_dst; size_t surf_bytes;
-    /* motion field output (ovhip_frame_set_mvfield_output), per picture likewise: written from the arrays of the job that decoded it */
-    int mvf_on;
-    ovhip_mvfield_format mvf_fmt; void *mvf_vec, *mvf_info; size_t mvf_vec_bytes, mvf_info_bytes;
+    /* the per-picture outputs (ovhip_frame_set_rgb_output / _surface_output / _mvfield_output) of the NEXT picture completed, each
+     * independent of the others: the destinations are that picture's, so the settings end with it (picture_end) */
+    frame_out outs[N_OUTS];
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -375,12 +379,15 @@ publish(ovhip_frame *f, int status)
     return r;
 }
 
+/* a picture that ends, however it ends, takes its RGB, surface and motion field destinations with it */
+static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; }
+
 int
 ovhip_frame_fail(ovhip_frame *f, int status)
 {
     if (!f) return OVHIP_EINVAL;
     if (!f->status) f->status = status ? status : OVHIP_EINVAL;
-    f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0;     /* (the picture that ends here takes its RGB, surface and motion field destinations with it) */
+    outs_clear(f);
     trace(f, OVHIP_FE_FAIL, f->key, 0, f->status, 0, 0);
     return publish(f, f->status);
 }
@@ -437,17 +444,16 @@ ovhip_frame_picture_hash(const ovhip_frame *f, ovhip_pic_hash_value *computed)
     return f->hash_done > 0;
 }
 
-/* the hash of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: of f->dst, the decoded picture as it was
- * published (its readers only read it, as this does), never of the post-processed copy an output makes.  A value that differs from
- * the expectation is a verdict, not an error */
+/* what the three setters below have in common once a format has passed its own checks: the record of output `which` */
 static int
-frame_hash(ovhip_frame *f)
+out_store(ovhip_frame *f, int which, const void *fmt, size_t fmt_bytes, const ovhip_window *win, void *d0, size_t n0, void *d1, size_t n1)
 {
-    f->hash_done = 0;
-    if (!f->hash_on) return OVHIP_OK;
-    const int r = ovhip_pic_hash(f->ctx, &f->dst, f->hash_method, f->hash_planes, &f->hash_computed);
-    if (r != OVHIP_OK) return r;
-    f->hash_done = !f->hash_expect || ovhip_pic_hash_equal(&f->hash_computed, &f->hash_expected) ? 1 : -1;
+    frame_out *o = &f->outs[which];
+    memset(o, 0, sizeof(*o));
+    memcpy(&o->fmt, fmt, fmt_bytes);
+    if (win) o->win = *win;
+    o->dst[0] = d0; o->bytes[0] = n0; o->dst[1] = d1; o->bytes[1] = n1;
+    o->on = 1;
     return OVHIP_OK;
 }
 
@@ -455,105 +461,111 @@ int
 ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!fmt) { f->rgb_on = 0; return OVHIP_OK; }
+    if (!fmt) { f->outs[OUT_RGB].on = 0; return OVHIP_OK; }
     int32_t coef[5], yoff;
     const int r = ovhip_rgb_coefs(fmt, coef, &yoff);          /* the format's refusals come back here, not from a picture's last call */
     if (r != OVHIP_OK) return r;
     if (fmt->layout > OVHIP_RGB_PACKED || fmt->chroma_loc > 5 || !d_dst) return OVHIP_EINVAL;
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to convert) */
-    f->rgb_on = 1; f->rgb_fmt = *fmt; f->rgb_dst = d_dst; f->rgb_bytes = dst_bytes;
-    memset(&f->rgb_win, 0, sizeof(f->rgb_win));
-    if (win) f->rgb_win = *win;
-    return OVHIP_OK;
-}
-
-/* the frame's post-process step as ovhip_post_pic_ takes it: a grain model is derived afresh for every picture, into *model */
-static int
-frame_post(const ovhip_frame *f, ovhip_post_ *post, ovhip_fg_model *model)
-{
-    *post = f->post;
-    if (post->kind == OVHIP_POST_GRAIN) {
-        const int r = ovhip_fg_derive(&f->fg, model, NULL);
-        if (r != OVHIP_OK) return r;
-        post->model = model;
-    }
-    return OVHIP_OK;
-}
-
-/* the output of a complete picture, for ovhip_frame_submit and the last ovhip_frame_band alike: the frame's post-process step (if any:
- * into the context's scratch picture -- f->dst itself is only read), then the delivery `out` names */
-static int
-frame_output(ovhip_frame *f, ovhip_frame_output *out)
-{
-    ovhip_post_ post;
-    ovhip_fg_model model;
-    const int r = frame_post(f, &post, &model);
-    return r != OVHIP_OK ? r : ovhip_post_deliver_(f->ctx, &f->dst, &post, out);
-}
-
-/* the RGB output of a complete picture, for the same two callers: of the picture the output shows (the same post-process step; a
- * delivery that follows makes the step again, into the same scratch picture), complete on the device at return.  The setting was
- * this picture's: it ends here whatever happens */
-static int
-frame_rgb(ovhip_frame *f)
-{
-    if (!f->rgb_on) return OVHIP_OK;
-    f->rgb_on = 0;
-    ovhip_post_ post;
-    ovhip_fg_model model;
-    const int r = frame_post(f, &post, &model);
-    return r != OVHIP_OK ? r : ovhip_rgb_post_(f->ctx, &f->dst, &post, &f->rgb_win, &f->rgb_fmt, f->rgb_dst, f->rgb_bytes);
+    return out_store(f, OUT_RGB, fmt, sizeof(*fmt), win, d_dst, dst_bytes, NULL, 0);
 }
 
 int
 ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!fmt) { f->surf_on = 0; return OVHIP_OK; }
+    if (!fmt) { f->outs[OUT_SURFACE].on = 0; return OVHIP_OK; }
     const int r = ovhip_surface_format_check_(fmt, NULL);      /* the format's refusals that need no picture come back here */
     if (r != OVHIP_OK) return r;
     if (!d_dst) return OVHIP_EINVAL;
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to convert) */
-    f->surf_on = 1; f->surf_fmt = *fmt; f->surf_dst = d_dst; f->surf_bytes = dst_bytes;
-    memset(&f->surf_win, 0, sizeof(f->surf_win));
-    if (win) f->surf_win = *win;
-    return OVHIP_OK;
-}
-
-/* the surface output of a complete picture, as frame_rgb: a post-process step of its own, complete on the device at return, and the
- * setting ends here whatever happens */
-static int
-frame_surface(ovhip_frame *f)
-{
-    if (!f->surf_on) return OVHIP_OK;
-    f->surf_on = 0;
-    ovhip_post_ post;
-    ovhip_fg_model model;
-    const int r = frame_post(f, &post, &model);
-    return r != OVHIP_OK ? r : ovhip_surface_post_(f->ctx, &f->dst, &post, &f->surf_win, &f->surf_fmt, f->surf_dst, f->surf_bytes);
+    return out_store(f, OUT_SURFACE, fmt, sizeof(*fmt), win, d_dst, dst_bytes, NULL, 0);
 }
 
 int
 ovhip_frame_set_mvfield_output(ovhip_frame *f, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!fmt) { f->mvf_on = 0; return OVHIP_OK; }
+    if (!fmt) { f->outs[OUT_MVFIELD].on = 0; return OVHIP_OK; }
     const int r = ovhip_mvfield_dst_check_(fmt, d_vec, vec_bytes, d_info, info_bytes, NULL);   /* the refusals that need no picture come back here */
     if (r != OVHIP_OK) return r;
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no motion to export) */
     if (f->band_mode) return OVHIP_EUNSUP;                     /* (a band-wise picture's arrays live in band arenas: ovhip_job_mvfield) */
-    f->mvf_on = 1; f->mvf_fmt = *fmt; f->mvf_vec = d_vec; f->mvf_vec_bytes = vec_bytes; f->mvf_info = d_info; f->mvf_info_bytes = info_bytes;
-    return OVHIP_OK;
+    return out_store(f, OUT_MVFIELD, fmt, sizeof(*fmt), NULL, d_vec, vec_bytes, d_info, info_bytes);
 }
 
-/* the motion field of a complete picture, from the arrays of the job `j` that decoded it (still bound to this frame's context):
- * complete on the device at return, and the setting ends here whatever happens */
+/* *shown = the picture this picture's outputs show: f->dst after the frame's post-process step (if any: into the context's scratch
+ * picture -- f->dst itself is only read; a grain model is derived afresh for every picture).  The step runs ONCE per picture, for the
+ * first output that asks (*have); the outputs after it read the same `shown`.  That is sound because the step and all its readers are
+ * enqueued by this one thread on this frame's own context and stream, in order, and nothing else writes that context's scratch
+ * picture in between: no other output of this context runs until picture_end returns */
 static int
-frame_mvfield(ovhip_frame *f, ovhip_job *j)
+frame_shown(ovhip_frame *f, ovhip_pic *shown, int *have)
 {
-    if (!f->mvf_on) return OVHIP_OK;
-    f->mvf_on = 0;
-    return ovhip_job_mvfield_done_(j, &f->mvf_fmt, f->mvf_vec, f->mvf_vec_bytes, f->mvf_info, f->mvf_info_bytes);
+    if (*have) return OVHIP_OK;
+    ovhip_post_ post = f->post;
+    ovhip_fg_model model;                                      /* (copied by the launch: not needed after it) */
+    if (post.kind == OVHIP_POST_GRAIN) {
+        const int r = ovhip_fg_derive(&f->fg, &model, NULL);
+        if (r != OVHIP_OK) return r;
+        post.model = &model;
+    }
+    const int r = ovhip_post_pic_(f->ctx, &f->dst, &post, shown);
+    *have = r == OVHIP_OK;
+    return r;
+}
+
+/* The end of a picture, for ovhip_frame_submit and the last ovhip_frame_band alike.  r: what the decode gave, after the wait (only the
+ * wait marks the picture complete).  j: the job that decoded it; borrowed: j when it is a caller's job bound to this frame's context
+ * (ovhip_frame_submit), which goes back to its own context here -- this frame and its context may be destroyed before the job.
+ *
+ *     publish (+ unpin the references) -> hash of f->dst -> RGB -> surface -> motion field -> the settings end -> delivery `out` names
+ *
+ * The picture is published first: its readers go on while this thread copies it out (the outputs only read; whoever keeps the key
+ * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns).  Each output is complete on the device
+ * when its step returns.  A dry frame publishes and touches no output. */
+static int
+picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_frame_output *out)
+{
+    if (f->dry) { if (f->status) r = f->status; (void)publish(f, r); return r; }
+    frame_out *rgb = &f->outs[OUT_RGB], *surf = &f->outs[OUT_SURFACE], *mvf = &f->outs[OUT_MVFIELD];
+    /* the motion field step reads the borrowed job's arrays on this frame's stream: the job goes home behind it */
+    const int keep_job = borrowed && mvf->on && r == OVHIP_OK;
+    if (borrowed && !keep_job) { int q = ovhip_job_bind(borrowed, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
+    if (f->status) r = f->status;         /* the first error, e.g. a failed reference rather than "callback failed" */
+    (void)publish(f, r);
+    ovhip_pic shown;
+    int have = 0;
+    /* the hash is of f->dst, the decoded picture as it was published (its readers only read it, as this does), never of the
+     * post-processed copy an output makes.  A value that differs from the expectation is a verdict, not an error */
+    f->hash_done = 0;
+    if (r == OVHIP_OK && f->hash_on) {
+        if ((r = ovhip_pic_hash(f->ctx, &f->dst, f->hash_method, f->hash_planes, &f->hash_computed)) != OVHIP_OK) fail(f, r, "picture hash");
+        else f->hash_done = !f->hash_expect || ovhip_pic_hash_equal(&f->hash_computed, &f->hash_expected) ? 1 : -1;
+    }
+    if (r == OVHIP_OK && rgb->on) {
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_rgb_launch(f->ctx, &shown, &rgb->win, &rgb->fmt.rgb, rgb->dst[0], rgb->bytes[0]);
+        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "RGB output");
+        if (r != OVHIP_OK) fail(f, r, "RGB output");
+    }
+    if (r == OVHIP_OK && surf->on) {
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_surface_launch(f->ctx, &shown, &surf->win, &surf->fmt.surf, surf->dst[0], surf->bytes[0]);
+        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "surface output");
+        if (r != OVHIP_OK) fail(f, r, "surface output");
+    }
+    if (r == OVHIP_OK && mvf->on && (r = ovhip_job_mvfield_done_(j, &mvf->fmt.mvf, mvf->dst[0], mvf->bytes[0], mvf->dst[1], mvf->bytes[1])) != OVHIP_OK)
+        fail(f, r, "motion field output");
+    outs_clear(f);                        /* whatever happened: a picture that failed takes its destinations with it */
+    if (keep_job) { int q = ovhip_job_bind(borrowed, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
+    if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
+        PT0();
+        /* (a mode that is none of the three is refused before anything is launched for it) */
+        r = out->mode < OVHIP_OUT_DIGEST || out->mode > OVHIP_OUT_PACKED ? OVHIP_EINVAL : frame_shown(f, &shown, &have);
+        if (r == OVHIP_OK) r = ovhip_deliver_(f->ctx, &shown, out);
+        PT(f->pt_output);
+        if (r != OVHIP_OK) fail(f, r, "picture output");
+    }
+    return r;
 }
 
 int
@@ -567,8 +579,7 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
         /* dry: the same waits and the same publication, no launches, no output */
         if (r == OVHIP_OK) r = acquire_refs(f);
         trace(f, OVHIP_FE_SUBMIT, f->key, 0, (int64_t)n_refined_units(f), f->n_refs, r);
-        (void)publish(f, r);
-        return r;
+        return picture_end(f, r, NULL, NULL, NULL);
     }
     trace(f, OVHIP_FE_SUBMIT, f->key, 0, (int64_t)n_refined_units(f), f->n_refs, r);
     if (r == OVHIP_OK && !j) r = fail(f, OVHIP_EINVAL, "ovhip_frame_submit: nothing was recorded");
@@ -591,26 +602,7 @@ ovhip_frame_submit(ovhip_frame *f, ovhip_job *job, const ovhip_pic *intra, const
         f->done_at = mono_s();
         if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_wait");
     }
-    /* a borrowed job goes back to its own context: this frame (and its context) may be destroyed before the job -- behind the motion
-     * field step where one is set, which reads that job's arrays on this frame's stream */
-    const int keep_job = job && f->mvf_on && r == OVHIP_OK;
-    if (job && !keep_job) { int q = ovhip_job_bind(job, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
-    if (f->status) r = f->status;         /* the first error, e.g. a failed reference rather than "callback failed" */
-    /* the picture is complete: its readers go on while this thread copies it out (the output only reads; whoever keeps the key
-     * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns) */
-    (void)publish(f, r);
-    if (r == OVHIP_OK && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
-    if (r == OVHIP_OK && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
-    if (r == OVHIP_OK && (r = frame_surface(f)) != OVHIP_OK) fail(f, r, "surface output");
-    if (r == OVHIP_OK && (r = frame_mvfield(f, j)) != OVHIP_OK) fail(f, r, "motion field output");
-    f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0;      /* (a picture that failed takes its destinations with it) */
-    if (keep_job) { int q = ovhip_job_bind(job, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
-    if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {
-        const double to0 = PT_ON() ? mono_s() : 0.0;
-        r = frame_output(f, out);
-        if (PT_ON()) f->pt_output += mono_s() - to0;
-        if (r != OVHIP_OK) fail(f, r, "picture output");
-    }
+    r = picture_end(f, r, j, job, out);
     PT(f->pt_submit); f->pn_pics += !f->band_mode;
     return r;
 }
@@ -726,7 +718,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     if (r != OVHIP_OK) {
         /* a latched error: nothing more goes to the device; the last call publishes the picture as failed */
         trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, r);
-        if (last) { (void)publish(f, r); f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0; }
+        if (last) (void)picture_end(f, r, NULL, NULL, NULL);
         return r;
     }
     if (last) row_end = f->h;
@@ -751,7 +743,7 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
     units_need_rows(f, &f->band_prev, &now, 0, need);
     r = refs_rows_ready(f, need, block);
     if (last) PT(f->pt_final_refs); else PT(f->pt_band_refs); }
-    if (r < 0) { trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, r); if (last) (void)publish(f, r); return r; }
+    if (r < 0) { trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, r); if (last) (void)picture_end(f, r, NULL, NULL, NULL); return r; }
     if (!r) { f->n_deferred++; trace(f, OVHIP_FE_BAND, f->key, 0, row_end, last, 0); return 0; }
     int32_t rows = 0; void *ev = NULL; const volatile uint32_t *abw = NULL;
     if (f->dry) {
@@ -779,19 +771,8 @@ frame_band(ovhip_frame *f, const ovhip_job_params *params, int32_t row_end, int3
         f->done_at = mono_s();
         if (q != OVHIP_OK) r = fail(f, q, "ovhip_job_wait");
     }
-    if (f->status) r = f->status;
-    (void)publish(f, r);
     f->pn_pics++;
-    if (r == OVHIP_OK && !f->dry && (r = frame_hash(f)) != OVHIP_OK) fail(f, r, "picture hash");
-    if (r == OVHIP_OK && !f->dry && (r = frame_rgb(f)) != OVHIP_OK) fail(f, r, "RGB output");
-    if (r == OVHIP_OK && !f->dry && (r = frame_surface(f)) != OVHIP_OK) fail(f, r, "surface output");
-    f->rgb_on = 0; f->surf_on = 0; f->mvf_on = 0;
-    if (r == OVHIP_OK && !f->dry && out && out->mode != OVHIP_OUT_NONE) {
-        PT0();
-        r = frame_output(f, out);
-        PT(f->pt_output);
-        if (r != OVHIP_OK) fail(f, r, "picture output");
-    }
+    r = picture_end(f, r, j, NULL, out);
     return r == OVHIP_OK ? 1 : r;
 }
 

@@ -1,9 +1,10 @@
-/* RGB output on the host: the coefficients, the refusals the launcher shares, the definition over planes in host memory, and the
- * synchronous convenience.  Definition: include/ovvc_hip.h, "RGB output on the device"; the device half is kernels_rgb.hip.
+/* RGB output on the host: the coefficients, the refusals the launcher shares, and the definition over planes in host
+ * memory.  Definition: include/ovvc_hip.h, "RGB output on the device"; the device half is kernels_rgb.hip.
  * Plain C, no HIP calls of its own. */
 #include <string.h>
 #include "ovvc_hip.h"
 #include "ovvc_dpb_priv.h"
+#include "ovvc_outdst_priv.h"
 
 /* round(p / q) for p, q > 0 (no coefficient is a tie: tests/spec_rgb.py asserts it on the exact rationals) */
 static int32_t rnd_div(uint64_t p, uint64_t q) { return (int32_t)((2 * p + q) / (2 * q)); }
@@ -39,10 +40,7 @@ static int elem_bytes(int dtype) { return dtype == OVHIP_RGB_U8 ? 1 : (dtype == 
 static int
 window_geom(int32_t w, int32_t h, const ovhip_window *win, ovhip_rgb_plan_ *p)
 {
-    if (w <= 0 || h <= 0 || (w & 3) || (h & 3)) return 0;
-    const int32_t l = win ? win->offset_lft : 0, r = win ? win->offset_rgt : 0, a = win ? win->offset_abv : 0, b = win ? win->offset_blw : 0;
-    p->x0 = 2 * l; p->y0 = 2 * a; p->W = w - 2 * (l + r); p->H = h - 2 * (a + b);
-    return p->W > 0 && p->H > 0;
+    return w > 0 && h > 0 && !(w & 3) && !(h & 3) && ovhip_out_window_(w, h, win, &p->x0, &p->y0, &p->W, &p->H);
 }
 
 size_t
@@ -51,12 +49,6 @@ ovhip_rgb_bytes(int32_t w, int32_t h, const ovhip_window *win, const ovhip_rgb_f
     ovhip_rgb_plan_ p;
     if (!fmt || fmt->dtype > OVHIP_RGB_F32 || fmt->layout > OVHIP_RGB_PACKED || !window_geom(w, h, win, &p)) return 0;
     return (size_t)3 * (size_t)p.W * (size_t)p.H * (size_t)elem_bytes(fmt->dtype);
-}
-
-static int
-ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
 }
 
 int
@@ -72,19 +64,15 @@ ovhip_rgb_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_
     const int r = ovhip_rgb_coefs(fmt, plan->coef, &plan->yoff);
     if (r != OVHIP_OK) { *why = r == OVHIP_EUNSUP ? "matrix coefficients not built" : "matrix coefficients unspecified"; return r; }
     if (!dst) { *why = "null destination"; return OVHIP_EINVAL; }
-    if (!pic->y || !pic->cb || !pic->cr) { *why = "missing plane"; return OVHIP_EINVAL; }
+    OVHIP_OUT_REFUSE_(ovhip_out_why_planes_(pic));
     if (pic->w <= 0 || pic->h <= 0 || (pic->w & 3) || (pic->h & 3)) { *why = "sizes must be positive multiples of 4"; return OVHIP_EINVAL; }
-    if (pic->stride_y < pic->w || pic->stride_c < pic->w / 2) { *why = "stride below the width"; return OVHIP_EINVAL; }
+    OVHIP_OUT_REFUSE_(ovhip_out_why_strides_(pic));
     if (!window_geom(pic->w, pic->h, win, plan)) { *why = "the window leaves nothing"; return OVHIP_EINVAL; }
     plan->es = elem_bytes(fmt->dtype);
     plan->bytes = (size_t)3 * (size_t)plan->W * (size_t)plan->H * (size_t)plan->es;
-    if (dst_bytes < plan->bytes) { *why = "destination too small"; return OVHIP_EINVAL; }
-    if ((uintptr_t)dst & (uintptr_t)(plan->es - 1)) { *why = "destination not aligned to its element"; return OVHIP_EINVAL; }
-    const size_t ny = ((size_t)(pic->h - 1) * (size_t)pic->stride_y + (size_t)pic->w) * 2;
-    const size_t nc = ((size_t)(pic->h / 2 - 1) * (size_t)pic->stride_c + (size_t)(pic->w / 2)) * 2;
-    if (ranges_overlap(dst, plan->bytes, pic->y, ny) || ranges_overlap(dst, plan->bytes, pic->cb, nc) || ranges_overlap(dst, plan->bytes, pic->cr, nc)) {
-        *why = "destination overlaps the picture"; return OVHIP_EINVAL;
-    }
+    OVHIP_OUT_REFUSE_(ovhip_out_why_small_(dst_bytes, plan->bytes));               /* (the size before the alignment: this plan's order) */
+    OVHIP_OUT_REFUSE_(ovhip_out_why_unaligned_(dst, plan->es));
+    OVHIP_OUT_REFUSE_(ovhip_out_why_overlap_(pic, dst, plan->bytes));
     plan->a = fmt->chroma_loc & 1;
     plan->b = fmt->chroma_loc < 2 ? 1 : (fmt->chroma_loc < 4 ? 0 : 2);
     plan->peak = fmt->dtype == OVHIP_RGB_U8 ? 255 : 1023;
@@ -142,21 +130,4 @@ ovhip_rgb_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_
         }
     }
     return OVHIP_OK;
-}
-
-int
-ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *host_dst, size_t dst_bytes)
-{
-    if (!ctx || !pic || !fmt || !host_dst) return OVHIP_EINVAL;
-    const size_t bytes = ovhip_rgb_bytes(pic->w, pic->h, win, fmt);
-    if (!bytes || dst_bytes < bytes) {
-        /* no size, or a host_dst that is too small: the launch refuses both before it looks at the pointer, and words the reason */
-        const int q = ovhip_rgb_launch(ctx, pic, win, fmt, host_dst, dst_bytes);
-        return q != OVHIP_OK ? q : OVHIP_EINVAL;
-    }
-    void *d = NULL;
-    int r = ovhip_rgb_scratch_(ctx, bytes, &d);
-    if (r == OVHIP_OK) r = ovhip_rgb_launch(ctx, pic, win, fmt, d, bytes);
-    if (r == OVHIP_OK) r = ovhip_d2h(ctx, host_dst, d, bytes);
-    return r;
 }

@@ -30,6 +30,10 @@ struct run_state;
 
 int ovhip_upload_streams_clear_of_(ovhip_ctx *keep_clear);     /* ovvc_picture.hip */
 
+/* a caller's device buffer of `slots` pictures' worth of an output, `bpp` bytes apart: picture idx lands in slot idx % slots */
+typedef struct slot_buf { char *base; size_t bpp; uint32_t slots; } slot_buf;
+static void *slot_of(const slot_buf *b, uint32_t idx) { return b->base ? b->base + (size_t)(idx % b->slots) * b->bpp : NULL; }
+
 struct ovhip_stream {
     ovhip_dpb *dpb;
     ovhip_stream_cfg cfg;
@@ -55,15 +59,12 @@ struct ovhip_stream {
     int hash_on, hash_method, hash_planes;
     const ovhip_pic_hash_value *hash_expected;
     ovhip_pic_hash_value *ph; uint32_t ph_n, ph_mismatch; int32_t ph_first_mismatch;
-    /* RGB output (ovhip_stream_set_rgb_output): picture idx lands in slot idx % rgb_slots of the caller's device buffer */
-    int rgb_on;
-    ovhip_rgb_format rgb_fmt; ovhip_window rgb_win; char *rgb_base; size_t rgb_bpp; uint32_t rgb_slots;
-    /* surface output (ovhip_stream_set_surface_output): the same way, in a buffer of its own */
-    int surf_on;
-    ovhip_surface_format surf_fmt; ovhip_window surf_win; char *surf_base; size_t surf_bpp; uint32_t surf_slots;
-    /* motion field output (ovhip_stream_set_mvfield_output): vectors and info in buffers of their own, either may be NULL */
-    int mvf_on;
-    ovhip_mvfield_format mvf_fmt; char *mvf_vec, *mvf_info; size_t mvf_vec_bpp, mvf_info_bpp; uint32_t mvf_slots;
+    /* the per-picture outputs (ovhip_stream_set_rgb_output / _surface_output / _mvfield_output), each in a device buffer of the caller's
+     * own: the motion field's vectors and info in one each, either may be absent */
+    int rgb_on, surf_on, mvf_on;
+    ovhip_rgb_format rgb_fmt; ovhip_surface_format surf_fmt; ovhip_mvfield_format mvf_fmt;
+    ovhip_window rgb_win, surf_win;
+    slot_buf rgb_buf, surf_buf, mvf_vec, mvf_info;
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -240,13 +241,9 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         if (s->post.kind == OVHIP_POST_GRAIN) (void)ovhip_frame_set_film_grain(f, &s->fg, p->poc);      /* (validated by the stream's setter) */
         if (s->ph) (void)ovhip_frame_set_picture_hash(f, s->hash_method, s->hash_planes, s->hash_expected ? &s->hash_expected[idx] : NULL);
         /* (validated by the stream's setter; the conversion is this frame thread's, after its wait: nothing goes through the output thread) */
-        if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, s->rgb_base + (size_t)(idx % s->rgb_slots) * s->rgb_bpp, s->rgb_bpp);
-        if (s->surf_on) (void)ovhip_frame_set_surface_output(f, &s->surf_fmt, &s->surf_win, s->surf_base + (size_t)(idx % s->surf_slots) * s->surf_bpp, s->surf_bpp);
-        if (s->mvf_on) {
-            const size_t slot = idx % s->mvf_slots;
-            (void)ovhip_frame_set_mvfield_output(f, &s->mvf_fmt, s->mvf_vec ? s->mvf_vec + slot * s->mvf_vec_bpp : NULL, s->mvf_vec_bpp,
-                                                 s->mvf_info ? s->mvf_info + slot * s->mvf_info_bpp : NULL, s->mvf_info_bpp);
-        }
+        if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, slot_of(&s->rgb_buf, idx), s->rgb_buf.bpp);
+        if (s->surf_on) (void)ovhip_frame_set_surface_output(f, &s->surf_fmt, &s->surf_win, slot_of(&s->surf_buf, idx), s->surf_buf.bpp);
+        if (s->mvf_on) (void)ovhip_frame_set_mvfield_output(f, &s->mvf_fmt, slot_of(&s->mvf_vec, idx), s->mvf_vec.bpp, slot_of(&s->mvf_info, idx), s->mvf_info.bpp);
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
         const double dt_sub = now_s() - t_sub;
@@ -565,22 +562,36 @@ ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, const
     return OVHIP_OK;
 }
 
+/* the size the stream outputs: its output scale's, else its pictures' */
+static void
+out_size(const ovhip_stream *s, int32_t *w, int32_t *h)
+{
+    const int scaled = s->post.kind == OVHIP_POST_SCALE;
+    *w = scaled ? s->post.out_w : s->cfg.w; *h = scaled ? s->post.out_h : s->cfg.h;
+}
+
+/* what the setters below have in common once a format has passed its own checks: the buffer's pointer and slots, and the bytes a
+ * picture is given against the bytes it needs (0: the format's size function refused the size or the window).  *b is written on success only */
+static int
+slot_buf_set(slot_buf *b, void *d_base, size_t bytes_per_picture, uint32_t n_slots, size_t need)
+{
+    if (!d_base || !n_slots || !need || bytes_per_picture < need) return OVHIP_EINVAL;
+    b->base = (char *)d_base; b->bpp = bytes_per_picture; b->slots = n_slots;
+    return OVHIP_OK;
+}
+
 int
 ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots)
 {
     if (!s) return OVHIP_EINVAL;
     if (!fmt) { s->rgb_on = 0; return OVHIP_OK; }
-    int32_t coef[5], yoff;
+    int32_t coef[5], yoff, w, h;
     const int r = ovhip_rgb_coefs(fmt, coef, &yoff);
     if (r != OVHIP_OK) return r;
-    if (fmt->layout > OVHIP_RGB_PACKED || fmt->chroma_loc > 5 || !d_base || !n_slots) return OVHIP_EINVAL;
-    /* the size the stream outputs: its output scale's, else its pictures' */
-    const int scaled = s->post.kind == OVHIP_POST_SCALE;
-    const size_t need = ovhip_rgb_bytes(scaled ? s->post.out_w : s->cfg.w, scaled ? s->post.out_h : s->cfg.h, win, fmt);
-    if (!need || bytes_per_picture < need) return OVHIP_EINVAL;
-    s->rgb_on = 1; s->rgb_fmt = *fmt; s->rgb_base = (char *)d_base; s->rgb_bpp = bytes_per_picture; s->rgb_slots = n_slots;
-    memset(&s->rgb_win, 0, sizeof(s->rgb_win));
-    if (win) s->rgb_win = *win;
+    if (fmt->layout > OVHIP_RGB_PACKED || fmt->chroma_loc > 5) return OVHIP_EINVAL;
+    out_size(s, &w, &h);
+    if (slot_buf_set(&s->rgb_buf, d_base, bytes_per_picture, n_slots, ovhip_rgb_bytes(w, h, win, fmt)) != OVHIP_OK) return OVHIP_EINVAL;
+    s->rgb_on = 1; s->rgb_fmt = *fmt; s->rgb_win = win ? *win : (ovhip_window){ 0, 0, 0, 0 };
     return OVHIP_OK;
 }
 
@@ -589,16 +600,12 @@ ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt
 {
     if (!s) return OVHIP_EINVAL;
     if (!fmt) { s->surf_on = 0; return OVHIP_OK; }
+    int32_t w, h;
     const int r = ovhip_surface_format_check_(fmt, NULL);
     if (r != OVHIP_OK) return r;
-    if (!d_base || !n_slots) return OVHIP_EINVAL;
-    /* the size the stream outputs: its output scale's, else its pictures' */
-    const int scaled = s->post.kind == OVHIP_POST_SCALE;
-    const size_t need = ovhip_surface_bytes(scaled ? s->post.out_w : s->cfg.w, scaled ? s->post.out_h : s->cfg.h, win, fmt);
-    if (!need || bytes_per_picture < need) return OVHIP_EINVAL;
-    s->surf_on = 1; s->surf_fmt = *fmt; s->surf_base = (char *)d_base; s->surf_bpp = bytes_per_picture; s->surf_slots = n_slots;
-    memset(&s->surf_win, 0, sizeof(s->surf_win));
-    if (win) s->surf_win = *win;
+    out_size(s, &w, &h);
+    if (slot_buf_set(&s->surf_buf, d_base, bytes_per_picture, n_slots, ovhip_surface_bytes(w, h, win, fmt)) != OVHIP_OK) return OVHIP_EINVAL;
+    s->surf_on = 1; s->surf_fmt = *fmt; s->surf_win = win ? *win : (ovhip_window){ 0, 0, 0, 0 };
     return OVHIP_OK;
 }
 
@@ -613,13 +620,13 @@ ovhip_stream_set_mvfield_output(ovhip_stream *s, const ovhip_mvfield_format *fmt
     const int r = ovhip_mvfield_dst_check_(fmt, d_vec_base, vec_bytes_per_picture * n_slots, d_info_base, info_bytes_per_picture * n_slots, NULL);
     if (r != OVHIP_OK) return r;
     size_t need_info = 0;
-    const size_t need_vec = ovhip_mvfield_bytes(s->cfg.w, s->cfg.h, fmt, &need_info);
+    const size_t need_vec = ovhip_mvfield_bytes(s->cfg.w, s->cfg.h, fmt, &need_info);       /* (the motion is the decoded picture's: no output scale) */
     if (!need_vec) return OVHIP_EINVAL;
     const size_t es = fmt->dtype == OVHIP_MVF_F16 ? 2 : 4;
-    if (d_vec_base && (vec_bytes_per_picture < need_vec || vec_bytes_per_picture % es)) return OVHIP_EINVAL;
-    if (d_info_base && (info_bytes_per_picture < need_info || info_bytes_per_picture % 4)) return OVHIP_EINVAL;
-    s->mvf_on = 1; s->mvf_fmt = *fmt; s->mvf_slots = n_slots;
-    s->mvf_vec = (char *)d_vec_base; s->mvf_vec_bpp = vec_bytes_per_picture; s->mvf_info = (char *)d_info_base; s->mvf_info_bpp = info_bytes_per_picture;
+    slot_buf vec = { NULL, vec_bytes_per_picture, n_slots }, info = { NULL, info_bytes_per_picture, n_slots };      /* (either may be absent) */
+    if (d_vec_base && (slot_buf_set(&vec, d_vec_base, vec_bytes_per_picture, n_slots, need_vec) != OVHIP_OK || vec_bytes_per_picture % es)) return OVHIP_EINVAL;
+    if (d_info_base && (slot_buf_set(&info, d_info_base, info_bytes_per_picture, n_slots, need_info) != OVHIP_OK || info_bytes_per_picture % 4)) return OVHIP_EINVAL;
+    s->mvf_on = 1; s->mvf_fmt = *fmt; s->mvf_vec = vec; s->mvf_info = info;
     return OVHIP_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <string.h>
 #include "ovvc_hip.h"
 #include "ovvc_dpb_priv.h"
+#include "ovvc_outdst_priv.h"
 
 #define SURF_MAX_SIZE 16384
 
@@ -37,9 +38,7 @@ surface_layout(int32_t w, int32_t h, const ovhip_window *win, const ovhip_surfac
     const int r = ovhip_surface_format_check_(fmt, why);
     if (r != OVHIP_OK) return r;
     if (w <= 0 || h <= 0 || (w & 1) || (h & 1) || w > SURF_MAX_SIZE || h > SURF_MAX_SIZE) { *why = "sizes must be positive, even and at most 16384"; return OVHIP_EINVAL; }
-    const int32_t l = win ? win->offset_lft : 0, rg = win ? win->offset_rgt : 0, a = win ? win->offset_abv : 0, b = win ? win->offset_blw : 0;
-    p->x0 = 2 * l; p->y0 = 2 * a; p->W = w - 2 * (l + rg); p->H = h - 2 * (a + b);
-    if (p->W <= 0 || p->H <= 0) { *why = "the window leaves nothing"; return OVHIP_EINVAL; }
+    if (!ovhip_out_window_(w, h, win, &p->x0, &p->y0, &p->W, &p->H)) { *why = "the window leaves nothing"; return OVHIP_EINVAL; }
     p->es = is_16bit(fmt->format) ? 2 : 1;
     p->semi = is_semi(fmt->format);
     p->n_planes = p->semi ? 2 : 3;
@@ -71,12 +70,6 @@ ovhip_surface_bytes(int32_t w, int32_t h, const ovhip_window *win, const ovhip_s
     return surface_layout(w, h, win, fmt, &p, &why) == OVHIP_OK ? p.bytes : 0;
 }
 
-static int
-ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
 int
 ovhip_surface_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, const void *dst, size_t dst_bytes,
                          ovhip_surface_plan_ *plan, const char **why)
@@ -90,16 +83,12 @@ ovhip_surface_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ov
     const size_t bytes = plan->bytes;
     plan->bytes = 0;
     if (!dst) { *why = "null destination"; return OVHIP_EINVAL; }
-    if (!pic->y || !pic->cb || !pic->cr) { *why = "missing plane"; return OVHIP_EINVAL; }
-    if (pic->stride_y < pic->w || pic->stride_c < pic->w / 2) { *why = "stride below the width"; return OVHIP_EINVAL; }
-    if ((uintptr_t)dst & (uintptr_t)(plan->es - 1)) { *why = "destination not aligned to its element"; return OVHIP_EINVAL; }
-    plan->bytes = bytes;
-    if (dst_bytes < bytes) { *why = "destination too small"; return OVHIP_EINVAL; }
-    const size_t ny = ((size_t)(pic->h - 1) * (size_t)pic->stride_y + (size_t)pic->w) * 2;
-    const size_t nc = ((size_t)(pic->h / 2 - 1) * (size_t)pic->stride_c + (size_t)(pic->w / 2)) * 2;
-    if (ranges_overlap(dst, bytes, pic->y, ny) || ranges_overlap(dst, bytes, pic->cb, nc) || ranges_overlap(dst, bytes, pic->cr, nc)) {
-        *why = "destination overlaps the picture"; return OVHIP_EINVAL;
-    }
+    OVHIP_OUT_REFUSE_(ovhip_out_why_planes_(pic));
+    OVHIP_OUT_REFUSE_(ovhip_out_why_strides_(pic));
+    OVHIP_OUT_REFUSE_(ovhip_out_why_unaligned_(dst, plan->es));                    /* (the alignment before the size: this plan's order) */
+    plan->bytes = bytes;                                                           /* (from here on: the launcher's message quotes it) */
+    OVHIP_OUT_REFUSE_(ovhip_out_why_small_(dst_bytes, bytes));
+    OVHIP_OUT_REFUSE_(ovhip_out_why_overlap_(pic, dst, bytes));
     *why = "";
     return OVHIP_OK;
 }

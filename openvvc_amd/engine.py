@@ -26,23 +26,38 @@ def rgb_shape(fmt: capi.RgbFormat, w: int, h: int, window=(0, 0, 0, 0)) -> tuple
     return (3, H, W) if fmt.layout == capi.RGB_PLANAR else (H, W, 3)
 
 
+def _device_tensor(tensor, what: str, dtypes: tuple, shape: "tuple | None" = None, need: "int | None" = None, slots: bool = False) -> "tuple[int, int, int]":
+    """(data_ptr, bytes of one slot, slots) of a torch tensor on the device that is to take `what` -- one, or with `slots` one per index of
+    its first dimension -- after checking device, dtype (one of `dtypes`) and contiguity, then either the exact `shape` of a slot or at
+    least `need` bytes in a slot.  The one place torch is more than a test import."""
+    import torch
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise EngineError(f"{what}: the destination must be a torch tensor on the device")
+    if tensor.dtype not in dtypes:
+        raise EngineError(f"{what}: tensor dtype {tensor.dtype}, the format takes {dtypes}")
+    if not tensor.is_contiguous():
+        raise EngineError(f"{what}: the destination tensor must be contiguous")
+    if slots and tensor.ndim < 2:
+        raise EngineError(f"{what}: a tensor of slots has them as its first dimension")
+    n = int(tensor.shape[0]) if slots else 1
+    if shape is not None:
+        if tuple(tensor.shape[1:] if slots else tensor.shape) != tuple(shape):
+            raise EngineError(f"{what}: tensor shape {tuple(tensor.shape)}, the output is {'[slots] + ' if slots else ''}{tuple(shape)}")
+        return tensor.data_ptr(), int(np.prod(shape, dtype=np.int64)) * tensor.element_size(), n
+    per = tensor.numel() * tensor.element_size() // n if n else 0
+    if not need or per < need:
+        raise EngineError(f"{what}: {per} bytes per picture, the output needs {need}")
+    return tensor.data_ptr(), per, n
+
+
 def _rgb_tensor(tensor, fmt: capi.RgbFormat, shape: tuple, n: "int | None" = None) -> "tuple[int, int]":
-    """(data_ptr, bytes per picture) of a torch tensor on the device that is to take RGB pictures of `shape` (n of them, one after the
-    other, with n given) -- after checking device, dtype, contiguity and shape.  The one place torch is more than a test import."""
+    """(data_ptr, bytes per picture) of a torch tensor that is to take RGB pictures of `shape` (n of them, one after the other, with n given)"""
     import torch
     want = {capi.RGB_U8: torch.uint8, capi.RGB_U16: torch.uint16, capi.RGB_F16: torch.float16, capi.RGB_F32: torch.float32}.get(fmt.dtype)
-    if want is None:
-        raise EngineError(f"rgb output: dtype {fmt.dtype}")
-    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
-        raise EngineError("rgb output: the destination must be a torch tensor on the device")
-    if tensor.dtype != want:
-        raise EngineError(f"rgb output: tensor dtype {tensor.dtype}, the format asks for {want}")
-    if not tensor.is_contiguous():
-        raise EngineError("rgb output: the destination tensor must be contiguous")
-    full = tuple(shape) if n is None else (n, *shape)
-    if tuple(tensor.shape) != full:
-        raise EngineError(f"rgb output: tensor shape {tuple(tensor.shape)}, the pictures need {full}")
-    return tensor.data_ptr(), shape[0] * shape[1] * shape[2] * tensor.element_size()
+    ptr, per, got = _device_tensor(tensor, "rgb output", (want,) if want is not None else (), shape=shape, slots=n is not None)
+    if n is not None and got != n:
+        raise EngineError(f"rgb output: {got} slots, {n} expected")
+    return ptr, per
 
 
 def surface_format(format: int = capi.SURF_NV12, rounding: int = capi.SURF_ROUND, pitch_y: int = 0, pitch_c: int = 0, offset_c=(0, 0)) -> capi.SurfaceFormat:
@@ -54,23 +69,10 @@ def surface_format(format: int = capi.SURF_NV12, rounding: int = capi.SURF_ROUND
 
 
 def _surface_tensor(tensor, fmt: capi.SurfaceFormat, need: int, slots: bool = False) -> "tuple[int, int, int]":
-    """(data_ptr, bytes of one slot, slots) of a torch tensor on the device that is to take surfaces of `need` bytes -- one, or with
-    `slots` one per index of its first dimension -- after checking device, dtype, contiguity and size"""
+    """(data_ptr, bytes of one slot, slots) of a torch tensor that is to take surfaces of `need` bytes"""
     import torch
-    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
-        raise EngineError("surface output: the destination must be a torch tensor on the device")
     allowed = (torch.uint8,) if capi.SURF_ELEM_BYTES.get(fmt.format) == 1 else (torch.uint8, torch.int16, torch.uint16)
-    if tensor.dtype not in allowed:
-        raise EngineError(f"surface output: tensor dtype {tensor.dtype}, the format takes {allowed}")
-    if not tensor.is_contiguous():
-        raise EngineError("surface output: the destination tensor must be contiguous")
-    if slots and tensor.ndim < 2:
-        raise EngineError("surface output: a stream's tensor has the slots as its first dimension")
-    n = int(tensor.shape[0]) if slots else 1
-    per = tensor.numel() * tensor.element_size() // n if n else 0
-    if not need or per < need:
-        raise EngineError(f"surface output: {per} bytes per picture, the surface needs {need}")
-    return tensor.data_ptr(), per, n
+    return _device_tensor(tensor, "surface output", allowed, need=need, slots=slots)
 
 
 def mvfield_format(dtype: int = capi.MVF_I32, layout: int = capi.MVF_PLANAR, vectors: int = capi.MVF_UNIT) -> capi.MvfieldFormat:
@@ -84,26 +86,6 @@ def mvfield_shape(fmt: capi.MvfieldFormat, w: int, h: int) -> "tuple[tuple, tupl
     return ((h4, w4, 4) if fmt.layout == capi.MVF_CELLS else (4, h4, w4)), (h4, w4)
 
 
-def _mvfield_tensor(tensor, dtypes: tuple, shape: tuple, what: str, slots: bool = False) -> "tuple[int, int, int]":
-    """(data_ptr, bytes of one slot, slots) of a torch tensor on the device that is to take `what` of a motion field -- one of `shape`, or
-    with `slots` one per index of its first dimension -- after checking device, dtype, contiguity and shape"""
-    import torch
-    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
-        raise EngineError(f"motion field output: the {what} must go to a torch tensor on the device")
-    if tensor.dtype not in dtypes:
-        raise EngineError(f"motion field output: {what} tensor of dtype {tensor.dtype}, the format takes {dtypes}")
-    if not tensor.is_contiguous():
-        raise EngineError(f"motion field output: the {what} tensor must be contiguous")
-    got = tuple(tensor.shape[1:]) if slots else tuple(tensor.shape)
-    if got != tuple(shape) or (slots and tensor.ndim != len(shape) + 1):
-        raise EngineError(f"motion field output: {what} tensor of shape {tuple(tensor.shape)}, the field is {'[slots] + ' if slots else ''}{tuple(shape)}")
-    n = int(tensor.shape[0]) if slots else 1
-    per = tensor.element_size()
-    for d in shape:
-        per *= d
-    return tensor.data_ptr(), per, n
-
-
 def _mvfield_dsts(vec, info, fmt: capi.MvfieldFormat, w: int, h: int, vec_bytes, info_bytes, slots: bool = False):
     """(vec ptr, vec bytes, info ptr, info bytes, slots) of a pair of destinations, each a torch tensor (checked against the field's
     shape), a device address with its byte count, or None"""
@@ -114,16 +96,55 @@ def _mvfield_dsts(vec, info, fmt: capi.MvfieldFormat, w: int, h: int, vec_bytes,
     else:
         import torch
         tdt = {capi.MVF_I32: (torch.int32,), capi.MVF_F32: (torch.float32,), capi.MVF_F16: (torch.float16,)}.get(fmt.dtype, ())
-        vp, vb, n = _mvfield_tensor(vec, tdt, vshape, "vectors", slots)
+        vp, vb, n = _device_tensor(vec, "motion field vectors", tdt, shape=vshape, slots=slots)
     if info is None or isinstance(info, int):
         ip, ib = info or 0, info_bytes or 0
     else:
         import torch
-        ip, ib, ni = _mvfield_tensor(info, (torch.int32, torch.uint32), ishape, "info", slots)
+        ip, ib, ni = _device_tensor(info, "motion field info", (torch.int32, torch.uint32), shape=ishape, slots=slots)
         if n is not None and ni != n:
             raise EngineError(f"motion field output: {n} slots of vectors, {ni} of info")
         n = ni
     return vp, vb, ip, ib, n
+
+
+def _set_output(owner, kind: str, fmt, dsts: list, window=None, n_slots: "int | None" = None, check: bool = True) -> int:
+    """The one flow behind Frame.set_*_output and Stream.set_*_output (kind: "rgb", "surface" or "mvfield").  dsts: the (destination,
+    bytes) pairs the C setter takes, each destination a torch tensor on the device (checked against what the output needs at the size
+    the owner outputs, and kept alive by the owner), a device address with its bytes, or -- the motion field's only -- None.  A
+    stream's tensors carry the slots as their first dimension; with addresses n_slots counts.  fmt None: off."""
+    stream = isinstance(owner, Stream)
+    who = "stream" if stream else "frame"
+    fn, handle = getattr(owner.lib, f"ovhip_{who}_set_{kind}_output"), owner.s if stream else owner.f
+    if fmt is None:
+        return fn(handle, None, *([None] if window is not None else []), *[a for _ in dsts for a in (None, 0)], *([0] if stream else []))
+    w, h = (owner.cfg.w, owner.cfg.h) if stream else (owner.w, owner.h)
+    win = capi.Window(*window) if window is not None else None
+    n = None
+    if kind == "mvfield":                                  # (the motion is the decoded picture's: no output scale)
+        (vec, vb), (info, ib) = dsts
+        vp, vb, ip, ib, n = _mvfield_dsts(vec, info, fmt, w, h, vb, ib, slots=stream)
+        dsts, keep = [(vp, vb), (ip, ib)], (vec, info)
+    elif not isinstance(dsts[0][0], int):
+        keep = dsts[0][0]
+        w, h = getattr(owner, "_out_size", None) or (w, h)
+        if kind == "rgb":
+            n = (int(keep.shape[0]) if getattr(keep, "ndim", 0) == 4 else 0) if stream else None
+            dsts = [_rgb_tensor(keep, fmt, rgb_shape(fmt, w, h, window), n)]
+        else:
+            ptr, per, n = _surface_tensor(keep, fmt, owner.lib.ovhip_surface_bytes(w, h, C.byref(win), C.byref(fmt)), slots=stream)
+            dsts = [(ptr, per)]
+    else:
+        keep = None
+    if keep is not None and stream:
+        owner._keep.append(keep)                           # (as long as the stream)
+    elif keep is not None:
+        setattr(owner, f"_{kind}_keep", keep)              # (until the frame's next setting of this kind)
+    r = fn(handle, C.byref(fmt), *([C.byref(win)] if win is not None else []), *[a for p, b in dsts for a in (C.c_void_p(p) if p else None, b or 0)],
+           *([n if n is not None else (n_slots or 0)] if stream else []))
+    if check and r:
+        raise EngineError(f"{who}_set_{kind}_output: {r}")
+    return r
 
 
 class Context:
@@ -1040,51 +1061,20 @@ class Frame:
     def set_rgb_output(self, dst, fmt: "capi.RgbFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_rgb_output: the NEXT picture completed is also written as RGB into `dst` -- a torch tensor on the device of
         shape (3, H, W) / (H, W, 3) for the size the frame outputs (checked here), or a device address with `nbytes`; fmt None: off"""
-        if fmt is None:
-            return self.lib.ovhip_frame_set_rgb_output(self.f, None, None, None, 0)
-        if isinstance(dst, int):
-            ptr = dst
-        else:
-            w, h = getattr(self, "_out_size", None) or (self.w, self.h)
-            ptr, nbytes = _rgb_tensor(dst, fmt, rgb_shape(fmt, w, h, window))
-            self._rgb_keep = dst
-        win = capi.Window(*window)
-        r = self.lib.ovhip_frame_set_rgb_output(self.f, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, nbytes or 0)
-        if check and r:
-            raise EngineError(f"frame_set_rgb_output: {r}")
-        return r
+        return _set_output(self, "rgb", fmt, [(dst, nbytes)], window, check=check)
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_surface_output: the NEXT picture completed is also written as a surface into `dst` -- a contiguous torch
         tensor on the device (uint8, or int16 / uint16 for the 16-bit formats) of at least the surface's bytes for the size the frame
         outputs (checked here), or a device address with `nbytes`; fmt None: off"""
-        if fmt is None:
-            return self.lib.ovhip_frame_set_surface_output(self.f, None, None, None, 0)
-        win = capi.Window(*window)
-        if isinstance(dst, int):
-            ptr = dst
-        else:
-            w, h = getattr(self, "_out_size", None) or (self.w, self.h)
-            ptr, nbytes, _n = _surface_tensor(dst, fmt, self.lib.ovhip_surface_bytes(w, h, C.byref(win), C.byref(fmt)))
-            self._surface_keep = dst
-        r = self.lib.ovhip_frame_set_surface_output(self.f, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, nbytes or 0)
-        if check and r:
-            raise EngineError(f"frame_set_surface_output: {r}")
-        return r
+        return _set_output(self, "surface", fmt, [(dst, nbytes)], window, check=check)
 
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None,
                            check: bool = True) -> int:
         """ovhip_frame_set_mvfield_output: the motion field of the NEXT picture completed goes to `vec` and `info` -- torch tensors on
         the device of mvfield_shape() for the frame's size (checked here, kept alive here), device addresses with their byte counts,
         or None for a destination that is not wanted; fmt None: off"""
-        if fmt is None:
-            return self.lib.ovhip_frame_set_mvfield_output(self.f, None, None, 0, None, 0)
-        vp, vb, ip, ib, _n = _mvfield_dsts(vec, info, fmt, self.w, self.h, vec_bytes, info_bytes)
-        self._mvfield_keep = (vec, info)
-        r = self.lib.ovhip_frame_set_mvfield_output(self.f, C.byref(fmt), C.c_void_p(vp) if vp else None, vb, C.c_void_p(ip) if ip else None, ib)
-        if check and r:
-            raise EngineError(f"frame_set_mvfield_output: {r}")
-        return r
+        return _set_output(self, "mvfield", fmt, [(vec, vec_bytes), (info, info_bytes)], check=check)
 
     def job(self) -> "Job":
         """the frame's own job as an engine.Job view (not owned)"""
@@ -1157,20 +1147,7 @@ class Stream:
         """ovhip_stream_set_rgb_output: picture idx of the following runs is also written as RGB into slot idx % n of `dst` -- a torch
         tensor on the device of shape (n, 3, H, W) / (n, H, W, 3) for the size the stream outputs (checked here, kept alive here), or
         a device address with bytes_per_picture and n_slots; fmt None: off"""
-        if fmt is None:
-            return self.lib.ovhip_stream_set_rgb_output(self.s, None, None, None, 0, 0)
-        if isinstance(dst, int):
-            ptr = dst
-        else:
-            w, h = getattr(self, "_out_size", None) or (self.cfg.w, self.cfg.h)
-            n_slots = int(dst.shape[0]) if getattr(dst, "ndim", 0) == 4 else 0
-            ptr, bytes_per_picture = _rgb_tensor(dst, fmt, rgb_shape(fmt, w, h, window), n_slots)
-            self._keep.append(dst)
-        win = capi.Window(*window)
-        r = self.lib.ovhip_stream_set_rgb_output(self.s, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, bytes_per_picture or 0, n_slots or 0)
-        if check and r:
-            raise EngineError(f"stream_set_rgb_output: {r}")
-        return r
+        return _set_output(self, "rgb", fmt, [(dst, bytes_per_picture)], window, n_slots, check)
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
                            n_slots: "int | None" = None, check: bool = True) -> int:
@@ -1178,34 +1155,14 @@ class Stream:
         a contiguous torch tensor on the device whose first dimension is the slot count and whose slots hold at least the surface's
         bytes for the size the stream outputs (checked here, kept alive here), or a device address with bytes_per_picture and n_slots;
         fmt None: off"""
-        if fmt is None:
-            return self.lib.ovhip_stream_set_surface_output(self.s, None, None, None, 0, 0)
-        win = capi.Window(*window)
-        if isinstance(dst, int):
-            ptr = dst
-        else:
-            w, h = getattr(self, "_out_size", None) or (self.cfg.w, self.cfg.h)
-            ptr, bytes_per_picture, n_slots = _surface_tensor(dst, fmt, self.lib.ovhip_surface_bytes(w, h, C.byref(win), C.byref(fmt)), slots=True)
-            self._keep.append(dst)
-        r = self.lib.ovhip_stream_set_surface_output(self.s, C.byref(fmt), C.byref(win), C.c_void_p(ptr) if ptr else None, bytes_per_picture or 0, n_slots or 0)
-        if check and r:
-            raise EngineError(f"stream_set_surface_output: {r}")
-        return r
+        return _set_output(self, "surface", fmt, [(dst, bytes_per_picture)], window, n_slots, check)
 
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes_per_picture: "int | None" = None,
                            info_bytes_per_picture: "int | None" = None, n_slots: "int | None" = None, check: bool = True) -> int:
         """ovhip_stream_set_mvfield_output: the motion field of picture idx of the following runs goes to slot idx % n of `vec` and
         `info` -- torch tensors on the device whose first dimension is the slot count and whose slots have mvfield_shape() for the
         stream's size (checked here, kept alive here), device addresses with bytes per picture and n_slots, or None; fmt None: off"""
-        if fmt is None:
-            return self.lib.ovhip_stream_set_mvfield_output(self.s, None, None, 0, None, 0, 0)
-        vp, vb, ip, ib, n = _mvfield_dsts(vec, info, fmt, self.cfg.w, self.cfg.h, vec_bytes_per_picture, info_bytes_per_picture, slots=True)
-        self._keep.append((vec, info))
-        r = self.lib.ovhip_stream_set_mvfield_output(self.s, C.byref(fmt), C.c_void_p(vp) if vp else None, vb, C.c_void_p(ip) if ip else None, ib,
-                                                     n if n is not None else (n_slots or 0))
-        if check and r:
-            raise EngineError(f"stream_set_mvfield_output: {r}")
-        return r
+        return _set_output(self, "mvfield", fmt, [(vec, vec_bytes_per_picture), (info, info_bytes_per_picture)], n_slots=n_slots, check=check)
 
     def set_picture_hashes(self, method: int, n_planes: int = 3, expected=None, check: bool = True) -> int:
         """ovhip_stream_set_picture_hashes; expected: a (capi.PicHashValue * n_total) array (kept alive here) or None"""

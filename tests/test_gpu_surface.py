@@ -11,7 +11,7 @@ import spec_film_grain as sf
 import spec_pp_scale as spp
 import spec_rgb as sr
 import spec_surface as ss
-from openvvc_amd import capi, engine, gop
+from openvvc_amd import capi, engine, gop, synth
 from test_film_grain_cpu import c_params
 from test_gpu_pic_hash import _frame_case
 from test_gpu_stream import _Keep, _contents, _jobs_for, _make_contents, _stream_pics
@@ -356,6 +356,65 @@ def test_frame_writes_rgb_and_surface_of_one_submit(built_lib):
     assert raw_surf[:need].tobytes() == want_surf.tobytes() and (raw_surf[need:] == ss.FILL).all()
     assert all(np.array_equal(a, b) for a, b in zip(published(0x100), dec))
     d_rgb.free(); d_surf.free()
+    f.close(); ctx.close(); dpb.close()
+
+
+@pytest.mark.parametrize("via", ["submit", "band"])
+@pytest.mark.parametrize("post", ["grain", "scale"])
+def test_frame_outputs_of_one_picture_share_the_post_processed_picture(built_lib, post, via):
+    """RGB, a surface and a PACKED delivery of ONE picture, behind film grain or an output scale: each equals, byte for byte, what the
+    picture gives when that output is the only one set (the post-process step runs once, all three read its picture), and a picture
+    with nothing set leaves all three destinations as they were"""
+    w, h = 72, 40
+    wl = synth.make_workload(w, h, 77, tools=synth.INTRA_TOOLS, intra_frac=1.0, calllog=True)
+    lib = built_lib
+    dpb = engine.Dpb((0,))
+    ctx = engine.Context(0)
+    f = engine.Frame(dpb, 0, w, h)
+    params = engine.Job.make_params(_Keep(), wl)
+    if post == "grain":
+        f.set_film_grain(c_params(sf.make_sei()), 9)
+        ow, oh = w, h
+    else:
+        ow, oh = 144, 80
+        f.set_output_scale(ow, oh)
+    rgb_fmt = engine.rgb_format(1, 0, 0, capi.RGB_U8, capi.RGB_PLANAR)
+    surf_fmt = engine.surface_format(capi.SURF_NV12, pitch_y=ow + 24, pitch_c=ow + 8)      # (pitches above the row's bytes)
+    win = capi.Window(0, 0, 0, 0)
+    n_rgb, n_surf = 3 * ow * oh, lib.ovhip_surface_bytes(ow, oh, C.byref(win), C.byref(surf_fmt))
+    n_packed = lib.ovhip_output_bytes(ow, oh, C.byref(win))
+    assert n_surf == (ow + 24) * oh + (ow + 8) * (oh // 2 - 1) + ow and n_packed == ow * oh * 3
+
+    def picture(key, rgb, surf, packed):
+        """one picture with the outputs named; what the three destinations hold after it (sentinel bytes where nothing was written)"""
+        d_rgb, d_surf = _a5(ctx, n_rgb + GUARD), _a5(ctx, n_surf + GUARD)
+        host = np.full(n_packed + GUARD, ss.FILL, np.uint8)
+        out = capi.FrameOutput()
+        out.mode, out.window, out.packed = (capi.OUT_PACKED if packed else capi.OUT_NONE), win, host.ctypes.data
+        if rgb:
+            f.set_rgb_output(d_rgb.ptr.value, rgb_fmt, nbytes=n_rgb)
+        if surf:
+            f.set_surface_output(d_surf.ptr.value, surf_fmt, nbytes=n_surf)
+        f.begin(key)
+        f.recorder().replay(wl.calllog)
+        if via == "submit":
+            assert f.submit(params, out=out) == 0
+        else:
+            assert lib.ovhip_frame_set_band_mode(f.f, 1) == 0
+            assert lib.ovhip_frame_band(f.f, C.byref(params), h, 1, C.byref(out)) == 1, lib.ovhip_frame_last_error(f.f)
+            assert lib.ovhip_frame_set_band_mode(f.f, 0) == 0
+        got = d_rgb.download().tobytes(), d_surf.download().tobytes(), host.tobytes()
+        d_rgb.free(); d_surf.free()
+        return got
+
+    untouched = tuple(bytes([ss.FILL]) * (n + GUARD) for n in (n_rgb, n_surf, n_packed))
+    all_three = picture(0x100, True, True, True)
+    assert picture(0x101, False, False, False) == untouched, "the settings were the first picture's"
+    alone = picture(0x102, True, False, False), picture(0x103, False, True, False), picture(0x104, False, False, True)
+    for k, name in enumerate(("RGB", "surface", "PACKED")):
+        assert all_three[k] != untouched[k] and all_three[k][-GUARD:] == untouched[k][-GUARD:], name
+        assert all_three[k] == alone[k][k], name
+        assert all(alone[k][j] == untouched[j] for j in range(3) if j != k), name
     f.close(); ctx.close(); dpb.close()
 
 

@@ -1,4 +1,4 @@
-/* tools/mvfield_check -- the host half of the motion field output (openvvc_amd/csrc/ovvc_mvfield.c) as a stand-alone program:
+/* tools/host_check -- the host half of the motion field output (openvvc_amd/csrc/ovvc_mvfield.c) as a stand-alone program:
  * ovhip_mvfield_host over generated unit lists that tile pictures of several sizes (sizes that are no multiple of 4 or of 16 among them,
  * so that units are clipped at the right and bottom edges) with units of all five lists, in every dtype, layout and vectors setting,
  * each destination alone and both; every list, the side arena, the refined array and every destination in a heap block of exactly its

@@ -1,16 +1,13 @@
-/* tools/rgb_check -- the host half of the RGB output (openvvc_amd/csrc/ovvc_rgb.c) as a stand-alone program: ovhip_rgb_host over the
+/* tools/host_check -- the host half of the RGB output (openvvc_amd/csrc/ovvc_rgb.c) as a stand-alone program: ovhip_rgb_host over the
  * sizes, windows, chroma locations, dtypes and layouts of tests/test_rgb_cpu.py, every plane and every destination in a heap block of
  * exactly its size (strides equal to the widths), so that a read or a write one sample outside is the sanitizer's to see; and the
- * refusals, which must write nothing.  `make asan`.  Host code only. */
+ * refusals, which must write nothing; and of a destination with two faults at once, which of them the plan names.  `make asan`.  Host
+ * code only. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "ovvc_hip.h"
-
-/* ovvc_rgb.c's convenience calls three device entry points; this program has no device and never gets there */
-int ovhip_rgb_launch(ovhip_ctx *c, const ovhip_pic *p, const ovhip_window *w, const ovhip_rgb_format *f, void *d, size_t n) { (void)c; (void)p; (void)w; (void)f; (void)d; (void)n; return OVHIP_ENODEV; }
-int ovhip_rgb_scratch_(ovhip_ctx *c, size_t n, void **d) { (void)c; (void)n; (void)d; return OVHIP_ENODEV; }
-int ovhip_d2h(ovhip_ctx *c, void *h, const void *d, size_t n) { (void)c; (void)h; (void)d; (void)n; return OVHIP_ENODEV; }
+#include "ovvc_dpb_priv.h"
 
 static uint32_t rng = 12345;
 static uint16_t next10(void) { rng = rng * 1664525u + 1013904223u; return (uint16_t)((rng >> 12) & 1023); }
@@ -24,9 +21,25 @@ plane(int w, int h)
     return p;
 }
 
+/* a destination both too small and not aligned to its element: the RGB plan names the size (the surface plan the alignment) */
+static int
+two_faults(void)
+{
+    static uint16_t y[8 * 8], c[4 * 4], buf[3 * 8 * 8 + 1];
+    const ovhip_pic pic = { y, c, c, 8, 8, 8, 4 };
+    const ovhip_rgb_format fmt = { 1, 0, 0, OVHIP_RGB_U16, OVHIP_RGB_PLANAR, { 0, 0, 0 } };
+    const size_t n = ovhip_rgb_bytes(8, 8, NULL, &fmt);
+    ovhip_rgb_plan_ plan;
+    const char *why = NULL;
+    const int r = ovhip_rgb_plan_make_(&pic, NULL, &fmt, (char *)buf + 1, n - 1, &plan, &why);
+    if (r != OVHIP_EINVAL || !why || strcmp(why, "destination too small")) { fprintf(stderr, "two faults: %d, \"%s\"\n", r, why ? why : "(null)"); return 1; }
+    return 0;
+}
+
 int
 main(void)
 {
+    if (two_faults()) return 1;
     static const int sizes[][2] = { { 8, 8 }, { 20, 12 }, { 24, 8 }, { 72, 40 } };
     static const ovhip_window wins[] = { { 0, 0, 0, 0 }, { 1, 0, 0, 1 }, { 0, 3, 2, 0 } };
     static const int matrices[] = { 1, 5, 6, 9 };

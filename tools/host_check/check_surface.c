@@ -1,12 +1,13 @@
-/* tools/surface_check -- the host half of the surface output (openvvc_amd/csrc/ovvc_surface.c) as a stand-alone program:
+/* tools/host_check -- the host half of the surface output (openvvc_amd/csrc/ovvc_surface.c) as a stand-alone program:
  * ovhip_surface_host over the sizes, windows, formats, roundings and layouts (tight, and with gaps) of tests/test_surface_cpu.py,
  * every plane and every destination in a heap block of exactly its size (strides equal to the widths), so that a read or a write one
- * sample outside is the sanitizer's to see; the gaps of a layout must stay as they were; and the refusals, which must write nothing.
- * `make asan`.  Host code only. */
+ * sample outside is the sanitizer's to see; the gaps of a layout must stay as they were; the refusals, which must write nothing; and of
+ * a destination with two faults at once, which of them the plan names.  `make asan`.  Host code only. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "ovvc_hip.h"
+#include "ovvc_dpb_priv.h"
 
 static uint32_t rng = 12345;
 static uint16_t next10(void) { rng = rng * 1664525u + 1013904223u; return (uint16_t)((rng >> 12) & 1023); }
@@ -25,9 +26,30 @@ plane(int w, int h)
 static int is16(int f) { return f == OVHIP_SURF_P010 || f == OVHIP_SURF_I010; }
 static int semi(int f) { return f == OVHIP_SURF_NV12 || f == OVHIP_SURF_P010; }
 
+/* a destination both too small and not aligned to its element: the surface plan names the alignment (the RGB plan the size), and
+ * quotes no size for it */
+static int
+two_faults(void)
+{
+    static uint16_t y[8 * 8], c[4 * 4], buf[8 * 8 + 8 * 4 + 1];
+    const ovhip_pic pic = { y, c, c, 8, 8, 8, 4 };
+    ovhip_surface_format fmt;
+    memset(&fmt, 0, sizeof(fmt));
+    fmt.format = OVHIP_SURF_P010;
+    const size_t n = ovhip_surface_bytes(8, 8, NULL, &fmt);
+    ovhip_surface_plan_ plan;
+    const char *why = NULL;
+    const int r = ovhip_surface_plan_make_(&pic, NULL, &fmt, (char *)buf + 1, n - 1, &plan, &why);
+    if (r != OVHIP_EINVAL || !why || strcmp(why, "destination not aligned to its element") || plan.bytes) {
+        fprintf(stderr, "two faults: %d, \"%s\", %zu bytes\n", r, why ? why : "(null)", plan.bytes); return 1;
+    }
+    return 0;
+}
+
 int
 main(void)
 {
+    if (two_faults()) return 1;
     static const int sizes[][2] = { { 8, 8 }, { 16, 8 }, { 20, 12 }, { 34, 18 }, { 72, 40 }, { 136, 72 }, { 264, 136 } };
     static const ovhip_window wins[] = { { 0, 0, 0, 0 }, { 1, 0, 0, 1 }, { 0, 1, 1, 0 }, { 1, 1, 1, 1 } };
     static const int modes[][2] = { { OVHIP_SURF_NV12, 0 }, { OVHIP_SURF_NV12, 1 }, { OVHIP_SURF_P010, 0 }, { OVHIP_SURF_I420, 0 }, { OVHIP_SURF_I420, 1 }, { OVHIP_SURF_I010, 0 } };
