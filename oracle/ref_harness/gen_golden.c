@@ -120,6 +120,47 @@ tt_slots(int l2w, int l2h, int max_tb, int depth, int base, int *out, int *n)
     out[(*n)++] = base;
 }
 
+/* what gen_itx and gen_itx_cells share: the prediction picture, the decoder state of one case, the CTU buffer before a case */
+static void
+itx_fill_pred(uint16_t *pred_y, uint16_t *pred_cb, uint16_t *pred_cr)
+{
+    fill_plane(pred_y, 128, 128, 128);
+    fill_plane(pred_cb, 64, 64, 64);
+    fill_plane(pred_cr, 64, 64, 64);
+    /* make clipping at both ends reachable */
+    for (int i = 0; i < 128 * 128; i += 37) pred_y[i] = (i & 1) ? 1023 : 0;
+    for (int i = 0; i < 64 * 64; i += 29) { pred_cb[i] = (i & 1) ? 1023 : 0; pred_cr[i] = (i & 1) ? 0 : 1023; }
+}
+
+static void
+itx_set_state(OVCTUDec *c, const ovhip_tu_state *st, int c_mode)
+{
+    c->dequant_luma.qp = st->qp_y; c->dequant_cb.qp = st->qp_cb; c->dequant_cr.qp = st->qp_cr;
+    c->dequant_joint_cb_cr.qp = st->qp_jcbcr;
+    c->dequant_luma_skip.qp = st->qp_y_skip; c->dequant_cb_skip.qp = st->qp_cb_skip;
+    c->dequant_cr_skip.qp = st->qp_cr_skip; c->dequant_jcbcr_skip.qp = st->qp_jcbcr_skip;
+    c->residual_coding_l = st->dep_quant ? &residual_coding_dpq : NULL;
+    c->mts_implicit = st->mts_implicit;
+    c->sh_ts_disabled = st->sh_ts_disabled;
+    c->lmcs_info.scale_c_flag = st->lmcs_scale_c;
+    c->lmcs_info.lmcs_chroma_scale = (uint16_t)st->lmcs_chroma_scale;
+    c->intra_mode = (uint8_t)st->intra_mode;
+    c->intra_mode_c = (uint8_t)c_mode;
+    c->qp_ctx.qp_bd_offset = 12;
+}
+
+static void
+itx_load_pred(OVCTUDec *c, const uint16_t *pred_y, const uint16_t *pred_cb, const uint16_t *pred_cr)
+{
+    const struct OVBuffInfo *cb = &c->rcn_ctx.ctu_buff;
+    for (int j = 0; j < 128; ++j) memcpy(cb->y + j * cb->stride, pred_y + j * 128, 256);
+    for (int j = 0; j < 64; ++j) {
+        memcpy(cb->cb + j * cb->stride_c, pred_cb + j * 64, 128);
+        memcpy(cb->cr + j * cb->stride_c, pred_cr + j * 64, 128);
+    }
+    memset(&c->dbf_info, 0, sizeof(c->dbf_info));
+}
+
 static void
 gen_itx(const char *dir)
 {
@@ -129,12 +170,7 @@ gen_itx(const char *dir)
     uint32_t n_cases = 0;
     g_seed = 0x266;
 
-    fill_plane(pred_y, 128, 128, 128);
-    fill_plane(pred_cb, 64, 64, 64);
-    fill_plane(pred_cr, 64, 64, 64);
-    /* make clipping at both ends reachable */
-    for (int i = 0; i < 128 * 128; i += 37) pred_y[i] = (i & 1) ? 1023 : 0;
-    for (int i = 0; i < 64 * 64; i += 29) { pred_cb[i] = (i & 1) ? 1023 : 0; pred_cr[i] = (i & 1) ? 0 : 1023; }
+    itx_fill_pred(pred_y, pred_cb, pred_cr);
 
     OVCTUDec *c = ref_new_ctudec(0, 0);
     c->rcn_funcs.intra_pred_c = stub_intra_pred_c;
@@ -231,28 +267,12 @@ gen_itx(const char *dir)
                     /* ---- reference state ---- */
                     rcn_init_ict_functions_10(&c->rcn_funcs, st.ict_type, 10);
                     if (g_shim) rcn_init_functions_hip(&c->rcn_funcs, st.ict_type, 1, 0, 0, 10);   /* per slice in the decoder (slicedec.c:1462) */
-                    c->dequant_luma.qp = st.qp_y; c->dequant_cb.qp = st.qp_cb; c->dequant_cr.qp = st.qp_cr;
-                    c->dequant_joint_cb_cr.qp = st.qp_jcbcr;
-                    c->dequant_luma_skip.qp = st.qp_y_skip; c->dequant_cb_skip.qp = st.qp_cb_skip;
-                    c->dequant_cr_skip.qp = st.qp_cr_skip; c->dequant_jcbcr_skip.qp = st.qp_jcbcr_skip;
-                    c->residual_coding_l = st.dep_quant ? &residual_coding_dpq : NULL;
-                    c->mts_implicit = st.mts_implicit;
-                    c->sh_ts_disabled = st.sh_ts_disabled;
-                    c->lmcs_info.scale_c_flag = st.lmcs_scale_c;
-                    c->lmcs_info.lmcs_chroma_scale = (uint16_t)st.lmcs_chroma_scale;
-                    c->intra_mode = (uint8_t)st.intra_mode;
-                    c->intra_mode_c = (uint8_t)c_mode;
-                    c->qp_ctx.qp_bd_offset = 12;
+                    itx_set_state(c, &st, c_mode);
                     tu.cbf_mask = d.cbf_mask; tu.pos_offset = (uint16_t)pos_offset; tu.tr_skip_mask = d.tr_skip_mask;
                     tu.cu_mts_flag = d.cu_mts_flag; tu.cu_mts_idx = d.cu_mts_idx;
                     tu.lfnst_flag = d.lfnst_flag; tu.lfnst_idx = d.lfnst_idx;
 
-                    for (int j = 0; j < 128; ++j) memcpy(cb->y + j * cb->stride, pred_y + j * 128, 256);
-                    for (int j = 0; j < 64; ++j) {
-                        memcpy(cb->cb + j * cb->stride_c, pred_cb + j * 64, 128);
-                        memcpy(cb->cr + j * cb->stride_c, pred_cr + j * 64, 128);
-                    }
-                    memset(&c->dbf_info, 0, sizeof(c->dbf_info));
+                    itx_load_pred(c, pred_y, pred_cb, pred_cr);
 
                     if (g_shim && tree == 2 && d.lfnst_flag) {
                         /* derive_lfnst_mode_c's inputs as the decoder holds them: an explicit angular chroma mode */
@@ -374,6 +394,417 @@ gen_itx(const char *dir)
     gfile_buf(&g, "exp", &b_exp);
     gfile_close(&g);
     fprintf(stderr, "itx.ovg: %u cases, %zu coef int16, %zu expected samples\n", n_cases, b_coefs.n, b_exp.n);
+}
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * itx_cells_<family>_NN.ovg: tmp.rcn_tu_st / tmp.rcn_tu_c on ENUMERATED inputs (itx.ovg draws 12 / 5 cases per shape), on itx.ovg's
+ * prediction picture and in its layout (state, desc, coef_off, coef_len, exp_off, coefs, exp), cut into files below 1 MiB.
+ * A family sets up state and descriptor, writes the levels into the decoder's residual buffers at offset 0 in the reference's
+ * layout, and hands the case to icells_case. */
+struct icells {
+    const char *dir, *family;
+    int file_no;
+    uint32_t n, n_total;
+    gbuf state, desc, coff, clen, coefs, eoff, exp;
+    OVCTUDec *c;
+    uint16_t pred_y[128 * 128], pred_cb[64 * 64], pred_cr[64 * 64];
+};
+
+static void
+icells_flush(struct icells *o)
+{
+    if (!o->n) return;
+    char name[64];
+    snprintf(name, sizeof(name), "itx_cells_%s_%02d.ovg", o->family, o->file_no++);
+    gfile g = gfile_open(o->dir, name);
+    uint32_t d2[2];
+    d2[0] = 128; d2[1] = 128; gfile_array(&g, "pred_y", T_U16, o->pred_y, 2, d2);
+    d2[0] = 64; d2[1] = 64;   gfile_array(&g, "pred_cb", T_U16, o->pred_cb, 2, d2);
+    gfile_array(&g, "pred_cr", T_U16, o->pred_cr, 2, d2);
+    d2[0] = o->n; d2[1] = sizeof(ovhip_tu_state); gfile_array(&g, "state", T_U8, o->state.data, 2, d2);
+    d2[1] = sizeof(ovhip_tu_desc); gfile_array(&g, "desc", T_U8, o->desc.data, 2, d2);
+    d2[1] = 3; gfile_array(&g, "coef_off", T_U32, o->coff.data, 2, d2);
+    gfile_array(&g, "coef_len", T_U32, o->clen.data, 2, d2);
+    gfile_array(&g, "exp_off", T_U32, o->eoff.data, 2, d2);
+    gfile_buf(&g, "coefs", &o->coefs);
+    gfile_buf(&g, "exp", &o->exp);
+    gfile_close(&g);
+    fprintf(stderr, "%s: %u cases, %zu coef int16, %zu expected samples\n", name, o->n, o->coefs.n, o->exp.n);
+    o->n = 0;
+    o->state.n = o->desc.n = o->coff.n = o->clen.n = o->coefs.n = o->eoff.n = o->exp.n = 0;
+}
+
+static void
+icells_begin(struct icells *o, const char *family)
+{
+    icells_flush(o);
+    o->family = family; o->file_no = 0; o->n_total = 0;
+}
+
+/* a fresh state / descriptor: mid QPs, no tool on; the block's position walks over the CTU so that the picture's samples at 0 and
+ * 1023 fall into blocks of every family */
+static void
+icells_init(const struct icells *o, ovhip_tu_state *st, ovhip_tu_desc *d, int tree, int l2w, int l2h)
+{
+    memset(st, 0, sizeof(*st)); memset(d, 0, sizeof(*d));
+    st->qp_y = 30; st->qp_cb = 31; st->qp_cr = 33; st->qp_jcbcr = 32;
+    st->qp_y_skip = 30; st->qp_cb_skip = 31; st->qp_cr_skip = 33; st->qp_jcbcr_skip = 32;
+    st->lmcs_chroma_scale = 1 << 11;
+    const int unit = tree ? 2 : 4, size = tree ? 64 : 128, w = 1 << l2w, h = 1 << l2h, k = (int)o->n_total;
+    d->x0 = (uint16_t)(((k * 5) % ((size - w) / unit + 1)) * unit);
+    d->y0 = (uint16_t)(((k * 3) % ((size - h) / unit + 1)) * unit);
+    d->log2_tb_w = (uint8_t)l2w; d->log2_tb_h = (uint8_t)l2h; d->tree = (uint8_t)tree;
+    d->cbf_mask = tree ? 0x3 : 0x10;
+    memset(o->c->residual_y, 0, sizeof(o->c->residual_y)); memset(o->c->residual_cb, 0, sizeof(o->c->residual_cb));
+    memset(o->c->residual_cr, 0, sizeof(o->c->residual_cr));
+}
+
+static void
+icells_case(struct icells *o, const ovhip_tu_state *st, ovhip_tu_desc *d, int c_mode)
+{
+    OVCTUDec *c = o->c;
+    const struct OVBuffInfo *cb = &c->rcn_ctx.ctu_buff;
+    const int tree = d->tree, l2w = d->log2_tb_w, l2h = d->log2_tb_h, w = 1 << l2w, h = 1 << l2h, x0 = d->x0, y0 = d->y0;
+    const int cl2w = tree ? l2w : l2w - 1, cl2h = tree ? l2h : l2h - 1;
+    struct TUInfo tu;
+    memset(&tu, 0, sizeof(tu));
+    /* a file stays below 1 MiB (worst case of one case: three blocks of levels and three expected rectangles) and holds 512 cases at
+     * most: the tests lay a file's cases out on 128-row bands of ONE picture, and a command addresses its row with 16 bits */
+    if (o->n == 512 || 49152 + (o->coefs.n + o->exp.n + 6 * (size_t)w * h) * 2 + (o->n + 1) * (sizeof(*st) + sizeof(*d) + 36) > 1000000) icells_flush(o);
+
+    int16_t *res[3] = { c->residual_cb, c->residual_cr, c->residual_y };
+    uint32_t off3[3] = { 0, 0, 0 }, len3[3] = { 0, 0, 0 };
+    for (int comp = 0; comp < 3; ++comp) {
+        const int is_l = comp == 2;
+        const int used = is_l ? (d->cbf_mask & 0x10) && tree != 2
+                              : (d->cbf_mask & 0x8) ? comp == 0 : (d->cbf_mask & (comp ? 0x1 : 0x2));
+        if (!used) continue;
+        const int tl2w = is_l ? l2w : cl2w, tl2h = is_l ? l2h : cl2h;
+        const int ts = is_l ? !!(d->tr_skip_mask & 0x10)
+                            : (d->cbf_mask & 0x8) ? !!(d->tr_skip_mask & 0x1) : !!(d->tr_skip_mask & (comp ? 0x1 : 0x2));
+        const int raster = (ts && !st->sh_ts_disabled) || tl2w < 2 || tl2h < 2;
+        const int cw = (1 << tl2w) > 32 ? 32 : (1 << tl2w), ch = (1 << tl2h) > 32 ? 32 : (1 << tl2h);
+        const int n = raster ? (1 << (tl2w + tl2h)) : cw * ch;
+        tu.tb_info[comp].sig_sb_map = d->sig_sb_map[comp]; tu.tb_info[comp].last_pos = d->last_pos[comp];
+        off3[comp] = (uint32_t)o->coefs.n; len3[comp] = (uint32_t)n;
+        gbuf_push(&o->coefs, res[comp], n);
+    }
+    rcn_init_ict_functions_10(&c->rcn_funcs, st->ict_type, 10);
+    itx_set_state(c, st, c_mode);
+    tu.cbf_mask = d->cbf_mask; tu.pos_offset = 0; tu.tr_skip_mask = d->tr_skip_mask;
+    tu.cu_mts_flag = d->cu_mts_flag; tu.cu_mts_idx = d->cu_mts_idx;
+    tu.lfnst_flag = d->lfnst_flag; tu.lfnst_idx = d->lfnst_idx;
+    itx_load_pred(c, o->pred_y, o->pred_cb, o->pred_cr);
+    if (tree == 0) c->rcn_funcs.tmp.rcn_tu_st(c, x0, y0, l2w, l2h, d->cu_flags, d->cbf_mask, &tu);
+    else           c->rcn_funcs.tmp.rcn_tu_c(c, x0, y0, l2w, l2h, d->cu_flags, d->cbf_mask, &tu);
+
+    uint32_t eoff[3] = { 0, 0, 0 };
+    if (tree == 0) {
+        eoff[0] = (uint32_t)o->exp.n; dump_rect(&o->exp, cb->y, cb->stride, x0, y0, w, h);
+        eoff[1] = (uint32_t)o->exp.n; dump_rect(&o->exp, cb->cb, cb->stride_c, x0 >> 1, y0 >> 1, w >> 1, h >> 1);
+        eoff[2] = (uint32_t)o->exp.n; dump_rect(&o->exp, cb->cr, cb->stride_c, x0 >> 1, y0 >> 1, w >> 1, h >> 1);
+    } else {
+        eoff[1] = (uint32_t)o->exp.n; dump_rect(&o->exp, cb->cb, cb->stride_c, x0, y0, w, h);
+        eoff[2] = (uint32_t)o->exp.n; dump_rect(&o->exp, cb->cr, cb->stride_c, x0, y0, w, h);
+    }
+    gbuf_push(&o->state, st, sizeof(*st));
+    gbuf_push(&o->desc, d, sizeof(*d));
+    gbuf_push(&o->coff, off3, 3); gbuf_push(&o->clen, len3, 3); gbuf_push(&o->eoff, eoff, 3);
+    o->n++; o->n_total++;
+}
+
+/* levels that stay levels: small ones with a few of three digits, never zero (a cleared sub-block must change the block) */
+static int16_t rnd_level(void)
+{
+    int v = rnd_range(0, 7) ? rnd_range(1, 24) : rnd_range(100, 900);
+    return (int16_t)(rnd_range(0, 1) ? v : -v);
+}
+
+/* the sub-block (sx, sy) of a block of levels in the reference's layout (cw = min(32, width)) */
+static void
+icells_sb(int16_t *dst, int cw, int sx, int sy, int16_t (*draw)(void))
+{
+    int16_t *sb = dst + sy * 4 * cw + sx * 16;
+    for (int i = 0; i < 16; ++i) sb[i] = draw();
+}
+
+/* one level at (x, y): raster, or inside its 4x4 sub-block */
+static void
+icells_put(int16_t *dst, int raster, int w, int x, int y, int v)
+{
+    if (raster) dst[y * w + x] = (int16_t)v;
+    else dst[(y >> 2) * 4 * (w > 32 ? 32 : w) + (x >> 2) * 16 + (y & 3) * 4 + (x & 3)] = (int16_t)v;
+}
+
+static uint64_t
+icells_full_map(int l2w, int l2h)
+{
+    const int nx = 1 << ((l2w > 5 ? 5 : l2w) - 2), ny = 1 << ((l2h > 5 ? 5 : l2h) - 2);
+    uint64_t m = 0;
+    for (int sy = 0; sy < ny; ++sy) m |= ((1ull << nx) - 1) << (8 * sy);
+    return m;
+}
+
+/* a luma transform block whose significant sub-blocks are `map`, levels from `draw` */
+static void
+icells_luma_map(struct icells *o, ovhip_tu_state *st, ovhip_tu_desc *d, uint64_t map, int16_t (*draw)(void))
+{
+    const int cw = (1 << d->log2_tb_w) > 32 ? 32 : (1 << d->log2_tb_w);
+    for (int b = 0; b < 64; ++b) if ((map >> b) & 1) icells_sb(o->c->residual_y, cw, b & 7, b >> 3, draw);
+    d->sig_sb_map[2] = map; d->last_pos[2] = 0x0302;
+    icells_case(o, st, d, 0);
+}
+
+/* the 16 levels of the de-quantisation family: both ends of int16, +-1 and values between (mostly small ones: where every sample
+ * ends at a picture clip, no QP shows); transform skip adds the de-quantised level itself to the sample: more of the smallest */
+static const int16_t icells_dq_levels[2][16] = { { 1, -1, 32767, -32768, 2, -3, 517, -32767, 90, -90, 7, -33, 4000, -15, 11, -6 },
+                                                 { 1, -1, 32767, -32768, 2, -2, 1, -1, 3, -3, 1, -1, 517, -32767, 5, -7 } };
+
+/* BDPCM levels of a w x h block: the first two lines along the direction run into the two int16 ends of the running sum */
+static void
+icells_bdpcm_levels(int16_t *dst, int raster, int w, int h, int vertical)
+{
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const int line = vertical ? x : y, pos = vertical ? y : x;
+            int v = line == 0 ? 20000 : line == 1 ? -20000 : line == 2 ? (pos & 1 ? -30000 : 31000) : ((x * 7 + y * 13) % 19) - 9;
+            icells_put(dst, raster, w, x, y, v);
+        }
+}
+
+static void
+gen_itx_cells(const char *dir)
+{
+    static struct icells O;
+    struct icells *o = &O;
+    ovhip_tu_state st; ovhip_tu_desc d;
+    memset(o, 0, sizeof(*o));
+    o->dir = dir;
+    o->state.type = T_U8; o->desc.type = T_U8; o->coff.type = T_U32; o->clen.type = T_U32; o->coefs.type = T_I16; o->eoff.type = T_U32; o->exp.type = T_U16;
+    g_seed = 0x266;
+    itx_fill_pred(o->pred_y, o->pred_cb, o->pred_cr);       /* itx.ovg's picture */
+    g_seed = 0x266 + 901;
+    OVCTUDec *c = o->c = ref_new_ctudec(0, 0);
+    c->rcn_funcs.intra_pred_c = stub_intra_pred_c;
+
+    /* ---- transform pairs: every luma shape 4..32, fully populated from rnd_coef's mixture: DCT-II / DCT-II and the four explicit
+     *      cu_mts_idx on an inter CU, implicit MTS on an intra CU; the shapes with a side of 64: DCT-II, zero-out to 32 ---- */
+    icells_begin(o, "tr");
+    for (int l2w = 2; l2w <= 6; ++l2w)
+        for (int l2h = 2; l2h <= 6; ++l2h)
+            for (int v = 0; v < 6; ++v) {
+                if ((l2w == 6 || l2h == 6) && v && !(v == 5 && (l2w <= 4 || l2h <= 4))) continue;   /* (implicit MTS: DST-VII along a side of at most 16) */
+                icells_init(o, &st, &d, 0, l2w, l2h);
+                st.qp_y = (uint8_t)(8 + v + l2w); st.dep_quant = v & 1;
+                if (v >= 1 && v <= 4) { d.cu_mts_flag = 1; d.cu_mts_idx = (uint8_t)(v - 1); }
+                if (v == 5) { d.cu_flags |= 1u << 1; st.mts_implicit = 1; }
+                icells_luma_map(o, &st, &d, icells_full_map(l2w, l2h), rnd_coef);
+            }
+
+    /* ---- extents: every (last significant sub-block column, row) of the one-wave shapes (at most 256 samples, no side above 32), a
+     *      map with a hole; the four corners and a hole for the four-wave shapes 32x32, 64x32, 32x64, 64x64 ---- */
+    icells_begin(o, "ext");
+    for (int l2w = 2; l2w <= 6; ++l2w)
+        for (int l2h = 2; l2h <= 6; ++l2h) {
+            const int one_wave = l2w + l2h <= 8 && l2w <= 5 && l2h <= 5;
+            if (!one_wave && (l2w < 5 || l2h < 5)) continue;
+            const int nx = 1 << ((l2w > 5 ? 5 : l2w) - 2), ny = 1 << ((l2h > 5 ? 5 : l2h) - 2);
+            for (int ly = 0; ly < ny; ++ly)
+                for (int lx = 0; lx < nx; ++lx) {
+                    if (!one_wave && !((lx == 0 || lx == nx - 1) && (ly == 0 || ly == ny - 1))) continue;
+                    icells_init(o, &st, &d, 0, l2w, l2h);
+                    st.qp_y = (uint8_t)(26 + lx + ly);
+                    icells_luma_map(o, &st, &d, 1ull | 1ull << lx | 1ull << (8 * ly) | 1ull << (8 * ly + lx), rnd_level);
+                }
+            if (nx * ny >= 4) {
+                icells_init(o, &st, &d, 0, l2w, l2h);
+                const int hx = nx >> 1, hy = (ny - 1) >> 1;
+                icells_luma_map(o, &st, &d, icells_full_map(l2w, l2h) & ~(1ull << (8 * hy + hx)), rnd_level);
+            }
+        }
+
+    /* ---- LFNST: the sets through the intra mode (0, 1: set 0; 12, 56: set 1; 18, 50: set 2; 30, 40: set 3; the modes above 34
+     *      transposed; 2 and 66 are remapped to wide angles on the non-square shapes), both indices, the size classes; levels in the
+     *      first sub-block only (4x4 and 8x8: its first 8 in scan order), the ends of int16 among them.  Luma, then dual-tree chroma
+     *      with the mode in lfnst_mode_c: the same modes and LM (67), which takes the mode of the luma block behind it ---- */
+    icells_begin(o, "lfnst");
+    {
+        static const uint8_t shapes[8][2] = { {2,2}, {2,4}, {4,2}, {3,3}, {4,4}, {3,5}, {5,3}, {5,5} };
+        static const uint8_t modes[11] = { 0, 1, 12, 56, 18, 50, 30, 40, 2, 66, 67 };
+        static const uint8_t scan8[8] = { 0, 4, 1, 8, 5, 2, 12, 9 };
+        for (int tree = 0; tree <= 2; tree += 2)
+            for (int s = 0; s < 8; ++s)
+                for (int m = 0; m < (tree ? 11 : 10); ++m)
+                    for (int idx = 0; idx < 2; ++idx) {
+                        const int l2w = shapes[s][0], l2h = shapes[s][1], n8 = l2w == l2h && l2w <= 3;
+                        icells_init(o, &st, &d, tree, l2w, l2h);
+                        d.cu_flags |= 1u << 1; d.lfnst_flag = 1; d.lfnst_idx = (uint8_t)idx;
+                        st.qp_y = st.qp_cb = st.qp_cr = (uint8_t)(4 + (m + idx) % 6 + ((m & 1) ? 20 : 0));
+                        int c_mode = 0, eff = modes[m];
+                        if (tree) {
+                            c_mode = modes[m];
+                            if (c_mode == 67) { eff = 40; memset(c->drv_ctx.intra_info.luma_modes, eff, sizeof(c->drv_ctx.intra_info.luma_modes)); }
+                            st.lfnst_mode_c = (int8_t)shim_lfnst_mode_c(l2w, l2h, eff);
+                        } else st.intra_mode = (int8_t)modes[m];
+                        for (int comp = tree ? 0 : 2; comp < (tree ? 2 : 3); ++comp) {
+                            int16_t *sb = comp == 2 ? c->residual_y : comp ? c->residual_cr : c->residual_cb;
+                            for (int i = 0; i < (n8 ? 8 : 16); ++i) {
+                                const int k = (i + m + idx + comp) % 7;
+                                sb[n8 ? scan8[i] : i] = k == 0 ? 32767 : k == 1 ? -32768 : k == 2 ? -32767 : rnd_level();
+                            }
+                            d.sig_sb_map[comp] = 1; d.last_pos[comp] = 0x0101;
+                        }
+                        icells_case(o, &st, &d, c_mode);
+                    }
+    }
+
+    /* ---- de-quantisation: every QP x dep_quant on 4x4, 8x4 (odd log2 sum), 16x16, 32x16, the first sub-block holding both ends of
+     *      int16, +-1 and values between; transform skip with the _skip QP (16 at least, as gen_itx sets it) and regular residual
+     *      coding (sh_ts_disabled: the levels are de-quantised); with TS residual coding the levels are final, whatever the QP:
+     *      the two small shapes at every QP, 16x16 and 32x16 (raster blocks of the one-wave generic and the four-wave body) at four,
+     *      with levels in the block's far corners too ---- */
+    icells_begin(o, "dq");
+    {
+        static const uint8_t shapes[4][2] = { {2,2}, {3,2}, {4,4}, {5,4} };
+        for (int qp = 0; qp <= 75; ++qp)
+            for (int dq = 0; dq < 2; ++dq)
+                for (int s = 0; s < 4; ++s) {
+                    icells_init(o, &st, &d, 0, shapes[s][0], shapes[s][1]);
+                    st.qp_y = (uint8_t)qp; st.qp_y_skip = (uint8_t)(qp < 16 ? 16 : qp); st.dep_quant = (uint8_t)dq;
+                    for (int i = 0; i < 16; ++i) c->residual_y[i] = icells_dq_levels[0][(i + qp) & 15];
+                    d.sig_sb_map[2] = 1; d.last_pos[2] = 0x0302;
+                    icells_case(o, &st, &d, 0);
+                }
+        for (int qp = 16; qp <= 75; ++qp)
+            for (int tsd = 0; tsd < 2; ++tsd)
+                for (int s = 0; s < 4; ++s) {
+                    const int l2w = shapes[s][0], l2h = shapes[s][1];
+                    if (!tsd && s >= 2 && (qp - 16) % 20 && qp != 75) continue;
+                    icells_init(o, &st, &d, 0, l2w, l2h);
+                    st.qp_y = st.qp_y_skip = (uint8_t)qp; st.sh_ts_disabled = (uint8_t)tsd; d.tr_skip_mask = 0x10;
+                    /* at the picture's corner, +1 on its sample (0, 0) = 0 and -1 on (3, 2) = 1023: from QP 57 on, the level 1 takes every
+                     * other sample of the picture to a clip */
+                    d.x0 = d.y0 = 0;
+                    for (int i = 0; i < 16; ++i) icells_put(c->residual_y, !tsd, 1 << l2w, i & 3, i >> 2, icells_dq_levels[1][i]);
+                    if (!tsd && s >= 2) {
+                        icells_put(c->residual_y, 1, 1 << l2w, (1 << l2w) - 1, 0, -2); icells_put(c->residual_y, 1, 1 << l2w, 0, (1 << l2h) - 1, 5);
+                        icells_put(c->residual_y, 1, 1 << l2w, (1 << l2w) - 1, (1 << l2h) - 1, 3);
+                    }
+                    d.sig_sb_map[2] = 1; d.last_pos[2] = 0x0302;
+                    icells_case(o, &st, &d, 0);
+                }
+    }
+
+    /* ---- transform skip with BDPCM: every shape up to 32x32, both directions, luma (TS and regular residual coding) and dual-tree
+     *      chroma; the running sum saturates at both ends ---- */
+    icells_begin(o, "bdpcm");
+    for (int tree = 0; tree <= 2; tree += 2)
+        for (int l2w = tree ? 1 : 2; l2w <= 5; ++l2w)
+            for (int l2h = tree ? 1 : 2; l2h <= 5; ++l2h)
+                for (int dir = 0; dir < 2; ++dir)
+                    for (int tsd = 0; tsd < 2; ++tsd) {
+                        icells_init(o, &st, &d, tree, l2w, l2h);
+                        st.sh_ts_disabled = (uint8_t)tsd;
+                        st.qp_y_skip = st.qp_cb_skip = st.qp_cr_skip = (uint8_t)(16 + 3 * l2w + l2h + dir);
+                        d.cu_flags |= 1u << 1;
+                        const int raster = !tsd || l2w < 2 || l2h < 2;
+                        if (tree) {
+                            d.tr_skip_mask = 0x3; d.cu_flags |= (1u << 9) | ((uint32_t)dir << 11);
+                            icells_bdpcm_levels(c->residual_cb, raster, 1 << l2w, 1 << l2h, dir);
+                            icells_bdpcm_levels(c->residual_cr, raster, 1 << l2w, 1 << l2h, dir);
+                            d.sig_sb_map[0] = d.sig_sb_map[1] = raster ? 1 : icells_full_map(l2w, l2h);
+                            d.last_pos[0] = d.last_pos[1] = 0x0101;
+                        } else {
+                            d.tr_skip_mask = 0x10; d.cu_flags |= (1u << 8) | ((uint32_t)dir << 10);
+                            icells_bdpcm_levels(c->residual_y, raster, 1 << l2w, 1 << l2h, dir);
+                            d.sig_sb_map[2] = raster ? 1 : icells_full_map(l2w, l2h); d.last_pos[2] = 0x0101;
+                        }
+                        icells_case(o, &st, &d, 0);
+                    }
+
+    /* ---- DC: every luma and dual-tree chroma shape with the first coefficient only: a moderate level, the level that the
+     *      de-quantisation clips at either end (|flat value| then is 1024, the most an int16 coefficient allows: the int16 clip of the
+     *      flat value itself cannot be reached), and a map whose bit 0 is clear ---- */
+    icells_begin(o, "dc");
+    for (int tree = 0; tree <= 2; tree += 2)
+        for (int l2w = tree ? 1 : 2; l2w <= (tree ? 5 : 6); ++l2w)
+            for (int l2h = tree ? 1 : 2; l2h <= (tree ? 5 : 6); ++l2h)
+                for (int v = 0; v < 4; ++v) {
+                    icells_init(o, &st, &d, tree, l2w, l2h);
+                    const int lvl = v == 0 ? 37 + 5 * l2w - 11 * l2h : v == 1 ? 32767 : v == 2 ? -32768 : -21;
+                    if (v == 1 || v == 2) st.qp_y = st.qp_cb = st.qp_cr = 51;
+                    for (int comp = tree ? 0 : 2; comp < (tree ? 2 : 3); ++comp) {
+                        (comp == 2 ? c->residual_y : comp ? c->residual_cr : c->residual_cb)[0] = (int16_t)(comp == 1 ? -lvl - (lvl == -32768) : lvl);
+                        d.sig_sb_map[comp] = v != 3; d.last_pos[comp] = 0;
+                    }
+                    icells_case(o, &st, &d, 0);
+                }
+
+    /* ---- sinks: dual-tree chroma 2x2 .. 32x32 (the raster 2xN / Nx2 shapes among them) x ict_type x cbf_mask (Cr, Cb, both, and
+     *      the three joint forms) x LMCS chroma scale off / on at both ends of its range (where ict_type applies a scale): the
+     *      reference derives (1 << 17) / (window size + offset) with a divisor of 8..511 (rcn_lmcs.c:341-342): 16384 .. 256 ---- */
+    icells_begin(o, "sink");
+    {
+        static const uint8_t cbfs[6] = { 0x1, 0x2, 0x3, 0x9, 0xa, 0xb };
+        for (int l2w = 1; l2w <= 5; ++l2w)
+            for (int l2h = 1; l2h <= 5; ++l2h)
+                for (int ict = 0; ict < 4; ++ict)
+                    for (int k = 0; k < 6; ++k)
+                        for (int lm = 0; lm < ((ict & 1) ? 3 : 1); ++lm) {
+                            icells_init(o, &st, &d, 2, l2w, l2h);
+                            st.ict_type = (uint8_t)ict; d.cbf_mask = cbfs[k];
+                            st.lmcs_scale_c = lm != 0; st.lmcs_chroma_scale = (int16_t)(lm == 1 ? 256 : lm == 2 ? 16384 : 2048);
+                            const int raster = l2w < 2 || l2h < 2;
+                            for (int comp = 0; comp < 2; ++comp) {
+                                const int used = (cbfs[k] & 0x8) ? comp == 0 : (cbfs[k] & (comp ? 0x1 : 0x2));
+                                if (!used) continue;
+                                int16_t *dst = comp ? c->residual_cr : c->residual_cb;
+                                if (raster) {
+                                    for (int i = 0; i < (1 << (l2w + l2h)); ++i) dst[i] = rnd_level();
+                                    d.sig_sb_map[comp] = 1;
+                                } else {
+                                    d.sig_sb_map[comp] = icells_full_map(l2w, l2h) & 0x0303;          /* the first 8x8 at most: the sinks are the subject */
+                                    for (int b = 0; b < 16; ++b) if ((d.sig_sb_map[comp] >> b) & 1) icells_sb(dst, 1 << l2w, b & 7, b >> 3, rnd_level);
+                                }
+                                d.last_pos[comp] = 0x0101;
+                            }
+                            icells_case(o, &st, &d, 0);
+                        }
+    }
+
+    /* ---- quads: luma blocks of the one-wave class that are not tiny, in fours, so that the recorder's stable split hands one
+     *      workgroup four DIFFERENT paths: LFNST, BDPCM, DC and plain specialised.  The shapes rotate through 16x16, 32x8, 8x32, 32x4
+     *      (the most LDS the class uses), then through the remaining shapes ---- */
+    icells_begin(o, "quad");
+    {
+        static const uint8_t big[4][2] = { {4,4}, {5,3}, {3,5}, {5,2} };
+        static const uint8_t rest[4][2] = { {2,5}, {4,3}, {3,4}, {4,2} };
+        for (int q = 0; q < 8; ++q)
+            for (int path = 0; path < 4; ++path) {
+                const uint8_t *sh = (q < 4 ? big : rest)[(path + q) & 3];
+                const int l2w = sh[0], l2h = sh[1], slot = (path + (q >> 1)) & 3;       /* the paths change waves too */
+                icells_init(o, &st, &d, 0, l2w, l2h);
+                st.qp_y = st.qp_y_skip = (uint8_t)(22 + q + slot);
+                if (slot == 0) {                 /* LFNST */
+                    d.cu_flags |= 1u << 1; d.lfnst_flag = 1; d.lfnst_idx = (uint8_t)(q & 1); st.intra_mode = (int8_t)(q & 2 ? 50 : 18);
+                    for (int i = 0; i < 16; ++i) c->residual_y[i] = rnd_level();
+                    d.sig_sb_map[2] = 1; d.last_pos[2] = 0x0101;
+                    icells_case(o, &st, &d, 0);
+                } else if (slot == 1) {          /* BDPCM, TS residual coding on even quads, regular on odd ones */
+                    st.sh_ts_disabled = q & 1; d.cu_flags |= (1u << 1) | (1u << 8) | ((uint32_t)((q >> 1) & 1) << 10); d.tr_skip_mask = 0x10;
+                    icells_bdpcm_levels(c->residual_y, !(q & 1), 1 << l2w, 1 << l2h, (q >> 1) & 1);
+                    d.sig_sb_map[2] = (q & 1) ? icells_full_map(l2w, l2h) : 1; d.last_pos[2] = 0x0101;
+                    icells_case(o, &st, &d, 0);
+                } else if (slot == 2) {          /* DC */
+                    c->residual_y[0] = (int16_t)(q & 1 ? -411 : 293); d.sig_sb_map[2] = 1; d.last_pos[2] = 0;
+                    icells_case(o, &st, &d, 0);
+                } else {                         /* plain, fully populated */
+                    if (q & 1) { d.cu_mts_flag = 1; d.cu_mts_idx = (uint8_t)((q >> 1) & 3); }
+                    icells_luma_map(o, &st, &d, icells_full_map(l2w, l2h), rnd_level);
+                }
+            }
+    }
+    icells_flush(o);
 }
 
 /* ====================================================================================== MC */
@@ -2397,6 +2828,7 @@ main(int argc, char **argv)
     if ((!only || !strcmp(only, "intra")) && !g_shim) gen_intra(dir);
     /* the cells intra.ovg does not reach: by name only, a run of its own */
     if (only && !strcmp(only, "intra_cells") && !g_shim) gen_intra_cells(dir);
+    if (only && !strcmp(only, "itx_cells") && !g_shim) gen_itx_cells(dir);
     if (!only || !strcmp(only, "intra_ctu")) gen_intra_ctu(dir);
     if (!only || !strcmp(only, "isp")) gen_isp(dir);
     return 0;

@@ -13,9 +13,26 @@ from oracle_lib import HostPic
 BAND = 128
 
 
-def itx_cases():
-    g = golden_io.load("itx.ovg")
+def itx_cell_files():
+    """the enumerated inverse transform cells (gen_itx_cells), one or more files per family"""
+    return sorted(p.name for p in golden_io.GOLDEN.glob("itx_cells_*.ovg"))
+
+
+def itx_cases(name="itx.ovg"):
+    """itx.ovg or one of itx_cell_files(): (picture, commands, coefficient arena, rects, expected); itx_cases_rec is the same with the
+    recorder and the number of commands each case emitted"""
+    pic, rec, n_cmds, rects, exp = itx_cases_rec(name)
+    return pic, rec.tb_cmds(), rec.coefs(), rects, exp
+
+
+def itx_cases_rec(name="itx.ovg", ordered=False):
+    """ordered: a TU of an intra CU that has a chroma residual is recorded with the CU's chroma prediction task, as the installed slots
+    record it (its blocks then leave through the residual picture, OVHIP_RES_STORE); rec.itasks() holds the tasks.  The reference run
+    behind the fixtures had intra_pred_c stubbed out: the caller keeps the tasks' residual half only (OVHIP_IT_RES_C)."""
+    g = golden_io.load(name)
     n = g["desc"].shape[0]
+    assert BAND * n <= 1 << 16, "a command addresses its row with 16 bits"
+    n_cmds = []
     pic = HostPic(128, BAND * n,
                   np.tile(g["pred_y"], (n, 1)), np.tile(g["pred_cb"], (n, 1)), np.tile(g["pred_cr"], (n, 1)))
     rec = capi.Recorder(128, BAND * n)
@@ -30,7 +47,13 @@ def itx_cases():
         for comp in range(3):
             ln = int(g["coef_len"][i, comp])
             d.coef[comp] = coefs[int(g["coef_off"][i, comp]):].ctypes.data if ln else None
-        rec.tu(st, d)
+        if ordered and (d.cu_flags & 2) and tree != 1 and (d.cbf_mask & 0xb):
+            t = capi.ITask()
+            t.x, t.y, t.kind = (d.x0, d.y0, capi.IT_CHROMA) if tree else (d.x0 >> 1, d.y0 >> 1, capi.IT_CHROMA)
+            t.log2_w, t.log2_h = (d.log2_tb_w, d.log2_tb_h) if tree else (d.log2_tb_w - 1, d.log2_tb_h - 1)
+            n_cmds.append(rec.tu_intra(st, d, None, t))
+        else:
+            n_cmds.append(rec.tu(st, d))
         eo = g["exp_off"][i]
         if tree == 0:
             rects.append((0, x0, y0 + i * BAND, w, h, int(eo[0])))
@@ -39,7 +62,7 @@ def itx_cases():
         else:
             rects.append((1, x0, y0 + i * (BAND // 2), w, h, int(eo[1])))
             rects.append((2, x0, y0 + i * (BAND // 2), w, h, int(eo[2])))
-    return pic, rec.tb_cmds(), rec.coefs(), rects, g["exp"]
+    return pic, rec, n_cmds, rects, g["exp"]
 
 
 def tt_cases():

@@ -251,7 +251,7 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     if not gen.exists() or not (root / "oracle" / "_ref" / "libovvcref.so").exists():
         pytest.skip("compiled reference not present")
     subprocess.check_call([str(gen), str(tmp_path)], stderr=subprocess.DEVNULL)
-    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra cells are runs of their own
+    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells", "itx_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra / inverse transform cells are runs of their own
         subprocess.check_call([str(gen), str(tmp_path), only], stderr=subprocess.DEVNULL)
     # shim_*: test_shim_cpu.py; pipe* / tiles*: the chained streams of gen_pipe, test_pipe_cpu.py
     names = sorted(p.name for p in (root / "tests" / "golden").glob("*.ovg") if not p.name.startswith(("shim_", "pipe", "tiles")))
@@ -259,6 +259,7 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     for n in names:
         assert (tmp_path / n).read_bytes() == (root / "tests" / "golden" / n).read_bytes(), f"{n} differs from a fresh run of the reference"
     assert sorted(p.name for p in tmp_path.glob("intra_cells_*.ovg")) == [n for n in names if n.startswith("intra_cells_")], "the generator cuts the intra cells into other files than the committed ones"
+    assert sorted(p.name for p in tmp_path.glob("itx_cells_*.ovg")) == [n for n in names if n.startswith("itx_cells_")], "the generator cuts the inverse transform cells into other files than the committed ones"
 
 
 def test_intra_oracle_matches_reference(built_lib):
@@ -373,3 +374,140 @@ def test_intra_fixture_census(built_lib):
     # (a figure, not a condition: the (mode, class) pairs hold modes that do not read the missing arm, and planar never reads the corner)
     new = sel >= n0
     print(f"enumerated cases without full availability that predict what full availability predicts: {int((new & ~sens).sum())} of {int(new.sum())}")
+
+
+def test_itx_oracle_matches_reference_on_the_enumerated_cells(built_lib):
+    """itx_cells_*.ovg (gen_itx_cells: transform pairs, extents, LFNST, de-quantisation, BDPCM, DC, sinks and the mixed quads, on itx.ovg's
+    picture and through the same slots): the oracle equals the reference on every block of every file."""
+    import golden_io
+    files = golden_cases.itx_cell_files()
+    assert {f.split("_")[2] for f in files} == {"tr", "ext", "lfnst", "dq", "bdpcm", "dc", "sink", "quad"}
+    assert all((golden_io.GOLDEN / f).stat().st_size < (1 << 20) for f in files)
+    n = 0
+    for f in files:
+        pic, cmds, coefs, rects, exp = golden_cases.itx_cases(f)
+        oracle_lib.itx(pic, cmds, coefs)
+        golden_cases.check_rects(pic, rects, exp, f"{f}: oracle vs reference")
+        n += len(cmds)
+    assert n > 3500
+
+
+def test_itx_fixture_census(built_lib):
+    """What the inverse transform slot fixtures reach, written down so that it cannot shrink unnoticed (tests/itx_census.py does the
+    counting, and asserts its restatement of the recorder's split against the recorder on every file).
+
+    itx.ovg alone, on the routes it had (every block four-wave; the picture job) -- cells reached of cells that exist:
+      plain luma transform blocks (body, shape, transform pair): four-wave 64 of 101, specialised 27 of 69, tiny 14 of 20;
+      LFNST (set, index, transposed, size class): 28 of 56 (no 4x4 block with set 0, 2 or 3 at index 0, ...);
+      (shape, nb_row, nb_col) of the one-wave shapes: specialised 29 of 97, tiny 8 of 9;
+      de-quantisation classes (scale, table, dq_neg, dq_shift) of the enumerated QP range: 169 of 186;
+      sink modes without STORE (first plane, mode, second plane's mode, scale on): 25 of 25, but the scale within 1200..3400 of the
+      256..16384 the reference can derive.
+    With itx_cells_*.ovg on the three routes every one of these cells has a case."""
+    import itx_census as ic
+    cmds, _ = ic.load(["itx.ovg"])
+    r = ic.reach(cmds, ("itx", "job"))
+    tr, ext = ic.tr_cells_that_exist(), ic.extent_cells_that_exist()
+    per_body = lambda cells, b: {c for c in cells if c[0] == b}
+    assert [len(per_body(tr, b)) for b in (ic.FOUR, ic.SPEC, ic.TINY)] == [101, 69, 20]
+    assert [len(per_body(r["tr"] & tr, b)) for b in (ic.FOUR, ic.SPEC, ic.TINY)] == [64, 27, 14] and r["tr"] <= tr
+    assert len(ic.lfnst_cells_that_exist()) == 56 and len(r["lfnst"]) == 28 and r["lfnst"] <= ic.lfnst_cells_that_exist()
+    assert len(ext) == 97 and len({c[1:] for c in per_body(r["extent"], ic.SPEC)} & ext) == 29
+    assert len({c[1:] for c in per_body(r["extent"], ic.TINY)} & ext) == 8
+    assert len(ic.dq_cells_that_exist()) == 186 and len(r["dq"] & ic.dq_cells_that_exist()) == 169
+    assert len(ic.sink_cells_that_exist()) == 25 and r["sink"] == ic.sink_cells_that_exist()
+    scales = cmds["c_scale"][(cmds["res_mode"] & capi.RES_SCALE) != 0]
+    assert 1200 <= scales.min() and scales.max() <= 3400
+
+    # ---- with the enumerated cells, on the three routes
+    cmds, _ = ic.load(["itx.ovg"] + golden_cases.itx_cell_files())
+    r = ic.reach(cmds)
+    assert r["tr"] == tr, f"(body, shape, transform pair) without a case: {sorted(tr - r['tr'])[:8]}"
+    lf = ic.lfnst_cells_that_exist()
+    assert r["lfnst"] == lf and r["lfnst_body"] == {(b, c) for c in lf for b in ((ic.FOUR,) if c[3] != "larger" else ()) + (ic.FOUR, ic.GENERIC)}
+    for b in (ic.FOUR, ic.SPEC):
+        assert {c[1:] for c in per_body(r["extent"], b)} >= ext, ic.BODY_NAMES[b]
+    assert {c[1:] for c in per_body(r["extent"], ic.TINY)} == {c for c in ext if c[0] in ic.TINY_SHAPES}
+    assert r["dq"] >= ic.dq_cells_that_exist() and r["sink"] >= ic.sink_cells_that_exist()
+    # the chroma scale at both ends of what the reference derives, (1 << 17) / (8 .. 511), on every scaled sink mode
+    for end in (256, 16384):
+        at_end = ic.label(cmds[((cmds["res_mode"] & capi.RES_SCALE) != 0) & (cmds["c_scale"] == end)])["sink"]
+        assert set(at_end) == {c for c in ic.sink_cells_that_exist() if c[4]}, end
+    # transform-skip blocks whose levels are final (TS residual coding), raster: 16x16 in the one-wave generic body, 32x16 four-wave
+    raw = {c[:2] for c in r["body_cells"] if c[3] == ic.K_TS_RAW}
+    assert {(ic.GENERIC, (2, 2)), (ic.GENERIC, (3, 2)), (ic.GENERIC, (4, 4)), (ic.FOUR, (4, 4)), (ic.FOUR, (5, 4))} <= raw
+    # every kind in every body that can take it: DC and raster DC in the one-wave shortcut, transform skip / BDPCM / raster blocks in the generic body
+    kinds = {(ic.BODY_NAMES[b], k, l) for b, k, l in r["kind_body"]}
+    assert {("one-wave DC", "DC", True), ("one-wave DC", "DC", False), ("one-wave DC", "raster DC", False), ("tiny", "DC", True), ("tiny", "DC", False),
+            ("one-wave generic", "raster TR", False)} <= kinds
+    assert {(ic.BODY_NAMES[b], k, l) for b in (ic.FOUR, ic.GENERIC) for k in ("TS", "TS_RAW", "BDPCM horizontal", "BDPCM vertical") for l in (True, False)} <= kinds
+
+
+def test_itx_cells_discriminate(built_lib):
+    """The enumerated cells pin what they are named after: the oracle (equal to the reference on every block, above) reconstructs ANOTHER
+    block when the command is edited -- transform pair: tr_h and tr_v swapped (where they differ), DST-VII replaced by DCT-VIII, DCT-II /
+    DCT-II by DST-VII / DST-VII (no side above 32); LFNST: every other (set, index, transposed); extent: the outermost significant sub-block
+    cleared (maps of more than one sub-block); de-quantisation: the class of QP - 1 and of QP + 1.  No cell may fail to."""
+    import golden_io
+    import itx_census as ic
+    g = golden_io.load("itx.ovg")
+    pred = (g["pred_y"], g["pred_cb"], g["pred_cr"])
+    dull, n = [], 0
+
+    def cases(prefix):
+        for f in golden_cases.itx_cell_files():
+            if f.startswith(prefix):
+                _, rec, n_cmds, _, _ = golden_cases.itx_cases_rec(f)
+                gg = golden_io.load(f)
+                cmds, coefs, k = rec.tb_cmds().copy(), rec.coefs().copy(), 0
+                for i, m in enumerate(n_cmds):
+                    for c in cmds[k:k + m]:
+                        yield f, i, c, coefs, capi.TuState.from_buffer_copy(gg["state"][i].tobytes()), capi.TuDesc.from_buffer_copy(gg["desc"][i].tobytes())
+                    k += m
+
+    for f, i, c, coefs, _, _ in cases("itx_cells_tr_"):
+        v, h = int(c["tr_v"]), int(c["tr_h"])
+        edits = [(h, v)] if v != h and max(c["log2_w"], c["log2_h"]) <= 5 else []      # (a side of 64 has DCT-II alone)
+        if capi.DST_VII in (v, h):
+            edits.append(tuple(capi.DCT_VIII if t == capi.DST_VII else t for t in (v, h)))
+        if (v, h) == (capi.DCT_II, capi.DCT_II) and max(c["log2_w"], c["log2_h"]) <= 5:
+            edits.append((capi.DST_VII, capi.DST_VII))
+        for ev, eh in edits:
+            n += 1
+            if not ic.changes(pred, c, coefs, tr_v=ev, tr_h=eh):
+                dull.append((f, i, "pair", (v, h), (ev, eh)))
+    n_tr = n
+    for f, i, c, coefs, _, _ in cases("itx_cells_lfnst_"):
+        for field in range(16):
+            other = 1 | (field << 1)
+            if other != int(c["lfnst"]):
+                n += 1
+                if not ic.changes(pred, c, coefs, lfnst=other):
+                    dull.append((f, i, "lfnst", int(c["lfnst"]), other))
+    n_lf = n - n_tr
+    for f, i, c, coefs, _, _ in cases("itx_cells_ext_"):
+        m = int(c["sig_sb_map"])
+        if m & (m - 1):
+            n += 1
+            if not ic.changes(pred, c, coefs, sig_sb_map=m & ~(1 << (m.bit_length() - 1))):
+                dull.append((f, i, "extent", hex(m)))
+    n_ext = n - n_tr - n_lf
+    for f, i, c, coefs, st, d in cases("itx_cells_dq_"):
+        if (int(c["kind"]) & 0x3f) == capi.TB_TS_RAW:
+            continue                                      # TS residual coding: the levels are final, there is no QP in the command
+        ts = bool(d.tr_skip_mask & 0x10)
+        kind, qp, l2s = (2, st.qp_y_skip, 4) if ts else (int(st.dep_quant), st.qp_y, int(c["log2_w"]) + int(c["log2_h"]))
+        assert ic.derive_dq(kind, qp, l2s) == (int(c["dq_scale"]), 0 if ts else l2s & 1, int(c["dq_neg"]), int(c["dq_shift"]))
+        for q in (qp - 1, qp + 1):
+            if 0 <= q <= 75:
+                scale, _, neg, shift = ic.derive_dq(kind, q, l2s)
+                # a transform-skip block adds the de-quantised level itself to the sample: where both classes take the level 1 to 1023 or
+                # more, every sample with a level ends at a picture clip under both -- no block can tell them apart
+                if ts and min(scale << shift if neg else 0, int(c["dq_scale"]) << int(c["dq_shift"]) if c["dq_neg"] else 0) >= 1023:
+                    continue
+                n += 1
+                if not ic.changes(pred, c, coefs, dq_scale=scale, dq_neg=neg, dq_shift=shift):
+                    dull.append((f, i, "dq", kind, qp, q))
+    print(f"edits: {n_tr} transform pairs, {n_lf} LFNST, {n_ext} extents, {n - n_tr - n_lf - n_ext} de-quantisation classes; without effect: {len(dull)}")
+    assert n_tr > 100 and n_lf == 512 * 15 and n_ext > 100 and n - n_tr - n_lf - n_ext > 1500
+    assert not dull, f"{len(dull)} of {n} edits leave the block as it is, first: {dull[:8]}"
