@@ -1293,7 +1293,7 @@ int  ovhip_pic_hash(ovhip_ctx *ctx, const ovhip_pic *pic, int method, int n_plan
  *   layout   PLANAR: the R plane, the G plane, the B plane, each H x W (CHW); PACKED: H x W x 3 (HWC).  Both tight.
  * matrix = H.273 MatrixCoefficients: 1 (Kr 0.2126, Kb 0.0722), 5 and 6 (0.299, 0.114), 9 (0.2627, 0.0593); 2 (unspecified) is
  * OVHIP_EINVAL -- the caller must decide --, every other value OVHIP_EUNSUP.  Not done: transfer functions, tone mapping,
- * constant-luminance and ICtCp matrices, normalisation, resizing.
+ * constant-luminance and ICtCp matrices, normalisation; a smaller tensor comes from "Reduced-size output on the device" below.
  * ---------------------------------------------------------------------------------- */
 enum { OVHIP_RGB_U8 = 0, OVHIP_RGB_U16 = 1, OVHIP_RGB_F16 = 2, OVHIP_RGB_F32 = 3 };      /* ovhip_rgb_format.dtype */
 enum { OVHIP_RGB_PLANAR = 0, OVHIP_RGB_PACKED = 1 };                                       /* ovhip_rgb_format.layout */
@@ -1492,6 +1492,57 @@ int  ovhip_pic_digest_scaled(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_s
 /* Device + page-locked bytes the context's grow-only scratch buffers hold (the synchronous conveniences above and of the output path):
  * constant from call to call once the sizes have been seen. */
 size_t ovhip_ctx_scratch_bytes(const ovhip_ctx *ctx);
+
+/* ------------------------------------------------------------------------------------
+ * Reduced-size output on the device: a finished 10-bit 4:2:0 picture leaves SMALLER than it was coded -- 2160p as 1080p for a
+ * transcoder's ladder, half- or quarter-size for a model -- by the exact area average.  Nothing in the reference does this (the
+ * down-sampling branch of pp_sample_rate_conv is dead code under `upscale` and reads past its chroma tables), and the resampler above
+ * keeps refusing down-sampling.  The definition is integer only, so every implementation of it (tests/spec_reduce.py,
+ * ovhip_output_reduce_host, k_output_reduce) is compared for equality.
+ *
+ *   Input    an ovhip_pic of w x h (multiples of 4, at most 16384) and a window in chroma units, read as the packed output reads it:
+ *            the region reduced starts at luma (2 lft, 2 abv) and is Ws = w - 2 (lft + rgt) by Hs = h - 2 (abv + blw), both positive
+ *            multiples of 4; the chroma region starts at (lft, abv) and is Ws/2 x Hs/2.
+ *   Output   Wd x Hd (positive multiples of 4), chroma Wd/2 x Hd/2, with the SAME Chroma420SampleLocType as the source.
+ *   Axis     S = Ws or Hs, D = Wd or Hd, g = gcd(S, D), p = S/g, q = D/g; the chroma planes have the same p and q.  Required:
+ *            D <= S, S <= 8 D, p <= 256.
+ *   Weights  along one axis of a plane with S' samples (S for luma, S/2 for chroma), in units where a sample is 4q long: sample j
+ *            occupies [4q j, 4q (j+1)) for every integer j, output k's footprint is [4p k - sigma, 4p (k+1) - sigma), and w(k, j)
+ *            is the length of their intersection.  A j outside 0 .. S'-1 is read as the nearest sample OF THE REGION: nothing
+ *            outside the window is ever read.  Every output's weights sum to 4p.  sigma = 0 for luma; for chroma
+ *            sigma = (p - q)(1 - a) horizontally and (p - q)(1 - b) vertically, a and b those of the RGB output: a = chroma_loc & 1,
+ *            b = 1 for chroma_loc 0, 1, b = 0 for 2, 3, b = 2 for 4, 5.
+ *   Value    V = sum_jy w_y(ky, jy) sum_jx w_x(kx, jx) s(jx, jy);  out = (V + n/2) div n,  n = 16 p_x p_y.  A mean of samples stays in
+ *            0..1023: no clip.  V + n/2 <= 16 * 256 * 256 * 1023 + 2^19 < 2^31: everything fits int32.
+ * The luma footprints tile the region: sum V = 16 q_x q_y sum s.  For integer ratios the weights' centroid is exactly the output's
+ * sample site; for other ratios the average is centred per footprint (a property of the method).  A ratio of 1 on an axis is a copy
+ * along it.  Example: 2:1 with horizontally co-sited chroma weighs samples 2k-1, 2k, 2k+1 with 1, 4, 3 over 8.
+ * Refused, the reason in the context's error text where there is a context: OVHIP_EUNSUP for D > S on an axis (up-sampling: that is
+ * ovhip_output_scale_*), for S > 8 D (the ratio) and for p > 256 (p/q, and the advice to pick sizes with a larger common divisor);
+ * OVHIP_EINVAL for sizes that are not multiples of 4 or above 16384, a window that leaves nothing or a region that is not a multiple
+ * of 4, chroma_loc > 5, non-zero rsv, a missing plane, a stride below the width, dst aliasing src.  Not done: up-sampling, ratios
+ * above 8, other filters, reduce together with film grain or the output scale, 4:2:2 / 4:4:4 and 8-bit pictures, a reduced motion
+ * field, a shim entry point.
+ * ---------------------------------------------------------------------------------- */
+typedef struct ovhip_reduce_info { ovhip_window win; uint8_t chroma_loc, rsv[3]; } ovhip_reduce_info;      /* rsv must be 0 */
+/* Host only (no device needed): the argument check the launch uses.  ratio[4] = p_x, q_x, p_y, q_y, written whenever they can be
+ * derived (0 otherwise). */
+int  ovhip_output_reduce_check(int32_t src_w, int32_t src_h, const ovhip_reduce_info *info, int32_t dst_w, int32_t dst_h, int32_t ratio[4]);
+/* The definition over pictures in HOST memory (both hold host pointers; strides in samples): tests, and callers that hold the picture
+ * on the host.  Refusals as the launch's; nothing is written when it refuses. */
+int  ovhip_output_reduce_host(const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_pic *dst);
+/* num / n as k_output_reduce divides (a reciprocal estimate and one correction step), on the host: num < 2^31, 0 < n <= 2^20, a
+ * quotient below 2048.  The twin divides with `/`; the two agree on every such pair.  Host only. */
+uint32_t ovhip_output_reduce_divide(uint32_t num, uint32_t n);
+/* Every sample of dst (its own w x h and strides) from the window of src.  One launch (k_output_reduce: luma and both chroma planes),
+ * asynchronous on the ctx stream; allocates nothing.  16-byte loads and stores where a row's address allows, narrower otherwise. */
+int  ovhip_output_reduce_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_pic *dst);
+/* Synchronous conveniences: reduce into the context's grow-only scratch picture (no allocation once a size has been seen; a refused
+ * request allocates nothing), then exactly ovhip_pic_output / ovhip_pic_digest on it; `win` applies to the REDUCED picture. */
+int  ovhip_pic_output_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, int32_t out_w, int32_t out_h,
+                              const ovhip_window *win, void *host_dst);
+int  ovhip_pic_digest_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, int32_t out_w, int32_t out_h,
+                              const ovhip_window *win, uint8_t out16[16]);
 
 /* ------------------------------------------------------------------------------------
  * Film grain synthesis (film grain characteristics SEI, frequency-filtering model): replaces fg_grain_apply_pic
@@ -1808,6 +1859,14 @@ int  ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, 
  * ovhip_frame_set_output_scale answers OVHIP_EUNSUP while grain is set: the reference resamples the ungrained frame over the grained one
  * (post_proc.c:107-126).  A dry frame accepts the call and delivers nothing. */
 int  ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_t poc);
+/* Output at a REDUCED size ("Reduced-size output on the device" above): while set, every output of ovhip_frame_submit and of the last
+ * ovhip_frame_band that shows the picture -- RGB, surface, DIGEST, PACKED, PLANES -- reads ONE reduced picture of out_w x out_h; their
+ * windows, sizes and the caller's planes are those of the reduced size.  The picture hash and the motion field stay at the coded
+ * picture, and what is published to the DPB is the decoded picture, unchanged.  (0, 0) switches it off, which is the default; info is
+ * copied (NULL: no window, chroma_loc 0).  Refusals as ovhip_output_reduce_check against the frame's size.  A frame holds ONE post
+ * setting: OVHIP_EUNSUP while film grain or an output scale is set, and those two setters answer OVHIP_EUNSUP while this is set.  A dry
+ * frame accepts the call and does nothing. */
+int  ovhip_frame_set_output_reduce(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_reduce_info *info);
 /* Decoded picture hash ("Decoded picture hash" above) of every following picture: taken in ovhip_frame_submit and in the last
  * ovhip_frame_band AFTER ovhip_job_wait (a second pass of the ordered pass rewrites the picture), on the decoded picture as it is
  * published -- whatever the output mode, the output scale or the film grain setting are (those post-process a copy).  expected: what
@@ -1982,6 +2041,10 @@ int  ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h
  * (ovhip_frame_set_film_grain); NULL: off.  The frames of OVHIP_OUT_PACKED -- and with them the MD5 of OVHIP_STREAM_FILE_MD5 -- and the
  * fingerprints of OVHIP_OUT_DIGEST are those of the grained pictures.  Refusals as the frame's setter. */
 int  ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params);
+/* Output at a reduced size for the following runs (ovhip_frame_set_output_reduce): call it before a run and before the setters of the
+ * RGB and surface outputs, whose slots are then sized for out_w x out_h.  The output thread's PACKED frames and the frame threads'
+ * DIGEST fingerprints are those of the reduced pictures; (0, 0) switches it off.  Refusals as the frame's setter. */
+int  ovhip_stream_set_output_reduce(ovhip_stream *s, int32_t out_w, int32_t out_h, const ovhip_reduce_info *info);
 /* Decoded picture hashes for the following runs: every frame thread hashes its own picture (ovhip_frame_set_picture_hash; nothing
  * goes through the output thread).  expected: one entry per picture of the stream (index in pics; the caller's array, read during the
  * runs) or NULL: compute only.  method < 0: off.  A mismatch leaves ovhip_stream_result.status at 0. */

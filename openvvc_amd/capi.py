@@ -411,6 +411,11 @@ class Window(C.Structure):
     _fields_ = [("offset_lft", C.c_uint16), ("offset_rgt", C.c_uint16), ("offset_abv", C.c_uint16), ("offset_blw", C.c_uint16)]
 
 
+class ReduceInfo(C.Structure):
+    """ovhip_reduce_info: the source window (chroma units) and the Chroma420SampleLocType of the reduced-size output"""
+    _fields_ = [("win", Window), ("chroma_loc", C.c_uint8), ("rsv", C.c_uint8 * 3)]
+
+
 # ---- frame threads, device DPB, stream driver (include/ovvc_hip.h) ----
 DPB_PIC_ALLOC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.POINTER(Pic))
 DPB_PIC_FREE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(Pic))
@@ -766,6 +771,14 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_ctx_scratch_bytes": (C.c_size_t, [vp]),
         "ovhip_frame_set_output_scale": (C.c_int, [vp, i32, i32, P(ScaleInfo)]),
         "ovhip_stream_set_output_scale": (C.c_int, [vp, i32, i32, P(ScaleInfo)]),
+        "ovhip_output_reduce_check": (C.c_int, [i32, i32, P(ReduceInfo), i32, i32, P(i32 * 4)]),
+        "ovhip_output_reduce_host": (C.c_int, [P(Pic), P(ReduceInfo), P(Pic)]),
+        "ovhip_output_reduce_divide": (u32, [u32, u32]),
+        "ovhip_output_reduce_launch": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(Pic)]),
+        "ovhip_pic_output_reduced": (C.c_int, [vp, P(Pic), P(ReduceInfo), i32, i32, P(Window), vp]),
+        "ovhip_pic_digest_reduced": (C.c_int, [vp, P(Pic), P(ReduceInfo), i32, i32, P(Window), vp]),
+        "ovhip_frame_set_output_reduce": (C.c_int, [vp, i32, i32, P(ReduceInfo)]),
+        "ovhip_stream_set_output_reduce": (C.c_int, [vp, i32, i32, P(ReduceInfo)]),
         "ovhip_frame_set_film_grain": (C.c_int, [vp, P(FgParams), i32]),
         "ovhip_stream_set_film_grain": (C.c_int, [vp, P(FgParams)]),
         "ovhip_fg_derive": (C.c_int, [P(FgParams), P(FgModel), P(FgParams)]),
@@ -852,6 +865,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_rgb_bytes", "ovhip_rgb_coefs", "ovhip_rgb_host", "ovhip_rgb_launch", "ovhip_pic_output_rgb", "ovhip_frame_set_rgb_output", "ovhip_stream_set_rgb_output",
     "ovhip_surface_bytes", "ovhip_surface_host", "ovhip_surface_launch", "ovhip_pic_output_surface", "ovhip_frame_set_surface_output", "ovhip_stream_set_surface_output",
     "ovhip_mvfield_bytes", "ovhip_mvfield_host", "ovhip_mvfield_launch", "ovhip_job_mvfield", "ovhip_frame_set_mvfield_output", "ovhip_stream_set_mvfield_output",
+    "ovhip_output_reduce_check", "ovhip_output_reduce_host", "ovhip_output_reduce_divide", "ovhip_output_reduce_launch", "ovhip_pic_output_reduced", "ovhip_pic_digest_reduced",
+    "ovhip_frame_set_output_reduce", "ovhip_stream_set_output_reduce",
 ]
 
 

@@ -1,6 +1,7 @@
 // Output path: conformance-window crop + pack into the byte layout examples/dectest.c:372-409 writes, and per-row
 // MD5 digests on the device (see include/ovvc_hip.h, "Output path"); and the one post-process step in front of every delivery
-// (ovhip_post_pic_ / ovhip_post_deliver_, ovvc_dpb_priv.h): none, resampled (kernels_scale.hip) or grained (kernels_grain.hip).
+// (ovhip_post_pic_ / ovhip_post_deliver_, ovvc_dpb_priv.h): none, resampled (kernels_scale.hip), grained (kernels_grain.hip) or
+// reduced (kernels_reduce.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -8,6 +9,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_common.hip.h"
 #include "ovvc_dpb_priv.h"
+#include "ovvc_reduce_priv.h"
 
 namespace {
 
@@ -361,14 +363,16 @@ extern "C" int ovhip_post_pic_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip
 {
     if (!ctx || !pic || !post || !shown) return OVHIP_EINVAL;
     if (post->kind == OVHIP_POST_NONE) { *shown = *pic; return OVHIP_OK; }
-    const bool scale = post->kind == OVHIP_POST_SCALE;
-    if (!scale && (post->kind != OVHIP_POST_GRAIN || !post->model)) return OVHIP_EINVAL;
+    const bool scale = post->kind == OVHIP_POST_SCALE, reduce = post->kind == OVHIP_POST_REDUCE, sized = scale || reduce;
+    if (!sized && (post->kind != OVHIP_POST_GRAIN || !post->model)) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     // refusals first: nothing is allocated for a request that will not run
     int r = scale ? ovhip_scale_refusal_(ctx, "scaled output", pic, &post->info, post->out_w, post->out_h)
+          : reduce ? ovhip_reduce_refusal_(ctx, "reduced output", pic, &post->rinfo, post->out_w, post->out_h)
                   : ovhip_grain_refusal_(ctx, "grained output", pic, post->model);
-    if (r == OVHIP_OK) r = post_scratch(ctx, scale ? post->out_w : pic->w, scale ? post->out_h : pic->h, shown);
+    if (r == OVHIP_OK) r = post_scratch(ctx, sized ? post->out_w : pic->w, sized ? post->out_h : pic->h, shown);
     if (r != OVHIP_OK) return r;
+    if (reduce) return ovhip_output_reduce_launch(ctx, pic, &post->rinfo, shown);
     return scale ? ovhip_output_scale_launch(ctx, pic, &post->info, shown) : ovhip_film_grain_launch(ctx, pic, post->model, post->poc, 0, shown);
 }
 
@@ -394,7 +398,7 @@ extern "C" int ovhip_wait_(ovhip_ctx *ctx, const char *what)
     return ov_sync_stream(ctx) != hipSuccess ? ov_fail(ctx, OVHIP_ELAUNCH, what, hipGetLastError()) : OVHIP_OK;
 }
 
-// The four conveniences of the header: their argument checks, then one call of the above -- PACKED into `packed`, or (packed == NULL)
+// The six conveniences of the header: their argument checks, then one call of the above -- PACKED into `packed`, or (packed == NULL)
 // DIGEST into out16.  win == NULL is the empty window.
 static int post_convenience(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ &post, const ovhip_window *win, void *packed, uint8_t *out16)
 {
@@ -433,4 +437,18 @@ extern "C" int ovhip_pic_digest_grain(ovhip_ctx *ctx, const ovhip_pic *pic, cons
 {
     if (!ctx || !pic || !model || !out16) return OVHIP_EINVAL;
     return post_convenience(ctx, pic, { OVHIP_POST_GRAIN, 0, 0, {}, model, poc }, win, nullptr, out16);
+}
+
+extern "C" int ovhip_pic_output_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, int32_t out_w, int32_t out_h,
+                                        const ovhip_window *win, void *host_dst)
+{
+    if (!ctx || !pic || !info || !host_dst) return OVHIP_EINVAL;
+    return post_convenience(ctx, pic, { OVHIP_POST_REDUCE, out_w, out_h, {}, nullptr, 0, *info }, win, host_dst, nullptr);
+}
+
+extern "C" int ovhip_pic_digest_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, int32_t out_w, int32_t out_h,
+                                        const ovhip_window *win, uint8_t out16[16])
+{
+    if (!ctx || !pic || !info || !out16) return OVHIP_EINVAL;
+    return post_convenience(ctx, pic, { OVHIP_POST_REDUCE, out_w, out_h, {}, nullptr, 0, *info }, win, nullptr, out16);
 }

@@ -15,14 +15,15 @@ double ovhip_frame_done_at(const ovhip_frame *f);
 #define OVHIP_HIDDEN_ __attribute__((visibility("hidden")))
 /* ---- the post-process step of the output path (kernels_output.hip): what happens to a finished picture on its way out.  One kind at
  * a time: the reference resamples the UNgrained frame over the grained one, so there is no parity to offer for both. */
-enum { OVHIP_POST_NONE = 0, OVHIP_POST_SCALE, OVHIP_POST_GRAIN };
+enum { OVHIP_POST_NONE = 0, OVHIP_POST_SCALE, OVHIP_POST_GRAIN, OVHIP_POST_REDUCE };
 typedef struct ovhip_post_ {
     int kind;
     int32_t out_w, out_h; ovhip_scale_info info;       /* SCALE: the output size and the scaling window / chroma collocation */
     const ovhip_fg_model *model; int32_t poc;          /* GRAIN: an already derived model (ovhip_fg_derive) and the picture's POC */
+    ovhip_reduce_info rinfo;                           /* REDUCE: out_w x out_h as SCALE's; the source window / chroma location */
 } ovhip_post_;
 /* *shown = the picture the output shows.  NONE: *pic itself, nothing launched, nothing allocated.  Otherwise the refusals of the kind's
- * launcher come first (same codes, reasons in the context's error text), then `pic` is resampled / grained into the context's
+ * launcher come first (same codes, reasons in the context's error text), then `pic` is resampled / grained / reduced into the context's
  * grow-only scratch picture, asynchronously on the context's stream, and that is handed out: it stays valid until the context's next
  * post-processed output.  `pic` is only read. */
 int  ovhip_post_pic_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_ *post, ovhip_pic *shown);
@@ -34,7 +35,8 @@ int  ovhip_post_deliver_(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_post_
 /* the wait for everything enqueued on the context's stream (the frame thread, behind an output's launch: complete on the device at
  * return); `what` names the output in the error text */
 OVHIP_HIDDEN_ int ovhip_wait_(ovhip_ctx *ctx, const char *what);
-/* the launchers' own refusals (kernels_scale.hip, kernels_grain.hip) under the name `who`: ovhip_post_pic_ asks before it allocates */
+/* the launchers' own refusals (kernels_scale.hip, kernels_grain.hip; kernels_reduce.hip's ovhip_reduce_refusal_ is in
+ * ovvc_reduce_priv.h) under the name `who`: ovhip_post_pic_ asks before it allocates */
 OVHIP_HIDDEN_ int ovhip_scale_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *src, const ovhip_scale_info *info, int32_t dst_w, int32_t dst_h);
 OVHIP_HIDDEN_ int ovhip_grain_refusal_(ovhip_ctx *ctx, const char *who, const ovhip_pic *pic, const ovhip_fg_model *model);
 /* ---- RGB output (ovvc_rgb.c, kernels_rgb.hip): what the host twin and the launcher share -- the refusals and everything a loop or a

@@ -56,7 +56,8 @@ struct ovhip_frame {
     int32_t band_row_prev, band_rows_posted, dry_row_prev2;
     int n_bands, n_deferred;
     /* what the outputs do to the picture first (ovvc_dpb_priv.h).  SCALE (ovhip_frame_set_output_scale): resampled to post.out_w x
-     * post.out_h; GRAIN (ovhip_frame_set_film_grain): with film grain at post.poc, the model derived afresh from fg for every picture */
+     * post.out_h; GRAIN (ovhip_frame_set_film_grain): with film grain at post.poc, the model derived afresh from fg for every picture;
+     * REDUCE (ovhip_frame_set_output_reduce): the window post.rinfo names reduced to post.out_w x post.out_h.  ONE kind at a time */
     ovhip_post_ post;
     ovhip_fg_params fg;
     /* decoded picture hash (ovhip_frame_set_picture_hash): what to take of every completed picture, what the caller expects of the next
@@ -398,6 +399,7 @@ ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, const
     if (!f) return OVHIP_EINVAL;
     if (!out_w && !out_h) { if (f->post.kind == OVHIP_POST_SCALE) f->post.kind = OVHIP_POST_NONE; return OVHIP_OK; }
     if (f->post.kind == OVHIP_POST_GRAIN) return OVHIP_EUNSUP;    /* the reference resamples the UNgrained frame over the grained one: no parity to offer */
+    if (f->post.kind == OVHIP_POST_REDUCE) return OVHIP_EUNSUP;   /* one post setting */
     ovhip_scale_info si;
     memset(&si, 0, sizeof(si));
     if (info) si = *info;
@@ -415,11 +417,29 @@ ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_
 {
     if (!f) return OVHIP_EINVAL;
     if (!params) { if (f->post.kind == OVHIP_POST_GRAIN) f->post.kind = OVHIP_POST_NONE; return OVHIP_OK; }
-    if (f->post.kind == OVHIP_POST_SCALE) return OVHIP_EUNSUP;
+    if (f->post.kind == OVHIP_POST_SCALE || f->post.kind == OVHIP_POST_REDUCE) return OVHIP_EUNSUP;
     ovhip_fg_model model;
     const int r = ovhip_fg_derive(params, &model, NULL);      /* the refusals come back here, not from a picture's output */
     if (r != OVHIP_OK) return r;
     f->post.kind = OVHIP_POST_GRAIN; f->post.poc = poc; f->fg = *params;      /* (a dry frame has no output: only remembered) */
+    return OVHIP_OK;
+}
+
+int
+ovhip_frame_set_output_reduce(ovhip_frame *f, int32_t out_w, int32_t out_h, const ovhip_reduce_info *info)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!out_w && !out_h) { if (f->post.kind == OVHIP_POST_REDUCE) f->post.kind = OVHIP_POST_NONE; return OVHIP_OK; }
+    if (f->post.kind == OVHIP_POST_GRAIN || f->post.kind == OVHIP_POST_SCALE) return OVHIP_EUNSUP;      /* one post setting */
+    ovhip_reduce_info ri;
+    memset(&ri, 0, sizeof(ri));
+    if (info) ri = *info;
+    if (!f->dry) {                                                /* (a dry frame has no output: only remembered) */
+        int32_t ratio[4];
+        const int r = ovhip_output_reduce_check(f->w, f->h, &ri, out_w, out_h, ratio);
+        if (r != OVHIP_OK) return r;
+    }
+    f->post.kind = OVHIP_POST_REDUCE; f->post.out_w = out_w; f->post.out_h = out_h; f->post.rinfo = ri;
     return OVHIP_OK;
 }
 

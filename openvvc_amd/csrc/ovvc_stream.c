@@ -53,7 +53,7 @@ struct ovhip_stream {
                                            * ask the DPB for it: a key the DPB never saw is an error there, not a wait) */
     pthread_mutex_t begun_mtx; pthread_cond_t begun_cnd;
     int n_moved, n_sharing;               /* streams replaced to clear the look-ahead thread's hardware queue / still sharing it */
-    ovhip_post_ post; ovhip_fg_params fg;  /* what the outputs do to a picture first (ovvc_dpb_priv.h): ovhip_stream_set_output_scale / _set_film_grain */
+    ovhip_post_ post; ovhip_fg_params fg;  /* what the outputs do to a picture first (ovvc_dpb_priv.h): ovhip_stream_set_output_scale / _set_film_grain / _set_output_reduce */
     /* decoded picture hashes (ovhip_stream_set_picture_hashes): the setting, the caller's expectations (one per picture of the stream, or
      * NULL), and of the last run its pictures' hashes and the verdict */
     int hash_on, hash_method, hash_planes;
@@ -497,7 +497,7 @@ static int
 out_host_follows(ovhip_stream *s, const ovhip_post_ *post)
 {
     if (s->cfg.output != OVHIP_OUT_PACKED) return OVHIP_OK;
-    const int scaled = post->kind == OVHIP_POST_SCALE;
+    const int scaled = post->kind == OVHIP_POST_SCALE || post->kind == OVHIP_POST_REDUCE;
     const size_t bytes = ovhip_output_bytes(scaled ? post->out_w : s->cfg.w, scaled ? post->out_h : s->cfg.h, &s->cfg.window);
     if (!bytes) return OVHIP_EINVAL;
     if (bytes != s->out_host_bytes) {
@@ -516,7 +516,7 @@ ovhip_stream_set_output_scale(ovhip_stream *s, int32_t out_w, int32_t out_h, con
     ovhip_post_ post = s->post;
     int r = OVHIP_OK;
     if (out_w || out_h) {
-        if (post.kind == OVHIP_POST_GRAIN) return OVHIP_EUNSUP;
+        if (post.kind == OVHIP_POST_GRAIN || post.kind == OVHIP_POST_REDUCE) return OVHIP_EUNSUP;
         int32_t scale[4];
         post.kind = OVHIP_POST_SCALE; post.out_w = out_w; post.out_h = out_h;
         memset(&post.info, 0, sizeof(post.info));
@@ -537,7 +537,7 @@ ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params)
     if (!s) return OVHIP_EINVAL;
     ovhip_post_ post = s->post;
     if (params) {
-        if (post.kind == OVHIP_POST_SCALE) return OVHIP_EUNSUP;
+        if (post.kind == OVHIP_POST_SCALE || post.kind == OVHIP_POST_REDUCE) return OVHIP_EUNSUP;
         post.kind = OVHIP_POST_GRAIN;
     } else if (post.kind == OVHIP_POST_GRAIN)
         post.kind = OVHIP_POST_NONE;
@@ -546,6 +546,28 @@ ovhip_stream_set_film_grain(ovhip_stream *s, const ovhip_fg_params *params)
     for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_film_grain(s->frames[i], params, 0);
     if (r == OVHIP_OK) r = out_host_follows(s, &post);          /* (grain leaves the size alone: nothing moves today) */
     if (r == OVHIP_OK) { s->post = post; if (params) s->fg = *params; }
+    return r;
+}
+
+int
+ovhip_stream_set_output_reduce(ovhip_stream *s, int32_t out_w, int32_t out_h, const ovhip_reduce_info *info)
+{
+    if (!s) return OVHIP_EINVAL;
+    ovhip_post_ post = s->post;
+    int r = OVHIP_OK;
+    if (out_w || out_h) {
+        if (post.kind == OVHIP_POST_GRAIN || post.kind == OVHIP_POST_SCALE) return OVHIP_EUNSUP;      /* one post setting */
+        int32_t ratio[4];
+        post.kind = OVHIP_POST_REDUCE; post.out_w = out_w; post.out_h = out_h;
+        memset(&post.rinfo, 0, sizeof(post.rinfo));
+        if (info) post.rinfo = *info;
+        r = ovhip_output_reduce_check(s->cfg.w, s->cfg.h, &post.rinfo, out_w, out_h, ratio);
+    } else if (post.kind == OVHIP_POST_REDUCE)
+        post.kind = OVHIP_POST_NONE;
+    if (r == OVHIP_OK) r = out_host_follows(s, &post);
+    /* the frame threads' outputs: DIGEST, RGB, surface */
+    for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_output_reduce(s->frames[i], out_w, out_h, &post.rinfo);
+    if (r == OVHIP_OK) s->post = post;
     return r;
 }
 
@@ -562,11 +584,11 @@ ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, const
     return OVHIP_OK;
 }
 
-/* the size the stream outputs: its output scale's, else its pictures' */
+/* the size the stream outputs: its output scale's or reduced size, else its pictures' */
 static void
 out_size(const ovhip_stream *s, int32_t *w, int32_t *h)
 {
-    const int scaled = s->post.kind == OVHIP_POST_SCALE;
+    const int scaled = s->post.kind == OVHIP_POST_SCALE || s->post.kind == OVHIP_POST_REDUCE;
     *w = scaled ? s->post.out_w : s->cfg.w; *h = scaled ? s->post.out_h : s->cfg.h;
 }
 

@@ -75,6 +75,14 @@ def _surface_tensor(tensor, fmt: capi.SurfaceFormat, need: int, slots: bool = Fa
     return _device_tensor(tensor, "surface output", allowed, need=need, slots=slots)
 
 
+def reduce_check(src_w: int, src_h: int, dst_w: int, dst_h: int, src_window=(0, 0, 0, 0), chroma_loc: int = 0) -> "tuple[int, tuple]":
+    """(code, (p_x, q_x, p_y, q_y)) of ovhip_output_reduce_check: whether src_w x src_h under src_window reduces to dst_w x dst_h
+    (include/ovvc_hip.h, "Reduced-size output on the device").  Host only."""
+    ratio = (C.c_int32 * 4)()
+    r = capi.load().ovhip_output_reduce_check(src_w, src_h, C.byref(capi.ReduceInfo(capi.Window(*src_window), chroma_loc)), dst_w, dst_h, ratio)
+    return r, tuple(ratio)
+
+
 def mvfield_format(dtype: int = capi.MVF_I32, layout: int = capi.MVF_PLANAR, vectors: int = capi.MVF_UNIT) -> capi.MvfieldFormat:
     """an ovhip_mvfield_format (include/ovvc_hip.h, "Motion field output on the device")"""
     return capi.MvfieldFormat(dtype, layout, vectors, 0)
@@ -509,6 +517,24 @@ class DevPic:
 
     def digest_scaled(self, out_w: int, out_h: int, scale_window=(0, 0, 0, 0), col=(0, 0), window=(0, 0, 0, 0)) -> bytes:
         return self._digest16(window, "pic_digest_scaled", C.byref(capi.ScaleInfo(*scale_window, *col)), out_w, out_h)
+
+    def reduce_into(self, dst: "DevPic", src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
+        """The exact area average of this picture's window (chroma sample units) into dst, its own smaller size
+        (ovhip_output_reduce_launch; include/ovvc_hip.h, "Reduced-size output on the device").  Asynchronous."""
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        r = self.ctx.lib.ovhip_output_reduce_launch(self.ctx.h, C.byref(self.s), C.byref(info), C.byref(dst.s))
+        if check:
+            self.ctx._chk(r, "output_reduce")
+        return r
+
+    def output_reduced(self, out_w: int, out_h: int, src_window=(0, 0, 0, 0), chroma_loc: int = 0, window=(0, 0, 0, 0)) -> np.ndarray:
+        """output() of the picture reduced to out_w x out_h; `window` crops the reduced picture"""
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        return self._packed(out_w, out_h, window, "pic_output_reduced", C.byref(info), out_w, out_h)
+
+    def digest_reduced(self, out_w: int, out_h: int, src_window=(0, 0, 0, 0), chroma_loc: int = 0, window=(0, 0, 0, 0)) -> bytes:
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        return self._digest16(window, "pic_digest_reduced", C.byref(info), out_w, out_h)
 
     def _fg_model(self, params: capi.FgParams) -> capi.FgModel:
         r, model, _ = capi.fg_derive(self.ctx.lib, params)
@@ -1058,6 +1084,16 @@ class Frame:
             self._out_size = (out_w, out_h) if out_w or out_h else None
         return r
 
+    def set_output_reduce(self, out_w: int, out_h: int, src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
+        """the frame's outputs (RGB, surface, PACKED / PLANES / DIGEST) read the picture reduced to out_w x out_h; (0, 0) switches it off"""
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        r = self.lib.ovhip_frame_set_output_reduce(self.f, out_w, out_h, C.byref(info))
+        if r < 0 and check:
+            raise EngineError(f"frame_set_output_reduce: {r}")
+        if r >= 0:
+            self._out_size = (out_w, out_h) if out_w or out_h else None
+        return r
+
     def set_rgb_output(self, dst, fmt: "capi.RgbFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_rgb_output: the NEXT picture completed is also written as RGB into `dst` -- a torch tensor on the device of
         shape (3, H, W) / (H, W, 3) for the size the frame outputs (checked here), or a device address with `nbytes`; fmt None: off"""
@@ -1138,6 +1174,17 @@ class Stream:
         r = self.lib.ovhip_stream_set_output_scale(self.s, out_w, out_h, C.byref(info))
         if r < 0 and check:
             raise EngineError(f"stream_set_output_scale: {r}")
+        if r >= 0:
+            self._out_size = (out_w, out_h) if out_w or out_h else None
+        return r
+
+    def set_output_reduce(self, out_w: int, out_h: int, src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
+        """before a run and before the RGB / surface setters: every output that shows the picture reads it reduced to out_w x out_h;
+        (0, 0): off"""
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        r = self.lib.ovhip_stream_set_output_reduce(self.s, out_w, out_h, C.byref(info))
+        if r < 0 and check:
+            raise EngineError(f"stream_set_output_reduce: {r}")
         if r >= 0:
             self._out_size = (out_w, out_h) if out_w or out_h else None
         return r
