@@ -1292,8 +1292,9 @@ int  ovhip_pic_hash(ovhip_ctx *ctx, const ovhip_pic *pic, int method, int n_plan
  *            float converted round-to-nearest-even.
  *   layout   PLANAR: the R plane, the G plane, the B plane, each H x W (CHW); PACKED: H x W x 3 (HWC).  Both tight.
  * matrix = H.273 MatrixCoefficients: 1 (Kr 0.2126, Kb 0.0722), 5 and 6 (0.299, 0.114), 9 (0.2627, 0.0593); 2 (unspecified) is
- * OVHIP_EINVAL -- the caller must decide --, every other value OVHIP_EUNSUP.  Not done: transfer functions, tone mapping,
- * constant-luminance and ICtCp matrices, normalisation; a smaller tensor comes from "Reduced-size output on the device" below.
+ * OVHIP_EINVAL -- the caller must decide --, every other value OVHIP_EUNSUP.  Not done: constant-luminance and ICtCp matrices,
+ * normalisation; transfer functions and tone mapping are the caller's, as a table: "RGB output through a colour table" below; a
+ * smaller tensor comes from "Reduced-size output on the device" below.
  * ---------------------------------------------------------------------------------- */
 enum { OVHIP_RGB_U8 = 0, OVHIP_RGB_U16 = 1, OVHIP_RGB_F16 = 2, OVHIP_RGB_F32 = 3 };      /* ovhip_rgb_format.dtype */
 enum { OVHIP_RGB_PLANAR = 0, OVHIP_RGB_PACKED = 1 };                                       /* ovhip_rgb_format.layout */
@@ -1316,6 +1317,56 @@ int  ovhip_rgb_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *
 /* Synchronous convenience beside ovhip_pic_output: the launch into the context's grow-only scratch, then one D2H into host_dst
  * (dst_bytes >= ovhip_rgb_bytes, pinned or pageable). */
 int  ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, void *host_dst, size_t dst_bytes);
+
+/* ------------------------------------------------------------------------------------
+ * RGB output through a colour table: the RGB output above with one table-driven step between its clip and its store -- a 3D colour
+ * lookup table with tetrahedral interpolation, what a .cube file or a baked colour transform is.  The caller owns the colour science
+ * (transfer function, tone mapping, gamut: all in the table's entries), the library one exact step: integer only, so every
+ * implementation of it (tests/spec_rgb_lut.py, ovhip_rgb_lut_host, k_rgb_lut) is compared for equality.
+ *
+ *   Input    everything up to and including the clip as "RGB output on the device", with one difference: the coefficients and the
+ *            clip are those of N = 10 (peak 1023) WHATEVER the dtype -- a U8 destination does not select the 8-bit coefficients.  The
+ *            step works on (R, G, B) in 0..1023.
+ *   Table    uint16_t table[S][S][S][3], S one of 17, 33, 65, n = S - 1; index order [b][g][r][c]: r is fastest, c = 0, 1, 2 the
+ *            OUTPUT's R, G, B.  A peak P in 1..65535; every entry <= P.
+ *   Cell     per input channel value v: t = v n, i = t / 1023, f = t - 1023 i; if i == n (only at v = 1023) then i = n - 1 and
+ *            f = 1023.  So f is in 0..1023 and the cell is (i_r, i_g, i_b).
+ *   Tetra    order the three channels by f descending, f1 >= f2 >= f3.  V0 = the cell's vertex (i_r, i_g, i_b); V1 = V0 with the
+ *            index of f1's channel raised by 1; V2 = V1 with f2's channel raised by 1; V3 = V2 with f3's channel raised by 1: the
+ *            opposite corner.  w0 = 1023 - f1, w1 = f1 - f2, w2 = f2 - f3, w3 = f3 (their sum is 1023); per output channel c
+ *              o_c = (w0 T[V0][c] + w1 T[V1][c] + w2 T[V2][c] + w3 T[V3][c] + 511) / 1023
+ *            -- an integer division of a non-negative value of at most 1023 * 65535 + 511 < 2^26: int32 holds it.  When two f are
+ *            equal the order between them does not change o, because the vertex in question has the weight 0: an implementation may
+ *            break ties any way it likes.
+ *   dtype    U8 (requires P <= 255), U16: o.  F32: (float)o * (float)(1.0 / P), one multiplication, round to nearest.  F16: that
+ *            float converted round-to-nearest-even, subnormal halves included (they occur when P > 16384).
+ *   layout   PLANAR, PACKED as above; the size is that of the RGB output above.
+ * With the lattice table T[b][g][r] = (1023 r, 1023 g, 1023 b) and P = 65535 the output is exactly n (R, G, B).
+ * Not done: 1D shaper tables in front of the cube, other sizes, trilinear interpolation, float tables, a table per picture from dynamic
+ * metadata, a table on the surface output.
+ * ---------------------------------------------------------------------------------- */
+typedef struct ovhip_rgb_lut ovhip_rgb_lut;          /* opaque: the table in device memory of ctx's device, S, P */
+/* OVHIP_OK for a size of 17, 33 or 65 and a peak in 1..65535 that fmt's dtype can store (U8: peak <= 255; fmt NULL: any dtype), else
+ * OVHIP_EINVAL.  Host only. */
+int  ovhip_rgb_lut_check(int size, int peak, const ovhip_rgb_format *fmt);
+/* The table on ctx's device: size and peak validated as above, every entry checked against the peak on the host (OVHIP_EINVAL, the
+ * first offending index in the context's error text), repacked to 8-byte texels (R, G, B, 0), uploaded once and waited for.  The table
+ * is immutable afterwards; host_table is not kept.  Any context of the same device may use it, from any thread. */
+int  ovhip_rgb_lut_create(ovhip_ctx *ctx, int size, int peak, const uint16_t *host_table, ovhip_rgb_lut **out);
+/* After the last launch that reads it is complete.  NULL: nothing. */
+void ovhip_rgb_lut_destroy(ovhip_rgb_lut *lut);
+/* The definition on host planes and a host table into host memory: tests, and callers that hold the picture on the host.  Refusals as
+ * the launch's, and a table entry above the peak (OVHIP_EINVAL); nothing is written when it refuses. */
+int  ovhip_rgb_lut_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
+                        const ovhip_window *win, const ovhip_rgb_format *fmt, int size, int peak, const uint16_t *host_table, void *dst, size_t dst_bytes);
+/* As the RGB launch above: d_dst in DEVICE memory, at least ovhip_rgb_bytes bytes, aligned to its element; asynchronous on the ctx
+ * stream; allocates nothing.  Refused before anything is launched, the reason in the context's error text: everything the RGB launch
+ * refuses, a null table, a table of another device, U8 with a table peak above 255 (OVHIP_EINVAL). */
+int  ovhip_rgb_lut_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, const ovhip_rgb_lut *lut,
+                          void *d_dst, size_t dst_bytes);
+/* Synchronous convenience: the launch into the context's grow-only scratch, then one D2H into host_dst. */
+int  ovhip_pic_output_rgb_lut(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_rgb_format *fmt, const ovhip_rgb_lut *lut,
+                              void *host_dst, size_t dst_bytes);
 
 /* ------------------------------------------------------------------------------------
  * Surface output on the device: a finished 10-bit 4:2:0 picture as a 4:2:0 SURFACE in DEVICE memory -- the picture's own samples in the
@@ -1886,6 +1937,13 @@ int  ovhip_frame_picture_hash(const ovhip_frame *f, ovhip_pic_hash_value *comput
  * The format's refusals come back here, the launch's from the picture's last call: a failed conversion fails that call's return
  * value, never the picture's publication.  A dry frame accepts the call and does nothing. */
 int  ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
+/* A colour table ("RGB output through a colour table" above) for the frame's RGB output.  Unlike the destination the setting is
+ * STICKY: while a table is set, every RGB output of this frame goes through it (ovhip_rgb_lut_launch in the place of ovhip_rgb_launch,
+ * after the post-process step: the window, film grain, the output scale and the reduced size compose with it); lut NULL switches it
+ * off, which is the default, and the frame's calls are then what they were.  The table is borrowed: the caller keeps it alive while it
+ * is set.  OVHIP_EINVAL for a table on another device than the frame's context; the launch's refusals (U8 with a peak above 255) come
+ * from the picture's last call.  A dry frame accepts the call and does nothing. */
+int  ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut);
 /* Surface output ("Surface output on the device" above) of the NEXT picture completed, exactly as the RGB output beside it: per
  * picture, fmt NULL switches it off (the default); the conversion runs in ovhip_frame_submit and in the last ovhip_frame_band after
  * ovhip_job_wait, on the picture the output shows (after the frame's post-process step; win is in chroma units of THAT picture),
@@ -2058,6 +2116,12 @@ int  ovhip_stream_picture_hashes(const ovhip_stream *s, ovhip_pic_hash_value *co
  * ovhip_rgb_bytes for the size the stream outputs (its output scale's, else its pictures'); the format's refusals as
  * ovhip_rgb_coefs.  A slot is the caller's to reuse once the picture n_slots later is decoded: the driver does not wait for a reader. */
 int  ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
+/* A colour table for the RGB output of the following runs (ovhip_frame_set_rgb_lut on every frame): one upload per device the stream
+ * drives, through the context of that device's first frame; the stream owns the tables until the setting is cleared (host_table NULL)
+ * or replaced, or the stream is destroyed.  host_table is not kept.  The refusals of ovhip_rgb_lut_create, the reason in
+ * ovhip_last_error of that context; on a refusal the previous setting stands.  The slot size is still ovhip_rgb_bytes.  Between runs
+ * only. */
+int  ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table);
 /* Surface output for the following runs, as the RGB output above and independent of it: picture idx lands at
  * d_base + (idx % n_slots) * bytes_per_picture in DEVICE memory, written by the frame thread that completes it
  * (ovhip_frame_set_surface_output), whatever the stream's output mode is.  fmt NULL: off.  OVHIP_EINVAL for a null base, n_slots 0, a

@@ -805,6 +805,14 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_rgb": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, C.c_size_t]),
         "ovhip_frame_set_rgb_output": (C.c_int, [vp, P(RgbFormat), P(Window), vp, C.c_size_t]),
         "ovhip_stream_set_rgb_output": (C.c_int, [vp, P(RgbFormat), P(Window), vp, C.c_size_t, u32]),
+        "ovhip_rgb_lut_check": (C.c_int, [C.c_int, C.c_int, P(RgbFormat)]),
+        "ovhip_rgb_lut_create": (C.c_int, [vp, C.c_int, C.c_int, vp, P(vp)]),
+        "ovhip_rgb_lut_destroy": (None, [vp]),
+        "ovhip_rgb_lut_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(RgbFormat), C.c_int, C.c_int, vp, vp, C.c_size_t]),
+        "ovhip_rgb_lut_launch": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, vp, C.c_size_t]),
+        "ovhip_pic_output_rgb_lut": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, vp, C.c_size_t]),
+        "ovhip_frame_set_rgb_lut": (C.c_int, [vp, vp]),
+        "ovhip_stream_set_rgb_lut": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "ovhip_surface_bytes": (C.c_size_t, [i32, i32, P(Window), P(SurfaceFormat)]),
         "ovhip_surface_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(SurfaceFormat), vp, C.c_size_t]),
         "ovhip_surface_launch": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
@@ -863,6 +871,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_pic_hash_host", "ovhip_pic_hash_parse_sei", "ovhip_pic_hash_equal", "ovhip_pic_hash_launch", "ovhip_pic_hash",
     "ovhip_frame_set_picture_hash", "ovhip_frame_picture_hash", "ovhip_stream_set_picture_hashes", "ovhip_stream_picture_hashes",
     "ovhip_rgb_bytes", "ovhip_rgb_coefs", "ovhip_rgb_host", "ovhip_rgb_launch", "ovhip_pic_output_rgb", "ovhip_frame_set_rgb_output", "ovhip_stream_set_rgb_output",
+    "ovhip_rgb_lut_check", "ovhip_rgb_lut_create", "ovhip_rgb_lut_destroy", "ovhip_rgb_lut_host", "ovhip_rgb_lut_launch", "ovhip_pic_output_rgb_lut",
+    "ovhip_frame_set_rgb_lut", "ovhip_stream_set_rgb_lut",
     "ovhip_surface_bytes", "ovhip_surface_host", "ovhip_surface_launch", "ovhip_pic_output_surface", "ovhip_frame_set_surface_output", "ovhip_stream_set_surface_output",
     "ovhip_mvfield_bytes", "ovhip_mvfield_host", "ovhip_mvfield_launch", "ovhip_job_mvfield", "ovhip_frame_set_mvfield_output", "ovhip_stream_set_mvfield_output",
     "ovhip_output_reduce_check", "ovhip_output_reduce_host", "ovhip_output_reduce_divide", "ovhip_output_reduce_launch", "ovhip_pic_output_reduced", "ovhip_pic_digest_reduced",

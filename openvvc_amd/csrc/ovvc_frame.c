@@ -17,6 +17,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_dpb_priv.h"
 #include "ovvc_mvfield_priv.h"
+#include "ovvc_rgb_lut_priv.h"
 
 #define MAX_REFS 16
 
@@ -67,6 +68,8 @@ struct ovhip_frame {
     /* the per-picture outputs (ovhip_frame_set_rgb_output / _surface_output / _mvfield_output) of the NEXT picture completed, each
      * independent of the others: the destinations are that picture's, so the settings end with it (picture_end) */
     frame_out outs[N_OUTS];
+    /* the colour table of the RGB output (ovhip_frame_set_rgb_lut): sticky, borrowed, NULL: none */
+    const ovhip_rgb_lut *rgb_lut;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -491,6 +494,15 @@ ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ov
 }
 
 int
+ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (lut && !f->dry && !ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
+    f->rgb_lut = f->dry ? NULL : lut;                          /* (a dry frame has no picture to convert) */
+    return OVHIP_OK;
+}
+
+int
 ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
 {
     if (!f) return OVHIP_EINVAL;
@@ -564,7 +576,9 @@ picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_fram
         else f->hash_done = !f->hash_expect || ovhip_pic_hash_equal(&f->hash_computed, &f->hash_expected) ? 1 : -1;
     }
     if (r == OVHIP_OK && rgb->on) {
-        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_rgb_launch(f->ctx, &shown, &rgb->win, &rgb->fmt.rgb, rgb->dst[0], rgb->bytes[0]);
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK)
+            r = f->rgb_lut ? ovhip_rgb_lut_launch(f->ctx, &shown, &rgb->win, &rgb->fmt.rgb, f->rgb_lut, rgb->dst[0], rgb->bytes[0])
+                           : ovhip_rgb_launch(f->ctx, &shown, &rgb->win, &rgb->fmt.rgb, rgb->dst[0], rgb->bytes[0]);
         if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "RGB output");
         if (r != OVHIP_OK) fail(f, r, "RGB output");
     }

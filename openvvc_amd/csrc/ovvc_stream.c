@@ -65,6 +65,7 @@ struct ovhip_stream {
     ovhip_rgb_format rgb_fmt; ovhip_surface_format surf_fmt; ovhip_mvfield_format mvf_fmt;
     ovhip_window rgb_win, surf_win;
     slot_buf rgb_buf, surf_buf, mvf_vec, mvf_info;
+    ovhip_rgb_lut **rgb_luts;             /* [n_dev], or NULL: the colour tables of the RGB output (ovhip_stream_set_rgb_lut), owned */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -477,6 +478,8 @@ ovhip_stream_destroy(ovhip_stream *s)
     for (int i = 0; s->frames && i < s->n_dev * s->tpd; ++i) ovhip_frame_destroy(s->frames[i]);
     for (int k = 0; s->out_ctx && k < s->n_dev; ++k) ovhip_ctx_destroy(s->out_ctx[k]);
     ovhip_host_free(s->out_host);
+    for (int k = 0; s->rgb_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->rgb_luts[k]);      /* (behind the frames that borrowed them) */
+    free(s->rgb_luts);
     free(s->ph);
     for (uint32_t i = 0; s->job_mtx && i < s->n_jobs; ++i) pthread_mutex_destroy(&s->job_mtx[i]);
     free(s->frames); free(s->out_ctx); free(s->job_mtx);
@@ -614,6 +617,33 @@ ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const 
     out_size(s, &w, &h);
     if (slot_buf_set(&s->rgb_buf, d_base, bytes_per_picture, n_slots, ovhip_rgb_bytes(w, h, win, fmt)) != OVHIP_OK) return OVHIP_EINVAL;
     s->rgb_on = 1; s->rgb_fmt = *fmt; s->rgb_win = win ? *win : (ovhip_window){ 0, 0, 0, 0 };
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table)
+{
+    if (!s) return OVHIP_EINVAL;
+    ovhip_rgb_lut **luts = NULL;
+    int r = OVHIP_OK;
+    if (host_table) {
+        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
+        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
+        if (!luts) return OVHIP_ENOMEM;
+        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
+        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_rgb_lut(s->frames[i], luts[i / s->tpd]);
+        if (r != OVHIP_OK) {
+            /* the previous setting stands */
+            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_lut(s->frames[i], s->rgb_luts ? s->rgb_luts[i / s->tpd] : NULL);
+            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
+            free(luts);
+            return r;
+        }
+    } else
+        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_lut(s->frames[i], NULL);
+    for (int k = 0; s->rgb_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->rgb_luts[k]);
+    free(s->rgb_luts);
+    s->rgb_luts = luts;
     return OVHIP_OK;
 }
 

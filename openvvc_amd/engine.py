@@ -453,6 +453,37 @@ class DevBuf:
         return out
 
 
+def _lut_table(table, what: str) -> "tuple[np.ndarray, int]":
+    """a colour table as the C ABI takes it: contiguous uint16 of shape (S, S, S, 3), index order [b][g][r][c] -> (array, S)"""
+    if not isinstance(table, np.ndarray) or table.dtype != np.uint16 or table.ndim != 4 or table.shape[3] != 3 or len(set(table.shape[:3])) != 1:
+        raise EngineError(f"{what}: the table must be a numpy array of shape (S, S, S, 3) and dtype uint16")
+    return np.ascontiguousarray(table), int(table.shape[0])
+
+
+class RgbLut:
+    """ovhip_rgb_lut: a 3D colour table on the device of `ctx` (include/ovvc_hip.h, "RGB output through a colour table"); table: numpy
+    uint16 of shape (S, S, S, 3), S one of 17, 33, 65, index order [b][g][r][c], every entry <= peak.  Immutable; usable from every
+    context of that device.  openvvc_amd.lut3d builds tables."""
+
+    def __init__(self, ctx: Context, table: np.ndarray, peak: int):
+        table, size = _lut_table(table, "RgbLut")
+        self.lib, self.size, self.peak = ctx.lib, size, int(peak)
+        h = C.c_void_p()
+        ctx._chk(ctx.lib.ovhip_rgb_lut_create(ctx.h, size, self.peak, table.ctypes.data, C.byref(h)), "rgb_lut_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.lib.ovhip_rgb_lut_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class DevPic:
     def __init__(self, ctx: Context, s: capi.Pic, owns: bool):
         self.ctx, self.s, self.owns = ctx, s, owns
@@ -575,24 +606,31 @@ class DevPic:
             self.ctx._chk(r, "pic_hash_launch")
         return r
 
-    def rgb(self, fmt: capi.RgbFormat, window=(0, 0, 0, 0)) -> np.ndarray:
+    def rgb(self, fmt: capi.RgbFormat, window=(0, 0, 0, 0), lut: "RgbLut | None" = None) -> np.ndarray:
         """ovhip_pic_output_rgb: this picture as RGB (include/ovvc_hip.h, "RGB output on the device"), converted on the device and
-        fetched with one D2H -> (3, H, W) or (H, W, 3) in the format's dtype"""
+        fetched with one D2H -> (3, H, W) or (H, W, 3) in the format's dtype.  lut: through that colour table
+        (ovhip_pic_output_rgb_lut, "RGB output through a colour table")"""
         win = capi.Window(*window)
         n = self.ctx.lib.ovhip_rgb_bytes(self.w, self.h, C.byref(win), C.byref(fmt))
         if not n:
             raise EngineError("rgb: bad size / window / format")
         out = np.empty(rgb_shape(fmt, self.w, self.h, window), capi.RGB_NP_DTYPE[fmt.dtype])
-        self.ctx._chk(self.ctx.lib.ovhip_pic_output_rgb(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), out.ctypes.data, out.nbytes), "pic_output_rgb")
+        if lut is None:
+            self.ctx._chk(self.ctx.lib.ovhip_pic_output_rgb(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), out.ctypes.data, out.nbytes), "pic_output_rgb")
+        else:
+            self.ctx._chk(self.ctx.lib.ovhip_pic_output_rgb_lut(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), lut.h, out.ctypes.data, out.nbytes),
+                          "pic_output_rgb_lut")
         return out
 
-    def rgb_into(self, ptr: int, nbytes: int, fmt: capi.RgbFormat, window=(0, 0, 0, 0), check: bool = True) -> int:
-        """ovhip_rgb_launch into device memory at `ptr` (a DevBuf's address plus an offset, a tensor's data_ptr()).  Asynchronous."""
+    def rgb_into(self, ptr: int, nbytes: int, fmt: capi.RgbFormat, window=(0, 0, 0, 0), check: bool = True, lut: "RgbLut | None" = None) -> int:
+        """ovhip_rgb_launch into device memory at `ptr` (a DevBuf's address plus an offset, a tensor's data_ptr()).  Asynchronous.
+        lut: through that colour table (ovhip_rgb_lut_launch)"""
         win = capi.Window(*window)
-        r = self.ctx.lib.ovhip_rgb_launch(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt) if fmt is not None else None,
-                                          C.c_void_p(ptr) if ptr else None, nbytes)
+        args = (self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt) if fmt is not None else None)
+        dst = (C.c_void_p(ptr) if ptr else None, nbytes)
+        r = self.ctx.lib.ovhip_rgb_launch(*args, *dst) if lut is None else self.ctx.lib.ovhip_rgb_lut_launch(*args, lut.h, *dst)
         if check:
-            self.ctx._chk(r, "rgb_launch")
+            self.ctx._chk(r, "rgb_launch" if lut is None else "rgb_lut_launch")
         return r
 
     def surface(self, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0)) -> np.ndarray:
@@ -1099,6 +1137,16 @@ class Frame:
         shape (3, H, W) / (H, W, 3) for the size the frame outputs (checked here), or a device address with `nbytes`; fmt None: off"""
         return _set_output(self, "rgb", fmt, [(dst, nbytes)], window, check=check)
 
+    def set_rgb_lut(self, lut: "RgbLut | None", check: bool = True) -> int:
+        """ovhip_frame_set_rgb_lut: while set, every RGB output of this frame goes through the colour table (sticky, unlike the
+        destination; kept alive here); None: off"""
+        r = self.lib.ovhip_frame_set_rgb_lut(self.f, lut.h if lut is not None else None)
+        if check and r:
+            raise EngineError(f"frame_set_rgb_lut: {r}")
+        if r == 0:
+            self._rgb_lut = lut
+        return r
+
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_surface_output: the NEXT picture completed is also written as a surface into `dst` -- a contiguous torch
         tensor on the device (uint8, or int16 / uint16 for the 16-bit formats) of at least the surface's bytes for the size the frame
@@ -1195,6 +1243,18 @@ class Stream:
         tensor on the device of shape (n, 3, H, W) / (n, H, W, 3) for the size the stream outputs (checked here, kept alive here), or
         a device address with bytes_per_picture and n_slots; fmt None: off"""
         return _set_output(self, "rgb", fmt, [(dst, bytes_per_picture)], window, n_slots, check)
+
+    def set_rgb_lut(self, table: "np.ndarray | None", peak: int = 0, check: bool = True) -> int:
+        """ovhip_stream_set_rgb_lut: the RGB output of the following runs goes through the colour table (numpy uint16 of shape
+        (S, S, S, 3), uploaded once per device, owned by the stream); None: off"""
+        if table is None:
+            r = self.lib.ovhip_stream_set_rgb_lut(self.s, 0, 0, None)
+        else:
+            table, size = _lut_table(table, "stream_set_rgb_lut")
+            r = self.lib.ovhip_stream_set_rgb_lut(self.s, size, int(peak), table.ctypes.data)
+        if check and r:
+            raise EngineError(f"stream_set_rgb_lut: {r}")
+        return r
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
                            n_slots: "int | None" = None, check: bool = True) -> int:
