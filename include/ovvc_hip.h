@@ -344,9 +344,11 @@ int ovhip_lmcs_build(const ovhip_lmcs_data *data, ovhip_lmcs_luts *out);
  * (dbf_load_info/dbf_store_info, drv_lines.c:618-761).  The recorder (ovhip_rec_dbf_ctu) runs the
  * edge enumeration, bS / QP lookup and filter-length derivation of vvc_dbf_ctu_hor/_ver and
  * vvc_dbf_chroma_hor/_ver (rcn_df.c:1151-1431, :1876-2167) WITHOUT touching samples and writes one
- * 16-bit parameter word per 4-sample edge segment into picture-level planes; the device then
- * filters all vertical edges of the picture, then all horizontal edges (ovhip_dbf_launch), which
- * yields the same samples as the reference's per-CTU V-then-H order.
+ * 16-bit parameter word per 4-sample edge segment; the device then filters all vertical edges of
+ * the picture, then all horizontal edges, which yields the same samples as the reference's per-CTU
+ * V-then-H order.  The decode path filters from the compact edge lists of those
+ * words (ovhip_dbf_launch_edges*); ovhip_dbf_launch applies the same filter to the picture-level
+ * planes laid out below.
  *
  * luma word   : bits 0-1 bS (0 = edge not filtered), 2-4 max filter length P side (1,2,3,5,7),
  *               5-7 max filter length Q side, 8-15 average QP byte of the two blocks

@@ -2,14 +2,20 @@
 //
 // Two launches per picture: every vertical edge (luma + Cb + Cr), then every horizontal edge --
 // the picture-level order the reference's per-CTU "vertical edges, then horizontal edges shifted
-// 8 samples left" schedule reproduces (libovvc/rcn_df.c:2099-2106, :2169-2198).  One lane per
-// 4-sample edge segment (2 chroma lines): the lane reads its 16-bit parameter word (bS, maximum
-// filter lengths, average QP -- produced on the host by ovhip_rec_dbf_ctu), derives tc / beta
-// (Table 43), evaluates the on/off + strong/weak + long-filter decisions on lines 0 and 3 and
-// filters its 4 lines in place.  Segments of one direction never touch each other's samples
-// (H.266 8.8.3: filter lengths are bounded by half the distance to the next edge), so all lanes
-// run independently.  Horizontal edges map lanes to consecutive columns (coalesced rows);
-// vertical edges read 16 samples per line per lane from the same rows as their neighbours (L1/L2).
+// 8 samples left" schedule reproduces (libovvc/rcn_df.c:2099-2106, :2169-2198).
+//
+// The filter is the quad form (luma_quad / chroma_quad): four lanes per 4-sample edge segment, one
+// line each (chroma: 2 lines, lanes 2 and 3 shadow lanes 0 and 1).  A quad shares the segment's
+// 16-bit parameter word (bS, maximum filter lengths, average QP -- produced on the host by
+// ovhip_rec_dbf_ctu) and derives tc / beta from it (Table 43); every lane loads its line once, the
+// on/off + strong/weak + long-filter decisions, which the reference takes on lines 0 and 3
+// (chroma: 0 and 1), travel by DPP quad broadcast, and the lane filters its line in place.
+// Segments of one direction never touch each other's samples (H.266 8.8.3: filter lengths are
+// bounded by half the distance to the next edge), so all quads run independently.
+//
+// Two kernels drive it.  k_dbf_list takes the compact edge lists (ovhip_dbf_compact, the recorder):
+// four lanes per list entry -- the decode path.  k_dbf walks the dense edge planes
+// (ovhip_dbf_planes): four lanes per plane word, and a quad whose word carries no edge leaves.
 //
 // Replaces filter_vertical_edge / filter_horizontal_edge(_c), use_strong_filter_*, the 22 long
 // filters filter_{h,v}_{3,5,7}_{3,5,7}, filter_luma_strong_small_*, filter_luma_weak_*,
@@ -44,14 +50,6 @@ __device__ __forceinline__ Lim dbf_limits(int qp, int bs, int tc_off, int beta_o
 // One line across the edge held in registers: s[8 + i] = q_i, s[7 - i] = p_i.
 struct Line16 { int s[16]; };
 
-template <int NP, int NQ>
-__device__ __forceinline__ void load_line(const uint16_t *pix, int step, int *s)
-{
-#pragma unroll
-    for (int i = 0; i < NP; ++i) s[7 - i] = pix[(-1 - i) * step];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) s[8 + i] = pix[i * step];
-}
 #define P(i) s[7 - (i)]
 #define Q(i) s[8 + (i)]
 
@@ -107,13 +105,6 @@ __device__ __forceinline__ void long_regs(const int *s, uint16_t *pix, int step,
     }
 }
 
-__device__ __forceinline__ void long_line(uint16_t *pix, int step, int tc, int lp, int lq)
-{
-    int s[16];
-    load_line<8, 8>(pix, step, s);
-    long_regs(s, pix, step, tc, lp, lq);
-}
-
 __device__ __forceinline__ void strong_regs(const int *s, uint16_t *pix, int step, int tc)
 {
     const int p3 = P(3), p2 = P(2), p1 = P(1), p0 = P(0), q0 = Q(0), q1 = Q(1), q2 = Q(2), q3 = Q(3);
@@ -123,13 +114,6 @@ __device__ __forceinline__ void strong_regs(const int *s, uint16_t *pix, int ste
     pix[0]         = (uint16_t)ov_clip3((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3, q0 - 3 * tc, q0 + 3 * tc);
     pix[1 * step]  = (uint16_t)ov_clip3((p0 + q0 + q1 + q2 + 2) >> 2, q1 - 2 * tc, q1 + 2 * tc);
     pix[2 * step]  = (uint16_t)ov_clip3((p0 + q0 + q1 + 3 * q2 + 2 * q3 + 4) >> 3, q2 - tc, q2 + tc);
-}
-
-__device__ __forceinline__ void strong_line(uint16_t *pix, int step, int tc)
-{
-    int s[16];
-    load_line<4, 4>(pix, step, s);
-    strong_regs(s, pix, step, tc);
 }
 
 __device__ __forceinline__ void weak_regs(const int *s, uint16_t *pix, int step, int tc, bool ext_p, bool ext_q)
@@ -148,16 +132,9 @@ __device__ __forceinline__ void weak_regs(const int *s, uint16_t *pix, int step,
     }
 }
 
-__device__ __forceinline__ void weak_line(uint16_t *pix, int step, int tc, bool ext_p, bool ext_q)
-{
-    int s[16];
-    load_line<3, 3>(pix, step, s);
-    weak_regs(s, pix, step, tc, ext_p, ext_q);
-}
-
-// ---- quad form (k_dbf_list): the 4 lanes of a quad hold the 4 lines of one segment, one line each, loaded ONCE;
-// the decisions, which the reference takes on lines 0 and 3 (chroma: 0 and 1), travel by DPP quad broadcast.
-// One memory round trip per segment instead of five (two decision lines, then four filtered lines one by one). ----
+// ---- quad form: the 4 lanes of a quad hold the 4 lines of one segment, one line each, loaded ONCE;
+// the decisions, which the reference takes on lines 0 and 3 (chroma: 0 and 1), travel by DPP quad broadcast:
+// one memory round trip per segment.  Callers keep quads whole: the 4 lanes enter and leave together. ----
 template <int SEL> __device__ __forceinline__ int quad_bcast(int v)
 {
     return __builtin_amdgcn_mov_dpp(v, SEL * 0x55, 0xf, 0xf, true);      // quad_perm [SEL, SEL, SEL, SEL]
@@ -256,127 +233,43 @@ __device__ __forceinline__ void chroma_quad(uint16_t *pix, int step, Lim lim, bo
     }
 }
 
-// filter_vertical_edge / filter_horizontal_edge (rcn_df.c:1433-1510, :2008-2085)
-__device__ __forceinline__ void luma_segment(uint16_t *pix0, int step, int lstep, Lim lim, int lp, int lq)
-{
-    const int beta = lim.beta, tc = lim.tc;
-    int a[16], b[16];                                 // lines 0 and 3
-    if (lp > 3 || lq > 3) { load_line<8, 8>(pix0, step, a); load_line<8, 8>(pix0 + 3 * lstep, step, b); }
-    else                  { load_line<4, 4>(pix0, step, a); load_line<4, 4>(pix0 + 3 * lstep, step, b); }
-    const int dp0 = dp_of(a, 0), dq0 = dq_of(a, 0), dp3 = dp_of(b, 0), dq3 = dq_of(b, 0);
-    const int d0 = dp0 + dq0, d3 = dp3 + dq3;
-    if (d0 + d3 >= beta) return;
-    bool sl = false;
-    if (lp > 3 || lq > 3) {
-        int dp0L = dp0, dq0L = dq0, dp3L = dp3, dq3L = dq3;
-        if (lp > 3) { dp0L = (dp0L + dp_of(a, 3) + 1) >> 1; dp3L = (dp3L + dp_of(b, 3) + 1) >> 1; }
-        if (lq > 3) { dq0L = (dq0L + dq_of(a, 3) + 1) >> 1; dq3L = (dq3L + dq_of(b, 3) + 1) >> 1; }
-        const int d0L = dp0L + dq0L, d3L = dp3L + dq3L;
-        sl = (d0L + d3L < beta) && (d0L < ((beta + 0x10) >> 5)) && (d3L < ((beta + 0x10) >> 5))
-             && strong_large(a, beta, tc, lp, lq) && strong_large(b, beta, tc, lp, lq);
-    }
-    if (sl) {
-#pragma unroll 1
-        for (int l = 0; l < 4; ++l) long_line(pix0 + l * lstep, step, tc, lp, lq);
-        return;
-    }
-    const bool sw = lp > 2 && (d0 < ((beta + 4) >> 3)) && (d3 < ((beta + 4) >> 3))
-                    && strong_small(a, beta, tc) && strong_small(b, beta, tc);
-    if (sw) {
-#pragma unroll 1
-        for (int l = 0; l < 4; ++l) strong_line(pix0 + l * lstep, step, tc);
-    } else {
-        const int side = (beta + (beta >> 1)) >> 3;
-        const bool ext_p = (dp0 + dp3) < side && lp > 1;
-        const bool ext_q = (dq0 + dq3) < side && lp > 1;   // sic: max_l_p gates the Q side too (rcn_df.c:1505, :2080)
-#pragma unroll 1
-        for (int l = 0; l < 4; ++l) weak_line(pix0 + l * lstep, step, tc, ext_p, ext_q);
-    }
-}
-
-// filter_veritcal_edge_c / filter_horizontal_edge_c (rcn_df.c:1107-1148, :1279-1319): 2 chroma lines
-__device__ __forceinline__ void chroma_segment(uint16_t *pix0, int step, int lstep, Lim lim, bool large, bool ctb_b)
-{
-    const int tc = lim.tc, beta = lim.beta;
-    if (tc == 0 || beta == 0) return;
-    int s0[16], s1[16];
-    load_line<4, 4>(pix0, step, s0);
-    load_line<4, 4>(pix0 + lstep, step, s1);
-    bool strong = false;
-    if (large) {
-        int d[2];
-        bool ok = true;
-#pragma unroll
-        for (int l = 0; l < 2; ++l) {
-            const int *s = l ? s1 : s0;
-            const int p3 = ctb_b ? P(1) : P(3);
-            const int dp = abs((ctb_b ? P(1) : P(2)) - 2 * P(1) + P(0));
-            d[l] = dp + dq_of(s, 0);
-            ok = ok && ((abs(p3 - P(0)) + abs(Q(3) - Q(0))) < (beta >> 3)) && (abs(P(0) - Q(0)) < ((tc * 5 + 1) >> 1));
-        }
-        strong = ok && (d[0] + d[1] < beta) && (2 * d[0] < (beta >> 2)) && (2 * d[1] < (beta >> 2));
-    }
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-        const int *s = l ? s1 : s0;
-        uint16_t *pix = pix0 + l * lstep;
-        const int p3 = P(3), p2 = P(2), p1 = P(1), p0 = P(0), q0 = Q(0), q1 = Q(1), q2 = Q(2), q3 = Q(3);
-        if (strong) {
-            if (ctb_b) {
-                pix[-1 * step] = (uint16_t)ov_clip3((3 * p1 + 2 * p0 + q0 + q1 + q2 + 4) >> 3, p0 - tc, p0 + tc);
-                pix[0]         = (uint16_t)ov_clip3((2 * p1 + p0 + 2 * q0 + q1 + q2 + q3 + 4) >> 3, q0 - tc, q0 + tc);
-            } else {
-                pix[-3 * step] = (uint16_t)ov_clip3((3 * p3 + 2 * p2 + p1 + p0 + q0 + 4) >> 3, p2 - tc, p2 + tc);
-                pix[-2 * step] = (uint16_t)ov_clip3((2 * p3 + p2 + 2 * p1 + p0 + q0 + q1 + 4) >> 3, p1 - tc, p1 + tc);
-                pix[-1 * step] = (uint16_t)ov_clip3((p3 + p2 + p1 + 2 * p0 + q0 + q1 + q2 + 4) >> 3, p0 - tc, p0 + tc);
-                pix[0]         = (uint16_t)ov_clip3((p2 + p1 + p0 + 2 * q0 + q1 + q2 + q3 + 4) >> 3, q0 - tc, q0 + tc);
-            }
-            pix[1 * step] = (uint16_t)ov_clip3((p1 + p0 + q0 + 2 * q1 + q2 + 2 * q3 + 4) >> 3, q1 - tc, q1 + tc);
-            pix[2 * step] = (uint16_t)ov_clip3((p0 + q0 + q1 + 2 * q2 + 3 * q3 + 4) >> 3, q2 - tc, q2 + tc);
-        } else {
-            const int delta = ov_clip3(((q0 << 2) - (p0 << 2) + p1 - q1 + 4) >> 3, -tc, tc);
-            pix[-1 * step] = (uint16_t)ov_clip_bd(p0 + delta);
-            pix[0]         = (uint16_t)ov_clip_bd(q0 - delta);
-        }
-    }
-}
 #undef P
 #undef Q
 
+// The filter over the dense edge planes (ovhip_dbf_planes), 4 lanes per plane word, one per line of the segment.
 // DIR 0: vertical edges, DIR 1: horizontal edges.  blockIdx.y: 0 luma, 1 Cb, 2 Cr.
 template <int DIR>
 __global__ __launch_bounds__(256) void k_dbf(ovhip_pic pic, ovhip_dbf_planes pl)
 {
     const int comp = blockIdx.y;
-    const int w4 = pl.w4, h4 = pl.h4;
-    const int nthreads = gridDim.x * 256;
-    // every lane strides over the edge-parameter plane (most words are 0 = no edge; k_dbf_list takes the compact lists)
+    const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t wi = tid >> 2;
+    const int l = tid & 3;
+    // the 4 lanes of a quad share one word (most are 0 = no edge): every exit below takes whole quads
     if (comp == 0) {
-        for (int tid = blockIdx.x * 256 + threadIdx.x; tid < w4 * h4; tid += nthreads) {
-            const int ux = tid % w4, uy = tid / w4;
-            const int v = (DIR ? pl.luma_h : pl.luma_v)[tid];
-            if (!(v & 3)) continue;
-            // never filter across the picture boundary (the recorder does not emit such edges)
-            if ((DIR ? uy : ux) == 0) continue;
-            const Lim lim = dbf_limits(v >> 8, v & 3, pl.tc_offset, pl.beta_offset);
-            if (!(lim.tc || lim.beta)) continue;
-            uint16_t *p = pic.y + (uy * 4) * pic.stride_y + ux * 4;
-            luma_segment(p, DIR ? pic.stride_y : 1, DIR ? 1 : pic.stride_y, lim, (v >> 2) & 7, (v >> 5) & 7);
-        }
+        const int w4 = pl.w4;
+        if (wi >= (uint32_t)(w4 * pl.h4)) return;
+        const int ux = wi % w4, uy = wi / w4;
+        const int v = (DIR ? pl.luma_h : pl.luma_v)[wi];
+        if (!(v & 3)) return;
+        // never filter across the picture boundary (the recorder does not emit such edges)
+        if ((DIR ? uy : ux) == 0) return;
+        const Lim lim = dbf_limits(v >> 8, v & 3, pl.tc_offset, pl.beta_offset);
+        if (!(lim.tc || lim.beta)) return;
+        uint16_t *p = pic.y + (uy * 4) * pic.stride_y + ux * 4 + l * (DIR ? 1 : pic.stride_y);
+        luma_quad<DIR>(p, DIR ? pic.stride_y : 1, lim, (v >> 2) & 7, (v >> 5) & 7);
     } else {
         // chroma edge planes: vertical [h4][w4c] (every second unit column), horizontal [h4c][w4]
-        const int cw = DIR ? w4 : (w4 + 1) >> 1, chh = DIR ? (h4 + 1) >> 1 : h4;
-        const uint16_t *plane = DIR ? (comp == 1 ? pl.cb_h : pl.cr_h) : (comp == 1 ? pl.cb_v : pl.cr_v);
-        for (int tid = blockIdx.x * 256 + threadIdx.x; tid < cw * chh; tid += nthreads) {
-            const int cx = tid % cw, cy = tid / cw;
-            const int v = plane[tid];
-            if (!(v & OVHIP_DBF_C_ON)) continue;
-            const int ux = DIR ? cx : cx * 2, uy = DIR ? cy * 2 : cy;
-            if ((DIR ? uy : ux) == 0) continue;
-            const Lim lim = dbf_limits(v >> 8, 1 + !!(v & OVHIP_DBF_C_BS2), pl.tc_offset, pl.beta_offset);
-            uint16_t *p = (comp == 1 ? pic.cb : pic.cr) + (uy * 2) * pic.stride_c + ux * 2;
-            chroma_segment(p, DIR ? pic.stride_c : 1, DIR ? 1 : pic.stride_c, lim, v & OVHIP_DBF_C_LARGE, v & OVHIP_DBF_C_CTB_B);
-        }
+        const int cw = DIR ? pl.w4 : (pl.w4 + 1) >> 1, chh = DIR ? (pl.h4 + 1) >> 1 : pl.h4;
+        if (wi >= (uint32_t)(cw * chh)) return;
+        const int cx = wi % cw, cy = wi / cw;
+        const int v = (DIR ? (comp == 1 ? pl.cb_h : pl.cr_h) : (comp == 1 ? pl.cb_v : pl.cr_v))[wi];
+        if (!(v & OVHIP_DBF_C_ON)) return;
+        const int ux = DIR ? cx : cx * 2, uy = DIR ? cy * 2 : cy;
+        if ((DIR ? uy : ux) == 0) return;
+        const Lim lim = dbf_limits(v >> 8, 1 + !!(v & OVHIP_DBF_C_BS2), pl.tc_offset, pl.beta_offset);
+        uint16_t *p = (comp == 1 ? pic.cb : pic.cr) + (uy * 2) * pic.stride_c + ux * 2 + (l & 1) * (DIR ? 1 : pic.stride_c);
+        chroma_quad<DIR>(p, DIR ? pic.stride_c : 1, lim, v & OVHIP_DBF_C_LARGE, v & OVHIP_DBF_C_CTB_B, l < 2);
     }
 }
 
@@ -446,9 +339,7 @@ extern "C" int ovhip_dbf_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhi
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_dbf_launch: null edge plane", hipSuccess);
     if (pl->w4 != (pic->w + 3) / 4 || pl->h4 != (pic->h + 3) / 4)
         return ov_fail(ctx, OVHIP_EINVAL, "ovhip_dbf_launch: edge planes do not match the picture", hipSuccess);
-    const int n = pl->w4 * pl->h4;
-    const int nb = (n + 255) / 256;
-    dim3 grid(nb, 3);                            // one lane per edge word measured faster than a capped resident grid
+    dim3 grid((pl->w4 * pl->h4 + 63) / 64, 3);   // 4 lanes per luma word; the chroma blocks past their smaller planes return at once
     hipLaunchKernelGGL(k_dbf<0>, grid, dim3(256), 0, ctx->stream, *pic, *pl);
     OV_LAUNCH_CHECK(ctx, "k_dbf<v>");
     hipLaunchKernelGGL(k_dbf<1>, grid, dim3(256), 0, ctx->stream, *pic, *pl);

@@ -699,7 +699,6 @@ class ResidentPicture:
         self.mc_units = ctx.upload(wl.mc_units)
         self.tb_cmds = ctx.upload(wl.tb_cmds)
         self.coefs = ctx.upload(wl.coefs)
-        self.dbf_planes = DevDbfPlanes(ctx, wl.dbf_planes)
         self.dbf_v = ctx.upload(wl.dbf_edges[0])              # the lists ovhip_rec_dbf_ctu emitted CTU by CTU
         self.dbf_h = ctx.upload(wl.dbf_edges[1])
         self.sao_params = ctx.upload(wl.sao_params)
@@ -802,7 +801,7 @@ class ResidentPicture:
         return self.mv_out.download(np.int32).reshape(-1, 4) if self.mv_out else np.zeros((0, 4), np.int32)
 
     def free(self):
-        for b in self.bufs + [self.dbf_planes, self.alf]:
+        for b in self.bufs + [self.alf]:
             b.free()
         for p in self.refs + [self.dst, self.tmp] + ([self.intra] if self.intra else []):
             p.free()

@@ -89,8 +89,12 @@ def _subset(idx, dense):
     return ev[keep[0]], eh[keep[1]], [c for c, k in zip(cv, keep[0]) if k], [c for c, k in zip(ch, keep[1]) if k]
 
 
-def test_dense_planes(ctx):
-    """ovhip_dbf_launch (k_dbf) on the planes the cells of ONE pair stand for: the whole luma matrix, long filters included"""
+@pytest.mark.parametrize("layout", ["tight", "view"])
+def test_dense_planes(ctx, layout):
+    """ovhip_dbf_launch (k_dbf) on the planes the cells of ONE pair stand for: the whole luma matrix, long filters included.
+    view: the picture is the left 320 columns of a 322-wide noise picture -- strides above the width, luma rows whose 8-byte
+    alignment alternates (stride 644 bytes) and chroma rows at every 2-byte alignment (322 bytes), so the vertical-edge line load
+    takes its vector and its scalar path; the columns outside the view must come back untouched"""
     y, cb, cr, _, _, offs, _, _ = cells()
     ev, eh, cv, ch = _subset(dbf_cells.DENSE_IDX, dense=True)
     want = spec_dbf.filter(y, cb, cr, ev, eh, offs)
@@ -103,10 +107,28 @@ def test_dense_planes(ctx):
     planes["beta_offset"], planes["tc_offset"] = dbf_cells.OFF_BETA[dbf_cells.DENSE_IDX], dbf_cells.OFF_TC[dbf_cells.DENSE_IDX]
     for d in (0, 1):                                # the planes hold exactly these segments
         assert len(capi.dbf_compact(planes, d)) == len((ev, eh)[d])
-    d = ctx.upload_pic(y, cb, cr)
-    ctx.dbf(d, engine.DevDbfPlanes(ctx, planes))
+    if layout == "tight":
+        d = ctx.upload_pic(y, cb, cr)
+        ctx.dbf(d, engine.DevDbfPlanes(ctx, planes))
+        ctx.sync()
+        compare(d.download(), want, "ovhip_dbf_launch (dense planes)")
+        return
+    W, H, WIDE = dbf_cells.W, dbf_cells.H, dbf_cells.W + 2
+    assert WIDE % 4 == 2
+    rng = np.random.default_rng(11)
+    wide = [rng.integers(0, 1024, (H // s, WIDE // s)).astype(np.uint16) for s in (1, 2, 2)]
+    for big, part in zip(wide, (y, cb, cr)):
+        big[:, :part.shape[1]] = part
+    pic = ctx.upload_pic(*wide)
+    assert (pic.s.stride_y, pic.s.stride_c) == (WIDE, WIDE // 2)
+    view = engine.DevPic(ctx, capi.Pic(pic.s.y, pic.s.cb, pic.s.cr, W, H, pic.s.stride_y, pic.s.stride_c), owns=False)
+    ctx.dbf(view, engine.DevDbfPlanes(ctx, planes))
     ctx.sync()
-    compare(d.download(), want, "ovhip_dbf_launch (dense planes)")
+    got = pic.download()
+    compare([g[:, :p.shape[1]] for g, p in zip(got, (y, cb, cr))], want, "ovhip_dbf_launch (dense planes, 320x320 view of 322x320)")
+    for name, g, big, part in zip(("Y", "Cb", "Cr"), got, wide, (y, cb, cr)):
+        assert np.array_equal(g[:, part.shape[1]:], big[:, part.shape[1]:]), f"plane {name}: columns outside the view changed"
+    pic.free()
 
 
 def test_single_pair_wrapper_with_a_negative_pair(ctx):

@@ -27,3 +27,10 @@ for how in ("emitted", "comp-major", "ctu-rows", "ctu-rows-mixed", "raster"):
     for _ in range(50): ctx.dbf_edges(pic, ev, eh, 0, 0)
     st.record_event(b); b.synchronize()
     print(f"{how:16s} {a.elapsed_time(b) * 1000 / 50:7.2f} us per picture (V + H)   edges {len(wl.dbf_edges[0])} + {len(wl.dbf_edges[1])}")
+planes = engine.DevDbfPlanes(ctx, wl.dbf_planes)             # the same picture through the dense planes (ovhip_dbf_launch)
+for _ in range(5): ctx.dbf(pic, planes)
+a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+st.record_event(a)
+for _ in range(50): ctx.dbf(pic, planes)
+st.record_event(b); b.synchronize()
+print(f"{'dense planes':16s} {a.elapsed_time(b) * 1000 / 50:7.2f} us per picture (V + H)   luma words {planes.s.w4 * planes.s.h4} + {planes.s.w4 * planes.s.h4}")
