@@ -406,6 +406,14 @@ class Context:
                                             lmcs_fwd.ptr if lmcs_fwd else None,
                                             mv_out.ptr if mv_out else None), "mcx_launch")
 
+    def dmvr_search(self, geom: "DevPic", refs: list, units: "DevBuf", mv_out: "DevBuf", n: int | None = None):
+        """The decoder-side MV refinement alone (ovhip_dmvr_search_launch) for the units that carry OVHIP_MC_DMVR: their refined
+        vectors into mv_out (int32[n][4]; the entries of other units are left alone); geom gives the picture geometry, nothing is
+        written to it."""
+        n = units.count if n is None else n
+        arr = (capi.Pic * len(refs))(*[r.s for r in refs])
+        self._chk(self.lib.ovhip_dmvr_search_launch(self.h, C.byref(geom.s), arr, len(refs), units.ptr, n, mv_out.ptr), "dmvr_search_launch")
+
 
 class DevDbfPlanes:
     """Deblocking edge planes resident on the device (ovhip_dbf_planes with device pointers)."""

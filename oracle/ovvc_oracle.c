@@ -461,8 +461,10 @@ static void mc_plane(const oracle_pic *dst, const oracle_pic *refs, const ovhip_
 #define BDOF_RS 18
 static int floor_log2u(uint32_t v) { int r = -1; while (v) { v >>= 1; ++r; } return r; }
 
+/* bt (may be NULL): per 4x4 block, raster order, 5 values -- sum_ax == 0, sum_ay == 0, wx, wy, x_off != 0 -- then at [80] / [81] whether
+ * an output sample was clipped at 0 / at 1023 */
 static void bdof_block(uint16_t *d, int dstride, const int16_t *p0, const int16_t *p1, const sampler *s0, const sampler *s1,
-                       const int ext[2][2], int w, int h)
+                       const int ext[2][2], int w, int h, int64_t *bt)
 {
     int16_t R[2][BDOF_RS * BDOF_RS], GX[2][BDOF_RS * BDOF_RS], GY[2][BDOF_RS * BDOF_RS];
     const int16_t *p[2] = { p0, p1 };
@@ -507,14 +509,18 @@ static void bdof_block(uint16_t *d, int dstride, const int16_t *p0, const int16_
                     sum_dx += ax < 0 ? -dr : (ax == 0 ? 0 : dr);
                     sum_dy += ay < 0 ? -dr : (ay == 0 ? 0 : dr);
                 }
+            int x_off = 0;
             if (sum_ax) wx = clip3i((sum_dx * 4) >> floor_log2u(sum_ax), -15, 15);
             if (sum_ay) {
-                int x_off = 0;
                 if (wx) {
                     int high = sum_xy >> 12, low = sum_xy & 4095;
                     x_off = (((wx * high) * 4096) + (wx * low)) >> 1;
                 }
                 wy = clip3i(((sum_dy * 4) - x_off) >> floor_log2u(sum_ay), -15, 15);
+            }
+            if (bt) {
+                int64_t *t = bt + 5 * ((sy >> 2) * (w >> 2) + (sx >> 2));
+                t[0] = !sum_ax; t[1] = !sum_ay; t[2] = wx; t[3] = wy; t[4] = x_off != 0;
             }
             /* rcn_apply_bdof_subblock (rcn_prof_bdof.c:59-103) */
             for (int j = 0; j < 4; ++j)
@@ -522,6 +528,7 @@ static void bdof_block(uint16_t *d, int dstride, const int16_t *p0, const int16_
                     int o = (sy + j + 1) * BDOF_RS + sx + i + 1;
                     int32_t b = wx * (GX[0][o] - GX[1][o]) + wy * (GY[0][o] - GY[1][o]);
                     int16_t v = (int16_t)((R[0][o] + R[1][o] + b + 16) >> 5);
+                    if (bt) { bt[80] |= v < 0; bt[81] |= v > PIX_MAX; }
                     d[(sy + j) * dstride + sx + i] = (uint16_t)clip_bd(v);
                 }
         }
@@ -573,8 +580,14 @@ static int32_t div_for_maxq7(int64_t num, int64_t den)
 
 /* One BDOF and/or DMVR unit (luma <= 16x16 + chroma): rcn_bdof_mcp_l (rcn_inter.c:1136-1250) followed
  * by the chroma of rcn_mcp_b_c, or rcn_dmvr_mv_refine (rcn_inter.c:872-1126). */
+/* trace (may be NULL): what DMVR decided, for the census of the fixtures (tests/mc_census.py) -- [0] searched (0: early exit),
+ * [1] arg-min index, [2] [3] the displacement (delta_h, delta_v) in 1/16, [4] the final cost, [5] BDOF switched off by the cost,
+ * [6] the centre SAD as measured, [7 .. 31] the 25 costs the arg-min saw (the centre's reduced by a quarter), [32] BDOF ran,
+ * [33 .. 114] bdof_block's trace.  true_apron: an edit for the tests, never what the reference does -- the final interpolation of
+ * a DMVR unit reads the reference picture where rcn_dmvr_mv_refine reads the 2-sample replicated apron of its windows */
+#define ORACLE_TRACE_LEN 115
 static void mc_refined_unit(const oracle_pic *dst, const oracle_pic *refs, const ovhip_mc_unit *u,
-                            const uint16_t *lmcs_fwd, int32_t *mv_out)
+                            const uint16_t *lmcs_fwd, int32_t *mv_out, int64_t *trace, int true_apron)
 {
     const int w = u->w, h = u->h;
     const int dmvr = (u->flags & OVHIP_MC_DMVR) != 0;
@@ -597,6 +610,7 @@ static void mc_refined_unit(const oracle_pic *dst, const oracle_pic *refs, const
         for (int l = 0; l < 2; ++l) dmvr_bilinear(B[l], &sl[l], w, h, ini[l][0] & 15, ini[l][1] & 15);
         uint64_t sad_c = dmvr_sad(B[0] + 2 * 20 + 2, B[1] + 2 * 20 + 2, w, h);
         uint64_t min_cost = sad_c - (sad_c >> 2);
+        if (trace) { trace[1] = 12; trace[6] = (int64_t)sad_c; }
         if (min_cost >= (uint64_t)(w * h)) {
             uint64_t sad[25], best = (uint64_t)-1;
             int idx = 12;
@@ -618,10 +632,14 @@ static void mc_refined_unit(const oracle_pic *dst, const oracle_pic *refs, const
             }
             mv[0][0] = clip3i(mv[0][0] + dh, -(1 << 17), (1 << 17) - 1); mv[0][1] = clip3i(mv[0][1] + dv, -(1 << 17), (1 << 17) - 1);
             mv[1][0] = clip3i(mv[1][0] - dh, -(1 << 17), (1 << 17) - 1); mv[1][1] = clip3i(mv[1][1] - dv, -(1 << 17), (1 << 17) - 1);
+            if (trace) { trace[0] = 1; trace[1] = idx; trace[2] = dh; trace[3] = dv; for (int k = 0; k < 25; ++k) trace[7 + k] = (int64_t)sad[k]; }
         }
+        if (trace) { trace[4] = (int64_t)min_cost; trace[5] = use_bdof && min_cost < (uint64_t)(2 * w * h); }
         if (use_bdof && min_cost < (uint64_t)(2 * w * h)) use_bdof = 0;
     }
     if (mv_out) { mv_out[0] = mv[0][0]; mv_out[1] = mv[0][1]; mv_out[2] = mv[1][0]; mv_out[3] = mv[1][1]; }
+    if (true_apron) sl[0].win = sl[1].win = 0;
+    if (trace) trace[32] = use_bdof;
 
     if (!(u->flags & OVHIP_MC_NO_LUMA)) {
         int16_t p[2][16 * 16];
@@ -634,7 +652,7 @@ static void mc_refined_unit(const oracle_pic *dst, const oracle_pic *refs, const
             predict14(p[l], 16, &sl[l], w, h, fh, fv, 8);
         }
         uint16_t *d = dst->y + u->y * dst->stride_y + u->x;
-        if (use_bdof) bdof_block(d, dst->stride_y, p[0], p[1], &sl[0], &sl[1], ext, w, h);
+        if (use_bdof) bdof_block(d, dst->stride_y, p[0], p[1], &sl[0], &sl[1], ext, w, h, trace ? trace + 33 : NULL);
         else
             for (int j = 0; j < h; ++j)
                 for (int i = 0; i < w; ++i) d[j * dst->stride_y + i] = (uint16_t)clip_bd((p[0][j * 16 + i] + p[1][j * 16 + i] + 16) >> 5);
@@ -651,7 +669,7 @@ static void mc_refined_unit(const oracle_pic *dst, const oracle_pic *refs, const
                 int cx = ini[l][0], cy = ini[l][1];
                 if (dmvr) clip_mv(u->x, u->y, rp->w, rp->h, w, h, &cx, &cy);   /* derive_dmvr_ref_buf_c, rcn_inter.c:473-517 */
                 sampler s = plane_sampler(rp, plane, (u->x >> 1) + (cx >> 5), (u->y >> 1) + (cy >> 5));
-                if (dmvr) { s.win = 1; s.lo = -1; s.hi_x = wc + 1; s.hi_y = hc + 1; }
+                if (dmvr && !true_apron) { s.win = 1; s.lo = -1; s.hi_x = wc + 1; s.hi_y = hc + 1; }
                 s.dx = (mv[l][0] >> 5) - (ini[l][0] >> 5);
                 s.dy = (mv[l][1] >> 5) - (ini[l][1] >> 5);
                 predict14(p[l], 16, &s, wc, hc, ovt_mc_chroma[mv[l][0] & 31], ovt_mc_chroma[mv[l][1] & 31], 4);
@@ -674,11 +692,20 @@ void oracle_mc_full(const oracle_pic *dst, const oracle_pic *refs, uint32_t n_re
     (void)n_refs;
     for (uint32_t i = 0; i < n; ++i) {
         const ovhip_mc_unit *u = &units[i];
-        if (u->flags & (OVHIP_MC_BDOF | OVHIP_MC_DMVR)) { mc_refined_unit(dst, refs, u, lmcs_fwd, mv_out ? mv_out + 4 * i : NULL); continue; }
+        if (u->flags & (OVHIP_MC_BDOF | OVHIP_MC_DMVR)) { mc_refined_unit(dst, refs, u, lmcs_fwd, mv_out ? mv_out + 4 * i : NULL, NULL, 0); continue; }
         if (mv_out) { mv_out[4 * i] = u->mv0x; mv_out[4 * i + 1] = u->mv0y; mv_out[4 * i + 2] = u->mv1x; mv_out[4 * i + 3] = u->mv1y; }
         if (!(u->flags & OVHIP_MC_NO_LUMA)) mc_plane(dst, refs, u, 0, lmcs_fwd, intra);
         if (!(u->flags & OVHIP_MC_NO_CHROMA)) { mc_plane(dst, refs, u, 1, lmcs_fwd, intra); mc_plane(dst, refs, u, 2, lmcs_fwd, intra); }
     }
+}
+
+/* one refined unit with the trace of its search and of BDOF (see mc_refined_unit): trace = int64[ORACLE_TRACE_LEN] = 115, mv_out = int32[4] */
+void oracle_mcx_trace(const oracle_pic *dst, const oracle_pic *refs, uint32_t n_refs, const ovhip_mc_unit *u, int32_t *mv_out, int64_t *trace,
+                      int true_apron)
+{
+    (void)n_refs;
+    memset(trace, 0, ORACLE_TRACE_LEN * sizeof(*trace));
+    mc_refined_unit(dst, refs, u, NULL, mv_out, trace, true_apron);
 }
 
 void oracle_mc_ex(const oracle_pic *dst, const oracle_pic *refs, uint32_t n_refs,

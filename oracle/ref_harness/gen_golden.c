@@ -922,17 +922,11 @@ gen_mc(const char *dir)
  *           (vcl_coding_unit.c:2450-2472, :2598-2668)                          -> K7, K8
  * Reference pictures: R0 smooth random; R1 = R0 displaced by a per-64x64-region integer shift plus a
  * per-region noise level (0 = exact copy: exercises DMVR's early exit and the BDOF disable);
- * R2 independent.  rpl0 = {R0, R2}, rpl1 = {R1, R0}. */
+ * R2 independent.  rpl0 = {R0, R2}, rpl1 = {R1, R0}.
+ * mcx_make_refs: those pictures (mcx_cells_*.ovg use them too and do not store them); draws from g_seed. */
 static void
-gen_mcx(const char *dir)
+mcx_make_refs(OVPicture *ref[3])
 {
-    gbuf b_desc = { .type = T_U8 }, b_eoff = { .type = T_U32 }, b_exp = { .type = T_U16 }, b_mv = { .type = T_I32 };
-    uint32_t n_cases = 0;
-    g_seed = 0x266 + 77;
-
-    OVCTUDec *c = ref_new_ctudec(0, 0);
-    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
-    OVPicture *ref[3];
     for (int i = 0; i < 3; ++i) {
         ref[i] = ref_new_picture(MC_W, MC_H, i == 0 ? 8 : (i == 1 ? 24 : 4));
         for (int p = 0; p < 3; ++p) fill_plane(ref[i]->frame->data[p], MC_W >> !!p, MC_H >> !!p, MC_W >> !!p);
@@ -951,6 +945,19 @@ gen_mcx(const char *dir)
                 b[y * w + x] = (uint16_t)(v < 0 ? 0 : v > 1023 ? 1023 : v);
             }
     }
+}
+
+static void
+gen_mcx(const char *dir)
+{
+    gbuf b_desc = { .type = T_U8 }, b_eoff = { .type = T_U32 }, b_exp = { .type = T_U16 }, b_mv = { .type = T_I32 };
+    uint32_t n_cases = 0;
+    g_seed = 0x266 + 77;
+
+    OVCTUDec *c = ref_new_ctudec(0, 0);
+    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
+    OVPicture *ref[3];
+    mcx_make_refs(ref);
     ic->rpl0[0] = ref[0]; ic->rpl0[1] = ref[2]; ic->rpl1[0] = ref[1]; ic->rpl1[1] = ref[0];
     static const uint8_t slot0[2] = { 0, 2 }, slot1[2] = { 1, 0 };
     for (int i = 0; i < 16; ++i) {
@@ -1564,6 +1571,572 @@ gen_gpm(const char *dir)
     gfile_buf(&g, "exp", &b_exp);
     gfile_close(&g);
     fprintf(stderr, "gpm.ovg: %u GPM + %u CIIP (planar stubbed) + %u CIIP cases, %zu expected samples\n", n_gpm, n_cases - n_gpm - n_ciip2, n_ciip2, b_exp.n);
+}
+
+/* ====================================================================================== MC / MCX cells
+ * mc_cells_<family>_<nn>.ovg : the cells of the plain units (k_mc2) that mc.ovg's random draws leave out, enumerated -- what the
+ * cells are and what reaches them is counted by tests/mc_census.py.  Same slots as mc.ovg (rcn_mcp_b / _l / _c; the combine family
+ * also rcn_gpm_b and rcn_ciip / rcn_ciip_b with the intra slots stubbed as in gpm.ovg), same 208x120 pictures (not stored again)
+ * except for the combine family, which paints its own.  A PU is one unit (<= 16x16) unless the cell needs a unit that lies wholly
+ * outside the picture, which only a unit of a larger PU can.  Families:
+ *   phase    every (shape, lists, chroma phase of 32) horizontally and vertically (the luma phase is its low four bits), the half-pel
+ *            rows; every window inside the picture
+ *   combine  uni L0 / L1, average, the five BCW indices, GPM and the three CIIP weights per shape, on pictures of full-swing steps:
+ *            the interpolation overshoots, so that the final clip binds at 0 and at 1023
+ *   planes   both, luma only, chroma only
+ *   border   per shape, for the luma and for the chroma window: the window crosses the left / right / top / bottom border or a
+ *            corner, or lies wholly outside on one side, at each offset 0..3 of its first column within an aligned group of 4
+ * Every case: the reference must leave the CTU buffer outside the PU untouched (checked here).  The cases sit on a grid of slots so
+ * that a test can launch many of them into one picture.
+ * mcx_cells_<family>_<nn>.ovg : refined units (rcn_dmvr_mv_refine) on mcx.ovg's pictures (not stored again):
+ *   far      DMVR with one or both initial vectors beyond clip_mv's range, on each side
+ *   limit    DMVR with initial vectors next to the +-2^17 limits of the refined vector */
+#define MCC_MAX_EXP 400000          /* expected samples per file */
+struct mcc_out {
+    const char *dir, *prefix, *fam;
+    int part, with_mv;
+    gbuf desc, eoff, exp, modes, mv;
+    uint32_t n;
+    OVPicture **ref;                /* pictures of the family's own: stored in each of its files */
+    uint16_t **intra;
+};
+
+static void
+mcc_flush(struct mcc_out *o)
+{
+    char name[96];
+    if (!o->n) return;
+    snprintf(name, sizeof(name), "%s_%s_%02d.ovg", o->prefix, o->fam, o->part++);
+    gfile g = gfile_open(o->dir, name);
+    if (o->ref) {
+        uint32_t d3[3] = { 3, MC_H, MC_W };
+        uint16_t *all = malloc(3 * MC_W * MC_H * 2);
+        for (int i = 0; i < 3; ++i) memcpy(all + i * MC_W * MC_H, o->ref[i]->frame->data[0], MC_W * MC_H * 2);
+        gfile_array(&g, "ref_y", T_U16, all, 3, d3);
+        d3[1] = MC_H / 2; d3[2] = MC_W / 2;
+        for (int p = 1; p < 3; ++p) {
+            for (int i = 0; i < 3; ++i) memcpy(all + i * (MC_W / 2) * (MC_H / 2), o->ref[i]->frame->data[p], (MC_W / 2) * (MC_H / 2) * 2);
+            gfile_array(&g, p == 1 ? "ref_cb" : "ref_cr", T_U16, all, 3, d3);
+        }
+        free(all);
+    }
+    if (o->intra) {
+        uint32_t di[2] = { MC_H, MC_W };
+        gfile_array(&g, "intra_y", T_U16, o->intra[0], 2, di);
+        di[0] = MC_H / 2; di[1] = MC_W / 2;
+        gfile_array(&g, "intra_cb", T_U16, o->intra[1], 2, di);
+        gfile_array(&g, "intra_cr", T_U16, o->intra[2], 2, di);
+    }
+    uint32_t d2[2] = { o->n, sizeof(ovhip_pu_desc) };
+    gfile_array(&g, "desc", T_U8, o->desc.data, 2, d2);
+    d2[1] = o->with_mv ? 4 : 3; gfile_array(&g, "exp_off", T_U32, o->eoff.data, 2, d2);
+    if (!o->with_mv) { d2[1] = 2; gfile_array(&g, "ciip_modes", T_I32, o->modes.data, 2, d2); }
+    gfile_buf(&g, "exp", &o->exp);
+    if (o->with_mv) gfile_buf(&g, "exp_mv", &o->mv);
+    gfile_close(&g);
+    fprintf(stderr, "%s: %u cases, %zu expected samples\n", name, o->n, o->exp.n);
+    o->desc.n = o->eoff.n = o->exp.n = o->modes.n = o->mv.n = 0; o->n = 0;
+}
+
+/* before a case: the CTU buffer filled; after it: the PU's three rectangles dumped, everything else must still hold the fill */
+static void
+mcc_fill(const struct OVBuffInfo *cb)
+{
+    for (int j = 0; j < 128; ++j) memset(cb->y + j * cb->stride, 0xAB, 256);
+    for (int j = 0; j < 64; ++j) { memset(cb->cb + j * cb->stride_c, 0xAB, 128); memset(cb->cr + j * cb->stride_c, 0xAB, 128); }
+}
+
+static void
+mcc_dump(struct mcc_out *o, const struct OVBuffInfo *cb, const ovhip_pu_desc *d, uint32_t eoff[3])
+{
+    const int x0 = d->x0 & 127, y0 = d->y0 & 127, w = 1 << d->log2_w, h = 1 << d->log2_h;
+    for (int p = 0; p < 3; ++p) {
+        const int c = p != 0, n = 128 >> c, stride = c ? cb->stride_c : cb->stride;
+        const uint16_t *q = p == 0 ? cb->y : p == 1 ? cb->cb : cb->cr;
+        const int written = p ? (d->planes & 2) : (d->planes & 1);
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) {
+                const int in = written && i >= (x0 >> c) && i < ((x0 + w) >> c) && j >= (y0 >> c) && j < ((y0 + h) >> c);
+                if (!in && q[j * stride + i] != 0xABAB) {
+                    fprintf(stderr, "%s %s case %u: the reference wrote plane %d at (%d, %d), outside the PU\n", o->prefix, o->fam, o->n, p, i, j);
+                    exit(1);
+                }
+            }
+        eoff[p] = (uint32_t)o->exp.n;
+        dump_rect(&o->exp, q, stride, x0 >> c, y0 >> c, w >> c, h >> c);
+    }
+}
+
+enum { MCC_PLAIN, MCC_GPM, MCC_CIIP };
+struct mcc_ctx { OVCTUDec *c; struct InterDRVCtx *ic; };
+static const uint8_t mcc_slot[2][2] = { { 0, 1 }, { 2, 0 } };            /* [list][ref_idx] -> picture slot, as mc.ovg and gpm.ovg */
+
+/* one case through the reference.  kind MCC_GPM: d->inter_dir holds the two partitions' lists (dir0 | dir1 << 2) on entry;
+ * MCC_CIIP: modes = the neighbours' CU modes (above, left), p_entry: the P-slice entry point rcn_ciip */
+static void
+mcc_case(struct mcc_out *o, struct mcc_ctx *m, ovhip_pu_desc *d, int kind, const int32_t modes[2], int p_entry)
+{
+    OVCTUDec *c = m->c;
+    struct InterDRVCtx *ic = m->ic;
+    const struct OVBuffInfo *cb = &c->rcn_ctx.ctu_buff;
+    const int w = 1 << d->log2_w, h = 1 << d->log2_h, l2w = d->log2_w, l2h = d->log2_h;
+    int32_t cargs[2] = { modes ? modes[0] : 0, modes ? modes[1] : 0 };
+    if ((d->x0 >> 7) != ((d->x0 + w - 1) >> 7) || d->y0 + h > MC_H || d->x0 + w > MC_W) { fprintf(stderr, "%s: PU outside its CTU or the picture\n", o->fam); exit(1); }
+    if (o->exp.n + (size_t)w * h * 3 / 2 > MCC_MAX_EXP) mcc_flush(o);
+    c->ctb_x = d->x0 >> 7; c->ctb_y = d->y0 >> 7;
+    const int x0 = d->x0 & 127, y0 = d->y0 & 127;
+    ic->prec_amvr = d->prec_amvr_half ? MV_PRECISION_HALF : 0;
+    mcc_fill(cb);
+    if (kind == MCC_GPM) {
+        struct VVCGPM *g = &ic->gpm_ctx;
+        memset(g, 0, sizeof(*g));
+        g->split_dir = d->gpm_split_dir;
+        g->inter_dir0 = d->inter_dir & 3; g->inter_dir1 = d->inter_dir >> 2;
+        g->mv0 = (OVMV){ .x = d->mv0x, .y = d->mv0y, .ref_idx = d->ref_idx0 };
+        g->mv1 = (OVMV){ .x = d->mv1x, .y = d->mv1y, .ref_idx = d->ref_idx1 };
+        d->ref0 = mcc_slot[g->inter_dir0 - 1][d->ref_idx0]; d->ref1 = mcc_slot[g->inter_dir1 - 1][d->ref_idx1];
+        d->inter_dir = 3; d->refine = OVHIP_PU_GPM; d->planes = 3;
+        c->rcn_funcs.rcn_gpm_b(c, g, x0, y0, l2w, l2h);
+    } else {
+        d->poc0 = ic->rpl0[d->ref_idx0]->poc; d->poc1 = ic->rpl1[d->ref_idx1]->poc;
+        d->ref0 = mcc_slot[0][d->ref_idx0]; d->ref1 = mcc_slot[1][d->ref_idx1];
+        OVMV mv0 = { .x = d->mv0x, .y = d->mv0y, .ref_idx = d->ref_idx0, .bcw_idx_plus1 = d->bcw_idx_plus1 };
+        OVMV mv1 = { .x = d->mv1x, .y = d->mv1y, .ref_idx = d->ref_idx1, .bcw_idx_plus1 = d->bcw_idx_plus1 };
+        if (kind == MCC_CIIP) {
+            d->planes = 3;
+            c->part_map.cu_mode_x[(x0 + w - 1) >> 2] = (uint8_t)cargs[0];
+            c->part_map.cu_mode_y[(y0 + h - 1) >> 2] = (uint8_t)cargs[1];
+            if (p_entry) c->rcn_funcs.rcn_ciip(c, x0, y0, l2w, l2h, mv0, d->ref_idx0);
+            else         c->rcn_funcs.rcn_ciip_b(c, mv0, mv1, x0, y0, l2w, l2h, d->inter_dir, d->ref_idx0, d->ref_idx1);
+        } else if (d->planes == 3) c->rcn_funcs.rcn_mcp_b(c, *cb, ic, c->part_ctx, mv0, mv1, x0, y0, l2w, l2h, d->inter_dir, d->ref_idx0, d->ref_idx1);
+        else if (d->planes == 1)   c->rcn_funcs.rcn_mcp_b_l(c, *cb, ic, c->part_ctx, mv0, mv1, x0, y0, l2w, l2h, d->inter_dir, d->ref_idx0, d->ref_idx1);
+        else                       c->rcn_funcs.rcn_mcp_b_c(c, *cb, ic, c->part_ctx, mv0, mv1, x0, y0, l2w, l2h, d->inter_dir, d->ref_idx0, d->ref_idx1);
+    }
+    uint32_t eoff[3];
+    mcc_dump(o, cb, d, eoff);
+    gbuf_push(&o->desc, d, sizeof(*d));
+    gbuf_push(&o->eoff, eoff, 3);
+    gbuf_push(&o->modes, cargs, 2);
+    o->n++;
+}
+
+/* the n-th slot of the grid for a pw x ph PU: 16-sample slots (32 for a side of 32), PUs narrower than their slot at every multiple
+ * of 4 inside it in turn; margin: the slots keep that far from the picture's borders */
+static void
+mcc_place(ovhip_pu_desc *d, int n, int margin)
+{
+    const int pw = 1 << d->log2_w, ph = 1 << d->log2_h, sw = pw > 16 ? 32 : 16, sh = ph > 16 ? 32 : 16;
+    const int x_lo = (margin + sw - 1) / sw * sw, y_lo = (margin + sh - 1) / sh * sh;
+    const int nx = (MC_W - margin - x_lo) / sw, ny = (MC_H - margin - y_lo) / sh;
+    d->x0 = (uint16_t)(x_lo + sw * (n % nx) + 4 * ((n / 7) % ((sw - pw) / 4 + 1)));
+    d->y0 = (uint16_t)(y_lo + sh * ((n / nx) % ny) + 4 * ((n / 5) % ((sh - ph) / 4 + 1)));
+}
+
+/* one axis of a reference window [s0, s0 + len) against [0, pic): 0 inside, 1 crosses the low border, 2 the high one, 3 / 4 wholly
+ * outside on the low / high side */
+static int
+mcc_axis_class(int s0, int len, int pic)
+{
+    return s0 + len <= 0 ? 3 : s0 >= pic ? 4 : s0 < 0 ? 1 : s0 + len > pic ? 2 : 0;
+}
+
+/* border family, one axis: a vector component (1/16) for the PU at pos (length pu_len, units of unit_len) so that SOME unit's window
+ * (luma: chroma == 0) has class `cls` and, if off >= 0, starts at offset `off` within its aligned group of 4; `pick` chooses among the
+ * vectors that do; frac: the fraction asked for (lost where clip_mv moves the vector).  Returns 0 if there is none. */
+static int
+mcc_find_mv(int pos, int pu_len, int unit_len, int pic, int chroma, int cls, int off, int frac, int pick, int32_t *mv)
+{
+    int found[1024], n = 0;
+    const int lo = -((pu_len + 3 + pos) << 4), hi = (pic + 2 - pos) << 4;
+    for (int dx = -(pu_len + 8 + pos); dx <= pic + 8 - pos && n < 1024; ++dx) {
+        int v = 16 * dx + frac;
+        v = v < lo ? lo : v > hi ? hi : v;                                   /* clip_mv */
+        if (n && found[n - 1] == v) continue;
+        for (int u = 0; u < pu_len; u += unit_len) {
+            const int s0 = chroma ? ((pos + u) >> 1) + (v >> 5) - 1 : pos + u + (v >> 4) - 3;
+            const int len = chroma ? (unit_len >> 1) + 3 : unit_len + 7;
+            if (mcc_axis_class(s0, len, chroma ? pic >> 1 : pic) == cls && (off < 0 || (s0 & 3) == off)) { found[n++] = v; break; }
+        }
+    }
+    if (!n) return 0;
+    *mv = found[pick % n];
+    return 1;
+}
+
+static void
+gen_mc_cells(const char *dir)
+{
+    g_seed = 0x266 + 1;                                       /* mc.ovg's seed: the first draws are its three pictures */
+    rcn_init_gpm_params();
+    OVCTUDec *c = ref_new_ctudec(0, 0);
+    g_ciip_c = c;
+    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
+    OVPicture *ref[3], *paint[3];
+    for (int i = 0; i < 3; ++i) {
+        ref[i] = ref_new_picture(MC_W, MC_H, 8 * (i + 1));
+        fill_plane(ref[i]->frame->data[0], MC_W, MC_H, MC_W);
+        fill_plane(ref[i]->frame->data[1], MC_W / 2, MC_H / 2, MC_W / 2);
+        fill_plane(ref[i]->frame->data[2], MC_W / 2, MC_H / 2, MC_W / 2);
+    }
+    g_seed = 0x266 + 811;                                     /* this generator's own */
+    /* the combine family's pictures: runs of 0 and 1023 (a few mid-range samples between), rows repeating with flips; the third
+     * picture is the first with a tenth of its samples drawn again, so that both lists of a bi-prediction overshoot together */
+    for (int i = 0; i < 3; ++i) {
+        paint[i] = ref_new_picture(MC_W, MC_H, 8 * (i + 1));
+        for (int p = 0; p < 3; ++p) {
+            const int w = MC_W >> !!p, h = MC_H >> !!p;
+            uint16_t *a = (uint16_t *)paint[i]->frame->data[p];
+            for (int y = 0; y < h; ++y) {
+                int v = rnd_range(0, 1) ? 1023 : 0, run = rnd_range(1, 7);
+                for (int x = 0; x < w; ++x) {
+                    if (!run--) { v = rnd_range(0, 7) == 0 ? rnd_range(0, 1023) : v > 511 ? 0 : 1023; run = rnd_range(1, 7); }
+                    a[y * w + x] = (uint16_t)((y % 3) && rnd_range(0, 7) ? a[(y - 1) * w + x] : v);
+                }
+            }
+            if (i == 2) {
+                const uint16_t *src = (const uint16_t *)paint[0]->frame->data[p];
+                for (int k = 0; k < w * h; ++k) if (rnd_range(0, 9)) a[k] = src[k];
+            }
+        }
+    }
+    for (int p = 0; p < 3; ++p) {
+        g_ciip_intra[p] = malloc((MC_W >> !!p) * (MC_H >> !!p) * 2);
+        for (int k = 0; k < (MC_W >> !!p) * (MC_H >> !!p); ++k) {
+            const int r = rnd_range(0, 3);
+            g_ciip_intra[p][k] = (uint16_t)(r == 0 ? 0 : r == 1 ? 1023 : rnd_range(0, 1023));
+        }
+    }
+    for (int i = 0; i < 16; ++i) {
+        ic->scale_fact_rpl0[i][0] = ic->scale_fact_rpl0[i][1] = 1 << RPR_SCALE_BITS;
+        ic->scale_fact_rpl1[i][0] = ic->scale_fact_rpl1[i][1] = 1 << RPR_SCALE_BITS;
+    }
+    c->rcn_funcs.intra_pred = stub_ciip_intra_l;
+    c->rcn_funcs.intra_pred_c = stub_ciip_intra_c;
+    c->part_map.cu_mode_x = calloc(64, 1);
+    struct mcc_ctx M = { c, ic };
+    #define MCC_REFS(r) do { ic->rpl0[0] = (r)[0]; ic->rpl0[1] = (r)[1]; ic->rpl1[0] = (r)[2]; ic->rpl1[1] = (r)[0]; } while (0)
+
+    /* ---- phase ---- */
+    {
+        struct mcc_out o = { .dir = dir, .prefix = "mc_cells", .fam = "phase", .desc = { .type = T_U8 }, .eoff = { .type = T_U32 }, .exp = { .type = T_U16 }, .modes = { .type = T_I32 } };
+        MCC_REFS(ref);
+        int n = 0;
+        for (int l2w = 2; l2w <= 4; ++l2w)
+            for (int l2h = 2; l2h <= 4; ++l2h)
+                for (int dirn = 1; dirn <= 3; ++dirn) {
+                    for (int k = 0; k < 32 + (l2w + l2h > 4 ? 4 : 0); ++k, ++n) {
+                        ovhip_pu_desc d;
+                        memset(&d, 0, sizeof(d));
+                        d.log2_w = l2w; d.log2_h = l2h; d.inter_dir = dirn; d.planes = 3;
+                        d.ref_idx0 = n & 1; d.ref_idx1 = 0;
+                        int fa[2], fb[2];                                     /* (fx, fy) of the list the case is about, of the other one */
+                        if (k < 32) { fa[0] = k; fa[1] = (13 * k + 5) & 31; fb[0] = 31 - k; fb[1] = (7 * k + 2) & 31; }
+                        else {
+                            static const int hp[4][2] = { { 8, 8 }, { 8, 24 }, { 24, 3 }, { 5, 8 } };
+                            fa[0] = hp[k - 32][0]; fa[1] = hp[k - 32][1]; fb[0] = fa[1]; fb[1] = fa[0];
+                            d.prec_amvr_half = 1;
+                        }
+                        const int ix = 32 * (k % 5 - 2), iy = 32 * (k % 3 - 1);
+                        const int a = dirn == 2;                              /* the list the case is about */
+                        int32_t mv[2][2] = { { ix + fa[0], iy + fa[1] }, { -ix + fb[0], -iy + fb[1] } };
+                        d.mv0x = mv[a][0]; d.mv0y = mv[a][1]; d.mv1x = mv[!a][0]; d.mv1y = mv[!a][1];
+                        mcc_place(&d, n, 12);
+                        mcc_case(&o, &M, &d, MCC_PLAIN, NULL, 0);
+                    }
+                }
+        mcc_flush(&o);
+    }
+    /* ---- combine ---- */
+    {
+        struct mcc_out o = { .dir = dir, .prefix = "mc_cells", .fam = "combine", .desc = { .type = T_U8 }, .eoff = { .type = T_U32 }, .exp = { .type = T_U16 }, .modes = { .type = T_I32 },
+                             .ref = paint, .intra = g_ciip_intra };
+        MCC_REFS(paint);
+        int n = 0;
+        for (int l2w = 2; l2w <= 4; ++l2w)
+            for (int l2h = 2; l2h <= 4; ++l2h) {
+                for (int cell = 0; cell < 8; ++cell)                          /* uni L0, uni L1, average, BCW index 1..5 */
+                    for (int rep = 0; rep < 3; ++rep, ++n) {
+                        ovhip_pu_desc d;
+                        memset(&d, 0, sizeof(d));
+                        d.log2_w = l2w; d.log2_h = l2h; d.planes = 3;
+                        d.inter_dir = cell < 2 ? cell + 1 : 3;
+                        d.bcw_idx_plus1 = cell < 3 ? 0 : cell - 2;
+                        d.ref_idx0 = 0; d.ref_idx1 = 0;                       /* the first picture and its near copy */
+                        d.mv0x = rnd_range(-40, 40) | 1; d.mv0y = rnd_range(-40, 40) | 2;
+                        d.mv1x = d.mv0x + 2 * rnd_range(-1, 1); d.mv1y = d.mv0y + 4 * rnd_range(-1, 1);
+                        mcc_place(&d, n, 12);
+                        mcc_case(&o, &M, &d, MCC_PLAIN, NULL, 0);
+                    }
+                if (l2w >= 3 && l2h >= 3)                                     /* GPM: coding units of 8x8 and more (rcn_gpm_b) */
+                    for (int k = 0; k < 16; ++k, ++n) {
+                        ovhip_pu_desc d;
+                        memset(&d, 0, sizeof(d));
+                        d.log2_w = l2w; d.log2_h = l2h;
+                        d.gpm_split_dir = (uint8_t)((4 * k + 2 * (l2w - 3) + (l2h - 3)) & 63);
+                        d.inter_dir = (uint8_t)(rnd_range(1, 2) | rnd_range(1, 2) << 2);
+                        d.ref_idx0 = 0; d.ref_idx1 = rnd_range(0, 1);
+                        d.mv0x = rnd_range(-40, 40) | 1; d.mv0y = rnd_range(-40, 40) | 2;
+                        d.mv1x = rnd_range(-40, 40) | 4; d.mv1y = rnd_range(-40, 40) | 1;
+                        d.prec_amvr_half = k % 5 == 2;
+                        mcc_place(&d, n, 12);
+                        mcc_case(&o, &M, &d, MCC_GPM, NULL, 0);
+                    }
+                if (l2w + l2h >= 6)                                           /* CIIP: coding units of 64 samples and more */
+                    for (int wt = 1; wt <= 3; ++wt)
+                        for (int dirn = 0; dirn <= 3; ++dirn, ++n) {          /* 0: list 0 through the P-slice entry point */
+                            ovhip_pu_desc d;
+                            memset(&d, 0, sizeof(d));
+                            d.log2_w = l2w; d.log2_h = l2h; d.inter_dir = dirn ? dirn : 1;
+                            d.ref_idx0 = 0; d.ref_idx1 = 0;
+                            d.mv0x = rnd_range(-40, 40) | 1; d.mv0y = rnd_range(-40, 40) | 2;
+                            d.mv1x = d.mv0x + 2 * rnd_range(-1, 1); d.mv1y = d.mv0y + 4 * rnd_range(-1, 1);
+                            const int32_t modes[2] = { wt >= 2 ? OV_INTRA : n & 1 ? OV_INTER : OV_INTER_SKIP, wt == 3 ? OV_MIP : OV_INTER };
+                            mcc_place(&d, n, 12);
+                            mcc_case(&o, &M, &d, MCC_CIIP, modes, dirn == 0);
+                        }
+            }
+        mcc_flush(&o);
+    }
+    /* ---- planes ---- */
+    {
+        struct mcc_out o = { .dir = dir, .prefix = "mc_cells", .fam = "planes", .desc = { .type = T_U8 }, .eoff = { .type = T_U32 }, .exp = { .type = T_U16 }, .modes = { .type = T_I32 } };
+        MCC_REFS(ref);
+        int n = 0;
+        for (int l2w = 2; l2w <= 4; ++l2w)
+            for (int l2h = 2; l2h <= 4; ++l2h)
+                for (int planes = 1; planes <= 3; ++planes)
+                    for (int dirn = 1; dirn <= 3; ++dirn, ++n) {
+                        ovhip_pu_desc d;
+                        memset(&d, 0, sizeof(d));
+                        d.log2_w = l2w; d.log2_h = l2h; d.inter_dir = dirn; d.planes = planes;
+                        d.ref_idx0 = n & 1; d.ref_idx1 = 0;
+                        d.bcw_idx_plus1 = n % 4 == 1 ? 1 + n % 5 : 0;
+                        d.mv0x = rnd_range(-60, 60); d.mv0y = rnd_range(-60, 60); d.mv1x = rnd_range(-60, 60); d.mv1y = rnd_range(-60, 60);
+                        mcc_place(&d, n, 12);
+                        mcc_case(&o, &M, &d, MCC_PLAIN, NULL, 0);
+                    }
+        mcc_flush(&o);
+    }
+    /* ---- border ---- */
+    {
+        struct mcc_out o = { .dir = dir, .prefix = "mc_cells", .fam = "border", .desc = { .type = T_U8 }, .eoff = { .type = T_U32 }, .exp = { .type = T_U16 }, .modes = { .type = T_I32 } };
+        MCC_REFS(ref);
+        /* (class along x, class along y) of the twelve side sets: L R T B, the corners LT RT LB RB, wholly outside L R T B */
+        static const int sets[12][2] = { { 1, 0 }, { 2, 0 }, { 0, 1 }, { 0, 2 }, { 1, 1 }, { 2, 1 }, { 1, 2 }, { 2, 2 }, { 3, 0 }, { 4, 0 }, { 0, 3 }, { 0, 4 } };
+        int n = 0;
+        for (int chroma = 0; chroma <= 1; ++chroma)
+            for (int l2w = 2; l2w <= 4; ++l2w)
+                for (int l2h = 2; l2h <= 4; ++l2h)
+                    for (int s = 0; s < 12; ++s)
+                        for (int off = 0; off < 4; ++off) {
+                            ovhip_pu_desc d;
+                            memset(&d, 0, sizeof(d));
+                            /* a unit wholly outside: of a PU of 32 where the unit's side is 16 (clip_mv keeps a PU's window
+                             * within reach of the picture; only a unit further out in a larger PU leaves it for good) */
+                            d.log2_w = (uint8_t)(sets[s][0] >= 3 && l2w == 4 ? 5 : l2w);
+                            d.log2_h = (uint8_t)(sets[s][1] >= 3 && l2h == 4 ? 5 : l2h);
+                            d.inter_dir = (uint8_t)(1 + n % 3); d.planes = 3;
+                            d.ref_idx0 = n & 1; d.ref_idx1 = 0;
+                            mcc_place(&d, n, 0);
+                            int32_t mvx, mvy;
+                            if (!mcc_find_mv(d.x0, 1 << d.log2_w, 1 << l2w, MC_W, chroma, sets[s][0], off, (5 * n + 3) & 15, 7 * n + 1, &mvx)) continue;
+                            if (!mcc_find_mv(d.y0, 1 << d.log2_h, 1 << l2h, MC_H, chroma, sets[s][1], -1, (3 * n + 6) & 15, 5 * n + 2, &mvy)) continue;
+                            const int a = d.inter_dir == 2 || (d.inter_dir == 3 && (n & 2));        /* the list the case is about */
+                            int32_t ox = rnd_range(-70, 70), oy = rnd_range(-70, 70);
+                            if (a) { d.mv1x = mvx; d.mv1y = mvy; d.mv0x = ox; d.mv0y = oy; }
+                            else   { d.mv0x = mvx; d.mv0y = mvy; d.mv1x = ox; d.mv1y = oy; }
+                            mcc_case(&o, &M, &d, MCC_PLAIN, NULL, 0);
+                            ++n;
+                        }
+        mcc_flush(&o);
+    }
+    #undef MCC_REFS
+}
+
+/* one DMVR PU (= one unit) through rcn_dmvr_mv_refine on the pictures of mcx.ovg's lists: rpl0 = { 0, 2 }, rpl1 = { 1, 0 } */
+static void
+mcxc_run(struct mcc_out *o, OVCTUDec *c, ovhip_pu_desc *d)
+{
+    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
+    const struct OVBuffInfo *cb = &c->rcn_ctx.ctu_buff;
+    static const uint8_t slot0[2] = { 0, 2 }, slot1[2] = { 1, 0 };
+    d->poc0 = ic->rpl0[d->ref_idx0]->poc; d->poc1 = ic->rpl1[d->ref_idx1]->poc;
+    d->ref0 = slot0[d->ref_idx0]; d->ref1 = slot1[d->ref_idx1];
+    c->ctb_x = d->x0 >> 7; c->ctb_y = d->y0 >> 7;
+    ic->prec_amvr = d->prec_amvr_half ? MV_PRECISION_HALF : 0;
+    mcc_fill(cb);
+    OVMV m0 = { .x = d->mv0x, .y = d->mv0y, .ref_idx = d->ref_idx0 }, m1 = { .x = d->mv1x, .y = d->mv1y, .ref_idx = d->ref_idx1 };
+    c->rcn_funcs.rcn_dmvr_mv_refine(c, *cb, d->x0 & 127, d->y0 & 127, d->log2_w, d->log2_h, &m0, &m1, d->ref_idx0, d->ref_idx1, d->refine & OVHIP_PU_BDOF);
+    uint32_t eoff[4];
+    eoff[3] = (uint32_t)o->mv.n;
+    int32_t out[4] = { m0.x, m0.y, m1.x, m1.y };
+    gbuf_push(&o->mv, out, 4);
+    mcc_dump(o, cb, d, eoff);
+    gbuf_push(&o->desc, d, sizeof(*d));
+    gbuf_push(&o->eoff, eoff, 4);
+    o->n++;
+}
+
+static void
+gen_mcx_cells(const char *dir)
+{
+    g_seed = 0x266 + 77;                                      /* mcx.ovg's seed: the first draws are its three pictures */
+    OVCTUDec *c = ref_new_ctudec(0, 0);
+    struct InterDRVCtx *ic = &c->drv_ctx.inter_ctx;
+    OVPicture *ref[3];
+    mcx_make_refs(ref);
+    g_seed = 0x266 + 877;                                     /* this generator's own */
+    ic->rpl0[0] = ref[0]; ic->rpl0[1] = ref[2]; ic->rpl1[0] = ref[1]; ic->rpl1[1] = ref[0];
+    for (int i = 0; i < 16; ++i) {
+        ic->scale_fact_rpl0[i][0] = ic->scale_fact_rpl0[i][1] = 1 << RPR_SCALE_BITS;
+        ic->scale_fact_rpl1[i][0] = ic->scale_fact_rpl1[i][1] = 1 << RPR_SCALE_BITS;
+    }
+    static const int shapes[3][2] = { { 3, 4 }, { 4, 3 }, { 4, 4 } };
+    for (int fam = 0; fam < 2; ++fam) {
+        struct mcc_out o = { .dir = dir, .prefix = "mcx_cells", .fam = fam ? "limit" : "far", .with_mv = 1, .desc = { .type = T_U8 }, .eoff = { .type = T_U32 },
+                             .exp = { .type = T_U16 }, .modes = { .type = T_I32 }, .mv = { .type = T_I32 } };
+        int n = 0;
+        for (int sh = 0; sh < 3; ++sh)
+            for (int refine = 2; refine <= 3; ++refine)
+                for (int s0 = 0; s0 < 4 + 4 * fam; ++s0)                      /* list 0: left, right, top, bottom (limit: the corner of signs, twice) */
+                    for (int s1 = 0; s1 < 5; ++s1, ++n) {                     /* list 1: within range, or one of the four (limit: its corner of signs) */
+                        ovhip_pu_desc d;
+                        memset(&d, 0, sizeof(d));
+                        d.log2_w = shapes[sh][0]; d.log2_h = shapes[sh][1]; d.inter_dir = 3; d.planes = 3; d.refine = (uint8_t)refine;
+                        d.ref_idx0 = n % 6 == 5; d.ref_idx1 = n % 8 == 7;
+                        d.prec_amvr_half = n % 5 == 2;
+                        mcc_place(&d, n, 0);
+                        const int w = 1 << d.log2_w, h = 1 << d.log2_h;
+                        int32_t mv[2][2];
+                        for (int l = 0; l < 2; ++l) {
+                            const int side = l ? s1 - 1 : s0;
+                            mv[l][0] = rnd_range(-40, 40); mv[l][1] = rnd_range(-40, 40);
+                            if (fam == 0) {
+                                /* beyond clip_mv's range by a fraction of a sample, or by whole samples */
+                                const int past = n % 3 == 0 ? 1 + n % 15 : 16 * (1 + n % 40) + rnd_range(0, 15);
+                                if (side == 0) mv[l][0] = -((w + 3 + d.x0) << 4) - past;
+                                if (side == 1) mv[l][0] = ((MC_W + 2 - d.x0) << 4) + past;
+                                if (side == 2) mv[l][1] = -((h + 3 + d.y0) << 4) - past;
+                                if (side == 3) mv[l][1] = ((MC_H + 2 - d.y0) << 4) + past;
+                                if (l && side < 0) { mv[1][0] = -(mv[0][0] % 64) + rnd_range(-20, 20); mv[1][1] = -(mv[0][1] % 64) + rnd_range(-20, 20); }
+                            } else {
+                                /* within a few sixteenths of +-2^17 in one or both components */
+                                const int sx = (l ? s1 : s0) & 1 ? 1 : -1, sy = (l ? s1 : s0) & 2 ? 1 : -1, e = rnd_range(0, 24);
+                                if ((n + l) % 3 != 1) mv[l][0] = sx > 0 ? (1 << 17) - 1 - e : -(1 << 17) + e;
+                                if ((n + l) % 3 != 2) mv[l][1] = sy > 0 ? (1 << 17) - 1 - e / 2 : -(1 << 17) + e / 2;
+                            }
+                        }
+                        d.mv0x = mv[0][0]; d.mv0y = mv[0][1]; d.mv1x = mv[1][0]; d.mv1y = mv[1][1];
+                        mcxc_run(&o, c, &d);
+                    }
+        mcc_flush(&o);
+    }
+
+    /* ---- paint: a pair of pictures made for the search's branches, in regions of 26 x 24 -- smooth content, rows that are flat, columns
+     * that are flat, a constant, a step edge; the second picture is the first displaced by a whole (dx, dy) of -2..2 per region plus
+     * noise of a per-region amplitude around the two cost thresholds (0: an exact copy; a constant region: offset by 0..6 instead).
+     * The cases are a table: 400000 random candidates (position, shape, vectors mirrored with a little jitter, some on whole samples)
+     * were once traced through the oracle and the 41 kept that reached an outcome of the search no earlier one had (early exit,
+     * arg-min index, tie kind, sub-pel branch per axis, +-7, BDOF kept or switched off by the cost); tests/mc_census.py says what
+     * each reaches now.  Two constant regions near the ends of the sample range, noisy enough for BDOF to stay on, clip its output. ---- */
+    {
+        OVPicture *paint[3];
+        for (int i = 0; i < 3; ++i) {
+            paint[i] = ref_new_picture(MC_W, MC_H, i == 0 ? 8 : (i == 1 ? 24 : 4));
+            for (int p = 0; p < 3; ++p) fill_plane(paint[i]->frame->data[p], MC_W >> !!p, MC_H >> !!p, MC_W >> !!p);
+        }
+        uint16_t *a = (uint16_t *)paint[0]->frame->data[0], *b = (uint16_t *)paint[1]->frame->data[0];
+        static int typ[40], shx[40], shy[40], amp[40], va[40], vb[40];
+        static const int amps[8] = { 0, 0, 1, 2, 3, 5, 8, 12 };
+        for (int k = 0; k < 40; ++k) {
+            typ[k] = k % 5; shx[k] = rnd_range(-2, 2); shy[k] = rnd_range(-2, 2); amp[k] = amps[rnd_range(0, 7)];
+            va[k] = rnd_range(100, 900); vb[k] = va[k] + rnd_range(-200, 200);
+        }
+        #define REGION(x, y) (((y) / 24) * 8 + (x) / 26)
+        for (int y = 0; y < MC_H; ++y)
+            for (int x = 0; x < MC_W; ++x) {
+                const int k = REGION(x, y);
+                if (typ[k] == 1) a[y * MC_W + x] = a[y * MC_W + (x / 26) * 26];                   /* flat rows */
+                if (typ[k] == 2) a[y * MC_W + x] = a[(y / 24) * 24 * MC_W + x];                   /* flat columns */
+                if (typ[k] == 3) a[y * MC_W + x] = (uint16_t)va[k];
+                if (typ[k] == 4) a[y * MC_W + x] = (uint16_t)(x % 26 < 13 ? va[k] : vb[k]);
+            }
+        for (int y = 0; y < MC_H; ++y)
+            for (int x = 0; x < MC_W; ++x) {
+                const int k = REGION(x, y);
+                int sx = x + shx[k], sy = y + shy[k];
+                sx = sx < 0 ? 0 : sx >= MC_W ? MC_W - 1 : sx; sy = sy < 0 ? 0 : sy >= MC_H ? MC_H - 1 : sy;
+                int v = typ[k] == 3 ? va[k] + k % 7 : a[sy * MC_W + sx] + (amp[k] ? rnd_range(-amp[k], amp[k]) : 0);
+                b[y * MC_W + x] = (uint16_t)(v < 0 ? 0 : v > 1023 ? 1023 : v);
+            }
+        #undef REGION
+        /* a zero denominator of the sub-pel step takes three equal costs around the minimum, and beside a minimum anywhere but at the
+         * centre the lower index would have won: the centre's cost (three quarters of its SAD) has to equal both neighbours'.  Two
+         * constant regions carry an offset profile made for that, for an 8x16 unit at (88, 4) along x and a 16x16 unit at (4, 28)
+         * along y (every second row counts): a shift by one sample either way lowers the SAD by exactly a quarter, by two raises it. */
+        for (int y = 0; y < 24; ++y)
+            for (int x = 78; x < 104; ++x) {
+                const int j = x - 88, g = j == 0 || j == 7 ? 6 : j > 0 && j < 7 ? 2 : j == -1 || j == 8 ? 0 : 20;
+                b[y * MC_W + x] = (uint16_t)(va[3] + g);
+            }
+        for (int y = 24; y < 48; ++y)
+            for (int x = 0; x < 26; ++x) {
+                const int j = y - 28, g = j == -1 || j == 15 ? 4 : j < -1 || j > 15 ? 20 : j & 1 ? 2 : 3;
+                b[y * MC_W + x] = (uint16_t)(va[8] + g);
+            }
+        /* BDOF's output clips: both pictures within 40 of an end of the range, independently drawn, in two regions no case of the
+         * table reads (high at (52, 0), low at (182, 96)) */
+        for (int hi = 0; hi <= 1; ++hi)
+            for (int y = hi ? 0 : 96; y < (hi ? 24 : 120); ++y)
+                for (int x = hi ? 52 : 182; x < (hi ? 78 : 208); ++x) {
+                    a[y * MC_W + x] = (uint16_t)(hi ? 1023 - rnd_range(0, 39) : rnd_range(0, 39));
+                    b[y * MC_W + x] = (uint16_t)(hi ? 1023 - rnd_range(0, 39) : rnd_range(0, 39));
+                }
+        ic->rpl0[0] = paint[0]; ic->rpl0[1] = paint[2]; ic->rpl1[0] = paint[1]; ic->rpl1[1] = paint[0];
+        struct mcc_out o = { .dir = dir, .prefix = "mcx_cells", .fam = "paint", .with_mv = 1, .desc = { .type = T_U8 }, .eoff = { .type = T_U32 },
+                             .exp = { .type = T_U16 }, .modes = { .type = T_I32 }, .mv = { .type = T_I32 }, .ref = paint };
+        static const int16_t found[41][9] = {      /* log2_w, log2_h, refine, x0, y0, mv0x, mv0y, mv1x, mv1y */
+            { 3, 4, 2, 20, 0, 0, 32, 0, -32 }, { 4, 3, 2, 176, 44, 0, -16, 0, 16 }, { 3, 4, 2, 128, 36, -33, -9, 33, 9 },
+            { 4, 3, 3, 56, 84, -48, 0, 48, 0 }, { 3, 4, 3, 200, 56, 16, 0, -16, 0 }, { 4, 4, 2, 20, 12, -5, -13, 5, 13 },
+            { 4, 4, 3, 16, 52, -23, -34, 39, 21 }, { 4, 4, 2, 60, 76, 21, 7, -21, -7 }, { 4, 3, 3, 64, 56, 16, 0, -16, 0 },
+            { 3, 4, 2, 160, 8, -16, 21, 6, -14 }, { 4, 3, 3, 180, 40, 15, -38, -28, 38 }, { 3, 4, 2, 136, 60, 16, -29, -7, 43 },
+            { 4, 3, 3, 144, 32, -22, -17, 22, 17 }, { 3, 4, 2, 84, 88, -16, 0, 16, 0 }, { 3, 4, 3, 156, 0, -32, -16, 32, 16 },
+            { 4, 3, 2, 100, 112, 11, 18, -2, -37 }, { 3, 4, 2, 8, 88, -16, 0, 16, 0 }, { 4, 4, 2, 112, 8, 9, 37, -9, -37 },
+            { 3, 4, 3, 48, 60, 14, 30, -14, -30 }, { 3, 4, 2, 96, 104, 16, 16, -16, -16 }, { 3, 4, 2, 32, 32, 18, 25, -28, -22 },
+            { 4, 4, 2, 52, 28, 22, -40, -13, 29 }, { 3, 4, 3, 152, 72, -16, 32, 16, -32 }, { 4, 3, 2, 84, 108, 17, -14, -17, 14 },
+            { 4, 3, 3, 24, 36, 17, -21, -17, 21 }, { 4, 4, 2, 104, 28, -16, 0, 16, 0 }, { 4, 3, 3, 128, 72, -48, 0, 48, 0 },
+            { 4, 3, 3, 4, 32, 16, -16, -16, 16 }, { 3, 4, 2, 104, 4, 23, -13, -10, 31 }, { 4, 4, 2, 140, 88, 1, -13, -4, 23 },
+            { 3, 4, 2, 168, 8, -48, -16, 48, 16 }, { 4, 3, 2, 156, 96, 0, 16, 0, -16 }, { 3, 4, 2, 92, 100, -16, 0, 16, 0 },
+            { 4, 4, 3, 156, 52, 0, -32, 0, 32 }, { 4, 4, 3, 176, 32, 11, -2, -15, 14 }, { 3, 4, 3, 56, 84, -32, 0, 32, 0 },
+            { 4, 4, 3, 4, 28, -24, -15, 36, 19 }, { 3, 4, 3, 0, 28, 21, 3, -21, -3 }, { 4, 4, 3, 4, 28, 0, 0, 0, 0 },
+            { 4, 3, 3, 140, 24, 23, 1, -26, 0 }, { 3, 4, 2, 88, 4, 0, 32, 0, -32 },
+        };
+        for (int k = 0; k < 41; ++k) {
+            ovhip_pu_desc d;
+            memset(&d, 0, sizeof(d));
+            d.log2_w = (uint8_t)found[k][0]; d.log2_h = (uint8_t)found[k][1]; d.inter_dir = 3; d.planes = 3; d.refine = (uint8_t)found[k][2];
+            d.x0 = (uint16_t)found[k][3]; d.y0 = (uint16_t)found[k][4];
+            d.mv0x = found[k][5]; d.mv0y = found[k][6]; d.mv1x = found[k][7]; d.mv1y = found[k][8];
+            mcxc_run(&o, c, &d);
+        }
+        for (int k = 0; k < 2; ++k) {                                        /* the two zero-denominator cases */
+            ovhip_pu_desc d;
+            memset(&d, 0, sizeof(d));
+            d.log2_w = k ? 4 : 3; d.log2_h = 4; d.inter_dir = 3; d.planes = 3; d.refine = OVHIP_PU_DMVR;
+            d.x0 = k ? 4 : 88; d.y0 = k ? 28 : 4;
+            mcxc_run(&o, c, &d);
+        }
+        for (int sh = 0; sh < 3; ++sh)                                      /* BDOF's output clips, at 1023 and at 0 */
+            for (int k = 0; k < 8; ++k) {
+                ovhip_pu_desc d;
+                memset(&d, 0, sizeof(d));
+                d.log2_w = shapes[sh][0]; d.log2_h = shapes[sh][1]; d.inter_dir = 3; d.planes = 3; d.refine = OVHIP_PU_DMVR | OVHIP_PU_BDOF;
+                d.x0 = (uint16_t)((k & 1 ? 184 : 56) + 4 * ((k >> 1) & 1)); d.y0 = (uint16_t)((k & 1 ? 100 : 4) + 4 * (k >> 2) * (shapes[sh][1] == 3));
+                d.mv0x = 3 + 2 * k; d.mv0y = 5 - k; d.mv1x = -d.mv0x + (k >> 2); d.mv1y = -d.mv0y;
+                mcxc_run(&o, c, &d);
+            }
+        mcc_flush(&o);
+    }
 }
 
 /* ====================================================================================== DBF */
@@ -2829,6 +3402,9 @@ main(int argc, char **argv)
     /* the cells intra.ovg does not reach: by name only, a run of its own */
     if (only && !strcmp(only, "intra_cells") && !g_shim) gen_intra_cells(dir);
     if (only && !strcmp(only, "itx_cells") && !g_shim) gen_itx_cells(dir);
+    /* the enumerated inter prediction cells: by name only, each a run of its own */
+    if (only && !strcmp(only, "mc_cells") && !g_shim) gen_mc_cells(dir);
+    if (only && !strcmp(only, "mcx_cells") && !g_shim) gen_mcx_cells(dir);
     if (!only || !strcmp(only, "intra_ctu")) gen_intra_ctu(dir);
     if (!only || !strcmp(only, "isp")) gen_isp(dir);
     return 0;

@@ -88,21 +88,47 @@ def tt_cases():
     return pic, rec.tb_cmds(), rec.coefs(), rects, g["exp"]
 
 
-def mc_cases():
-    g = golden_io.load("mc.ovg")
-    n = g["desc"].shape[0]
+def mc_cell_files():
+    """the enumerated cells of the plain prediction units (gen_mc_cells), one or more files per family"""
+    return sorted(p.name for p in golden_io.GOLDEN.glob("mc_cells_*.ovg"))
+
+
+def mcx_cell_files():
+    """the enumerated cells of the refined (DMVR) units (gen_mcx_cells)"""
+    return sorted(p.name for p in golden_io.GOLDEN.glob("mcx_cells_*.ovg"))
+
+
+def _refs(g, fallback):
+    if "ref_y" not in g:
+        g = golden_io.load(fallback)       # the cell files on mc.ovg's / mcx.ovg's pictures do not store them again
     _, rh, rw = g["ref_y"].shape
-    refs = [HostPic(rw, rh, g["ref_y"][k], g["ref_cb"][k], g["ref_cr"][k]) for k in range(3)]
+    return [HostPic(rw, rh, g["ref_y"][k], g["ref_cb"][k], g["ref_cr"][k]) for k in range(3)]
+
+
+def mc_cases(name="mc.ovg"):
+    g = golden_io.load(name)
+    n = g["desc"].shape[0]
     descs = [capi.PuDesc.from_buffer_copy(g["desc"][i].tobytes()) for i in range(n)]
-    return refs, descs, g["exp_off"], g["exp"]
+    return _refs(g, "mc.ovg"), descs, g["exp_off"], g["exp"]
 
 
-def mcx_cases():
+def mc_cell_cases(name):
+    """one of mc_cell_files(): (refs, intra HostPic or None, descs, exp_off, exp).  The descriptors of the CIIP cases carry the fused
+    blend's weight (ovhip_ciip_weight of the neighbours' modes the reference ran with); those of the GPM cases are as recorded."""
+    g = golden_io.load(name)
+    refs, descs, exp_off, exp = mc_cases(name)
+    intra = HostPic(refs[0].w, refs[0].h, g["intra_y"], g["intra_cb"], g["intra_cr"]) if "intra_y" in g else None
+    for d, m in zip(descs, g["ciip_modes"]):
+        if m[0] or m[1]:
+            d.ciip_wt = capi.load().ovhip_ciip_weight(int(m[0]), int(m[1]))
+    return refs, intra, descs, exp_off, exp
+
+
+def mcx_cases(name="mcx.ovg"):
     """BDOF / DMVR: (refs, descs, exp_off [n,4] (Y, Cb, Cr sample offsets + index of the first refined MV), exp, exp_mv [m,4])."""
-    g = golden_io.load("mcx.ovg")
+    g = golden_io.load(name)
     n = g["desc"].shape[0]
-    _, rh, rw = g["ref_y"].shape
-    refs = [HostPic(rw, rh, g["ref_y"][k], g["ref_cb"][k], g["ref_cr"][k]) for k in range(3)]
+    refs = _refs(g, "mcx.ovg")
     descs = [capi.PuDesc.from_buffer_copy(g["desc"][i].tobytes()) for i in range(n)]
     return refs, descs, g["exp_off"], g["exp"], g["exp_mv"].reshape(-1, 4)
 

@@ -34,6 +34,8 @@ def lib():
         _lib.oracle_mc_full.restype = None
         _lib.oracle_mc_ex.argtypes = [C.POINTER(OPic), C.POINTER(OPic), C.c_uint32, vp, C.c_uint32, vp, vp]
         _lib.oracle_mc_ex.restype = None
+        _lib.oracle_mcx_trace.argtypes = [C.POINTER(OPic), C.POINTER(OPic), C.c_uint32, vp, vp, vp, C.c_int]
+        _lib.oracle_mcx_trace.restype = None
         _lib.oracle_tmvp_cells.argtypes = [vp, C.c_uint32, vp, C.c_int, C.c_int, vp]
         _lib.oracle_tmvp_cells.restype = None
         _lib.oracle_itx_ex.argtypes = [C.POINTER(OPic), vp, C.c_uint32, vp, vp]
@@ -184,6 +186,17 @@ def mc_ex(dst: HostPic, refs, units: np.ndarray, lmcs_fwd=None) -> np.ndarray:
     mv = np.zeros((len(units), 4), np.int32)
     lib().oracle_mc_ex(C.byref(s), arr, len(refs), units.ctypes.data, len(units), lut, mv.ctypes.data)
     return mv
+
+
+def dmvr_trace(dst: HostPic, refs, unit, true_apron: bool = False) -> "tuple[np.ndarray, np.ndarray]":
+    """One refined unit through the oracle with the trace of its search and of BDOF -> (int64[115] as mc_refined_unit documents it,
+    refined vector).  true_apron: the edit that reads the reference picture in place of DMVR's replicated apron."""
+    s = dst.struct()
+    arr = (OPic * len(refs))(*[r.struct() for r in refs])
+    u = np.ascontiguousarray(np.array([unit], dtype=unit.dtype))
+    trace, mv = np.zeros(115, np.int64), np.zeros(4, np.int32)
+    lib().oracle_mcx_trace(C.byref(s), arr, len(refs), u.ctypes.data, mv.ctypes.data, trace.ctypes.data, int(true_apron))
+    return trace, mv
 
 
 def dbf_planes_struct(planes: dict):

@@ -251,7 +251,7 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     if not gen.exists() or not (root / "oracle" / "_ref" / "libovvcref.so").exists():
         pytest.skip("compiled reference not present")
     subprocess.check_call([str(gen), str(tmp_path)], stderr=subprocess.DEVNULL)
-    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells", "itx_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra / inverse transform cells are runs of their own
+    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells", "itx_cells", "mc_cells", "mcx_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra / inverse transform / inter prediction cells are runs of their own
         subprocess.check_call([str(gen), str(tmp_path), only], stderr=subprocess.DEVNULL)
     # shim_*: test_shim_cpu.py; pipe* / tiles*: the chained streams of gen_pipe, test_pipe_cpu.py
     names = sorted(p.name for p in (root / "tests" / "golden").glob("*.ovg") if not p.name.startswith(("shim_", "pipe", "tiles")))
@@ -260,6 +260,8 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
         assert (tmp_path / n).read_bytes() == (root / "tests" / "golden" / n).read_bytes(), f"{n} differs from a fresh run of the reference"
     assert sorted(p.name for p in tmp_path.glob("intra_cells_*.ovg")) == [n for n in names if n.startswith("intra_cells_")], "the generator cuts the intra cells into other files than the committed ones"
     assert sorted(p.name for p in tmp_path.glob("itx_cells_*.ovg")) == [n for n in names if n.startswith("itx_cells_")], "the generator cuts the inverse transform cells into other files than the committed ones"
+    assert sorted(p.name for p in tmp_path.glob("mc_cells_*.ovg")) == [n for n in names if n.startswith("mc_cells_")], "the generator cuts the plain prediction cells into other files than the committed ones"
+    assert sorted(p.name for p in tmp_path.glob("mcx_cells_*.ovg")) == [n for n in names if n.startswith("mcx_cells_")], "the generator cuts the refined prediction cells into other files than the committed ones"
 
 
 def test_intra_oracle_matches_reference(built_lib):
@@ -511,3 +513,263 @@ def test_itx_cells_discriminate(built_lib):
     print(f"edits: {n_tr} transform pairs, {n_lf} LFNST, {n_ext} extents, {n - n_tr - n_lf - n_ext} de-quantisation classes; without effect: {len(dull)}")
     assert n_tr > 100 and n_lf == 512 * 15 and n_ext > 100 and n - n_tr - n_lf - n_ext > 1500
     assert not dull, f"{len(dull)} of {n} edits leave the block as it is, first: {dull[:8]}"
+
+
+def _filled(w, h, fill=0xABAB):
+    pic = HostPic(w, h)
+    pic.y[:] = fill; pic.cb[:] = fill; pic.cr[:] = fill
+    return pic
+
+
+def _same_picture(got, want, what):
+    for name, a, b in zip("Y Cb Cr".split(), got.planes(), want.planes()):
+        bad = np.argwhere(a != b)
+        assert len(bad) == 0, f"{what}, plane {name}: {len(bad)} samples differ from the reference's picture, first at (y, x) {bad[:6].tolist()}"
+
+
+def test_mc_oracle_matches_reference_on_the_enumerated_cells(built_lib):
+    """mc_cells_*.ovg (gen_mc_cells: phases, combines, planes, windows across and beyond every border; the reference's rcn_mcp_b / _l / _c,
+    rcn_gpm_b, rcn_ciip / rcn_ciip_b): the oracle equals the reference on every case -- over the WHOLE picture: the cases run sheet by
+    sheet (PUs that do not overlap) into a filled picture, and every sample outside the PUs keeps the fill, as the generator checked the
+    reference's CTU buffer does."""
+    import golden_io
+    import mc_census as mc
+    files = golden_cases.mc_cell_files()
+    assert {f.split("_")[2] for f in files} == {"phase", "combine", "planes", "border"}
+    assert all((golden_io.GOLDEN / f).stat().st_size < (1 << 20) for f in files)
+    n = 0
+    for f in files:
+        refs, intra, descs, exp_off, exp, units = mc.plain_fixture(f)
+        for k, cases in enumerate(mc.sheets(descs)):
+            dst = _filled(refs[0].w, refs[0].h)
+            want = set(cases)
+            oracle_lib.mc(dst, refs, np.array([u for i, u, _ in units if i in want], capi.MC_UNIT_DTYPE), intra=intra)
+            _same_picture(dst, mc.expected_picture(descs, exp_off, exp, refs[0].w, refs[0].h, cases), f"{f} sheet {k}")
+        n += len(descs)
+    assert n > 2000
+
+
+def test_mcx_oracle_matches_reference_on_the_enumerated_cells(built_lib):
+    """mcx_cells_*.ovg (gen_mcx_cells: rcn_dmvr_mv_refine with initial vectors beyond clip_mv's range on every side, and next to the
+    +-2^17 limits): samples over the whole picture and the refined vectors."""
+    import golden_io
+    import mc_census as mc
+    files = golden_cases.mcx_cell_files()
+    assert {f.split("_")[2] for f in files} == {"far", "limit", "paint"}
+    assert all((golden_io.GOLDEN / f).stat().st_size < (1 << 20) for f in files)
+    for f in files:
+        refs, descs, exp_off, exp, exp_mv, units = mc.refined_fixture(f)
+        assert len(units) == len(descs) == len(exp_mv)           # a PU is one unit
+        for k, cases in enumerate(mc.sheets(descs)):
+            dst = _filled(refs[0].w, refs[0].h)
+            mv = oracle_lib.mc_ex(dst, refs, np.array([units[i][1] for i in cases], capi.MC_UNIT_DTYPE))
+            assert np.array_equal(mv, exp_mv[cases]), f"{f} sheet {k}: refined vectors differ from the reference's"
+            _same_picture(dst, mc.expected_picture(descs, exp_off, exp, refs[0].w, refs[0].h, cases), f"{f} sheet {k}")
+
+
+def test_mc_fixture_census(built_lib):
+    """What the inter prediction slot fixtures reach, written down so that it cannot shrink unnoticed (tests/mc_census.py does the
+    counting from the units Recorder.pu() cuts, and asserts its restatement of that cut against the recorder on every plain PU).
+
+    mc.ovg alone (750 random draws -> 1912 plain units, 4814 reference windows, 2415 of them luma) -- cells reached of cells that exist:
+      phase cells (pass, plane, shape, lists, list, phase; the luma phase is the tap row, 16 = half-pel): 1637 of 3520.  Keyed as the
+        issue counted them: luma H (shape, list, fx) 234 of 288, luma V (shape, fy) 142 of 144 + 8 half-pel, chroma H (shape, list, fx
+        of 32) 345 of 576, chroma V (shape, fy) 231 of 288;
+      combine cells (shape, uni L0 / L1 / weight pair / GPM / CIIP weight): 54 of 85 -- 36 of the 45 (shape, pair), no GPM, no CIIP;
+      plane cells (shape, lists, both / luma only / chroma only): 74 of 81;
+      luma windows: 1495 inside the picture, 260 wholly outside, 660 across a border; border cells (plane, shape, side set, offset 0..3)
+        365 of 732; staging paths interior and clamped, never slow; LMCS never on.
+    With mc_cells_*.ovg every cell that exists is reached, and every (shape, combine) of the combine family has a case whose combine
+    leaves the sample range below 0 and one above 1023 (from mc_census.final_before_clip, which is asserted to reproduce the reference's
+    samples on that family).  Not covered at this level: LMCS (the plain slots of the reference take no reshaper, so no fixture sets
+    the flag and the label only says so; tests/test_gpu_mc_cells.py runs the planes family with it against the oracle, the picture
+    streams pipe*.ovg run it against the reference), the slow staging path (no recorder emits it: it takes a picture whose stride or width is no multiple of 4,
+    tests/test_gpu_mc_cells.py runs the border family through such a view).
+
+    mcx.ovg alone (450 draws -> 1108 units, 728 of them DMVR): clip_mv moves the initial vector of 7 DMVR units (narrow units next to
+    the border; the far range is drawn for BDOF-only cases alone), never of both lists; 46 DMVR units keep their vectors; no refined
+    vector ends at a +-2^17 limit.  With mcx_cells_*.ovg: clip_mv moves the vector of each list on each of the four sides, for every
+    refined shape, with and without BDOF, and of both lists at once; the final clip stops every component of the refined vectors at
+    either limit where the initial vector was not there, which breaks the mirrored update.
+    DMVR's outcome, labelled from the oracle's trace of the 25 costs (the labels predict the reference's refined vector on every DMVR
+    unit of every file: mc_census.refined_fixture asserts it).  mcx.ovg alone: never an early exit (the 46 units that stay are centre
+    wins), all 25 arg-min indices, index ties but no centre tie, 8 of the 14 (axis, sub-pel branch) -- no zero denominator, no -8, no
+    +8 --, +-7 on both axes, BDOF never switched off by the cost (3 of 9 cells).  With the paint family every cell of
+    mc_census.dmvr_cells_that_exist() is reached.
+    Steps 3 and 4 of k_mcx (mc_census.refined_reads / label_bdof / refined_cells_that_exist).  mcx.ovg alone reaches all 18 (shape,
+    BDOF / DMVR / both, half-pel), all 25 (ldx, ldy) and 9 (cdx, cdy), and reads the apron on all four sides of the luma and of the
+    chroma windows in a way that shows (the reference picture's samples there would give another block: its pictures are rough
+    enough, computed from the pictures); of the 30 (shape, BDOF label) it reaches 24 -- never an output clipped at 0 or at 1023.  The paint family's two
+    regions near the ends of the sample range add those."""
+    import mc_census as mc
+    refs, _, descs, _, _, units = mc.plain_fixture("mc.ovg")
+    W, H = refs[0].w, refs[0].h
+    labels = [lb for _, _, lb in units]
+    r = mc.reach_plain(labels)
+    ph, cb, pl, bd = mc.phase_cells_that_exist(), mc.combine_cells_that_exist(), mc.plane_cells_that_exist(), mc.border_cells_that_exist(W, H)
+    assert (len(ph), len(cb), len(pl), len(bd)) == (3520, 85, 81, 732)
+    assert len(descs) == 750 and len(units) == 1912 and sum(len(lb["windows"]) for lb in labels) == 4814
+    assert r["phase"] <= ph and r["combine"] <= cb and r["planes"] <= pl and r["border"] <= bd
+    assert (len(r["phase"]), len(r["combine"]), len(r["planes"]), len(r["border"])) == (1637, 54, 74, 365)
+    coarse = lambda axis, plane, key: len({key(c) for c in r["phase"] if c[:2] == (axis, plane)})
+    assert coarse("H", "luma", lambda c: (c[2], c[4], c[5])) == 234 and coarse("V", "luma", lambda c: (c[2], c[5])) == 142
+    assert coarse("H", "chroma", lambda c: (c[2], c[4], c[5])) == 345 and coarse("V", "chroma", lambda c: (c[2], c[5])) == 231
+    assert len({c for c in r["combine"] if c[1][0] == "bi"}) == 36 and not {c for c in r["combine"] if c[1][0] in ("gpm", "ciip")}
+    lw = [w for lb in labels for w in lb["windows"] if not w[1]]
+    assert len(lw) == 2415 and sum(w[3] is None for w in lw) == 1495 and sum(w[3] is not None and w[3].startswith("out") for w in lw) == 260
+    assert r["path"] == {"interior", "clamped"} and r["lmcs"] == {False}
+
+    # ---- with the enumerated cells
+    fams = {}
+    for f in golden_cases.mc_cell_files():
+        refs_f, intra, descs_f, exp_off, exp, units_f = mc.plain_fixture(f)
+        assert (refs_f[0].w, refs_f[0].h) == (W, H)
+        fr = mc.reach_plain([lb for _, _, lb in units_f])
+        fam = fams.setdefault(f.split("_")[2], {k: set() for k in fr if isinstance(fr[k], set)})
+        for k in fam:
+            fam[k] |= fr[k]
+        r = {k: (r[k] | fr[k] if isinstance(fr[k], set) else r[k]) for k in r}
+    assert r["phase"] == ph, f"phase cells without a case: {sorted(ph - r['phase'])[:8]}"
+    assert r["combine"] == cb, f"combine cells without a case: {sorted(cb - r['combine'], key=str)[:8]}"
+    assert r["planes"] == pl and r["border"] == bd, f"border cells without a case: {sorted(bd - r['border'])[:8]}"
+    # each family reaches its cells on its own, the phase family with every window inside the picture
+    assert fams["phase"]["phase"] == ph and fams["phase"]["path"] == {"interior"}
+    assert fams["combine"]["combine"] == cb and fams["planes"]["planes"] == pl and fams["border"]["border"] == bd
+    assert r["nout"] == {(nl, nc, ls) for nl, nc in ((1, 1), (2, 1), (4, 2)) for ls in ("L0", "L1", "BI")}
+    # the combine family: the restated combine reproduces the reference, and the clip binds at both ends in every cell
+    clips = {}
+    for f in golden_cases.mc_cell_files():
+        if "_combine_" not in f:
+            continue
+        refs_f, intra, descs_f, exp_off, exp, units_f = mc.plain_fixture(f)
+        for i, u, lb in units_f:
+            d = descs_f[i]
+            assert (d.x0, d.y0, 1 << d.log2_w, 1 << d.log2_h) == (u["x"], u["y"], u["w"], u["h"])       # a PU is one unit
+            want = mc.expected_picture(descs_f, exp_off, exp, W, H, [i]).planes()
+            for p, (v, s) in enumerate(zip(mc.final_before_clip(u, refs_f), mc.final_samples(u, refs_f, intra))):
+                c = p != 0
+                x, y = d.x0 >> c, d.y0 >> c
+                assert np.array_equal(s, want[p][y:y + s.shape[0], x:x + s.shape[1]]), f"{f} case {i} plane {p}: the census restates another combine than the reference's"
+                ends = clips.setdefault((lb["shape"], lb["combine"][:3] if lb["combine"][0] == "ciip" else lb["combine"]), set())
+                ends |= ({"below 0"} if (v < 0).any() else set()) | ({"above 1023"} if (v > 1023).any() else set())
+    assert set(clips) == cb
+    dull = sorted((k for k, v in clips.items() if v != {"below 0", "above 1023"}), key=str)
+    assert not dull, f"(shape, combine) whose cases never leave the sample range at both ends: {dull[:8]}"
+
+    # ---- refined units
+    _, descs_x, _, _, _, ux = mc.refined_fixture("mcx.ovg")
+    dm = [lb for _, _, lb in ux if lb["dmvr"]]
+    assert len(descs_x) == 450 and len(ux) == 1108 and len(dm) == 728
+    assert sum(bool(lb["clip"]) for lb in dm) == 7 and not any(len({l for l, _ in lb["clip"]}) == 2 for lb in dm)
+    assert sum(not lb["moved"] for lb in dm) == 46 and not any(lb["at_limit"] for lb in dm) and all(lb["symmetric"] for lb in dm)
+    far = [lb for f in golden_cases.mcx_cell_files() if "_far_" in f for _, _, lb in mc.refined_fixture(f)[5]]
+    lim = [lb for f in golden_cases.mcx_cell_files() if "_limit_" in f for _, _, lb in mc.refined_fixture(f)[5]]
+    assert all(lb["dmvr"] for lb in far + lim)
+    want = {(s, b, l, side) for s in ((8, 16), (16, 8), (16, 16)) for b in (False, True) for l in (0, 1) for side in "LRTB"}
+    assert {(lb["shape"], lb["bdof"], l, side) for lb in far for l, side in lb["clip"]} == want
+    assert any(len({l for l, _ in lb["clip"]}) == 2 for lb in far) and any(lb["moved"] for lb in far if lb["clip"])
+    assert {e for lb in lim for e in lb["at_limit"] - lb["ini_at_limit"]} == {(k, hi) for k in range(4) for hi in (False, True)}, "a component the final clip never stops"
+    assert any(not lb["symmetric"] for lb in lim), "the +-2^17 clip never breaks the mirrored update"
+    # DMVR's outcome
+    cells = mc.dmvr_cells_that_exist()
+    rd = mc.reach_dmvr(dm)
+    assert all(rd[k] <= cells[k] for k in cells)
+    assert rd["exit"] == {(s, False) for s in mc.REFINED_SHAPES} and rd["idx"] == cells["idx"] and rd["tie"] == {"none", "index"}
+    assert rd["branch"] == {(a, b) for a in "xy" for b in ("ring", "q<0", "q=0", "q>0")} and rd["q7"] == cells["q7"]
+    assert not rd["clip"] and rd["bdof_off"] == {(s, True, False) for s in mc.REFINED_SHAPES}
+    assert all(lb["outcome"]["idx"] == 12 and lb["outcome"]["searched"] for lb in dm if not lb["moved"])
+    everything = dm + [lb for f in golden_cases.mcx_cell_files() for _, _, lb in mc.refined_fixture(f)[5]]
+    ra = mc.reach_dmvr(everything)
+    for k in cells:
+        assert ra[k] == cells[k], f"DMVR {k} cells without a case: {sorted(cells[k] - ra[k], key=str)}"
+    assert {e for lb in lim for e in lb["outcome"]["clip_binds"]} == cells["clip"]
+    # steps 3 and 4: flags, displacements, apron reads, BDOF
+    rc, all_x = mc.refined_cells_that_exist(), [lb for _, _, lb in ux]
+    r0 = mc.reach_refined(all_x)
+    assert all(r0[k] <= rc[k] for k in rc) and r0["disp_all"] <= rc["disp_l"]
+    assert (len(rc["flags"]), len(rc["disp_l"]), len(rc["disp_c"]), len(rc["apron"]), len(rc["bdof"])) == (18, 25, 9, 8, 30)
+    assert all(r0[k] == rc[k] for k in ("flags", "disp_l", "disp_c", "apron"))
+    assert rc["bdof"] - r0["bdof"] == {(s, c) for s in mc.REFINED_SHAPES for c in ("clip at 0", "clip at 1023")}
+    ra = mc.reach_refined(all_x + [lb for lb in everything if lb not in dm])
+    for k in rc:
+        assert ra[k] == rc[k], f"refined {k} cells without a case: {sorted(rc[k] - ra[k], key=str)}"
+    cells_alone = mc.reach_refined([lb for f in golden_cases.mcx_cell_files() for _, _, lb in mc.refined_fixture(f)[5]])
+    assert cells_alone["apron"] == rc["apron"] and cells_alone["bdof"] == rc["bdof"] and cells_alone["disp_l"] == rc["disp_l"]
+
+
+def test_mc_cells_discriminate(built_lib):
+    """The enumerated cells pin what they are named after: the oracle (equal to the reference on every case, above) predicts ANOTHER
+    block when a unit is edited -- every vector component of a list the unit reads moved by one sixteenth either way (the next phase;
+    phase family), the weights of a BCW pair swapped (combine family), and for the DMVR units whose initial vector lies beyond clip_mv's
+    range that component mirrored to the same distance inside it (far family: samples or refined vectors must change).  No edit may
+    fail to.  The apron edit (the oracle's true_apron switch: the final interpolation and BDOF's ring read the reference picture where
+    rcn_dmvr_mv_refine reads the 2-sample replicated apron) runs on every DMVR unit of mcx.ovg and of the cell files that
+    mc_census.refined_reads labels as reading the apron in a way that shows (the averaged sample or a ring sample differs): every one
+    must come out another block, on every (plane, side)."""
+    import mc_census as mc
+    dull, n = [], {"phase": 0, "bcw": 0, "clip": 0}
+
+    def run(refs, u, intra=None, refined=False):
+        dst = _filled(refs[0].w, refs[0].h, 0)
+        a = np.array([u], capi.MC_UNIT_DTYPE)
+        mv = oracle_lib.mc_ex(dst, refs, a) if refined else oracle_lib.mc(dst, refs, a, intra=intra)
+        return [p.copy() for p in dst.planes()], None if mv is None else mv.tolist()
+
+    def differs(a, b):
+        return a[1] != b[1] or any(not np.array_equal(p, q) for p, q in zip(a[0], b[0]))
+
+    for f in golden_cases.mc_cell_files():
+        fam = f.split("_")[2]
+        if fam not in ("phase", "combine"):
+            continue
+        refs, intra, _, _, _, units = mc.plain_fixture(f)
+        for i, u, lb in units:
+            base = run(refs, u, intra)
+            if fam == "phase":
+                for l in lb["phases"]:
+                    for field in ("mv1x", "mv1y") if l else ("mv0x", "mv0y"):
+                        for step in (-1, 1):
+                            e = u.copy()
+                            e[field] += step
+                            n["phase"] += 1
+                            if not differs(base, run(refs, e, intra)):
+                                dull.append((f, i, field, step))
+            elif lb["combine"][0] == "bi" and lb["combine"][1] != lb["combine"][2]:
+                e = u.copy()
+                e["w0"], e["w1"] = u["w1"], u["w0"]
+                n["bcw"] += 1
+                if not differs(base, run(refs, e)):
+                    dull.append((f, i, "bcw pair"))
+    for f in golden_cases.mcx_cell_files():
+        if "_far_" not in f:
+            continue
+        refs, _, _, _, _, units = mc.refined_fixture(f)
+        for i, u, lb in units:
+            base = run(refs, u, refined=True)
+            for l, side in sorted(lb["clip"]):
+                field = ("mv1" if l else "mv0") + ("x" if side in "LR" else "y")
+                cx, cy = mc.clip_mv(refs[0].w, refs[0].h, int(u["x"]), int(u["y"]), int(u["w"]), int(u["h"]), int(u["mv1x" if l else "mv0x"]), int(u["mv1y" if l else "mv0y"]))
+                limit = cx if side in "LR" else cy
+                e = u.copy()
+                e[field] = 2 * limit - int(u[field])
+                n["clip"] += 1
+                if not differs(base, run(refs, e, refined=True)):
+                    dull.append((f, i, field, "across the clip limit"))
+    apron_changed, apron_n = set(), 0
+    for f in ["mcx.ovg"] + golden_cases.mcx_cell_files():
+        refs, _, _, _, _, units = mc.refined_fixture(f)
+        for i, u, lb in units:
+            if lb["reads"]["apron"]:
+                a, b = _filled(refs[0].w, refs[0].h, 0), _filled(refs[0].w, refs[0].h, 0)
+                _, mv_a = oracle_lib.dmvr_trace(a, refs, u)
+                _, mv_b = oracle_lib.dmvr_trace(b, refs, u, true_apron=True)
+                assert np.array_equal(mv_a, mv_b)                         # the search reads no apron: the vectors stay
+                apron_n += 1
+                apron_changed |= lb["reads"]["apron"]
+                if all(np.array_equal(p, q) for p, q in zip(a.planes(), b.planes())):
+                    dull.append((f, i, "apron", sorted(lb["reads"]["apron"])))
+    n["apron"] = apron_n
+    assert apron_n > 500 and apron_changed == {(p, sd) for p in ("luma", "chroma") for sd in "LRTB"}
+    print(f"edits: {n}; without effect: {len(dull)}")
+    assert n["phase"] > 5000 and n["bcw"] >= 9 * 4 * 3 and n["clip"] > 150
+    assert not dull, f"{len(dull)} edits leave the prediction as it is, first: {dull[:8]}"
