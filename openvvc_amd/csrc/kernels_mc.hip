@@ -16,7 +16,6 @@
 // rcn_motion_compensation_b_l/_c (libovvc/rcn_mc.c:382-1610; rcn_inter.c:520-602, :1391-1554,
 // :1822-1904) and lmcs_reshape_forward (rcn_lmcs.c:275-295).
 #include "mc_common.hip.h"
-#include <stdlib.h>
 
 // Occupancy hint (waves per SIMD the register allocator must leave room for; 0 = compiler default).
 // -DOV_WPE_MC=n overrides it for sweeps.
@@ -31,29 +30,6 @@
 
 namespace {
 
-// geometric partitioning: w = clip3(0, 8, (K + A*x + B*y) >> 3), put_weighted_gpm_bi_pixels (rcn_mc.c:1630-1655)
-__device__ __forceinline__ int mc_gpm(uint32_t aux, int x, int y, int p0, int p1)
-{
-    const int k = (int16_t)(aux & 0xffff), a = (int8_t)((aux >> 16) & 0xff), b = (int8_t)(aux >> 24);
-    const int wgt = ov_clip3((k + __mul24(a, x) + __mul24(b, y)) >> 3, 0, 8);
-    return ov_clip_bd((__mul24(p1, 8 - wgt) + __mul24(p0, wgt) + 64) >> 7);
-}
-
-// uni (p + 8) >> 4, bi average (p0 + p1 + 16) >> 5, BCW (p1 w1 + p0 w0 + 64) >> 7 (put_vvc_uni/bi(_w)_*): one
-// weighted form whose constants are chosen ONCE per unit -- per-sample three-way branches on wave-uniform unit
-// fields cost scalar issue slots, which is what bounds this kernel
-struct Combine { int a0, a1, rnd, sh; };
-__device__ __forceinline__ Combine mc_combine_of(const ovhip_mc_unit &u)
-{
-    Combine c;
-    if (u.dir != 3)                 { c.a0 = u.dir == 1; c.a1 = u.dir != 1; c.rnd = 8; c.sh = 4; }
-    else if (u.w0 == 4 && u.w1 == 4) { c.a0 = 1; c.a1 = 1; c.rnd = 16; c.sh = 5; }
-    else                            { c.a0 = u.w0; c.a1 = u.w1; c.rnd = 64; c.sh = 7; }
-    return c;
-}
-// (24-bit multiplies: the 14-bit intermediates and the weights fit, and v_mad_i32_i24 is full rate where v_mul_lo_u32 is not)
-__device__ __forceinline__ int mc_combine(const Combine &c, int p0, int p1) { return ov_clip_bd((__mul24(p1, c.a1) + __mul24(p0, c.a0) + c.rnd) >> c.sh); }
-
 // =====================================================================================================
 // k_mc2 (the first version, k_mc, ran one pass per list and per plane with 4 rows per lane: SQ counters showed it
 // bound by VALU issue at ~57 % of the chip with most passes at 10-50 % lane occupancy for 8x8 / 16x8 units; this
@@ -63,9 +39,6 @@ __device__ __forceinline__ int mc_combine(const Combine &c, int p0, int p1) { re
 //     the whole block once; each lane runs both lists for its samples and combines in registers; chroma:
 //     both planes in the same pass
 // =====================================================================================================
-// fused CIIP blend: (intra * wt + inter * (4 - wt) + 2) >> 2, put_weighted_ciip_pixels (rcn_mc.c:1611-1628)
-__device__ __forceinline__ int ciip_blend(int inter, int intra, int wt) { return ov_clip_bd((__mul24(intra, wt) + __mul24(inter, 4 - wt) + 2) >> 2); }
-
 #define HLS 26   /* k_mc2's transposed luma H tile: odd dword stride (conflict-free columns), rows h + 7 <= 23 */
 template <int NOUT>
 __device__ __forceinline__ void luma_finish(const ovhip_mc_unit &u, const ovhip_pic &dst, const int16_t *s_hl, const int tv[2][4],
@@ -105,42 +78,6 @@ __device__ __forceinline__ void luma_finish(const ovhip_mc_unit &u, const ovhip_
     for (int j = 0; j < NOUT; ++j) d[j * dst.stride_y] = (uint16_t)v[j];
 }
 
-template <int NOUT>
-__device__ __forceinline__ void chroma_finish(const ovhip_mc_unit &u, const ovhip_pic &dst, const int16_t *s_hc, const int tv[2][2],
-                                              int lane, int log2wc, int hc, const ovhip_pic &intra)
-{
-    const int wc = 1 << log2wc;
-    const int per_plane = (wc * hc) / NOUT;                   // lanes per plane (power of two, <= 32)
-    const int plane = lane >= per_plane, ll = lane - plane * per_plane;
-    if (lane >= 2 * per_plane) return;
-    const int x = ll & (wc - 1), y0 = (ll >> log2wc) * NOUT;
-    int P[2][NOUT];
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) P[l][o] = 0;
-        if (u.dir & (1 << l)) v_outputs<4, NOUT>(s_hc + (plane * 2 + l) * 8 * CHT_STRIDE + x * CHT_STRIDE, y0, tv[l], P[l]);
-    }
-    uint16_t *d = (plane ? dst.cr : dst.cb) + ov_rowoff((u.y >> 1) + y0, dst.stride_c) + (u.x >> 1) + x;
-    const bool ciip = !(u.flags & OVHIP_MC_GPM) && u.aux && !(u.aux & 0x100);
-    const uint16_t *ip = ciip ? (plane ? intra.cr : intra.cb) + ov_rowoff((u.y >> 1) + y0, intra.stride_c) + (u.x >> 1) + x : nullptr;
-    int v[NOUT];
-    if (u.flags & OVHIP_MC_GPM) {
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j) v[j] = mc_gpm(u.aux, 2 * x, 2 * (y0 + j), P[0][j], P[1][j]);
-    } else {
-        const Combine cmb = mc_combine_of(u);
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j) v[j] = mc_combine(cmb, P[0][j], P[1][j]);
-    }
-    if (ciip) {
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j) v[j] = ciip_blend(v[j], ip[j * intra.stride_c], u.aux & 7);
-    }
-#pragma unroll
-    for (int j = 0; j < NOUT; ++j) d[j * dst.stride_c] = (uint16_t)v[j];
-}
-
 #ifdef OV_MC_PHASES
 // Debug build only (-DOV_MC_PHASES): per-phase shader-clock totals of k_mc2, summed over waves.
 #define OV_MC_PHASE_UNITS 65536
@@ -152,7 +89,7 @@ __device__ unsigned int g_mc_phase[OV_MC_PHASE_UNITS * 8];
 #endif
 
 __global__ __launch_bounds__(64) OV_OCC_MC void k_mc2(ovhip_pic dst, RefTable refs, const ovhip_mc_unit *__restrict__ units,
-                                             uint32_t n_units, const uint16_t *__restrict__ lmcs_fwd, int xcd, ovhip_pic intra)
+                                             uint32_t n_units, const uint16_t *__restrict__ lmcs_fwd, ovhip_pic intra)
 {
     // One LDS block of 5024 B -- under the 5120 B step at which a CU holds 32 of these single-wave workgroups (measured:
     // 5632..6400 B -> 24, 6608 B -> 21):  [ luma windows, list 0 / 1 | chroma windows, later the luma H tiles | chroma H tiles ].
@@ -172,7 +109,7 @@ __global__ __launch_bounds__(64) OV_OCC_MC void k_mc2(ovhip_pic dst, RefTable re
     {
     const uint32_t wg = blockIdx.x;
     if (wg >= n_units) return;
-    const uint32_t bid = xcd ? ov_xcd_slot(wg, n_units) : wg;
+    const uint32_t bid = ov_xcd_slot(wg, n_units);          // XCD-aware unit order: an XCD takes one contiguous chunk of the list
 #ifdef OV_MC_PHASES
     unsigned long long ph[8] = {}, tprev = __builtin_readcyclecounter();
 #endif
@@ -336,19 +273,12 @@ extern "C" int ovhip_mc_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhip
     if (!ctx || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     if (!n_units) return OVHIP_OK;
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_launch: bad reference table / units", hipSuccess);
+    if (!d_units) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_launch: null units", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mc_launch: reference picture geometry differs from dst (RPR)")) return e;
-    static int cfg_xcd = -1;
-#ifdef OVHIP_TUNING
-    if (cfg_xcd < 0) { const char *x = getenv("OVHIP_MC_XCD"); cfg_xcd = x ? atoi(x) : 1; }   // experiment knob: XCD-aware unit order
-#else
-    cfg_xcd = 1;
-#endif
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mc_launch")) return e;
     // one single-wave workgroup per unit (measured faster than a resident grid-stride grid).  Units with a fused CIIP
     // blend read `intra`; without such units the argument is never dereferenced.
-    hipLaunchKernelGGL(k_mc2, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut, cfg_xcd,
+    hipLaunchKernelGGL(k_mc2, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut,
                        intra ? *intra : *dst);
     OV_LAUNCH_CHECK(ctx, "k_mc2");
     return OVHIP_OK;

@@ -17,7 +17,6 @@
 //      18x18 LDS tile, per-sample gradients, 6x6 window sums by 4 lanes per 4x4 block, +-15 weights,
 //      corrected average; otherwise the plain average
 #include "mc_common.hip.h"
-#include <stdlib.h>
 
 // Occupancy hint (waves per SIMD the register allocator must leave room for; 0 = compiler default).
 // -DOV_WPE_MCX=n overrides it for sweeps.
@@ -95,36 +94,19 @@ __device__ __forceinline__ int div_for_maxq7(int num, int den)
     return sign ? -q : q;
 }
 
-template <int NOUT>
-__device__ __forceinline__ void chroma_avg(const ovhip_mc_unit &u, const ovhip_pic &dst, const int16_t *s_hc, const int tv[2][2],
-                                           int lane, int log2wc, int hc)
-{
-    const int wc = 1 << log2wc;
-    const int per_plane = (wc * hc) / NOUT;
-    const int plane = lane >= per_plane, ll = lane - plane * per_plane;
-    if (lane >= 2 * per_plane) return;
-    const int x = ll & (wc - 1), y0 = (ll >> log2wc) * NOUT;
-    int P[2][NOUT];
-#pragma unroll
-    for (int l = 0; l < 2; ++l) v_outputs<4, NOUT>(s_hc + (plane * 2 + l) * 8 * CHT_STRIDE + x * CHT_STRIDE, y0, tv[l], P[l]);
-    uint16_t *d = (plane ? dst.cr : dst.cb) + ov_rowoff((u.y >> 1) + y0, dst.stride_c) + (u.x >> 1) + x;
-#pragma unroll
-    for (int j = 0; j < NOUT; ++j) d[j * dst.stride_c] = (uint16_t)ov_clip_bd((P[0][j] + P[1][j] + 16) >> 5);
-}
-
 // LDS of one refined unit: luma windows [list], chroma windows [Cb/Cr][list], H-pass tiles
 #define MCX_LDS_WL (2 * XWIN_ROWS * XWIN_STRIDE * 2)
 #define MCX_LDS_WC (4 * XCWIN_ROWS * XCWIN_STRIDE * 2)
 #define MCX_LDS    (MCX_LDS_WL + MCX_LDS_WC + (2 * 16 * HT_STRIDE + 4 * 8 * CHT_STRIDE) * 2)
 
-// units wg0, wg0 + wstride, ... (one single-wave workgroup; `lds` = MCX_LDS bytes, 16-byte aligned)
+// unit `wg` of the launch's n_units, in XCD slot order (one single-wave workgroup; `lds` = MCX_LDS bytes, 16-byte aligned)
 // SEARCH_ONLY: the decoder-side MV refinement alone (steps 1-2) for the units that carry OVHIP_MC_DMVR, refined vectors
 // to mv_out, nothing written to dst -- the eager per-CTU-row pass that keeps the host's TMVP motion field final before
 // a row is published (ovhip_job_dmvr_rows).
 template <bool SEARCH_ONLY>
 __device__ __forceinline__ void mcx_units(const ovhip_pic &dst, const RefTable &refs, const ovhip_mc_unit *__restrict__ units,
                                           uint32_t n_units, const uint16_t *__restrict__ lmcs_fwd, int32_t *__restrict__ mv_out,
-                                          uint32_t wg0, uint32_t wstride, char *lds)
+                                          uint32_t wg, char *lds)
 {
     uint16_t (*const s_wl)[XWIN_ROWS * XWIN_STRIDE] = reinterpret_cast<uint16_t (*)[XWIN_ROWS * XWIN_STRIDE]>(lds);
     uint16_t (*const s_wc)[2][XCWIN_ROWS * XCWIN_STRIDE] =
@@ -144,9 +126,8 @@ __device__ __forceinline__ void mcx_units(const ovhip_pic &dst, const RefTable &
 
     const int lane = threadIdx.x;
     {   // one unit per workgroup (a grid-stride loop's carried scalars cost SGPRs; see k_mc2)
-    const uint32_t wg = wg0;
     if (wg >= n_units) return;
-    const uint32_t bid = wstride >= n_units ? ov_xcd_slot(wg, n_units) : wg;        // XCD-aware order, see k_mc2
+    const uint32_t bid = ov_xcd_slot(wg, n_units);                                  // XCD-aware order, see k_mc2
     const ovhip_mc_unit u = units[bid];
     const bool dmvr = u.flags & OVHIP_MC_DMVR;
     if (SEARCH_ONLY && !dmvr) return;
@@ -295,26 +276,19 @@ __device__ __forceinline__ void mcx_units(const ovhip_pic &dst, const RefTable &
     const uint2 hc_tp = *reinterpret_cast<const uint2 *>(g_taps.chroma[hfc]);
     // lanes dealt to the windows in fixed groups (luma 2 x 32, chroma 4 x 16), as in k_mc2: only the row changes in the loops
     if (do_l) {
-        const int log2seg = log2w - 2;
-        const int l = lane >> 5, tl = lane & 31;
+        const int l = lane >> 5;
         const int tp[4] = { (int)hl_tp.x, (int)hl_tp.y, (int)hl_tp.z, (int)hl_tp.w };
         const uint16_t *src = s_wl[0] + l * (XWIN_ROWS * XWIN_STRIDE) + (2 + (l ? ldy[1] : ldy[0])) * XWIN_STRIDE;
         const int off = 4 + (l ? offl[1] + ldx[1] : offl[0] + ldx[0]);
-        const bool ident = hfx == 0;
-        int16_t *ht = s_hl[0] + l * 16 * HT_STRIDE;
-        const int x0 = (tl & ((1 << log2seg) - 1)) << 2, rstep = 32 >> log2seg;
-        for (int r = tl >> log2seg; r < h + 7; r += rstep) h_task<8>(src + r * XWIN_STRIDE, off, x0, tp, ident, ht, HT_STRIDE, r);
+        h_pass<8>(src, XWIN_STRIDE, off, h + 7, log2w - 2, 5, lane & 31, tp, hfx == 0, s_hl[0] + l * 16 * HT_STRIDE, HT_STRIDE);
     }
     if (do_c) {
-        const int log2seg = log2wc > 2 ? log2wc - 2 : 0;
-        const int qi = lane >> 4, tl = lane & 15, l = qi & 1;            // window qi = plane * 2 + list
+        const int qi = lane >> 4, l = qi & 1;                            // window qi = plane * 2 + list
         const int tp[2] = { (int)hc_tp.x, (int)hc_tp.y };
         const uint16_t *src = s_wc[0][0] + qi * (XCWIN_ROWS * XCWIN_STRIDE) + (2 + (l ? cdy[1] : cdy[0])) * XCWIN_STRIDE;
         const int off = 4 + (l ? offc[1] + cdx[1] : offc[0] + cdx[0]);
-        const bool ident = hfc == 0;
-        int16_t *ht = s_hc[0][0] + qi * 8 * CHT_STRIDE;
-        const int x0 = (tl & ((1 << log2seg) - 1)) << 2, rstep = 16 >> log2seg;
-        for (int r = tl >> log2seg; r < hc + 3; r += rstep) h_task<4>(src + r * XCWIN_STRIDE, off, x0, tp, ident, ht, CHT_STRIDE, r);
+        h_pass<4>(src, XCWIN_STRIDE, off, hc + 3, log2wc > 2 ? log2wc - 2 : 0, 4, lane & 15, tp, hfc == 0, s_hc[0][0] + qi * 8 * CHT_STRIDE,
+                  CHT_STRIDE);
     }
     __syncthreads();
 
@@ -427,8 +401,8 @@ __device__ __forceinline__ void mcx_units(const ovhip_pic &dst, const RefTable &
     if (do_c) {
         int tvc[2][2];                                   // vertical chroma taps, loaded where they are used
         load_taps<2>(g_taps.chroma[mv[0][1] & 31], tvc[0]); load_taps<2>(g_taps.chroma[mv[1][1] & 31], tvc[1]);
-        if (wc * hc >= 64) chroma_avg<2>(u, dst, s_hc[0][0], tvc, lane, log2wc, hc);
-        else               chroma_avg<1>(u, dst, s_hc[0][0], tvc, lane, log2wc, hc);
+        if (wc * hc >= 64) chroma_finish<2, true>(u, dst, s_hc[0][0], tvc, lane, log2wc, hc, dst);
+        else               chroma_finish<1, true>(u, dst, s_hc[0][0], tvc, lane, log2wc, hc, dst);
     }
     __syncthreads();          // LDS is reused by the next unit
     }
@@ -448,60 +422,10 @@ __device__ __forceinline__ void mcx_units(const ovhip_pic &dst, const RefTable &
 // =====================================================================================================
 namespace {
 
-#define AWS 12     /* luma window row: <= 3 aligned qwords                     */
+#define AWS AFF_WS /* luma window row: <= 3 aligned qwords                     */
 #define AHS 12     /* transposed H tile: 9 rows per column, 8-byte aligned     */
-#define ACS 12     /* chroma window row: off(<=3) + 7 -> 3 qwords              */
+#define ACS AFF_WS /* chroma window row: off(<=3) + 7 -> 3 qwords              */
 #define ACHS 8     /* chroma transposed H tile: 7 rows per column              */
-
-__device__ __forceinline__ int aff_combine(int dir, int w0, int w1, int p0, int p1)
-{
-    if (dir != 3)           return ov_clip_bd(((dir == 1 ? p0 : p1) + 8) >> 4);
-    if (w0 == 4 && w1 == 4) return ov_clip_bd((p0 + p1 + 16) >> 5);
-    return ov_clip_bd((__mul24(p1, w1) + __mul24(p0, w0) + 64) >> 7);
-}
-
-// window of ROWS x COLS samples -> LDS rows of 12 samples.  4 lanes (c = 0..3) per window.
-template <int ROWS, int COLS>
-__device__ __forceinline__ int aff_stage(const uint16_t *__restrict__ ref, int rstride, int rw, int rh, int sx0, int sy0,
-                                         int c, uint16_t *win)
-{
-    const int ax = sx0 & ~3;
-    int off = sx0 - ax;
-    const int nq = (off + COLS + 3) >> 2;
-    const bool fast = ax >= 0 && ax + 4 * nq <= rw && sy0 >= 0 && sy0 + ROWS <= rh && !(rstride & 3);
-    if (fast) {
-        if (c < nq) {
-            uint2 q[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) q[r] = *reinterpret_cast<const uint2 *>(ref + ov_rowoff(sy0 + r, rstride) + ax + 4 * c);
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) *reinterpret_cast<uint2 *>(win + r * 12 + 4 * c) = q[r];
-        }
-    } else if (!((rstride | rw) & 3)) {
-        // border, aligned geometry: clamped rows, outside groups = replicated edge sample (see WinStage)
-        if (c < nq) {
-            const int qx = ax + 4 * c, side = qx < 0 ? -1 : qx >= rw ? 1 : 0;
-            const uint16_t *base = ref + ov_clip3(qx, 0, rw - 4);
-            uint2 q[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) q[r] = *reinterpret_cast<const uint2 *>(base + ov_rowoff(ov_clip3(sy0 + r, 0, rh - 1), rstride));
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                uint2 v = q[r];
-                if (side) { const uint32_t e = (side < 0 ? v.x & 0xffffu : v.y >> 16) * 0x10001u; v.x = e; v.y = e; }
-                *reinterpret_cast<uint2 *>(win + r * 12 + 4 * c) = v;
-            }
-        }
-    } else {
-        off = 0;
-        for (int i = c; i < COLS; i += 4) {
-            const int sx = ov_clip3(sx0 + i, 0, rw - 1);
-#pragma unroll 1
-            for (int r = 0; r < ROWS; ++r) win[r * 12 + i] = ref[ov_clip3(sy0 + r, 0, rh - 1) * rstride + sx];
-        }
-    }
-    return off;
-}
 
 #ifdef OV_MCA_PHASES
 // Debug build only (-DOV_MCA_PHASES): per-unit shader-clock phase times of k_mca (tools/probe_mc_phases.py).
@@ -513,63 +437,16 @@ __device__ unsigned int g_mca_phase[OV_MCA_PHASE_UNITS * 8];
 #define OV_APHASE(i) do { } while (0)
 #endif
 
-// Luma window of one sub-block and list, split into issue (loads into registers) and park (registers -> LDS) so that
-// list 1's loads are in flight while list 0 is being filtered.  Geometry that is not a multiple of 4 samples is
-// fetched sample by sample with clamped coordinates at park time.
-struct AffLumaStage {
-    uint2 q[9];
-    const uint16_t *ref;
-    int sx0, sy0, off, side;
-    bool fast;
-
-    __device__ __forceinline__ void issue(const uint16_t *__restrict__ r, int rstride, int rw, int rh, int x0, int y0, int c)
-    {
-        ref = r; sx0 = x0; sy0 = y0;
-        const int ax = sx0 & ~3;
-        off = sx0 - ax;
-        const int nq = (off + 9 + 3) >> 2;
-        fast = !((rstride | rw) & 3);
-        if (fast && c < nq) {
-            // rows clamp per lane; an aligned group outside the picture = the edge sample replicated (see WinStage)
-            const int qx = ax + 4 * c;
-            side = qx < 0 ? -1 : qx >= rw ? 1 : 0;
-            const uint16_t *base = ref + ov_clip3(qx, 0, rw - 4);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) q[k] = *reinterpret_cast<const uint2 *>(base + ov_rowoff(ov_clip3(sy0 + k, 0, rh - 1), rstride));
-        }
-    }
-    __device__ __forceinline__ int park(int rstride, int rw, int rh, int c, uint16_t *win)
-    {
-        if (fast) {
-            if (c < ((off + 9 + 3) >> 2)) {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    uint2 v = q[k];
-                    if (side) { const uint32_t e = (side < 0 ? v.x & 0xffffu : v.y >> 16) * 0x10001u; v.x = e; v.y = e; }
-                    *reinterpret_cast<uint2 *>(win + k * AWS + 4 * c) = v;
-                }
-            }
-            return off;
-        }
-        for (int i = c; i < 9; i += 4) {
-            const int sx = ov_clip3(sx0 + i, 0, rw - 1);
-#pragma unroll 1
-            for (int k = 0; k < 9; ++k) win[k * AWS + i] = ref[ov_clip3(sy0 + k, 0, rh - 1) * rstride + sx];
-        }
-        return 0;
-    }
-};
-
 #define MCA_LDS_WIN  (16 * 9 * AWS * 2)
 #define MCA_LDS_HT   (16 * 4 * AHS * 2)
 #define MCA_LDS_T    (16 * 40 * 2)
 #define MCA_LDS_CWIN (2 * 8 * 7 * ACS * 2)
 #define MCA_LDS      (MCA_LDS_WIN + MCA_LDS_HT + MCA_LDS_T + MCA_LDS_CWIN + 2 * 8 * 4 * ACHS * 2)
 
-// units wg0, wg0 + wstride, ... (one single-wave workgroup; `lds` = MCA_LDS bytes, 16-byte aligned)
+// unit `wg` of the launch's n_units, in XCD slot order (one single-wave workgroup; `lds` = MCA_LDS bytes, 16-byte aligned)
 __device__ __forceinline__ void mca_units(const ovhip_pic &dst, const RefTable &refs, const ovhip_aff_unit *__restrict__ units,
                                           uint32_t n_units, const int32_t *__restrict__ side, const uint16_t *__restrict__ lmcs_fwd,
-                                          uint32_t wg0, uint32_t wstride, char *lds)
+                                          uint32_t wg, char *lds)
 {
     // Luma tiles hold ONE list at a time (list 1 is filtered after list 0, its window waiting in registers): with both
     // lists resident the 16 KB workgroup allowed 10 per CU and a 4K picture's affine units needed two rounds.
@@ -581,9 +458,8 @@ __device__ __forceinline__ void mca_units(const ovhip_pic &dst, const RefTable &
 
     const int lane = threadIdx.x;
     {   // one unit per workgroup
-    const uint32_t wg = wg0;
     if (wg >= n_units) return;
-    const uint32_t bid = wstride >= n_units ? ov_xcd_slot(wg, n_units) : wg;        // XCD-aware order, see k_mc2
+    const uint32_t bid = ov_xcd_slot(wg, n_units);                                  // XCD-aware order, see k_mc2
 #ifdef OV_MCA_PHASES
     unsigned int ph[8] = {}; unsigned long long tprev = __builtin_readcyclecounter();
 #endif
@@ -609,8 +485,9 @@ __device__ __forceinline__ void mca_units(const ovhip_pic &dst, const RefTable &
 
     OV_APHASE(1);
 
-    // ---- 1. windows: the first luma list into registers, chroma straight to LDS; PROF offsets prefetched ----
-    AffLumaStage st;
+    // ---- 1. windows: the first luma list into registers (list 1's loads are in flight while list 0 is being filtered),
+    //         chroma straight to LDS; PROF offsets prefetched ----
+    AffStage<9> st;
     const int rsy = dst.stride_y, rpw = dst.w, rph = dst.h;               // reference geometry = dst's (checked at launch)
     const int lfirst = (u.dir & 1) ? 0 : 1;
     if (act) {
@@ -620,8 +497,9 @@ __device__ __forceinline__ void mca_units(const ovhip_pic &dst, const RefTable &
     if (cact) {
         const ovhip_pic &rp = refs.p[cl ? u.ref1 : u.ref0];
         const int mvx = cl ? cm.z : cm.x, mvy = cl ? cm.w : cm.y;
-        coff = aff_stage<7, 7>(ccomp ? rp.cr : rp.cb, rp.stride_c, rp.w >> 1, rp.h >> 1, cbx + (mvx >> 5) - 1, cby + (mvy >> 5) - 1, cc,
-                               s_cwin[cl][cwi]);
+        AffStage<7> cst;
+        cst.issue(ccomp ? rp.cr : rp.cb, rp.stride_c, rp.w >> 1, rp.h >> 1, cbx + (mvx >> 5) - 1, cby + (mvy >> 5) - 1, cc);
+        coff = cst.park(rp.stride_c, rp.w >> 1, rp.h >> 1, cc, s_cwin[cl][cwi]);
     }
     bool prof[2];
     int pdx[2][4], pdy[2][4];
@@ -684,41 +562,20 @@ __device__ __forceinline__ void mca_units(const ovhip_pic &dst, const RefTable &
             for (int o = 0; o < 4; ++o) P[l][o] >>= 6;
         }
         if (prof[l]) {
-            // 6x6 tile: interior = prediction column, ring = integer reference samples << 4 (5 ring samples per lane)
-            int16_t *t = s_t[sb];
             const int ex = (mvx & 15) >> 3, ey = (mvy & 15) >> 3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) t[(j + 1) * 6 + c + 1] = (int16_t)P[l][j];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const int e = 5 * c + k;
-                int i, j;
-                if (e < 6)       { i = e; j = 0; }
-                else if (e < 12) { i = e - 6; j = 5; }
-                else if (e < 16) { i = 0; j = e - 11; }
-                else             { i = 5; j = e - 15; }
-                t[j * 6 + i] = (int16_t)(s_win[sb][(j + 1 + ey) * AWS + off + i + 1 + ex] << 4);
-            }
+            const uint16_t *wp = s_win[sb] + (1 + ey) * AWS + off + 1 + ex;
+            prof_fill(s_t[sb], c, P[l], [wp](int i, int j) { return (int)wp[j * AWS + i]; });
         }
         __syncthreads();
-        if (prof[l]) {
-            const int16_t *t = s_t[sb];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int o = (j + 1) * 6 + c + 1;
-                const int gx = (t[o + 1] >> 6) - (t[o - 1] >> 6), gy = (t[o + 6] >> 6) - (t[o - 6] >> 6);
-                const int add = ov_clip3(__mul24(pdx[l][j], gx) + __mul24(pdy[l][j], gy), -(1 << 13), (1 << 13) - 1);
-                P[l][j] = (int)(int16_t)(P[l][j] + add);
-            }
-        }
+        if (prof[l]) prof_refine(s_t[sb], c, pdx[l], pdy[l], P[l]);
     }
     OV_APHASE(4);
     if (act) {
-        const int dir = ((u.ident_l >> sb) & 1) ? 2 : u.dir;
+        const Combine cmb = mc_combine_of(BiMode{ ((u.ident_l >> sb) & 1) ? 2 : u.dir, u.w0, u.w1 });
         uint16_t *d = dst.y + ov_rowoff(by, dst.stride_y) + bx + c;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            int v = aff_combine(dir, u.w0, u.w1, P[0][j], P[1][j]);
+            int v = mc_combine(cmb, P[0][j], P[1][j]);
             if ((u.flags & OVHIP_AFF_LMCS) && lmcs_fwd) v = lmcs_fwd[v];
             d[j * dst.stride_y] = (uint16_t)v;
         }
@@ -740,10 +597,10 @@ __device__ __forceinline__ void mca_units(const ovhip_pic &dst, const RefTable &
 #pragma unroll
             for (int o = 0; o < 4; ++o) Pc[l][o] >>= 6;
         }
-        const int dir = ((u.ident_c >> cblk) & 1) ? 2 : u.dir;
+        const Combine cmb = mc_combine_of(BiMode{ ((u.ident_c >> cblk) & 1) ? 2 : u.dir, u.w0, u.w1 });
         uint16_t *d = (ccomp ? dst.cr : dst.cb) + ov_rowoff(cby, dst.stride_c) + cbx + cc;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) d[j * dst.stride_c] = (uint16_t)aff_combine(dir, u.w0, u.w1, Pc[0][j], Pc[1][j]);
+        for (int j = 0; j < 4; ++j) d[j * dst.stride_c] = (uint16_t)mc_combine(cmb, Pc[0][j], Pc[1][j]);
     }
     __syncthreads();
 #ifdef OV_MCA_PHASES
@@ -761,21 +618,21 @@ __global__ __launch_bounds__(64) OV_OCC_MCX void k_mcx(ovhip_pic dst, RefTable r
                                              uint32_t n_units, const uint16_t *__restrict__ lmcs_fwd, int32_t *__restrict__ mv_out)
 {
     __shared__ __attribute__((aligned(16))) char lds[MCX_LDS];
-    mcx_units<false>(dst, refs, units, n_units, lmcs_fwd, mv_out, blockIdx.x, gridDim.x, lds);
+    mcx_units<false>(dst, refs, units, n_units, lmcs_fwd, mv_out, blockIdx.x, lds);
 }
 
 __global__ __launch_bounds__(64) OV_OCC_MCX void k_dmvr_search(ovhip_pic geom, RefTable refs, const ovhip_mc_unit *__restrict__ units,
                                                      uint32_t n_units, int32_t *__restrict__ mv_out)
 {
     __shared__ __attribute__((aligned(16))) char lds[MCX_LDS];
-    mcx_units<true>(geom, refs, units, n_units, nullptr, mv_out, blockIdx.x, gridDim.x, lds);
+    mcx_units<true>(geom, refs, units, n_units, nullptr, mv_out, blockIdx.x, lds);
 }
 
 __global__ __launch_bounds__(64) OV_OCC_MCX void k_mca(ovhip_pic dst, RefTable refs, const ovhip_aff_unit *__restrict__ units,
                                              uint32_t n_units, const int32_t *__restrict__ side, const uint16_t *__restrict__ lmcs_fwd)
 {
     __shared__ __attribute__((aligned(16))) char lds[MCA_LDS];
-    mca_units(dst, refs, units, n_units, side, lmcs_fwd, blockIdx.x, gridDim.x, lds);
+    mca_units(dst, refs, units, n_units, side, lmcs_fwd, blockIdx.x, lds);
 }
 
 // Both kinds of unit in ONE launch: workgroups [0, n_a) take the affine units (few, long, latency-bound -- first, so that
@@ -785,8 +642,8 @@ __global__ __launch_bounds__(64) OV_OCC_MCX void k_mcxa(ovhip_pic dst, RefTable 
                                               const int32_t *__restrict__ side, const uint16_t *__restrict__ lmcs_fwd)
 {
     __shared__ __attribute__((aligned(16))) char lds[MCX_LDS > MCA_LDS ? MCX_LDS : MCA_LDS];
-    if (blockIdx.x < n_a) mca_units(dst, refs, aunits, n_a, side, lmcs_fwd, blockIdx.x, n_a, lds);
-    else                  mcx_units<false>(dst, refs, xunits, n_x, lmcs_fwd, mv_out, blockIdx.x - n_a, n_x, lds);
+    if (blockIdx.x < n_a) mca_units(dst, refs, aunits, n_a, side, lmcs_fwd, blockIdx.x, lds);
+    else                  mcx_units<false>(dst, refs, xunits, n_x, lmcs_fwd, mv_out, blockIdx.x - n_a, lds);
 }
 
 } // namespace
@@ -805,10 +662,9 @@ extern "C" int ovhip_mcx_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhi
     if (!ctx || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     if (!n_units) return OVHIP_OK;
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mcx_launch: bad reference table / units", hipSuccess);
+    if (!d_units) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mcx_launch: null units", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mcx_launch: reference picture geometry differs from dst (RPR)")) return e;
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mcx_launch")) return e;
     hipLaunchKernelGGL(k_mcx, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut, d_mv_out);
     OV_LAUNCH_CHECK(ctx, "k_mcx");
     return OVHIP_OK;
@@ -820,10 +676,9 @@ extern "C" int ovhip_dmvr_search_launch(ovhip_ctx *ctx, const ovhip_pic *geom, c
     if (!ctx || !geom) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     if (!n_units) return OVHIP_OK;
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_mv_out)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_dmvr_search_launch: bad reference table / units", hipSuccess);
+    if (!d_units || !d_mv_out) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_dmvr_search_launch: null units / vectors", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, geom, "ovhip_dmvr_search_launch: reference picture geometry differs (RPR)")) return e;
+    if (int e = ref_table(ctx, &t, refs, n_refs, geom, "ovhip_dmvr_search_launch")) return e;
     hipLaunchKernelGGL(k_dmvr_search, dim3(n_units), dim3(64), 0, ctx->stream, *geom, t, d_units, n_units, d_mv_out);
     OV_LAUNCH_CHECK(ctx, "k_dmvr_search");
     return OVHIP_OK;
@@ -836,10 +691,9 @@ extern "C" int ovhip_mca_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovhi
     if (!ctx || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     if (!n_units) return OVHIP_OK;
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_side)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_launch: bad reference table / units / side arena", hipSuccess);
+    if (!d_units || !d_side) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_launch: null units / side arena", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mca_launch: reference picture geometry differs from dst (RPR)")) return e;
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mca_launch")) return e;
     hipLaunchKernelGGL(k_mca, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_side, d_lmcs_fwd_lut);
     OV_LAUNCH_CHECK(ctx, "k_mca");
     return OVHIP_OK;
@@ -854,10 +708,9 @@ extern "C" int ovhip_mcxa_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const ovh
     OV_DEVICE(ctx);
     if (!n_aunits) return ovhip_mcx_launch(ctx, dst, refs, n_refs, d_xunits, n_xunits, d_lmcs_fwd_lut, d_mv_out);
     if (!n_xunits) return ovhip_mca_launch(ctx, dst, refs, n_refs, d_aunits, n_aunits, d_side, d_lmcs_fwd_lut);
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_xunits || !d_aunits || !d_side)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mcxa_launch: bad reference table / units / side arena", hipSuccess);
+    if (!d_xunits || !d_aunits || !d_side) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mcxa_launch: null units / side arena", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mcxa_launch: reference picture geometry differs from dst (RPR)")) return e;
+    if (int e = ref_table(ctx, &t, refs, n_refs, dst, "ovhip_mcxa_launch")) return e;
     hipLaunchKernelGGL(k_mcxa, dim3(n_aunits + n_xunits), dim3(64), 0, ctx->stream, *dst, t, d_xunits, n_xunits, d_mv_out,
                        d_aunits, n_aunits, d_side, d_lmcs_fwd_lut);
     OV_LAUNCH_CHECK(ctx, "k_mcxa");

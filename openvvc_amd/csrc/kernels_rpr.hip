@@ -109,11 +109,29 @@ __device__ __forceinline__ void rpr_plane(const uint16_t *__restrict__ ref, int 
     __syncthreads();
 }
 
-__device__ __forceinline__ int rpr_gpm(uint32_t aux, int x, int y, int p0, int p1)
+// Combine, LMCS forward mapping, CIIP blend and store of one plane of a unit: P = rpr_plane's outputs per list (a uni-predicted
+// unit's are finished samples already, the put_vvc_pel_rpr_clip quirk included), (x0, y0) / w x h the unit in the plane, pw x ph
+// the plane; cs: the plane's subsampling shift, for the GPM weights' luma coordinates; lmcs / ip: nullptr = no mapping / no blend.
+__device__ __forceinline__ void rpr_finish(const ovhip_rpr_unit &u, const int P[2][4], int x0, int y0, int w, int h, int pw, int ph, int cs,
+                                           uint16_t *d, int dstride, const uint16_t *__restrict__ lmcs, const uint16_t *ip, int istride,
+                                           int lane)
 {
-    const int k = (int16_t)(aux & 0xffff), a = (int8_t)((aux >> 16) & 0xff), b = (int8_t)(aux >> 24);
-    const int wgt = ov_clip3((k + a * x + b * y) >> 3, 0, 8);
-    return ov_clip_bd((p1 * (8 - wgt) + p0 * wgt + 64) >> 7);
+    const int dir = u.dir & 3;
+    const Combine cmb = mc_combine_of(BiMode{ dir, u.w0, u.w1 });
+    int j = 0;
+    for (int t = lane; t < w * h; t += 64, ++j) {
+        const int r = t / w, c = t - r * w;
+        const int p0 = P[0][j & 3], p1 = P[1][j & 3];
+        int v;
+        if (dir != 3)                       v = dir == 1 ? p0 : p1;
+        else if (u.flags & OVHIP_RPR_GPM)   v = mc_gpm(u.aux, c << cs, r << cs, p0, p1);
+        else                                v = mc_combine(cmb, p0, p1);
+        if (lmcs) v = lmcs[v];
+        const int px = x0 + c, py = y0 + r;
+        if (px >= pw || py >= ph) continue;
+        if (ip) v = ciip_blend(v, ip[(size_t)py * istride + px], u.aux & 7);
+        d[(size_t)py * dstride + px] = (uint16_t)v;
+    }
 }
 
 __global__ __launch_bounds__(64) void k_mc_rpr(ovhip_pic dst, RefTable refs, const ovhip_rpr_unit *__restrict__ units, uint32_t n_units,
@@ -140,21 +158,8 @@ __global__ __launch_bounds__(64) void k_mc_rpr(ovhip_pic dst, RefTable refs, con
             rpr_plane<8, RPR_LROWS>(rp.y, rp.stride_y, rp.w, rp.h, ax, ay, min(s.filt & 15, 5), min(s.filt >> 4, 5), hpel && !sc, uni, w, h,
                                     u.ox, u.oy, s_tile, lane, P[l]);
         }
-        int j = 0;
-        for (int t = lane; t < w * h; t += 64, ++j) {
-            const int r = t / w, c = t - r * w;
-            const int p0 = P[0][j & 3], p1 = P[1][j & 3];
-            int v;
-            if (uni)                          v = dir == 1 ? p0 : p1;
-            else if (gpm)                     v = rpr_gpm(u.aux, c, r, p0, p1);
-            else if (u.w0 == 4 && u.w1 == 4)  v = ov_clip_bd((p0 + p1 + 16) >> 5);
-            else                              v = ov_clip_bd((p0 * u.w0 + p1 * u.w1 + 64) >> 7);
-            if ((u.flags & OVHIP_RPR_LMCS) && lmcs_fwd) v = lmcs_fwd[v];
-            const int px = u.x + c, py = u.y + r;
-            if (px >= dst.w || py >= dst.h) continue;
-            if (!gpm && u.aux) v = ov_clip_bd((intra.y[(size_t)py * intra.stride_y + px] * (int)(u.aux & 7) + v * (4 - (int)(u.aux & 7)) + 2) >> 2);
-            dst.y[(size_t)py * dst.stride_y + px] = (uint16_t)v;
-        }
+        rpr_finish(u, P, u.x, u.y, w, h, dst.w, dst.h, 0, dst.y, dst.stride_y, (u.flags & OVHIP_RPR_LMCS) ? lmcs_fwd : nullptr,
+                   !gpm && u.aux ? intra.y : nullptr, intra.stride_y, lane);
     }
     if (!(u.flags & OVHIP_RPR_NO_CHROMA)) {
         const int wc = w >> 1, hc = h >> 1;
@@ -170,23 +175,9 @@ __global__ __launch_bounds__(64) void k_mc_rpr(ovhip_pic dst, RefTable refs, con
                 rpr_plane<4, RPR_CROWS>(plane == 1 ? rp.cb : rp.cr, rp.stride_c, rp.w >> 1, rp.h >> 1, ax, ay, min(s.filt_c & 15, 2),
                                         min(s.filt_c >> 4, 2), false, uni, wc, hc, u.ox >> 1, u.oy >> 1, s_tile, lane, P[l]);
             }
-            uint16_t *d = plane == 1 ? dst.cb : dst.cr;
             const uint16_t *ip = plane == 1 ? intra.cb : intra.cr;
-            const bool ciip = !gpm && u.aux && !(u.aux & 0x100);
-            int j = 0;
-            for (int t = lane; t < wc * hc; t += 64, ++j) {
-                const int r = t / wc, c = t - r * wc;
-                const int p0 = P[0][j & 3], p1 = P[1][j & 3];
-                int v;
-                if (uni)                          v = dir == 1 ? p0 : p1;
-                else if (gpm)                     v = rpr_gpm(u.aux, 2 * c, 2 * r, p0, p1);
-                else if (u.w0 == 4 && u.w1 == 4)  v = ov_clip_bd((p0 + p1 + 16) >> 5);
-                else                              v = ov_clip_bd((p0 * u.w0 + p1 * u.w1 + 64) >> 7);
-                const int px = (u.x >> 1) + c, py = (u.y >> 1) + r;
-                if (px >= (dst.w >> 1) || py >= (dst.h >> 1)) continue;
-                if (ciip) v = ov_clip_bd((ip[(size_t)py * intra.stride_c + px] * (int)(u.aux & 7) + v * (4 - (int)(u.aux & 7)) + 2) >> 2);
-                d[(size_t)py * dst.stride_c + px] = (uint16_t)v;
-            }
+            rpr_finish(u, P, u.x >> 1, u.y >> 1, wc, hc, dst.w >> 1, dst.h >> 1, 1, plane == 1 ? dst.cb : dst.cr, dst.stride_c, nullptr,
+                       !gpm && u.aux && !(u.aux & 0x100) ? ip : nullptr, intra.stride_c, lane);
         }
     }
 }
@@ -255,13 +246,6 @@ __device__ __forceinline__ void mcar_block(const uint16_t *__restrict__ ref, int
     }
 }
 
-__device__ __forceinline__ int mcar_combine(int dir, int w0, int w1, int p0, int p1)
-{
-    if (dir != 3)           return ov_clip_bd(((dir == 1 ? p0 : p1) + 8) >> 4);
-    if (w0 == 4 && w1 == 4) return ov_clip_bd((p0 + p1 + 16) >> 5);
-    return ov_clip_bd((p0 * w0 + p1 * w1 + 64) >> 7);
-}
-
 __global__ __launch_bounds__(64) void k_mca_rpr(ovhip_pic dst, RefTable refs, const ovhip_aff_rpr_unit *__restrict__ units, uint32_t n_units,
                                                 const int32_t *__restrict__ side, const uint16_t *__restrict__ lmcs_fwd)
 {
@@ -299,42 +283,28 @@ __global__ __launch_bounds__(64) void k_mca_rpr(ovhip_pic dst, RefTable refs, co
                 mcar_block<8>(rp.y, rp.stride_y, rp.w, rp.h, ax, ay, min(s.filt & 15, 5), min(s.filt >> 4, 5), c, s_tile[sb], P[l], q);
             }
             if (prof) {
-                // 6x6 tile: interior = the lane's prediction column, ring = integer reference samples << 4 (5 ring samples per lane)
                 if (on) {
-                    int16_t *t = s_t[sb];
                     const int rx = bx + (a >> 4) - 1 + ((a & 15) >> 3), ry = by + (b >> 4) - 1 + ((b & 15) >> 3);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[(j + 1) * 6 + c + 1] = (int16_t)P[l][j];
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) {
-                        const int e = 5 * c + k;
-                        int i, j;
-                        if (e < 6)       { i = e; j = 0; }
-                        else if (e < 12) { i = e - 6; j = 5; }
-                        else if (e < 16) { i = 0; j = e - 11; }
-                        else             { i = 5; j = e - 15; }
-                        t[j * 6 + i] = (int16_t)(rp.y[(size_t)clampi(ry + j, 0, rp.h - 1) * rp.stride_y + clampi(rx + i, 0, rp.w - 1)] << 4);
-                    }
+                    prof_fill(s_t[sb], c, P[l], [&](int i, int j) {
+                        return (int)rp.y[(size_t)clampi(ry + j, 0, rp.h - 1) * rp.stride_y + clampi(rx + i, 0, rp.w - 1)];
+                    });
                 }
                 __syncthreads();
                 if (on) {
-                    const int16_t *t = s_t[sb];
                     const int16_t *pt = reinterpret_cast<const int16_t *>(side + u.prof_off) + 32 * l;
+                    int pdx[4], pdy[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int o = (j + 1) * 6 + c + 1;
-                        const int gx = (t[o + 1] >> 6) - (t[o - 1] >> 6), gy = (t[o + 6] >> 6) - (t[o - 6] >> 6);
-                        const int add = ov_clip3((int)pt[4 * j + c] * gx + (int)pt[16 + 4 * j + c] * gy, -(1 << 13), (1 << 13) - 1);
-                        P[l][j] = (int)(int16_t)(P[l][j] + add);
-                    }
+                    for (int j = 0; j < 4; ++j) { pdx[j] = pt[4 * j + c]; pdy[j] = pt[16 + 4 * j + c]; }
+                    prof_refine(s_t[sb], c, pdx, pdy, P[l]);
                 }
                 __syncthreads();
             }
         }
         if (act) {
+            const Combine cmb = mc_combine_of(BiMode{ dir, u.w0, u.w1 });
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                int v = mcar_combine(dir, u.w0, u.w1, P[0][j], P[1][j]);
+                int v = mc_combine(cmb, P[0][j], P[1][j]);
                 if ((u.flags & OVHIP_AFFR_LMCS) && lmcs_fwd) v = lmcs_fwd[v];
                 const int px = bx + c, py = by + j;
                 if (px < dst.w && py < dst.h) dst.y[(size_t)py * dst.stride_y + px] = (uint16_t)v;
@@ -361,9 +331,10 @@ __global__ __launch_bounds__(64) void k_mca_rpr(ovhip_pic dst, RefTable refs, co
                               s_tile[comp * 4 + blk], P[l], Q[l]);
             }
             uint16_t *d = comp ? dst.cr : dst.cb;
+            const Combine cmb = mc_combine_of(BiMode{ dir, u.w0, u.w1 });
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                int v = mcar_combine(dir, u.w0, u.w1, P[0][j], P[1][j]);
+                int v = mc_combine(cmb, P[0][j], P[1][j]);
                 // put_vvc_pel_rpr_clip reads the horizontal intermediate as uint16: a negative one clips to the maximum
                 const int qv = dir == 1 ? Q[0][j] : Q[1][j];
                 if (dir != 3 && qv >= 0) v = ov_clip_bd((qv + 8) >> 4);
@@ -383,10 +354,9 @@ extern "C" int ovhip_mca_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const 
     if (!ctx || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     if (!n_units) return OVHIP_OK;
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units || !d_side)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_rpr_launch: bad reference table / units / side arena", hipSuccess);
+    if (!d_units || !d_side) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mca_rpr_launch: null units / side arena", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, nullptr, "ovhip_mca_rpr_launch: bad reference picture")) return e;
+    if (int e = ref_table(ctx, &t, refs, n_refs, nullptr, "ovhip_mca_rpr_launch")) return e;
     hipLaunchKernelGGL(k_mca_rpr, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_side, d_lmcs_fwd_lut);
     OV_LAUNCH_CHECK(ctx, "k_mca_rpr");
     return OVHIP_OK;
@@ -399,10 +369,9 @@ extern "C" int ovhip_mc_rpr_launch(ovhip_ctx *ctx, const ovhip_pic *dst, const o
     if (!ctx || !dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
     if (!n_units) return OVHIP_OK;
-    if (!refs || !n_refs || n_refs > MC_MAX_REFS || !d_units)
-        return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_rpr_launch: bad reference table / units", hipSuccess);
+    if (!d_units) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_mc_rpr_launch: null units", hipSuccess);
     RefTable t;
-    if (int e = ref_table(ctx, &t, refs, n_refs, nullptr, "ovhip_mc_rpr_launch: bad reference picture")) return e;
+    if (int e = ref_table(ctx, &t, refs, n_refs, nullptr, "ovhip_mc_rpr_launch")) return e;
     hipLaunchKernelGGL(k_mc_rpr, dim3(n_units), dim3(64), 0, ctx->stream, *dst, t, d_units, n_units, d_lmcs_fwd_lut,
                        intra ? *intra : *dst);
     OV_LAUNCH_CHECK(ctx, "k_mc_rpr");

@@ -1,6 +1,13 @@
-// mc_common.hip.h -- device building blocks shared by the plain (kernels_mc.hip) and the refined
-// BDOF / DMVR (kernels_mcx.hip) motion-compensation kernels: reference-window staging, packed
-// v_dot2 FIR, separable H (LDS->LDS, transposed) and V (LDS->registers) passes.
+// mc_common.hip.h -- device building blocks shared by the inter-prediction kernels: plain units (kernels_mc.hip), refined BDOF /
+// DMVR and affine units (kernels_mcx.hip), units that read a reference of another size (kernels_rpr.hip).  Every decision that more
+// than one of them takes is written here once:
+//   ref_table                        the launchers' reference table and its argument checks
+//   WinStage, stage_unit_windows     reference windows of a <= 16x16 unit -> LDS (k_mc2, k_mcx)
+//   AffStage                         reference window of one 4x4 affine block -> LDS (k_mca: luma 9x9, chroma 7x7)
+//   fir4 / firn, h_task, h_pass, v_pass, v_outputs    packed v_dot2 FIR; separable H (LDS->LDS, transposed) and V (LDS->registers) passes
+//   Combine, mc_gpm, ciip_blend      uni / average / BCW, geometric-partition and CIIP blends of the lists' 14-bit intermediates
+//   chroma_finish                    chroma V pass + combine + store of a unit (k_mc2, k_mcx)
+//   prof_ring, prof_fill, prof_refine    PROF on a 6x6 tile (k_mca, k_mca_rpr)
 #pragma once
 #include "ovvc_common.hip.h"
 #define OVT_ATTR __device__
@@ -11,18 +18,25 @@ namespace {
 #define MC_MAX_REFS 16
 struct RefTable { ovhip_pic p[MC_MAX_REFS]; };
 
-// Host: the reference table of a launch from the caller's (refs, n_refs), 1 <= n_refs <= MC_MAX_REFS (the launcher has checked
-// that); unused entries repeat refs[0].  geom: the picture whose window geometry the kernel applies to every reference -- one of
-// another size is RPR, outside such a kernel (OVHIP_EUNSUP); nullptr: every reference is read with its own geometry, and only a
-// plane that is not there is refused (OVHIP_EINVAL).  `what`: the message of that failure, led by the entry point's name.
-static inline int ref_table(ovhip_ctx *ctx, RefTable *t, const ovhip_pic *refs, uint32_t n_refs, const ovhip_pic *geom, const char *what)
+// Host: the reference table of a launch from the caller's (refs, n_refs), 1 <= n_refs <= MC_MAX_REFS (anything else, or no table,
+// is refused: OVHIP_EINVAL); unused entries repeat refs[0].  geom: the picture whose window geometry the kernel applies to every
+// reference -- one of another size is RPR, outside such a kernel (OVHIP_EUNSUP); nullptr: every reference is read with its own
+// geometry, and only a plane that is not there is refused (OVHIP_EINVAL).  `who`: the entry point's name, which leads the messages.
+static inline int ref_table(ovhip_ctx *ctx, RefTable *t, const ovhip_pic *refs, uint32_t n_refs, const ovhip_pic *geom, const char *who)
 {
+    char what[96];
+    if (!refs || !n_refs || n_refs > MC_MAX_REFS) {
+        snprintf(what, sizeof(what), "%s: bad reference table", who);
+        return ov_fail(ctx, OVHIP_EINVAL, what, hipSuccess);
+    }
     memset(t, 0, sizeof(*t));
     for (uint32_t i = 0; i < n_refs; ++i) {
         const ovhip_pic &p = refs[i];
         if (geom ? p.w != geom->w || p.h != geom->h || p.stride_y != geom->stride_y || p.stride_c != geom->stride_c
-                 : !p.y || !p.cb || !p.cr || p.w < 8 || p.h < 8 || p.stride_y < p.w || p.stride_c < (p.w >> 1))
+                 : !p.y || !p.cb || !p.cr || p.w < 8 || p.h < 8 || p.stride_y < p.w || p.stride_c < (p.w >> 1)) {
+            snprintf(what, sizeof(what), geom ? "%s: reference picture geometry differs (RPR)" : "%s: bad reference picture", who);
             return ov_fail(ctx, geom ? OVHIP_EUNSUP : OVHIP_EINVAL, what, hipSuccess);
+        }
         t->p[i] = p;
     }
     for (uint32_t i = n_refs; i < MC_MAX_REFS; ++i) t->p[i] = refs[0];
@@ -89,7 +103,7 @@ struct WinStage {
         }
     }
     __device__ __forceinline__ void issue_slow(const uint16_t *__restrict__ ref, int rstride, int rw, int rh, int sx0, int sy0,
-                                               int ww, int wh, int lane, uint16_t *s_win, int wstride)
+                                               int ww, int wh, int lane, uint16_t *s_win, int winstride)
     {
         off = 0; fast = false; side = 0;
         const int c = lane & (COLS - 1), r0 = lane / COLS;
@@ -97,11 +111,11 @@ struct WinStage {
 #pragma unroll 1
         for (int k = 0; k < NITS; ++k) {
             const int r = (64 / COLS) * k + r0;
-            if (c < ww && r < wh) s_win[r * wstride + c] = ref[ov_clip3(sy0 + r, 0, rh - 1) * rstride + sx];
+            if (c < ww && r < wh) s_win[r * winstride + c] = ref[ov_clip3(sy0 + r, 0, rh - 1) * rstride + sx];
         }
     }
     template <bool FIX = true>
-    __device__ __forceinline__ void park(uint16_t *s_win, int wstride, int ww, int wh, int lane) const
+    __device__ __forceinline__ void park(uint16_t *s_win, int winstride, int ww, int wh, int lane) const
     {
         if (fast) {
             const int nq = (off + ww + 3) >> 2;
@@ -112,7 +126,7 @@ struct WinStage {
                 if (c < nq && r < wh) {
                     uint2 v = q[k];
                     if (FIX && side) { const uint32_t e = (side < 0 ? v.x & 0xffffu : v.y >> 16) * 0x10001u; v.x = e; v.y = e; }
-                    *reinterpret_cast<uint2 *>(s_win + r * wstride + 4 * c) = v;
+                    *reinterpret_cast<uint2 *>(s_win + r * winstride + 4 * c) = v;
                 }
             }
         }
@@ -359,5 +373,176 @@ __device__ __forceinline__ void v_outputs(const int16_t *col, int s0, const int 
     for (int o = 0; o < NOUT; ++o) P[o] >>= 6;
 }
 
+// The horizontal pass of ONE window by the 2^l2per lanes dealt to it (tl = the lane's index among them): one task = one window
+// row x 4 outputs, so that everything a task needs except its row -- taps, alignment, tile -- is fixed per lane and leaves the
+// loop.  win / winstride / off: the window, its row stride and sub-group offset; rows: its height; log2seg: log2 of the plane
+// width in 4-sample segments, the caller's to clamp at 0 (k_mcx's luma is >= 8 wide and passes log2w - 2 as it is).
+// (k_mc2 spells the same two loops out: through this function the compiler orders the set-up in front of its loops differently --
+// same instructions, other schedule and registers -- and that kernel's instruction text is kept fixed.)
+template <int NT>
+__device__ __forceinline__ void h_pass(const uint16_t *win, int winstride, int off, int rows, int log2seg, int l2per, int tl,
+                                       const int tp[NT / 2], bool ident, int16_t *ht, int htstride)
+{
+    const int x0 = (tl & ((1 << log2seg) - 1)) << 2, rstep = (1 << l2per) >> log2seg;
+    for (int r = tl >> log2seg; r < rows; r += rstep) h_task<NT>(win + r * winstride, off, x0, tp, ident, ht, htstride, r);
+}
+
+// ---- the lists' 14-bit intermediates -> one sample.  24-bit multiplies throughout (v_mad_i32_i24 is full rate where
+// v_mul_lo_u32 is not); every operand fits: the intermediates are int16 (PROF's refinement included; the scaled filters' stay
+// below 2^19), the BCW weights lie in {-2, 3, 4, 5, 10}, the GPM slopes are int8 and its coordinates unit-relative (<= 30), the
+// intra samples and CIIP weights are 10 and 2 bits. ----
+// uni (p + 8) >> 4, bi average (p0 + p1 + 16) >> 5, BCW (p1 w1 + p0 w0 + 64) >> 7 (put_vvc_uni/bi(_w)_*): one weighted form whose
+// constants are chosen ONCE per unit (k_mca: per block) -- per-sample three-way branches on wave-uniform unit fields cost scalar
+// issue slots, which is what bounds k_mc2.  M: anything with dir, w0 and w1 -- a unit, or a BiMode where the direction is the
+// block's and not the unit's (k_mca, k_mca_rpr: a block whose lists are identical is predicted from list 1 alone)
+struct Combine { int a0, a1, rnd, sh; };
+struct BiMode { int dir, w0, w1; };
+template <class M>
+__device__ __forceinline__ Combine mc_combine_of(const M &u)
+{
+    Combine c;
+    if (u.dir != 3)                 { c.a0 = u.dir == 1; c.a1 = u.dir != 1; c.rnd = 8; c.sh = 4; }
+    else if (u.w0 == 4 && u.w1 == 4) { c.a0 = 1; c.a1 = 1; c.rnd = 16; c.sh = 5; }
+    else                            { c.a0 = u.w0; c.a1 = u.w1; c.rnd = 64; c.sh = 7; }
+    return c;
+}
+__device__ __forceinline__ int mc_combine(const Combine &c, int p0, int p1) { return ov_clip_bd((__mul24(p1, c.a1) + __mul24(p0, c.a0) + c.rnd) >> c.sh); }
+
+// geometric partitioning: w = clip3(0, 8, (K + A*x + B*y) >> 3), put_weighted_gpm_bi_pixels (rcn_mc.c:1630-1655)
+__device__ __forceinline__ int mc_gpm(uint32_t aux, int x, int y, int p0, int p1)
+{
+    const int k = (int16_t)(aux & 0xffff), a = (int8_t)((aux >> 16) & 0xff), b = (int8_t)(aux >> 24);
+    const int wgt = ov_clip3((k + __mul24(a, x) + __mul24(b, y)) >> 3, 0, 8);
+    return ov_clip_bd((__mul24(p1, 8 - wgt) + __mul24(p0, wgt) + 64) >> 7);
+}
+
+// fused CIIP blend: (intra * wt + inter * (4 - wt) + 2) >> 2, put_weighted_ciip_pixels (rcn_mc.c:1611-1628)
+__device__ __forceinline__ int ciip_blend(int inter, int intra, int wt) { return ov_clip_bd((__mul24(intra, wt) + __mul24(inter, 4 - wt) + 2) >> 2); }
+
+// ---- chroma vertical pass + combine + store of one unit: both planes in one pass, NOUT rows per lane so that the lanes cover
+// both.  s_hc: the transposed H tiles [plane * 2 + list][8 * CHT_STRIDE].  AVG (k_mcx: refined units are plain bi-predicted):
+// both lists, the average, and no GPM or CIIP code in the instantiation -- `intra` is then never read. ----
+template <int NOUT, bool AVG = false>
+__device__ __forceinline__ void chroma_finish(const ovhip_mc_unit &u, const ovhip_pic &dst, const int16_t *s_hc, const int tv[2][2],
+                                              int lane, int log2wc, int hc, const ovhip_pic &intra)
+{
+    const int wc = 1 << log2wc;
+    const int per_plane = (wc * hc) / NOUT;                   // lanes per plane (power of two, <= 32)
+    const int plane = lane >= per_plane, ll = lane - plane * per_plane;
+    if (lane >= 2 * per_plane) return;
+    const int x = ll & (wc - 1), y0 = (ll >> log2wc) * NOUT;
+    int P[2][NOUT];
+#pragma unroll
+    for (int l = 0; l < 2; ++l) {
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) P[l][o] = 0;
+        if (AVG || (u.dir & (1 << l))) v_outputs<4, NOUT>(s_hc + (plane * 2 + l) * 8 * CHT_STRIDE + x * CHT_STRIDE, y0, tv[l], P[l]);
+    }
+    uint16_t *d = (plane ? dst.cr : dst.cb) + ov_rowoff((u.y >> 1) + y0, dst.stride_c) + (u.x >> 1) + x;
+    const bool ciip = !AVG && !(u.flags & OVHIP_MC_GPM) && u.aux && !(u.aux & 0x100);
+    const uint16_t *ip = ciip ? (plane ? intra.cr : intra.cb) + ov_rowoff((u.y >> 1) + y0, intra.stride_c) + (u.x >> 1) + x : nullptr;
+    int v[NOUT];
+    if (!AVG && (u.flags & OVHIP_MC_GPM)) {
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) v[j] = mc_gpm(u.aux, 2 * x, 2 * (y0 + j), P[0][j], P[1][j]);
+    } else {
+        const Combine cmb = AVG ? Combine{ 1, 1, 16, 5 } : mc_combine_of(u);
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) v[j] = mc_combine(cmb, P[0][j], P[1][j]);
+    }
+    if (ciip) {
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) v[j] = ciip_blend(v[j], ip[j * intra.stride_c], u.aux & 7);
+    }
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) d[j * dst.stride_c] = (uint16_t)v[j];
+}
+
+// ---- PROF of one 4x4 block and list on a 6x6 int16 tile (extend_prof_buff / compute_prof_grad / rcn_prof,
+// rcn_prof_bdof.c:152-290): interior = the prediction, ring = integer reference samples << 4.  Lane c of the block's 4 owns
+// column c of the interior and the ring samples 5c .. 5c + 4. ----
+// ring sample e (0 .. 19) -> column i, row j of the tile: top row, bottom row, left column, right column
+__device__ __forceinline__ void prof_ring(int e, int &i, int &j)
+{
+    if (e < 6)       { i = e; j = 0; }
+    else if (e < 12) { i = e - 6; j = 5; }
+    else if (e < 16) { i = 0; j = e - 11; }
+    else             { i = 5; j = e - 15; }
+}
+// fill: the lane's share of the tile; ring(i, j) = the reference sample under tile position (i, j)
+template <class Ring>
+__device__ __forceinline__ void prof_fill(int16_t *t, int c, const int P[4], Ring ring)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[(j + 1) * 6 + c + 1] = (int16_t)P[j];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        int i, j;
+        prof_ring(5 * c + k, i, j);
+        t[j * 6 + i] = (int16_t)(ring(i, j) << 4);
+    }
+}
+// refine (after a barrier): gradients of the lane's 4 samples, P += clip(dx gx + dy gy); dx / dy: the lane's offsets (int16)
+__device__ __forceinline__ void prof_refine(const int16_t *t, int c, const int dx[4], const int dy[4], int P[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int o = (j + 1) * 6 + c + 1;
+        const int gx = (t[o + 1] >> 6) - (t[o - 1] >> 6), gy = (t[o + 6] >> 6) - (t[o - 6] >> 6);
+        const int add = ov_clip3(__mul24(dx[j], gx) + __mul24(dy[j], gy), -(1 << 13), (1 << 13) - 1);
+        P[j] = (int)(int16_t)(P[j] + add);
+    }
+}
+
+// ---- reference window of one 4x4 affine block and list (ROWS x ROWS samples: luma 9, chroma 7) -> LDS rows of AFF_WS samples,
+// by the block's 4 lanes (c = 0 .. 3, one aligned group of 4 samples each).  Split into issue (loads into registers) and park
+// (registers -> LDS, returns the sub-group offset) so that a window can fly while another is being filtered.  Aligned geometry
+// takes WinStage's clamped loads, inside the picture and at its borders alike; any other geometry is fetched sample by sample
+// with clamped coordinates at park time, at offset 0. ----
+#define AFF_WS 12
+template <int ROWS>
+struct AffStage {
+    uint2 q[ROWS];
+    const uint16_t *ref;
+    int sx0, sy0, off, side;
+    bool fast;
+
+    __device__ __forceinline__ void issue(const uint16_t *__restrict__ r, int rstride, int rw, int rh, int x0, int y0, int c)
+    {
+        ref = r; sx0 = x0; sy0 = y0;
+        const int ax = sx0 & ~3;
+        off = sx0 - ax;
+        const int nq = (off + ROWS + 3) >> 2;
+        fast = !((rstride | rw) & 3);
+        if (fast && c < nq) {
+            // rows clamp per lane; an aligned group outside the picture = the edge sample replicated (see WinStage)
+            const int qx = ax + 4 * c;
+            side = qx < 0 ? -1 : qx >= rw ? 1 : 0;
+            const uint16_t *base = ref + ov_clip3(qx, 0, rw - 4);
+#pragma unroll
+            for (int k = 0; k < ROWS; ++k) q[k] = *reinterpret_cast<const uint2 *>(base + ov_rowoff(ov_clip3(sy0 + k, 0, rh - 1), rstride));
+        }
+    }
+    __device__ __forceinline__ int park(int rstride, int rw, int rh, int c, uint16_t *win)
+    {
+        if (fast) {
+            if (c < ((off + ROWS + 3) >> 2)) {
+#pragma unroll
+                for (int k = 0; k < ROWS; ++k) {
+                    uint2 v = q[k];
+                    if (side) { const uint32_t e = (side < 0 ? v.x & 0xffffu : v.y >> 16) * 0x10001u; v.x = e; v.y = e; }
+                    *reinterpret_cast<uint2 *>(win + k * AFF_WS + 4 * c) = v;
+                }
+            }
+            return off;
+        }
+        for (int i = c; i < ROWS; i += 4) {
+            const int sx = ov_clip3(sx0 + i, 0, rw - 1);
+#pragma unroll 1
+            for (int k = 0; k < ROWS; ++k) win[k * AFF_WS + i] = ref[ov_clip3(sy0 + k, 0, rh - 1) * rstride + sx];
+        }
+        return 0;
+    }
+};
 
 } // namespace

@@ -15,6 +15,8 @@ The cases of a file are dealt to sheets (mc_census.sheets: PUs that do not overl
                           (k_mcxa), vectors after each;
   LMCS           the planes family once more with OVHIP_MC_LMCS set and a forward table of lmcs.ovg, against the oracle (the reference's
                  plain slots take no reshaper: no fixture of it).
+  affine units   "view"   mca.ovg's CUs (not cells: the fixture of test_gpu_parity_golden) through ovhip_mca_launch on the same kind of
+                          208-wide view: AffStage's per-sample path.
 tests/mc_census.py labels the units; test_routes_run_every_cell_the_census_claims ties what the routes launched to its cells."""
 import functools
 
@@ -164,6 +166,47 @@ def test_mc_border_cells_slow_staging(ctx, pool, name):
         same_picture([g[:, :p.shape[1]] for g, p in zip(got, want.planes())], want, f"{name} sheet {k}, 208-wide view of 210")
         for g, s, p in zip(got, start, want.planes()):
             assert np.array_equal(g[:, p.shape[1]:], s[:, p.shape[1]:]), f"{name} sheet {k}: columns outside the view changed"
+
+
+def test_mca_slow_staging(ctx, pool):
+    """mca.ovg's affine CUs through ovhip_mca_launch with its 208x120 pictures as the left 208 columns of 210-wide ones (luma stride 210,
+    chroma 105 samples): neither plane has aligned 8-byte groups, so every window of every unit, luma 9x9 and chroma 7x7, is fetched
+    sample by sample.  The fixture's expected samples do not depend on the stride; the columns outside the view must come back untouched."""
+    refs, cases, exp_off, exp = golden_cases.mca_cases()
+    W, H, n = refs[0].w, refs[0].h, len(cases)
+    rng = np.random.default_rng(6)
+
+    def wide(planes):
+        big = []
+        for k, p in enumerate(planes):
+            b = rng.integers(0, 1024, (p.shape[0], p.shape[1] + (1 if k else 2)), dtype=np.uint16)
+            b[:, :p.shape[1]] = p
+            big.append(b)
+        d = pool.planes(*big)
+        return d, big, engine.DevPic(ctx, capi.Pic(d.s.y, d.s.cb, d.s.cr, W, planes[0].shape[0], d.s.stride_y, d.s.stride_c), owns=False)
+
+    vrefs = [wide(r.planes())[2] for r in refs]
+    fill = np.full((H * n, W), FILL, np.uint16)
+    d, start, tall = wide((fill, fill[:H * n // 2, :W // 2], fill[:H * n // 2, :W // 2]))
+    for v in vrefs + [tall]:
+        assert (v.s.stride_y | v.s.w) & 3 and (v.s.stride_c | (v.s.w >> 1)) & 3, "a plane is back on the aligned staging path"
+    rec = capi.Recorder(W, H)
+    rects, n_units = [], 0
+    for i, (c, mv0, mv1) in enumerate(cases):
+        rec.reset()
+        rec.affine_cu(c, mv0, mv1)
+        ctx.mca(tall.band(i * H, H), vrefs, pool.buf(rec.aff_units()), pool.buf(rec.aff_side()))
+        n_units += len(rec.aff_units())
+        w, h = 1 << c.log2_w, 1 << c.log2_h
+        rects += [(0, c.x0, c.y0 + i * H, w, h, int(exp_off[i, 0])),
+                  (1, c.x0 >> 1, (c.y0 >> 1) + i * (H // 2), w >> 1, h >> 1, int(exp_off[i, 1])),
+                  (2, c.x0 >> 1, (c.y0 >> 1) + i * (H // 2), w >> 1, h >> 1, int(exp_off[i, 2]))]
+    ctx.sync()
+    assert n_units >= len(cases) > 0
+    got = d.download()
+    golden_cases.check_rects(HostPic(W, H * n, *[g[:, :W >> (k != 0)] for k, g in enumerate(got)]), rects, exp, "mca HIP, 208-wide view of 210")
+    for k, (g, s) in enumerate(zip(got, start)):
+        assert np.array_equal(g[:, W >> (k != 0):], s[:, W >> (k != 0):]), f"plane {k}: columns outside the view changed"
 
 
 def run_refined(ctx, pool, drefs, plain, refined, w, h, route, extra=None):
