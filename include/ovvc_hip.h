@@ -1598,6 +1598,53 @@ int  ovhip_pic_digest_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_
                               const ovhip_window *win, uint8_t out16[16]);
 
 /* ------------------------------------------------------------------------------------
+ * Output ladder on the device: ONE finished 10-bit 4:2:0 picture leaves as SEVERAL reduced surfaces -- 2160p as the 1080p, 720p, 540p
+ * and 360p rungs of a transcoder's ladder --, each at its own size, format and address, from ONE launch that reads the picture once
+ * per rung and writes no intermediate picture.  There is no new arithmetic, no new rounding and no new table: the ladder is the
+ * composition of the two definitions above, so every implementation of it (tests/spec_ladder.py, ovhip_ladder_host, k_output_ladder)
+ * is compared for equality.
+ *
+ *   Ladder   one ovhip_reduce_info -- the window in chroma units and chroma_loc -- for the picture shown, and n rungs,
+ *            1 <= n <= OVHIP_LADDER_MAX_RUNGS = 8 (k_output_ladder's arguments for 8 rungs are about 1 KB: inside the 4 KB a
+ *            launch's kernel arguments may take).
+ *   Rung r   out_w x out_h, a surface format, a destination of dst_bytes.  By definition
+ *                rung r = surface(reduce(src, info, out_w_r, out_h_r), window NULL, fmt_r)
+ *            with reduce of "Reduced-size output on the device" and surface of "Surface output on the device", byte for byte: the
+ *            dither thresholds are keyed by the coordinates in the rung's own output planes, bytes between rows and planes are
+ *            never written.  Rungs are independent of one another.  A rung of the region's own size is 1:1 on both axes: allowed,
+ *            the ladder's top rung.  Two rungs may have one size and different formats.
+ * A ladder is ALL OR NOTHING.  Refused before anything is launched or written, the reason and the rung's index in the context's error
+ * text where there is a context: whatever ovhip_output_reduce_check refuses for a rung (OVHIP_EUNSUP or OVHIP_EINVAL as there);
+ * whatever the surface output refuses for a rung's size, format, destination and dst_bytes (OVHIP_EINVAL); n out of range; null
+ * rungs, info or picture; a missing plane or a stride below the width; two rungs' destinations that overlap one another, or one that
+ * overlaps the picture.  Not done: RGB rungs, a colour table, rungs of different windows, up-sampling rungs, ratios above 8, an event
+ * hand-off to the consumer, a shim entry point.
+ * ---------------------------------------------------------------------------------- */
+#define OVHIP_LADDER_MAX_RUNGS 8
+typedef struct ovhip_ladder_rung {
+    int32_t out_w, out_h;
+    ovhip_surface_format fmt;            /* its rsv must be 0, as everywhere */
+    void *dst; size_t dst_bytes;         /* at least ovhip_surface_bytes(out_w, out_h, NULL, &fmt) */
+} ovhip_ladder_rung;
+/* Host only (no device needed): the checks the launch makes that need no picture and no destination -- n, every rung's reduce check
+ * and format, against a src_w x src_h picture.  ratio[r] = p_x, q_x, p_y, q_y of rung r (ratio may be NULL), written for every rung
+ * whose values can be derived (0 otherwise).  The first refusal's code. */
+int  ovhip_ladder_check(int32_t src_w, int32_t src_h, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n, int32_t ratio[][4]);
+/* The definition over a picture and destinations in HOST memory: ovhip_output_reduce_host, then ovhip_surface_host, per rung (it
+ * allocates one reduced picture per rung on the host heap; OVHIP_ENOMEM when that fails, before anything is written).  Refusals as the
+ * launch's; nothing is written when it refuses. */
+int  ovhip_ladder_host(const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n);
+/* Every rung's surface at its dst (DEVICE memory, aligned to its element) from the window of src.  ONE launch (k_output_ladder: all
+ * rungs, all planes; a workgroup finds its rung, plane and tile from a prefix table in the arguments, reduces the tile as
+ * k_output_reduce does and stores it as the surface's elements: 16-byte stores where the address allows, narrower at row tails, odd
+ * pitches and offsets; the Cb and the Cr of an interleaved row leave together).  Asynchronous on the ctx stream; allocates nothing,
+ * uploads nothing. */
+int  ovhip_ladder_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n);
+/* Synchronous convenience, as ovhip_pic_output_surface: the rungs' dst are HOST memory; the launch into the context's grow-only
+ * scratch, then one D2H per rung (a layout with gaps: one strided D2H per plane, so the gaps stay unwritten in host memory too). */
+int  ovhip_pic_output_ladder(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n);
+
+/* ------------------------------------------------------------------------------------
  * Film grain synthesis (film grain characteristics SEI, frequency-filtering model): replaces fg_grain_apply_pic
  * (pp_film_grain.c:814-978) as pp_process_frame calls it (post_proc.c:106-108: no IDR offset, edge smoothing on, 10 bit, 4:2:0),
  * bit-exactly wherever the reference is defined.  Per 8x8 block of a plane: the average of the block's samples inside the plane
@@ -1913,7 +1960,7 @@ int  ovhip_frame_set_output_scale(ovhip_frame *f, int32_t out_w, int32_t out_h, 
  * (post_proc.c:107-126).  A dry frame accepts the call and delivers nothing. */
 int  ovhip_frame_set_film_grain(ovhip_frame *f, const ovhip_fg_params *params, int32_t poc);
 /* Output at a REDUCED size ("Reduced-size output on the device" above): while set, every output of ovhip_frame_submit and of the last
- * ovhip_frame_band that shows the picture -- RGB, surface, DIGEST, PACKED, PLANES -- reads ONE reduced picture of out_w x out_h; their
+ * ovhip_frame_band that shows the picture -- RGB, surface, ladder, DIGEST, PACKED, PLANES -- reads ONE reduced picture of out_w x out_h; their
  * windows, sizes and the caller's planes are those of the reduced size.  The picture hash and the motion field stay at the coded
  * picture, and what is published to the DPB is the decoded picture, unchanged.  (0, 0) switches it off, which is the default; info is
  * copied (NULL: no window, chroma_loc 0).  Refusals as ovhip_output_reduce_check against the frame's size.  A frame holds ONE post
@@ -1956,6 +2003,17 @@ int  ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut);
  * independent: a frame with both set writes both.  Each of RGB output, surface output and delivery makes its own post-process step
  * (into the same scratch picture): with two of them the step runs twice, with all three three times. */
 int  ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
+/* Ladder output ("Output ladder on the device" above) of the NEXT picture completed, an output beside RGB and surface and independent
+ * of them: per picture, rungs NULL switches it off (the default).  ovhip_ladder_launch runs in ovhip_frame_submit and in the last
+ * ovhip_frame_band after the surface step and before the motion field, on the picture the outputs show -- after the frame's
+ * post-process step, which still runs once per picture: film grain, the output scale or a first reduce compose in front of the
+ * ladder, and info's window and the rungs' sizes are read against THAT picture --, whatever out->mode is, a NULL out included, and is
+ * complete on the device when the call returns.  info (NULL: no window, chroma_loc 0) and the n rungs are copied; the rungs' dst are
+ * DEVICE memory.  What needs no picture comes back here: n out of range, a null destination, a format's own refusals, and
+ * ovhip_ladder_check against the size the post-process setting of the moment leaves (set that one first).  The others come from the picture's last call: a
+ * failed ladder fails that call's return value, never the picture's publication, and writes nothing.  A dry frame accepts the call and
+ * does nothing. */
+int  ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n);
 /* Motion field output ("Motion field output on the device" above) of the NEXT picture completed: per picture, fmt NULL switches it
  * off (the default); either destination may be NULL.  ovhip_job_mvfield runs in ovhip_frame_submit after a successful
  * ovhip_job_wait and after the picture's publication, on the job that decoded it -- a borrowed job goes back to its home context
@@ -2130,6 +2188,12 @@ int  ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_
  * format the frame's setter refuses, or a bytes_per_picture below ovhip_surface_bytes() for the size the stream outputs (its output
  * scale's, else its pictures').  A slot is the caller's to reuse once the picture n_slots later is decoded. */
 int  ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
+/* Ladder output for the following runs, as the surface output above and independent of it: rung r gives its base as rungs[r].dst and
+ * its bytes per picture as rungs[r].dst_bytes, and rung r of picture idx lands at dst + (idx % n_slots) * dst_bytes in DEVICE memory,
+ * written by the frame thread that completes it (ovhip_frame_set_ladder_output).  rungs NULL: off.  The refusals of ovhip_ladder_check
+ * against the size the stream outputs (its output scale's or reduced size, else its pictures'); OVHIP_EINVAL for a null base,
+ * n_slots 0, or a rung whose bytes per picture are below its surface's size. */
+int  ovhip_stream_set_ladder_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n, uint32_t n_slots);
 /* Motion field output for the following runs: the vectors of picture idx land at d_vec_base + (idx % n_slots) *
  * vec_bytes_per_picture, its info at d_info_base + (idx % n_slots) * info_bytes_per_picture, in DEVICE memory, written by the frame
  * thread that completes it (ovhip_frame_set_mvfield_output).  Either base may be NULL (not wanted).  fmt NULL: off.  OVHIP_EINVAL

@@ -514,6 +514,14 @@ class SurfaceFormat(C.Structure):
                 ("offset_c", C.c_uint64 * 2)]
 
 
+LADDER_MAX_RUNGS = 8                                          # OVHIP_LADDER_MAX_RUNGS
+
+
+class LadderRung(C.Structure):
+    """ovhip_ladder_rung: one rung of the output ladder -- its size, its surface format, its destination and the bytes there"""
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("fmt", SurfaceFormat), ("dst", C.c_void_p), ("dst_bytes", C.c_size_t)]
+
+
 MVF_I32, MVF_F32, MVF_F16 = 0, 1, 2                 # ovhip_mvfield_format.dtype
 MVF_PLANAR, MVF_CELLS = 0, 1                         # ovhip_mvfield_format.layout: [4][H4][W4] / [H4][W4][4]
 MVF_UNIT, MVF_REFINED = 0, 1                         # ovhip_mvfield_format.vectors
@@ -813,6 +821,12 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_rgb_lut": (C.c_int, [vp, P(Pic), P(Window), P(RgbFormat), vp, vp, C.c_size_t]),
         "ovhip_frame_set_rgb_lut": (C.c_int, [vp, vp]),
         "ovhip_stream_set_rgb_lut": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+        "ovhip_ladder_check": (C.c_int, [i32, i32, P(ReduceInfo), P(LadderRung), i32, vp]),
+        "ovhip_ladder_host": (C.c_int, [P(Pic), P(ReduceInfo), P(LadderRung), i32]),
+        "ovhip_ladder_launch": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(LadderRung), i32]),
+        "ovhip_pic_output_ladder": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(LadderRung), i32]),
+        "ovhip_frame_set_ladder_output": (C.c_int, [vp, P(ReduceInfo), P(LadderRung), i32]),
+        "ovhip_stream_set_ladder_output": (C.c_int, [vp, P(ReduceInfo), P(LadderRung), i32, u32]),
         "ovhip_surface_bytes": (C.c_size_t, [i32, i32, P(Window), P(SurfaceFormat)]),
         "ovhip_surface_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(SurfaceFormat), vp, C.c_size_t]),
         "ovhip_surface_launch": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
@@ -877,6 +891,7 @@ EXPORTED_SYMBOLS = [
     "ovhip_mvfield_bytes", "ovhip_mvfield_host", "ovhip_mvfield_launch", "ovhip_job_mvfield", "ovhip_frame_set_mvfield_output", "ovhip_stream_set_mvfield_output",
     "ovhip_output_reduce_check", "ovhip_output_reduce_host", "ovhip_output_reduce_divide", "ovhip_output_reduce_launch", "ovhip_pic_output_reduced", "ovhip_pic_digest_reduced",
     "ovhip_frame_set_output_reduce", "ovhip_stream_set_output_reduce",
+    "ovhip_ladder_check", "ovhip_ladder_host", "ovhip_ladder_launch", "ovhip_pic_output_ladder", "ovhip_frame_set_ladder_output", "ovhip_stream_set_ladder_output",
 ]
 
 

@@ -16,6 +16,7 @@
 #include "ovvc_common.hip.h"
 #include "ovvc_dpb_priv.h"
 #include "run_io.hip.h"
+#include "surface_values.hip.h"
 
 namespace {
 
@@ -33,23 +34,7 @@ struct SurfArgs {
     unsigned n_items;
 };
 
-// the stored values of two samples in one dword; thr: the two thresholds of the row, D[y & 1][0] | D[y & 1][1] << 16 (ROUND: 2 | 2 << 16)
-template <int FMT> __device__ __forceinline__ uint32_t surf_pair(uint32_t w, uint32_t thr)
-{
-    if constexpr (FMT == OVHIP_SURF_I010) return w;
-    else if constexpr (FMT == OVHIP_SURF_P010) return w << 6;                  // (s <= 1023: nothing crosses into the upper half)
-    else {
-        const uint32_t q = ((w + thr) >> 2) & 0x01FF01FFu;                     // s + 3 <= 1026: each half <= 256, no carry between them
-        return q - ((q >> 8) & 0x00010001u);                                   // min(255, .): 256 is the only value above
-    }
-}
-
-// four 8-bit values out of two dwords of two 16-bit values each
-__device__ __forceinline__ uint32_t narrow4(uint32_t a, uint32_t b)
-{
-    return (a & 0xFFu) | ((a >> 8) & 0xFF00u) | ((b & 0xFFu) << 16) | ((b & 0xFF0000u) << 8);
-}
-
+// (the value functions -- surf_thr, surf_pair, narrow4, surf_interleave -- are surface_values.hip.h's: k_output_ladder stores with them too)
 template <int FMT, int DITHER>
 __global__ __launch_bounds__(SURF_NT) void k_surface(SurfArgs a)
 {
@@ -69,7 +54,7 @@ __global__ __launch_bounds__(SURF_NT) void k_surface(SurfArgs a)
     char *dst = pl == 0 ? a.dst[0] : (pl == 1 ? a.dst[1] : a.dst[2]);
     const int row = (int)(item / (unsigned)groups), g = (int)(item - (unsigned)row * (unsigned)groups);
     const int e0 = g * SURF_RUN, n = min(SURF_RUN, elems - e0);
-    const uint32_t thr = DITHER ? ((row & 1) ? (3u | (1u << 16)) : (0u | (2u << 16))) : (2u | (2u << 16));
+    const uint32_t thr = surf_thr(DITHER, row);
 
     uint32_t v[SURF_RUN / 2];                                                  // the run's values as 16-bit elements, in output order
     if (SEMI && pl == 1) {
@@ -81,8 +66,7 @@ __global__ __launch_bounds__(SURF_NT) void k_surface(SurfArgs a)
 #pragma unroll
         for (int k = 0; k < SURF_RUN / 4; ++k) {
             const uint32_t pb = surf_pair<FMT>(b[k], thr), pr = surf_pair<FMT>(r[k], thr);
-            v[2 * k] = (pb & 0xFFFFu) | (pr << 16);
-            v[2 * k + 1] = (pb >> 16) | (pr & 0xFFFF0000u);
+            surf_interleave(pb, pr, &v[2 * k], &v[2 * k + 1]);
         }
     } else {
         run_load<SURF_RUN>(src + (size_t)row * (size_t)stride + (size_t)e0, v, n);

@@ -68,6 +68,10 @@ struct ovhip_frame {
     /* the per-picture outputs (ovhip_frame_set_rgb_output / _surface_output / _mvfield_output) of the NEXT picture completed, each
      * independent of the others: the destinations are that picture's, so the settings end with it (picture_end) */
     frame_out outs[N_OUTS];
+    /* the ladder output (ovhip_frame_set_ladder_output) of the NEXT picture completed, beside them and ending with the picture as they do */
+    int ladder_on; int32_t ladder_n;
+    ovhip_reduce_info ladder_info;
+    ovhip_ladder_rung ladder[OVHIP_LADDER_MAX_RUNGS];
     /* the colour table of the RGB output (ovhip_frame_set_rgb_lut): sticky, borrowed, NULL: none */
     const ovhip_rgb_lut *rgb_lut;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
@@ -383,8 +387,8 @@ publish(ovhip_frame *f, int status)
     return r;
 }
 
-/* a picture that ends, however it ends, takes its RGB, surface and motion field destinations with it */
-static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; }
+/* a picture that ends, however it ends, takes its RGB, surface, ladder and motion field destinations with it */
+static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; f->ladder_on = 0; }
 
 int
 ovhip_frame_fail(ovhip_frame *f, int status)
@@ -515,6 +519,31 @@ ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, 
 }
 
 int
+ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!rungs) { f->ladder_on = 0; return OVHIP_OK; }
+    if (n < 1 || n > OVHIP_LADDER_MAX_RUNGS) return OVHIP_EINVAL;
+    ovhip_reduce_info ri;
+    memset(&ri, 0, sizeof(ri));
+    if (info) ri = *info;
+    for (int32_t k = 0; k < n; ++k) {                         /* what needs no picture comes back here */
+        const int r = ovhip_surface_format_check_(&rungs[k].fmt, NULL);
+        if (r != OVHIP_OK) return r;
+        if (!rungs[k].dst) return OVHIP_EINVAL;
+    }
+    if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to reduce) */
+    /* the size the ladder reads: the one the post-process step set now leaves (grain leaves the frame's) */
+    const int resized = f->post.kind == OVHIP_POST_SCALE || f->post.kind == OVHIP_POST_REDUCE;
+    const int r = ovhip_ladder_check(resized ? f->post.out_w : f->w, resized ? f->post.out_h : f->h, &ri, rungs, n, NULL);
+    if (r != OVHIP_OK) return r;
+    f->ladder_info = ri; f->ladder_n = n;
+    memcpy(f->ladder, rungs, (size_t)n * sizeof(*rungs));
+    f->ladder_on = 1;
+    return OVHIP_OK;
+}
+
+int
 ovhip_frame_set_mvfield_output(ovhip_frame *f, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes)
 {
     if (!f) return OVHIP_EINVAL;
@@ -551,7 +580,7 @@ frame_shown(ovhip_frame *f, ovhip_pic *shown, int *have)
  * wait marks the picture complete).  j: the job that decoded it; borrowed: j when it is a caller's job bound to this frame's context
  * (ovhip_frame_submit), which goes back to its own context here -- this frame and its context may be destroyed before the job.
  *
- *     publish (+ unpin the references) -> hash of f->dst -> RGB -> surface -> motion field -> the settings end -> delivery `out` names
+ *     publish (+ unpin the references) -> hash of f->dst -> RGB -> surface -> ladder -> motion field -> the settings end -> delivery `out` names
  *
  * The picture is published first: its readers go on while this thread copies it out (the outputs only read; whoever keeps the key
  * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns).  Each output is complete on the device
@@ -586,6 +615,11 @@ picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_fram
         if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_surface_launch(f->ctx, &shown, &surf->win, &surf->fmt.surf, surf->dst[0], surf->bytes[0]);
         if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "surface output");
         if (r != OVHIP_OK) fail(f, r, "surface output");
+    }
+    if (r == OVHIP_OK && f->ladder_on) {
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_ladder_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n);
+        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "ladder output");
+        if (r != OVHIP_OK) fail(f, r, "ladder output");
     }
     if (r == OVHIP_OK && mvf->on && (r = ovhip_job_mvfield_done_(j, &mvf->fmt.mvf, mvf->dst[0], mvf->bytes[0], mvf->dst[1], mvf->bytes[1])) != OVHIP_OK)
         fail(f, r, "motion field output");

@@ -65,6 +65,11 @@ struct ovhip_stream {
     ovhip_rgb_format rgb_fmt; ovhip_surface_format surf_fmt; ovhip_mvfield_format mvf_fmt;
     ovhip_window rgb_win, surf_win;
     slot_buf rgb_buf, surf_buf, mvf_vec, mvf_info;
+    /* the ladder output (ovhip_stream_set_ladder_output): every rung its own slots */
+    int ladder_on; int32_t ladder_n;
+    ovhip_reduce_info ladder_info;
+    ovhip_ladder_rung ladder[OVHIP_LADDER_MAX_RUNGS];
+    slot_buf ladder_buf[OVHIP_LADDER_MAX_RUNGS];
     ovhip_rgb_lut **rgb_luts;             /* [n_dev], or NULL: the colour tables of the RGB output (ovhip_stream_set_rgb_lut), owned */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
@@ -244,6 +249,11 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         /* (validated by the stream's setter; the conversion is this frame thread's, after its wait: nothing goes through the output thread) */
         if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, slot_of(&s->rgb_buf, idx), s->rgb_buf.bpp);
         if (s->surf_on) (void)ovhip_frame_set_surface_output(f, &s->surf_fmt, &s->surf_win, slot_of(&s->surf_buf, idx), s->surf_buf.bpp);
+        if (s->ladder_on) {
+            ovhip_ladder_rung rungs[OVHIP_LADDER_MAX_RUNGS];
+            for (int32_t k = 0; k < s->ladder_n; ++k) { rungs[k] = s->ladder[k]; rungs[k].dst = slot_of(&s->ladder_buf[k], idx); }
+            (void)ovhip_frame_set_ladder_output(f, &s->ladder_info, rungs, s->ladder_n);
+        }
         if (s->mvf_on) (void)ovhip_frame_set_mvfield_output(f, &s->mvf_fmt, slot_of(&s->mvf_vec, idx), s->mvf_vec.bpp, slot_of(&s->mvf_info, idx), s->mvf_info.bpp);
         const double t_sub = now_s();
         r = ovhip_frame_submit(f, job, NULL, &pr, &out);
@@ -658,6 +668,28 @@ ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt
     out_size(s, &w, &h);
     if (slot_buf_set(&s->surf_buf, d_base, bytes_per_picture, n_slots, ovhip_surface_bytes(w, h, win, fmt)) != OVHIP_OK) return OVHIP_EINVAL;
     s->surf_on = 1; s->surf_fmt = *fmt; s->surf_win = win ? *win : (ovhip_window){ 0, 0, 0, 0 };
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_ladder_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n, uint32_t n_slots)
+{
+    if (!s) return OVHIP_EINVAL;
+    if (!rungs) { s->ladder_on = 0; return OVHIP_OK; }
+    int32_t w, h;
+    ovhip_reduce_info ri;
+    memset(&ri, 0, sizeof(ri));
+    if (info) ri = *info;
+    out_size(s, &w, &h);
+    const int r = ovhip_ladder_check(w, h, &ri, rungs, n, NULL);
+    if (r != OVHIP_OK) return r;
+    slot_buf bufs[OVHIP_LADDER_MAX_RUNGS];
+    for (int32_t k = 0; k < n; ++k)
+        if (slot_buf_set(&bufs[k], rungs[k].dst, rungs[k].dst_bytes, n_slots, ovhip_surface_bytes(rungs[k].out_w, rungs[k].out_h, NULL, &rungs[k].fmt)) != OVHIP_OK)
+            return OVHIP_EINVAL;
+    s->ladder_on = 1; s->ladder_n = n; s->ladder_info = ri;
+    memcpy(s->ladder, rungs, (size_t)n * sizeof(*rungs));
+    memcpy(s->ladder_buf, bufs, (size_t)n * sizeof(*bufs));
     return OVHIP_OK;
 }
 

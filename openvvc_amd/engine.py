@@ -83,6 +83,38 @@ def reduce_check(src_w: int, src_h: int, dst_w: int, dst_h: int, src_window=(0, 
     return r, tuple(ratio)
 
 
+def ladder_rung(out_w: int, out_h: int, fmt: "capi.SurfaceFormat | None" = None, dst=None, nbytes: "int | None" = None, slots: bool = False) -> capi.LadderRung:
+    """an ovhip_ladder_rung (include/ovvc_hip.h, "Output ladder on the device"): out_w x out_h as a surface of `fmt` (default: tight
+    NV12) at `dst` -- a contiguous torch tensor on the device (checked against the surface's bytes and kept alive by the rung; with
+    `slots` its first dimension counts a stream's slots and the rung's bytes are one slot's), an address with `nbytes`, or None for a
+    rung that only describes (ladder_check, DevPic.ladder)"""
+    fmt = fmt if fmt is not None else surface_format()
+    rung = capi.LadderRung(out_w, out_h, fmt)
+    if dst is None or isinstance(dst, int):
+        rung.dst, rung.dst_bytes = dst or None, nbytes or 0
+    else:
+        need = capi.load().ovhip_surface_bytes(out_w, out_h, None, C.byref(fmt))
+        ptr, per, n = _surface_tensor(dst, fmt, need, slots=slots)
+        rung.dst, rung.dst_bytes = ptr, per
+        rung._keep, rung._slots = dst, n
+    return rung
+
+
+def _rung_array(rungs) -> "tuple":
+    """(the C array, n) of a sequence of capi.LadderRung"""
+    rungs = list(rungs)
+    return (capi.LadderRung * max(len(rungs), 1))(*rungs), len(rungs)
+
+
+def ladder_check(src_w: int, src_h: int, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0) -> "tuple[int, list]":
+    """(code, [(p_x, q_x, p_y, q_y) per rung]) of ovhip_ladder_check: whether src_w x src_h under src_window leaves as these rungs.
+    Host only."""
+    arr, n = _rung_array(rungs)
+    ratio = ((C.c_int32 * 4) * capi.LADDER_MAX_RUNGS)()
+    r = capi.load().ovhip_ladder_check(src_w, src_h, C.byref(capi.ReduceInfo(capi.Window(*src_window), chroma_loc)), arr, n, ratio)
+    return r, [tuple(ratio[k]) for k in range(min(n, capi.LADDER_MAX_RUNGS))]
+
+
 def mvfield_format(dtype: int = capi.MVF_I32, layout: int = capi.MVF_PLANAR, vectors: int = capi.MVF_UNIT) -> capi.MvfieldFormat:
     """an ovhip_mvfield_format (include/ovvc_hip.h, "Motion field output on the device")"""
     return capi.MvfieldFormat(dtype, layout, vectors, 0)
@@ -661,6 +693,31 @@ class DevPic:
             self.ctx._chk(r, "surface_launch")
         return r
 
+    def ladder(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0) -> "list[np.ndarray]":
+        """ovhip_pic_output_ladder: this picture as the rungs of a ladder (include/ovvc_hip.h, "Output ladder on the device"; each
+        rung a ladder_rung() without a destination), written on the device by one launch and fetched -> the surfaces' bytes, one
+        array per rung (bytes a layout leaves out are 0)"""
+        outs, full = [], []
+        for g in rungs:
+            n = self.ctx.lib.ovhip_surface_bytes(g.out_w, g.out_h, None, C.byref(g.fmt))
+            if not n:
+                raise EngineError("ladder: bad size / format of a rung")
+            outs.append(np.zeros(n, np.uint8))
+            full.append(ladder_rung(g.out_w, g.out_h, g.fmt, outs[-1].ctypes.data, n))
+        arr, n = _rung_array(full)
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        self.ctx._chk(self.ctx.lib.ovhip_pic_output_ladder(self.ctx.h, C.byref(self.s), C.byref(info), arr, n), "pic_output_ladder")
+        return outs
+
+    def ladder_into(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
+        """ovhip_ladder_launch: every rung (ladder_rung() with a torch tensor or a device address) written by one launch.  Asynchronous."""
+        arr, n = _rung_array(rungs)
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        r = self.ctx.lib.ovhip_ladder_launch(self.ctx.h, C.byref(self.s), C.byref(info), arr, n)
+        if check:
+            self.ctx._chk(r, "ladder_launch")
+        return r
+
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
         win = capi.Window(*window)
         rows = self.ctx.lib.ovhip_output_rows(self.w, self.h, C.byref(win))
@@ -1160,6 +1217,20 @@ class Frame:
         outputs (checked here), or a device address with `nbytes`; fmt None: off"""
         return _set_output(self, "surface", fmt, [(dst, nbytes)], window, check=check)
 
+    def set_ladder_output(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
+        """ovhip_frame_set_ladder_output: the NEXT picture completed is also written as the rungs of a ladder (ladder_rung() with torch
+        tensors on the device, kept alive here, or device addresses); None: off"""
+        if rungs is None:
+            return self.lib.ovhip_frame_set_ladder_output(self.f, None, None, 0)
+        arr, n = _rung_array(rungs)
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        r = self.lib.ovhip_frame_set_ladder_output(self.f, C.byref(info), arr, n)
+        if check and r:
+            raise EngineError(f"frame_set_ladder_output: {r}")
+        if r == 0:
+            self._ladder_keep = list(rungs)
+        return r
+
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None,
                            check: bool = True) -> int:
         """ovhip_frame_set_mvfield_output: the motion field of the NEXT picture completed goes to `vec` and `info` -- torch tensors on
@@ -1270,6 +1341,26 @@ class Stream:
         bytes for the size the stream outputs (checked here, kept alive here), or a device address with bytes_per_picture and n_slots;
         fmt None: off"""
         return _set_output(self, "surface", fmt, [(dst, bytes_per_picture)], window, n_slots, check)
+
+    def set_ladder_output(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0, n_slots: "int | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_ladder_output: picture idx of the following runs is also written as the rungs of a ladder, rung r into slot
+        idx % n of its own destination -- ladder_rung(..., slots=True) with a contiguous torch tensor on the device whose first
+        dimension is the slot count (the same for every rung; kept alive here), or device addresses with the bytes per picture and
+        n_slots; None: off"""
+        if rungs is None:
+            return self.lib.ovhip_stream_set_ladder_output(self.s, None, None, 0, 0)
+        rungs = list(rungs)
+        counts = {g._slots for g in rungs if hasattr(g, "_slots")}
+        if len(counts) > 1 or (counts and n_slots is not None and counts != {n_slots}):
+            raise EngineError(f"ladder output: the rungs' slots differ: {sorted(counts)}")
+        arr, n = _rung_array(rungs)
+        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
+        r = self.lib.ovhip_stream_set_ladder_output(self.s, C.byref(info), arr, n, counts.pop() if counts else (n_slots or 0))
+        if check and r:
+            raise EngineError(f"stream_set_ladder_output: {r}")
+        if r == 0:
+            self._keep.append(rungs)
+        return r
 
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes_per_picture: "int | None" = None,
                            info_bytes_per_picture: "int | None" = None, n_slots: "int | None" = None, check: bool = True) -> int:
