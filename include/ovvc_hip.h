@@ -1345,7 +1345,7 @@ int  ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_wind
  *   layout   PLANAR, PACKED as above; the size is that of the RGB output above.
  * With the lattice table T[b][g][r] = (1023 r, 1023 g, 1023 b) and P = 65535 the output is exactly n (R, G, B).
  * Not done: 1D shaper tables in front of the cube, other sizes, trilinear interpolation, float tables, a table per picture from dynamic
- * metadata, a table on the surface output.
+ * metadata.  A table on the surface output: "Surface output through a colour table" below.
  * ---------------------------------------------------------------------------------- */
 typedef struct ovhip_rgb_lut ovhip_rgb_lut;          /* opaque: the table in device memory of ctx's device, S, P */
 /* OVHIP_OK for a size of 17, 33 or 65 and a peak in 1..65535 that fmt's dtype can store (U8: peak <= 255; fmt NULL: any dtype), else
@@ -1401,7 +1401,8 @@ int  ovhip_pic_output_rgb_lut(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_
  * unknown format or rounding; a rounding other than 0 on a 16-bit format; non-zero rsv; a non-zero offset_c[1] on a semi-planar
  * format; a pitch below the row's bytes; a pitch or offset that is not a multiple of the element size; a destination that is not
  * element-aligned; planes that overlap one another; dst_bytes below the surface's size ("too small", with both numbers); a
- * destination that overlaps the picture.  Not done: 4:2:2 and 4:4:4, NV21 / YV12 / P016, error diffusion, any colour conversion.
+ * destination that overlaps the picture.  Not done: 4:2:2 and 4:4:4, NV21 / YV12 / P016, error diffusion.  A colour conversion on the
+ * way: "Surface output through a colour table" below.
  * ---------------------------------------------------------------------------------- */
 enum { OVHIP_SURF_NV12 = 0, OVHIP_SURF_P010 = 1, OVHIP_SURF_I420 = 2, OVHIP_SURF_I010 = 3 };      /* ovhip_surface_format.format */
 enum { OVHIP_SURF_ROUND = 0, OVHIP_SURF_DITHER = 1 };                                             /* ovhip_surface_format.rounding */
@@ -1425,6 +1426,75 @@ int  ovhip_surface_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_wind
  * (dst_bytes >= ovhip_surface_bytes(), pinned or pageable; a layout with gaps: one strided D2H per plane, so the gaps stay unwritten
  * in host memory too). */
 int  ovhip_pic_output_surface(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_format *fmt, void *host_dst, size_t dst_bytes);
+
+/* ------------------------------------------------------------------------------------
+ * Surface output through a colour table: a finished 10-bit 4:2:0 picture leaves as an NV12 / P010 / I420 / I010 surface whose samples
+ * are those of the CONVERTED picture -- the decoded picture taken to R'G'B', through the caller's 3D colour table (the ovhip_rgb_lut of
+ * "RGB output through a colour table": the same object, the same sizes, any peak), back to Y'CbCr with a destination matrix and range,
+ * and sub-sampled to 4:2:0 at a destination chroma location.  A BT.2020 PQ or HLG picture as the BT.709 SDR NV12 an encoder or a
+ * display next to the decoder takes: one launch, no intermediate picture.  Integer only, so every implementation of it
+ * (tests/spec_surface_lut.py, ovhip_surface_lut_host, k_surface_lut) is compared for equality.  By definition
+ *                output = surface(converted picture, window NULL, fmt)
+ * with surface of "Surface output on the device", byte for byte; the converted picture has the window's size W x H:
+ *
+ *   Conv     ovhip_surface_conv: src_matrix, src_full_range, src_chroma_loc as the three fields of ovhip_rgb_format: same values,
+ *            same refusals; dst_matrix 1, 5, 6 or 9 (2: OVHIP_EINVAL, others OVHIP_EUNSUP); dst_full_range 0 or 1; dst_chroma_loc
+ *            0..3 (4 and 5: OVHIP_EUNSUP, nobody produces them); rsv 0.
+ *   RGB      for every luma position of the window (R, G, B) in 0..1023 is `Input` of "RGB output through a colour table": N = 10
+ *            whatever the destination, chroma taps clamped to the whole picture.  (o_r, o_g, o_b) in 0..P is its `Cell` and `Tetra`.
+ *   Norm     q_c = (16368 o_c + P / 2) / P, integer divisions: 0..16368 (P = 1023: 16 o_c).
+ *   Matrix   (Kr, Kb) of dst_matrix, Kg = 1 - Kr - Kb.  Limited range: sy = 876 / 1023, sc = 896 / 1023, yoff = 64; full range:
+ *            sy = sc = 1, yoff = 0.  rnd = times 2^14, rounded to nearest on the exact rational (no case is a tie):
+ *              T = rnd(sy), y_r = rnd(sy Kr), y_b = rnd(sy Kb), y_g = T - y_r - y_b
+ *              b_r = rnd(-sc Kr / (2 (1 - Kb))), b_g = rnd(-sc Kg / (2 (1 - Kb))), b_b = -b_r - b_g
+ *              r_g = rnd(-sc Kg / (2 (1 - Kr))), r_b = rnd(-sc Kb / (2 (1 - Kr))), r_r = -r_g - r_b
+ *            and with arithmetic shifts, everything in int32:
+ *              Y14 = 16 yoff + ((y_r q_r + y_g q_g + y_b q_b + 2^13) >> 14)
+ *              Cb14 = 8192 + ((b_r q_r + b_g q_g + b_b q_b + 2^13) >> 14),  Cr14 likewise with r_r, r_g, r_b
+ *            Both chroma rows sum to zero: every grey (q_r = q_g = q_b) gives exactly 8192.  BT.709 limited is (2983, 10034, 1013),
+ *            (-1644, -5531, 7175), (7175, -6517, -658).
+ *   Luma     of the converted picture: clip((Y14 + 8) >> 4, 0, 1023).  (The clip never acts: the row's coefficients are positive and sum
+ *            to rnd(sy), and q <= 16368, so the value lies in 0..1023 for every table.  The chroma clip below acts at its upper end
+ *            only: the value before it spans 1..1024.)
+ *   Chroma   W/2 x H/2 samples, separable filters in WINDOW coordinates, tap positions clamped to the window's luma rectangle
+ *            0..W-1, 0..H-1 (what lies outside the window is not shown: luma outside it is never read).  Horizontally
+ *            dst_chroma_loc 0, 2 (co-sited): columns 2i-1, 2i, 2i+1 with weights 1, 2, 1; 1, 3 (centred): 2i, 2i+1 with 2, 2.
+ *            Vertically 0, 1 (centred): rows 2j, 2j+1 with 2, 2; 2, 3 (top): rows 2j-1, 2j, 2j+1 with 1, 2, 1.
+ *              C = clip((sum of w_x w_y C14 + 128) >> 8, 0, 1023)        -- the weights sum to 16.
+ *            (W and H are even, so only column -1 and row -1 are ever clamped.)
+ *   Surface  `Formats`, `Values` and `Layout` of "Surface output on the device" on that picture: s is its 10-bit sample, rounding and
+ *            dither go by output coordinates, gaps are never written, ovhip_surface_bytes gives the size.
+ * Refused before anything is launched or written, the reason in the context's error text: the conversion's refusals above; everything
+ * the surface output refuses; everything the RGB output through a table refuses of the picture and the table -- a null table, a table
+ * of another device, sizes that are not multiples of 4 (stricter than the surface's "even").  No restriction on P.
+ * Not done: ladder rungs through the table; a conversion without a table (the lattice table is the identity); destination locations
+ * 4 and 5; constant-luminance / ICtCp; 4:2:2 / 4:4:4; error diffusion; a table per picture.
+ * ---------------------------------------------------------------------------------- */
+typedef struct ovhip_surface_conv {
+    uint8_t src_matrix, src_full_range, src_chroma_loc;      /* the decoded picture: as ovhip_rgb_format's matrix, full_range, chroma_loc */
+    uint8_t dst_matrix, dst_full_range, dst_chroma_loc;      /* the converted picture */
+    uint8_t rsv[2];                                          /* must be 0 */
+} ovhip_surface_conv;                    /* 8 bytes */
+/* OVHIP_OK when the conversion, the format's picture-independent part (enums, rsv, rounding, pitch and offset multiples) and the
+ * table's size and peak are all accepted, else the code the launch would give.  Host only. */
+int  ovhip_surface_lut_check(const ovhip_surface_conv *conv, const ovhip_surface_format *fmt, int size, int peak);
+/* The forward matrix of conv's destination: coef = y_r y_g y_b, b_r b_g b_b, r_r r_g r_b; *yoff = 64 or 0.  Host only. */
+int  ovhip_surface_lut_coefs(const ovhip_surface_conv *conv, int32_t coef[9], int32_t *yoff);
+/* The definition on host planes and a host table into a host surface: tests, and callers that hold the picture on the host.  Refusals
+ * as the launch's, and a table entry above the peak (OVHIP_EINVAL); nothing is written when it refuses.  It allocates the converted
+ * picture (OVHIP_ENOMEM). */
+int  ovhip_surface_lut_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
+                            const ovhip_window *win, const ovhip_surface_conv *conv, const ovhip_surface_format *fmt, int size, int peak,
+                            const uint16_t *host_table, void *dst, size_t dst_bytes);
+/* As the surface launch: d_dst in DEVICE memory, at least ovhip_surface_bytes() bytes, aligned to its element; asynchronous on the ctx
+ * stream; allocates nothing.  ONE launch (k_surface_lut: a lane owns 8 luma columns of an output row pair and the 4 chroma pairs under
+ * them, with one more column or row where the destination's chroma filter reaches across). */
+int  ovhip_surface_lut_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_conv *conv, const ovhip_surface_format *fmt,
+                              const ovhip_rgb_lut *lut, void *d_dst, size_t dst_bytes);
+/* Synchronous convenience, as ovhip_pic_output_surface: the launch into the context's grow-only scratch, then a D2H of the rows' own
+ * bytes into host_dst (the gaps stay unwritten in host memory too). */
+int  ovhip_pic_output_surface_lut(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_window *win, const ovhip_surface_conv *conv, const ovhip_surface_format *fmt,
+                                  const ovhip_rgb_lut *lut, void *host_dst, size_t dst_bytes);
 
 /* ------------------------------------------------------------------------------------
  * Motion field output on the device: the motion of a decoded picture -- vectors, reference slots and prediction kinds of every inter
@@ -2003,6 +2073,14 @@ int  ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut);
  * independent: a frame with both set writes both.  Each of RGB output, surface output and delivery makes its own post-process step
  * (into the same scratch picture): with two of them the step runs twice, with all three three times. */
 int  ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes);
+/* A colour table and a conversion ("Surface output through a colour table" above) for the frame's surface output.  STICKY, as
+ * ovhip_frame_set_rgb_lut: while set, every surface output of this frame runs ovhip_surface_lut_launch in the place of
+ * ovhip_surface_launch, after the post-process step (the window, film grain, the output scale and the reduced size compose with it);
+ * lut NULL switches it off, which is the default, and the frame's calls are then what they were.  The table is borrowed, conv is
+ * copied; the setting is independent of the RGB output's table (the same table may serve both).  OVHIP_EINVAL for a null conv beside a
+ * table or a table on another device than the frame's context, the conversion's own refusals with their codes; the launch's refusals
+ * (sizes that are not multiples of 4) come from the picture's last call.  A dry frame accepts the call and does nothing. */
+int  ovhip_frame_set_surface_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv);
 /* Ladder output ("Output ladder on the device" above) of the NEXT picture completed, an output beside RGB and surface and independent
  * of them: per picture, rungs NULL switches it off (the default).  ovhip_ladder_launch runs in ovhip_frame_submit and in the last
  * ovhip_frame_band after the surface step and before the motion field, on the picture the outputs show -- after the frame's
@@ -2188,6 +2266,11 @@ int  ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_
  * format the frame's setter refuses, or a bytes_per_picture below ovhip_surface_bytes() for the size the stream outputs (its output
  * scale's, else its pictures').  A slot is the caller's to reuse once the picture n_slots later is decoded. */
 int  ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots);
+/* A colour table and a conversion for the surface output of the following runs (ovhip_frame_set_surface_lut on every frame), as
+ * ovhip_stream_set_rgb_lut and independent of it: one upload per device, owned by the stream until the setting is cleared (host_table
+ * NULL) or replaced, or the stream is destroyed; conv is copied.  The refusals of ovhip_rgb_lut_create and of the conversion; on a
+ * refusal the previous setting stands.  The slot size is still ovhip_surface_bytes.  Between runs only. */
+int  ovhip_stream_set_surface_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table);
 /* Ladder output for the following runs, as the surface output above and independent of it: rung r gives its base as rungs[r].dst and
  * its bytes per picture as rungs[r].dst_bytes, and rung r of picture idx lands at dst + (idx % n_slots) * dst_bytes in DEVICE memory,
  * written by the frame thread that completes it (ovhip_frame_set_ladder_output).  rungs NULL: off.  The refusals of ovhip_ladder_check

@@ -517,6 +517,12 @@ class SurfaceFormat(C.Structure):
 LADDER_MAX_RUNGS = 8                                          # OVHIP_LADDER_MAX_RUNGS
 
 
+class SurfaceConv(C.Structure):
+    """ovhip_surface_conv: matrix, range and chroma location of the decoded picture and of the converted one"""
+    _fields_ = [("src_matrix", C.c_uint8), ("src_full_range", C.c_uint8), ("src_chroma_loc", C.c_uint8),
+                ("dst_matrix", C.c_uint8), ("dst_full_range", C.c_uint8), ("dst_chroma_loc", C.c_uint8), ("rsv", C.c_uint8 * 2)]
+
+
 class LadderRung(C.Structure):
     """ovhip_ladder_rung: one rung of the output ladder -- its size, its surface format, its destination and the bytes there"""
     _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("fmt", SurfaceFormat), ("dst", C.c_void_p), ("dst_bytes", C.c_size_t)]
@@ -833,6 +839,13 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_surface": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
         "ovhip_frame_set_surface_output": (C.c_int, [vp, P(SurfaceFormat), P(Window), vp, C.c_size_t]),
         "ovhip_stream_set_surface_output": (C.c_int, [vp, P(SurfaceFormat), P(Window), vp, C.c_size_t, u32]),
+        "ovhip_surface_lut_check": (C.c_int, [P(SurfaceConv), P(SurfaceFormat), C.c_int, C.c_int]),
+        "ovhip_surface_lut_coefs": (C.c_int, [P(SurfaceConv), P(i32), P(i32)]),
+        "ovhip_surface_lut_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(SurfaceConv), P(SurfaceFormat), C.c_int, C.c_int, vp, vp, C.c_size_t]),
+        "ovhip_surface_lut_launch": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceConv), P(SurfaceFormat), vp, vp, C.c_size_t]),
+        "ovhip_pic_output_surface_lut": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceConv), P(SurfaceFormat), vp, vp, C.c_size_t]),
+        "ovhip_frame_set_surface_lut": (C.c_int, [vp, vp, P(SurfaceConv)]),
+        "ovhip_stream_set_surface_lut": (C.c_int, [vp, P(SurfaceConv), C.c_int, C.c_int, vp]),
         "ovhip_mvfield_bytes": (C.c_size_t, [i32, i32, P(MvfieldFormat), P(C.c_size_t)]),
         "ovhip_mvfield_host": (C.c_int, [i32, i32, P(MvfieldSrc), P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t]),
         "ovhip_mvfield_launch": (C.c_int, [vp, i32, i32, P(MvfieldSrc), P(MvfieldFormat), vp, C.c_size_t, vp, C.c_size_t]),
@@ -888,6 +901,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_rgb_lut_check", "ovhip_rgb_lut_create", "ovhip_rgb_lut_destroy", "ovhip_rgb_lut_host", "ovhip_rgb_lut_launch", "ovhip_pic_output_rgb_lut",
     "ovhip_frame_set_rgb_lut", "ovhip_stream_set_rgb_lut",
     "ovhip_surface_bytes", "ovhip_surface_host", "ovhip_surface_launch", "ovhip_pic_output_surface", "ovhip_frame_set_surface_output", "ovhip_stream_set_surface_output",
+    "ovhip_surface_lut_check", "ovhip_surface_lut_coefs", "ovhip_surface_lut_host", "ovhip_surface_lut_launch", "ovhip_pic_output_surface_lut",
+    "ovhip_frame_set_surface_lut", "ovhip_stream_set_surface_lut",
     "ovhip_mvfield_bytes", "ovhip_mvfield_host", "ovhip_mvfield_launch", "ovhip_job_mvfield", "ovhip_frame_set_mvfield_output", "ovhip_stream_set_mvfield_output",
     "ovhip_output_reduce_check", "ovhip_output_reduce_host", "ovhip_output_reduce_divide", "ovhip_output_reduce_launch", "ovhip_pic_output_reduced", "ovhip_pic_digest_reduced",
     "ovhip_frame_set_output_reduce", "ovhip_stream_set_output_reduce",

@@ -18,6 +18,7 @@
 #include "ovvc_dpb_priv.h"
 #include "ovvc_mvfield_priv.h"
 #include "ovvc_rgb_lut_priv.h"
+#include "ovvc_surface_lut_priv.h"
 
 #define MAX_REFS 16
 
@@ -74,6 +75,9 @@ struct ovhip_frame {
     ovhip_ladder_rung ladder[OVHIP_LADDER_MAX_RUNGS];
     /* the colour table of the RGB output (ovhip_frame_set_rgb_lut): sticky, borrowed, NULL: none */
     const ovhip_rgb_lut *rgb_lut;
+    /* the colour table and the conversion of the surface output (ovhip_frame_set_surface_lut): sticky, the table borrowed, NULL: none */
+    const ovhip_rgb_lut *surf_lut;
+    ovhip_surface_conv surf_conv;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -507,6 +511,20 @@ ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut)
 }
 
 int
+ovhip_frame_set_surface_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (lut) {
+        const int r = ovhip_surface_conv_check_(conv, NULL);
+        if (r != OVHIP_OK) return r;
+        if (!f->dry && !ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
+        f->surf_conv = *conv;
+    }
+    f->surf_lut = f->dry ? NULL : lut;                         /* (a dry frame has no picture to convert) */
+    return OVHIP_OK;
+}
+
+int
 ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
 {
     if (!f) return OVHIP_EINVAL;
@@ -612,7 +630,9 @@ picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_fram
         if (r != OVHIP_OK) fail(f, r, "RGB output");
     }
     if (r == OVHIP_OK && surf->on) {
-        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_surface_launch(f->ctx, &shown, &surf->win, &surf->fmt.surf, surf->dst[0], surf->bytes[0]);
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK)
+            r = f->surf_lut ? ovhip_surface_lut_launch(f->ctx, &shown, &surf->win, &f->surf_conv, &surf->fmt.surf, f->surf_lut, surf->dst[0], surf->bytes[0])
+                            : ovhip_surface_launch(f->ctx, &shown, &surf->win, &surf->fmt.surf, surf->dst[0], surf->bytes[0]);
         if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "surface output");
         if (r != OVHIP_OK) fail(f, r, "surface output");
     }

@@ -23,6 +23,7 @@
 #include "ovvc_hip.h"
 #include "ovvc_dpb_priv.h"
 #include "ovvc_mvfield_priv.h"
+#include "ovvc_surface_lut_priv.h"
 
 #define STAGE_ALL (OVHIP_STAGE_MC | OVHIP_STAGE_ITX | OVHIP_STAGE_DBF | OVHIP_STAGE_SAO | OVHIP_STAGE_ALF | OVHIP_STAGE_INTRA)
 
@@ -71,6 +72,8 @@ struct ovhip_stream {
     ovhip_ladder_rung ladder[OVHIP_LADDER_MAX_RUNGS];
     slot_buf ladder_buf[OVHIP_LADDER_MAX_RUNGS];
     ovhip_rgb_lut **rgb_luts;             /* [n_dev], or NULL: the colour tables of the RGB output (ovhip_stream_set_rgb_lut), owned */
+    ovhip_rgb_lut **surf_luts;            /* [n_dev], or NULL: the colour tables of the surface output (ovhip_stream_set_surface_lut), owned */
+    ovhip_surface_conv surf_conv;         /* their conversion */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -490,6 +493,8 @@ ovhip_stream_destroy(ovhip_stream *s)
     ovhip_host_free(s->out_host);
     for (int k = 0; s->rgb_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->rgb_luts[k]);      /* (behind the frames that borrowed them) */
     free(s->rgb_luts);
+    for (int k = 0; s->surf_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->surf_luts[k]);
+    free(s->surf_luts);
     free(s->ph);
     for (uint32_t i = 0; s->job_mtx && i < s->n_jobs; ++i) pthread_mutex_destroy(&s->job_mtx[i]);
     free(s->frames); free(s->out_ctx); free(s->job_mtx);
@@ -654,6 +659,35 @@ ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_t *ho
     for (int k = 0; s->rgb_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->rgb_luts[k]);
     free(s->rgb_luts);
     s->rgb_luts = luts;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_surface_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table)
+{
+    if (!s) return OVHIP_EINVAL;
+    ovhip_rgb_lut **luts = NULL;
+    int r = OVHIP_OK;
+    if (host_table) {
+        if ((r = ovhip_surface_conv_check_(conv, NULL)) != OVHIP_OK) return r;    /* (before anything is uploaded) */
+        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
+        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
+        if (!luts) return OVHIP_ENOMEM;
+        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
+        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_surface_lut(s->frames[i], luts[i / s->tpd], conv);
+        if (r != OVHIP_OK) {
+            /* the previous setting stands */
+            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_surface_lut(s->frames[i], s->surf_luts ? s->surf_luts[i / s->tpd] : NULL, &s->surf_conv);
+            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
+            free(luts);
+            return r;
+        }
+        s->surf_conv = *conv;
+    } else
+        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_surface_lut(s->frames[i], NULL, NULL);
+    for (int k = 0; s->surf_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->surf_luts[k]);
+    free(s->surf_luts);
+    s->surf_luts = luts;
     return OVHIP_OK;
 }
 

@@ -68,6 +68,13 @@ def surface_format(format: int = capi.SURF_NV12, rounding: int = capi.SURF_ROUND
     return fmt
 
 
+def surface_conv(src_matrix: int = 9, src_full_range: int = 0, src_chroma_loc: int = 2, dst_matrix: int = 1, dst_full_range: int = 0,
+                 dst_chroma_loc: int = 0) -> capi.SurfaceConv:
+    """an ovhip_surface_conv (include/ovvc_hip.h, "Surface output through a colour table"): matrix, range and chroma location of the
+    decoded picture and of the converted one.  The defaults: BT.2020 limited, chroma top-left, to BT.709 limited, chroma left"""
+    return capi.SurfaceConv(src_matrix, src_full_range, src_chroma_loc, dst_matrix, dst_full_range, dst_chroma_loc)
+
+
 def _surface_tensor(tensor, fmt: capi.SurfaceFormat, need: int, slots: bool = False) -> "tuple[int, int, int]":
     """(data_ptr, bytes of one slot, slots) of a torch tensor that is to take surfaces of `need` bytes"""
     import torch
@@ -673,24 +680,37 @@ class DevPic:
             self.ctx._chk(r, "rgb_launch" if lut is None else "rgb_lut_launch")
         return r
 
-    def surface(self, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0)) -> np.ndarray:
+    def surface(self, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0), lut: "RgbLut | None" = None, conv: "capi.SurfaceConv | None" = None) -> np.ndarray:
         """ovhip_pic_output_surface: this picture as a surface (include/ovvc_hip.h, "Surface output on the device"), written on the
-        device and fetched -> the surface's bytes (bytes the layout leaves out are 0)"""
+        device and fetched -> the surface's bytes (bytes the layout leaves out are 0).  lut and conv (surface_conv()): the converted
+        picture's surface (ovhip_pic_output_surface_lut, "Surface output through a colour table")"""
+        if (lut is None) != (conv is None):
+            raise EngineError("surface: lut and conv go together")
         win = capi.Window(*window)
         n = self.ctx.lib.ovhip_surface_bytes(self.w, self.h, C.byref(win), C.byref(fmt))
         if not n:
             raise EngineError("surface: bad size / window / format")
         out = np.zeros(n, np.uint8)
-        self.ctx._chk(self.ctx.lib.ovhip_pic_output_surface(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), out.ctypes.data, out.nbytes), "pic_output_surface")
+        if lut is None:
+            self.ctx._chk(self.ctx.lib.ovhip_pic_output_surface(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt), out.ctypes.data, out.nbytes), "pic_output_surface")
+        else:
+            self.ctx._chk(self.ctx.lib.ovhip_pic_output_surface_lut(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(conv), C.byref(fmt), lut.h, out.ctypes.data,
+                                                                    out.nbytes), "pic_output_surface_lut")
         return out
 
-    def surface_into(self, ptr: int, nbytes: int, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0), check: bool = True) -> int:
-        """ovhip_surface_launch into device memory at `ptr` (a DevBuf's address plus an offset, a tensor's data_ptr()).  Asynchronous."""
+    def surface_into(self, ptr: int, nbytes: int, fmt: capi.SurfaceFormat, window=(0, 0, 0, 0), check: bool = True, lut: "RgbLut | None" = None,
+                     conv: "capi.SurfaceConv | None" = None) -> int:
+        """ovhip_surface_launch into device memory at `ptr` (a DevBuf's address plus an offset, a tensor's data_ptr()).  Asynchronous.
+        conv: ovhip_surface_lut_launch with that conversion through the colour table `lut` (which may be None only to see the refusal)"""
         win = capi.Window(*window)
-        r = self.ctx.lib.ovhip_surface_launch(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(fmt) if fmt is not None else None,
-                                              C.c_void_p(ptr) if ptr else None, nbytes)
+        f, d = C.byref(fmt) if fmt is not None else None, C.c_void_p(ptr) if ptr else None
+        if conv is None and lut is None:
+            r = self.ctx.lib.ovhip_surface_launch(self.ctx.h, C.byref(self.s), C.byref(win), f, d, nbytes)
+        else:
+            r = self.ctx.lib.ovhip_surface_lut_launch(self.ctx.h, C.byref(self.s), C.byref(win), C.byref(conv) if conv is not None else None, f,
+                                                      lut.h if lut is not None else None, d, nbytes)
         if check:
-            self.ctx._chk(r, "surface_launch")
+            self.ctx._chk(r, "surface_launch" if conv is None and lut is None else "surface_lut_launch")
         return r
 
     def ladder(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0) -> "list[np.ndarray]":
@@ -1211,6 +1231,17 @@ class Frame:
             self._rgb_lut = lut
         return r
 
+    def set_surface_lut(self, lut: "RgbLut | None", conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
+        """ovhip_frame_set_surface_lut: while set, every surface output of this frame is that of the picture converted by `conv`
+        (surface_conv()) through the colour table (sticky, unlike the destination; kept alive here; independent of set_rgb_lut);
+        None: off"""
+        r = self.lib.ovhip_frame_set_surface_lut(self.f, lut.h if lut is not None else None, C.byref(conv) if conv is not None else None)
+        if check and r:
+            raise EngineError(f"frame_set_surface_lut: {r}")
+        if r == 0:
+            self._surface_lut = lut
+        return r
+
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_surface_output: the NEXT picture completed is also written as a surface into `dst` -- a contiguous torch
         tensor on the device (uint8, or int16 / uint16 for the 16-bit formats) of at least the surface's bytes for the size the frame
@@ -1332,6 +1363,19 @@ class Stream:
             r = self.lib.ovhip_stream_set_rgb_lut(self.s, size, int(peak), table.ctypes.data)
         if check and r:
             raise EngineError(f"stream_set_rgb_lut: {r}")
+        return r
+
+    def set_surface_lut(self, table: "np.ndarray | None", peak: int = 0, conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_surface_lut: the surface output of the following runs is that of the pictures converted by `conv`
+        (surface_conv()) through the colour table (numpy uint16 of shape (S, S, S, 3), uploaded once per device, owned by the
+        stream); None: off"""
+        if table is None:
+            r = self.lib.ovhip_stream_set_surface_lut(self.s, None, 0, 0, None)
+        else:
+            table, size = _lut_table(table, "stream_set_surface_lut")
+            r = self.lib.ovhip_stream_set_surface_lut(self.s, C.byref(conv) if conv is not None else None, size, int(peak), table.ctypes.data)
+        if check and r:
+            raise EngineError(f"stream_set_surface_lut: {r}")
         return r
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
