@@ -10,6 +10,14 @@
 // plane (PLANAR) or 24 / 48 / 96 bytes (PACKED); a run goes out 16 bytes at a time where its address is a multiple of 16, else 8 or 4
 // at a time, else element by element -- the path of a row's tail (W & 7 pixels), and of a destination that is only element-aligned,
 // such as a slice of a batch tensor at odd sizes.  Which path a run takes depends on its address alone, never on the data.
+//
+// The source's arguments and their fill, the chroma row load and the pixel (horizontal blend, matrix, clip) are colour_stage.hip.h's,
+// shared with k_rgb_lut and k_surface_lut.  The luma row load and the vertical blend are written out here: as functions of the header
+// (luma_row; the blend over the rows' arrays or one column at a time) they cost 8 and 3 of the 16 instantiations a wave (5 to 10 more
+// VGPRs, such as 73 -> 83, 77 -> 84: LABBOOK 36).  RgbArgs' field order is part of that: with the source in front of dst and peak the same
+// 3 lose a wave.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): 70-86 VGPRs, 44-52 SGPRs, 5-7 waves per SIMD, no
+// scratch, no LDS.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -17,23 +25,15 @@
 #include "ovvc_common.hip.h"
 #include "ovvc_dpb_priv.h"
 #include "run_io.hip.h"
+#include "colour_stage.hip.h"
 
 namespace {
 
-#define RGB_NT  256
-#define RGB_RUN 8            /* pixels of a row per lane */
-
-struct RgbArgs {
-    const uint16_t *y, *cb, *cr;
+struct RgbArgs {                          // (in this order: see above)
     char *dst;
-    int stride_y, stride_c, cw, ch;       // (cw x ch: the chroma plane of the WHOLE picture, where the taps clamp)
-    int x0, y0, W, H, groups;             // the window's first luma sample, the output size, runs per row
-    int b;                                // V = 2y - b   (U = 2x - A: the kernel's template argument)
-    int cy16, rv, gu, gv, bu, yoff, peak; // cy16 = 16 cy
-    unsigned n_items;                     // groups * H / 2
+    int peak;                             // the clip is to 0..peak
+    ColSrc s;
 };
-
-template <int DT> struct ElemBytes { static constexpr int v = DT == OVHIP_RGB_U8 ? 1 : (DT == OVHIP_RGB_F32 ? 4 : 2); };
 
 // the stored bits of one channel value
 template <int DT> __device__ __forceinline__ uint32_t rgb_bits(int v)
@@ -46,29 +46,16 @@ template <int DT> __device__ __forceinline__ uint32_t rgb_bits(int v)
     }
 }
 
-// one chroma row's 6 columns cbase - 1 .. cbase + 4, clamped to the plane (A == 0 never reads the first)
-template <int A> __device__ __forceinline__ void chroma_row(const uint16_t *row, int cbase, int cw, bool full, int (&c)[6])
-{
-    if (full && (((uintptr_t)(row + cbase)) & 7) == 0) {          // (a full run: cbase + 3 <= cw - 1)
-        const uint2 v = *reinterpret_cast<const uint2 *>(row + cbase);
-        c[1] = (int)(v.x & 0xFFFFu); c[2] = (int)(v.x >> 16); c[3] = (int)(v.y & 0xFFFFu); c[4] = (int)(v.y >> 16);
-    } else {
-#pragma unroll
-        for (int t = 1; t < 5; ++t) c[t] = row[min(cbase - 1 + t, cw - 1)];
-    }
-    c[0] = A ? (int)row[max(cbase - 1, 0)] : 0;
-    c[5] = row[min(cbase + 4, cw - 1)];
-}
-
 template <int DT, int PACKED, int A>
-__global__ __launch_bounds__(RGB_NT) void k_rgb(RgbArgs a)
+__global__ __launch_bounds__(COL_NT) void k_rgb(RgbArgs ra)
 {
-    constexpr int ES = ElemBytes<DT>::v;
-    const unsigned item = blockIdx.x * RGB_NT + threadIdx.x;
+    const ColSrc &a = ra.s;
+    constexpr int ES = RgbElemBytes<DT>::v;
+    const unsigned item = blockIdx.x * COL_NT + threadIdx.x;
     if (item >= a.n_items) return;
     const int rp = (int)(item / (unsigned)a.groups), g = (int)(item - (unsigned)rp * (unsigned)a.groups);
-    const int ox = g * RGB_RUN, n = min(RGB_RUN, a.W - ox);
-    const bool full = n == RGB_RUN;
+    const int ox = g * COL_RUN, n = min(COL_RUN, a.W - ox);
+    const bool full = n == COL_RUN;
     const int px = a.x0 + ox, py = a.y0 + 2 * rp;                  // both even
     const int cbase = px >> 1, k = py >> 1;
 
@@ -89,8 +76,9 @@ __global__ __launch_bounds__(RGB_NT) void k_rgb(RgbArgs a)
     const size_t plane = (size_t)a.W * (size_t)a.H;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        // luma
-        int Y[RGB_RUN];
+        // luma (the text of colour_stage.hip.h's luma_row, kept here for the registers) and the vertical blend:
+        // V = 2 (2k + r) - b = 4k + (2r - b), so j0 = k + ((2r - b) >> 2) and fy = (2r - b) & 3
+        int Y[COL_RUN], ub[6], vb[6];
         const uint16_t *yrow = a.y + (size_t)(py + r) * (size_t)a.stride_y + px;
         if (full && ((uintptr_t)yrow & 15) == 0) {
             const uint4 v = *reinterpret_cast<const uint4 *>(yrow);
@@ -98,11 +86,9 @@ __global__ __launch_bounds__(RGB_NT) void k_rgb(RgbArgs a)
             Y[4] = (int)(v.z & 0xFFFFu); Y[5] = (int)(v.z >> 16); Y[6] = (int)(v.w & 0xFFFFu); Y[7] = (int)(v.w >> 16);
         } else {
 #pragma unroll
-            for (int i = 0; i < RGB_RUN; ++i) Y[i] = yrow[min(i, n - 1)];
+            for (int i = 0; i < COL_RUN; ++i) Y[i] = yrow[min(i, n - 1)];
         }
-        // vertical blend: V = 2 (2k + r) - b = 4k + (2r - b), so j0 = k + ((2r - b) >> 2) and fy = (2r - b) & 3
         const int d = 2 * r - a.b, fy = d & 3, t0 = 1 + (d >> 2);          // t0: 0 or 1, the same in every lane
-        int ub[6], vb[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const int ulo = t0 ? cbv[1][i] : cbv[0][i], uhi = t0 ? cbv[2][i] : cbv[1][i];
@@ -110,18 +96,14 @@ __global__ __launch_bounds__(RGB_NT) void k_rgb(RgbArgs a)
             ub[i] = (4 - fy) * ulo + fy * uhi;
             vb[i] = (4 - fy) * vlo + fy * vhi;
         }
-        // horizontal blend, matrix, pack
-        constexpr int NWP = RGB_RUN * ES / 4, NWK = PACKED ? 3 * NWP : 1;          // dwords of a plane's run / of the packed run
+        // the pixels, packed as they come
+        constexpr int NWP = COL_RUN * ES / 4, NWK = PACKED ? 3 * NWP : 1;          // dwords of a plane's run / of the packed run
         uint32_t wr[NWP] = {}, wg[NWP] = {}, wb[NWP] = {}, wk[NWK] = {};
 #pragma unroll
-        for (int i = 0; i < RGB_RUN; ++i) {
-            const int q = 2 * i - A + 4, idx = q >> 2, fx = q & 3;          // column idx of the 6 <-> cbase - 1 + idx
-            const int u = (4 - fx) * ub[idx] + fx * ub[idx + 1] - 8192;
-            const int v = (4 - fx) * vb[idx] + fx * vb[idx + 1] - 8192;
-            const int L = a.cy16 * (Y[i] - a.yoff) + (1 << 17);
-            const uint32_t R = rgb_bits<DT>(ov_clip3((L + a.rv * v) >> 18, 0, a.peak));
-            const uint32_t G = rgb_bits<DT>(ov_clip3((L - a.gu * u - a.gv * v) >> 18, 0, a.peak));
-            const uint32_t B = rgb_bits<DT>(ov_clip3((L + a.bu * u) >> 18, 0, a.peak));
+        for (int i = 0; i < COL_RUN; ++i) {
+            int Ri, Gi, Bi;
+            col_pixel<A>(a, ub, vb, i, Y[i], ra.peak, Ri, Gi, Bi);
+            const uint32_t R = rgb_bits<DT>(Ri), G = rgb_bits<DT>(Gi), B = rgb_bits<DT>(Bi);
             if constexpr (PACKED) {
                 run_put<ES, NWK>(wk, 3 * i, R); run_put<ES, NWK>(wk, 3 * i + 1, G); run_put<ES, NWK>(wk, 3 * i + 2, B);
             } else {
@@ -130,20 +112,20 @@ __global__ __launch_bounds__(RGB_NT) void k_rgb(RgbArgs a)
         }
         const size_t at = (size_t)(2 * rp + r) * (size_t)a.W + (size_t)ox;
         if constexpr (PACKED) {
-            run_store<ES, 3 * RGB_RUN>(a.dst + at * 3 * ES, wk, 3 * n);
+            run_store<ES, 3 * COL_RUN>(ra.dst + at * 3 * ES, wk, 3 * n);
         } else {
-            run_store<ES, RGB_RUN>(a.dst + at * ES, wr, n);
-            run_store<ES, RGB_RUN>(a.dst + (plane + at) * ES, wg, n);
-            run_store<ES, RGB_RUN>(a.dst + (2 * plane + at) * ES, wb, n);
+            run_store<ES, COL_RUN>(ra.dst + at * ES, wr, n);
+            run_store<ES, COL_RUN>(ra.dst + (plane + at) * ES, wg, n);
+            run_store<ES, COL_RUN>(ra.dst + (2 * plane + at) * ES, wb, n);
         }
     }
 }
 
 template <int DT, int PACKED> void rgb_launch_a(const RgbArgs &a, int A, hipStream_t st)
 {
-    const unsigned wgs = (a.n_items + RGB_NT - 1) / RGB_NT;
-    if (A) hipLaunchKernelGGL((k_rgb<DT, PACKED, 1>), dim3(wgs), dim3(RGB_NT), 0, st, a);
-    else   hipLaunchKernelGGL((k_rgb<DT, PACKED, 0>), dim3(wgs), dim3(RGB_NT), 0, st, a);
+    const unsigned wgs = (a.s.n_items + COL_NT - 1) / COL_NT;
+    if (A) hipLaunchKernelGGL((k_rgb<DT, PACKED, 1>), dim3(wgs), dim3(COL_NT), 0, st, a);
+    else   hipLaunchKernelGGL((k_rgb<DT, PACKED, 0>), dim3(wgs), dim3(COL_NT), 0, st, a);
 }
 template <int DT> void rgb_launch_l(const RgbArgs &a, int packed, int A, hipStream_t st)
 {
@@ -164,14 +146,8 @@ extern "C" int ovhip_rgb_launch(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhi
         return r;
     }
     RgbArgs a;
-    a.y = pic->y; a.cb = pic->cb; a.cr = pic->cr; a.dst = (char *)d_dst;
-    a.stride_y = pic->stride_y; a.stride_c = pic->stride_c; a.cw = pic->w / 2; a.ch = pic->h / 2;
-    a.x0 = p.x0; a.y0 = p.y0; a.W = p.W; a.H = p.H; a.groups = (p.W + RGB_RUN - 1) / RGB_RUN;
-    a.b = p.b;
-    a.cy16 = 16 * p.coef[0]; a.rv = p.coef[1]; a.gu = p.coef[2]; a.gv = p.coef[3]; a.bu = p.coef[4]; a.yoff = p.yoff; a.peak = p.peak;
-    const size_t items = (size_t)a.groups * (size_t)(p.H / 2);
-    if (items > 0x7FFFFFFFu) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_rgb_launch: picture too large", hipSuccess);
-    a.n_items = (unsigned)items;
+    if (!col_src_fill(a.s, pic, p)) return ov_fail(ctx, OVHIP_EINVAL, "ovhip_rgb_launch: picture too large", hipSuccess);
+    a.dst = (char *)d_dst; a.peak = p.peak;
     switch (fmt->dtype) {
     case OVHIP_RGB_U8:  rgb_launch_l<OVHIP_RGB_U8>(a, fmt->layout, p.a, ctx->stream); break;
     case OVHIP_RGB_U16: rgb_launch_l<OVHIP_RGB_U16>(a, fmt->layout, p.a, ctx->stream); break;
@@ -186,14 +162,5 @@ extern "C" int ovhip_pic_output_rgb(ovhip_ctx *ctx, const ovhip_pic *pic, const 
 {
     if (!ctx || !pic || !fmt || !host_dst) return OVHIP_EINVAL;
     OV_DEVICE(ctx);
-    const size_t bytes = ovhip_rgb_bytes(pic->w, pic->h, win, fmt);
-    if (!bytes || dst_bytes < bytes) {
-        /* no size, or a host_dst that is too small: the launch refuses both before it looks at the pointer, and words the reason */
-        const int q = ovhip_rgb_launch(ctx, pic, win, fmt, host_dst, dst_bytes);
-        return q != OVHIP_OK ? q : OVHIP_EINVAL;
-    }
-    int r = ov_scratch(ctx, bytes, 0);
-    if (r == OVHIP_OK) r = ovhip_rgb_launch(ctx, pic, win, fmt, ctx->scratch_d, bytes);
-    if (r == OVHIP_OK) r = ovhip_d2h(ctx, host_dst, ctx->scratch_d, bytes);
-    return r;
+    return rgb_output_host(ctx, pic, win, fmt, host_dst, dst_bytes, [&](void *d, size_t n) { return ovhip_rgb_launch(ctx, pic, win, fmt, d, n); });
 }

@@ -80,19 +80,6 @@ ovhip_rgb_plan_make_(const ovhip_pic *pic, const ovhip_window *win, const ovhip_
     return OVHIP_OK;
 }
 
-static inline int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-/* float32 -> float16 bits, round to nearest even, for the values that occur: 0 and [1 / 1023, 1] (normal in both formats) */
-static inline uint16_t
-half_bits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if (!u) return 0;
-    u += 0xFFF + ((u >> 13) & 1);
-    return (uint16_t)((u >> 13) - ((127 - 15) << 10));
-}
-
 int
 ovhip_rgb_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
                const ovhip_window *win, const ovhip_rgb_format *fmt, void *dst, size_t dst_bytes)
@@ -101,31 +88,15 @@ ovhip_rgb_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_
     ovhip_rgb_plan_ p;
     const int r = ovhip_rgb_plan_make_(&pic, win, fmt, dst, dst_bytes, &p, NULL);
     if (r != OVHIP_OK) return r;
-    const int32_t cw = w / 2, ch = h / 2;
-    const int32_t cy = p.coef[0], rv = p.coef[1], gu = p.coef[2], gv = p.coef[3], bu = p.coef[4];
     const float to_unit = (float)(1.0 / 1023);
     const size_t plane = (size_t)p.W * (size_t)p.H;
     for (int32_t oy = 0; oy < p.H; ++oy) {
-        const int32_t py = p.y0 + oy, V = 2 * py - p.b, fy = V & 3;
-        const int32_t j0 = clampi(V >> 2, 0, ch - 1), j1 = clampi((V >> 2) + 1, 0, ch - 1);
         for (int32_t ox = 0; ox < p.W; ++ox) {
-            const int32_t px = p.x0 + ox, U = 2 * px - p.a, fx = U & 3;
-            const int32_t i0 = clampi(U >> 2, 0, cw - 1), i1 = clampi((U >> 2) + 1, 0, cw - 1);
-            const int32_t w00 = (4 - fx) * (4 - fy), w01 = fx * (4 - fy), w10 = (4 - fx) * fy, w11 = fx * fy;
-            const size_t a0 = (size_t)j0 * stride_c, a1 = (size_t)j1 * stride_c;
-            const int32_t u = w00 * cb[a0 + i0] + w01 * cb[a0 + i1] + w10 * cb[a1 + i0] + w11 * cb[a1 + i1] - 8192;
-            const int32_t v = w00 * cr[a0 + i0] + w01 * cr[a0 + i1] + w10 * cr[a1 + i0] + w11 * cr[a1 + i1] - 8192;
-            const int32_t L = 16 * cy * ((int32_t)y[(size_t)py * stride_y + px] - p.yoff) + (1 << 17);
-            const int32_t rgb[3] = { clampi((L + rv * v) >> 18, 0, p.peak), clampi((L - gu * u - gv * v) >> 18, 0, p.peak), clampi((L + bu * u) >> 18, 0, p.peak) };
+            int32_t rgb[3];
+            ovhip_rgb_pixel_(&pic, &p, p.x0 + ox, p.y0 + oy, p.peak, rgb);
             for (int c = 0; c < 3; ++c) {
                 const size_t e = fmt->layout == OVHIP_RGB_PLANAR ? (size_t)c * plane + (size_t)oy * p.W + ox : ((size_t)oy * p.W + ox) * 3 + c;
-                const float f = (float)rgb[c] * to_unit;
-                switch (fmt->dtype) {
-                case OVHIP_RGB_U8:  ((uint8_t *)dst)[e] = (uint8_t)rgb[c]; break;
-                case OVHIP_RGB_U16: ((uint16_t *)dst)[e] = (uint16_t)rgb[c]; break;
-                case OVHIP_RGB_F16: ((uint16_t *)dst)[e] = half_bits(f); break;
-                default:            ((float *)dst)[e] = f; break;
-                }
+                ovhip_rgb_put_(dst, e, fmt->dtype, rgb[c], to_unit);
             }
         }
     }

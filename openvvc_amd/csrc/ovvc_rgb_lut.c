@@ -4,6 +4,7 @@
 #include <string.h>
 #include "ovvc_hip.h"
 #include "ovvc_rgb_lut_priv.h"
+#include "ovvc_outdst_priv.h"
 
 int
 ovhip_rgb_lut_check(int size, int peak, const ovhip_rgb_format *fmt)
@@ -50,28 +51,6 @@ ovhip_rgb_lut_repack_(int size, const uint16_t *table, uint16_t *texels)
     }
 }
 
-static inline int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-/* float32 -> float16 bits, round to nearest even, for 0 <= f <= 1: normal and subnormal halves (a table peak above 16384 puts small
- * outputs below 2^-14) */
-static inline uint16_t
-half_bits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    const int32_t e = (int32_t)(u >> 23) - 127;                /* (f >= 0: no sign) */
-    if (e >= -14) {                                            /* a normal half, unless the rounding carries it to the next exponent: the sum does that too */
-        u += 0xFFF + ((u >> 13) & 1);
-        return (uint16_t)((u >> 13) - ((127 - 15) << 10));
-    }
-    if (e < -25) return 0;                                     /* below half of the smallest subnormal (2^-25 itself is the tie, to even: 0; above it: see below) */
-    /* subnormal: the value in units of 2^-24 is m * 2^(e - 23 + 24) with m the 24-bit significand; shift right by s = -(e + 1) in 14..24 */
-    const uint32_t m = (u & 0x7FFFFF) | 0x800000;
-    const int s = -(e + 1);
-    const uint32_t q = m >> s, rem = m & ((1u << s) - 1), half = 1u << (s - 1);
-    return (uint16_t)(q + (rem > half || (rem == half && (q & 1))));
-}
-
 int
 ovhip_rgb_lut_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, int32_t w, int32_t h, int32_t stride_y, int32_t stride_c,
                    const ovhip_window *win, const ovhip_rgb_format *fmt, int size, int peak, const uint16_t *host_table, void *dst, size_t dst_bytes)
@@ -81,22 +60,13 @@ ovhip_rgb_lut_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, in
     const int r = ovhip_rgb_lut_plan_make_(&pic, win, fmt, size, peak, host_table != NULL, dst, dst_bytes, &p, NULL);
     if (r != OVHIP_OK) return r;
     if (ovhip_rgb_lut_first_above_(size, peak, host_table) >= 0) return OVHIP_EINVAL;
-    const int32_t cw = w / 2, ch = h / 2, n = size - 1;
-    const int32_t cy = p.coef[0], rv = p.coef[1], gu = p.coef[2], gv = p.coef[3], bu = p.coef[4];
+    const int32_t n = size - 1;
     const float to_unit = (float)(1.0 / peak);
     const size_t plane = (size_t)p.W * (size_t)p.H;
     for (int32_t oy = 0; oy < p.H; ++oy) {
-        const int32_t py = p.y0 + oy, V = 2 * py - p.b, fy = V & 3;
-        const int32_t j0 = clampi(V >> 2, 0, ch - 1), j1 = clampi((V >> 2) + 1, 0, ch - 1);
         for (int32_t ox = 0; ox < p.W; ++ox) {
-            const int32_t px = p.x0 + ox, U = 2 * px - p.a, fx = U & 3;
-            const int32_t i0 = clampi(U >> 2, 0, cw - 1), i1 = clampi((U >> 2) + 1, 0, cw - 1);
-            const int32_t w00 = (4 - fx) * (4 - fy), w01 = fx * (4 - fy), w10 = (4 - fx) * fy, w11 = fx * fy;
-            const size_t a0 = (size_t)j0 * stride_c, a1 = (size_t)j1 * stride_c;
-            const int32_t u = w00 * cb[a0 + i0] + w01 * cb[a0 + i1] + w10 * cb[a1 + i0] + w11 * cb[a1 + i1] - 8192;
-            const int32_t v = w00 * cr[a0 + i0] + w01 * cr[a0 + i1] + w10 * cr[a1 + i0] + w11 * cr[a1 + i1] - 8192;
-            const int32_t L = 16 * cy * ((int32_t)y[(size_t)py * stride_y + px] - p.yoff) + (1 << 17);
-            const int32_t rgb[3] = { clampi((L + rv * v) >> 18, 0, 1023), clampi((L - gu * u - gv * v) >> 18, 0, 1023), clampi((L + bu * u) >> 18, 0, 1023) };
+            int32_t rgb[3];
+            ovhip_rgb_pixel_(&pic, &p, p.x0 + ox, p.y0 + oy, 1023, rgb);
             /* the cell and the fractions; ch_[k]: the channel with the k-th largest fraction */
             int32_t idx[3], f[3], ch_[3] = { 0, 1, 2 };
             for (int c = 0; c < 3; ++c) {
@@ -115,15 +85,8 @@ ovhip_rgb_lut_host(const uint16_t *y, const uint16_t *cb, const uint16_t *cr, in
                 for (int c = 0; c < 3; ++c) acc[c] += wt[k] * (int32_t)e[c];
             }
             for (int c = 0; c < 3; ++c) {
-                const int32_t o = acc[c] / 1023;
                 const size_t e = fmt->layout == OVHIP_RGB_PLANAR ? (size_t)c * plane + (size_t)oy * p.W + ox : ((size_t)oy * p.W + ox) * 3 + c;
-                const float fl = (float)o * to_unit;
-                switch (fmt->dtype) {
-                case OVHIP_RGB_U8:  ((uint8_t *)dst)[e] = (uint8_t)o; break;
-                case OVHIP_RGB_U16: ((uint16_t *)dst)[e] = (uint16_t)o; break;
-                case OVHIP_RGB_F16: ((uint16_t *)dst)[e] = half_bits(fl); break;
-                default:            ((float *)dst)[e] = fl; break;
-                }
+                ovhip_rgb_put_(dst, e, fmt->dtype, acc[c] / 1023, to_unit);
             }
         }
     }

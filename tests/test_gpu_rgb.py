@@ -72,6 +72,13 @@ def test_every_format_at_72x40(ctx, matrix):
     _check_formats(ctx, sr.random_planes(72, 40, 500 + matrix), [(matrix, full, loc) for full in (0, 1) for loc in range(6)])
 
 
+@pytest.mark.parametrize("w,h", [(72, 40), (20, 12)])
+def test_every_instantiation_and_vertical_case(ctx, w, h):
+    """every k_rgb<dtype, layout, a> under every row selection b: the six chroma locations are a = loc & 1 with b = 1, 1, 0, 0, 2, 2, each
+    in every dtype and layout over the full window.  72 x 40: nine full runs per row, twenty row pairs; 20 x 12: a run tail of 4"""
+    _check_formats(ctx, sr.random_planes(w, h, 77 + w), [(9, 0, loc) for loc in range(6)], [(0, 0, 0, 0)])
+
+
 @pytest.mark.parametrize("w,h,wd", [(20, 12, (0, 0, 0, 0)), (72, 40, (1, 0, 0, 1)), (136, 72, (0, 0, 0, 0))])
 def test_a_destination_offset_by_one_element(ctx, w, h, wd):
     """a slice of a batch tensor at odd sizes is aligned to its element and to nothing more: the bytes around it stay as they were"""

@@ -77,6 +77,17 @@ def test_every_dtype_and_layout_at_72x40(ctx, peak):
     _check(ctx, census_planes(72, 40, 500 + peak % 7), sl.random_table(33, peak, peak), peak, combos, [(0, 0, 0, 0), (1, 0, 0, 1), (0, 3, 2, 0)], loc=2)
 
 
+@pytest.mark.parametrize("w,h", [(72, 40), (20, 12)])
+@pytest.mark.parametrize("loc", range(6))
+def test_every_instantiation_and_vertical_case(ctx, w, h, loc):
+    """every k_rgb_lut<dtype, layout, a> under every row selection b: the six chroma locations are a = loc & 1 with b = 1, 1, 0, 0, 2, 2.
+    72 x 40: nine full runs per row, twenty row pairs; 20 x 12: a run tail of 4.  The table's output is restated once per location and
+    peak and stored in every dtype and layout"""
+    planes = census_planes(w, h, 40 + loc)
+    _check(ctx, planes, sl.random_table(17, 255, loc), 255, [(sr.U8, lay) for lay in LAYOUTS], [(0, 0, 0, 0)], loc=loc)
+    _check(ctx, planes, sl.random_table(17, 65535, 6 + loc), 65535, [(dt, lay) for dt in DTYPES if dt != sr.U8 for lay in LAYOUTS], [(0, 0, 0, 0)], loc=loc)
+
+
 def test_the_lattice_table_gives_exactly_n_times_the_rgb_output(ctx):
     planes = census_planes(136, 72, 6)
     pic = ctx.upload_pic(*planes)

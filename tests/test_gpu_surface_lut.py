@@ -85,6 +85,19 @@ def test_launch_and_convenience_equal_host_and_restatement(ctx, w, h, dloc):
     _check(ctx, w, h, cs.conv_of(n, (dloc + w // 4) % 3, dloc), cs.TABLE_SIZES[(n + 1) % 3], cs.PEAKS[(dloc + w // 8) % 4], cs.WINDOWS, modes, gaps=(bool(dloc & 2),))
 
 
+@pytest.mark.parametrize("w,h", cs.PICTURES)
+@pytest.mark.parametrize("sloc", range(6))
+def test_every_instantiation_and_vertical_case(ctx, w, h, sloc):
+    """every k_surface_lut<format, a, hc> under every row selection of the source (a = sloc & 1 with b = 1, 1, 0, 0, 2, 2) and both
+    vertical cases of the destination (hc = 1 at dloc 0 and 2, the halo row at dloc 2 and 3), the full window, tight rows; the 8-bit formats
+    round and dither in turn, the 16-bit ones take rounding only.  72 x 40: nine full runs per row, twenty row pairs; 20 x 12: a run
+    tail of 4.  A case's converted picture is restated once and stored in the four formats"""
+    for dloc in sx.DST_LOCS:
+        r8 = (ss.ROUND, ss.DITHER)[(sloc + dloc) & 1]
+        modes = [(ss.NV12, r8), (ss.I420, ss.ROUND + ss.DITHER - r8), (ss.P010, ss.ROUND), (ss.I010, ss.ROUND)]
+        _check(ctx, w, h, cs.conv_of((sloc + dloc) % 3, sloc, dloc), cs.TABLE_SIZES[(sloc + dloc) % 3], cs.PEAKS[dloc], [(0, 0, 0, 0)], modes, gaps=(False,))
+
+
 def test_a_destination_offset_by_one_element(ctx):
     """aligned to its element and to nothing more, with a pitch with gaps, over a sentinel: no byte outside the rows' own bytes is written"""
     _check(ctx, 72, 40, cs.conv_of(1, 2, 2), 17, 1023, [(0, 0, 0, 0), (1, 0, 0, 1)], gaps=(True,), leads=(1, 3))

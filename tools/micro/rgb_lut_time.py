@@ -1,6 +1,6 @@
 """RGB output through a colour table (k_rgb_lut) on the device: the numbers LABBOOK 30 / DESIGN 8 f3 quote.
 
-    python tools/micro/rgb_lut_time.py launches 3840x2160 [N]
+    python tools/micro/rgb_lut_time.py launches 3840x2160 [N] [out.json]
         per dtype (planar): k_rgb -- kernels_rgb.hip is byte for byte the parent commit's, so this IS the parent's k_rgb, in the same
         process -- then k_rgb_lut for each table size (17, 33, 65) and each of three tables: `smooth` (lut3d.pq_bt2020_to_bt709),
         `lattice` (lut3d.lattice; peak 65535, so not for U8) and `random` (the worst case for locality), then k_rgb again.  Each
@@ -14,6 +14,7 @@
         rgb_time.py's stream, three ways in one process, alternating, profiler off: OVHIP_OUT_NONE, OVHIP_OUT_NONE with RGB output on
         (F16 planar into a device-resident torch tensor of 32 slots), the same through a table (size 33, smooth).  Pictures/s each.
 """
+import json
 import sys
 import time
 from pathlib import Path
@@ -50,7 +51,7 @@ def tables(s, peak):
     return out
 
 
-def launches(s, n):
+def launches(s, n, out=None):
     import torch
     from openvvc_amd import capi, engine
     stream = torch.cuda.Stream()
@@ -74,24 +75,34 @@ def launches(s, n):
             rounds.append(1e3 * e0.elapsed_time(e1) / n)
         return float(np.median(rounds)), rounds
 
+    results = {"size": f"{w}x{h}", "launches_per_round": n, "unit": "us per launch, median of 3 rounds", "figures": {}}
+
+    def note(name, us, r):
+        results["figures"][name] = {"median_us": round(us, 2), "rounds_us": [round(v, 2) for v in r]}
+
     for dtype, dn in DTYPES.items():
         peak = 255 if dtype == 0 else 65535
         fmt = capi.RgbFormat(9, 0, 0, dtype, 0)
         base = {}
         for pn, pic in pics.items():
             base[pn], r = timed(lambda: pic.rgb_into(d.ptr.value, d.nbytes, fmt))
+            note(f"k_rgb {dn} planar, {pn}", base[pn], r)
             print(f"{w}x{h} {dn} planar, {pn} picture, k_rgb: {base[pn]:.1f} us per launch (rounds: {', '.join(f'{v:.1f}' for v in r)})", flush=True)
         for sz in (17, 33, 65):
             for tn, table in tables(sz, peak).items():
                 with engine.RgbLut(ctx, table, peak) as lut:
                     for pn, pic in pics.items():
                         us, r = timed(lambda: pic.rgb_into(d.ptr.value, d.nbytes, fmt, lut=lut))
+                        note(f"k_rgb_lut {dn} planar S={sz} {tn} table, {pn}", us, r)
                         print(f"{w}x{h} {dn} planar, {pn} picture, k_rgb_lut S={sz} {tn} table: {us:.1f} us per launch = {us / base[pn]:.2f} x k_rgb "
                               f"(rounds: {', '.join(f'{v:.1f}' for v in r)})", flush=True)
         for pn, pic in pics.items():
             again, r = timed(lambda: pic.rgb_into(d.ptr.value, d.nbytes, fmt))
+            note(f"k_rgb {dn} planar again, {pn}", again, r)
             print(f"{w}x{h} {dn} planar, {pn} picture, k_rgb again: {again:.1f} us per launch (first: {base[pn]:.1f})", flush=True)
     d.free(); [p.free() for p in pics.values()]; ctx.close()
+    if out:
+        Path(out).write_text(json.dumps(results, indent=1) + "\n")
 
 
 def stream(s, threads):
@@ -152,7 +163,7 @@ def stream(s, threads):
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else ""
     if mode == "launches":
-        launches(size(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 200)
+        launches(size(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 200, sys.argv[4] if len(sys.argv) > 4 else None)
     elif mode == "stream":
         stream(size(sys.argv[2]) if len(sys.argv) > 2 else (3840, 2160), int(sys.argv[3]) if len(sys.argv) > 3 else 16)
     else:

@@ -1,11 +1,11 @@
 """RGB output (k_rgb) on the device: the numbers LABBOOK / DESIGN 8 f3 quote.
 
-    python tools/micro/rgb_time.py launches 3840x2160 [N]
+    python tools/micro/rgb_time.py launches 3840x2160 [N] [out.json]
         warm-up, then N (default 200) launches of ovhip_rgb_launch per dtype and layout, and of ovhip_output_pack_launch on the same
         picture (the comparison: the kernel every PACKED output runs), one synchronise each: run it under
         `rocprofv3 --kernel-trace --stats -d <dir> -- python ...` and read the averages of k_rgb<dtype, packed, a> and k_output_pack
         from its output (the `kernels` view of the results database: avg(end - start) by name).  Prints the bytes each has to move and, from a host clock around the N launches (enqueue included: NOT the kernel
-        time), the time per launch.
+        time), the time per launch; with out.json, those times as a file.
     python tools/micro/rgb_time.py share 3840x2160 <dtype> <kernel_us>
         those bytes over a kernel time taken from the trace: GB/s and the share of the 8 TB/s HBM peak (no device needed).
     python tools/micro/rgb_time.py stream [3840x2160] [threads]
@@ -14,6 +14,7 @@
         into a device-resident torch tensor of 32 slots), OVHIP_OUT_PACKED.  The first intra period warms up, the second is timed;
         three rounds, pictures/s each.
 """
+import json
 import sys
 import time
 from pathlib import Path
@@ -47,11 +48,12 @@ def noise_pic(ctx, w, h, seed):
     return ctx.upload_pic(*(rs.randint(0, 1024, shape).astype(np.uint16) for shape in ((h, w), (h // 2, w // 2), (h // 2, w // 2))))
 
 
-def launches(s, n):
+def launches(s, n, out=None):
     import ctypes as C
     from openvvc_amd import capi, engine
     ctx = engine.Context(0)
     pic, d = noise_pic(ctx, s[0], s[1], 1), ctx.alloc(s[0] * s[1] * 3 * 4)
+    results = {"size": f"{s[0]}x{s[1]}", "launches": n, "unit": "us per launch on the host clock, enqueue included", "figures": {}}
 
     def timed(name, nbytes, fn):
         for _ in range(20):
@@ -62,6 +64,7 @@ def launches(s, n):
             fn()
         ctx.sync()
         dt = (time.perf_counter() - t0) / n
+        results["figures"][name] = round(1e6 * dt, 2)
         print(f"{s[0]}x{s[1]} {name}: {n} launches, {1e6 * dt:.1f} us per launch on the host clock (enqueue included); {nbytes / 1e6:.2f} MB to move per launch")
 
     for dtype, (dn, es) in DTYPES.items():
@@ -71,6 +74,8 @@ def launches(s, n):
     win = capi.Window(0, 0, 0, 0)
     timed("k_output_pack", pack_bytes(s), lambda: ctx._chk(ctx.lib.ovhip_output_pack_launch(ctx.h, C.byref(pic.s), C.byref(win), d.ptr), "pack"))
     d.free(); pic.free(); ctx.close()
+    if out:
+        Path(out).write_text(json.dumps(results, indent=1) + "\n")
 
 
 def stream(s, threads):
@@ -127,7 +132,7 @@ def stream(s, threads):
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else ""
     if mode == "launches":
-        launches(size(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 200)
+        launches(size(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 200, sys.argv[4] if len(sys.argv) > 4 else None)
     elif mode == "share":
         s, es, us = size(sys.argv[2]), {v[0]: v[1] for v in DTYPES.values()}[sys.argv[3]], float(sys.argv[4])
         nb = rgb_bytes(s, es)
