@@ -1467,8 +1467,9 @@ int  ovhip_pic_output_surface(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_
  * Refused before anything is launched or written, the reason in the context's error text: the conversion's refusals above; everything
  * the surface output refuses; everything the RGB output through a table refuses of the picture and the table -- a null table, a table
  * of another device, sizes that are not multiples of 4 (stricter than the surface's "even").  No restriction on P.
- * Not done: ladder rungs through the table; a conversion without a table (the lattice table is the identity); destination locations
- * 4 and 5; constant-luminance / ICtCp; 4:2:2 / 4:4:4; error diffusion; a table per picture.
+ * Several reduced sizes of one picture through the table: "Output ladder through a colour table" below.
+ * Not done: a conversion without a table (the lattice table is the identity); destination locations 4 and 5; constant-luminance /
+ * ICtCp; 4:2:2 / 4:4:4; error diffusion; a table per picture.
  * ---------------------------------------------------------------------------------- */
 typedef struct ovhip_surface_conv {
     uint8_t src_matrix, src_full_range, src_chroma_loc;      /* the decoded picture: as ovhip_rgb_format's matrix, full_range, chroma_loc */
@@ -1687,8 +1688,8 @@ int  ovhip_pic_digest_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_
  * text where there is a context: whatever ovhip_output_reduce_check refuses for a rung (OVHIP_EUNSUP or OVHIP_EINVAL as there);
  * whatever the surface output refuses for a rung's size, format, destination and dst_bytes (OVHIP_EINVAL); n out of range; null
  * rungs, info or picture; a missing plane or a stride below the width; two rungs' destinations that overlap one another, or one that
- * overlaps the picture.  Not done: RGB rungs, a colour table, rungs of different windows, up-sampling rungs, ratios above 8, an event
- * hand-off to the consumer, a shim entry point.
+ * overlaps the picture.  Rungs through a colour table: "Output ladder through a colour table" below.  Not done: RGB rungs, rungs of
+ * different windows, up-sampling rungs, ratios above 8, an event hand-off to the consumer, a shim entry point.
  * ---------------------------------------------------------------------------------- */
 #define OVHIP_LADDER_MAX_RUNGS 8
 typedef struct ovhip_ladder_rung {
@@ -1713,6 +1714,49 @@ int  ovhip_ladder_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_reduc
 /* Synchronous convenience, as ovhip_pic_output_surface: the rungs' dst are HOST memory; the launch into the context's grow-only
  * scratch, then one D2H per rung (a layout with gaps: one strided D2H per plane, so the gaps stay unwritten in host memory too). */
 int  ovhip_pic_output_ladder(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n);
+
+/* ------------------------------------------------------------------------------------
+ * Output ladder through a colour table: ONE finished 10-bit 4:2:0 picture leaves as SEVERAL reduced surfaces whose samples are those of
+ * the CONVERTED reduced pictures -- a BT.2020 PQ or HLG 2160p picture as the BT.709 SDR 1080p, 720p, 540p and 360p NV12 rungs of a
+ * transcoder's ladder --, from ONE launch that writes no intermediate picture.  Nothing new is computed: with one ovhip_reduce_info, n
+ * rungs (the ovhip_ladder_rung above, 1 <= n <= OVHIP_LADDER_MAX_RUNGS), one ovhip_surface_conv and one ovhip_rgb_lut table of 17, 33 or
+ * 65 points per axis and any peak, by definition
+ *                rung r = surface_lut(reduce(src, info, out_w_r, out_h_r), window NULL, conv, fmt_r, lut)
+ * with reduce of "Reduced-size output on the device" and surface_lut of "Surface output through a colour table", byte for byte; every
+ * implementation of it (tests/spec_ladder_lut.py, ovhip_ladder_lut_host, k_ladder_lut) is compared for equality.  So the source's chroma
+ * taps clamp to the REDUCED picture's chroma plane, the destination chroma filter's taps to the reduced picture's luma rectangle, the
+ * dither thresholds go by the rung's own output coordinates, bytes between rows and planes are never written, rungs are independent
+ * of one another, and a rung of the region's own size is surface_lut of the region.  One table and one conversion serve all rungs.
+ * Reduce first, then convert, on purpose: a rung equals what a frame writes with ovhip_frame_set_output_reduce in front of
+ * ovhip_frame_set_surface_lut, and the conversion runs on the rungs' pixels only.  (Averaging in linear light -- convert first -- is
+ * not this.)
+ * A ladder is ALL OR NOTHING.  Refused before anything is launched or written, the reason and the rung's index in the context's error
+ * text: everything ovhip_ladder_launch refuses; the conversion's own refusals with their codes; conv->src_chroma_loc other than
+ * info->chroma_loc (OVHIP_EINVAL: the reduced picture keeps the source's sample location, so two values are a mistake that would shift
+ * the chroma silently); everything ovhip_surface_lut_launch refuses of a rung's picture, format and destination -- rung sizes that
+ * are not multiples of 4 among them --; a null table, a table of another device.
+ * Not done: RGB rungs, a table or a conversion per rung, convert-then-reduce, rungs of different windows, up-sampling rungs, ratios
+ * above 8, destination locations 4 and 5, a conversion without a table, a shim entry point.
+ * ---------------------------------------------------------------------------------- */
+/* Host only: the checks the launch makes that need no picture and no destination, against a src_w x src_h picture and a table of
+ * `size` points and peak `peak`.  ratio as ovhip_ladder_check's.  The first refusal's code. */
+int  ovhip_ladder_lut_check(int32_t src_w, int32_t src_h, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n,
+                            const ovhip_surface_conv *conv, int size, int peak, int32_t ratio[][4]);
+/* The definition over a picture, a table and destinations in HOST memory: ovhip_output_reduce_host, then ovhip_surface_lut_host, per
+ * rung (one reduced picture per rung on the host heap; OVHIP_ENOMEM when that fails).  Refusals as the launch's, and a table entry above
+ * the peak (OVHIP_EINVAL); nothing is written when it refuses. */
+int  ovhip_ladder_lut_host(const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n, const ovhip_surface_conv *conv,
+                           int size, int peak, const uint16_t *host_table);
+/* Every rung's surface at its dst (DEVICE memory, aligned to its element) from the window of src.  ONE launch (k_ladder_lut: all rungs,
+ * all planes; a workgroup finds its rung and tile from a prefix table in the arguments, reduces the tile's Y, Cb and Cr with their halo
+ * into LDS, converts from there and stores the surface's elements).  Asynchronous on the ctx stream; allocates nothing, uploads
+ * nothing; no intermediate picture in device memory. */
+int  ovhip_ladder_lut_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n,
+                             const ovhip_surface_conv *conv, const ovhip_rgb_lut *lut);
+/* Synchronous convenience, as ovhip_pic_output_ladder: the rungs' dst are HOST memory; the launch into the context's grow-only scratch,
+ * then the rows' own bytes of every plane to the host (the gaps stay unwritten in host memory too). */
+int  ovhip_pic_output_ladder_lut(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n,
+                                 const ovhip_surface_conv *conv, const ovhip_rgb_lut *lut);
 
 /* ------------------------------------------------------------------------------------
  * Film grain synthesis (film grain characteristics SEI, frequency-filtering model): replaces fg_grain_apply_pic
@@ -2092,6 +2136,17 @@ int  ovhip_frame_set_surface_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const
  * failed ladder fails that call's return value, never the picture's publication, and writes nothing.  A dry frame accepts the call and
  * does nothing. */
 int  ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n);
+/* A colour table and a conversion ("Output ladder through a colour table" above) for the frame's ladder output.  STICKY, exactly as
+ * ovhip_frame_set_surface_lut: while set, the frame's ladder step runs ovhip_ladder_lut_launch in the place of ovhip_ladder_launch,
+ * after the post-process step (film grain, the output scale or a first reduce compose in front of it); lut NULL switches it off, which
+ * is the default, and the frame's calls and launches are then what they were.  The table is borrowed, conv is copied; the setting is
+ * independent of the RGB output's table and of the surface output's (the same object may serve all three).  OVHIP_EINVAL for a null
+ * conv beside a table or a table on another device than the frame's context, the conversion's own refusals with their codes.
+ * conv->src_chroma_loc must be the ladder's info->chroma_loc: OVHIP_EINVAL from whichever of this setter and
+ * ovhip_frame_set_ladder_output is called second (that one then asks ovhip_ladder_lut_check in the place of ovhip_ladder_check, so
+ * rung sizes that are not multiples of 4 come back there too), and the launch makes the refusal again.  A dry frame accepts the call
+ * and does nothing. */
+int  ovhip_frame_set_ladder_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv);
 /* Motion field output ("Motion field output on the device" above) of the NEXT picture completed: per picture, fmt NULL switches it
  * off (the default); either destination may be NULL.  ovhip_job_mvfield runs in ovhip_frame_submit after a successful
  * ovhip_job_wait and after the picture's publication, on the job that decoded it -- a borrowed job goes back to its home context
@@ -2277,6 +2332,13 @@ int  ovhip_stream_set_surface_lut(ovhip_stream *s, const ovhip_surface_conv *con
  * against the size the stream outputs (its output scale's or reduced size, else its pictures'); OVHIP_EINVAL for a null base,
  * n_slots 0, or a rung whose bytes per picture are below its surface's size. */
 int  ovhip_stream_set_ladder_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n, uint32_t n_slots);
+/* A colour table and a conversion for the ladder output of the following runs (ovhip_frame_set_ladder_lut on every frame), as
+ * ovhip_stream_set_surface_lut and independent of it and of ovhip_stream_set_rgb_lut: one upload per device, owned by the stream until
+ * the setting is cleared (host_table NULL) or replaced, or the stream is destroyed; conv is copied.  The refusals of
+ * ovhip_rgb_lut_create and of the conversion, and -- from whichever of this setter and ovhip_stream_set_ladder_output is called second --
+ * those of ovhip_ladder_lut_check for the ladder set; on a refusal the previous setting stands.  The rungs' slot sizes are still
+ * ovhip_surface_bytes.  Between runs only. */
+int  ovhip_stream_set_ladder_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table);
 /* Motion field output for the following runs: the vectors of picture idx land at d_vec_base + (idx % n_slots) *
  * vec_bytes_per_picture, its info at d_info_base + (idx % n_slots) * info_bytes_per_picture, in DEVICE memory, written by the frame
  * thread that completes it (ovhip_frame_set_mvfield_output).  Either base may be NULL (not wanted).  fmt NULL: off.  OVHIP_EINVAL

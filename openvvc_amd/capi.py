@@ -833,6 +833,12 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_ladder": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(LadderRung), i32]),
         "ovhip_frame_set_ladder_output": (C.c_int, [vp, P(ReduceInfo), P(LadderRung), i32]),
         "ovhip_stream_set_ladder_output": (C.c_int, [vp, P(ReduceInfo), P(LadderRung), i32, u32]),
+        "ovhip_ladder_lut_check": (C.c_int, [i32, i32, P(ReduceInfo), P(LadderRung), i32, P(SurfaceConv), C.c_int, C.c_int, vp]),
+        "ovhip_ladder_lut_host": (C.c_int, [P(Pic), P(ReduceInfo), P(LadderRung), i32, P(SurfaceConv), C.c_int, C.c_int, vp]),
+        "ovhip_ladder_lut_launch": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(LadderRung), i32, P(SurfaceConv), vp]),
+        "ovhip_pic_output_ladder_lut": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(LadderRung), i32, P(SurfaceConv), vp]),
+        "ovhip_frame_set_ladder_lut": (C.c_int, [vp, vp, P(SurfaceConv)]),
+        "ovhip_stream_set_ladder_lut": (C.c_int, [vp, P(SurfaceConv), C.c_int, C.c_int, vp]),
         "ovhip_surface_bytes": (C.c_size_t, [i32, i32, P(Window), P(SurfaceFormat)]),
         "ovhip_surface_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(SurfaceFormat), vp, C.c_size_t]),
         "ovhip_surface_launch": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
@@ -907,6 +913,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_output_reduce_check", "ovhip_output_reduce_host", "ovhip_output_reduce_divide", "ovhip_output_reduce_launch", "ovhip_pic_output_reduced", "ovhip_pic_digest_reduced",
     "ovhip_frame_set_output_reduce", "ovhip_stream_set_output_reduce",
     "ovhip_ladder_check", "ovhip_ladder_host", "ovhip_ladder_launch", "ovhip_pic_output_ladder", "ovhip_frame_set_ladder_output", "ovhip_stream_set_ladder_output",
+    "ovhip_ladder_lut_check", "ovhip_ladder_lut_host", "ovhip_ladder_lut_launch", "ovhip_pic_output_ladder_lut", "ovhip_frame_set_ladder_lut",
+    "ovhip_stream_set_ladder_lut",
 ]
 
 

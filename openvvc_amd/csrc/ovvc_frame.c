@@ -78,6 +78,9 @@ struct ovhip_frame {
     /* the colour table and the conversion of the surface output (ovhip_frame_set_surface_lut): sticky, the table borrowed, NULL: none */
     const ovhip_rgb_lut *surf_lut;
     ovhip_surface_conv surf_conv;
+    /* the colour table and the conversion of the ladder output (ovhip_frame_set_ladder_lut): sticky, the table borrowed, NULL: none */
+    const ovhip_rgb_lut *ladder_lut;
+    ovhip_surface_conv ladder_conv;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -525,6 +528,22 @@ ovhip_frame_set_surface_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhi
 }
 
 int
+ovhip_frame_set_ladder_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (lut) {
+        const int r = ovhip_surface_conv_check_(conv, NULL);
+        if (r != OVHIP_OK) return r;
+        if (!f->dry && !ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
+        /* a ladder already set for the next picture: the reduced pictures keep ITS sample location */
+        if (f->ladder_on && conv->src_chroma_loc != f->ladder_info.chroma_loc) return OVHIP_EINVAL;
+        f->ladder_conv = *conv;
+    }
+    f->ladder_lut = f->dry ? NULL : lut;                       /* (a dry frame has no picture to convert) */
+    return OVHIP_OK;
+}
+
+int
 ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
 {
     if (!f) return OVHIP_EINVAL;
@@ -553,7 +572,10 @@ ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, con
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to reduce) */
     /* the size the ladder reads: the one the post-process step set now leaves (grain leaves the frame's) */
     const int resized = f->post.kind == OVHIP_POST_SCALE || f->post.kind == OVHIP_POST_REDUCE;
-    const int r = ovhip_ladder_check(resized ? f->post.out_w : f->w, resized ? f->post.out_h : f->h, &ri, rungs, n, NULL);
+    const int32_t sw = resized ? f->post.out_w : f->w, sh = resized ? f->post.out_h : f->h;
+    /* with a table set, the table's share too: the location the conversion reads, rung sizes in multiples of 4 */
+    const int r = f->ladder_lut ? ovhip_ladder_lut_check(sw, sh, &ri, rungs, n, &f->ladder_conv, f->ladder_lut->size, f->ladder_lut->peak, NULL)
+                                : ovhip_ladder_check(sw, sh, &ri, rungs, n, NULL);
     if (r != OVHIP_OK) return r;
     f->ladder_info = ri; f->ladder_n = n;
     memcpy(f->ladder, rungs, (size_t)n * sizeof(*rungs));
@@ -637,7 +659,9 @@ picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_fram
         if (r != OVHIP_OK) fail(f, r, "surface output");
     }
     if (r == OVHIP_OK && f->ladder_on) {
-        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_ladder_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n);
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) 
+            r = f->ladder_lut ? ovhip_ladder_lut_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n, &f->ladder_conv, f->ladder_lut)
+                              : ovhip_ladder_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n);
         if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "ladder output");
         if (r != OVHIP_OK) fail(f, r, "ladder output");
     }

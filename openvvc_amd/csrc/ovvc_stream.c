@@ -74,6 +74,8 @@ struct ovhip_stream {
     ovhip_rgb_lut **rgb_luts;             /* [n_dev], or NULL: the colour tables of the RGB output (ovhip_stream_set_rgb_lut), owned */
     ovhip_rgb_lut **surf_luts;            /* [n_dev], or NULL: the colour tables of the surface output (ovhip_stream_set_surface_lut), owned */
     ovhip_surface_conv surf_conv;         /* their conversion */
+    ovhip_rgb_lut **ladder_luts;          /* [n_dev], or NULL: the colour tables of the ladder output (ovhip_stream_set_ladder_lut), owned */
+    ovhip_surface_conv ladder_conv;       /* their conversion */
     uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -495,6 +497,8 @@ ovhip_stream_destroy(ovhip_stream *s)
     free(s->rgb_luts);
     for (int k = 0; s->surf_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->surf_luts[k]);
     free(s->surf_luts);
+    for (int k = 0; s->ladder_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->ladder_luts[k]);
+    free(s->ladder_luts);
     free(s->ph);
     for (uint32_t i = 0; s->job_mtx && i < s->n_jobs; ++i) pthread_mutex_destroy(&s->job_mtx[i]);
     free(s->frames); free(s->out_ctx); free(s->job_mtx);
@@ -692,6 +696,41 @@ ovhip_stream_set_surface_lut(ovhip_stream *s, const ovhip_surface_conv *conv, in
 }
 
 int
+ovhip_stream_set_ladder_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table)
+{
+    if (!s) return OVHIP_EINVAL;
+    ovhip_rgb_lut **luts = NULL;
+    int r = OVHIP_OK;
+    if (host_table) {
+        if ((r = ovhip_surface_conv_check_(conv, NULL)) != OVHIP_OK) return r;    /* (before anything is uploaded) */
+        /* the ladder of the following runs, if set: its rungs through this table, the conversion reading its sample location */
+        if (s->ladder_on) {
+            int32_t w, h;
+            out_size(s, &w, &h);
+            if ((r = ovhip_ladder_lut_check(w, h, &s->ladder_info, s->ladder, s->ladder_n, conv, size, peak, NULL)) != OVHIP_OK) return r;
+        }
+        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
+        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
+        if (!luts) return OVHIP_ENOMEM;
+        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
+        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_ladder_lut(s->frames[i], luts[i / s->tpd], conv);
+        if (r != OVHIP_OK) {
+            /* the previous setting stands */
+            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_ladder_lut(s->frames[i], s->ladder_luts ? s->ladder_luts[i / s->tpd] : NULL, &s->ladder_conv);
+            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
+            free(luts);
+            return r;
+        }
+        s->ladder_conv = *conv;
+    } else
+        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_ladder_lut(s->frames[i], NULL, NULL);
+    for (int k = 0; s->ladder_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->ladder_luts[k]);
+    free(s->ladder_luts);
+    s->ladder_luts = luts;
+    return OVHIP_OK;
+}
+
+int
 ovhip_stream_set_surface_output(ovhip_stream *s, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_base, size_t bytes_per_picture, uint32_t n_slots)
 {
     if (!s) return OVHIP_EINVAL;
@@ -715,7 +754,9 @@ ovhip_stream_set_ladder_output(ovhip_stream *s, const ovhip_reduce_info *info, c
     memset(&ri, 0, sizeof(ri));
     if (info) ri = *info;
     out_size(s, &w, &h);
-    const int r = ovhip_ladder_check(w, h, &ri, rungs, n, NULL);
+    /* with a table set, the table's share too: the location the conversion reads, rung sizes in multiples of 4 */
+    const int r = s->ladder_luts ? ovhip_ladder_lut_check(w, h, &ri, rungs, n, &s->ladder_conv, s->ladder_luts[0]->size, s->ladder_luts[0]->peak, NULL)
+                                 : ovhip_ladder_check(w, h, &ri, rungs, n, NULL);
     if (r != OVHIP_OK) return r;
     slot_buf bufs[OVHIP_LADDER_MAX_RUNGS];
     for (int32_t k = 0; k < n; ++k)

@@ -1,5 +1,6 @@
 // reduce_walk.hip.h -- the walk of the reduced-size output over one tile of one plane, shared by k_output_reduce (kernels_reduce.hip:
-// the tile leaves as 16-bit samples of a picture) and k_output_ladder (kernels_ladder.hip: the tile leaves as a surface's elements).
+// the tile leaves as 16-bit samples of a picture), k_output_ladder (kernels_ladder.hip: the tile leaves as a surface's elements) and
+// k_ladder_lut (kernels_ladder_lut.hip: the tiles of a rung's Y, Cb and Cr stay in LDS for the colour conversion).
 // Definition: include/ovvc_hip.h, "Reduced-size output on the device"; the arithmetic both sides of the library agree on:
 // ovvc_reduce_priv.h.
 //
@@ -74,18 +75,46 @@ __device__ __forceinline__ uint4 stage_load(const uint16_t *row, bool valid, int
     return make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
 }
 
-// The tile t into s_out (every lane's column: a lane past the plane's width repeats the last column), then epi(k0, k1, ka, kb): the
-// tile's columns k0 .. k1 and rows ka .. kb - 1 of the destination plane, behind a barrier, so the epilogue may read all of s_out.
+// where a walk's columns and rows lie in the destination plane, and who walks.  RdGrid: tile (t.tx, t.ty) of the grid of 64 x RD_BAND
+// tiles, by a workgroup of one wave.  RdAt: columns k0 .. k1 (at most RD_TW of them) and rows ka .. kb - 1 (at most RD_BAND) wherever the
+// caller puts them -- k_ladder_lut's tiles carry a halo, so their origins are no multiples of the tile; t.tx and t.ty are not read
+// then --, by ONE WAVE of a larger workgroup, with s_row and s_out of its own: its lanes wait for one another only (the fences order its
+// LDS writes and reads as __syncthreads' do, without the workgroup's barrier), so the waves of a workgroup walk different tiles at once.
+struct RdGrid {
+    __device__ __forceinline__ int lane() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    __device__ __forceinline__ int k0(const RdTile &t) const { return t.tx * RD_TW; }
+    __device__ __forceinline__ int k1(const RdTile &t, int k0) const { return min(k0 + RD_TW, t.dw) - 1; }
+    __device__ __forceinline__ int ka(const RdTile &t) const { return t.ty * RD_BAND; }
+    __device__ __forceinline__ int kb(const RdTile &t, int ka) const { return min(ka + RD_BAND, t.dh); }
+};
+struct RdAt {
+    int c0, c1, ra, rb;
+    __device__ __forceinline__ int lane() const { return (int)threadIdx.x & (RD_NT - 1); }
+    __device__ __forceinline__ void sync() const
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    __device__ __forceinline__ int k0(const RdTile &) const { return c0; }
+    __device__ __forceinline__ int k1(const RdTile &, int) const { return c1; }
+    __device__ __forceinline__ int ka(const RdTile &) const { return ra; }
+    __device__ __forceinline__ int kb(const RdTile &, int) const { return rb; }
+};
+
+// The columns and rows `at` names into s_out (every lane's column: a lane past the last column repeats it), then epi(k0, k1, ka, kb):
+// columns k0 .. k1 and rows ka .. kb - 1 of the destination plane, behind at.sync(), so the epilogue may read all of s_out.
 // s_row is free again when the epilogue runs.
-template <class Epi>
-__device__ __forceinline__ void rd_walk(const RdTile &t, uint16_t (*s_row)[RD_LDS], uint16_t (*s_out)[RD_TW], Epi epi)
+template <class At, class Epi>
+__device__ __forceinline__ void rd_walk_at(const RdTile &t, const At at, uint16_t (*s_row)[RD_LDS], uint16_t (*s_out)[RD_TW], Epi epi)
 {
-    const int lane = (int)threadIdx.x;
+    const int lane = at.lane();
     const int px = t.px, qx = t.qx, py = t.py, qy = t.qy;
     const int rows = t.rows, cpr = t.cpr, rstride = cpr * RD_CHUNK + RD_SLACK;
 
     // this lane's column: its first sample and its weights (a lane past the plane's width works on the last column and stores nothing)
-    const int k0 = t.tx * RD_TW, k1 = min(k0 + RD_TW, t.dw) - 1;
+    const int k0 = at.k0(t), k1 = at.k1(t, k0);
     const int kx = min(k0 + lane, k1);
     const int jb = ovhip_reduce_first_(kx, px, qx, t.sgx, t.sw);
     int w[RD_TAPS];
@@ -93,7 +122,7 @@ __device__ __forceinline__ void rd_walk(const RdTile &t, uint16_t (*s_row)[RD_LD
     for (int i = 0; i < RD_TAPS; ++i) w[i] = jb + i < t.sw ? ovhip_reduce_weight_(kx, jb + i, px, qx, t.sgx, t.sw) : 0;
     const int xs = ovhip_reduce_first_(k0, px, qx, t.sgx, t.sw), xe = ovhip_reduce_last_(k1, px, qx, t.sgx, t.sw);
 
-    const int ka = t.ty * RD_BAND, kb = min(ka + RD_BAND, t.dh);
+    const int ka = at.ka(t), kb = at.kb(t, ka);
     const int ys = ovhip_reduce_first_(ka, py, qy, t.sgy, t.sh), ye = ovhip_reduce_last_(kb - 1, py, qy, t.sgy, t.sh);
 
     // this lane's chunk slots: row of the group and chunk of that row, the same for every group
@@ -114,7 +143,7 @@ __device__ __forceinline__ void rd_walk(const RdTile &t, uint16_t (*s_row)[RD_LD
 #pragma unroll
         for (int c = 0; c < RD_NCH; ++c)
             if (sr[c] < rows) *reinterpret_cast<uint4 *>(s + sr[c] * rstride + RD_CHUNK * sc[c]) = v[c];
-        __syncthreads();
+        at.sync();
 #pragma unroll
         for (int c = 0; c < RD_NCH; ++c) {                      // the next group's loads fly while this group is summed
             const int y = jy + rows + sr[c];
@@ -139,8 +168,15 @@ __device__ __forceinline__ void rd_walk(const RdTile &t, uint16_t (*s_row)[RD_LD
         }
         buf ^= 1;
     }
-    __syncthreads();
+    at.sync();
     epi(k0, k1, ka, kb);
+}
+
+// the tile (t.tx, t.ty) of the destination plane
+template <class Epi>
+__device__ __forceinline__ void rd_walk(const RdTile &t, uint16_t (*s_row)[RD_LDS], uint16_t (*s_out)[RD_TW], Epi epi)
+{
+    rd_walk_at(t, RdGrid{}, s_row, s_out, epi);
 }
 
 } // namespace

@@ -122,6 +122,23 @@ def ladder_check(src_w: int, src_h: int, rungs, src_window=(0, 0, 0, 0), chroma_
     return r, [tuple(ratio[k]) for k in range(min(n, capi.LADDER_MAX_RUNGS))]
 
 
+def ladder_lut_check(src_w: int, src_h: int, rungs, conv: "capi.SurfaceConv | None", size: int, peak: int, src_window=(0, 0, 0, 0),
+                     chroma_loc: "int | None" = None) -> "tuple[int, list]":
+    """(code, [(p_x, q_x, p_y, q_y) per rung]) of ovhip_ladder_lut_check: whether src_w x src_h under src_window leaves as these rungs
+    converted by `conv` through a table of `size` points and peak `peak` (include/ovvc_hip.h, "Output ladder through a colour table").
+    chroma_loc None: conv's src_chroma_loc.  Host only."""
+    arr, n = _rung_array(rungs)
+    ratio = ((C.c_int32 * 4) * capi.LADDER_MAX_RUNGS)()
+    info = capi.ReduceInfo(capi.Window(*src_window), _ladder_loc(chroma_loc, conv))
+    r = capi.load().ovhip_ladder_lut_check(src_w, src_h, C.byref(info), arr, n, C.byref(conv) if conv is not None else None, size, peak, ratio)
+    return r, [tuple(ratio[k]) for k in range(min(n, capi.LADDER_MAX_RUNGS))]
+
+
+def _ladder_loc(chroma_loc: "int | None", conv: "capi.SurfaceConv | None") -> int:
+    """the ladder's chroma location: the one given, else the one the conversion reads (the reduced pictures keep it), else 0"""
+    return chroma_loc if chroma_loc is not None else (conv.src_chroma_loc if conv is not None else 0)
+
+
 def mvfield_format(dtype: int = capi.MVF_I32, layout: int = capi.MVF_PLANAR, vectors: int = capi.MVF_UNIT) -> capi.MvfieldFormat:
     """an ovhip_mvfield_format (include/ovvc_hip.h, "Motion field output on the device")"""
     return capi.MvfieldFormat(dtype, layout, vectors, 0)
@@ -713,10 +730,14 @@ class DevPic:
             self.ctx._chk(r, "surface_launch" if conv is None and lut is None else "surface_lut_launch")
         return r
 
-    def ladder(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0) -> "list[np.ndarray]":
+    def ladder(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, lut: "RgbLut | None" = None,
+               conv: "capi.SurfaceConv | None" = None) -> "list[np.ndarray]":
         """ovhip_pic_output_ladder: this picture as the rungs of a ladder (include/ovvc_hip.h, "Output ladder on the device"; each
         rung a ladder_rung() without a destination), written on the device by one launch and fetched -> the surfaces' bytes, one
-        array per rung (bytes a layout leaves out are 0)"""
+        array per rung (bytes a layout leaves out are 0).  lut and conv (surface_conv()): the rungs of the CONVERTED reduced pictures
+        (ovhip_pic_output_ladder_lut, "Output ladder through a colour table"); chroma_loc None: conv's src_chroma_loc, else 0"""
+        if (lut is None) != (conv is None):
+            raise EngineError("ladder: lut and conv go together")
         outs, full = [], []
         for g in rungs:
             n = self.ctx.lib.ovhip_surface_bytes(g.out_w, g.out_h, None, C.byref(g.fmt))
@@ -725,17 +746,27 @@ class DevPic:
             outs.append(np.zeros(n, np.uint8))
             full.append(ladder_rung(g.out_w, g.out_h, g.fmt, outs[-1].ctypes.data, n))
         arr, n = _rung_array(full)
-        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
-        self.ctx._chk(self.ctx.lib.ovhip_pic_output_ladder(self.ctx.h, C.byref(self.s), C.byref(info), arr, n), "pic_output_ladder")
+        info = capi.ReduceInfo(capi.Window(*src_window), _ladder_loc(chroma_loc, conv))
+        if lut is None:
+            self.ctx._chk(self.ctx.lib.ovhip_pic_output_ladder(self.ctx.h, C.byref(self.s), C.byref(info), arr, n), "pic_output_ladder")
+        else:
+            self.ctx._chk(self.ctx.lib.ovhip_pic_output_ladder_lut(self.ctx.h, C.byref(self.s), C.byref(info), arr, n, C.byref(conv), lut.h), "pic_output_ladder_lut")
         return outs
 
-    def ladder_into(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
-        """ovhip_ladder_launch: every rung (ladder_rung() with a torch tensor or a device address) written by one launch.  Asynchronous."""
+    def ladder_into(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, check: bool = True, lut: "RgbLut | None" = None,
+                    conv: "capi.SurfaceConv | None" = None) -> int:
+        """ovhip_ladder_launch: every rung (ladder_rung() with a torch tensor or a device address) written by one launch.  Asynchronous.
+        conv: ovhip_ladder_lut_launch with that conversion through the colour table `lut` (which may be None only to see the refusal);
+        chroma_loc None: conv's src_chroma_loc, else 0"""
         arr, n = _rung_array(rungs)
-        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
-        r = self.ctx.lib.ovhip_ladder_launch(self.ctx.h, C.byref(self.s), C.byref(info), arr, n)
+        info = capi.ReduceInfo(capi.Window(*src_window), _ladder_loc(chroma_loc, conv))
+        if conv is None and lut is None:
+            r = self.ctx.lib.ovhip_ladder_launch(self.ctx.h, C.byref(self.s), C.byref(info), arr, n)
+        else:
+            r = self.ctx.lib.ovhip_ladder_lut_launch(self.ctx.h, C.byref(self.s), C.byref(info), arr, n, C.byref(conv) if conv is not None else None,
+                                                     lut.h if lut is not None else None)
         if check:
-            self.ctx._chk(r, "ladder_launch")
+            self.ctx._chk(r, "ladder_launch" if conv is None and lut is None else "ladder_lut_launch")
         return r
 
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
@@ -1242,6 +1273,17 @@ class Frame:
             self._surface_lut = lut
         return r
 
+    def set_ladder_lut(self, lut: "RgbLut | None", conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
+        """ovhip_frame_set_ladder_lut: while set, the rungs of this frame's ladder output are those of the reduced pictures converted
+        by `conv` (surface_conv()) through the colour table (sticky, unlike the rungs; kept alive here; independent of set_rgb_lut
+        and set_surface_lut); None: off"""
+        r = self.lib.ovhip_frame_set_ladder_lut(self.f, lut.h if lut is not None else None, C.byref(conv) if conv is not None else None)
+        if check and r:
+            raise EngineError(f"frame_set_ladder_lut: {r}")
+        if r == 0:
+            self._ladder_lut = lut
+        return r
+
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_surface_output: the NEXT picture completed is also written as a surface into `dst` -- a contiguous torch
         tensor on the device (uint8, or int16 / uint16 for the 16-bit formats) of at least the surface's bytes for the size the frame
@@ -1376,6 +1418,19 @@ class Stream:
             r = self.lib.ovhip_stream_set_surface_lut(self.s, C.byref(conv) if conv is not None else None, size, int(peak), table.ctypes.data)
         if check and r:
             raise EngineError(f"stream_set_surface_lut: {r}")
+        return r
+
+    def set_ladder_lut(self, table: "np.ndarray | None", peak: int = 0, conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_ladder_lut: the ladder output of the following runs is that of the reduced pictures converted by `conv`
+        (surface_conv()) through the colour table (numpy uint16 of shape (S, S, S, 3), uploaded once per device, owned by the
+        stream); None: off"""
+        if table is None:
+            r = self.lib.ovhip_stream_set_ladder_lut(self.s, None, 0, 0, None)
+        else:
+            table, size = _lut_table(table, "stream_set_ladder_lut")
+            r = self.lib.ovhip_stream_set_ladder_lut(self.s, C.byref(conv) if conv is not None else None, size, int(peak), table.ctypes.data)
+        if check and r:
+            raise EngineError(f"stream_set_ladder_lut: {r}")
         return r
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
