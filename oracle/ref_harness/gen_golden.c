@@ -2541,6 +2541,24 @@ flt_pics_for(int alf, int log2_ctu)
     return alf ? &al[log2_ctu - 5] : &sao[log2_ctu - 5];
 }
 
+/* SAO of a whole picture (one rect entry): call order of decode_ctu_line / decode_ctu_last_line (slicedec.c:934-956, :1058-1073) */
+static void
+sao_filter_picture(OVCTUDec *c, struct RectEntryInfo *einfo, int ny)
+{
+    for (int cy = 0; cy < ny; ++cy) {
+        c->ctb_y = cy;
+        if (cy == 0) {
+            TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_first_pix_rows(c, einfo, 0));
+            if (ny == 1) TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, einfo, 0));
+        } else if (cy == ny - 1) {
+            TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, einfo, cy - 1));
+            TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, einfo, cy));
+        } else {
+            TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, einfo, cy - 1));
+        }
+    }
+}
+
 static void
 gen_sao(const char *dir, int log2_ctu)
 {
@@ -2589,19 +2607,7 @@ gen_sao(const char *dir, int log2_ctu)
         struct RectEntryInfo einfo;
         memset(&einfo, 0, sizeof(einfo));
         einfo.nb_ctu_w = nx; einfo.nb_ctu_h = ny;
-        /* call order of decode_ctu_line / decode_ctu_last_line (slicedec.c:934-956, :1058-1073) */
-        for (int cy = 0; cy < ny; ++cy) {
-            c->ctb_y = cy;
-            if (cy == 0) {
-                TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_first_pix_rows(c, &einfo, 0));
-                if (ny == 1) TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, &einfo, 0));
-            } else if (cy == ny - 1) {
-                TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, &einfo, cy - 1));
-                TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, &einfo, cy));
-            } else {
-                TIMED(TS_SAO, c->rcn_funcs.sao.rcn_sao_filter_line(c, &einfo, cy - 1));
-            }
-        }
+        sao_filter_picture(c, &einfo, ny);
         if (g_shim) {
             size_t nc = 0;
             const ovhip_sao_ctu *sp = ovhip_shim_sao_params(c, &nc);
@@ -2780,6 +2786,613 @@ gen_alf(const char *dir, int log2_ctu)
     }
     g_part.log2_ctu_s = 7;
     gfile_close(&g);
+}
+
+/* ====================================================================================== SAO and ALF: enumerated cells
+ * sao_cells_<family>_NN.ovg / alf_cells_<family>_NN.ovg: one picture a file, in the layout of sao.ovg / alf.ovg (p0_*) plus
+ * "log2_ctu"; the expected planes are the reference's, through the slots and the call order of gen_sao / gen_alf.  What the
+ * families have to reach is asserted from tests/filter_census.py (tests/test_oracle_golden.py); the generator only draws content
+ * and parameters so that they do.
+ *   sao    equal runs, plateaus, two-level steps and both ends of the sample range beside noise; distinct offsets up to +-31;
+ *          every band position; pictures with a ragged last group of 8 in luma and chroma, a truncated last CTU row, one of a
+ *          single CTU row; CTU 128, 64 and 32
+ *   class  16x16 patches of curved surfaces, drawn, classified (the generator's own fc_block_sums / fc_class) and kept while a
+ *          (class, transpose) pair still lacks blocks -- on a fixed filter set and on an APS set apart, and among the blocks at a
+ *          virtual boundary every activity class, direction class and transpose; every luma_set value
+ *   edge   patches moved sample by sample (a local search from such a surface) until the 4x4 block at their centre has a given
+ *          act, a sum_h + sum_v on either side of an activity threshold, or one of the five ties of alf_derive_filter_idx -- on
+ *          plain blocks and on blocks at a virtual boundary; the all-zero block; the largest sums (0 / 1023 checkerboard, stripes)
+ *   taps   APS sets built for the purpose (see alf_cells_taps) on the content of the sao family */
+static void
+fcell_put_planes(gfile *g, const char *what, const OVFrame *f, int W, int H)
+{
+    char nm[32];
+    uint32_t d2[2] = { H, W };
+    snprintf(nm, 32, "p0_%s_y", what); gfile_array(g, nm, T_U16, f->data[0], 2, d2);
+    d2[0] = H / 2; d2[1] = W / 2;
+    snprintf(nm, 32, "p0_%s_cb", what); gfile_array(g, nm, T_U16, f->data[1], 2, d2);
+    snprintf(nm, 32, "p0_%s_cr", what); gfile_array(g, nm, T_U16, f->data[2], 2, d2);
+}
+
+/* cells of cs x cs samples, each of one kind of content */
+static void
+fcell_fill_plane(uint16_t *p, int w, int h, int cs)
+{
+    for (int cy = 0; cy < h; cy += cs)
+        for (int cx = 0; cx < w; cx += cs) {
+            const int mode = rnd_range(0, 7), base = rnd_range(3, 1019), step = rnd_range(1, 3);
+            for (int y = cy; y < cy + cs && y < h; ++y)
+                for (int x = cx; x < cx + cs && x < w; ++x) {
+                    int v;
+                    switch (mode) {
+                    case 2: v = base + rnd_range(0, 1); break;                                          /* two levels */
+                    case 3: v = ((x | y) & 1) ? p[(y & ~1) * w + (x & ~1)] : rnd_range(0, 1023); break; /* 2x2 plateaus */
+                    case 4: v = (x & 3) ? p[y * w + x - 1] : rnd_range(0, 1023); break;                 /* runs of four */
+                    case 5: v = rnd_range(0, 24); break;                                                /* the ends of the range */
+                    case 6: v = 1023 - rnd_range(0, 24); break;
+                    case 7: v = base + rnd_range(-step, step); break;
+                    default: v = rnd_range(0, 1023); break;
+                    }
+                    p[y * w + x] = (uint16_t)v;
+                }
+        }
+}
+
+static OVFrame *
+fcell_frame(int w, int h)
+{
+    OVFrame *f = ref_new_picture(w, h, 0)->frame;
+    fcell_fill_plane((uint16_t *)f->data[0], w, h, 8);
+    fcell_fill_plane((uint16_t *)f->data[1], w / 2, h / 2, 4);
+    fcell_fill_plane((uint16_t *)f->data[2], w / 2, h / 2, 4);
+    return f;
+}
+
+/* a picture cut into rect entries (tiles): the CTU columns col[k] .. col[k + 1] and rows row[k] .. row[k + 1]; NULL: one entry.  The
+ * reference's line drivers run once per entry with that entry's RectEntryInfo and entry-local parameter arrays, one entry after
+ * the other on one OVCTUDec, as the slice decoder calls them (slicedec.c:636-657); is_border comes from the entry-local CTU index. */
+struct fcell_cut { int nc, nr, col[4], row[4]; };
+static int
+fcell_border(const struct fcell_cut *cut, int cx, int cy)
+{
+    int b = 0;
+    if (!cut) return 0;
+    for (int k = 0; k < cut->nc; ++k) { if (cx == cut->col[k]) b |= OVHIP_BORDER_LEFT; if (cx == cut->col[k + 1] - 1) b |= OVHIP_BORDER_RIGHT; }
+    for (int k = 0; k < cut->nr; ++k) {
+        if (cy == cut->row[k]) b |= OVHIP_BORDER_UPPER;
+        if (cy == cut->row[k + 1] - 1) b |= OVHIP_BORDER_BOTTOM;
+        if (cy == cut->row[k] && cut->row[k + 1] - cut->row[k] == 1) b |= OVHIP_BORDER_ONE_ROW;
+    }
+    return b;
+}
+
+static void
+sao_cells_picture(const char *dir, const char *name, int W, int H, int log2_ctu, const struct fcell_cut *cut)
+{
+    const int ctu = 1 << log2_ctu, nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu, n = nx * ny;
+    gfile g = gfile_open(dir, name);
+    g_part.log2_ctu_s = log2_ctu;
+    OVFrame *f = fcell_frame(W, H);
+    OVCTUDec *c = ref_new_ctudec(0, 0);
+    c->pic_w = W; c->pic_h = H;
+    c->rcn_ctx.frame_start = f;
+    harness_alloc_filter_buffers(&c->rcn_ctx, nx, 3, log2_ctu);
+    c->sao_info.sao_luma_flag = 1; c->sao_info.sao_chroma_flag = 1; c->sao_info.chroma_format_idc = 1;
+    SAOParamsCtu *prm = calloc(n, sizeof(*prm));
+    ovhip_sao_ctu *mine = calloc(n, sizeof(*mine));
+    c->sao_info.sao_params = prm;
+    /* few CTUs: every second one edge, one off, the rest band; many: every third one edge.  The edge classes and the band positions
+     * run on from CTU to CTU, shifted per plane; the offsets are all different, with +-31 at the ends, in both sign patterns */
+    int n_band[3] = { 0, 0, 0 }, n_edge[3] = { 0, 0, 0 };
+    for (int i = 0; i < n; ++i)
+        for (int comp = 0; comp < 3; ++comp) {
+            const int t = n < 12 ? (i % 2 == 0 ? 2 : i == 3 ? 0 : 1) : (i % 3 == 0 ? 2 : 1), s = ((i + comp) & 1) ? 1 : -1;
+            static const int16_t band[4] = { 31, -31, 17, -9 }, edge[5] = { 31, -23, 0, 13, -31 };
+            prm[i].type_idx[comp] = t;
+            prm[i].band_position[comp] = (29 + 11 * comp + n_band[comp]) & 31;
+            prm[i].eo_class[comp] = (n_edge[comp] + comp + (ny == 1)) & 3;          /* (a single CTU row: luma not horizontal, for the 6-row quirk) */
+            n_band[comp] += t == 1; n_edge[comp] += t == 2;
+            for (int k = 0; k < 5; ++k) prm[i].offset_val[comp][k] = (int16_t)(s * (t == 2 ? edge[k] : k < 4 ? band[k] : 0));
+            mine[i].type[comp] = t; mine[i].band_position[comp] = prm[i].band_position[comp];
+            mine[i].eo_class[comp] = prm[i].eo_class[comp];
+            memcpy(mine[i].offset_val[comp], prm[i].offset_val[comp], 10);
+            if (t == 1) {
+                /* a band CTU holds a sample of each of its four bands, wherever else its content lies */
+                const int sh = comp ? 1 : 0, cs = ctu >> sh, pw = W >> sh, ph = H >> sh, x0 = (i % nx) * cs, y0 = (i / nx) * cs;
+                for (int k = 0; k < 4; ++k) {
+                    const int x = x0 + rnd_range(0, (x0 + cs < pw ? cs : pw - x0) - 1), y = y0 + rnd_range(0, (y0 + cs < ph ? cs : ph - y0) - 1);
+                    ((uint16_t *)f->data[comp])[y * pw + x] = (uint16_t)((((prm[i].band_position[comp] + k) & 31) << 5) + rnd_range(0, 31));
+                }
+            }
+        }
+    fcell_put_planes(&g, "in", f, W, H);
+    struct RectEntryInfo einfo;
+    memset(&einfo, 0, sizeof(einfo));
+    einfo.nb_ctu_w = nx; einfo.nb_ctu_h = ny;
+    if (!cut) sao_filter_picture(c, &einfo, ny);
+    else
+        for (int er = 0; er < cut->nr; ++er)
+            for (int ec = 0; ec < cut->nc; ++ec) {
+                einfo.ctb_x = cut->col[ec]; einfo.ctb_y = cut->row[er];
+                einfo.nb_ctu_w = cut->col[ec + 1] - cut->col[ec]; einfo.nb_ctu_h = cut->row[er + 1] - cut->row[er];
+                SAOParamsCtu *loc = calloc(einfo.nb_ctu_w * einfo.nb_ctu_h, sizeof(*loc));
+                for (int y = 0; y < einfo.nb_ctu_h; ++y)
+                    for (int x = 0; x < einfo.nb_ctu_w; ++x) {
+                        loc[y * einfo.nb_ctu_w + x] = prm[(einfo.ctb_y + y) * nx + einfo.ctb_x + x];
+                        mine[(einfo.ctb_y + y) * nx + einfo.ctb_x + x].border = fcell_border(cut, einfo.ctb_x + x, einfo.ctb_y + y);
+                    }
+                c->sao_info.sao_params = loc;
+                sao_filter_picture(c, &einfo, einfo.nb_ctu_h);
+            }
+    fcell_put_planes(&g, "exp", f, W, H);
+    uint32_t d2[2] = { n, sizeof(ovhip_sao_ctu) }, d1 = 1;
+    int32_t l2 = log2_ctu;
+    gfile_array(&g, "p0_params", T_U8, mine, 2, d2);
+    gfile_array(&g, "log2_ctu", T_I32, &l2, 1, &d1);
+    fprintf(stderr, "%s: %dx%d (%d CTUs of %d)\n", name, W, H, n, ctu);
+    g_part.log2_ctu_s = 7;
+    gfile_close(&g);
+}
+
+static void
+gen_sao_cells(const char *dir)
+{
+    g_seed = 0x266 + 13;
+    sao_cells_picture(dir, "sao_cells_sao_00.ovg", 300, 264, 7, NULL);       /* 3 x 3 CTUs, the last row 8 rows high; 300 and 150: ragged groups */
+    sao_cells_picture(dir, "sao_cells_sao_01.ovg", 140, 72, 7, NULL);        /* a single CTU row (the 6-row quirk) */
+    sao_cells_picture(dir, "sao_cells_sao64_00.ovg", 300, 200, 6, NULL);
+    sao_cells_picture(dir, "sao_cells_sao32_00.ovg", 252, 172, 5, NULL);     /* 8 x 6 CTUs: 32 band CTUs a plane, one per band position */
+    /* 2 x 2 rect entries: 5 x 4 CTUs of 64 cut into columns of 3 and 2 and rows of 1 (an entry a single CTU row high) and 3 */
+    static const struct fcell_cut cut = { 2, 2, { 0, 3, 5 }, { 0, 1, 4 } };
+    sao_cells_picture(dir, "sao_cells_entry64_00.ovg", 300, 200, 6, &cut);
+}
+
+/* ---- ALF: the generator's own classification, to choose content by (the expected planes come from the reference alone) */
+/* Laplacian sums v, h, d, b of the 4x4 block at (bx, by); vb: picture row of the virtual boundary of the block's CTU */
+static int
+fc_block_sums(const uint16_t *p, int stride, int bx, int by, int vb, uint32_t s[4])
+{
+    int first = 0, last = 3, is_vb = 0;
+    if (by == vb - 4) { last = 2; is_vb = 1; }
+    if (by == vb)     { first = 1; is_vb = 1; }
+    s[0] = s[1] = s[2] = s[3] = 0;
+#define FP(x, y) ((int)p[(y) * stride + (x)])
+    for (int k = first; k <= last; ++k) {
+        const int r = by - 2 + 2 * k;
+        const int above = r == vb ? r : r - 1, below = r + 2 == vb ? r + 1 : r + 2;
+        for (int q = 0; q < 4; ++q) {
+            const int c0 = bx - 2 + 2 * q, c1 = c0 + 1, y1 = FP(c0, r) << 1, y2 = FP(c1, r + 1) << 1;
+            s[0] += abs(y1 - FP(c0, above) - FP(c0, r + 1)) + abs(y2 - FP(c1, r) - FP(c1, below));
+            s[1] += abs(y1 - FP(c0 + 1, r) - FP(c0 - 1, r)) + abs(y2 - FP(c1 + 1, r + 1) - FP(c1 - 1, r + 1));
+            s[2] += abs(y1 - FP(c0 - 1, above) - FP(c0 + 1, r + 1)) + abs(y2 - FP(c1 - 1, r) - FP(c1 + 1, below));
+            s[3] += abs(y1 - FP(c0 - 1, r + 1) - FP(c0 + 1, above)) + abs(y2 - FP(c1 - 1, below) - FP(c1 + 1, r));
+        }
+    }
+#undef FP
+    return is_vb;
+}
+
+struct fc_cls { int act, cls, tr; uint64_t max_dir, min_dir, cross_a, cross_b; };
+static struct fc_cls
+fc_class(const uint32_t s[4], int is_vb)
+{
+    static const int th[16] = { 0, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 3, 4 }, tr_lut[8] = { 0, 1, 0, 2, 2, 3, 1, 3 };
+    const uint64_t sv = s[0], sh = s[1], sd = s[2], sb = s[3];
+    struct fc_cls o;
+    const uint64_t a = ((sh + sv) * (is_vb ? 96 : 64)) >> 14;
+    o.act = a > 15 ? 15 : (int)a;
+    const uint64_t max_hv = sv > sh ? sv : sh, min_hv = sv > sh ? sh : sv, max_db = sd > sb ? sd : sb, min_db = sd > sb ? sb : sd;
+    const int dir_hv = sv > sh ? 1 : 3, dir_db = sd > sb ? 0 : 2;
+    o.cross_a = max_db * min_hv; o.cross_b = max_hv * min_db;
+    const int db = o.cross_a > o.cross_b, main_dir = db ? dir_db : dir_hv, sec_dir = db ? dir_hv : dir_db;
+    o.max_dir = db ? max_db : max_hv; o.min_dir = db ? min_db : min_hv;
+    o.cls = th[o.act];
+    if (o.max_dir * 2 > 9 * o.min_dir) o.cls += (((main_dir & 1) << 1) + 2) * 5;
+    else if (o.max_dir > 2 * o.min_dir) o.cls += (((main_dir & 1) << 1) + 1) * 5;
+    o.tr = tr_lut[(main_dir << 1) + (sec_dir >> 1)];
+    return o;
+}
+
+/* a 16x16 patch of base + (2 a x^2 + 2 b y^2 + c (x + y)^2 + e (x - y)^2) / 64 + noise (+ a wave), x and y from the patch's centre */
+static void
+fc_surface(uint16_t *p, int stride, int amp, int noise)
+{
+    int k[4];
+    for (int i = 0; i < 4; ++i) k[i] = rnd_range(0, 1) ? rnd_range(-amp, amp) : 0;
+    const int base = rnd_range(300, 700);
+    /* every other patch: one or two triangle waves of period 4 across one of the four directions on top (high activity that keeps a direction) */
+    static const int tri[4] = { 0, 1, 2, 1 }, dirs[4][2] = { { 1, 0 }, { 0, 1 }, { 1, 1 }, { 1, 3 } };
+    const int wmax = amp < 8 ? 8 : amp > 160 ? 160 : amp;
+    const int wave = rnd_range(0, 1) ? rnd_range(1, wmax) : 0, wd = rnd_range(0, 3), wave2 = wave && rnd_range(0, 1) ? rnd_range(1, wmax) : 0, wd2 = rnd_range(0, 3);
+    for (int y = 0; y < 16; ++y)
+        for (int x = 0; x < 16; ++x) {
+            const int X = x - 8, Y = y - 8;
+            int v = base + (2 * k[0] * X * X + 2 * k[1] * Y * Y + k[2] * (X + Y) * (X + Y) + k[3] * (X - Y) * (X - Y)) / 64 + rnd_range(-noise, noise)
+                    + wave * tri[(dirs[wd][0] * x + dirs[wd][1] * y) & 3] + wave2 * tri[(dirs[wd2][0] * x + dirs[wd2][1] * y + 1) & 3];
+            p[y * stride + x] = (uint16_t)(v < 0 ? 0 : v > 1023 ? 1023 : v);
+        }
+}
+static void
+fc_draw_surface(uint16_t *p, int stride)
+{
+    static const int amps[10] = { 1, 2, 4, 8, 16, 32, 64, 128, 256, 512 }, noises[12] = { 0, 0, 0, 1, 1, 2, 3, 5, 8, 13, 21, 34 };
+    fc_surface(p, stride, amps[rnd_range(0, 9)], noises[rnd_range(0, 11)]);
+}
+
+/* the slots of the 16x16 patches: columns 4 + 16 i; in every CTU row of full height rows 4 + 16 k up to the one that ends at ctu - 12,
+ * then one at ctu - 12 whose inner blocks are the two at the virtual boundary (rows ctu - 8 and ctu - 4) */
+struct fc_slot { int x, y, vb; };                    /* vb: the slot at a virtual boundary */
+static int
+fc_slots(struct fc_slot *out, int W, int H, int ctu)
+{
+    int n = 0;
+    for (int b = 0; b + ctu <= H; b += ctu)
+        for (int k = 0; k <= (ctu - 16) / 16; ++k) {
+            const int y = b + (k < (ctu - 16) / 16 ? 4 + 16 * k : ctu - 12), vb = k == (ctu - 16) / 16;
+            if (y + 16 > H) continue;
+            for (int x = 4; x + 16 <= W; x += 16) { out[n].x = x; out[n].y = y; out[n].vb = vb; ++n; }
+        }
+    return n;
+}
+
+/* ALF of a whole picture with the tables of aps[5] (two luma sets, chroma, CC Cb, CC Cr) and the CTU parameters of `mine`; writes the file */
+static void
+alf_cells_write(const char *dir, const char *name, OVFrame *f, int W, int H, int log2_ctu, OVALFData *aps, ovhip_alf_ctu *mine, const struct fcell_cut *cut)
+{
+    const int ctu = 1 << log2_ctu, nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu, n = nx * ny;
+    gfile g = gfile_open(dir, name);
+    g_part.log2_ctu_s = log2_ctu;
+    fcell_put_planes(&g, "in", f, W, H);
+    OVCTUDec *c = ref_new_ctudec(0, 0);
+    c->pic_w = W; c->pic_h = H;
+    c->rcn_ctx.frame_start = f;
+    harness_alloc_filter_buffers(&c->rcn_ctx, nx, 3, log2_ctu);
+    struct ALFInfo *ai = &c->alf_info;
+    ai->alf_luma_enabled_flag = ai->alf_cb_enabled_flag = ai->alf_cr_enabled_flag = 1;
+    ai->cc_alf_cb_enabled_flag = ai->cc_alf_cr_enabled_flag = 1;
+    ai->num_alf_aps_ids_luma = 2;
+    ai->aps_alf_data[0] = &aps[0]; ai->aps_alf_data[1] = &aps[1];
+    ai->aps_alf_data_c = &aps[2]; ai->aps_cc_alf_data_cb = &aps[3]; ai->aps_cc_alf_data_cr = &aps[4];
+    ai->ctb_alf_params = calloc(n, sizeof(ALFParamsCtu));
+    ai->ctb_cc_alf_filter_idx[0] = calloc(n, 1); ai->ctb_cc_alf_filter_idx[1] = calloc(n, 1);
+    c->rcn_funcs.alf.rcn_alf_reconstruct_coeff_APS(&ai->rcn_alf, c, 1, 1);
+    static const struct fcell_cut whole = { 1, 1 };
+    struct fcell_cut one = whole;
+    one.col[1] = nx; one.row[1] = ny;
+    const struct fcell_cut *ct = cut ? cut : &one;
+    for (int er = 0; er < ct->nr; ++er)
+        for (int ec = 0; ec < ct->nc; ++ec) {
+            struct RectEntryInfo einfo;
+            memset(&einfo, 0, sizeof(einfo));
+            einfo.ctb_x = ct->col[ec]; einfo.ctb_y = ct->row[er];
+            einfo.nb_ctu_w = ct->col[ec + 1] - ct->col[ec]; einfo.nb_ctu_h = ct->row[er + 1] - ct->row[er];
+            /* the parameter arrays are entry-local */
+            for (int y = 0; y < einfo.nb_ctu_h; ++y)
+                for (int x = 0; x < einfo.nb_ctu_w; ++x) {
+                    ovhip_alf_ctu *m = &mine[(einfo.ctb_y + y) * nx + einfo.ctb_x + x];
+                    const int i = y * einfo.nb_ctu_w + x;
+                    ALFParamsCtu *p = &ai->ctb_alf_params[i];
+                    p->ctb_alf_flag = m->flags; p->ctb_alf_idx = m->luma_set;
+                    p->cb_alternative = m->cb_alt; p->cr_alternative = m->cr_alt;
+                    ai->ctb_cc_alf_filter_idx[0][i] = m->cc_cb_idx; ai->ctb_cc_alf_filter_idx[1][i] = m->cc_cr_idx;
+                    m->border = fcell_border(cut, einfo.ctb_x + x, einfo.ctb_y + y);
+                }
+            for (int cy = 0; cy < einfo.nb_ctu_h; ++cy) { c->ctb_y = cy; c->rcn_funcs.alf.rcn_alf_filter_line(c, &einfo, cy); }
+        }
+    fcell_put_planes(&g, "exp", f, W, H);
+    uint32_t d2[2] = { n, sizeof(ovhip_alf_ctu) }, d1 = 1;
+    gfile_array(&g, "p0_ctus", T_U8, mine, 2, d2);
+    d2[0] = 24; d2[1] = OVHIP_ALF_LUMA_SET_SIZE;
+    gfile_array(&g, "p0_luma_coeff", T_I16, ai->rcn_alf.filter_coeff_dec, 2, d2);
+    gfile_array(&g, "p0_luma_clip", T_I16, ai->rcn_alf.filter_clip_dec, 2, d2);
+    d2[0] = 8; d2[1] = 7;
+    gfile_array(&g, "p0_chroma_coeff", T_I16, ai->rcn_alf.chroma_coeff_final, 2, d2);
+    gfile_array(&g, "p0_chroma_clip", T_I16, ai->rcn_alf.chroma_clip_final, 2, d2);
+    int16_t cc[2][4][8];
+    memcpy(cc[0], aps[3].alf_cc_mapped_coeff[0], sizeof(cc[0]));
+    memcpy(cc[1], aps[4].alf_cc_mapped_coeff[1], sizeof(cc[1]));
+    uint32_t d3[3] = { 2, 4, 8 };
+    gfile_array(&g, "p0_cc_coeff", T_I16, cc, 3, d3);
+    int32_t l2 = log2_ctu;
+    gfile_array(&g, "log2_ctu", T_I32, &l2, 1, &d1);
+    fprintf(stderr, "%s: %dx%d (%d CTUs of %d)\n", name, W, H, n, ctu);
+    g_part.log2_ctu_s = 7;
+    gfile_close(&g);
+}
+
+/* the tables rcn_alf_reconstruct_coeff_APS builds from aps[0..1], to compare coefficient rows with */
+static const int16_t *
+fc_luma_rows(OVALFData *aps)
+{
+    static OVCTUDec *c;
+    if (!c) c = ref_new_ctudec(0, 0);
+    struct ALFInfo *ai = &c->alf_info;
+    ai->num_alf_aps_ids_luma = 2;
+    ai->aps_alf_data[0] = &aps[0]; ai->aps_alf_data[1] = &aps[1]; ai->aps_alf_data_c = &aps[2];
+    c->rcn_funcs.alf.rcn_alf_reconstruct_coeff_APS(&ai->rcn_alf, c, 1, 1);
+    return (const int16_t *)ai->rcn_alf.filter_coeff_dec;
+}
+/* the row of (set, cls, tr) differs from the rows of the other transposes, of the classes cls +- 1 in its group of five and cls +- 5 */
+static int
+fc_row_stands_out(const int16_t *t, int set, int cls, int tr)
+{
+#define ROW(c_, t_) (t + set * OVHIP_ALF_LUMA_SET_SIZE + (t_) * 25 * 13 + (c_) * 13)
+    const int16_t *own = ROW(cls, tr);
+    for (int k = 1; k < 4; ++k) if (!memcmp(own, ROW(cls, (tr + k) & 3), 24)) return 0;
+    if (cls % 5 > 0 && !memcmp(own, ROW(cls - 1, tr), 24)) return 0;
+    if (cls % 5 < 4 && !memcmp(own, ROW(cls + 1, tr), 24)) return 0;
+    if (cls >= 5 && !memcmp(own, ROW(cls - 5, tr), 24)) return 0;
+    if (cls < 20 && !memcmp(own, ROW(cls + 5, tr), 24)) return 0;
+#undef ROW
+    return 1;
+}
+
+/* APS sets whose 25 classes all have a filter of their own, the first linear, the second with clipping */
+static void
+alf_cells_class_aps(OVALFData *aps)
+{
+    for (int i = 0; i < 5; ++i) rand_alf_aps(&aps[i]);
+    for (int i = 0; i < 2; ++i) {
+        aps[i].alf_luma_num_filters_signalled_minus1 = 24;
+        aps[i].alf_luma_clip_flag = i;
+        for (int cl = 0; cl < 25; ++cl) aps[i].alf_luma_coeff_delta_idx[cl] = cl;
+    }
+}
+
+static void
+alf_cells_random_ctus(ovhip_alf_ctu *mine, int n, const OVALFData *aps)
+{
+    for (int i = 0; i < n; ++i) {
+        mine[i].flags = 4 | rnd_range(0, 3);
+        mine[i].cb_alt = rnd_range(0, aps[2].alf_chroma_num_alt_filters_minus1);
+        mine[i].cr_alt = rnd_range(0, aps[2].alf_chroma_num_alt_filters_minus1);
+        mine[i].cc_cb_idx = rnd_range(0, 4); mine[i].cc_cr_idx = rnd_range(0, 4);
+    }
+}
+
+enum { FC_MAX_SLOTS = 512 };
+/* blocks wanted per (kind of set, class, transpose): more where the activity is low, since a nearly flat block often filters alike under
+ * neighbouring classes and then does not count */
+#define FC_TARGET(cls) ((cls) % 5 == 0 ? 20 : (cls) % 5 == 1 ? 10 : 6)
+struct fc_need { int pair[2][25][4], vb_act[5], vb_dir[5], vb_tr[4]; };
+static int
+fc_need_open(const struct fc_need *nd)
+{
+    int open = 0;
+    for (int k = 0; k < 2; ++k) for (int cl = 0; cl < 25; ++cl) for (int t = 0; t < 4; ++t) open += nd->pair[k][cl][t] < FC_TARGET(cl);
+    for (int i = 0; i < 5; ++i) open += (nd->vb_act[i] < 2) + (nd->vb_dir[i] < 2);
+    for (int i = 0; i < 4; ++i) open += nd->vb_tr[i] < 2;
+    return open;
+}
+
+/* one picture of the class family: patches are drawn and kept while they add to what `nd` still lacks */
+static void
+alf_cells_class_picture(const char *dir, const char *name, int W, int H, int log2_ctu, int pic, struct fc_need *nd, int max_draws)
+{
+    const int ctu = 1 << log2_ctu, nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu, n = nx * ny;
+    static OVALFData aps[5];
+    alf_cells_class_aps(aps);
+    const int16_t *rows = fc_luma_rows(aps);
+    OVFrame *f = harness_frame(W, H);
+    uint16_t *py = (uint16_t *)f->data[0];
+    ovhip_alf_ctu *mine = calloc(n, sizeof(*mine));
+    alf_cells_random_ctus(mine, n, aps);
+    /* CTU 128: fixed and APS sets alternate, the fixed ones running on from picture to picture; CTU 64: every set in turn */
+    for (int i = 0; i < n; ++i) mine[i].luma_set = log2_ctu == 7 ? ((i + pic) & 1 ? 16 + ((i >> 1) & 1) : (pic * 5 + (i >> 1)) & 15) : i % 18;
+    static struct fc_slot slots[FC_MAX_SLOTS];
+    const int ns = fc_slots(slots, W, H, ctu);
+    if (ns > FC_MAX_SLOTS) { fprintf(stderr, "alf_cells: too many slots\n"); exit(1); }
+    uint8_t *taken = calloc(ns, 1);
+    int placed = 0;
+    uint16_t patch[256];
+    for (int draw = 0; draw < max_draws && placed < ns && fc_need_open(nd); ++draw) {
+        fc_draw_surface(patch, 16);
+        /* the four inner blocks' windows lie inside the patch: classified once as plain blocks, once as the blocks of a slot at a virtual
+         * boundary (rows 4 and 8 of the patch are the rows vb - 4 and vb) */
+        struct { int ok, cls, tr, is_vb; } blk[2][4];
+        for (int v = 0; v < 2; ++v)
+            for (int b = 0; b < 4; ++b) {
+                uint32_t s[4];
+                blk[v][b].is_vb = fc_block_sums(patch, 16, 4 + 4 * (b & 1), 4 + 4 * (b >> 1), v ? 8 : -1000, s);
+                const struct fc_cls k = fc_class(s, blk[v][b].is_vb);
+                /* a block whose diagonal sums (or the other two) are equal is mirror-symmetric as far as the classifier sees, and such
+                 * content often filters alike under two transposes: it is not counted */
+                blk[v][b].ok = s[0] != s[1] && s[2] != s[3]; blk[v][b].cls = k.cls; blk[v][b].tr = k.tr;
+            }
+        /* the first free slot that the patch adds something to; slots of one CTU and kind see it alike, so the first of each is asked */
+        for (int si = 0; si < ns; ++si) {
+            if (taken[si]) continue;
+            const struct fc_slot *sl = &slots[si];
+            int gain = 0, upd[4][4], nu = 0;
+            for (int b = 0; b < 4; ++b) {
+                const int bx = sl->x + 4 + 4 * (b & 1), by = sl->y + 4 + 4 * (b >> 1), set = mine[(by / ctu) * nx + bx / ctu].luma_set;
+                const int cls = blk[sl->vb][b].cls, tr = blk[sl->vb][b].tr, is_vb = blk[sl->vb][b].is_vb, kind = set >= 16;
+                if (!blk[sl->vb][b].ok || !fc_row_stands_out(rows, set, cls, tr)) continue;
+                if (!sl->vb && nd->pair[kind][cls][tr] < FC_TARGET(cls)) ++gain;             /* (the slots at a boundary are kept for what only they can add) */
+                if (is_vb && (nd->vb_act[cls % 5] < 2 || nd->vb_dir[cls / 5] < 2 || nd->vb_tr[tr] < 2)) ++gain;
+                upd[nu][0] = kind; upd[nu][1] = cls; upd[nu][2] = tr; upd[nu][3] = is_vb; ++nu;
+            }
+            /* early draws have to add several blocks, so that the slots last for the rare pairs */
+            if (gain >= (sl->vb ? 1 : draw < 30000 ? 3 : draw < 120000 ? 2 : 1)) {
+                for (int u = 0; u < nu; ++u) {
+                    ++nd->pair[upd[u][0]][upd[u][1]][upd[u][2]];
+                    if (upd[u][3]) { ++nd->vb_act[upd[u][1] % 5]; ++nd->vb_dir[upd[u][1] / 5]; ++nd->vb_tr[upd[u][2]]; }
+                }
+                for (int y = 0; y < 16; ++y) memcpy(py + (sl->y + y) * W + sl->x, patch + 16 * y, 32);
+                taken[si] = 1; ++placed;
+                break;
+            }
+            int sj = si + 1;
+            while (sj < ns && (taken[sj] || (slots[sj].vb == sl->vb && (slots[sj].y & ~(ctu - 1)) == (sl->y & ~(ctu - 1)) && (slots[sj].x + 4) / ctu == (sl->x + 4) / ctu))) ++sj;
+            si = sj - 1;
+        }
+    }
+    fprintf(stderr, "%s: %d of %d slots hold a kept patch, %d needs open\n", name, placed, ns, fc_need_open(nd));
+    alf_cells_write(dir, name, f, W, H, log2_ctu, aps, mine, NULL);
+}
+
+/* ---- edge family: a patch moved sample by sample until cost() of the block at its centre is 0 */
+enum { FE_HV, FE_TIE_VH, FE_TIE_DB, FE_TIE_CROSS, FE_TIE_9, FE_TIE_2 };
+static uint64_t
+fe_cost(const uint32_t s[4], int is_vb, int kind, int64_t target)
+{
+    const struct fc_cls k = fc_class(s, is_vb);
+    const uint64_t zero = (!s[0] || !s[1] || !s[2] || !s[3]) ? 1000 : 0;
+#define AD(a, b) ((a) > (b) ? (a) - (b) : (b) - (a))
+    switch (kind) {
+    case FE_HV: return AD((int64_t)s[0] + s[1], target);
+    case FE_TIE_VH: return AD(s[0], s[1]) + zero;
+    case FE_TIE_DB: return AD(s[2], s[3]) + zero;
+    case FE_TIE_CROSS: return AD(k.cross_a, k.cross_b) + zero + (s[0] == s[1]) + (s[2] == s[3]);
+    case FE_TIE_9: return AD(2 * k.max_dir, 9 * k.min_dir) + zero;
+    default: return AD(k.max_dir, 2 * k.min_dir) + zero;
+    }
+#undef AD
+}
+static void
+fe_search(uint16_t *py, int W, int ctu, const struct fc_slot *sl, int lower, int kind, int64_t target, const char *what)
+{
+    const int bx = sl->x + 4, by = sl->y + (lower ? 8 : 4), vb = (by & ~(ctu - 1)) + ctu - 4;
+    uint32_t s[4];
+    for (int attempt = 0; attempt < 64; ++attempt) {
+        static const int amps[4] = { 4, 16, 64, 256 };
+        fc_surface(py + sl->y * W + sl->x, W, kind == FE_HV ? (target < 600 ? 8 : target < 2000 ? 64 : 256) : amps[attempt & 3], kind == FE_HV ? (target < 300 ? 1 : 6) : 1 + (attempt & 3));
+        int is_vb = fc_block_sums(py, W, bx, by, vb, s);
+        uint64_t best = fe_cost(s, is_vb, kind, target);
+        for (int step = 0; step < 20000 && best; ++step) {
+            const int x = sl->x + rnd_range(0, 15), y = sl->y + rnd_range(0, 15), d = rnd_range(1, 3) * (rnd_range(0, 1) ? 1 : -1);
+            const int old = py[y * W + x], v = old + d;
+            if (v < 0 || v > 1023) continue;
+            py[y * W + x] = (uint16_t)v;
+            is_vb = fc_block_sums(py, W, bx, by, vb, s);
+            const uint64_t cost = fe_cost(s, is_vb, kind, target);
+            if (cost <= best) best = cost; else py[y * W + x] = (uint16_t)old;
+        }
+        if (!best) return;
+    }
+    fprintf(stderr, "alf_cells edge: no patch for %s\n", what);
+    exit(1);
+}
+
+static void
+alf_cells_edge_picture(const char *dir, const char *name, int W, int H)
+{
+    const int log2_ctu = 7, ctu = 128, nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu, n = nx * ny;
+    static OVALFData aps[5];
+    alf_cells_class_aps(aps);
+    OVFrame *f = harness_frame(W, H);
+    uint16_t *py = (uint16_t *)f->data[0];
+    ovhip_alf_ctu *mine = calloc(n, sizeof(*mine));
+    alf_cells_random_ctus(mine, n, aps);
+    for (int i = 0; i < n; ++i) mine[i].luma_set = (7 * i + 3) % 18;
+    static struct fc_slot slots[FC_MAX_SLOTS];
+    const int ns = fc_slots(slots, W, H, ctu);
+    int next[2] = { 0, 0 };
+    char what[64];
+    for (int vbk = 0; vbk < 2; ++vbk) {
+        static const int edges[2][8] = { { 255, 256, 511, 512, 1791, 1792, 3839, 3840 }, { 170, 171, 341, 342, 1194, 1195, 2559, 2560 } };
+#define FE_SLOT() ({ while (next[vbk] < ns && slots[next[vbk]].vb != vbk) ++next[vbk]; if (next[vbk] >= ns) { fprintf(stderr, "alf_cells edge: out of slots\n"); exit(1); } &slots[next[vbk]++]; })
+        int lower = 0;
+        for (int act = 0; act < 16; ++act, lower ^= vbk) {
+            /* the middle of the range of sum_h + sum_v that gives this act */
+            const int64_t lo = vbk ? (act * 16384 + 95) / 96 : act * 256, hi = act == 15 ? lo + 400 : vbk ? ((act + 1) * 16384 + 95) / 96 : (act + 1) * 256;
+            snprintf(what, 64, "act %d vb %d", act, vbk);
+            fe_search(py, W, ctu, FE_SLOT(), lower, FE_HV, (lo + hi) / 2, what);
+        }
+        for (int e = 0; e < 8; ++e, lower ^= vbk) {
+            snprintf(what, 64, "sum %d vb %d", edges[vbk][e], vbk);
+            fe_search(py, W, ctu, FE_SLOT(), lower, FE_HV, edges[vbk][e], what);
+        }
+        if (vbk) break;
+        for (int t = FE_TIE_VH; t <= FE_TIE_2; ++t) {
+            snprintf(what, 64, "tie %d", t);
+            fe_search(py, W, ctu, FE_SLOT(), 0, t, 0, what);
+        }
+        /* the all-zero block; the largest sums: a 0 / 1023 checkerboard, stripes along the four directions */
+        for (int pat = 0; pat < 6; ++pat) {
+            const struct fc_slot *sl = FE_SLOT();
+            for (int y = 0; y < 16; ++y)
+                for (int x = 0; x < 16; ++x) {
+                    const int on = pat == 0 ? 0 : pat == 1 ? (x + y) & 1 : pat == 2 ? x & 1 : pat == 3 ? y & 1 : pat == 4 ? ((x + y) >> 1) & 1 : ((x - y + 16) >> 1) & 1;
+                    py[(sl->y + y) * W + sl->x + x] = pat == 0 ? 600 : on ? 1023 : 0;
+                }
+        }
+#undef FE_SLOT
+    }
+    alf_cells_write(dir, name, f, W, H, log2_ctu, aps, mine, NULL);
+}
+
+/* ---- taps family.  aps[0]: alf_luma_clip_flag = 0.  aps[1]: the flag on, the classes alternately on filter 0 (every clip index 0: its
+ * clip values cannot clip) and on filters 1..4, whose 12 taps carry every clip index between them; the coefficients include -128 and
+ * 127.  aps[2]: 8 chroma alternatives whose 6 taps carry every clip index, the flag off or on.  CC-ALF: coefficients up to +-64. */
+static void
+alf_cells_taps_picture(const char *dir, const char *name, int W, int H, int log2_ctu, int chroma_clip, const struct fcell_cut *cut)
+{
+    const int ctu = 1 << log2_ctu, nx = (W + ctu - 1) / ctu, ny = (H + ctu - 1) / ctu, n = nx * ny;
+    static OVALFData aps[5];
+    for (int i = 0; i < 5; ++i) rand_alf_aps(&aps[i]);
+    for (int i = 0; i < 2; ++i) {
+        aps[i].alf_luma_num_filters_signalled_minus1 = 4;
+        aps[i].alf_luma_clip_flag = i;
+        for (int cl = 0; cl < 25; ++cl) aps[i].alf_luma_coeff_delta_idx[cl] = (cl & 1) ? 1 + ((cl >> 1) & 3) : 0;
+        for (int fl = 0; fl < 5; ++fl)
+            for (int k = 0; k < 12; ++k) {
+                aps[i].alf_luma_clip_idx[fl][k] = fl ? (k + fl) & 3 : 0;
+                if ((k + 5 * fl) % 7 == 0) aps[i].alf_luma_coeff[fl][k] = (k + fl) & 1 ? -128 : 127;
+            }
+    }
+    if (chroma_clip)                     /* the second picture: no class of aps[0] is linear either, for waves that clip in every lane */
+        for (int cl = 0; cl < 25; ++cl) { aps[0].alf_luma_clip_flag = 1; aps[0].alf_luma_coeff_delta_idx[cl] = 1 + (cl & 3); }
+    aps[2].alf_chroma_clip_flag = chroma_clip;
+    aps[2].alf_chroma_num_alt_filters_minus1 = 7;
+    for (int a = 0; a < 8; ++a)
+        for (int k = 0; k < 6; ++k) {
+            aps[2].alf_chroma_clip_idx[a][k] = (k + a) & 3;
+            if ((k + a) % 5 == 0) aps[2].alf_chroma_coeff[a][k] = (k + a) & 1 ? -128 : 127;
+        }
+    for (int cc = 0; cc < 2; ++cc) for (int k = 0; k < 7; ++k) { aps[3 + cc].alf_cc_mapped_coeff[cc][0][k] = (k + cc) & 1 ? -64 : 64; aps[3 + cc].alf_cc_mapped_coeff[cc][1][k] = k < 3 + cc ? 64 : -64; }
+    OVFrame *f = fcell_frame(W, H);
+    /* luma: every other 16x16 region is a surface of the class family, for classes beside the highest activity */
+    for (int y = 0; y + 16 <= H; y += 16)
+        for (int x = (y & 16); x + 16 <= W; x += 32) fc_draw_surface((uint16_t *)f->data[0] + y * W + x, W);
+    ovhip_alf_ctu *mine = calloc(n, sizeof(*mine));
+    for (int i = 0; i < n; ++i) {
+        /* the three pictures between them: every flags value, every alternative on either plane under either chroma APS */
+        static const uint8_t sets[6] = { 17, 16, 17, 3, 17, 12 }, flags[2][9] = { { 7, 7, 6, 5, 7, 4, 3, 7, 7 }, { 7, 2, 7, 1, 7, 0, 7, 7, 7 } };
+        mine[i].flags = n == 9 ? flags[chroma_clip][i] : 7;
+        mine[i].luma_set = sets[(i + chroma_clip) % 6];
+        mine[i].cb_alt = n == 9 ? i & 7 : 3 + 2 * i; mine[i].cr_alt = n == 9 ? (i + 3) & 7 : 4 * i;
+        mine[i].cc_cb_idx = i % 5; mine[i].cc_cr_idx = (i + 2) % 5;
+        if (cut) { mine[i].flags = 7; mine[i].cb_alt = i & 7; mine[i].cr_alt = (i + 3) & 7; mine[i].cc_cb_idx = 1 + i % 4; mine[i].cc_cr_idx = 1 + (i + 2) % 4; }
+    }
+    alf_cells_write(dir, name, f, W, H, log2_ctu, aps, mine, cut);
+}
+
+static void
+gen_alf_cells(const char *dir)
+{
+    g_seed = 0x266 + 14;
+    struct fc_need nd;
+    memset(&nd, 0, sizeof(nd));
+    char name[64];
+    int pic = 0;
+    for (; pic < 4 && fc_need_open(&nd); ++pic) {
+        snprintf(name, 64, "alf_cells_class_%02d.ovg", pic);
+        alf_cells_class_picture(dir, name, 296, 264, 7, pic, &nd, 1500000);
+    }
+    if (fc_need_open(&nd)) {
+        for (int k = 0; k < 2; ++k) for (int cl = 0; cl < 25; ++cl) for (int t = 0; t < 4; ++t) if (nd.pair[k][cl][t] < FC_TARGET(cl)) fprintf(stderr, " open: kind %d class %d transpose %d: %d\n", k, cl, t, nd.pair[k][cl][t]);
+        fprintf(stderr, "alf_cells class: %d needs still open after %d pictures\n", fc_need_open(&nd), pic); exit(1);
+    }
+    memset(&nd, 0, sizeof(nd));
+    alf_cells_class_picture(dir, "alf_cells_class64_00.ovg", 296, 264, 6, 0, &nd, 150000);     /* what so many draws reach: the pairs are all required at CTU 128 */
+    alf_cells_edge_picture(dir, "alf_cells_edge_00.ovg", 296, 264);
+    alf_cells_taps_picture(dir, "alf_cells_taps_00.ovg", 296, 264, 7, 0, NULL);
+    alf_cells_taps_picture(dir, "alf_cells_taps_01.ovg", 296, 264, 7, 1, NULL);
+    alf_cells_taps_picture(dir, "alf_cells_taps_02.ovg", 136, 72, 7, 1, NULL);      /* a single, truncated CTU row: the boundary is the picture's height */
+    /* 2 x 2 rect entries, as sao_cells_entry64_00.ovg; every CTU with luma, chroma and CC-ALF on */
+    static const struct fcell_cut cut = { 2, 2, { 0, 3, 5 }, { 0, 1, 4 } };
+    alf_cells_taps_picture(dir, "alf_cells_entry64_00.ovg", 296, 200, 6, 1, &cut);
 }
 
 /* ====================================================================================== INTRA
@@ -3405,6 +4018,9 @@ main(int argc, char **argv)
     /* the enumerated inter prediction cells: by name only, each a run of its own */
     if (only && !strcmp(only, "mc_cells") && !g_shim) gen_mc_cells(dir);
     if (only && !strcmp(only, "mcx_cells") && !g_shim) gen_mcx_cells(dir);
+    /* the enumerated SAO and ALF cells: by name only, each a run of its own */
+    if (only && !strcmp(only, "sao_cells") && !g_shim) gen_sao_cells(dir);
+    if (only && !strcmp(only, "alf_cells") && !g_shim) gen_alf_cells(dir);
     if (!only || !strcmp(only, "intra_ctu")) gen_intra_ctu(dir);
     if (!only || !strcmp(only, "isp")) gen_isp(dir);
     return 0;

@@ -18,6 +18,21 @@ def itx_cell_files():
     return sorted(p.name for p in golden_io.GOLDEN.glob("itx_cells_*.ovg"))
 
 
+def sao_cell_files():
+    """the enumerated SAO cells (gen_sao_cells): sao_cells_<family>_NN.ovg, one picture a file, read by sao_cases(name)"""
+    return sorted(p.name for p in golden_io.GOLDEN.glob("sao_cells_*.ovg"))
+
+
+def alf_cell_files():
+    """the enumerated ALF cells (gen_alf_cells): alf_cells_<family>_NN.ovg, one picture a file, read by alf_cases(name)"""
+    return sorted(p.name for p in golden_io.GOLDEN.glob("alf_cells_*.ovg"))
+
+
+def filter_cell_ctu(name):
+    """log2 of the CTU size a SAO / ALF cell file was generated at (its family says so too: sao64, class64, entry64, sao32)"""
+    return int(golden_io.load(name)["log2_ctu"][0])
+
+
 def itx_cases(name="itx.ovg"):
     """itx.ovg or one of itx_cell_files(): (picture, commands, coefficient arena, rects, expected); itx_cases_rec is the same with the
     recorder and the number of commands each case emitted"""

@@ -240,6 +240,185 @@ def test_alf_oracle_matches_reference_small_ctu(built_lib, name, log2_ctu, sizes
             assert len(bad) == 0, f"{name} picture {i} plane {name_}: {len(bad)} samples differ, first at (y,x) {bad[:6].tolist()}"
 
 
+# ---------------------------------------------------------------------------------------------- SAO and ALF: census and enumerated cells
+_OLD_SAO = {"sao.ovg": 7, "sao_ctu64.ovg": 6, "sao_ctu32.ovg": 5}
+_OLD_ALF = {"alf.ovg": 7, "alf_ctu64.ovg": 6, "alf_ctu32.ovg": 5}
+_filter_labels = {}
+
+
+def _filter_census(name):
+    """[(input, parameters, the reference's picture, the census's restated picture, its labels)] per picture of a SAO or ALF fixture,
+    computed once for all the tests below"""
+    import filter_census as fc
+    if name not in _filter_labels:
+        is_sao = name.startswith("sao")
+        l2 = (_OLD_SAO | _OLD_ALF)[name] if name in _OLD_SAO | _OLD_ALF else golden_cases.filter_cell_ctu(name)
+        cases = golden_cases.sao_cases(name) if is_sao else golden_cases.alf_cases(name)
+        _filter_labels[name] = [(pic, prm, exp) + (fc.sao if is_sao else fc.alf)(pic, prm, l2) for pic, prm, exp in cases], l2
+    return _filter_labels[name]
+
+
+def _family(files, fam):
+    return [f for f in files if f.split("_")[2] == fam]
+
+
+def test_sao_and_alf_oracle_match_reference_on_the_enumerated_cells(built_lib):
+    """sao_cells_*.ovg / alf_cells_*.ovg (gen_sao_cells / gen_alf_cells: the reference's rcn_sao_first_pix_rows / rcn_sao_filter_line and
+    rcn_alf_filter_line, in the entry family once per rect entry with that entry's RectEntryInfo): the oracle equals the reference on
+    every picture, at the CTU size the file was generated at."""
+    import golden_io
+    sf, af = golden_cases.sao_cell_files(), golden_cases.alf_cell_files()
+    assert {f.split("_")[2] for f in sf} == {"sao", "sao64", "sao32", "entry64"} and {f.split("_")[2] for f in af} == {"class", "class64", "edge", "taps", "entry64"}
+    assert all((golden_io.GOLDEN / f).stat().st_size < (1 << 20) for f in sf + af)
+    for f in sf + af:
+        l2 = golden_cases.filter_cell_ctu(f)
+        (pic, prm, exp), = golden_cases.sao_cases(f) if f in sf else golden_cases.alf_cases(f)
+        out = HostPic(pic.w, pic.h)
+        (oracle_lib.sao if f in sf else oracle_lib.alf)(out, pic, prm, l2)
+        _same_picture(out, exp, f"{f} (CTU {1 << l2}): oracle")
+        assert all((a != b).sum() > 100 for a, b in zip(exp.planes(), pic.planes())), f
+
+
+def test_filter_census_restates_the_reference(built_lib):
+    """tests/filter_census.py's numpy restatements of SAO and ALF -- written from rcn_sao.c and rcn_alf.c, with the virtual boundary, the
+    single-CTU-row quirks and the rect-entry borders -- equal the reference's expected planes on EVERY SAO and ALF fixture, old and new:
+    what makes the labels below trustworthy, since a label only comes out of the functions that computed these planes."""
+    n = 0
+    for f in list(_OLD_SAO) + list(_OLD_ALF) + golden_cases.sao_cell_files() + golden_cases.alf_cell_files():
+        cases, l2 = _filter_census(f)
+        for i, (_, _, exp, got, _) in enumerate(cases):
+            _same_picture(got, exp, f"{f} picture {i} (CTU {1 << l2}): census restatement")
+            n += 1
+    assert n == 11 + 11 + len(golden_cases.sao_cell_files()) + len(golden_cases.alf_cell_files())
+
+
+def test_sao_fixture_census(built_lib):
+    """What the SAO slot fixtures reach of what k_sao decides, per plane (tests/filter_census.py; cells reached of cells that exist).
+
+    sao.ovg alone: band positions with a sample in one of the four bands 17 of 105 (32 positions a plane, 29..31 also with the `& 31` wrap
+    acting); (edge class, sign of either comparison) 86 of 108; (band / edge, clip at 0 / at 1023) 7 of 12; group positions 0 and 7 under
+    the horizontal and the diagonal classes 14 of 18; skip reasons 8 of 18.  A comparison with an equal neighbour is 1.4 to 3.7 % of the
+    filtered edge samples of a plane, both equal at most 0.08 %.
+    With sao_ctu64.ovg and sao_ctu32.ovg: band positions 50 of 105, sign pairs 106 of 108, clips 8 of 12, skip reasons 9 of 18 -- the
+    three reasons that take a rect entry's border on every plane are out of their reach, every ovhip_sao_ctu.border being 0.
+    The enumerated cells reach every cell, the families at CTU 128 / 64 / 32 between them; on its own each CTU size reaches what depends
+    on the CTU size: a neighbour in another CTU, the picture's border columns and rows, all nine sign pairs of every class."""
+    import filter_census as fc
+    ex = fc.sao_cells_that_exist()
+    count = lambda r: {k: len(r[k] & ex[k]) for k in ex}
+    assert {k: len(v) for k, v in ex.items()} == {"type": 9, "band_k": 15, "band_pos": 105, "edge": 108, "clip": 12, "skip": 18, "group": 18, "across": 9}
+    labels = lambda files: [lb for f in files for case in _filter_census(f)[0] for lb in case[4]]
+    r = fc.sao_reach(labels(["sao.ovg"]))
+    assert count(r) == {"type": 9, "band_k": 15, "band_pos": 17, "edge": 86, "clip": 7, "skip": 8, "group": 14, "across": 9}
+    eq = [(((lb["sa"] == 0) | (lb["sb"] == 0))[lb["run"]].mean(), ((lb["sa"] == 0) & (lb["sb"] == 0))[lb["run"]].mean()) for lb in labels(["sao.ovg"]) if lb["run"].any()]
+    assert 0.013 < min(e for e, _ in eq) and max(e for e, _ in eq) < 0.038 and max(b for _, b in eq) < 0.0009
+    r = fc.sao_reach(labels(_OLD_SAO))
+    assert count(r) == {"type": 9, "band_k": 15, "band_pos": 50, "edge": 106, "clip": 8, "skip": 9, "group": 18, "across": 9}
+    assert ex["skip"] - r["skip"] == {(p, why) for p in range(3) for why in ("entry column", "entry row", "BORDER_ONE_ROW")}
+    assert not any(prm["border"].any() for f in _OLD_SAO for _, prm, _, _, _ in _filter_census(f)[0])
+
+    # ---- the enumerated cells
+    files = golden_cases.sao_cell_files()
+    r = fc.sao_reach(labels(files))
+    for k in ex:
+        assert r[k] == ex[k], f"SAO {k} cells without a case: {sorted(ex[k] - r[k], key=str)[:8]}"
+    for fam in ("sao", "sao64", "sao32"):
+        r = fc.sao_reach(labels(_family(files, fam)))
+        assert r["edge"] == ex["edge"] and r["across"] == ex["across"] and r["group"] == ex["group"] and r["band_k"] == ex["band_k"], fam
+        assert {(p, why) for p in range(3) for why in ("picture column", "picture row")} <= r["skip"], fam
+    assert fc.sao_reach(labels(_family(files, "sao32")))["band_pos"] == ex["band_pos"]
+    # the rect entries: every border bit on a CTU whose three planes have an edge class on; the three reasons on every plane
+    (_, prm, _, _, lbs), = _filter_census("sao_cells_entry64_00.ovg")[0]
+    edge_on = (prm["type"] == fc.SAO_EDGE).all(axis=1)
+    for bit in (capi.BORDER_LEFT, capi.BORDER_RIGHT, capi.BORDER_UPPER, capi.BORDER_BOTTOM, capi.BORDER_ONE_ROW):
+        assert ((prm["border"] & bit) != 0)[edge_on].any(), bit
+    assert {(p, why) for p in range(3) for why in ("entry column", "entry row", "BORDER_ONE_ROW")} <= fc.sao_reach(lbs)["skip"]
+    # pictures with a ragged last group of 8 on every plane, a truncated last CTU row, a single CTU row
+    sizes = [(c[0].w, c[0].h, _filter_census(f)[1]) for f in files for c in _filter_census(f)[0]]
+    assert any(w % 8 and (w // 2) % 8 and h % (1 << l2) for w, h, l2 in sizes) and any(h <= 1 << l2 for w, h, l2 in sizes)
+    # the load and store paths: in an allocation whose strides are multiples of 8 samples the full groups go 16 bytes at a time, in
+    # one as wide as the picture (no width here is a multiple of 8) or two samples wider (tests/test_gpu_filter_cells.py) sample by sample
+    for w, h, l2 in sizes:
+        ragged = {(p, "ragged") for p in range(3) if (w >> (p > 0)) % 8}
+        assert len(ragged) >= 2 and fc.sao_paths(w, h, (w + 15) & ~15, ((w + 15) & ~15) // 2) == {(p, "16-byte") for p in range(3)} | ragged
+        assert fc.sao_paths(w, h, w, w // 2) == fc.sao_paths(w, h, w + 2, w // 2 + 1) == {(p, "scalar") for p in range(3)} | ragged
+
+
+def test_alf_fixture_census(built_lib):
+    """What the ALF slot fixtures reach of what k_alf decides (tests/filter_census.py; cells reached of cells that exist).  A 4x4 luma
+    block counts for its (class, transpose) pair only if it discriminates: the filter of each other transpose of its class, of the
+    class one step away in activity and of the class one step away in direction gives another 4x4 block, from the picture's own tables.
+
+    alf.ovg alone: 5924 luma blocks, 5737 of them in class 4; 8 of the 25 classes and 19 of the 100 (class, transpose) pairs occur, 18
+    with a block that discriminates, 13 with four; act 6 and 8..15 only; luma sets 7 of 18; no luma tap is ever clipped (every luma set
+    in use is linear: (tap, clip index, state) 12 of 120, waves linear alone); chroma taps 12 of 120; chroma alternatives 6 of 16; none
+    of the 16 sums next to an activity threshold; ties 2 of 5; no all-zero block; max_db * min_hv at most 1.1e8 of 2^32.
+    With alf_ctu64.ovg and alf_ctu32.ovg: 11136 blocks, 10596 in class 4, 27 pairs, 25 that discriminate, 18 with four; act 3..15; sets
+    15 of 18; luma taps 120 of 120, chroma taps 84 of 120, waves linear and clipping but never mixed; thresholds 0 of 16; ties 3 of 5.
+    The enumerated cells: see the assertions per family below."""
+    import filter_census as fc
+    ex = fc.alf_cells_that_exist()
+    count = lambda r: {k: len(r[k] & ex[k]) for k in ex}
+    labels = lambda files: [case[4] for f in files for case in _filter_census(f)[0]]
+    blocks = lambda lbs, key: np.concatenate([L["blocks"][key][L["blocks"]["on"]] for L in lbs])
+    assert {k: len(v) for k, v in ex.items()} == {"pair": 100, "set": 18, "act": 32, "ties": 5, "luma_tap": 120, "chroma_tap": 120, "wave": 3, "clip": 6, "alt": 16,
+                                                  "cc": 10, "cc_row": 6, "cc_clip": 8, "flags": 8, "d": 24, "thresholds": 16}
+    lbs = labels(["alf.ovg"])
+    r = fc.alf_reach(lbs)
+    assert count(r) == {"pair": 18, "set": 7, "act": 15, "ties": 2, "luma_tap": 12, "chroma_tap": 12, "wave": 1, "clip": 6, "alt": 6, "cc": 8, "cc_row": 6,
+                        "cc_clip": 6, "flags": 7, "d": 24, "thresholds": 0}
+    cls, tr = blocks(lbs, "cls"), blocks(lbs, "tr")
+    assert (len(cls), int((cls == 4).sum()), sorted(set(cls.tolist())), len(set(zip(cls.tolist(), tr.tolist())))) == (5924, 5737, [2, 3, 4, 8, 9, 18, 19, 24], 19)
+    assert sum(v >= 4 for v in r["pair_n"].values()) == 13 and sorted({a for a, _ in r["act"]}) == [6, 8, 9, 10, 11, 12, 13, 14, 15]
+    assert not r["all_zero"] and r["max_cross"] < 1.2e8 and r["wave"] == {"linear"}
+    lbs = labels(_OLD_ALF)
+    r = fc.alf_reach(lbs)
+    assert count(r) == {"pair": 25, "set": 15, "act": 25, "ties": 3, "luma_tap": 120, "chroma_tap": 84, "wave": 2, "clip": 6, "alt": 8, "cc": 10, "cc_row": 6,
+                        "cc_clip": 7, "flags": 8, "d": 24, "thresholds": 0}
+    cls, tr = blocks(lbs, "cls"), blocks(lbs, "tr")
+    assert (len(cls), int((cls == 4).sum()), len(set(zip(cls.tolist(), tr.tolist())))) == (11136, 10596, 27)
+    assert sum(v >= 4 for v in r["pair_n"].values()) == 18 and r["wave"] == {"linear", "clipping"} and not r["all_zero"]
+    assert not any(t["ctus"]["border"].any() for f in _OLD_ALF for _, t, _, _, _ in _filter_census(f)[0])
+
+    files = golden_cases.alf_cell_files()
+    # ---- class: all 100 pairs by at least 4 discriminating blocks on a fixed set and again on an APS set; every luma_set on a CTU that
+    # is on; among the blocks at a virtual boundary every activity class, direction class and transpose
+    lbs = labels(_family(files, "class"))
+    for kind in ("fixed", "aps"):
+        n = fc.alf_reach(lbs, kind)["pair_n"]
+        thin = sorted(p for p in ex["pair"] if n.get(p, 0) < 4)
+        assert not thin, f"(class, transpose) with fewer than 4 discriminating blocks on a {kind} set: {[(p, n.get(p, 0)) for p in thin[:8]]}"
+    r = fc.alf_reach(lbs + labels(_family(files, "class64")))
+    assert r["set"] == ex["set"] and (r["vb_actc"], r["vb_dirc"], r["vb_tr"]) == (set(range(5)), set(range(5)), set(range(4)))
+    r = fc.alf_reach(lbs)
+    assert (r["vb_actc"], r["vb_dirc"], r["vb_tr"]) == (set(range(5)), set(range(5)), set(range(4))) and len(r["set"]) == 16
+    # (the picture regenerated at CTU 64, 150000 draws: as measured)
+    assert len(fc.alf_reach(labels(_family(files, "class64")))["pair"]) == 93
+    # ---- edge: every act on plain blocks and on blocks at a virtual boundary, both sides of each activity threshold exactly, each of
+    # the five ties with non-zero sums, the all-zero block, the largest sums: 65472^2 = 2^32 - 8384512
+    r = fc.alf_reach(labels(_family(files, "edge")))
+    assert r["act"] == ex["act"] and r["thresholds"] == ex["thresholds"] and r["ties"] == ex["ties"] and r["all_zero"]
+    assert r["max_cross"] == 65472 ** 2 == (1 << 32) - 8384512
+    # ---- taps
+    r = fc.alf_reach(labels(_family(files, "taps")))
+    for k in ("luma_tap", "chroma_tap", "wave", "clip", "alt", "cc", "cc_row", "cc_clip", "flags", "d"):
+        assert r[k] == ex[k], f"ALF {k} cells without a case in the taps family: {sorted(ex[k] - r[k], key=str)[:8]}"
+    for f in _family(files, "taps"):
+        (_, t, _, _, _), = _filter_census(f)[0]
+        assert {-128, 127} <= set(np.asarray(t["luma_coeff"])[16:18].ravel().tolist()) and {-128, 127} <= set(np.asarray(t["chroma_coeff"]).ravel().tolist())
+    # ---- entry: every border bit on a CTU with luma, both chroma planes and both CC-ALF filters on
+    (_, t, _, _, L), = _filter_census("alf_cells_entry64_00.ovg")[0]
+    c = t["ctus"]
+    full = (c["flags"] == 7) & (c["cc_cb_idx"] > 0) & (c["cc_cr_idx"] > 0)
+    for bit in (capi.BORDER_LEFT, capi.BORDER_RIGHT, capi.BORDER_UPPER, capi.BORDER_BOTTOM, capi.BORDER_ONE_ROW):
+        assert ((c["border"] & bit) != 0)[full].any(), bit
+    paths, sides = fc.alf_paths(L["w"], L["h"], L["w"], L["w"] // 2, t, 6)
+    assert {s for s in sides if any(s)} >= {(True, False, False, False), (False, True, False, False), (False, False, True, False), (False, False, False, True)}
+    # at least one picture per family has a width that is no multiple of 64 in luma or chroma and a truncated last CTU row
+    for fam in ("class", "edge", "taps"):
+        assert any(c[0].w % 64 and c[0].h % 128 for f in _family(files, fam) for c in _filter_census(f)[0]), fam
+
+
 def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     """Where the compiled reference is available (this container: oracle/_ref built from /root/reference),
     re-running the harness reproduces every committed fixture byte for byte."""
@@ -251,7 +430,7 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     if not gen.exists() or not (root / "oracle" / "_ref" / "libovvcref.so").exists():
         pytest.skip("compiled reference not present")
     subprocess.check_call([str(gen), str(tmp_path)], stderr=subprocess.DEVNULL)
-    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells", "itx_cells", "mc_cells", "mcx_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra / inverse transform / inter prediction cells are runs of their own
+    for only in ("dbf_ends", "sao_ctu64", "sao_ctu32", "alf_ctu64", "alf_ctu32", "intra_cells", "itx_cells", "mc_cells", "mcx_cells", "sao_cells", "alf_cells"):        # deblocking's second profile, the smaller CTU sizes and the enumerated intra / inverse transform / inter prediction / SAO / ALF cells are runs of their own
         subprocess.check_call([str(gen), str(tmp_path), only], stderr=subprocess.DEVNULL)
     # shim_*: test_shim_cpu.py; pipe* / tiles*: the chained streams of gen_pipe, test_pipe_cpu.py
     names = sorted(p.name for p in (root / "tests" / "golden").glob("*.ovg") if not p.name.startswith(("shim_", "pipe", "tiles")))
@@ -262,6 +441,8 @@ def test_fixtures_regenerate_from_the_compiled_reference(tmp_path):
     assert sorted(p.name for p in tmp_path.glob("itx_cells_*.ovg")) == [n for n in names if n.startswith("itx_cells_")], "the generator cuts the inverse transform cells into other files than the committed ones"
     assert sorted(p.name for p in tmp_path.glob("mc_cells_*.ovg")) == [n for n in names if n.startswith("mc_cells_")], "the generator cuts the plain prediction cells into other files than the committed ones"
     assert sorted(p.name for p in tmp_path.glob("mcx_cells_*.ovg")) == [n for n in names if n.startswith("mcx_cells_")], "the generator cuts the refined prediction cells into other files than the committed ones"
+    assert sorted(p.name for p in tmp_path.glob("sao_cells_*.ovg")) == [n for n in names if n.startswith("sao_cells_")], "the generator cuts the SAO cells into other files than the committed ones"
+    assert sorted(p.name for p in tmp_path.glob("alf_cells_*.ovg")) == [n for n in names if n.startswith("alf_cells_")], "the generator cuts the ALF cells into other files than the committed ones"
 
 
 def test_intra_oracle_matches_reference(built_lib):
