@@ -1688,8 +1688,8 @@ int  ovhip_pic_digest_reduced(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_
  * text where there is a context: whatever ovhip_output_reduce_check refuses for a rung (OVHIP_EUNSUP or OVHIP_EINVAL as there);
  * whatever the surface output refuses for a rung's size, format, destination and dst_bytes (OVHIP_EINVAL); n out of range; null
  * rungs, info or picture; a missing plane or a stride below the width; two rungs' destinations that overlap one another, or one that
- * overlaps the picture.  Rungs through a colour table: "Output ladder through a colour table" below.  Not done: RGB rungs, rungs of
- * different windows, up-sampling rungs, ratios above 8, an event hand-off to the consumer, a shim entry point.
+ * overlaps the picture.  Rungs through a colour table: "Output ladder through a colour table" below.  RGB tensors at several sizes: "RGB pyramid on the
+ * device" below.  Not done: rungs of different windows, up-sampling rungs, ratios above 8, an event hand-off to the consumer, a shim entry point.
  * ---------------------------------------------------------------------------------- */
 #define OVHIP_LADDER_MAX_RUNGS 8
 typedef struct ovhip_ladder_rung {
@@ -1735,7 +1735,8 @@ int  ovhip_pic_output_ladder(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_r
  * info->chroma_loc (OVHIP_EINVAL: the reduced picture keeps the source's sample location, so two values are a mistake that would shift
  * the chroma silently); everything ovhip_surface_lut_launch refuses of a rung's picture, format and destination -- rung sizes that
  * are not multiples of 4 among them --; a null table, a table of another device.
- * Not done: RGB rungs, a table or a conversion per rung, convert-then-reduce, rungs of different windows, up-sampling rungs, ratios
+ * RGB tensors at several sizes, with or without a table: "RGB pyramid on the device" below.
+ * Not done: a table or a conversion per rung, convert-then-reduce, rungs of different windows, up-sampling rungs, ratios
  * above 8, destination locations 4 and 5, a conversion without a table, a shim entry point.
  * ---------------------------------------------------------------------------------- */
 /* Host only: the checks the launch makes that need no picture and no destination, against a src_w x src_h picture and a table of
@@ -1757,6 +1758,67 @@ int  ovhip_ladder_lut_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_r
  * then the rows' own bytes of every plane to the host (the gaps stay unwritten in host memory too). */
 int  ovhip_pic_output_ladder_lut(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n,
                                  const ovhip_surface_conv *conv, const ovhip_rgb_lut *lut);
+
+/* ------------------------------------------------------------------------------------
+ * RGB pyramid on the device: ONE finished 10-bit 4:2:0 picture leaves as SEVERAL reduced RGB tensors -- 2160p as a 1080p and a 540p
+ * F16 CHW tensor for two models and a 640x360 U8 HWC thumbnail --, each at its own size, dtype, layout and address, from ONE launch
+ * that writes no intermediate picture.  It is an OUTPUT beside RGB, surface and ladder, not a post-process setting: film grain, the
+ * output scale or a first reduce compose in front of it, and the other outputs of the picture see what they saw without it.  There is
+ * no new arithmetic, no new rounding and no new table; with one ovhip_reduce_info, n levels and, optionally, one ovhip_rgb_lut table,
+ * by definition
+ *     without a table    level r = rgb(reduce(src, info, out_w_r, out_h_r), window NULL, fmt_r)
+ *     with a table       level r = rgb_lut(reduce(src, info, out_w_r, out_h_r), window NULL, fmt_r, lut)
+ * with reduce of "Reduced-size output on the device", rgb of "RGB output on the device" and rgb_lut of "RGB output through a colour
+ * table", byte for byte; every implementation of it (tests/spec_rgb_pyramid.py, ovhip_rgb_pyramid_host, k_rgb_pyramid) is compared
+ * for equality.  So the chroma taps clamp to the REDUCED picture's chroma plane; without a table a U8 level takes the 8-bit
+ * coefficients and every other level the 10-bit ones -- two levels of one pyramid may carry different coefficient sets --; with a
+ * table the matrix is at 10 bits for every dtype and a U8 level needs a peak of at most 255.
+ *
+ *   Pyramid  one ovhip_reduce_info -- the window in chroma units and chroma_loc -- for the picture shown, and n levels,
+ *            1 <= n <= OVHIP_PYRAMID_MAX_LEVELS = 8 (k_rgb_pyramid's arguments for 8 levels are about 1 KB: inside the 4 KB a launch's
+ *            kernel arguments may take).
+ *   Level r  out_w x out_h (multiples of 4, as the RGB output's), an ovhip_rgb_format, a destination of dst_bytes.  dtype and layout
+ *            are the level's own.  matrix, full_range and chroma_loc describe the one SOURCE and must be equal in all levels, and
+ *            chroma_loc must be info->chroma_loc: the reduced picture keeps the source's sample location, so two values are a mistake
+ *            that would shift the chroma silently.  A level of the region's own size is 1:1 on both axes: allowed.  Two levels may
+ *            have one size and different formats.  One table serves all levels.
+ * A pyramid is ALL OR NOTHING.  Refused before anything is launched or written, the reason and the level's index in the context's
+ * error text where there is a context: whatever ovhip_output_reduce_check refuses for a level (OVHIP_EUNSUP or OVHIP_EINVAL as there);
+ * whatever ovhip_rgb_launch -- with a table: ovhip_rgb_lut_launch -- refuses for a level's size, format, destination and dst_bytes,
+ * with its code; n out of range; null levels, info or picture; a missing plane or a stride below the width; formats that disagree in
+ * matrix, range or location; two levels' destinations that overlap one another, or one that overlaps the picture; a table of another
+ * device.
+ * Not done: a window per level, up-sampling levels, ratios above 8, normalisation (mean / std), a table per level,
+ * convert-then-reduce (averaging in linear light), a shim entry point.
+ * ---------------------------------------------------------------------------------- */
+#define OVHIP_PYRAMID_MAX_LEVELS 8
+typedef struct ovhip_rgb_level {
+    int32_t out_w, out_h;
+    ovhip_rgb_format fmt;
+    void *dst; size_t dst_bytes;         /* at least ovhip_rgb_bytes(out_w, out_h, NULL, &fmt) */
+} ovhip_rgb_level;
+/* Host only (no device needed): the checks the launch makes that need no picture and no destination -- n, every level's reduce check,
+ * size and format, the formats' agreement -- against a src_w x src_h picture and a table of lut_size points and peak lut_peak;
+ * lut_size 0: no table.  ratio[r] = p_x, q_x, p_y, q_y of level r (ratio may be NULL), written for every level whose values can be
+ * derived (0 otherwise).  The first refusal's code. */
+int  ovhip_rgb_pyramid_check(int32_t src_w, int32_t src_h, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n, int lut_size, int lut_peak,
+                             int32_t ratio[][4]);
+/* The definition over a picture, an optional table (lut_size 0: none) and destinations in HOST memory: ovhip_output_reduce_host, then
+ * ovhip_rgb_host or ovhip_rgb_lut_host, per level (one reduced picture per level on the host heap; OVHIP_ENOMEM when that fails, before
+ * anything is written).  Refusals as the launch's, and a table entry above the peak (OVHIP_EINVAL); nothing is written when it refuses. */
+int  ovhip_rgb_pyramid_host(const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n, int lut_size, int lut_peak,
+                            const uint16_t *host_table);
+/* Every level's tensor at its dst (DEVICE memory, aligned to its element) from the window of src; lut NULL: without a table.  ONE
+ * launch (k_rgb_pyramid: all levels; a workgroup finds its level and tile from a prefix table in the arguments, reduces the tile's Y,
+ * Cb and Cr with the chroma halo into LDS, converts from there and stores the level's elements: 16-byte stores where the address
+ * allows, narrower at row tails and unaligned bases).  Asynchronous on the ctx stream; allocates nothing, uploads nothing; no
+ * intermediate picture in device memory. */
+int  ovhip_rgb_pyramid_launch(ovhip_ctx *ctx, const ovhip_pic *src, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n,
+                              const ovhip_rgb_lut *lut);
+/* Synchronous convenience, as ovhip_pic_output_rgb: the levels' dst are HOST memory; the launch into the context's grow-only scratch
+ * (no allocation once the sizes have been seen; a refused request allocates nothing), then one D2H per level. */
+int  ovhip_pic_output_rgb_pyramid(ovhip_ctx *ctx, const ovhip_pic *pic, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n,
+                                  const ovhip_rgb_lut *lut);
 
 /* ------------------------------------------------------------------------------------
  * Film grain synthesis (film grain characteristics SEI, frequency-filtering model): replaces fg_grain_apply_pic
@@ -2147,6 +2209,25 @@ int  ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info
  * rung sizes that are not multiples of 4 come back there too), and the launch makes the refusal again.  A dry frame accepts the call
  * and does nothing. */
 int  ovhip_frame_set_ladder_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv);
+/* RGB pyramid output ("RGB pyramid on the device" above) of the NEXT picture completed, an output beside RGB, surface and ladder and
+ * independent of them: per picture, levels NULL switches it off (the default).  ovhip_rgb_pyramid_launch runs in ovhip_frame_submit and
+ * in the last ovhip_frame_band after the ladder step and before the motion field, on the picture the outputs show -- after the frame's
+ * post-process step, which still runs once per picture: film grain, the output scale or a first reduce compose in front of the
+ * pyramid, and info's window and the levels' sizes are read against THAT picture --, whatever out->mode is, a NULL out included, and
+ * is complete on the device when the call returns.  info (NULL: no window, chroma_loc 0) and the n levels are copied; the levels' dst
+ * are DEVICE memory.  What needs no picture comes back here: n out of range, a null destination, and ovhip_rgb_pyramid_check -- with
+ * the table of ovhip_frame_set_rgb_pyramid_lut where one is set -- against the size the post-process setting of the moment leaves (set
+ * that one first).  The others come from the picture's last call: a failed pyramid fails that call's return value, never the
+ * picture's publication, and writes nothing.  A dry frame makes the same checks (it has a size, and never a table), accepts the call
+ * and does nothing. */
+int  ovhip_frame_set_rgb_pyramid_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n);
+/* A colour table for the frame's RGB pyramid output.  STICKY, as ovhip_frame_set_rgb_lut: while set, the frame's pyramid step hands the
+ * table to ovhip_rgb_pyramid_launch; lut NULL switches it off, which is the default.  The table is borrowed; the setting is independent
+ * of the other outputs' tables (the same object may serve all).  OVHIP_EINVAL for a table on another device than the frame's context.
+ * With a pyramid already set for the next picture this setter, being the second, asks ovhip_rgb_pyramid_check for those levels through
+ * this table (a U8 level needs a peak of at most 255) and on a refusal leaves the setting as it was; ovhip_frame_set_rgb_pyramid_output
+ * called second does the same.  A dry frame accepts the call and does nothing. */
+int  ovhip_frame_set_rgb_pyramid_lut(ovhip_frame *f, const ovhip_rgb_lut *lut);
 /* Motion field output ("Motion field output on the device" above) of the NEXT picture completed: per picture, fmt NULL switches it
  * off (the default); either destination may be NULL.  ovhip_job_mvfield runs in ovhip_frame_submit after a successful
  * ovhip_job_wait and after the picture's publication, on the job that decoded it -- a borrowed job goes back to its home context
@@ -2339,6 +2420,19 @@ int  ovhip_stream_set_ladder_output(ovhip_stream *s, const ovhip_reduce_info *in
  * those of ovhip_ladder_lut_check for the ladder set; on a refusal the previous setting stands.  The rungs' slot sizes are still
  * ovhip_surface_bytes.  Between runs only. */
 int  ovhip_stream_set_ladder_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table);
+/* RGB pyramid output for the following runs, as the ladder output above and independent of it: level r gives its base as
+ * levels[r].dst and its bytes per picture as levels[r].dst_bytes, and level r of picture idx lands at dst + (idx % n_slots) * dst_bytes
+ * in DEVICE memory, written by the frame thread that completes it (ovhip_frame_set_rgb_pyramid_output).  levels NULL: off.  The refusals
+ * of ovhip_rgb_pyramid_check -- through the table of ovhip_stream_set_rgb_pyramid_lut where one is set -- against the size the stream
+ * outputs (its output scale's or reduced size, else its pictures'); OVHIP_EINVAL for a null base, n_slots 0, or a level whose bytes
+ * per picture are below its tensor's size or no multiple of its element.  On a refusal the previous setting stands. */
+int  ovhip_stream_set_rgb_pyramid_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n, uint32_t n_slots);
+/* A colour table for the RGB pyramid output of the following runs (ovhip_frame_set_rgb_pyramid_lut on every frame), as
+ * ovhip_stream_set_rgb_lut and independent of it: one upload per device, owned by the stream until the setting is cleared (host_table
+ * NULL) or replaced, or the stream is destroyed.  The refusals of ovhip_rgb_lut_create and -- from whichever of this setter and
+ * ovhip_stream_set_rgb_pyramid_output is called second -- those of ovhip_rgb_pyramid_check for the pyramid set; on a refusal the
+ * previous setting stands.  Between runs only. */
+int  ovhip_stream_set_rgb_pyramid_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table);
 /* Motion field output for the following runs: the vectors of picture idx land at d_vec_base + (idx % n_slots) *
  * vec_bytes_per_picture, its info at d_info_base + (idx % n_slots) * info_bytes_per_picture, in DEVICE memory, written by the frame
  * thread that completes it (ovhip_frame_set_mvfield_output).  Either base may be NULL (not wanted).  fmt NULL: off.  OVHIP_EINVAL

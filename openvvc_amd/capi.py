@@ -528,6 +528,14 @@ class LadderRung(C.Structure):
     _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("fmt", SurfaceFormat), ("dst", C.c_void_p), ("dst_bytes", C.c_size_t)]
 
 
+PYRAMID_MAX_LEVELS = 8                                        # OVHIP_PYRAMID_MAX_LEVELS
+
+
+class RgbLevel(C.Structure):
+    """ovhip_rgb_level: one level of the RGB pyramid -- its size, its RGB format, its destination and the bytes there"""
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("fmt", RgbFormat), ("dst", C.c_void_p), ("dst_bytes", C.c_size_t)]
+
+
 MVF_I32, MVF_F32, MVF_F16 = 0, 1, 2                 # ovhip_mvfield_format.dtype
 MVF_PLANAR, MVF_CELLS = 0, 1                         # ovhip_mvfield_format.layout: [4][H4][W4] / [H4][W4][4]
 MVF_UNIT, MVF_REFINED = 0, 1                         # ovhip_mvfield_format.vectors
@@ -839,6 +847,14 @@ def load(path: os.PathLike | None = None) -> C.CDLL:
         "ovhip_pic_output_ladder_lut": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(LadderRung), i32, P(SurfaceConv), vp]),
         "ovhip_frame_set_ladder_lut": (C.c_int, [vp, vp, P(SurfaceConv)]),
         "ovhip_stream_set_ladder_lut": (C.c_int, [vp, P(SurfaceConv), C.c_int, C.c_int, vp]),
+        "ovhip_rgb_pyramid_check": (C.c_int, [i32, i32, P(ReduceInfo), P(RgbLevel), i32, C.c_int, C.c_int, vp]),
+        "ovhip_rgb_pyramid_host": (C.c_int, [P(Pic), P(ReduceInfo), P(RgbLevel), i32, C.c_int, C.c_int, vp]),
+        "ovhip_rgb_pyramid_launch": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(RgbLevel), i32, vp]),
+        "ovhip_pic_output_rgb_pyramid": (C.c_int, [vp, P(Pic), P(ReduceInfo), P(RgbLevel), i32, vp]),
+        "ovhip_frame_set_rgb_pyramid_output": (C.c_int, [vp, P(ReduceInfo), P(RgbLevel), i32]),
+        "ovhip_frame_set_rgb_pyramid_lut": (C.c_int, [vp, vp]),
+        "ovhip_stream_set_rgb_pyramid_output": (C.c_int, [vp, P(ReduceInfo), P(RgbLevel), i32, u32]),
+        "ovhip_stream_set_rgb_pyramid_lut": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "ovhip_surface_bytes": (C.c_size_t, [i32, i32, P(Window), P(SurfaceFormat)]),
         "ovhip_surface_host": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(Window), P(SurfaceFormat), vp, C.c_size_t]),
         "ovhip_surface_launch": (C.c_int, [vp, P(Pic), P(Window), P(SurfaceFormat), vp, C.c_size_t]),
@@ -915,6 +931,8 @@ EXPORTED_SYMBOLS = [
     "ovhip_ladder_check", "ovhip_ladder_host", "ovhip_ladder_launch", "ovhip_pic_output_ladder", "ovhip_frame_set_ladder_output", "ovhip_stream_set_ladder_output",
     "ovhip_ladder_lut_check", "ovhip_ladder_lut_host", "ovhip_ladder_lut_launch", "ovhip_pic_output_ladder_lut", "ovhip_frame_set_ladder_lut",
     "ovhip_stream_set_ladder_lut",
+    "ovhip_rgb_pyramid_check", "ovhip_rgb_pyramid_host", "ovhip_rgb_pyramid_launch", "ovhip_pic_output_rgb_pyramid", "ovhip_frame_set_rgb_pyramid_output",
+    "ovhip_frame_set_rgb_pyramid_lut", "ovhip_stream_set_rgb_pyramid_output", "ovhip_stream_set_rgb_pyramid_lut",
 ]
 
 

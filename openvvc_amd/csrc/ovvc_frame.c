@@ -81,6 +81,12 @@ struct ovhip_frame {
     /* the colour table and the conversion of the ladder output (ovhip_frame_set_ladder_lut): sticky, the table borrowed, NULL: none */
     const ovhip_rgb_lut *ladder_lut;
     ovhip_surface_conv ladder_conv;
+    /* the RGB pyramid output (ovhip_frame_set_rgb_pyramid_output) of the NEXT picture completed, beside them and ending with the picture
+     * as they do; pyr_w x pyr_h: the size it was checked against.  Its colour table (ovhip_frame_set_rgb_pyramid_lut): sticky, borrowed */
+    int pyr_on; int32_t pyr_n, pyr_w, pyr_h;
+    ovhip_reduce_info pyr_info;
+    ovhip_rgb_level pyr[OVHIP_PYRAMID_MAX_LEVELS];
+    const ovhip_rgb_lut *pyr_lut;
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -394,8 +400,8 @@ publish(ovhip_frame *f, int status)
     return r;
 }
 
-/* a picture that ends, however it ends, takes its RGB, surface, ladder and motion field destinations with it */
-static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; f->ladder_on = 0; }
+/* a picture that ends, however it ends, takes its RGB, surface, ladder, pyramid and motion field destinations with it */
+static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; f->ladder_on = 0; f->pyr_on = 0; }
 
 int
 ovhip_frame_fail(ovhip_frame *f, int status)
@@ -584,6 +590,45 @@ ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, con
 }
 
 int
+ovhip_frame_set_rgb_pyramid_lut(ovhip_frame *f, const ovhip_rgb_lut *lut)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (lut && !f->dry) {
+        if (!ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
+        /* a pyramid already set for the next picture: its levels through THIS table (a U8 level and the peak) */
+        if (f->pyr_on) {
+            const int r = ovhip_rgb_pyramid_check(f->pyr_w, f->pyr_h, &f->pyr_info, f->pyr, f->pyr_n, lut->size, lut->peak, NULL);
+            if (r != OVHIP_OK) return r;
+        }
+    }
+    f->pyr_lut = f->dry ? NULL : lut;                          /* (a dry frame has no picture to convert) */
+    return OVHIP_OK;
+}
+
+int
+ovhip_frame_set_rgb_pyramid_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n)
+{
+    if (!f) return OVHIP_EINVAL;
+    if (!levels) { f->pyr_on = 0; return OVHIP_OK; }
+    if (n < 1 || n > OVHIP_PYRAMID_MAX_LEVELS) return OVHIP_EINVAL;
+    ovhip_reduce_info ri;
+    memset(&ri, 0, sizeof(ri));
+    if (info) ri = *info;
+    for (int32_t k = 0; k < n; ++k)                           /* what needs no picture comes back here */
+        if (!levels[k].dst) return OVHIP_EINVAL;
+    /* the size the pyramid reads: the one the post-process step set now leaves (grain leaves the frame's) */
+    const int resized = f->post.kind == OVHIP_POST_SCALE || f->post.kind == OVHIP_POST_REDUCE;
+    const int32_t sw = resized ? f->post.out_w : f->w, sh = resized ? f->post.out_h : f->h;
+    const int r = ovhip_rgb_pyramid_check(sw, sh, &ri, levels, n, f->pyr_lut ? f->pyr_lut->size : 0, f->pyr_lut ? f->pyr_lut->peak : 0, NULL);
+    if (r != OVHIP_OK) return r;
+    if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to reduce: it answers and remembers nothing) */
+    f->pyr_info = ri; f->pyr_n = n; f->pyr_w = sw; f->pyr_h = sh;
+    memcpy(f->pyr, levels, (size_t)n * sizeof(*levels));
+    f->pyr_on = 1;
+    return OVHIP_OK;
+}
+
+int
 ovhip_frame_set_mvfield_output(ovhip_frame *f, const ovhip_mvfield_format *fmt, void *d_vec, size_t vec_bytes, void *d_info, size_t info_bytes)
 {
     if (!f) return OVHIP_EINVAL;
@@ -620,7 +665,7 @@ frame_shown(ovhip_frame *f, ovhip_pic *shown, int *have)
  * wait marks the picture complete).  j: the job that decoded it; borrowed: j when it is a caller's job bound to this frame's context
  * (ovhip_frame_submit), which goes back to its own context here -- this frame and its context may be destroyed before the job.
  *
- *     publish (+ unpin the references) -> hash of f->dst -> RGB -> surface -> ladder -> motion field -> the settings end -> delivery `out` names
+ *     publish (+ unpin the references) -> hash of f->dst -> RGB -> surface -> ladder -> RGB pyramid -> motion field -> the settings end -> delivery `out` names
  *
  * The picture is published first: its readers go on while this thread copies it out (the outputs only read; whoever keeps the key
  * alive -- the decoder's DPB, the stream driver's hold -- does so until this call returns).  Each output is complete on the device
@@ -664,6 +709,11 @@ picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_fram
                               : ovhip_ladder_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n);
         if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "ladder output");
         if (r != OVHIP_OK) fail(f, r, "ladder output");
+    }
+    if (r == OVHIP_OK && f->pyr_on) {
+        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_rgb_pyramid_launch(f->ctx, &shown, &f->pyr_info, f->pyr, f->pyr_n, f->pyr_lut);
+        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "RGB pyramid output");
+        if (r != OVHIP_OK) fail(f, r, "RGB pyramid output");
     }
     if (r == OVHIP_OK && mvf->on && (r = ovhip_job_mvfield_done_(j, &mvf->fmt.mvf, mvf->dst[0], mvf->bytes[0], mvf->dst[1], mvf->bytes[1])) != OVHIP_OK)
         fail(f, r, "motion field output");

@@ -76,7 +76,14 @@ struct ovhip_stream {
     ovhip_surface_conv surf_conv;         /* their conversion */
     ovhip_rgb_lut **ladder_luts;          /* [n_dev], or NULL: the colour tables of the ladder output (ovhip_stream_set_ladder_lut), owned */
     ovhip_surface_conv ladder_conv;       /* their conversion */
-    uint8_t *dg;                          /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
+    /* the RGB pyramid output (ovhip_stream_set_rgb_pyramid_output): every level its own slots; its colour tables
+     * (ovhip_stream_set_rgb_pyramid_lut): [n_dev], or NULL, owned */
+    int pyr_on; int32_t pyr_n;
+    ovhip_reduce_info pyr_info;
+    ovhip_rgb_level pyr[OVHIP_PYRAMID_MAX_LEVELS];
+    slot_buf pyr_buf[OVHIP_PYRAMID_MAX_LEVELS];
+    ovhip_rgb_lut **pyr_luts; int pyr_lut_size, pyr_lut_peak;
+    uint8_t *dg;                         /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
 struct dev_queue { uint32_t *order; unsigned char *taken; uint32_t n, next; pthread_mutex_t take; pthread_cond_t moved; };
@@ -258,6 +265,11 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
             ovhip_ladder_rung rungs[OVHIP_LADDER_MAX_RUNGS];
             for (int32_t k = 0; k < s->ladder_n; ++k) { rungs[k] = s->ladder[k]; rungs[k].dst = slot_of(&s->ladder_buf[k], idx); }
             (void)ovhip_frame_set_ladder_output(f, &s->ladder_info, rungs, s->ladder_n);
+        }
+        if (s->pyr_on) {
+            ovhip_rgb_level levels[OVHIP_PYRAMID_MAX_LEVELS];
+            for (int32_t k = 0; k < s->pyr_n; ++k) { levels[k] = s->pyr[k]; levels[k].dst = slot_of(&s->pyr_buf[k], idx); }
+            (void)ovhip_frame_set_rgb_pyramid_output(f, &s->pyr_info, levels, s->pyr_n);
         }
         if (s->mvf_on) (void)ovhip_frame_set_mvfield_output(f, &s->mvf_fmt, slot_of(&s->mvf_vec, idx), s->mvf_vec.bpp, slot_of(&s->mvf_info, idx), s->mvf_info.bpp);
         const double t_sub = now_s();
@@ -499,6 +511,8 @@ ovhip_stream_destroy(ovhip_stream *s)
     free(s->surf_luts);
     for (int k = 0; s->ladder_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->ladder_luts[k]);
     free(s->ladder_luts);
+    for (int k = 0; s->pyr_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->pyr_luts[k]);
+    free(s->pyr_luts);
     free(s->ph);
     for (uint32_t i = 0; s->job_mtx && i < s->n_jobs; ++i) pthread_mutex_destroy(&s->job_mtx[i]);
     free(s->frames); free(s->out_ctx); free(s->job_mtx);
@@ -727,6 +741,67 @@ ovhip_stream_set_ladder_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int
     for (int k = 0; s->ladder_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->ladder_luts[k]);
     free(s->ladder_luts);
     s->ladder_luts = luts;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_rgb_pyramid_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table)
+{
+    if (!s) return OVHIP_EINVAL;
+    ovhip_rgb_lut **luts = NULL;
+    int r = OVHIP_OK;
+    if (host_table) {
+        /* the pyramid of the following runs, if set: its levels through this table (before anything is uploaded) */
+        if (s->pyr_on) {
+            int32_t w, h;
+            out_size(s, &w, &h);
+            if (ovhip_rgb_lut_check(size, peak, NULL) != OVHIP_OK) return OVHIP_EINVAL;
+            if ((r = ovhip_rgb_pyramid_check(w, h, &s->pyr_info, s->pyr, s->pyr_n, size, peak, NULL)) != OVHIP_OK) return r;
+        }
+        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
+        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
+        if (!luts) return OVHIP_ENOMEM;
+        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
+        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_rgb_pyramid_lut(s->frames[i], luts[i / s->tpd]);
+        if (r != OVHIP_OK) {
+            /* the previous setting stands */
+            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_pyramid_lut(s->frames[i], s->pyr_luts ? s->pyr_luts[i / s->tpd] : NULL);
+            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
+            free(luts);
+            return r;
+        }
+        s->pyr_lut_size = size; s->pyr_lut_peak = peak;
+    } else
+        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_pyramid_lut(s->frames[i], NULL);
+    for (int k = 0; s->pyr_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->pyr_luts[k]);
+    free(s->pyr_luts);
+    s->pyr_luts = luts;
+    return OVHIP_OK;
+}
+
+int
+ovhip_stream_set_rgb_pyramid_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n, uint32_t n_slots)
+{
+    if (!s) return OVHIP_EINVAL;
+    if (!levels) { s->pyr_on = 0; return OVHIP_OK; }
+    int32_t w, h;
+    ovhip_reduce_info ri;
+    memset(&ri, 0, sizeof(ri));
+    if (info) ri = *info;
+    out_size(s, &w, &h);
+    const int r = ovhip_rgb_pyramid_check(w, h, &ri, levels, n, s->pyr_luts ? s->pyr_lut_size : 0, s->pyr_luts ? s->pyr_lut_peak : 0, NULL);
+    if (r != OVHIP_OK) return r;
+    slot_buf bufs[OVHIP_PYRAMID_MAX_LEVELS];
+    for (int32_t k = 0; k < n; ++k) {
+        const size_t es = levels[k].fmt.dtype == OVHIP_RGB_U8 ? 1 : (levels[k].fmt.dtype == OVHIP_RGB_F32 ? 4 : 2);
+        /* (every slot's base is aligned to the element as the first one is) */
+        if (levels[k].dst_bytes % es) return OVHIP_EINVAL;
+        if (slot_buf_set(&bufs[k], levels[k].dst, levels[k].dst_bytes, n_slots, ovhip_rgb_bytes(levels[k].out_w, levels[k].out_h, NULL, &levels[k].fmt)) != OVHIP_OK)
+            return OVHIP_EINVAL;
+    }
+    s->pyr_on = 1; s->pyr_n = n; s->pyr_info = ri;
+    memcpy(s->pyr, levels, (size_t)n * sizeof(*levels));
+    memcpy(s->pyr_buf, bufs, (size_t)n * sizeof(*bufs));
     return OVHIP_OK;
 }
 

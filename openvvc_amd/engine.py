@@ -139,6 +139,51 @@ def _ladder_loc(chroma_loc: "int | None", conv: "capi.SurfaceConv | None") -> in
     return chroma_loc if chroma_loc is not None else (conv.src_chroma_loc if conv is not None else 0)
 
 
+def rgb_level(out_w: int, out_h: int, fmt: "capi.RgbFormat | None" = None, dst=None, slots: bool = False, nbytes: "int | None" = None) -> capi.RgbLevel:
+    """an ovhip_rgb_level (include/ovvc_hip.h, "RGB pyramid on the device"): out_w x out_h as an RGB tensor of `fmt` (default:
+    rgb_format()) at `dst` -- a contiguous torch tensor on the device of the format's dtype and the level's shape, such as one picture of
+    a batch tensor (kept alive by the level; with `slots` its first dimension counts a stream's slots and the level's bytes are one
+    slot's), an address with `nbytes`, or None for a level that only describes (rgb_pyramid_check, DevPic.rgb_pyramid)"""
+    fmt = fmt if fmt is not None else rgb_format()
+    level = capi.RgbLevel(out_w, out_h, fmt)
+    if dst is None or isinstance(dst, int):
+        level.dst, level.dst_bytes = dst or None, nbytes or 0
+    else:
+        ptr, per, n = _device_tensor(dst, "rgb pyramid output", _rgb_torch_dtypes(fmt), shape=rgb_shape(fmt, out_w, out_h), slots=slots)
+        level.dst, level.dst_bytes = ptr, per
+        level._keep, level._slots = dst, n
+    return level
+
+
+def _rgb_torch_dtypes(fmt: capi.RgbFormat) -> tuple:
+    import torch
+    want = {capi.RGB_U8: torch.uint8, capi.RGB_U16: torch.uint16, capi.RGB_F16: torch.float16, capi.RGB_F32: torch.float32}.get(fmt.dtype)
+    return (want,) if want is not None else ()
+
+
+def _level_array(levels) -> "tuple":
+    """(the C array, n) of a sequence of capi.RgbLevel"""
+    levels = list(levels)
+    return (capi.RgbLevel * max(len(levels), 1))(*levels), len(levels)
+
+
+def _pyramid_info(levels, src_window, chroma_loc: "int | None") -> capi.ReduceInfo:
+    """the pyramid's ovhip_reduce_info; chroma_loc None: the one the first level's format names (the reduced pictures keep it), else 0"""
+    levels = list(levels)
+    loc = chroma_loc if chroma_loc is not None else (levels[0].fmt.chroma_loc if levels else 0)
+    return capi.ReduceInfo(capi.Window(*src_window), loc)
+
+
+def rgb_pyramid_check(src_w: int, src_h: int, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, lut_size: int = 0,
+                      lut_peak: int = 0) -> "tuple[int, list]":
+    """(code, [(p_x, q_x, p_y, q_y) per level]) of ovhip_rgb_pyramid_check: whether src_w x src_h under src_window leaves as these levels,
+    through a table of lut_size points and peak lut_peak unless lut_size is 0.  chroma_loc None: the first level's.  Host only."""
+    arr, n = _level_array(levels)
+    ratio = ((C.c_int32 * 4) * capi.PYRAMID_MAX_LEVELS)()
+    r = capi.load().ovhip_rgb_pyramid_check(src_w, src_h, C.byref(_pyramid_info(levels, src_window, chroma_loc)), arr, n, lut_size, lut_peak, ratio)
+    return r, [tuple(ratio[k]) for k in range(min(n, capi.PYRAMID_MAX_LEVELS))]
+
+
 def mvfield_format(dtype: int = capi.MVF_I32, layout: int = capi.MVF_PLANAR, vectors: int = capi.MVF_UNIT) -> capi.MvfieldFormat:
     """an ovhip_mvfield_format (include/ovvc_hip.h, "Motion field output on the device")"""
     return capi.MvfieldFormat(dtype, layout, vectors, 0)
@@ -769,6 +814,32 @@ class DevPic:
             self.ctx._chk(r, "ladder_launch" if conv is None and lut is None else "ladder_lut_launch")
         return r
 
+    def rgb_pyramid(self, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, lut: "RgbLut | None" = None) -> "list[np.ndarray]":
+        """ovhip_pic_output_rgb_pyramid: this picture as the levels of an RGB pyramid (include/ovvc_hip.h, "RGB pyramid on the device";
+        each level an rgb_level() without a destination), written on the device by one launch and fetched -> one array per level,
+        (3, H, W) or (H, W, 3) in the level's dtype.  lut: through that colour table; chroma_loc None: the first level's"""
+        outs, full = [], []
+        for g in levels:
+            if not self.ctx.lib.ovhip_rgb_bytes(g.out_w, g.out_h, None, C.byref(g.fmt)):
+                raise EngineError("rgb_pyramid: bad size / format of a level")
+            outs.append(np.empty(rgb_shape(g.fmt, g.out_w, g.out_h), capi.RGB_NP_DTYPE[g.fmt.dtype]))
+            full.append(rgb_level(g.out_w, g.out_h, g.fmt, outs[-1].ctypes.data, nbytes=outs[-1].nbytes))
+        arr, n = _level_array(full)
+        info = _pyramid_info(full, src_window, chroma_loc)
+        self.ctx._chk(self.ctx.lib.ovhip_pic_output_rgb_pyramid(self.ctx.h, C.byref(self.s), C.byref(info), arr, n, lut.h if lut is not None else None),
+                      "pic_output_rgb_pyramid")
+        return outs
+
+    def rgb_pyramid_into(self, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, check: bool = True, lut: "RgbLut | None" = None) -> int:
+        """ovhip_rgb_pyramid_launch: every level (rgb_level() with a torch tensor or a device address) written by one launch.
+        Asynchronous.  lut: through that colour table; chroma_loc None: the first level's"""
+        arr, n = _level_array(levels)
+        r = self.ctx.lib.ovhip_rgb_pyramid_launch(self.ctx.h, C.byref(self.s), C.byref(_pyramid_info(levels, src_window, chroma_loc)), arr, n,
+                                                  lut.h if lut is not None else None)
+        if check:
+            self.ctx._chk(r, "rgb_pyramid_launch")
+        return r
+
     def row_digests(self, window=(0, 0, 0, 0)) -> np.ndarray:
         win = capi.Window(*window)
         rows = self.ctx.lib.ovhip_output_rows(self.w, self.h, C.byref(win))
@@ -1304,6 +1375,29 @@ class Frame:
             self._ladder_keep = list(rungs)
         return r
 
+    def set_rgb_pyramid_output(self, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, check: bool = True) -> int:
+        """ovhip_frame_set_rgb_pyramid_output: the NEXT picture completed is also written as the levels of an RGB pyramid (rgb_level()
+        with torch tensors on the device, kept alive here, or device addresses); None: off.  chroma_loc None: the first level's"""
+        if levels is None:
+            return self.lib.ovhip_frame_set_rgb_pyramid_output(self.f, None, None, 0)
+        arr, n = _level_array(levels)
+        r = self.lib.ovhip_frame_set_rgb_pyramid_output(self.f, C.byref(_pyramid_info(levels, src_window, chroma_loc)), arr, n)
+        if check and r:
+            raise EngineError(f"frame_set_rgb_pyramid_output: {r}")
+        if r == 0:
+            self._pyramid_keep = list(levels)
+        return r
+
+    def set_rgb_pyramid_lut(self, lut: "RgbLut | None", check: bool = True) -> int:
+        """ovhip_frame_set_rgb_pyramid_lut: while set, the levels of this frame's RGB pyramid output go through the colour table (sticky,
+        unlike the levels; kept alive here; independent of the other outputs' tables); None: off"""
+        r = self.lib.ovhip_frame_set_rgb_pyramid_lut(self.f, lut.h if lut is not None else None)
+        if check and r:
+            raise EngineError(f"frame_set_rgb_pyramid_lut: {r}")
+        if r == 0:
+            self._pyramid_lut = lut
+        return r
+
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None,
                            check: bool = True) -> int:
         """ovhip_frame_set_mvfield_output: the motion field of the NEXT picture completed goes to `vec` and `info` -- torch tensors on
@@ -1459,6 +1553,38 @@ class Stream:
             raise EngineError(f"stream_set_ladder_output: {r}")
         if r == 0:
             self._keep.append(rungs)
+        return r
+
+    def set_rgb_pyramid_output(self, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, n_slots: "int | None" = None, check: bool = True) -> int:
+        """ovhip_stream_set_rgb_pyramid_output: picture idx of the following runs is also written as the levels of an RGB pyramid, level r
+        into slot idx % n of its own destination -- rgb_level(..., slots=True) with a contiguous torch tensor on the device whose first
+        dimension is the slot count (the same for every level; kept alive here), or device addresses with the bytes per picture and
+        n_slots; None: off.  chroma_loc None: the first level's"""
+        if levels is None:
+            return self.lib.ovhip_stream_set_rgb_pyramid_output(self.s, None, None, 0, 0)
+        levels = list(levels)
+        counts = {g._slots for g in levels if hasattr(g, "_slots")}
+        if len(counts) > 1 or (counts and n_slots is not None and counts != {n_slots}):
+            raise EngineError(f"rgb pyramid output: the levels' slots differ: {sorted(counts)}")
+        arr, n = _level_array(levels)
+        r = self.lib.ovhip_stream_set_rgb_pyramid_output(self.s, C.byref(_pyramid_info(levels, src_window, chroma_loc)), arr, n,
+                                                         counts.pop() if counts else (n_slots or 0))
+        if check and r:
+            raise EngineError(f"stream_set_rgb_pyramid_output: {r}")
+        if r == 0:
+            self._keep.append(levels)
+        return r
+
+    def set_rgb_pyramid_lut(self, table: "np.ndarray | None", peak: int = 0, check: bool = True) -> int:
+        """ovhip_stream_set_rgb_pyramid_lut: the RGB pyramid output of the following runs goes through the colour table (numpy uint16 of
+        shape (S, S, S, 3), uploaded once per device, owned by the stream); None: off"""
+        if table is None:
+            r = self.lib.ovhip_stream_set_rgb_pyramid_lut(self.s, 0, 0, None)
+        else:
+            table, size = _lut_table(table, "stream_set_rgb_pyramid_lut")
+            r = self.lib.ovhip_stream_set_rgb_pyramid_lut(self.s, size, int(peak), table.ctypes.data)
+        if check and r:
+            raise EngineError(f"stream_set_rgb_pyramid_lut: {r}")
         return r
 
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes_per_picture: "int | None" = None,
