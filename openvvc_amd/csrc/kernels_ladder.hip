@@ -17,6 +17,7 @@
 #include "ovvc_outdst_priv.h"
 #include "reduce_walk.hip.h"
 #include "run_io.hip.h"
+#include "stage_out.hip.h"
 #include "surface_values.hip.h"
 
 namespace {
@@ -146,13 +147,7 @@ extern "C" int ovhip_ladder_launch(ovhip_ctx *ctx, const ovhip_pic *src, const o
     LadderArgs a;
     memset(&a, 0, sizeof(a));
     const ovhip_reduce_plan_ &p0 = pl.red[0];                                  // (the region is the same in every rung)
-    const uint16_t *sp[3] = { src->y, src->cb, src->cr };
-    for (int i = 0; i < 3; ++i) {
-        const int c = i != 0, stride = c ? src->stride_c : src->stride_y;
-        a.src[i] = sp[i] + (size_t)(p0.y0 >> c) * (size_t)stride + (size_t)(p0.x0 >> c);
-    }
-    a.sstride[0] = src->stride_y; a.sstride[1] = src->stride_c;
-    a.sw = p0.Ws; a.sh = p0.Hs;
+    rd_src_fill(a, src, p0);
     a.n_rungs = n;
     int64_t nb = 0;
     for (int k = 0; k < n; ++k) {
@@ -161,11 +156,7 @@ extern "C" int ovhip_ladder_launch(ovhip_ctx *ctx, const ovhip_pic *src, const o
         LadderRung &g = a.r[k];
         for (int q = 0; q < 3; ++q) g.dst[q] = q < sp2.n_planes ? (char *)rungs[k].dst + sp2.off[q] : nullptr;
         g.pitch[0] = sp2.pitch[0]; g.pitch[1] = sp2.pitch[1];
-        g.px = rp.px; g.qx = rp.qx; g.py = rp.py; g.qy = rp.qy;
-        g.n = rp.n; g.rcp = 1.0f / (float)rp.n;
-        rd_shape(rp, &g.ntap, &g.cpr, &g.rows);
-        g.sgx = rp.sgx; g.sgy = rp.sgy;
-        g.dw = rp.Wd; g.dh = rp.Hd;
+        rd_level_fill(g, rp);
         g.fmt = rungs[k].fmt.format; g.dither = sp2.dither;
         for (int c = 0; c < 2; ++c) g.ntx[c] = ((rp.Wd >> c) + RD_TW - 1) / RD_TW;
         const int64_t ty = (rp.Hd + RD_BAND - 1) / RD_BAND, tc = ((rp.Hd >> 1) + RD_BAND - 1) / RD_BAND;
@@ -191,49 +182,15 @@ extern "C" int ovhip_pic_output_ladder(ovhip_ctx *ctx, const ovhip_pic *pic, con
         const int q = pic ? ovhip_ladder_launch(ctx, pic, info, rungs, n) : ov_fail(ctx, OVHIP_EINVAL, "ovhip_pic_output_ladder: null picture", hipSuccess);
         return q != OVHIP_OK ? q : OVHIP_EINVAL;
     }
-    /* the rungs again with device destinations behind one another in the scratch, each on a 256-byte boundary */
-    ovhip_ladder_rung dev[OVHIP_LADDER_MAX_RUNGS];
-    size_t off[OVHIP_LADDER_MAX_RUNGS], total = 0;
-    for (int k = 0; k < n; ++k) {
-        const size_t bytes = ovhip_surface_bytes(rungs[k].out_w, rungs[k].out_h, nullptr, &rungs[k].fmt);
-        if (!rungs[k].dst || !bytes || rungs[k].dst_bytes < bytes) {
-            /* no size, a null or too small host destination: the launch refuses each before it looks at the pointer's memory */
-            const int q = ovhip_ladder_launch(ctx, pic, info, rungs, n);
-            return q != OVHIP_OK ? q : OVHIP_EINVAL;
-        }
-        off[k] = total;
-        total += (bytes + 255) & ~(size_t)255;
-        dev[k] = rungs[k];
-        dev[k].dst_bytes = bytes;
-        for (int j = 0; j < k; ++j)
-            if (ovhip_ranges_overlap_(rungs[k].dst, bytes, rungs[j].dst, dev[j].dst_bytes)) {
-                snprintf(ctx->err, sizeof(ctx->err), "ovhip_pic_output_ladder: rung %d: destination overlaps rung %d's", k, j);
-                return OVHIP_EINVAL;
-            }
-    }
-    {   /* what needs no destination is refused before the scratch grows: a refused request allocates nothing */
-        ovhip_ladder_plan_ pl;
-        char why[240];
-        const int q = ovhip_ladder_plan_make_(nullptr, pic->w, pic->h, info, rungs, n, &pl, why, sizeof(why));
-        if (q != OVHIP_OK) { snprintf(ctx->err, sizeof(ctx->err), "ovhip_pic_output_ladder: %s", why); return q; }
-    }
-    int r = ov_scratch(ctx, total, 0);
-    if (r != OVHIP_OK) return r;
-    char *d = (char *)ctx->scratch_d;
-    for (int k = 0; k < n; ++k) dev[k].dst = d + off[k];
-    r = ovhip_ladder_launch(ctx, pic, info, dev, n);
-    if (r != OVHIP_OK) return r;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < n && e == hipSuccess; ++k) {
-        const ovhip_pic red = { pic->y, pic->cb, pic->cr, dev[k].out_w, dev[k].out_h, pic->stride_y, pic->stride_c };
-        ovhip_surface_plan_ p;
-        (void)ovhip_surface_plan_make_(&red, nullptr, &dev[k].fmt, dev[k].dst, dev[k].dst_bytes, &p, nullptr);      // (accepted by the launch)
-        /* the rows' own bytes only: what lies between them in host memory stays as it was */
-        for (int q = 0; q < p.n_planes && e == hipSuccess; ++q)
-            e = hipMemcpy2DAsync((char *)rungs[k].dst + p.off[q], p.pitch[q], (char *)dev[k].dst + p.off[q], p.pitch[q], (size_t)p.elems[q] * p.es,
-                                 (size_t)p.rows[q], hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e != hipSuccess) return ov_fail(ctx, OVHIP_ENODEV, "ovhip_pic_output_ladder: D2H", e);
-    if (ov_sync_stream(ctx) != hipSuccess) return ov_fail(ctx, OVHIP_ELAUNCH, "ovhip_pic_output_ladder", hipGetLastError());
-    return OVHIP_OK;
+    OvStaged<ovhip_ladder_rung> st(rungs, n, [](const ovhip_ladder_rung &g) { return ovhip_surface_bytes(g.out_w, g.out_h, nullptr, &g.fmt); });
+    return ov_stage_out(ctx, "ovhip_pic_output_ladder", "rung", st,
+        [&](const ovhip_ladder_rung *d) { return ovhip_ladder_launch(ctx, pic, info, d, n); },
+        [&] {
+            ovhip_ladder_plan_ pl;
+            char why[240];
+            const int q = ovhip_ladder_plan_make_(nullptr, pic->w, pic->h, info, rungs, n, &pl, why, sizeof(why));
+            if (q != OVHIP_OK) snprintf(ctx->err, sizeof(ctx->err), "ovhip_pic_output_ladder: %s", why);
+            return q;
+        },
+        [&](const ovhip_ladder_rung &d, void *host) { return ov_stage_rung_back(ctx, pic, d, host); });
 }

@@ -39,6 +39,7 @@
 #include "ovvc_outdst_priv.h"
 #include "reduce_walk.hip.h"
 #include "run_io.hip.h"
+#include "stage_out.hip.h"
 #include "colour_stage.hip.h"
 
 namespace {
@@ -254,13 +255,7 @@ extern "C" int ovhip_rgb_pyramid_launch(ovhip_ctx *ctx, const ovhip_pic *src, co
     PyArgs a;
     memset(&a, 0, sizeof(a));
     const ovhip_reduce_plan_ &p0 = pl.red[0];                                  // (the region is the same in every level)
-    const uint16_t *sp[3] = { src->y, src->cb, src->cr };
-    for (int i = 0; i < 3; ++i) {
-        const int c = i != 0, stride = c ? src->stride_c : src->stride_y;
-        a.src[i] = sp[i] + (size_t)(p0.y0 >> c) * (size_t)stride + (size_t)(p0.x0 >> c);
-    }
-    a.sstride[0] = src->stride_y; a.sstride[1] = src->stride_c;
-    a.sw = p0.Ws; a.sh = p0.Hs;
+    rd_src_fill(a, src, p0);
     a.n_levels = n;
     a.peak[0] = 1023; a.peak[1] = 255;
     int64_t nb = 0;
@@ -268,11 +263,7 @@ extern "C" int ovhip_rgb_pyramid_launch(ovhip_ctx *ctx, const ovhip_pic *src, co
         const ovhip_reduce_plan_ &rp = pl.red[k];
         PyLevel &g = a.r[k];
         g.dst = (char *)levels[k].dst;
-        g.px = rp.px; g.qx = rp.qx; g.py = rp.py; g.qy = rp.qy;
-        g.n = rp.n; g.rcp = 1.0f / (float)rp.n;
-        rd_shape(rp, &g.ntap, &g.cpr, &g.rows);
-        g.sgx = rp.sgx; g.sgy = rp.sgy;
-        g.dw = rp.Wd; g.dh = rp.Hd;
+        rd_level_fill(g, rp);
         g.dtype = (int)levels[k].fmt.dtype; g.packed = levels[k].fmt.layout == OVHIP_RGB_PACKED;
         g.cs = pl.rgb[k].peak == 255;                                          // (the level's plan: by the table 1023 whatever the dtype)
         py_col_fill(a.c[g.cs], pl.rgb[k]);
@@ -307,43 +298,17 @@ extern "C" int ovhip_pic_output_rgb_pyramid(ovhip_ctx *ctx, const ovhip_pic *pic
         const int q = ovhip_rgb_pyramid_launch(ctx, pic, info, levels, n, lut);
         return q != OVHIP_OK ? q : OVHIP_EINVAL;
     }
-    /* the levels again with device destinations behind one another in the scratch, each on a 256-byte boundary */
-    ovhip_rgb_level dev[OVHIP_PYRAMID_MAX_LEVELS];
-    size_t off[OVHIP_PYRAMID_MAX_LEVELS], total = 0;
-    for (int k = 0; k < n; ++k) {
-        const size_t bytes = ovhip_rgb_bytes(levels[k].out_w, levels[k].out_h, nullptr, &levels[k].fmt);
-        if (!levels[k].dst || !bytes || levels[k].dst_bytes < bytes) {
-            /* no size, a null or too small host destination: the launch refuses each before it looks at the pointer's memory */
-            const int q = ovhip_rgb_pyramid_launch(ctx, pic, info, levels, n, lut);
-            return q != OVHIP_OK ? q : OVHIP_EINVAL;
-        }
-        off[k] = total;
-        total += (bytes + 255) & ~(size_t)255;
-        dev[k] = levels[k];
-        dev[k].dst_bytes = bytes;
-        for (int j = 0; j < k; ++j)
-            if (ovhip_ranges_overlap_(levels[k].dst, bytes, levels[j].dst, dev[j].dst_bytes)) {
-                snprintf(ctx->err, sizeof(ctx->err), "ovhip_pic_output_rgb_pyramid: level %d: destination overlaps level %d's", k, j);
-                return OVHIP_EINVAL;
-            }
-    }
-    {   /* what needs no destination is refused before the scratch grows: a refused request allocates nothing */
-        ovhip_rgb_pyramid_plan_ pl;
-        char why[240];
-        int q = ovhip_rgb_pyramid_plan_make_(nullptr, pic->w, pic->h, info, levels, n, lut != NULL, lut ? lut->size : 0, lut ? lut->peak : 0, 1, &pl, why, sizeof(why));
-        if (q == OVHIP_OK && lut && lut->device != ctx->device) { snprintf(why, sizeof(why), "the table lives on another device"); q = OVHIP_EINVAL; }
-        if (q != OVHIP_OK) { snprintf(ctx->err, sizeof(ctx->err), "ovhip_pic_output_rgb_pyramid: %s", why); return q; }
-    }
-    int r = ov_scratch(ctx, total, 0);
-    if (r != OVHIP_OK) return r;
-    char *d = (char *)ctx->scratch_d;
-    for (int k = 0; k < n; ++k) dev[k].dst = d + off[k];
-    r = ovhip_rgb_pyramid_launch(ctx, pic, info, dev, n, lut);
-    if (r != OVHIP_OK) return r;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < n && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(levels[k].dst, dev[k].dst, dev[k].dst_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) return ov_fail(ctx, OVHIP_ENODEV, "ovhip_pic_output_rgb_pyramid: D2H", e);
-    if (ov_sync_stream(ctx) != hipSuccess) return ov_fail(ctx, OVHIP_ELAUNCH, "ovhip_pic_output_rgb_pyramid", hipGetLastError());
-    return OVHIP_OK;
+    OvStaged<ovhip_rgb_level> st(levels, n, [](const ovhip_rgb_level &g) { return ovhip_rgb_bytes(g.out_w, g.out_h, nullptr, &g.fmt); });
+    return ov_stage_out(ctx, "ovhip_pic_output_rgb_pyramid", "level", st,
+        [&](const ovhip_rgb_level *d) { return ovhip_rgb_pyramid_launch(ctx, pic, info, d, n, lut); },
+        [&] {
+            ovhip_rgb_pyramid_plan_ pl;
+            char why[240];
+            int q = ovhip_rgb_pyramid_plan_make_(nullptr, pic->w, pic->h, info, levels, n, lut != NULL, lut ? lut->size : 0, lut ? lut->peak : 0, 1, &pl, why, sizeof(why));
+            if (q == OVHIP_OK && lut && lut->device != ctx->device) { snprintf(why, sizeof(why), "the table lives on another device"); q = OVHIP_EINVAL; }
+            if (q != OVHIP_OK) snprintf(ctx->err, sizeof(ctx->err), "ovhip_pic_output_rgb_pyramid: %s", why);
+            return q;
+        },
+        /* a level is dense: one copy */
+        [&](const ovhip_rgb_level &d, void *host) { return hipMemcpyAsync(host, d.dst, d.dst_bytes, hipMemcpyDeviceToHost, ctx->stream); });
 }

@@ -22,6 +22,13 @@ typedef struct ovhip_post_ {
     const ovhip_fg_model *model; int32_t poc;          /* GRAIN: an already derived model (ovhip_fg_derive) and the picture's POC */
     ovhip_reduce_info rinfo;                           /* REDUCE: out_w x out_h as SCALE's; the source window / chroma location */
 } ovhip_post_;
+/* the size the outputs read under `post` of a w x h picture: SCALE and REDUCE leave post->out_w x out_h, grain leaves the picture's */
+static inline void
+ovhip_post_size_(const ovhip_post_ *post, int32_t w, int32_t h, int32_t *sw, int32_t *sh)
+{
+    const int resized = post->kind == OVHIP_POST_SCALE || post->kind == OVHIP_POST_REDUCE;
+    *sw = resized ? post->out_w : w; *sh = resized ? post->out_h : h;
+}
 /* *shown = the picture the output shows.  NONE: *pic itself, nothing launched, nothing allocated.  Otherwise the refusals of the kind's
  * launcher come first (same codes, reasons in the context's error text), then `pic` is resampled / grained / reduced into the context's
  * grow-only scratch picture, asynchronously on the context's stream, and that is handed out: it stays valid until the context's next

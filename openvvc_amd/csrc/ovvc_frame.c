@@ -24,15 +24,26 @@
 
 static double mono_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 
-/* one per-picture output: RGB and surface write dst[0] through the window `win`; the motion field writes its vectors to dst[0] and its
- * info to dst[1] (either may be NULL) from the arrays of the job that decoded the picture */
-enum { OUT_RGB, OUT_SURFACE, OUT_MVFIELD, N_OUTS };
+/* one per-picture output, in the order picture_end runs them.  RGB and surface write dst[0] through the window `win`; the motion field
+ * writes its vectors to dst[0] and its info to dst[1] (either may be NULL) from the arrays of the job that decoded the picture; the
+ * ladder and the RGB pyramid carry their rungs / levels, the pyramid also the size w x h it was checked against */
+enum { OUT_RGB, OUT_SURFACE, OUT_LADDER, OUT_PYRAMID, OUT_MVFIELD, N_OUTS };
+#define N_LUT_OUTS OUT_MVFIELD            /* the outputs in front of the motion field show the picture: each may go through a colour table */
 typedef struct frame_out {
     int on;
-    union { ovhip_rgb_format rgb; ovhip_surface_format surf; ovhip_mvfield_format mvf; } fmt;
-    ovhip_window win;
-    void *dst[2]; size_t bytes[2];
+    union {
+        struct {
+            union { ovhip_rgb_format rgb; ovhip_surface_format surf; ovhip_mvfield_format mvf; } fmt;
+            ovhip_window win;
+            void *dst[2]; size_t bytes[2];
+        };
+        struct { ovhip_reduce_info info; int32_t n; ovhip_ladder_rung rungs[OVHIP_LADDER_MAX_RUNGS]; } ladder;
+        struct { ovhip_reduce_info info; int32_t n, w, h; ovhip_rgb_level levels[OVHIP_PYRAMID_MAX_LEVELS]; } pyr;
+    };
 } frame_out;
+/* the colour table of such an output (ovhip_frame_set_rgb_lut / _surface_lut / _ladder_lut / _rgb_pyramid_lut) and, where the output
+ * converts through it, the conversion: sticky, the table borrowed, NULL: none */
+typedef struct frame_lut { const ovhip_rgb_lut *lut; ovhip_surface_conv conv; } frame_lut;
 
 struct ovhip_frame {
     ovhip_dpb *dpb;
@@ -66,27 +77,11 @@ struct ovhip_frame {
      * one, what the last one gave */
     int hash_on, hash_method, hash_planes, hash_expect, hash_done;
     ovhip_pic_hash_value hash_expected, hash_computed;
-    /* the per-picture outputs (ovhip_frame_set_rgb_output / _surface_output / _mvfield_output) of the NEXT picture completed, each
-     * independent of the others: the destinations are that picture's, so the settings end with it (picture_end) */
+    /* the per-picture outputs (ovhip_frame_set_rgb_output / _surface_output / _ladder_output / _rgb_pyramid_output / _mvfield_output) of
+     * the NEXT picture completed, each independent of the others: the destinations are that picture's, so the settings end with it
+     * (picture_end); their colour tables do not */
     frame_out outs[N_OUTS];
-    /* the ladder output (ovhip_frame_set_ladder_output) of the NEXT picture completed, beside them and ending with the picture as they do */
-    int ladder_on; int32_t ladder_n;
-    ovhip_reduce_info ladder_info;
-    ovhip_ladder_rung ladder[OVHIP_LADDER_MAX_RUNGS];
-    /* the colour table of the RGB output (ovhip_frame_set_rgb_lut): sticky, borrowed, NULL: none */
-    const ovhip_rgb_lut *rgb_lut;
-    /* the colour table and the conversion of the surface output (ovhip_frame_set_surface_lut): sticky, the table borrowed, NULL: none */
-    const ovhip_rgb_lut *surf_lut;
-    ovhip_surface_conv surf_conv;
-    /* the colour table and the conversion of the ladder output (ovhip_frame_set_ladder_lut): sticky, the table borrowed, NULL: none */
-    const ovhip_rgb_lut *ladder_lut;
-    ovhip_surface_conv ladder_conv;
-    /* the RGB pyramid output (ovhip_frame_set_rgb_pyramid_output) of the NEXT picture completed, beside them and ending with the picture
-     * as they do; pyr_w x pyr_h: the size it was checked against.  Its colour table (ovhip_frame_set_rgb_pyramid_lut): sticky, borrowed */
-    int pyr_on; int32_t pyr_n, pyr_w, pyr_h;
-    ovhip_reduce_info pyr_info;
-    ovhip_rgb_level pyr[OVHIP_PYRAMID_MAX_LEVELS];
-    const ovhip_rgb_lut *pyr_lut;
+    frame_lut luts[N_LUT_OUTS];
     /* OVVC_HIP_FRAME_PROF=1: where the frame-level calls spend their wall time, printed when the frame is destroyed (seconds) */
     double pt_collect, pt_rows_begin, pt_band_refs, pt_band_job, pt_final_refs, pt_job_wait, pt_output, pt_submit; int pn_pics;
     double pt_fl_prepare, pt_fl_upload, pt_fl_refs, pt_fl_launch;      /* ovhip_job_flush by phase (ovhip_job_stats.host_us_*) */
@@ -401,7 +396,7 @@ publish(ovhip_frame *f, int status)
 }
 
 /* a picture that ends, however it ends, takes its RGB, surface, ladder, pyramid and motion field destinations with it */
-static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; f->ladder_on = 0; f->pyr_on = 0; }
+static void outs_clear(ovhip_frame *f) { for (int k = 0; k < N_OUTS; ++k) f->outs[k].on = 0; }
 
 int
 ovhip_frame_fail(ovhip_frame *f, int status)
@@ -510,44 +505,35 @@ ovhip_frame_set_rgb_output(ovhip_frame *f, const ovhip_rgb_format *fmt, const ov
     return out_store(f, OUT_RGB, fmt, sizeof(*fmt), win, d_dst, dst_bytes, NULL, 0);
 }
 
-int
-ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut)
-{
-    if (!f) return OVHIP_EINVAL;
-    if (lut && !f->dry && !ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
-    f->rgb_lut = f->dry ? NULL : lut;                          /* (a dry frame has no picture to convert) */
-    return OVHIP_OK;
-}
-
-int
-ovhip_frame_set_surface_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv)
+/* What the four table setters below have in common: the conversion's own refusals where the output has one, the table's device, the
+ * output's own extra check of what is already set for the next picture, and the dry-frame rule.  conv: read for the surface and the ladder only */
+static int
+lut_store(ovhip_frame *f, int which, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv)
 {
     if (!f) return OVHIP_EINVAL;
     if (lut) {
-        const int r = ovhip_surface_conv_check_(conv, NULL);
-        if (r != OVHIP_OK) return r;
+        const frame_out *o = &f->outs[which];
+        const int has_conv = which == OUT_SURFACE || which == OUT_LADDER;
+        int r;
+        if (has_conv && (r = ovhip_surface_conv_check_(conv, NULL)) != OVHIP_OK) return r;
         if (!f->dry && !ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
-        f->surf_conv = *conv;
+        /* (a dry frame never has an output set: the two checks below are a live frame's) */
+        /* meant: a ladder already set for the next picture is asked for its sample location only -- the reduced pictures keep ITS
+         * location --, not checked again through the table */
+        if (which == OUT_LADDER && o->on && conv->src_chroma_loc != o->ladder.info.chroma_loc) return OVHIP_EINVAL;
+        /* meant: a pyramid already set for the next picture is checked again in full, its levels through THIS table (a U8 level and the peak) */
+        if (which == OUT_PYRAMID && o->on
+            && (r = ovhip_rgb_pyramid_check(o->pyr.w, o->pyr.h, &o->pyr.info, o->pyr.levels, o->pyr.n, lut->size, lut->peak, NULL)) != OVHIP_OK) return r;
+        if (has_conv) f->luts[which].conv = *conv;
     }
-    f->surf_lut = f->dry ? NULL : lut;                         /* (a dry frame has no picture to convert) */
+    f->luts[which].lut = f->dry ? NULL : lut;                  /* (a dry frame has no picture to convert) */
     return OVHIP_OK;
 }
 
-int
-ovhip_frame_set_ladder_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv)
-{
-    if (!f) return OVHIP_EINVAL;
-    if (lut) {
-        const int r = ovhip_surface_conv_check_(conv, NULL);
-        if (r != OVHIP_OK) return r;
-        if (!f->dry && !ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
-        /* a ladder already set for the next picture: the reduced pictures keep ITS sample location */
-        if (f->ladder_on && conv->src_chroma_loc != f->ladder_info.chroma_loc) return OVHIP_EINVAL;
-        f->ladder_conv = *conv;
-    }
-    f->ladder_lut = f->dry ? NULL : lut;                       /* (a dry frame has no picture to convert) */
-    return OVHIP_OK;
-}
+int ovhip_frame_set_rgb_lut(ovhip_frame *f, const ovhip_rgb_lut *lut) { return lut_store(f, OUT_RGB, lut, NULL); }
+int ovhip_frame_set_surface_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv) { return lut_store(f, OUT_SURFACE, lut, conv); }
+int ovhip_frame_set_ladder_lut(ovhip_frame *f, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv) { return lut_store(f, OUT_LADDER, lut, conv); }
+int ovhip_frame_set_rgb_pyramid_lut(ovhip_frame *f, const ovhip_rgb_lut *lut) { return lut_store(f, OUT_PYRAMID, lut, NULL); }
 
 int
 ovhip_frame_set_surface_output(ovhip_frame *f, const ovhip_surface_format *fmt, const ovhip_window *win, void *d_dst, size_t dst_bytes)
@@ -565,7 +551,7 @@ int
 ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!rungs) { f->ladder_on = 0; return OVHIP_OK; }
+    if (!rungs) { f->outs[OUT_LADDER].on = 0; return OVHIP_OK; }
     if (n < 1 || n > OVHIP_LADDER_MAX_RUNGS) return OVHIP_EINVAL;
     ovhip_reduce_info ri;
     memset(&ri, 0, sizeof(ri));
@@ -575,33 +561,19 @@ ovhip_frame_set_ladder_output(ovhip_frame *f, const ovhip_reduce_info *info, con
         if (r != OVHIP_OK) return r;
         if (!rungs[k].dst) return OVHIP_EINVAL;
     }
+    /* meant: a dry frame answers BEFORE the ladder is checked against a size (the pyramid's setter checks first) */
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to reduce) */
-    /* the size the ladder reads: the one the post-process step set now leaves (grain leaves the frame's) */
-    const int resized = f->post.kind == OVHIP_POST_SCALE || f->post.kind == OVHIP_POST_REDUCE;
-    const int32_t sw = resized ? f->post.out_w : f->w, sh = resized ? f->post.out_h : f->h;
+    /* the size the ladder reads: the one the post-process step set now leaves */
+    int32_t sw, sh;
+    ovhip_post_size_(&f->post, f->w, f->h, &sw, &sh);
     /* with a table set, the table's share too: the location the conversion reads, rung sizes in multiples of 4 */
-    const int r = f->ladder_lut ? ovhip_ladder_lut_check(sw, sh, &ri, rungs, n, &f->ladder_conv, f->ladder_lut->size, f->ladder_lut->peak, NULL)
-                                : ovhip_ladder_check(sw, sh, &ri, rungs, n, NULL);
+    const frame_lut *t = &f->luts[OUT_LADDER];
+    const int r = t->lut ? ovhip_ladder_lut_check(sw, sh, &ri, rungs, n, &t->conv, t->lut->size, t->lut->peak, NULL) : ovhip_ladder_check(sw, sh, &ri, rungs, n, NULL);
     if (r != OVHIP_OK) return r;
-    f->ladder_info = ri; f->ladder_n = n;
-    memcpy(f->ladder, rungs, (size_t)n * sizeof(*rungs));
-    f->ladder_on = 1;
-    return OVHIP_OK;
-}
-
-int
-ovhip_frame_set_rgb_pyramid_lut(ovhip_frame *f, const ovhip_rgb_lut *lut)
-{
-    if (!f) return OVHIP_EINVAL;
-    if (lut && !f->dry) {
-        if (!ovhip_rgb_lut_on_ctx_(lut, f->ctx)) return OVHIP_EINVAL;
-        /* a pyramid already set for the next picture: its levels through THIS table (a U8 level and the peak) */
-        if (f->pyr_on) {
-            const int r = ovhip_rgb_pyramid_check(f->pyr_w, f->pyr_h, &f->pyr_info, f->pyr, f->pyr_n, lut->size, lut->peak, NULL);
-            if (r != OVHIP_OK) return r;
-        }
-    }
-    f->pyr_lut = f->dry ? NULL : lut;                          /* (a dry frame has no picture to convert) */
+    frame_out *o = &f->outs[OUT_LADDER];
+    o->ladder.info = ri; o->ladder.n = n;
+    memcpy(o->ladder.rungs, rungs, (size_t)n * sizeof(*rungs));
+    o->on = 1;
     return OVHIP_OK;
 }
 
@@ -609,22 +581,25 @@ int
 ovhip_frame_set_rgb_pyramid_output(ovhip_frame *f, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n)
 {
     if (!f) return OVHIP_EINVAL;
-    if (!levels) { f->pyr_on = 0; return OVHIP_OK; }
+    if (!levels) { f->outs[OUT_PYRAMID].on = 0; return OVHIP_OK; }
     if (n < 1 || n > OVHIP_PYRAMID_MAX_LEVELS) return OVHIP_EINVAL;
     ovhip_reduce_info ri;
     memset(&ri, 0, sizeof(ri));
     if (info) ri = *info;
     for (int32_t k = 0; k < n; ++k)                           /* what needs no picture comes back here */
         if (!levels[k].dst) return OVHIP_EINVAL;
-    /* the size the pyramid reads: the one the post-process step set now leaves (grain leaves the frame's) */
-    const int resized = f->post.kind == OVHIP_POST_SCALE || f->post.kind == OVHIP_POST_REDUCE;
-    const int32_t sw = resized ? f->post.out_w : f->w, sh = resized ? f->post.out_h : f->h;
-    const int r = ovhip_rgb_pyramid_check(sw, sh, &ri, levels, n, f->pyr_lut ? f->pyr_lut->size : 0, f->pyr_lut ? f->pyr_lut->peak : 0, NULL);
+    /* the size the pyramid reads: the one the post-process step set now leaves */
+    int32_t sw, sh;
+    ovhip_post_size_(&f->post, f->w, f->h, &sw, &sh);
+    const ovhip_rgb_lut *lut = f->luts[OUT_PYRAMID].lut;
+    const int r = ovhip_rgb_pyramid_check(sw, sh, &ri, levels, n, lut ? lut->size : 0, lut ? lut->peak : 0, NULL);
     if (r != OVHIP_OK) return r;
+    /* meant: a dry frame answers only AFTER the check (the ladder's setter answers before its own) */
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no picture to reduce: it answers and remembers nothing) */
-    f->pyr_info = ri; f->pyr_n = n; f->pyr_w = sw; f->pyr_h = sh;
-    memcpy(f->pyr, levels, (size_t)n * sizeof(*levels));
-    f->pyr_on = 1;
+    frame_out *o = &f->outs[OUT_PYRAMID];
+    o->pyr.info = ri; o->pyr.n = n; o->pyr.w = sw; o->pyr.h = sh;
+    memcpy(o->pyr.levels, levels, (size_t)n * sizeof(*levels));
+    o->on = 1;
     return OVHIP_OK;
 }
 
@@ -636,7 +611,7 @@ ovhip_frame_set_mvfield_output(ovhip_frame *f, const ovhip_mvfield_format *fmt, 
     const int r = ovhip_mvfield_dst_check_(fmt, d_vec, vec_bytes, d_info, info_bytes, NULL);   /* the refusals that need no picture come back here */
     if (r != OVHIP_OK) return r;
     if (f->dry) return OVHIP_OK;                               /* (a dry frame has no motion to export) */
-    if (f->band_mode) return OVHIP_EUNSUP;                     /* (a band-wise picture's arrays live in band arenas: ovhip_job_mvfield) */
+    if (f->band_mode) return OVHIP_EUNSUP;                     /* (meant, and this output's alone: a band-wise picture's arrays live in band arenas: ovhip_job_mvfield) */
     return out_store(f, OUT_MVFIELD, fmt, sizeof(*fmt), NULL, d_vec, vec_bytes, d_info, info_bytes);
 }
 
@@ -674,7 +649,8 @@ static int
 picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_frame_output *out)
 {
     if (f->dry) { if (f->status) r = f->status; (void)publish(f, r); return r; }
-    frame_out *rgb = &f->outs[OUT_RGB], *surf = &f->outs[OUT_SURFACE], *mvf = &f->outs[OUT_MVFIELD];
+    static const char *const name[N_OUTS] = { "RGB output", "surface output", "ladder output", "RGB pyramid output", "motion field output" };
+    frame_out *mvf = &f->outs[OUT_MVFIELD];
     /* the motion field step reads the borrowed job's arrays on this frame's stream: the job goes home behind it */
     const int keep_job = borrowed && mvf->on && r == OVHIP_OK;
     if (borrowed && !keep_job) { int q = ovhip_job_bind(borrowed, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
@@ -689,34 +665,35 @@ picture_end(ovhip_frame *f, int r, ovhip_job *j, ovhip_job *borrowed, ovhip_fram
         if ((r = ovhip_pic_hash(f->ctx, &f->dst, f->hash_method, f->hash_planes, &f->hash_computed)) != OVHIP_OK) fail(f, r, "picture hash");
         else f->hash_done = !f->hash_expect || ovhip_pic_hash_equal(&f->hash_computed, &f->hash_expected) ? 1 : -1;
     }
-    if (r == OVHIP_OK && rgb->on) {
+    /* the outputs that show the picture, in the enum's order: the launch (through the output's table when one is set), then the wait */
+    for (int k = 0; k < N_LUT_OUTS && r == OVHIP_OK; ++k) {
+        const frame_out *o = &f->outs[k];
+        const ovhip_rgb_lut *lut = f->luts[k].lut;
+        const ovhip_surface_conv *conv = &f->luts[k].conv;
+        if (!o->on) continue;
         if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK)
-            r = f->rgb_lut ? ovhip_rgb_lut_launch(f->ctx, &shown, &rgb->win, &rgb->fmt.rgb, f->rgb_lut, rgb->dst[0], rgb->bytes[0])
-                           : ovhip_rgb_launch(f->ctx, &shown, &rgb->win, &rgb->fmt.rgb, rgb->dst[0], rgb->bytes[0]);
-        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "RGB output");
-        if (r != OVHIP_OK) fail(f, r, "RGB output");
-    }
-    if (r == OVHIP_OK && surf->on) {
-        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK)
-            r = f->surf_lut ? ovhip_surface_lut_launch(f->ctx, &shown, &surf->win, &f->surf_conv, &surf->fmt.surf, f->surf_lut, surf->dst[0], surf->bytes[0])
-                            : ovhip_surface_launch(f->ctx, &shown, &surf->win, &surf->fmt.surf, surf->dst[0], surf->bytes[0]);
-        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "surface output");
-        if (r != OVHIP_OK) fail(f, r, "surface output");
-    }
-    if (r == OVHIP_OK && f->ladder_on) {
-        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) 
-            r = f->ladder_lut ? ovhip_ladder_lut_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n, &f->ladder_conv, f->ladder_lut)
-                              : ovhip_ladder_launch(f->ctx, &shown, &f->ladder_info, f->ladder, f->ladder_n);
-        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "ladder output");
-        if (r != OVHIP_OK) fail(f, r, "ladder output");
-    }
-    if (r == OVHIP_OK && f->pyr_on) {
-        if ((r = frame_shown(f, &shown, &have)) == OVHIP_OK) r = ovhip_rgb_pyramid_launch(f->ctx, &shown, &f->pyr_info, f->pyr, f->pyr_n, f->pyr_lut);
-        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, "RGB pyramid output");
-        if (r != OVHIP_OK) fail(f, r, "RGB pyramid output");
+            switch (k) {
+            case OUT_RGB:
+                r = lut ? ovhip_rgb_lut_launch(f->ctx, &shown, &o->win, &o->fmt.rgb, lut, o->dst[0], o->bytes[0])
+                        : ovhip_rgb_launch(f->ctx, &shown, &o->win, &o->fmt.rgb, o->dst[0], o->bytes[0]);
+                break;
+            case OUT_SURFACE:
+                r = lut ? ovhip_surface_lut_launch(f->ctx, &shown, &o->win, conv, &o->fmt.surf, lut, o->dst[0], o->bytes[0])
+                        : ovhip_surface_launch(f->ctx, &shown, &o->win, &o->fmt.surf, o->dst[0], o->bytes[0]);
+                break;
+            case OUT_LADDER:
+                r = lut ? ovhip_ladder_lut_launch(f->ctx, &shown, &o->ladder.info, o->ladder.rungs, o->ladder.n, conv, lut)
+                        : ovhip_ladder_launch(f->ctx, &shown, &o->ladder.info, o->ladder.rungs, o->ladder.n);
+                break;
+            default:
+                r = ovhip_rgb_pyramid_launch(f->ctx, &shown, &o->pyr.info, o->pyr.levels, o->pyr.n, lut);
+                break;
+            }
+        if (r == OVHIP_OK) r = ovhip_wait_(f->ctx, name[k]);
+        if (r != OVHIP_OK) fail(f, r, name[k]);
     }
     if (r == OVHIP_OK && mvf->on && (r = ovhip_job_mvfield_done_(j, &mvf->fmt.mvf, mvf->dst[0], mvf->bytes[0], mvf->dst[1], mvf->bytes[1])) != OVHIP_OK)
-        fail(f, r, "motion field output");
+        fail(f, r, name[OUT_MVFIELD]);
     outs_clear(f);                        /* whatever happened: a picture that failed takes its destinations with it */
     if (keep_job) { int q = ovhip_job_bind(borrowed, NULL); if (q != OVHIP_OK && r == OVHIP_OK) r = fail(f, q, "ovhip_job_bind(home)"); }
     if (r == OVHIP_OK && out && out->mode != OVHIP_OUT_NONE) {

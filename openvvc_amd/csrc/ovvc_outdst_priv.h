@@ -25,6 +25,27 @@ ovhip_ranges_overlap_(const void *a, size_t na, const void *b, size_t nb)
     return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
 }
 
+/* The staging plan of an output that leaves as n host destinations through one device scratch (the ladder's rungs, the pyramid's levels):
+ * item k has the host destination dst[k] of given[k] bytes and needs need[k] of them.  The items are asked in order, each first for
+ * itself, then against the items before it.  OVHIP_STAGE_OK_: off[k] is item k's place in the scratch, on a 256-byte boundary, and
+ * *total the scratch's size.  OVHIP_STAGE_UNFIT_: item *k has no destination, needs nothing (its size was refused) or was given too
+ * little.  OVHIP_STAGE_OVERLAP_: the need[*k] bytes of item *k overlap the need[*j] bytes of the earlier item *j.  Nothing is read
+ * through the pointers */
+enum { OVHIP_STAGE_OK_ = 0, OVHIP_STAGE_UNFIT_, OVHIP_STAGE_OVERLAP_ };
+static inline int
+ovhip_stage_plan_(int n, void *const *dst, const size_t *given, const size_t *need, size_t *off, size_t *total, int *k, int *j)
+{
+    *total = 0;
+    for (*k = 0; *k < n; ++*k) {
+        if (!dst[*k] || !need[*k] || given[*k] < need[*k]) return OVHIP_STAGE_UNFIT_;
+        off[*k] = *total;
+        *total += (need[*k] + 255) & ~(size_t)255;
+        for (*j = 0; *j < *k; ++*j)
+            if (ovhip_ranges_overlap_(dst[*k], need[*k], dst[*j], need[*j])) return OVHIP_STAGE_OVERLAP_;
+    }
+    return OVHIP_STAGE_OK_;
+}
+
 static inline const char *
 ovhip_out_why_planes_(const ovhip_pic *pic)
 {

@@ -16,6 +16,7 @@
  */
 #define _GNU_SOURCE
 #include <pthread.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,6 +35,33 @@ int ovhip_upload_streams_clear_of_(ovhip_ctx *keep_clear);     /* ovvc_picture.h
 /* a caller's device buffer of `slots` pictures' worth of an output, `bpp` bytes apart: picture idx lands in slot idx % slots */
 typedef struct slot_buf { char *base; size_t bpp; uint32_t slots; } slot_buf;
 static void *slot_of(const slot_buf *b, uint32_t idx) { return b->base ? b->base + (size_t)(idx % b->slots) * b->bpp : NULL; }
+
+/* an output of several destinations per picture -- the ladder's rungs, the RGB pyramid's levels --, every item its own slots.  The two
+ * item types differ in their format only; multi_items says where an item's destination and its bytes lie */
+#define MULTI_MAX 8
+_Static_assert(OVHIP_LADDER_MAX_RUNGS == MULTI_MAX && OVHIP_PYRAMID_MAX_LEVELS == MULTI_MAX, "one record holds a ladder or a pyramid");
+typedef struct multi_out {
+    int on; int32_t n;
+    ovhip_reduce_info info;
+    union { ovhip_ladder_rung rungs[MULTI_MAX]; ovhip_rgb_level levels[MULTI_MAX]; } item;
+    slot_buf buf[MULTI_MAX];
+} multi_out;
+typedef struct multi_items { size_t stride, off_dst, off_bytes; } multi_items;
+static const multi_items RUNGS = { sizeof(ovhip_ladder_rung), offsetof(ovhip_ladder_rung, dst), offsetof(ovhip_ladder_rung, dst_bytes) };
+static const multi_items LEVELS = { sizeof(ovhip_rgb_level), offsetof(ovhip_rgb_level, dst), offsetof(ovhip_rgb_level, dst_bytes) };
+
+/* items[0 .. m->n): the output's items with picture idx's slot of each as the destination */
+static void
+multi_point(const multi_out *m, const multi_items *t, uint32_t idx, void *items)
+{
+    memcpy(items, &m->item, (size_t)m->n * t->stride);
+    for (int32_t k = 0; k < m->n; ++k) *(void **)((char *)items + (size_t)k * t->stride + t->off_dst) = slot_of(&m->buf[k], idx);
+}
+
+/* the colour tables of one output, one per device ([n_dev], or NULL: none), owned; what they were made of, and the conversion of an
+ * output that has one */
+enum { TAB_RGB, TAB_SURFACE, TAB_LADDER, TAB_PYRAMID, N_TABS };
+typedef struct stream_lut { ovhip_rgb_lut **luts; int size, peak; ovhip_surface_conv conv; } stream_lut;
 
 struct ovhip_stream {
     ovhip_dpb *dpb;
@@ -66,23 +94,8 @@ struct ovhip_stream {
     ovhip_rgb_format rgb_fmt; ovhip_surface_format surf_fmt; ovhip_mvfield_format mvf_fmt;
     ovhip_window rgb_win, surf_win;
     slot_buf rgb_buf, surf_buf, mvf_vec, mvf_info;
-    /* the ladder output (ovhip_stream_set_ladder_output): every rung its own slots */
-    int ladder_on; int32_t ladder_n;
-    ovhip_reduce_info ladder_info;
-    ovhip_ladder_rung ladder[OVHIP_LADDER_MAX_RUNGS];
-    slot_buf ladder_buf[OVHIP_LADDER_MAX_RUNGS];
-    ovhip_rgb_lut **rgb_luts;             /* [n_dev], or NULL: the colour tables of the RGB output (ovhip_stream_set_rgb_lut), owned */
-    ovhip_rgb_lut **surf_luts;            /* [n_dev], or NULL: the colour tables of the surface output (ovhip_stream_set_surface_lut), owned */
-    ovhip_surface_conv surf_conv;         /* their conversion */
-    ovhip_rgb_lut **ladder_luts;          /* [n_dev], or NULL: the colour tables of the ladder output (ovhip_stream_set_ladder_lut), owned */
-    ovhip_surface_conv ladder_conv;       /* their conversion */
-    /* the RGB pyramid output (ovhip_stream_set_rgb_pyramid_output): every level its own slots; its colour tables
-     * (ovhip_stream_set_rgb_pyramid_lut): [n_dev], or NULL, owned */
-    int pyr_on; int32_t pyr_n;
-    ovhip_reduce_info pyr_info;
-    ovhip_rgb_level pyr[OVHIP_PYRAMID_MAX_LEVELS];
-    slot_buf pyr_buf[OVHIP_PYRAMID_MAX_LEVELS];
-    ovhip_rgb_lut **pyr_luts; int pyr_lut_size, pyr_lut_peak;
+    multi_out ladder, pyr;                /* the ladder output (ovhip_stream_set_ladder_output) and the RGB pyramid output (ovhip_stream_set_rgb_pyramid_output) */
+    stream_lut luts[N_TABS];              /* the colour tables (ovhip_stream_set_rgb_lut / _surface_lut / _ladder_lut / _rgb_pyramid_lut) */
     uint8_t *dg;                         /* OVHIP_OUT_DIGEST: the pictures' digests, computed by their frame threads (begun[idx] == 2: there) */
 };
 
@@ -261,15 +274,15 @@ decode_picture(struct run_state *rs, ovhip_frame *f, uint32_t idx, int job_locke
         /* (validated by the stream's setter; the conversion is this frame thread's, after its wait: nothing goes through the output thread) */
         if (s->rgb_on) (void)ovhip_frame_set_rgb_output(f, &s->rgb_fmt, &s->rgb_win, slot_of(&s->rgb_buf, idx), s->rgb_buf.bpp);
         if (s->surf_on) (void)ovhip_frame_set_surface_output(f, &s->surf_fmt, &s->surf_win, slot_of(&s->surf_buf, idx), s->surf_buf.bpp);
-        if (s->ladder_on) {
-            ovhip_ladder_rung rungs[OVHIP_LADDER_MAX_RUNGS];
-            for (int32_t k = 0; k < s->ladder_n; ++k) { rungs[k] = s->ladder[k]; rungs[k].dst = slot_of(&s->ladder_buf[k], idx); }
-            (void)ovhip_frame_set_ladder_output(f, &s->ladder_info, rungs, s->ladder_n);
+        if (s->ladder.on) {
+            ovhip_ladder_rung rungs[MULTI_MAX];
+            multi_point(&s->ladder, &RUNGS, idx, rungs);
+            (void)ovhip_frame_set_ladder_output(f, &s->ladder.info, rungs, s->ladder.n);
         }
-        if (s->pyr_on) {
-            ovhip_rgb_level levels[OVHIP_PYRAMID_MAX_LEVELS];
-            for (int32_t k = 0; k < s->pyr_n; ++k) { levels[k] = s->pyr[k]; levels[k].dst = slot_of(&s->pyr_buf[k], idx); }
-            (void)ovhip_frame_set_rgb_pyramid_output(f, &s->pyr_info, levels, s->pyr_n);
+        if (s->pyr.on) {
+            ovhip_rgb_level levels[MULTI_MAX];
+            multi_point(&s->pyr, &LEVELS, idx, levels);
+            (void)ovhip_frame_set_rgb_pyramid_output(f, &s->pyr.info, levels, s->pyr.n);
         }
         if (s->mvf_on) (void)ovhip_frame_set_mvfield_output(f, &s->mvf_fmt, slot_of(&s->mvf_vec, idx), s->mvf_vec.bpp, slot_of(&s->mvf_info, idx), s->mvf_info.bpp);
         const double t_sub = now_s();
@@ -447,6 +460,14 @@ comm_thread(void *argp)
 }
 
 /* ---------------------------------------------------------------- life cycle */
+/* one output's tables, one per device, and their array (NULL: none) */
+static void
+luts_free(const ovhip_stream *s, ovhip_rgb_lut **luts)
+{
+    for (int k = 0; luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
+    free(luts);
+}
+
 int
 ovhip_stream_create(ovhip_stream **out, ovhip_dpb *dpb, const ovhip_stream_cfg *cfg, const ovhip_stream_content *contents,
                     uint32_t n_contents, ovhip_job *const *jobs, uint32_t n_jobs)
@@ -505,14 +526,7 @@ ovhip_stream_destroy(ovhip_stream *s)
     for (int i = 0; s->frames && i < s->n_dev * s->tpd; ++i) ovhip_frame_destroy(s->frames[i]);
     for (int k = 0; s->out_ctx && k < s->n_dev; ++k) ovhip_ctx_destroy(s->out_ctx[k]);
     ovhip_host_free(s->out_host);
-    for (int k = 0; s->rgb_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->rgb_luts[k]);      /* (behind the frames that borrowed them) */
-    free(s->rgb_luts);
-    for (int k = 0; s->surf_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->surf_luts[k]);
-    free(s->surf_luts);
-    for (int k = 0; s->ladder_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->ladder_luts[k]);
-    free(s->ladder_luts);
-    for (int k = 0; s->pyr_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->pyr_luts[k]);
-    free(s->pyr_luts);
+    for (int t = 0; t < N_TABS; ++t) luts_free(s, s->luts[t].luts);                          /* (behind the frames that borrowed them) */
     free(s->ph);
     for (uint32_t i = 0; s->job_mtx && i < s->n_jobs; ++i) pthread_mutex_destroy(&s->job_mtx[i]);
     free(s->frames); free(s->out_ctx); free(s->job_mtx);
@@ -533,8 +547,9 @@ static int
 out_host_follows(ovhip_stream *s, const ovhip_post_ *post)
 {
     if (s->cfg.output != OVHIP_OUT_PACKED) return OVHIP_OK;
-    const int scaled = post->kind == OVHIP_POST_SCALE || post->kind == OVHIP_POST_REDUCE;
-    const size_t bytes = ovhip_output_bytes(scaled ? post->out_w : s->cfg.w, scaled ? post->out_h : s->cfg.h, &s->cfg.window);
+    int32_t w, h;
+    ovhip_post_size_(post, s->cfg.w, s->cfg.h, &w, &h);
+    const size_t bytes = ovhip_output_bytes(w, h, &s->cfg.window);
     if (!bytes) return OVHIP_EINVAL;
     if (bytes != s->out_host_bytes) {
         void *p = ovhip_host_alloc(bytes);
@@ -621,12 +636,7 @@ ovhip_stream_set_picture_hashes(ovhip_stream *s, int method, int n_planes, const
 }
 
 /* the size the stream outputs: its output scale's or reduced size, else its pictures' */
-static void
-out_size(const ovhip_stream *s, int32_t *w, int32_t *h)
-{
-    const int scaled = s->post.kind == OVHIP_POST_SCALE || s->post.kind == OVHIP_POST_REDUCE;
-    *w = scaled ? s->post.out_w : s->cfg.w; *h = scaled ? s->post.out_h : s->cfg.h;
-}
+static void out_size(const ovhip_stream *s, int32_t *w, int32_t *h) { ovhip_post_size_(&s->post, s->cfg.w, s->cfg.h, w, h); }
 
 /* what the setters below have in common once a format has passed its own checks: the buffer's pointer and slots, and the bytes a
  * picture is given against the bytes it needs (0: the format's size function refused the size or the window).  *b is written on success only */
@@ -653,129 +663,85 @@ ovhip_stream_set_rgb_output(ovhip_stream *s, const ovhip_rgb_format *fmt, const 
     return OVHIP_OK;
 }
 
-int
-ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table)
+/* output `which`'s setter of the frames */
+static int
+frame_set_lut(ovhip_frame *f, int which, const ovhip_rgb_lut *lut, const ovhip_surface_conv *conv)
 {
-    if (!s) return OVHIP_EINVAL;
-    ovhip_rgb_lut **luts = NULL;
-    int r = OVHIP_OK;
-    if (host_table) {
-        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
-        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
-        if (!luts) return OVHIP_ENOMEM;
-        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
-        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_rgb_lut(s->frames[i], luts[i / s->tpd]);
-        if (r != OVHIP_OK) {
-            /* the previous setting stands */
-            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_lut(s->frames[i], s->rgb_luts ? s->rgb_luts[i / s->tpd] : NULL);
-            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
-            free(luts);
-            return r;
-        }
-    } else
-        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_lut(s->frames[i], NULL);
-    for (int k = 0; s->rgb_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->rgb_luts[k]);
-    free(s->rgb_luts);
-    s->rgb_luts = luts;
+    switch (which) {
+    case TAB_RGB:     return ovhip_frame_set_rgb_lut(f, lut);
+    case TAB_SURFACE: return ovhip_frame_set_surface_lut(f, lut, conv);
+    case TAB_LADDER:  return ovhip_frame_set_ladder_lut(f, lut, conv);
+    default:          return ovhip_frame_set_rgb_pyramid_lut(f, lut);
+    }
+}
+
+/* What output `which` asks of a new table before anything is uploaded.  conv: NULL for an output without a conversion */
+static int
+lut_precheck(const ovhip_stream *s, int which, const ovhip_surface_conv *conv, int size, int peak)
+{
+    int32_t w, h;
+    int r;
+    out_size(s, &w, &h);
+    if ((which == TAB_SURFACE || which == TAB_LADDER) && (r = ovhip_surface_conv_check_(conv, NULL)) != OVHIP_OK) return r;
+    /* the ladder of the following runs, if set: its rungs through this table, the conversion reading its sample location */
+    if (which == TAB_LADDER && s->ladder.on) return ovhip_ladder_lut_check(w, h, &s->ladder.info, s->ladder.item.rungs, s->ladder.n, conv, size, peak, NULL);
+    /* the pyramid of the following runs, if set: its levels through this table.  Meant: the table's own refusals (ovhip_rgb_lut_check)
+     * are asked first and answered OVHIP_EINVAL, whatever the pyramid's check would say of the same table */
+    if (which == TAB_PYRAMID && s->pyr.on)
+        return ovhip_rgb_lut_check(size, peak, NULL) != OVHIP_OK ? OVHIP_EINVAL : ovhip_rgb_pyramid_check(w, h, &s->pyr.info, s->pyr.item.levels, s->pyr.n, size, peak, NULL);
     return OVHIP_OK;
 }
 
-int
-ovhip_stream_set_surface_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table)
+/* The one transaction behind the four table setters: a table per device, handed to every frame; a refusal leaves the previous setting
+ * standing; the tables replaced are released.  host_table NULL: off */
+static int
+stream_set_lut(ovhip_stream *s, int which, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table)
 {
     if (!s) return OVHIP_EINVAL;
+    stream_lut *t = &s->luts[which];
+    const int n_frames = s->n_dev * s->tpd;
     ovhip_rgb_lut **luts = NULL;
     int r = OVHIP_OK;
     if (host_table) {
-        if ((r = ovhip_surface_conv_check_(conv, NULL)) != OVHIP_OK) return r;    /* (before anything is uploaded) */
+        if ((r = lut_precheck(s, which, conv, size, peak)) != OVHIP_OK) return r;
         /* one table per device, through the context of the device's first frame; all of them before the setting changes */
         luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
         if (!luts) return OVHIP_ENOMEM;
         for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
-        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_surface_lut(s->frames[i], luts[i / s->tpd], conv);
+        for (int i = 0; i < n_frames && r == OVHIP_OK; ++i) r = frame_set_lut(s->frames[i], which, luts[i / s->tpd], conv);
         if (r != OVHIP_OK) {
             /* the previous setting stands */
-            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_surface_lut(s->frames[i], s->surf_luts ? s->surf_luts[i / s->tpd] : NULL, &s->surf_conv);
-            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
-            free(luts);
+            for (int i = 0; i < n_frames; ++i) (void)frame_set_lut(s->frames[i], which, t->luts ? t->luts[i / s->tpd] : NULL, &t->conv);
+            luts_free(s, luts);
             return r;
         }
-        s->surf_conv = *conv;
+        t->size = size; t->peak = peak;
+        if (conv) t->conv = *conv;
     } else
-        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_surface_lut(s->frames[i], NULL, NULL);
-    for (int k = 0; s->surf_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->surf_luts[k]);
-    free(s->surf_luts);
-    s->surf_luts = luts;
+        for (int i = 0; i < n_frames; ++i) (void)frame_set_lut(s->frames[i], which, NULL, NULL);
+    luts_free(s, t->luts);
+    t->luts = luts;
     return OVHIP_OK;
 }
 
-int
-ovhip_stream_set_ladder_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table)
-{
-    if (!s) return OVHIP_EINVAL;
-    ovhip_rgb_lut **luts = NULL;
-    int r = OVHIP_OK;
-    if (host_table) {
-        if ((r = ovhip_surface_conv_check_(conv, NULL)) != OVHIP_OK) return r;    /* (before anything is uploaded) */
-        /* the ladder of the following runs, if set: its rungs through this table, the conversion reading its sample location */
-        if (s->ladder_on) {
-            int32_t w, h;
-            out_size(s, &w, &h);
-            if ((r = ovhip_ladder_lut_check(w, h, &s->ladder_info, s->ladder, s->ladder_n, conv, size, peak, NULL)) != OVHIP_OK) return r;
-        }
-        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
-        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
-        if (!luts) return OVHIP_ENOMEM;
-        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
-        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_ladder_lut(s->frames[i], luts[i / s->tpd], conv);
-        if (r != OVHIP_OK) {
-            /* the previous setting stands */
-            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_ladder_lut(s->frames[i], s->ladder_luts ? s->ladder_luts[i / s->tpd] : NULL, &s->ladder_conv);
-            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
-            free(luts);
-            return r;
-        }
-        s->ladder_conv = *conv;
-    } else
-        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_ladder_lut(s->frames[i], NULL, NULL);
-    for (int k = 0; s->ladder_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->ladder_luts[k]);
-    free(s->ladder_luts);
-    s->ladder_luts = luts;
-    return OVHIP_OK;
-}
+int ovhip_stream_set_rgb_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table) { return stream_set_lut(s, TAB_RGB, NULL, size, peak, host_table); }
+int ovhip_stream_set_surface_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table) { return stream_set_lut(s, TAB_SURFACE, conv, size, peak, host_table); }
+int ovhip_stream_set_ladder_lut(ovhip_stream *s, const ovhip_surface_conv *conv, int size, int peak, const uint16_t *host_table) { return stream_set_lut(s, TAB_LADDER, conv, size, peak, host_table); }
+int ovhip_stream_set_rgb_pyramid_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table) { return stream_set_lut(s, TAB_PYRAMID, NULL, size, peak, host_table); }
 
-int
-ovhip_stream_set_rgb_pyramid_lut(ovhip_stream *s, int size, int peak, const uint16_t *host_table)
+/* What the ladder's and the pyramid's setter have in common once the items have passed their own check: every item's slots against
+ * the bytes it needs (need[k]), then the record.  *m is written on success only */
+static int
+multi_store(multi_out *m, const multi_items *t, const ovhip_reduce_info *ri, const void *items, int32_t n, uint32_t n_slots, const size_t *need)
 {
-    if (!s) return OVHIP_EINVAL;
-    ovhip_rgb_lut **luts = NULL;
-    int r = OVHIP_OK;
-    if (host_table) {
-        /* the pyramid of the following runs, if set: its levels through this table (before anything is uploaded) */
-        if (s->pyr_on) {
-            int32_t w, h;
-            out_size(s, &w, &h);
-            if (ovhip_rgb_lut_check(size, peak, NULL) != OVHIP_OK) return OVHIP_EINVAL;
-            if ((r = ovhip_rgb_pyramid_check(w, h, &s->pyr_info, s->pyr, s->pyr_n, size, peak, NULL)) != OVHIP_OK) return r;
-        }
-        /* one table per device, through the context of the device's first frame; all of them before the setting changes */
-        luts = (ovhip_rgb_lut **)calloc((size_t)s->n_dev, sizeof(*luts));
-        if (!luts) return OVHIP_ENOMEM;
-        for (int k = 0; k < s->n_dev && r == OVHIP_OK; ++k) r = ovhip_rgb_lut_create(ovhip_frame_ctx(s->frames[k * s->tpd]), size, peak, host_table, &luts[k]);
-        for (int i = 0; i < s->n_dev * s->tpd && r == OVHIP_OK; ++i) r = ovhip_frame_set_rgb_pyramid_lut(s->frames[i], luts[i / s->tpd]);
-        if (r != OVHIP_OK) {
-            /* the previous setting stands */
-            for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_pyramid_lut(s->frames[i], s->pyr_luts ? s->pyr_luts[i / s->tpd] : NULL);
-            for (int k = 0; k < s->n_dev; ++k) ovhip_rgb_lut_destroy(luts[k]);
-            free(luts);
-            return r;
-        }
-        s->pyr_lut_size = size; s->pyr_lut_peak = peak;
-    } else
-        for (int i = 0; i < s->n_dev * s->tpd; ++i) (void)ovhip_frame_set_rgb_pyramid_lut(s->frames[i], NULL);
-    for (int k = 0; s->pyr_luts && k < s->n_dev; ++k) ovhip_rgb_lut_destroy(s->pyr_luts[k]);
-    free(s->pyr_luts);
-    s->pyr_luts = luts;
+    slot_buf bufs[MULTI_MAX];
+    for (int32_t k = 0; k < n; ++k) {
+        const char *it = (const char *)items + (size_t)k * t->stride;
+        if (slot_buf_set(&bufs[k], *(void *const *)(it + t->off_dst), *(const size_t *)(it + t->off_bytes), n_slots, need[k]) != OVHIP_OK) return OVHIP_EINVAL;
+    }
+    m->on = 1; m->n = n; m->info = *ri;
+    memcpy(&m->item, items, (size_t)n * t->stride);
+    memcpy(m->buf, bufs, (size_t)n * sizeof(*bufs));
     return OVHIP_OK;
 }
 
@@ -783,26 +749,23 @@ int
 ovhip_stream_set_rgb_pyramid_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_rgb_level *levels, int32_t n, uint32_t n_slots)
 {
     if (!s) return OVHIP_EINVAL;
-    if (!levels) { s->pyr_on = 0; return OVHIP_OK; }
+    if (!levels) { s->pyr.on = 0; return OVHIP_OK; }
     int32_t w, h;
     ovhip_reduce_info ri;
     memset(&ri, 0, sizeof(ri));
     if (info) ri = *info;
     out_size(s, &w, &h);
-    const int r = ovhip_rgb_pyramid_check(w, h, &ri, levels, n, s->pyr_luts ? s->pyr_lut_size : 0, s->pyr_luts ? s->pyr_lut_peak : 0, NULL);
+    const stream_lut *t = &s->luts[TAB_PYRAMID];
+    const int r = ovhip_rgb_pyramid_check(w, h, &ri, levels, n, t->luts ? t->size : 0, t->luts ? t->peak : 0, NULL);
     if (r != OVHIP_OK) return r;
-    slot_buf bufs[OVHIP_PYRAMID_MAX_LEVELS];
+    size_t need[MULTI_MAX];
     for (int32_t k = 0; k < n; ++k) {
         const size_t es = levels[k].fmt.dtype == OVHIP_RGB_U8 ? 1 : (levels[k].fmt.dtype == OVHIP_RGB_F32 ? 4 : 2);
-        /* (every slot's base is aligned to the element as the first one is) */
+        /* meant, and the pyramid's alone: every slot's base is aligned to the element as the first one is */
         if (levels[k].dst_bytes % es) return OVHIP_EINVAL;
-        if (slot_buf_set(&bufs[k], levels[k].dst, levels[k].dst_bytes, n_slots, ovhip_rgb_bytes(levels[k].out_w, levels[k].out_h, NULL, &levels[k].fmt)) != OVHIP_OK)
-            return OVHIP_EINVAL;
+        need[k] = ovhip_rgb_bytes(levels[k].out_w, levels[k].out_h, NULL, &levels[k].fmt);
     }
-    s->pyr_on = 1; s->pyr_n = n; s->pyr_info = ri;
-    memcpy(s->pyr, levels, (size_t)n * sizeof(*levels));
-    memcpy(s->pyr_buf, bufs, (size_t)n * sizeof(*bufs));
-    return OVHIP_OK;
+    return multi_store(&s->pyr, &LEVELS, &ri, levels, n, n_slots, need);
 }
 
 int
@@ -823,24 +786,19 @@ int
 ovhip_stream_set_ladder_output(ovhip_stream *s, const ovhip_reduce_info *info, const ovhip_ladder_rung *rungs, int32_t n, uint32_t n_slots)
 {
     if (!s) return OVHIP_EINVAL;
-    if (!rungs) { s->ladder_on = 0; return OVHIP_OK; }
+    if (!rungs) { s->ladder.on = 0; return OVHIP_OK; }
     int32_t w, h;
     ovhip_reduce_info ri;
     memset(&ri, 0, sizeof(ri));
     if (info) ri = *info;
     out_size(s, &w, &h);
     /* with a table set, the table's share too: the location the conversion reads, rung sizes in multiples of 4 */
-    const int r = s->ladder_luts ? ovhip_ladder_lut_check(w, h, &ri, rungs, n, &s->ladder_conv, s->ladder_luts[0]->size, s->ladder_luts[0]->peak, NULL)
-                                 : ovhip_ladder_check(w, h, &ri, rungs, n, NULL);
+    const stream_lut *t = &s->luts[TAB_LADDER];
+    const int r = t->luts ? ovhip_ladder_lut_check(w, h, &ri, rungs, n, &t->conv, t->size, t->peak, NULL) : ovhip_ladder_check(w, h, &ri, rungs, n, NULL);
     if (r != OVHIP_OK) return r;
-    slot_buf bufs[OVHIP_LADDER_MAX_RUNGS];
-    for (int32_t k = 0; k < n; ++k)
-        if (slot_buf_set(&bufs[k], rungs[k].dst, rungs[k].dst_bytes, n_slots, ovhip_surface_bytes(rungs[k].out_w, rungs[k].out_h, NULL, &rungs[k].fmt)) != OVHIP_OK)
-            return OVHIP_EINVAL;
-    s->ladder_on = 1; s->ladder_n = n; s->ladder_info = ri;
-    memcpy(s->ladder, rungs, (size_t)n * sizeof(*rungs));
-    memcpy(s->ladder_buf, bufs, (size_t)n * sizeof(*bufs));
-    return OVHIP_OK;
+    size_t need[MULTI_MAX];
+    for (int32_t k = 0; k < n; ++k) need[k] = ovhip_surface_bytes(rungs[k].out_w, rungs[k].out_h, NULL, &rungs[k].fmt);
+    return multi_store(&s->ladder, &RUNGS, &ri, rungs, n, n_slots, need);
 }
 
 int

@@ -54,6 +54,28 @@ static inline void rd_shape(const ovhip_reduce_plan_ &pl, int *ntap, int *cpr, i
     *rows = RD_SLOTS / *cpr < 1 ? 1 : (RD_SLOTS / *cpr > RD_ROWS ? RD_ROWS : RD_SLOTS / *cpr);
 }
 
+// What the launchers of the one-launch outputs (k_output_ladder, k_ladder_lut, k_rgb_pyramid) fill alike in their argument structs, by the
+// members' names -- the structs themselves stay apart.  rd_src_fill: the source region of plan p0 (the same in every rung or level);
+// rd_level_fill: a rung's or a level's ratios, shape and size
+template <class Args> static inline void rd_src_fill(Args &a, const ovhip_pic *src, const ovhip_reduce_plan_ &p0)
+{
+    const uint16_t *sp[3] = { src->y, src->cb, src->cr };
+    for (int i = 0; i < 3; ++i) {
+        const int c = i != 0, stride = c ? src->stride_c : src->stride_y;
+        a.src[i] = sp[i] + (size_t)(p0.y0 >> c) * (size_t)stride + (size_t)(p0.x0 >> c);
+    }
+    a.sstride[0] = src->stride_y; a.sstride[1] = src->stride_c;
+    a.sw = p0.Ws; a.sh = p0.Hs;
+}
+template <class Level> static inline void rd_level_fill(Level &g, const ovhip_reduce_plan_ &rp)
+{
+    g.px = rp.px; g.qx = rp.qx; g.py = rp.py; g.qy = rp.qy;
+    g.n = rp.n; g.rcp = 1.0f / (float)rp.n;
+    rd_shape(rp, &g.ntap, &g.cpr, &g.rows);
+    g.sgx = rp.sgx; g.sgy = rp.sgy;
+    g.dw = rp.Wd; g.dh = rp.Hd;
+}
+
 // the first staged sample of a row whose segment begins at sample xs: back to the 16-byte boundary at or below its address
 __device__ __forceinline__ int stage_base(const uint16_t *row, int xs)
 {

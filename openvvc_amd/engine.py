@@ -256,6 +256,55 @@ def _set_output(owner, kind: str, fmt, dsts: list, window=None, n_slots: "int | 
     return r
 
 
+def _set_lut(owner, kind: str, lut_or_table, peak: int = 0, conv=None, check: bool = True) -> int:
+    """The one flow behind Frame.set_*_lut and Stream.set_*_lut (kind: "rgb", "surface", "ladder" or "rgb_pyramid"; the surface's and the
+    ladder's C setters take the conversion `conv`).  A frame takes an RgbLut and keeps it alive; a stream takes the table as a numpy
+    array with its peak and uploads it itself.  None: off."""
+    stream = isinstance(owner, Stream)
+    who = "stream" if stream else "frame"
+    fn, handle = getattr(owner.lib, f"ovhip_{who}_set_{kind}_lut"), owner.s if stream else owner.f
+    off = lut_or_table is None
+    cv = [C.byref(conv) if conv is not None and not (stream and off) else None] if kind in ("surface", "ladder") else []
+    if stream:
+        table, size = (None, 0) if off else _lut_table(lut_or_table, f"stream_set_{kind}_lut")
+        r = fn(handle, *cv, size, 0 if off else int(peak), None if off else table.ctypes.data)
+    else:
+        r = fn(handle, None if off else lut_or_table.h, *cv)
+    if check and r:
+        raise EngineError(f"{who}_set_{kind}_lut: {r}")
+    if r == 0 and not stream:
+        setattr(owner, f"_{kind.replace('rgb_pyramid', 'pyramid')}_lut", lut_or_table)
+    return r
+
+
+def _set_levels(owner, kind: str, items, info, n_slots: "int | None" = None, check: bool = True) -> int:
+    """The one flow behind set_ladder_output and set_rgb_pyramid_output of Frame and Stream (kind: "ladder" or "rgb_pyramid").  items:
+    the rungs or the levels, kept alive by the owner; info: their capi.ReduceInfo.  A stream's items carry the slots they were made with
+    (the same for all); with addresses n_slots counts.  None: off."""
+    stream = isinstance(owner, Stream)
+    who = "stream" if stream else "frame"
+    fn, handle = getattr(owner.lib, f"ovhip_{who}_set_{kind}_output"), owner.s if stream else owner.f
+    if items is None:
+        return fn(handle, None, None, 0, *([0] if stream else []))
+    items = list(items)
+    slots = []
+    if stream:
+        name, noun = ("ladder", "rungs") if kind == "ladder" else ("rgb pyramid", "levels")
+        counts = {g._slots for g in items if hasattr(g, "_slots")}
+        if len(counts) > 1 or (counts and n_slots is not None and counts != {n_slots}):
+            raise EngineError(f"{name} output: the {noun}' slots differ: {sorted(counts)}")
+        slots = [counts.pop() if counts else (n_slots or 0)]
+    arr, n = _rung_array(items) if kind == "ladder" else _level_array(items)
+    r = fn(handle, C.byref(info), arr, n, *slots)
+    if check and r:
+        raise EngineError(f"{who}_set_{kind}_output: {r}")
+    if r == 0 and stream:
+        owner._keep.append(items)                              # (as long as the stream)
+    elif r == 0:
+        setattr(owner, f"_{kind.replace('rgb_pyramid', 'pyramid')}_keep", items)      # (until the frame's next setting of this kind)
+    return r
+
+
 class Context:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load()
@@ -1326,34 +1375,19 @@ class Frame:
     def set_rgb_lut(self, lut: "RgbLut | None", check: bool = True) -> int:
         """ovhip_frame_set_rgb_lut: while set, every RGB output of this frame goes through the colour table (sticky, unlike the
         destination; kept alive here); None: off"""
-        r = self.lib.ovhip_frame_set_rgb_lut(self.f, lut.h if lut is not None else None)
-        if check and r:
-            raise EngineError(f"frame_set_rgb_lut: {r}")
-        if r == 0:
-            self._rgb_lut = lut
-        return r
+        return _set_lut(self, "rgb", lut, check=check)
 
     def set_surface_lut(self, lut: "RgbLut | None", conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_surface_lut: while set, every surface output of this frame is that of the picture converted by `conv`
         (surface_conv()) through the colour table (sticky, unlike the destination; kept alive here; independent of set_rgb_lut);
         None: off"""
-        r = self.lib.ovhip_frame_set_surface_lut(self.f, lut.h if lut is not None else None, C.byref(conv) if conv is not None else None)
-        if check and r:
-            raise EngineError(f"frame_set_surface_lut: {r}")
-        if r == 0:
-            self._surface_lut = lut
-        return r
+        return _set_lut(self, "surface", lut, conv=conv, check=check)
 
     def set_ladder_lut(self, lut: "RgbLut | None", conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_ladder_lut: while set, the rungs of this frame's ladder output are those of the reduced pictures converted
         by `conv` (surface_conv()) through the colour table (sticky, unlike the rungs; kept alive here; independent of set_rgb_lut
         and set_surface_lut); None: off"""
-        r = self.lib.ovhip_frame_set_ladder_lut(self.f, lut.h if lut is not None else None, C.byref(conv) if conv is not None else None)
-        if check and r:
-            raise EngineError(f"frame_set_ladder_lut: {r}")
-        if r == 0:
-            self._ladder_lut = lut
-        return r
+        return _set_lut(self, "ladder", lut, conv=conv, check=check)
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), nbytes: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_surface_output: the NEXT picture completed is also written as a surface into `dst` -- a contiguous torch
@@ -1364,39 +1398,18 @@ class Frame:
     def set_ladder_output(self, rungs, src_window=(0, 0, 0, 0), chroma_loc: int = 0, check: bool = True) -> int:
         """ovhip_frame_set_ladder_output: the NEXT picture completed is also written as the rungs of a ladder (ladder_rung() with torch
         tensors on the device, kept alive here, or device addresses); None: off"""
-        if rungs is None:
-            return self.lib.ovhip_frame_set_ladder_output(self.f, None, None, 0)
-        arr, n = _rung_array(rungs)
-        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
-        r = self.lib.ovhip_frame_set_ladder_output(self.f, C.byref(info), arr, n)
-        if check and r:
-            raise EngineError(f"frame_set_ladder_output: {r}")
-        if r == 0:
-            self._ladder_keep = list(rungs)
-        return r
+        return _set_levels(self, "ladder", rungs, capi.ReduceInfo(capi.Window(*src_window), chroma_loc), check=check)
 
     def set_rgb_pyramid_output(self, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, check: bool = True) -> int:
         """ovhip_frame_set_rgb_pyramid_output: the NEXT picture completed is also written as the levels of an RGB pyramid (rgb_level()
         with torch tensors on the device, kept alive here, or device addresses); None: off.  chroma_loc None: the first level's"""
-        if levels is None:
-            return self.lib.ovhip_frame_set_rgb_pyramid_output(self.f, None, None, 0)
-        arr, n = _level_array(levels)
-        r = self.lib.ovhip_frame_set_rgb_pyramid_output(self.f, C.byref(_pyramid_info(levels, src_window, chroma_loc)), arr, n)
-        if check and r:
-            raise EngineError(f"frame_set_rgb_pyramid_output: {r}")
-        if r == 0:
-            self._pyramid_keep = list(levels)
-        return r
+        levels = list(levels) if levels is not None else None
+        return _set_levels(self, "rgb_pyramid", levels, None if levels is None else _pyramid_info(levels, src_window, chroma_loc), check=check)
 
     def set_rgb_pyramid_lut(self, lut: "RgbLut | None", check: bool = True) -> int:
         """ovhip_frame_set_rgb_pyramid_lut: while set, the levels of this frame's RGB pyramid output go through the colour table (sticky,
         unlike the levels; kept alive here; independent of the other outputs' tables); None: off"""
-        r = self.lib.ovhip_frame_set_rgb_pyramid_lut(self.f, lut.h if lut is not None else None)
-        if check and r:
-            raise EngineError(f"frame_set_rgb_pyramid_lut: {r}")
-        if r == 0:
-            self._pyramid_lut = lut
-        return r
+        return _set_lut(self, "rgb_pyramid", lut, check=check)
 
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes: "int | None" = None, info_bytes: "int | None" = None,
                            check: bool = True) -> int:
@@ -1492,40 +1505,19 @@ class Stream:
     def set_rgb_lut(self, table: "np.ndarray | None", peak: int = 0, check: bool = True) -> int:
         """ovhip_stream_set_rgb_lut: the RGB output of the following runs goes through the colour table (numpy uint16 of shape
         (S, S, S, 3), uploaded once per device, owned by the stream); None: off"""
-        if table is None:
-            r = self.lib.ovhip_stream_set_rgb_lut(self.s, 0, 0, None)
-        else:
-            table, size = _lut_table(table, "stream_set_rgb_lut")
-            r = self.lib.ovhip_stream_set_rgb_lut(self.s, size, int(peak), table.ctypes.data)
-        if check and r:
-            raise EngineError(f"stream_set_rgb_lut: {r}")
-        return r
+        return _set_lut(self, "rgb", table, peak, check=check)
 
     def set_surface_lut(self, table: "np.ndarray | None", peak: int = 0, conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
         """ovhip_stream_set_surface_lut: the surface output of the following runs is that of the pictures converted by `conv`
         (surface_conv()) through the colour table (numpy uint16 of shape (S, S, S, 3), uploaded once per device, owned by the
         stream); None: off"""
-        if table is None:
-            r = self.lib.ovhip_stream_set_surface_lut(self.s, None, 0, 0, None)
-        else:
-            table, size = _lut_table(table, "stream_set_surface_lut")
-            r = self.lib.ovhip_stream_set_surface_lut(self.s, C.byref(conv) if conv is not None else None, size, int(peak), table.ctypes.data)
-        if check and r:
-            raise EngineError(f"stream_set_surface_lut: {r}")
-        return r
+        return _set_lut(self, "surface", table, peak, conv, check)
 
     def set_ladder_lut(self, table: "np.ndarray | None", peak: int = 0, conv: "capi.SurfaceConv | None" = None, check: bool = True) -> int:
         """ovhip_stream_set_ladder_lut: the ladder output of the following runs is that of the reduced pictures converted by `conv`
         (surface_conv()) through the colour table (numpy uint16 of shape (S, S, S, 3), uploaded once per device, owned by the
         stream); None: off"""
-        if table is None:
-            r = self.lib.ovhip_stream_set_ladder_lut(self.s, None, 0, 0, None)
-        else:
-            table, size = _lut_table(table, "stream_set_ladder_lut")
-            r = self.lib.ovhip_stream_set_ladder_lut(self.s, C.byref(conv) if conv is not None else None, size, int(peak), table.ctypes.data)
-        if check and r:
-            raise EngineError(f"stream_set_ladder_lut: {r}")
-        return r
+        return _set_lut(self, "ladder", table, peak, conv, check)
 
     def set_surface_output(self, dst, fmt: "capi.SurfaceFormat | None", window=(0, 0, 0, 0), bytes_per_picture: "int | None" = None,
                            n_slots: "int | None" = None, check: bool = True) -> int:
@@ -1540,52 +1532,20 @@ class Stream:
         idx % n of its own destination -- ladder_rung(..., slots=True) with a contiguous torch tensor on the device whose first
         dimension is the slot count (the same for every rung; kept alive here), or device addresses with the bytes per picture and
         n_slots; None: off"""
-        if rungs is None:
-            return self.lib.ovhip_stream_set_ladder_output(self.s, None, None, 0, 0)
-        rungs = list(rungs)
-        counts = {g._slots for g in rungs if hasattr(g, "_slots")}
-        if len(counts) > 1 or (counts and n_slots is not None and counts != {n_slots}):
-            raise EngineError(f"ladder output: the rungs' slots differ: {sorted(counts)}")
-        arr, n = _rung_array(rungs)
-        info = capi.ReduceInfo(capi.Window(*src_window), chroma_loc)
-        r = self.lib.ovhip_stream_set_ladder_output(self.s, C.byref(info), arr, n, counts.pop() if counts else (n_slots or 0))
-        if check and r:
-            raise EngineError(f"stream_set_ladder_output: {r}")
-        if r == 0:
-            self._keep.append(rungs)
-        return r
+        return _set_levels(self, "ladder", rungs, capi.ReduceInfo(capi.Window(*src_window), chroma_loc), n_slots, check)
 
     def set_rgb_pyramid_output(self, levels, src_window=(0, 0, 0, 0), chroma_loc: "int | None" = None, n_slots: "int | None" = None, check: bool = True) -> int:
         """ovhip_stream_set_rgb_pyramid_output: picture idx of the following runs is also written as the levels of an RGB pyramid, level r
         into slot idx % n of its own destination -- rgb_level(..., slots=True) with a contiguous torch tensor on the device whose first
         dimension is the slot count (the same for every level; kept alive here), or device addresses with the bytes per picture and
         n_slots; None: off.  chroma_loc None: the first level's"""
-        if levels is None:
-            return self.lib.ovhip_stream_set_rgb_pyramid_output(self.s, None, None, 0, 0)
-        levels = list(levels)
-        counts = {g._slots for g in levels if hasattr(g, "_slots")}
-        if len(counts) > 1 or (counts and n_slots is not None and counts != {n_slots}):
-            raise EngineError(f"rgb pyramid output: the levels' slots differ: {sorted(counts)}")
-        arr, n = _level_array(levels)
-        r = self.lib.ovhip_stream_set_rgb_pyramid_output(self.s, C.byref(_pyramid_info(levels, src_window, chroma_loc)), arr, n,
-                                                         counts.pop() if counts else (n_slots or 0))
-        if check and r:
-            raise EngineError(f"stream_set_rgb_pyramid_output: {r}")
-        if r == 0:
-            self._keep.append(levels)
-        return r
+        levels = list(levels) if levels is not None else None
+        return _set_levels(self, "rgb_pyramid", levels, None if levels is None else _pyramid_info(levels, src_window, chroma_loc), n_slots, check)
 
     def set_rgb_pyramid_lut(self, table: "np.ndarray | None", peak: int = 0, check: bool = True) -> int:
         """ovhip_stream_set_rgb_pyramid_lut: the RGB pyramid output of the following runs goes through the colour table (numpy uint16 of
         shape (S, S, S, 3), uploaded once per device, owned by the stream); None: off"""
-        if table is None:
-            r = self.lib.ovhip_stream_set_rgb_pyramid_lut(self.s, 0, 0, None)
-        else:
-            table, size = _lut_table(table, "stream_set_rgb_pyramid_lut")
-            r = self.lib.ovhip_stream_set_rgb_pyramid_lut(self.s, size, int(peak), table.ctypes.data)
-        if check and r:
-            raise EngineError(f"stream_set_rgb_pyramid_lut: {r}")
-        return r
+        return _set_lut(self, "rgb_pyramid", table, peak, check=check)
 
     def set_mvfield_output(self, fmt: "capi.MvfieldFormat | None", vec=None, info=None, vec_bytes_per_picture: "int | None" = None,
                            info_bytes_per_picture: "int | None" = None, n_slots: "int | None" = None, check: bool = True) -> int:
